@@ -98,6 +98,27 @@ def code_object_hash(lib_path):
         return None
     return None
 
+DUMP_BYTES = 64 << 20  # --dump-outputs: at most this much in all
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: saves each array as d/<name>.npy.  Were they larger than DUMP_BYTES together (no workload's film is: the
+    largest, living-room's, is 14.7 MB), each would be cut to a fixed, seeded sample of its pixels (rows of the [pixels, channels]
+    view) with the sampled pixel indices beside it as d/<name>_index.npy."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        if total > DUMP_BYTES - (1 << 20):      # (1 MB for the .npy headers)
+            rows = a.reshape(-1, a.shape[-1])
+            keep = max(1, int(rows.shape[0] * (DUMP_BYTES - (1 << 20)) / total / 3))      # (a third: the float64 indices ride along)
+            idx = np.sort(np.random.default_rng(0).choice(rows.shape[0], keep, replace=False))
+            np.save(os.path.join(d, name + "_index.npy"), idx.astype(np.float64))
+            a = rows[idx]
+        np.save(os.path.join(d, name + ".npy"), a)
+
+
 WORKLOADS = {
     # name: (description, how to build the model, spp, cpu sample spp, data label)
     "atrium": ("Sponza-class atrium STAND-IN (311,728 tris, matte+plastic, point light; the reference ships no Sponza geometry) 700x700, "
@@ -130,6 +151,9 @@ def parse_args():
                     help="profiling runs: ONE plain step of the headline workload and nothing else (no warm-up, counting passes, "
                          "secondary workloads or CPU baseline), so that a rocprofv3 summary of the process is the summary of a step")
     ap.add_argument("--dump-film", default="", help="rank 0 saves the merged film of the last headline step (numpy [H,W,4]); tests use it")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0 writes what the last timed headline step computed, as DIR/<name>.npy (float32), for comparing two builds "
+                         "output for output: film.npy = the merged film (xyz + filter weight sum per pixel, [H,W,4])")
     ap.add_argument("--rehearse-on-one-gpu", action="store_true",
                     help="all ranks share cuda:0 and the films are merged through gloo (RCCL refuses two ranks on one device): "
                          "the N>1 control flow on a 1-GPU box")
@@ -467,6 +491,8 @@ def main():
     elapsed, total_rays, total_samples, stats = timed(head, args.steps, args.warmup)
     if rank == 0 and args.dump_film:
         np.save(args.dump_film, head.film.cpu().numpy())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"film": head.film.cpu().numpy()})      # (every render clears the film: this is the last step's)
 
     def kernel_figures(w, stats):
         """rank 0: counting passes (untimed) + the roofline object of k_trace<closest> for workload w"""

@@ -15,6 +15,11 @@ OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "lib")
 HOST_SRCS = ["pbrt_frontend.cpp", "loop_subdiv.cpp", "scene_io.cpp", "texture_io.cpp", "bvh_builder.cpp", "wide_bvh.cpp", "halton_tables.cpp", "capi_host.cpp"]
 HIP_SRCS = ["device/kernels.hip", "capi_device.hip", "capi_gather.hip"]
+# hipcc names every HIP translation unit by a CUID (the __hip_cuid_* symbol in its code object) that it otherwise hashes from
+# the source's and the object's ABSOLUTE paths, so the code objects — and the sha256 profiles/rNN_counters.json is stamped
+# with — would depend on where the tree is checked out.  Pinned to the values the stamped build derived: the same code
+# objects, byte for byte, from any directory.
+CUIDS = {"device/kernels.hip": "a6cd736c50efffab", "capi_device.hip": "1b24418c11488d5c", "capi_gather.hip": "89501e8167866ce2"}
 COMMON = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-Wall", "-Wno-unused-function"]
 
 
@@ -54,12 +59,12 @@ def build(verbose=False, force=False):
     for s in HIP_SRCS:
         src = os.path.join(CSRC, s)
         obj = os.path.join(OBJ, s.replace("/", "_") + ".o")
-        cmd = [hipcc, "--offload-arch=gfx950"] + COMMON + ["-Wno-unused-result", "-c", src, "-o", obj]
+        cmd = [hipcc, "--offload-arch=gfx950"] + COMMON + ["-Wno-unused-result", "-cuid=" + CUIDS[s], "-c", src, "-o", obj]
         jobs.append((src, obj, cmd))
 
     def run(job):
         src, obj, cmd = job
-        if not force and not _newer([src] + headers, obj):
+        if not force and not _newer([src, os.path.abspath(__file__)] + headers, obj):   # (build.py: a changed flag rebuilds too)
             return None
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
