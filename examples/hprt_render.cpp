@@ -60,6 +60,24 @@ int main(int argc, char **argv) {
     // one scene per GPU; rank r renders tiles r, r + N, ...
     std::vector<HprtScene *> scenes((size_t)gpus, nullptr);
     for (int g = 0; g < gpus; ++g) TRY(hprt_scene_create_from_model(model, bvh, g, &scenes[(size_t)g]));
+    // Accelerator "kdtree" (MakeAccelerator, core/api.cpp:800-814): the kd-tree is built on the host and every scene walks it.
+    // A scene with object instances keeps its BVH (the library has no two-level kd walk: HPRT_E_UNSUPPORTED; the model's
+    // warnings already say so)
+    char accel[64] = "";
+    TRY(hprt_model_accelerator(model, accel, sizeof(accel)));
+    if (std::strcmp(accel, "kdtree") == 0) {
+        HprtKdTree *kd = nullptr;
+        const int rc = hprt_kdtree_build(model, &kd);
+        if (rc == HPRT_OK) {
+            int arc = HPRT_OK;
+            for (int g = 0; g < gpus && arc == HPRT_OK; ++g) arc = hprt_scene_attach_kdtree(scenes[(size_t)g], kd);
+            hprt_kdtree_destroy(kd);
+            if (arc != HPRT_OK) { std::fprintf(stderr, "hprt_scene_attach_kdtree failed (%d): %s\n", arc, hprt_last_error()); return 1; }
+        } else if (rc != HPRT_E_UNSUPPORTED) {
+            std::fprintf(stderr, "hprt_kdtree_build failed (%d): %s\n", rc, hprt_last_error());
+            return 1;
+        }
+    }
     // one host thread per GPU (the renders are independent; errors are thread-local in the library, so each thread keeps its own)
     std::vector<HprtRenderStats> stats((size_t)gpus);
     std::vector<int> rcs((size_t)gpus, HPRT_OK);

@@ -116,6 +116,34 @@ int hprt_bvh_object_info(const HprtBvh *b, uint32_t object, uint32_t info[4], fl
 int hprt_bvh_object_copy(const HprtBvh *b, uint32_t object, void *nodes32, uint32_t *prim_order);
 
 /* ------------------------------------------------------------------------ */
+/* kd-tree (Accelerator "kdtree").  Stands in for KdTreeAccel::KdTreeAccel +  */
+/* buildTree (accelerators/kdtreeaccel.cpp:163-380) and                       */
+/* CreateKdTreeAccelerator (:523-545).  Host side; the node array is          */
+/* byte-identical to the reference's KdAccelNode[] (8 bytes per node: split   */
+/* or onePrimitive or primitiveIndicesOffset, then flags | nPrims << 2 or     */
+/* axis | aboveChild << 2) and primitiveIndices; primitives are numbered in   */
+/* creation order.  splitalpha / alphatype / axisselectiontype /              */
+/* axisselectionamount only feed the reference's statistics and are ignored.  */
+/* ------------------------------------------------------------------------ */
+typedef struct HprtKdTree HprtKdTree;
+/* The scene's Accelerator name as written ("bvh", "kdtree", ...): cap bytes including the terminating 0.  Baked models
+ * report "bvh". */
+int hprt_model_accelerator(const HprtModel *m, char *name, size_t cap);
+/* Built with the parameters of the scene's Accelerator line (defaults intersectcost 80, traversalcost 1, emptybonus 0,
+ * maxprims 1, maxdepth -1 = round(2 + 1.6 Log2Int(N))).  Models with object instances: HPRT_E_UNSUPPORTED. */
+int hprt_kdtree_build(const HprtModel *m, HprtKdTree **out);
+/* The same from the primitives' world bounds (3 floats per primitive, creation order). */
+int hprt_kdtree_build_from_bounds(size_t n_prims, const float *bmin, const float *bmax, int isect_cost, int trav_cost,
+                                  float empty_bonus, int max_prims, int max_depth, HprtKdTree **out);
+/* info[0..3] = nodes, leaves, primitive references (primitiveIndices entries), depth (interior levels of the deepest
+ * path).  A tree deeper than HPRT_KD_MAX_DEPTH is refused by the builders with HPRT_E_UNSUPPORTED. */
+int hprt_kdtree_info(const HprtKdTree *t, uint32_t info[4]);
+#define HPRT_KD_MAX_DEPTH 64       /* the device walk's todo capacity: pbrt's maxTodo (kdtreeaccel.cpp:393) */
+/* nodes8: info[0] * 8 bytes; prim_indices: info[2] uint32 (either may be NULL) */
+int hprt_kdtree_copy(const HprtKdTree *t, void *nodes8, uint32_t *prim_indices);
+void hprt_kdtree_destroy(HprtKdTree *t);
+
+/* ------------------------------------------------------------------------ */
 /* Device scene.  Upload step that follows the BVH build: stands in for the  */
 /* `primitives`/`nodes` members BVHAccel keeps (accelerators/bvh.h:69-79) and */
 /* the Scene object (core/scene.h:50-80).  The library copies everything to   */
@@ -221,6 +249,16 @@ int hprt_scene_create(const HprtSceneDesc *desc, int device, HprtScene **out);
 /* Convenience: the same from a parsed model and its BVH. */
 int hprt_scene_create_from_model(const HprtModel *m, const HprtBvh *b, int device, HprtScene **out);
 void hprt_scene_destroy(HprtScene *s);
+/* Makes the scene walk a kd-tree (KdTreeAccel::Intersect / IntersectP, accelerators/kdtreeaccel.cpp:381-521) from now
+ * on: hprt_intersect*, hprt_occluded*, their _device forms and hprt_render.  The tree must be built over this scene's
+ * primitives (creation order, the numbering of the BVH's prim_order); it is validated (child offsets, leaf index ranges,
+ * primitive count, depth <= HPRT_KD_MAX_DEPTH: else HPRT_E_INVALID / HPRT_E_UNSUPPORTED) and copied to HBM.  Hits keep
+ * reporting ORDERED primitive indices (the BVH's numbering) so that shading is unchanged.  Scenes with object instances:
+ * HPRT_E_UNSUPPORTED (no two-level kd walk).  Attaching again replaces the tree.
+ * Counters of a kd scene: [0] nbNodeTraversals (every node the walk loop visits), [1] kdTreeNodeTraversals (interior
+ * nodes), [2] triangle tests, [3] sphere tests; HprtRenderStats::nodes_fetched[_p] / nodes_entered[_p] carry [0] / [1],
+ * and HPRT_RENDER_PIXEL_STATS slots 5 / 6 hold kdTreeNodeTraversals[P] (write them with hprt_write_pixel_stats_accel). */
+int hprt_scene_attach_kdtree(HprtScene *s, const HprtKdTree *t);
 
 /* ------------------------------------------------------------------------ */
 /* Batched Aggregate interface.  Stand in for                                */
@@ -328,6 +366,12 @@ int hprt_pixel_stats_read(HprtScene *s, uint64_t *out7, size_t n_pixels);
  * image per line, values separated by blanks) and the all-zero kd-tree / BSP matrices the fork
  * writes for a BVH render.  Its -renderTime.txt (wall-clock per pixel) has no counterpart here. */
 int hprt_write_pixel_stats(const char *prefix, const uint64_t *stats7, int width, int height);
+/* The same for a render of either accelerator: accel 0 (BVH) writes what hprt_write_pixel_stats writes; accel 1 (kd-tree)
+ * writes slots 5 / 6 to -kdTreeNodeTraversals.txt / -kdTreeNodeTraversalsP.txt, as the fork does for a kd render (the
+ * BSP matrices stay zero). */
+#define HPRT_ACCEL_BVH 0
+#define HPRT_ACCEL_KDTREE 1
+int hprt_write_pixel_stats_accel(const char *prefix, const uint64_t *stats7, int width, int height, int accel);
 /* Film::WriteImage arithmetic (core/film.cpp:266-303) on a host copy of a film
  * state: rgb_out = 3*W*H floats, top row first. */
 int hprt_film_resolve(const float *xyzw, size_t n_pixels, float film_scale, float *rgb_out);

@@ -5,6 +5,7 @@ accelerates:
 
     Model   <- pbrtParseFile / api.cpp state          (core/parser.cpp, core/api.cpp)
     Bvh     <- CreateBVHAccelerator / BVHAccel ctor   (accelerators/bvh.cpp:155-185,529-535)
+    KdTree  <- CreateKdTreeAccelerator / buildTree    (accelerators/kdtreeaccel.cpp:212-380,523-545)
     Scene   <- Scene + BVHAccel::Intersect/IntersectP (accelerators/bvh.cpp:354-437)
                and SamplerIntegrator::Render with PathIntegrator::Li
                (core/integrator.cpp:230-360, integrators/path.cpp:64-204)
@@ -34,6 +35,8 @@ RENDER_PIXEL_STATS = 2
 RENDER_COUNT_TRACED = 4
 RENDER_TRACE_ALL = 8
 RENDER_EXPORT_FOREIGN = 16
+ACCEL_BVH, ACCEL_KDTREE = 0, 1
+KD_MAX_DEPTH = 64        # HPRT_KD_MAX_DEPTH: the kd walk's todo capacity
 COMM_ID_BYTES = 128
 # HprtFilmRecord: one cross-tile film contribution (include/hprt.h)
 FILM_RECORD = np.dtype([("dest_pixel", np.uint32), ("src_tile", np.uint32), ("xyz", np.float32, 3), ("weight", np.float32)])
@@ -176,6 +179,14 @@ def _load():
         "hprt_scene_reserve": (C.c_int, [vp, P(RenderDesc)]),
         "hprt_film_records_read": (C.c_int, [vp, vp, sz, P(sz)]),
         "hprt_film_records_merge": (C.c_int, [vp, sz, vp, sz]),
+        "hprt_model_accelerator": (C.c_int, [vp, vp, sz]),
+        "hprt_kdtree_build": (C.c_int, [vp, P(vp)]),
+        "hprt_kdtree_build_from_bounds": (C.c_int, [sz, vp, vp, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, P(vp)]),
+        "hprt_kdtree_info": (C.c_int, [vp, P(u32)]),
+        "hprt_kdtree_copy": (C.c_int, [vp, vp, vp]),
+        "hprt_kdtree_destroy": (None, [vp]),
+        "hprt_scene_attach_kdtree": (C.c_int, [vp, vp]),
+        "hprt_write_pixel_stats_accel": (C.c_int, [cp, vp, C.c_int, C.c_int, C.c_int]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)   # raises AttributeError if an export is missing
@@ -254,6 +265,13 @@ class Model:
             levels.append(a)
         return {"levels": info[0], "trilinear": bool(info[1]), "wrap": info[2], "max_anisotropy": ma.value}, levels
 
+    @property
+    def accelerator(self):
+        """The scene's Accelerator name ("bvh", "kdtree", ...); baked models report "bvh"."""
+        buf = C.create_string_buffer(256)
+        _check(lib.hprt_model_accelerator(self._h, buf, 256))
+        return buf.value.decode()
+
     def warnings(self):
         w = lib.hprt_model_warnings(self._h).decode()
         return [x for x in w.split("\n") if x]
@@ -308,6 +326,42 @@ class Bvh:
             self._h = None
 
 
+class KdTree:
+    """kd-tree (host): CreateKdTreeAccelerator(prims, params) — KdAccelNode[] and primitiveIndices as the reference builds them."""
+
+    def __init__(self, model=None, handle=None):
+        if handle is None:
+            handle = C.c_void_p()
+            _check(lib.hprt_kdtree_build(model._h, C.byref(handle)))
+        self._h = handle
+
+    @staticmethod
+    def from_bounds(bmin, bmax, isect_cost=80, trav_cost=1, empty_bonus=0.0, max_prims=1, max_depth=-1):
+        bmin = np.ascontiguousarray(bmin, np.float32); bmax = np.ascontiguousarray(bmax, np.float32)
+        h = C.c_void_p()
+        _check(lib.hprt_kdtree_build_from_bounds(bmin.shape[0], _ptr(bmin), _ptr(bmax), isect_cost, trav_cost, C.c_float(empty_bonus),
+                                                 max_prims, max_depth, C.byref(h)))
+        return KdTree(handle=h)
+
+    def info(self):
+        i = (C.c_uint32 * 4)()
+        _check(lib.hprt_kdtree_info(self._h, i))
+        return {"nodes": i[0], "leaves": i[1], "prim_refs": i[2], "depth": i[3]}
+
+    def arrays(self):
+        """(nodes [n, 2] uint32: word 0 split / onePrimitive / primitiveIndicesOffset, word 1 flags; prim_indices uint32)"""
+        inf = self.info()
+        nodes = np.zeros((inf["nodes"], 2), np.uint32)
+        idx = np.zeros(inf["prim_refs"], np.uint32)
+        _check(lib.hprt_kdtree_copy(self._h, _ptr(nodes), _ptr(idx)))
+        return nodes, idx
+
+    def __del__(self):
+        if getattr(self, "_h", None) and lib is not None:      # (module globals are cleared at interpreter exit)
+            lib.hprt_kdtree_destroy(self._h)
+            self._h = None
+
+
 class Scene:
     """Device-resident scene: Aggregate (Intersect/IntersectP) + Integrator (Render)."""
 
@@ -327,6 +381,11 @@ class Scene:
         sc._h = h
         sc._model = None
         return sc
+
+    def attach_kdtree(self, kdtree):
+        """hprt_scene_attach_kdtree: every later trace and render walks `kdtree` (built over this scene's primitives)."""
+        _check(lib.hprt_scene_attach_kdtree(self._h, kdtree._h))
+        self._kdtree = kdtree
 
     def intersect(self, o, d, tmax, count=False):
         o = np.ascontiguousarray(o, np.float32); d = np.ascontiguousarray(d, np.float32)
@@ -491,6 +550,12 @@ def write_pixel_stats(prefix, stats7):
     """Film::WriteGeneralStats: the fork's per-pixel text matrices, '<prefix>-<counter>.txt'."""
     stats7 = np.ascontiguousarray(stats7, np.uint64)
     _check(lib.hprt_write_pixel_stats(prefix.encode(), _ptr(stats7), stats7.shape[1], stats7.shape[0]))
+
+
+def write_pixel_stats_accel(prefix, stats7, accel):
+    """The same for a render of either accelerator (ACCEL_BVH, ACCEL_KDTREE: slots 5 / 6 are kdTreeNodeTraversals[P])."""
+    stats7 = np.ascontiguousarray(stats7, np.uint64)
+    _check(lib.hprt_write_pixel_stats_accel(prefix.encode(), _ptr(stats7), stats7.shape[1], stats7.shape[0], accel))
 
 
 def write_pfm(path, rgb):

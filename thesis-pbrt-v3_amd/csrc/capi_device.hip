@@ -359,6 +359,7 @@ int hprt_scene_create(const HprtSceneDesc *d, int device, HprtScene **out) try {
 
     HprtScene *sc = new HprtScene();
     sc->device = dev; sc->nPrims = totalPrims;
+    sc->topOrder.assign(d->prim_order, d->prim_order + d->n_prims); sc->instanced = d->n_instances != 0;
     std::unique_ptr<HprtScene> guard(sc);
     // ---- flatten ----
     const uint32_t nVtx = (uint32_t)vtxBase[d->n_shapes];
@@ -793,8 +794,9 @@ int hprt_scene_create(const HprtSceneDesc *d, int device, HprtScene **out) try {
 } catch (...) { return hprt::HandleException(); }
 
 // Diagnostics hook (not part of include/hprt.h): the 128 sample points of a voxel, RadicalInverse(0..4, i) as [5][128]
-// Diagnostics hook (not part of include/hprt.h): 1 when plain renders of this scene take the leaf-exact wide walk (k_walk4), 0 for the binary walk
-__attribute__((visibility("default"))) int hprt_debug_scene_walk(HprtScene *s) { return s && hprt::WideWalkInUse(s->dev) ? 1 : 0; }
+// Diagnostics hook (not part of include/hprt.h): 1 when plain renders of this scene take the leaf-exact wide walk (k_walk4), else 0: the
+// binary walk, or the kd walk once a kd-tree is attached (callers test the value for truth: "is it k_walk4")
+__attribute__((visibility("default"))) int hprt_debug_scene_walk(HprtScene *s) { return s && !s->kdAttached && hprt::WideWalkInUse(s->dev) ? 1 : 0; }
 __attribute__((visibility("default"))) int hprt_debug_poison_workspace(HprtScene *s, int byte) { if (!s) return HPRT_E_INVALID; s->poisonByte = byte < 0 ? -1 : (byte & 255); return HPRT_OK; }
 // Diagnostics hook (not part of include/hprt.h): the first batch of the next hprt_render copies the rays that bounce `bounce` queues
 // (kind 0: the path segments entering bounce + 1, 1: its shadow rays, 2: its BSDF-sampled light rays) into d_out7 ([7][cap] planes:
@@ -805,9 +807,16 @@ __attribute__((visibility("default"))) int hprt_debug_capture_rays(HprtScene *s,
     return HPRT_OK;
 }
 static int ApiStreams(HprtScene *s, size_t n, RayStream *rays, HitStream *hits);
+// Every trace of a scene: the kd walk once a kd-tree is attached (hprt_scene_attach_kdtree), else the BVH walks (LaunchTrace)
+static void Trace(HprtScene *s, hipStream_t st, bool anyHit, bool count, const uint32_t *queue, const uint32_t *countPtr, uint32_t countImm,
+                  uint32_t gridItems, const RayStream &rays, const HitStream &hits, uint8_t *occ, DevCounters *counters, uint32_t *workCounter,
+                  uint4 *rayStats = nullptr) {
+    if (s->kdAttached) LaunchKdTrace(st, s->dev, s->kd, anyHit, count, queue, countPtr, countImm, gridItems, rays, hits, occ, counters, workCounter, rayStats);
+    else LaunchTrace(st, s->dev, anyHit, count, queue, countPtr, countImm, gridItems, rays, hits, occ, counters, workCounter, rayStats);
+}
 // Diagnostics (tools/sort_experiment.py): what consuming rays through a PERMUTED index queue costs.  The n rays of d_rays7 stay where
 // they are; d_queue lists them in the order to be traced.  ms[0]: a streaming pass that gathers the rays through the queue into
-// [7][n] planes at d_scratch7 (the physical permutation a sort would have to do), ms[1]: k_trace reading the rays through the queue.
+// [7][n] planes at d_scratch7 (the physical permutation a sort would have to do), ms[1]: the scene's walk reading the rays through the queue.
 __attribute__((visibility("default"))) int hprt_debug_trace_queued(HprtScene *s, size_t n, const float *d_rays7, const uint32_t *d_queue, int anyHit,
                                                                     float *d_scratch7, float ms[2]) try {
     if (!s || !d_rays7 || !d_queue || !d_scratch7 || !ms || n == 0 || n > 0x7ffffff0ull) return SetError(HPRT_E_INVALID, "hprt_debug_trace_queued: bad argument");
@@ -823,7 +832,7 @@ __attribute__((visibility("default"))) int hprt_debug_trace_queued(HprtScene *s,
     LaunchCaptureRays(nullptr, d_queue, (uint32_t)n, rays, d_scratch7, (uint32_t)n);
     HIP_TRY(hipEventRecord(e[1], nullptr));
     HitStream none; none.a = nullptr; none.b = nullptr;
-    LaunchTrace(nullptr, s->dev, anyHit != 0, false, d_queue, nullptr, (uint32_t)n, (uint32_t)n, rays, anyHit ? none : hits, anyHit ? occ.as<uint8_t>() : nullptr, nullptr, s->workCounter.as<uint32_t>());
+    Trace(s, nullptr, anyHit != 0, false, d_queue, nullptr, (uint32_t)n, (uint32_t)n, rays, anyHit ? none : hits, anyHit ? occ.as<uint8_t>() : nullptr, nullptr, s->workCounter.as<uint32_t>());
     HIP_TRY(hipEventRecord(e[2], nullptr));
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipEventElapsedTime(&ms[0], e[0], e[1])); HIP_TRY(hipEventElapsedTime(&ms[1], e[1], e[2]));
@@ -1015,6 +1024,44 @@ int hprt_scene_create_from_model(const HprtModel *m, const HprtBvh *b, int devic
     return hprt_scene_create(&d, device, out);
 } catch (...) { return hprt::HandleException(); }
 
+// MakeAccelerator("kdtree") (core/api.cpp:790-830): the tree is checked, its creation-order primitive numbers are mapped to the
+// scene's ordered indices (the inverse of prim_order), and from now on every trace of the scene walks it (Trace above)
+int hprt_scene_attach_kdtree(HprtScene *s, const HprtKdTree *t) try {
+    if (!s || !t) return SetError(HPRT_E_INVALID, "hprt_scene_attach_kdtree: null argument");
+    if (s->instanced) return SetError(HPRT_E_UNSUPPORTED, "kd-trees over object instances are not supported: the scene keeps its BVH");
+    const KdTree &kt = t->tree;
+    const uint32_t nTop = (uint32_t)s->topOrder.size();
+    if (kt.nPrims != nTop)
+        return SetError(HPRT_E_INVALID, "the kd-tree holds " + std::to_string(kt.nPrims) + " primitives, the scene " + std::to_string(nTop));
+    uint32_t depth = 0;
+    const char *bad = CheckKdTree(kt, &depth);
+    if (*bad) return SetError(HPRT_E_INVALID, std::string("malformed kd-tree: ") + bad);
+    if (depth > KD_TODO_MAX)
+        return SetError(HPRT_E_UNSUPPORTED, "kd-tree of depth " + std::to_string(depth) + " is deeper than the walk's todo list (" + std::to_string((unsigned)KD_TODO_MAX) + ")");
+    std::vector<uint32_t> toOrdered(nTop);
+    for (uint32_t i = 0; i < nTop; ++i) toOrdered[s->topOrder[i]] = i;
+    std::vector<uint2> nodes(kt.nodes.size());
+    for (size_t k = 0; k < nodes.size(); ++k) {
+        const KdNode &nd = kt.nodes[k];
+        const bool onePrim = (nd.b & 3u) == 3u && (nd.b >> 2) == 1u;
+        nodes[k] = make_uint2(onePrim ? toOrdered[nd.a] : nd.a, nd.b);
+    }
+    std::vector<uint32_t> prims(kt.primIndices.size());
+    for (size_t k = 0; k < prims.size(); ++k) prims[k] = toOrdered[kt.primIndices[k]];
+    HIP_TRY(hipSetDevice(s->device));
+    SceneCall call(s, nullptr);
+    HIP_TRY(hipDeviceSynchronize());      // a render or trace of the old tree may still be running
+    HIP_TRY(upload(s->kdNodes, nodes));
+    HIP_TRY(upload(s->kdPrims, prims));
+    DevKd &kd = s->kd;
+    kd.nodes = s->kdNodes.as<uint2>(); kd.nNodes = (uint32_t)nodes.size();
+    kd.primIdx = s->kdPrims.as<uint32_t>(); kd.nPrimIdx = (uint32_t)prims.size();
+    for (int a = 0; a < 3; ++a) { kd.lo[a] = kt.bounds[a]; kd.hi[a] = kt.bounds[3 + a]; }
+    kd.depth = depth;
+    s->kdAttached = true;
+    return HPRT_OK;
+} catch (...) { return hprt::HandleException(); }
+
 void hprt_scene_destroy(HprtScene *s) {
     if (!s) return;
     (void)hipSetDevice(s->device);
@@ -1050,7 +1097,7 @@ int hprt_intersect_device(HprtScene *s, size_t n, const float *d_rays7, float *d
     int rc = ApiStreams(s, n, &rays, &hits);
     if (rc != HPRT_OK) return rc;
     LaunchPackRays(st, d_rays7, (uint32_t)n, rays);
-    LaunchTrace(st, s->dev, false, false, nullptr, nullptr, (uint32_t)n, (uint32_t)n, rays, hits, nullptr, nullptr, s->workCounter.as<uint32_t>());
+    Trace(s, st, false, false, nullptr, nullptr, (uint32_t)n, (uint32_t)n, rays, hits, nullptr, nullptr, s->workCounter.as<uint32_t>());
     LaunchUnpackHits(st, hits, (uint32_t)n, d_t, d_prim, d_bary3);
     call.leave_async();
     HIP_TRY(hipGetLastError());
@@ -1068,7 +1115,7 @@ int hprt_occluded_device(HprtScene *s, size_t n, const float *d_rays7, uint8_t *
     if (rc != HPRT_OK) return rc;
     LaunchPackRays(st, d_rays7, (uint32_t)n, rays);
     HitStream none; none.a = nullptr; none.b = nullptr;
-    LaunchTrace(st, s->dev, true, false, nullptr, nullptr, (uint32_t)n, (uint32_t)n, rays, none, d_occ, nullptr, s->workCounter.as<uint32_t>());
+    Trace(s, st, true, false, nullptr, nullptr, (uint32_t)n, (uint32_t)n, rays, none, d_occ, nullptr, s->workCounter.as<uint32_t>());
     call.leave_async();
     HIP_TRY(hipGetLastError());
     return HPRT_OK;
@@ -1094,7 +1141,7 @@ static int TraceHost(HprtScene *s, bool anyHit, size_t n, const float *o, const 
     HIP_TRY(hipMemset(s->counters.p, 0, sizeof(DevCounters)));
     const bool count = counters != nullptr;
     if (!anyHit) {
-        LaunchTrace(nullptr, s->dev, false, count, nullptr, nullptr, (uint32_t)n, (uint32_t)n, rays, hits, nullptr, s->counters.as<DevCounters>(), s->workCounter.as<uint32_t>());
+        Trace(s, nullptr, false, count, nullptr, nullptr, (uint32_t)n, (uint32_t)n, rays, hits, nullptr, s->counters.as<DevCounters>(), s->workCounter.as<uint32_t>());
         HIP_TRY(hipGetLastError()); HIP_TRY(hipDeviceSynchronize());
         std::vector<float4> ha(n); std::vector<float2> hb(n);
         HIP_TRY(hipMemcpy(ha.data(), hits.a, 16 * n, hipMemcpyDeviceToHost));
@@ -1109,7 +1156,7 @@ static int TraceHost(HprtScene *s, bool anyHit, size_t n, const float *o, const 
         DevBuf outOcc;
         HIP_TRY(outOcc.alloc(n));
         HitStream none; none.a = nullptr; none.b = nullptr;
-        LaunchTrace(nullptr, s->dev, true, count, nullptr, nullptr, (uint32_t)n, (uint32_t)n, rays, none, outOcc.as<uint8_t>(), s->counters.as<DevCounters>(), s->workCounter.as<uint32_t>());
+        Trace(s, nullptr, true, count, nullptr, nullptr, (uint32_t)n, (uint32_t)n, rays, none, outOcc.as<uint8_t>(), s->counters.as<DevCounters>(), s->workCounter.as<uint32_t>());
         HIP_TRY(hipGetLastError()); HIP_TRY(hipDeviceSynchronize());
         if (occ_out) HIP_TRY(hipMemcpy(occ_out, outOcc.p, n, hipMemcpyDeviceToHost));
     }
@@ -1159,7 +1206,7 @@ int RunBatch(HprtScene *s, hipStream_t st, const RenderParams &rp, const Workspa
         const PathStream &in = w.path[bounce & 1];
         hipEvent_t e0 = ev.get(), e1 = ev.get();
         HIP_TRY(hipEventRecord(e0, st));
-        LaunchTrace(st, s->dev, false, count, activeQ, nullptr, active, active, in.ray, w.hit, nullptr, ctr, wcPath, rayStats);
+        Trace(s, st, false, count, activeQ, nullptr, active, active, in.ray, w.hit, nullptr, ctr, wcPath, rayStats);
         if (pixelStats) LaunchPixelStats(st, rayStats, bounce == 0 ? nullptr : in.beta, activeQ, nullptr, active, active, rp.nPix, false, pixelStats);
         HIP_TRY(hipEventRecord(e1, st));
         evExt.push_back({e0, e1}); bt->extendRays += active; ++bt->extendLaunches;
@@ -1214,7 +1261,7 @@ int RunBatch(HprtScene *s, hipStream_t st, const RenderParams &rp, const Workspa
             hipEvent_t a = ev.get(), b = ev.get();
             HIP_TRY(hipEventRecord(a, st));
             HitStream none; none.a = nullptr; none.b = nullptr;
-            LaunchTrace(st, s->dev, true, count, cur.shadow, nullptr, nShadow, nShadow, w.vs.shadow, none, w.vs.occluded, ctr, wcPath, rayStats);
+            Trace(s, st, true, count, cur.shadow, nullptr, nShadow, nShadow, w.vs.shadow, none, w.vs.occluded, ctr, wcPath, rayStats);
             if (pixelStats) LaunchPixelStats(st, rayStats, w.vs.pendBeta, cur.shadow, nullptr, nShadow, nShadow, rp.nPix, true, pixelStats);
             HIP_TRY(hipEventRecord(b, st));
             evOcc.push_back({a, b}); bt->occludedRays += nShadow; ++bt->occludedLaunches;
@@ -1223,7 +1270,7 @@ int RunBatch(HprtScene *s, hipStream_t st, const RenderParams &rp, const Workspa
         if (nMis) {
             hipEvent_t a = ev.get(), b = ev.get();
             HIP_TRY(hipEventRecord(a, st));
-            LaunchTrace(st, s->dev, false, count, cur.mis, nullptr, nMis, nMis, w.vs.mis, w.vs.misHit, nullptr, ctr, wcPath, rayStats);
+            Trace(s, st, false, count, cur.mis, nullptr, nMis, nMis, w.vs.mis, w.vs.misHit, nullptr, ctr, wcPath, rayStats);
             if (pixelStats) LaunchPixelStats(st, rayStats, w.vs.pendBeta, cur.mis, nullptr, nMis, nMis, rp.nPix, false, pixelStats);
             HIP_TRY(hipEventRecord(b, st));
             evExt.push_back({a, b}); bt->extendRays += nMis; ++bt->extendLaunches;

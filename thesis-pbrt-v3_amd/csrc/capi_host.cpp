@@ -47,7 +47,10 @@ int hprt_model_parse(const char *pbrt_path, const char *const *subst, int n_subs
     HprtModel *m = new HprtModel();
     std::string err;
     if (!ParsePbrtFile(pbrt_path, sm, &m->sc, &err)) { delete m; return SetError(HPRT_E_PARSE, err); }
-    if (m->sc.opt.accelerator != "bvh") m->sc.warnings.push_back("Accelerator \"" + m->sc.opt.accelerator + "\" is outside the hot-path scope; \"bvh\" used");
+    // a kd-tree over object instances is not built (hprt_kdtree_build: HPRT_E_UNSUPPORTED): such a scene keeps the BVH and the warning
+    if (m->sc.opt.accelerator == "kdtree" && m->sc.nObjects == 0 && m->sc.instances.empty())
+        m->sc.warnings.push_back("Accelerator \"kdtree\": the host builds the tree (hprt_kdtree_build) and attaches it to the scene (hprt_scene_attach_kdtree); a scene without it walks a BVH");
+    else if (m->sc.opt.accelerator != "bvh") m->sc.warnings.push_back("Accelerator \"" + m->sc.opt.accelerator + "\" is outside the hot-path scope; \"bvh\" used");
     if (m->sc.opt.integrator != "path") m->sc.warnings.push_back("Integrator \"" + m->sc.opt.integrator + "\" is outside the hot-path scope; \"path\" used");
     if (m->sc.opt.sampler != "halton") m->sc.warnings.push_back("Sampler \"" + m->sc.opt.sampler + "\" is outside the hot-path scope; \"halton\" used");
     *out = m;
@@ -160,6 +163,59 @@ int hprt_bvh_build_from_bounds(size_t n, const float *bmin, const float *bmax, i
     return HPRT_OK;
 } catch (...) { return hprt::HandleException(); }
 void hprt_bvh_destroy(HprtBvh *b) { delete b; }
+
+// ---- kd-tree (Accelerator "kdtree") ----
+static int FinishKdTree(HprtKdTree *t, HprtKdTree **out) {
+    if (t->tree.depth > KD_TODO_MAX) {
+        const std::string msg = "kd-tree of depth " + std::to_string(t->tree.depth) + " is deeper than the device walk's todo list (" +
+                                std::to_string((unsigned)KD_TODO_MAX) + " entries); lower \"maxdepth\"";
+        delete t;
+        return SetError(HPRT_E_UNSUPPORTED, msg);
+    }
+    *out = t;
+    return HPRT_OK;
+}
+int hprt_model_accelerator(const HprtModel *m, char *name, size_t cap) try {
+    if (!m || !name || cap == 0) return SetError(HPRT_E_INVALID, "hprt_model_accelerator: bad argument");
+    const std::string &a = m->sc.opt.accelerator;
+    if (a.size() + 1 > cap) return SetError(HPRT_E_INVALID, "hprt_model_accelerator: buffer too small");
+    memcpy(name, a.c_str(), a.size() + 1);
+    return HPRT_OK;
+} catch (...) { return hprt::HandleException(); }
+int hprt_kdtree_build(const HprtModel *m, HprtKdTree **out) try {
+    if (!m || !out) return SetError(HPRT_E_INVALID, "hprt_kdtree_build: null argument");
+    if (m->sc.nObjects != 0 || !m->sc.instances.empty()) return SetError(HPRT_E_UNSUPPORTED, "kd-trees over object instances are not supported (the scene keeps its BVH)");
+    std::vector<float> lo, hi;
+    ComputePrimBounds(m->sc, {}, &lo, &hi);
+    const RenderOptions &o = m->sc.opt;
+    KdParams p;
+    p.isectCost = o.kdIsectCost; p.travCost = o.kdTravCost; p.emptyBonus = o.kdEmptyBonus; p.maxPrims = o.kdMaxPrims; p.maxDepth = o.kdMaxDepth;
+    HprtKdTree *t = new HprtKdTree();
+    BuildKdTree(lo.size() / 3, lo.data(), hi.data(), p, &t->tree);
+    return FinishKdTree(t, out);
+} catch (...) { return hprt::HandleException(); }
+int hprt_kdtree_build_from_bounds(size_t n, const float *bmin, const float *bmax, int isectCost, int travCost, float emptyBonus,
+                                  int maxPrims, int maxDepth, HprtKdTree **out) try {
+    if (!out || (n && (!bmin || !bmax))) return SetError(HPRT_E_INVALID, "hprt_kdtree_build_from_bounds: null argument");
+    if (n > 0x3fffffffull) return SetError(HPRT_E_UNSUPPORTED, "more than 2^30 primitives");
+    KdParams p;
+    p.isectCost = isectCost; p.travCost = travCost; p.emptyBonus = emptyBonus; p.maxPrims = maxPrims; p.maxDepth = maxDepth;
+    HprtKdTree *t = new HprtKdTree();
+    BuildKdTree(n, bmin, bmax, p, &t->tree);
+    return FinishKdTree(t, out);
+} catch (...) { return hprt::HandleException(); }
+int hprt_kdtree_info(const HprtKdTree *t, uint32_t info[4]) try {
+    if (!t || !info) return SetError(HPRT_E_INVALID, "hprt_kdtree_info: null argument");
+    info[0] = (uint32_t)t->tree.nodes.size(); info[1] = t->tree.leaves; info[2] = (uint32_t)t->tree.primIndices.size(); info[3] = t->tree.depth;
+    return HPRT_OK;
+} catch (...) { return hprt::HandleException(); }
+int hprt_kdtree_copy(const HprtKdTree *t, void *nodes8, uint32_t *primIndices) try {
+    if (!t) return SetError(HPRT_E_INVALID, "hprt_kdtree_copy: null argument");
+    if (nodes8) memcpy(nodes8, t->tree.nodes.data(), t->tree.nodes.size() * sizeof(KdNode));
+    if (primIndices && !t->tree.primIndices.empty()) memcpy(primIndices, t->tree.primIndices.data(), t->tree.primIndices.size() * 4);
+    return HPRT_OK;
+} catch (...) { return hprt::HandleException(); }
+void hprt_kdtree_destroy(HprtKdTree *t) { delete t; }
 int hprt_bvh_info(const HprtBvh *b, uint32_t info[4], float bounds6[6]) try {
     if (!b || !info) return SetError(HPRT_E_INVALID, "hprt_bvh_info: null argument");
     info[0] = (uint32_t)b->tree.nodes.size(); info[1] = (uint32_t)b->tree.primOrder.size();
@@ -225,10 +281,16 @@ int hprt_film_resolve(const float *xyzw, size_t n, float scale, float *rgb) try 
 
 // Film::WriteGeneralStatMatrix, core/film.cpp:189-210: "<file minus extension>-<name>.txt", one image row per line
 int hprt_write_pixel_stats(const char *prefix, const uint64_t *stats7, int width, int height) try {
+    return hprt_write_pixel_stats_accel(prefix, stats7, width, height, HPRT_ACCEL_BVH);
+} catch (...) { return hprt::HandleException(); }
+int hprt_write_pixel_stats_accel(const char *prefix, const uint64_t *stats7, int width, int height, int accel) try {
     if (!prefix || !stats7 || width <= 0 || height <= 0) return SetError(HPRT_E_INVALID, "hprt_write_pixel_stats: bad argument");
-    // the matrices Film::WriteGeneralStats writes (core/film.cpp:170-187), with the index of the value in stats7 (-1: zero for a BVH render)
-    static const struct { const char *name; int field; } kMatrices[] = {
-        {"primitiveIntersections", 1}, {"primitiveIntersectionsP", 2}, {"kdTreeNodeTraversals", -1}, {"kdTreeNodeTraversalsP", -1},
+    if (accel != HPRT_ACCEL_BVH && accel != HPRT_ACCEL_KDTREE) return SetError(HPRT_E_INVALID, "hprt_write_pixel_stats_accel: unknown accelerator");
+    // the matrices Film::WriteGeneralStats writes (core/film.cpp:170-187), with the index of the value in stats7 (-1: zero for this
+    // accelerator): a kd render's interior-node counts (slots 5, 6) are its kdTreeNodeTraversals[P]
+    const int kd = accel == HPRT_ACCEL_KDTREE ? 5 : -1, kdP = accel == HPRT_ACCEL_KDTREE ? 6 : -1;
+    const struct { const char *name; int field; } kMatrices[] = {
+        {"primitiveIntersections", 1}, {"primitiveIntersectionsP", 2}, {"kdTreeNodeTraversals", kd}, {"kdTreeNodeTraversalsP", kdP},
         {"bspTreeNodeTraversals", -1}, {"bspTreeNodeTraversalsP", -1}, {"leafNodeTraversals", 3}, {"leafNodeTraversalsP", 4}};
     for (const auto &m : kMatrices) {
         const std::string path = std::string(prefix) + "-" + m.name + ".txt";

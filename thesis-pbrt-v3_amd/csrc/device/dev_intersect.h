@@ -248,6 +248,21 @@ static_assert(HPRT_WIDE_STACK_MAX - HPRT_WIDE_LDS_CLOSEST <= HPRT_SPILL_STACK &&
 
 struct TraceCount { unsigned int fetched, entered, tri, sphere, leaf; };   // leaf: of the entered nodes, leaves
 
+// per-wave reduction of a traversal kernel's counters, then one atomic per counter per wave (k_trace, k_walk4, k_kdwalk)
+__device__ __forceinline__ void wave_count_add(DevCounters *c, bool anyHit, const TraceCount &t) {
+    // per-wave reduction, then one atomic per counter per wave
+    unsigned int f = t.fetched, e = t.entered, tr = t.tri, sp = t.sphere;
+    for (int off = 32; off > 0; off >>= 1) {
+        f += __shfl_down(f, off); e += __shfl_down(e, off); tr += __shfl_down(tr, off); sp += __shfl_down(sp, off);
+    }
+    if (__lane_id() == 0) {
+        if (!anyHit) { atomicAdd(&c->nodesFetched, (unsigned long long)f); atomicAdd(&c->nodesEntered, (unsigned long long)e);
+                       atomicAdd(&c->triTests, (unsigned long long)tr); atomicAdd(&c->sphereTests, (unsigned long long)sp); }
+        else { atomicAdd(&c->nodesFetchedP, (unsigned long long)f); atomicAdd(&c->nodesEnteredP, (unsigned long long)e);
+               atomicAdd(&c->triTestsP, (unsigned long long)tr); atomicAdd(&c->sphereTestsP, (unsigned long long)sp); }
+    }
+}
+
 // `cur` of a lane: >= 0 interior pair, REF_NONE finished, REF_EXIT leaving an instance, otherwise ~(parked primitive index)
 __device__ __forceinline__ bool is_parked(int cur) { return (uint32_t)cur > (uint32_t)REF_EXIT; }
 // with object instances: parked primitives and the REF_EXIT sentinel are both handled by the primitive phase

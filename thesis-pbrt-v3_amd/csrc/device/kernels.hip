@@ -93,20 +93,6 @@ __device__ __forceinline__ void block_append(BlockAppendLds *lds, uint32_t *cons
                  __builtin_amdgcn_mbcnt_hi((uint32_t)(mask[k] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask[k], 0u));
 }
 
-__device__ __forceinline__ void wave_count_add(DevCounters *c, bool anyHit, const TraceCount &t) {
-    // per-wave reduction, then one atomic per counter per wave
-    unsigned int f = t.fetched, e = t.entered, tr = t.tri, sp = t.sphere;
-    for (int off = 32; off > 0; off >>= 1) {
-        f += __shfl_down(f, off); e += __shfl_down(e, off); tr += __shfl_down(tr, off); sp += __shfl_down(sp, off);
-    }
-    if (__lane_id() == 0) {
-        if (!anyHit) { atomicAdd(&c->nodesFetched, (unsigned long long)f); atomicAdd(&c->nodesEntered, (unsigned long long)e);
-                       atomicAdd(&c->triTests, (unsigned long long)tr); atomicAdd(&c->sphereTests, (unsigned long long)sp); }
-        else { atomicAdd(&c->nodesFetchedP, (unsigned long long)f); atomicAdd(&c->nodesEnteredP, (unsigned long long)e);
-               atomicAdd(&c->triTestsP, (unsigned long long)tr); atomicAdd(&c->sphereTestsP, (unsigned long long)sp); }
-    }
-}
-
 // ---------------------------------------------------------------------------
 // k_trace: persistent wavefronts with dynamic ray fetch over the child-pair layout.
 //

@@ -8,6 +8,7 @@
 #include <vector>
 #include "../../include/hprt.h"
 #include "device/kernels.h"
+#include "device/kd_walk.h"
 #include "hprt_internal.h"
 
 #define HIP_TRY(expr)                                                                                   \
@@ -85,6 +86,10 @@ struct HprtScene {
     uint32_t *hostCounts = nullptr;                   // pinned
     size_t filmPixels = 0;
     uint32_t nPrims = 0;
+    // hprt_scene_attach_kdtree: the kd walk replaces the BVH walks of every trace (kdNodes / kdPrims back `kd`); topOrder keeps
+    // the top-level prim_order (ordered -> creation number) to map the tree's creation-order primitives; instanced: no kd walk
+    hprt::DevBuf kdNodes, kdPrims; hprt::DevKd kd{}; bool kdAttached = false;
+    std::vector<uint32_t> topOrder; bool instanced = false;
     bool hasSubstrateBin = false;                     // some triangle carries BIN_SUBSTRATE: the substrate shading variant is launched
     ~HprtScene() { if (hostCounts) (void)hipHostFree(hostCounts); if (lastUse) (void)hipEventDestroy(lastUse); }
 };

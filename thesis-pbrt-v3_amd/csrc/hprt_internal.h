@@ -3,6 +3,7 @@
 #include <string>
 #include <vector>
 #include "bvh_builder.h"
+#include "kdtree_builder.h"
 #include "scene_model.h"
 
 struct HprtModel { hprt::SceneModel sc; };
@@ -10,6 +11,8 @@ struct HprtBvh {
     hprt::BvhTree tree;                       // top-level aggregate (renderOptions->primitives)
     std::vector<hprt::BvhTree> objects;       // one per object definition (the accelerator ObjectInstance builds, core/api.cpp:1798-1806)
 };
+
+struct HprtKdTree { hprt::KdTree tree; };
 
 namespace hprt {
 extern thread_local std::string g_lastError;

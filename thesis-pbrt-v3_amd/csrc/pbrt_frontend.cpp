@@ -618,6 +618,16 @@ struct Frontend {
         o.maxNodePrims = accelParams.oneInt("maxnodeprims", 4);
         o.isectCost = accelParams.oneInt("intersectcost", 8);
         o.travCost = accelParams.oneInt("traversalcost", 1);
+        if (sc->opt.accelerator == "kdtree") {
+            // CreateKdTreeAccelerator, accelerators/kdtreeaccel.cpp:523-545.  splitalpha, alphatype, axisselectiontype and
+            // axisselectionamount feed only statistics there (buildTree never reads them): accepted and ignored
+            o.kdIsectCost = accelParams.oneInt("intersectcost", 80);
+            o.kdTravCost = accelParams.oneInt("traversalcost", 1);
+            o.kdEmptyBonus = accelParams.oneFloat("emptybonus", 0.f);
+            o.kdMaxPrims = accelParams.oneInt("maxprims", 1);
+            o.kdMaxDepth = accelParams.oneInt("maxdepth", -1);
+            for (const char *n : {"splitalpha", "alphatype", "axisselectiontype", "axisselectionamount"}) (void)accelParams.find(n, "float", "integer");
+        }
         reportUnused(filmParams, "Film", {"diagonal"});
         reportUnused(filterParams, "PixelFilter");
         reportUnused(cameraParams, "Camera");

@@ -86,6 +86,8 @@ struct RenderOptions {
     int32_t spp = 16, samplePixelCenter = 0;
     int32_t maxDepth = 5; float rrThreshold = 1.f; int32_t lightStrategy = kSpatial;
     int32_t maxNodePrims = 4, isectCost = 8, travCost = 1;
+    // Accelerator "kdtree": CreateKdTreeAccelerator's parameters (accelerators/kdtreeaccel.cpp:523-545); host side only (not baked)
+    int32_t kdIsectCost = 80, kdTravCost = 1, kdMaxPrims = 1, kdMaxDepth = -1; float kdEmptyBonus = 0.f;
     std::string filename = "pbrt.exr", accelerator = "bvh", integrator = "path", sampler = "halton";
 };
 struct SceneModel {
