@@ -12,7 +12,9 @@
  *
  * Device entry points (hprt_scene_*, hprt_intersect, hprt_occluded, hprt_render,
  * hprt_film_*) require a gfx950 GPU and fail with HPRT_E_NO_DEVICE otherwise:
- * there is no CPU fallback behind this ABI.
+ * there is no CPU fallback behind this ABI.  hprt_scene_create checks the scene
+ * description first: a malformed one is reported as such (HPRT_E_INVALID or
+ * HPRT_E_UNSUPPORTED) even without a device.
  *
  * Concurrency.  An HprtScene allows ONE call in flight at a time: its work counter,
  * ray / hit staging, traversal-stack area and render workspace belong to the scene,

@@ -14,6 +14,9 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "lib")
 HOST_SRCS = ["pbrt_frontend.cpp", "loop_subdiv.cpp", "scene_io.cpp", "texture_io.cpp", "bvh_builder.cpp", "kdtree_builder.cpp", "wide_bvh.cpp", "halton_tables.cpp", "capi_host.cpp"]
+# host code built by hipcc without an offload target (no code object): the float operations of the scene layout keep the code
+# generator they had when they sat in capi_device.hip
+HIPCC_HOST_SRCS = ["scene_layout.cpp"]
 HIP_SRCS = ["device/kernels.hip", "device/kd_walk.hip", "capi_device.hip", "capi_gather.hip"]
 # hipcc names every HIP translation unit by a CUID (the __hip_cuid_* symbol in its code object) that it otherwise hashes from
 # the source's and the object's ABSOLUTE paths, so the code objects — and the sha256 profiles/rNN_counters.json is stamped
@@ -52,10 +55,10 @@ def build(verbose=False, force=False):
     hipcc = _hipcc()
     headers = _headers()
     jobs = []
-    for s in HOST_SRCS:
+    for s in HOST_SRCS + HIPCC_HOST_SRCS:
         src = os.path.join(CSRC, s)
         obj = os.path.join(OBJ, s.replace("/", "_") + ".o")
-        cmd = ["g++"] + COMMON + ["-c", src, "-o", obj]
+        cmd = [hipcc if s in HIPCC_HOST_SRCS else "g++"] + COMMON + ["-c", src, "-o", obj]
         jobs.append((src, obj, cmd))
     for s in HIP_SRCS:
         src = os.path.join(CSRC, s)

@@ -220,4 +220,22 @@ void BuildBvh(size_t nPrims, const float *bmin, const float *bmax, int maxPrimsI
     }
 }
 
+const char *CheckBvhNodes(const BvhNode *nd, uint32_t nNodes, uint32_t nPrims, int *depthOut) {
+    // children always follow their parent, so depths fill back to front
+    std::vector<int> depth(nNodes, 1);
+    for (uint32_t i = nNodes; i-- > 0;) {
+        const uint32_t count = nd[i].countAxis >> 2;
+        if ((nd[i].countAxis & 3u) == 3u) {
+            if (count == 0) return "a BVH leaf is empty";
+            if (nd[i].offset < 0 || (uint64_t)nd[i].offset + count > nPrims) return "a BVH leaf references primitives out of range";
+        } else {
+            if (i + 1 >= nNodes) return "the last BVH node is an interior node";
+            if (nd[i].offset <= (int32_t)i || (uint32_t)nd[i].offset >= nNodes) return "a BVH interior node's second child is out of range";
+            depth[i] = 1 + std::max(depth[i + 1], depth[nd[i].offset]);
+        }
+    }
+    if (depthOut) *depthOut = nNodes ? depth[0] : 0;
+    return "";
+}
+
 }  // namespace hprt

@@ -17,6 +17,12 @@ struct BvhNode {                 // == LinearBVHNode, accelerators/bvh.cpp:123-1
 };
 static_assert(sizeof(BvhNode) == 32, "BvhNode must be 32 bytes");
 
+// Structural check of a caller's node array, as the walks and BuildWide read it: every interior node has its first child next
+// and its second child further on, inside the array; every leaf holds at least one primitive, inside [0, nPrims) (pass
+// UINT32_MAX when the count is unknown).  *depth (may be null): the tree's depth in nodes, 0 for an empty array.
+// Returns an empty string when the array is well-formed, else what is wrong.
+const char *CheckBvhNodes(const BvhNode *nodes, uint32_t nNodes, uint32_t nPrims, int *depth);
+
 struct BvhTree {
     std::vector<BvhNode> nodes;
     std::vector<uint32_t> primOrder;   // ordered position -> creation-order primitive number

@@ -18,6 +18,7 @@
 #include "host_transform.h"
 #include "hprt_internal.h"
 #include "device_state.h"
+#include "scene_layout.h"
 #include "wide_bvh.h"
 
 using namespace hprt;
@@ -34,36 +35,6 @@ int CheckDevice(int device, int *chosen) {
     if (hipSetDevice(device) != hipSuccess) return SetError(HPRT_E_DEVICE, "hipSetDevice failed");
     *chosen = device;
     return HPRT_OK;
-}
-
-// TrowbridgeReitzDistribution::RoughnessToAlpha, core/microfacet.h:123-128 (host libm logf,
-// as in the reference; constant textures make it a per-material constant)
-float RoughnessToAlpha(float roughness) {
-    roughness = sel_max(roughness, (float)1e-3);
-    float x = std::log(roughness);
-    return 1.62142f + 0.819955f * x + 0.1734f * x * x + 0.0171201f * x * x * x + 0.000640711f * x * x * x * x;
-}
-
-// Would Triangle::Intersect reject every hit on this triangle as "bogus"
-// (shapes/triangle.cpp:300-316)?  Depends on the triangle only, so decided here.
-bool TriangleIsBogus(vec3 p0, vec3 p1, vec3 p2, const float *uv0, const float *uv1, const float *uv2) {
-    float u0x = 0, u0y = 0, u1x = 1, u1y = 0, u2x = 1, u2y = 1;
-    if (uv0) { u0x = uv0[0]; u0y = uv0[1]; u1x = uv1[0]; u1y = uv1[1]; u2x = uv2[0]; u2y = uv2[1]; }
-    float duv02x = u0x - u2x, duv02y = u0y - u2y, duv12x = u1x - u2x, duv12y = u1y - u2y;
-    vec3 dp02 = p0 - p2, dp12 = p1 - p2;
-    float determinant = duv02x * duv12y - duv02y * duv12x;
-    bool degenerateUV = std::fabs(determinant) < 1e-8;
-    vec3 dpdu, dpdv;
-    if (!degenerateUV) {
-        float invdet = 1 / determinant;
-        dpdu = (duv12y * dp02 - duv02y * dp12) * invdet;
-        dpdv = (-duv12x * dp02 + duv02x * dp12) * invdet;
-    }
-    if (degenerateUV || length2(cross(dpdu, dpdv)) == 0) {
-        vec3 ng = cross(p2 - p0, p1 - p0);
-        if (length2(ng) == 0) return true;
-    }
-    return false;
 }
 
 struct PlaneAllocator {
@@ -119,30 +90,6 @@ void MakeCamera(const HprtRenderOptions &o, DevCamera *cam) {
     // cameras/perspective.cpp:55-58
     cam->dxCamera = xf_point(cam->rasterToCamera, vec3(1, 0, 0)) - xf_point(cam->rasterToCamera, vec3(0, 0, 0));
     cam->dyCamera = xf_point(cam->rasterToCamera, vec3(0, 1, 0)) - xf_point(cam->rasterToCamera, vec3(0, 0, 0));
-}
-
-// RadicalInverse(0..4, i), i < 128 (core/lowdiscrepancy.cpp:2478-2488, 389-403): the 3D point and the 2D light sample of
-// SpatialLightDistribution::ComputeDistribution's 128 samples per voxel, as [5][128]
-void VoxelSamplePoints(float *out) {
-    const int bases[5] = {2, 3, 5, 7, 11};
-    for (int b = 0; b < 5; ++b)
-        for (uint32_t i = 0; i < 128; ++i) {
-            float v;
-            if (b == 0) {
-                uint32_t n = i;      // ReverseBits32(a) * 0x1p-32, evaluated in double
-                n = (n << 16) | (n >> 16); n = ((n & 0x00ff00ffu) << 8) | ((n & 0xff00ff00u) >> 8); n = ((n & 0x0f0f0f0fu) << 4) | ((n & 0xf0f0f0f0u) >> 4);
-                n = ((n & 0x33333333u) << 2) | ((n & 0xccccccccu) >> 2); n = ((n & 0x55555555u) << 1) | ((n & 0xaaaaaaaau) >> 1);
-                v = (float)((double)n * 0x1p-32);
-            } else {
-                const int base = bases[b];
-                const float invBase = (float)1 / (float)base;
-                uint64_t reversedDigits = 0, a = i;
-                float invBaseN = 1;
-                while (a) { uint64_t next = a / base, digit = a - next * base; reversedDigits = reversedDigits * base + digit; invBaseN *= invBase; a = next; }
-                v = sel_min((float)reversedDigits * invBaseN, HPRT_ONE_MINUS_EPS);
-            }
-            out[128 * b + i] = v;
-        }
 }
 
 // A path vertex consumes up to 8 sampler dimensions after the camera sample's 5; the reference's
@@ -203,556 +150,64 @@ void AddTilePixels(FrameSetup *f, int tile) {
 
 extern "C" {
 
-// MIPMap<RGBSpectrum>::Lookup(st, width) on the host, over an HprtTextureDesc (core/mipmap.h:203-260; repeat wrap): the same
-// float operations as the device's mip_triangle / the oracle's MipLookupWidth.  Used once per infinite light for the scalar image
-// of its Distribution2D (lights/infinite.cpp:66-85) and for Power() (:87-91).
-namespace {
-inline int HostModI(int a, int b) { const int r = a - (a / b) * b; return r < 0 ? r + b : r; }
-inline rgb HostMipTexel(const HprtTextureDesc &tx, int level, int s, int t) {
-    const HprtTextureLevel &l = tx.levels[level];
-    s = HostModI(s, l.w); t = HostModI(t, l.h);
-    const float *p = l.rgb + 3 * ((size_t)t * (size_t)l.w + (size_t)s);
-    return rgb(p[0], p[1], p[2]);
-}
-inline rgb HostMipTriangle(const HprtTextureDesc &tx, int level, float su, float sv) {
-    level = level < 0 ? 0 : (level > (int)tx.n_levels - 1 ? (int)tx.n_levels - 1 : level);
-    const HprtTextureLevel &l = tx.levels[level];
-    const float s = su * l.w - 0.5f, t = sv * l.h - 0.5f;
-    const int s0 = (int)std::floor(s), t0 = (int)std::floor(t);
-    const float ds = s - s0, dt = t - t0;
-    return (1 - ds) * (1 - dt) * HostMipTexel(tx, level, s0, t0) + (1 - ds) * dt * HostMipTexel(tx, level, s0, t0 + 1) +
-           ds * (1 - dt) * HostMipTexel(tx, level, s0 + 1, t0) + ds * dt * HostMipTexel(tx, level, s0 + 1, t0 + 1);
-}
-inline rgb HostMipLookupWidth(const HprtTextureDesc &tx, float su, float sv, float width) {
-    const int nLevels = (int)tx.n_levels;
-    const float invLog2 = 1.442695040888963387004650940071;
-    const float level = nLevels - 1 + det_logf(sel_max(width, (float)1e-8)) * invLog2;
-    if (level < 0) return HostMipTriangle(tx, 0, su, sv);
-    else if (level >= nLevels - 1) return HostMipTexel(tx, nLevels - 1, 0, 0);
-    const int iLevel = (int)std::floor(level);
-    const float delta = level - iLevel;
-    return (1 - delta) * HostMipTriangle(tx, iLevel, su, sv) + delta * HostMipTriangle(tx, iLevel + 1, su, sv);
-}
-}  // namespace
-
 int hprt_scene_create(const HprtSceneDesc *d, int device, HprtScene **out) try {
     if (!d || !out) return SetError(HPRT_E_INVALID, "hprt_scene_create: null argument");
-    if ((d->n_nodes && !d->nodes) || (d->n_prims && !d->prim_order) || (d->n_shapes && !d->shapes) ||
-        (d->n_materials && !d->materials) || (d->n_lights && !d->lights))
-        return SetError(HPRT_E_INVALID, "hprt_scene_create: null array with non-zero count");
-    if (d->n_textures && !d->textures) return SetError(HPRT_E_INVALID, "hprt_scene_create: null texture array with non-zero count");
-    if ((d->n_objects && !d->objects) || (d->n_instances && !d->instances) || (d->n_top && !d->top))
-        return SetError(HPRT_E_INVALID, "hprt_scene_create: null instancing array with non-zero count");
-    // ---- validate the description against what the kernels assume ----
-    std::vector<uint64_t> vtxBase(d->n_shapes + 1, 0);
-    std::vector<uint32_t> shapePrims(d->n_shapes, 0);
-    uint32_t nSpheres = 0;
-    for (uint32_t s = 0; s < d->n_shapes; ++s) {
-        const HprtShapeDesc &sh = d->shapes[s];
-        if (sh.material < 0 || (uint32_t)sh.material >= d->n_materials) return SetError(HPRT_E_INVALID, "shape material index out of range");
-        if (sh.area_light >= (int32_t)d->n_lights) return SetError(HPRT_E_INVALID, "shape area light index out of range");
-        if (sh.kind == 0) {
-            if (sh.n_tris && (!sh.indices || !sh.P)) return SetError(HPRT_E_INVALID, "mesh without indices or positions");
-            for (uint64_t i = 0; i < 3ull * sh.n_tris; ++i)
-                if (sh.indices[i] < 0 || (uint32_t)sh.indices[i] >= sh.n_verts) return SetError(HPRT_E_INVALID, "mesh vertex index out of range");
-            // an emissive mesh owns one light per triangle, consecutive and in face order (core/api.cpp:1609-1636)
-            if (sh.area_light >= 0) {
-                if ((uint64_t)sh.area_light + sh.n_tris > d->n_lights) return SetError(HPRT_E_INVALID, "emissive mesh: its per-triangle lights exceed the light table");
-                for (uint32_t t = 0; t < sh.n_tris; ++t)
-                    if (d->lights[sh.area_light + t].type != 2 || d->lights[sh.area_light + t].shape != (int32_t)s)
-                        return SetError(HPRT_E_INVALID, "emissive mesh: light area_light + t must be the diffuse area light of its triangle t");
-            }
-            shapePrims[s] = sh.n_tris; vtxBase[s + 1] = vtxBase[s] + sh.n_verts;
-        } else if (sh.kind == 1) {
-            shapePrims[s] = 1; vtxBase[s + 1] = vtxBase[s]; ++nSpheres;
-        } else return SetError(HPRT_E_INVALID, "unknown shape kind");
-    }
-    (void)nSpheres;
-    if (vtxBase[d->n_shapes] > 0xffffffffull) return SetError(HPRT_E_UNSUPPORTED, "more than 2^32 vertices");
-    // ---- aggregates: 0 = the top level (renderOptions->primitives), 1 + k = object definition k ----
-    struct AggPrim { int32_t shape; uint32_t local; };      // shape < 0: instance `local`
-    struct Agg { const BvhNode *nodes; uint32_t nNodes; const uint32_t *order; uint32_t nPrims; std::vector<AggPrim> prims; };
-    std::vector<Agg> aggs(1 + (size_t)d->n_objects);
-    std::vector<int32_t> objectOfShape(d->n_shapes, -1);
-    aggs[0].nodes = (const BvhNode *)d->nodes; aggs[0].nNodes = d->n_nodes; aggs[0].order = d->prim_order; aggs[0].nPrims = d->n_prims;
-    auto addShape = [&](Agg &a, uint32_t s) { for (uint32_t k = 0; k < shapePrims[s]; ++k) a.prims.push_back(AggPrim{(int32_t)s, k}); };
-    for (uint32_t k = 0; k < d->n_objects; ++k) {
-        const HprtObjectDesc &o = d->objects[k];
-        Agg &a = aggs[1 + (size_t)k];
-        if ((uint64_t)o.first_shape + o.n_shapes > d->n_shapes) return SetError(HPRT_E_INVALID, "object shape range out of bounds");
-        if ((o.n_nodes && !o.nodes) || (o.n_prims && !o.prim_order)) return SetError(HPRT_E_INVALID, "object without its aggregate arrays");
-        a.nodes = (const BvhNode *)o.nodes; a.nNodes = o.n_nodes; a.order = o.prim_order; a.nPrims = o.n_prims;
-        for (uint32_t s = o.first_shape; s < o.first_shape + o.n_shapes; ++s) {
-            if (objectOfShape[s] >= 0) return SetError(HPRT_E_INVALID, "a shape belongs to two objects");
-            if (d->shapes[s].area_light >= 0) return SetError(HPRT_E_UNSUPPORTED, "area lights are not supported with object instancing (core/api.cpp:1640)");
-            objectOfShape[s] = (int32_t)k;
-            addShape(a, s);
-        }
-    }
-    for (uint32_t i = 0; i < d->n_instances; ++i) {
-        const int32_t o = d->instances[i].object;
-        if (o < 0 || (uint32_t)o >= d->n_objects) return SetError(HPRT_E_INVALID, "instance object index out of range");
-        if (aggs[1 + (size_t)o].prims.empty()) return SetError(HPRT_E_INVALID, "instance of an empty object");
-    }
-    if (d->top) {
-        for (uint32_t t = 0; t < d->n_top; ++t) {
-            const HprtTopItem &it = d->top[t];
-            if (it.kind == 0) {
-                if (it.index >= d->n_shapes || objectOfShape[it.index] >= 0) return SetError(HPRT_E_INVALID, "top-level item references a missing or object-owned shape");
-                addShape(aggs[0], it.index);
-            } else if (it.kind == 1) {
-                if (it.index >= d->n_instances) return SetError(HPRT_E_INVALID, "top-level item references a missing instance");
-                aggs[0].prims.push_back(AggPrim{-1, it.index});
-            } else return SetError(HPRT_E_INVALID, "unknown top-level item kind");
-        }
-    } else {
-        if (d->n_instances) return SetError(HPRT_E_INVALID, "instances need the top-level item list");
-        for (uint32_t s = 0; s < d->n_shapes; ++s) if (objectOfShape[s] < 0) addShape(aggs[0], s);
-    }
-    // primitive records and node pairs of all aggregates share one array each; 32-bit byte offsets address them
-    std::vector<uint32_t> primBase(aggs.size() + 1, 0), pairBase(aggs.size() + 1, 0);
-    {
-        uint64_t np = 0, npair = 0;
-        for (size_t a = 0; a < aggs.size(); ++a) {
-            const Agg &g = aggs[a];
-            if (g.prims.size() != g.nPrims) return SetError(HPRT_E_INVALID, "prim_order length does not match the aggregate's primitive count");
-            // BVH sanity: every child/primitive reference must stay inside the arrays
-            uint32_t interior = 0;
-            for (uint32_t i = 0; i < g.nNodes; ++i) {
-                uint32_t axis = g.nodes[i].countAxis & 3u, cnt = g.nodes[i].countAxis >> 2;
-                if (axis == 3u) { if (g.nodes[i].offset < 0 || cnt == 0 || (uint64_t)g.nodes[i].offset + cnt > g.nPrims) return SetError(HPRT_E_INVALID, "BVH leaf is empty or references primitives out of range"); }
-                else { ++interior; if (g.nodes[i].offset <= (int32_t)i || (uint32_t)g.nodes[i].offset >= g.nNodes || i + 1 >= g.nNodes) return SetError(HPRT_E_INVALID, "BVH interior node has an invalid child"); }
-            }
-            if ((g.nPrims != 0) != (g.nNodes != 0)) return SetError(HPRT_E_INVALID, "aggregate with primitives but no nodes (or the reverse)");
-            for (uint32_t i = 0; i < g.nPrims; ++i) if (g.order[i] >= g.nPrims) return SetError(HPRT_E_INVALID, "prim_order entry out of range");
-            primBase[a] = (uint32_t)np; pairBase[a] = (uint32_t)npair;
-            np += g.nPrims; npair += g.nNodes ? interior + 1u : 0u;
-            if (np * 48ull > 0xffffffffull || npair * 64ull > 0xffffffffull)
-                return SetError(HPRT_E_UNSUPPORTED, "more than 89,478,485 primitives (or 67,108,863 interior nodes) over all aggregates");
-        }
-        primBase[aggs.size()] = (uint32_t)np; pairBase[aggs.size()] = (uint32_t)npair;
-    }
-    const uint32_t totalPrims = primBase[aggs.size()];
-    for (uint32_t l = 0; l < d->n_lights; ++l) {
-        const HprtLightDesc &L = d->lights[l];
-        if (L.type < 0 || L.type > 3) return SetError(HPRT_E_INVALID, "unknown light type");
-        if (L.type == 3) {
-            if (L.texture < 0 || (uint32_t)L.texture >= d->n_textures) return SetError(HPRT_E_INVALID, "infinite light: map index out of range");
-            const HprtTextureDesc &mt = d->textures[L.texture];
-            if (!mt.levels || mt.n_levels == 0 || mt.n_levels > 26 || mt.wrap != 0) return SetError(HPRT_E_INVALID, "infinite light: its map must be a repeat-wrapped pyramid of at most 26 levels");
-            if ((uint64_t)mt.levels[0].w * (uint64_t)mt.levels[0].h > (1ull << 26)) return SetError(HPRT_E_UNSUPPORTED, "infinite light: map larger than 2^26 texels");
-        }
-        if (L.type == 2) {
-            if (L.shape < 0 || (uint32_t)L.shape >= d->n_shapes) return SetError(HPRT_E_INVALID, "area light shape out of range");
-            const HprtShapeDesc &ls = d->shapes[L.shape];
-            const bool own = ls.kind == 1 ? ls.area_light == (int32_t)l
-                                          : ls.area_light >= 0 && (int32_t)l >= ls.area_light && (uint32_t)((int32_t)l - ls.area_light) < ls.n_tris;
-            if (!own) return SetError(HPRT_E_INVALID, "area light and its shape do not reference each other");
-        }
-    }
-    // CreateLightSampleDistribution (core/lightdistrib.cpp:48-66): a single light always gets the uniform distribution
-    const int lightStrategy = d->n_lights <= 1 ? 0 : d->light_strategy;
-    if (lightStrategy < 0 || lightStrategy > 2) return SetError(HPRT_E_INVALID, "light_strategy must be 0 (uniform), 1 (power) or 2 (spatial)");
+    SceneLayout L;
+    if (int rc = BuildSceneLayout(*d, &L)) return rc;
     int dev;
-    int rc = CheckDevice(device, &dev);
-    if (rc != HPRT_OK) return rc;
-
-    HprtScene *sc = new HprtScene();
-    sc->device = dev; sc->nPrims = totalPrims;
-    sc->topOrder.assign(d->prim_order, d->prim_order + d->n_prims); sc->instanced = d->n_instances != 0;
-    std::unique_ptr<HprtScene> guard(sc);
-    // ---- flatten ----
-    const uint32_t nVtx = (uint32_t)vtxBase[d->n_shapes];
-    std::vector<float> vUV(2 * (size_t)nVtx, 0.f), vS(3 * (size_t)nVtx, 0.f);
-    std::vector<DevShape> shapes(d->n_shapes);
-    std::vector<DevSphere> spheres; std::vector<int> sphereOfShape(d->n_shapes, -1);
-    for (uint32_t s = 0; s < d->n_shapes; ++s) {
-        const HprtShapeDesc &sh = d->shapes[s];
-        DevShape &o = shapes[s];
-        o.material = sh.material; o.areaLight = sh.area_light; o.sphere = -1;
-        o.flags = ((sh.reverse_orientation != 0) ^ (sh.transform_swaps_handedness != 0)) ? SHAPE_FLIP : 0u;
-        if (sh.reverse_orientation) o.flags |= SHAPE_REVERSE;
-        if (sh.kind == 0) {
-            size_t b = vtxBase[s];
-            if (sh.N) o.flags |= SHAPE_HAS_N;
-            if (sh.UV) { o.flags |= SHAPE_HAS_UV; memcpy(&vUV[2 * b], sh.UV, 8 * (size_t)sh.n_verts); }
-            if (sh.S) { o.flags |= SHAPE_HAS_S; memcpy(&vS[3 * b], sh.S, 12 * (size_t)sh.n_verts); }
-        } else {
-            DevSphere sp;
-            memcpy(sp.o2w.m, sh.object_to_world, 64); memcpy(sp.w2o.m, sh.world_to_object, 64);
-            sp.radius = sh.radius; sp.zMin = sh.z_min; sp.zMax = sh.z_max; sp.thetaMin = sh.theta_min; sp.thetaMax = sh.theta_max; sp.phiMax = sh.phi_max;
-            o.sphere = sphereOfShape[s] = (int)spheres.size();
-            spheres.push_back(sp);
-        }
-    }
-    std::vector<float4> tris(3 * (size_t)totalPrims);
-    std::vector<uint32_t> primVtx(3 * (size_t)totalPrims, 0u);
-    std::vector<float4> primN(3 * (size_t)totalPrims, make_float4(0.f, 0.f, 0.f, 0.f));
-    std::vector<int32_t> lightPrim(d->n_lights, -1);      // triangle lights: ordered index of their triangle
-    for (size_t ai = 0; ai < aggs.size(); ++ai) {
-        const Agg &g = aggs[ai];
-        for (uint32_t oi = 0; oi < g.nPrims; ++oi) {
-            const size_t i = (size_t)primBase[ai] + oi;
-            const AggPrim e = g.prims[g.order[oi]];
-            float4 r0, r1, r2;
-            if (e.shape < 0) {     // TransformedPrimitive
-                r0 = make_float4(0, 0, 0, u2f(TAG_INSTANCE)); r1 = make_float4(0, 0, 0, u2f(0u)); r2 = make_float4(0, 0, 0, u2f(e.local));
-            } else {
-                const uint32_t s = (uint32_t)e.shape;
-                const HprtShapeDesc &sh = d->shapes[s];
-                if (sh.kind == 0) {
-                    const int32_t *v = &sh.indices[3 * (size_t)e.local];
-                    const float *a = &sh.P[3 * (size_t)v[0]], *b = &sh.P[3 * (size_t)v[1]], *c = &sh.P[3 * (size_t)v[2]];
-                    bool bogus = TriangleIsBogus(vec3(a[0], a[1], a[2]), vec3(b[0], b[1], b[2]), vec3(c[0], c[1], c[2]),
-                                                 sh.UV ? &sh.UV[2 * (size_t)v[0]] : nullptr, sh.UV ? &sh.UV[2 * (size_t)v[1]] : nullptr,
-                                                 sh.UV ? &sh.UV[2 * (size_t)v[2]] : nullptr);
-                    const HprtMaterialDesc &md = d->materials[sh.material];
-                    // a triangle of an emissive mesh: aux = 1 + its light, and TAG_GENERIC — the generic shading variant is the one that looks for Le
-                    const int32_t triLight = sh.area_light >= 0 ? sh.area_light + (int32_t)e.local : -1;
-                    if (triLight >= 0) lightPrim[triLight] = (int32_t)i;
-                    const bool textured = md.kd_texture >= 0 || md.ks_texture >= 0 || (md.type == 6 && md.opacity_texture >= 0);
-                    // the shading bin: plain matte / plastic / substrate triangles have kernels of their own; emitters, textured and every other
-                    // material (OrenNayar, mirror, metal, glass, uber) are shaded by the generic variant
-                    const uint32_t bin = textured ? BIN_TEXTURED : triLight >= 0 ? BIN_GENERIC : md.type == 1 ? BIN_PLASTIC : md.type == 3 ? BIN_SUBSTRATE :
-                                         (md.type == 0 && clampf(md.sigma, 0.f, 90.f) == 0.f) ? BIN_MATTE : BIN_GENERIC;
-                    uint32_t tag = (bogus ? TAG_BOGUS : 0u) | (bin << TAG_BIN_SHIFT);
-                    if (bin == BIN_SUBSTRATE) sc->hasSubstrateBin = true;
-                    r0 = make_float4(a[0], a[1], a[2], u2f(tag)); r1 = make_float4(b[0], b[1], b[2], u2f(s)); r2 = make_float4(c[0], c[1], c[2], u2f((uint32_t)(triLight + 1)));
-                    for (int k = 0; k < 3; ++k) {
-                        primVtx[3 * i + k] = (uint32_t)(vtxBase[s] + (uint32_t)v[k]);
-                        if (sh.N) { const float *nn = &sh.N[3 * (size_t)v[k]]; primN[3 * i + k] = make_float4(nn[0], nn[1], nn[2], 0.f); }
-                    }
-                } else {
-                    const HprtMaterialDesc &md = d->materials[sh.material];
-                    const bool textured = md.kd_texture >= 0 || md.ks_texture >= 0 || (md.type == 6 && md.opacity_texture >= 0);
-                    r0 = make_float4(0, 0, 0, u2f(TAG_SPHERE | ((textured ? BIN_TEXTURED : BIN_GENERIC) << TAG_BIN_SHIFT))); r1 = make_float4(0, 0, 0, u2f(s)); r2 = make_float4(0, 0, 0, u2f((uint32_t)sphereOfShape[s]));
-                }
-            }
-            tris[3 * i] = r0; tris[3 * i + 1] = r1; tris[3 * i + 2] = r2;
-        }
-    }
-    std::vector<DevMaterial> mats(d->n_materials);
-    for (uint32_t m = 0; m < d->n_materials; ++m) {
-        const HprtMaterialDesc &in = d->materials[m];
-        if (in.type < 0 || in.type > 6) return SetError(HPRT_E_UNSUPPORTED, "material type outside the hot-path scope (matte, plastic, mirror, substrate, metal, glass, uber)");
-        if (in.kd_texture >= (int32_t)d->n_textures || in.ks_texture >= (int32_t)d->n_textures || (in.type == 6 && in.opacity_texture >= (int32_t)d->n_textures))
-            return SetError(HPRT_E_INVALID, "material texture index out of range");
-        DevMaterial &o = mats[m];
-        o.KdTex = in.kd_texture >= 0 ? in.kd_texture : -1; o.KsTex = in.ks_texture >= 0 ? in.ks_texture : -1;
-        o.opTex = in.type == 6 && in.opacity_texture >= 0 ? in.opacity_texture : -1;
-        o.type = in.type; memcpy(o.Kd, in.Kd, 12); memcpy(o.Ks, in.Ks, 12);
-        o.alpha = in.remap_roughness ? RoughnessToAlpha(in.roughness) : in.roughness;
-        o.alphaY = o.alpha;
-        if (in.type == 3 || in.type == 4 || in.type == 6) o.alphaY = in.remap_roughness ? RoughnessToAlpha(in.sigma) : in.sigma;      // substrate / metal / uber: sigma carries vroughness
-        memcpy(o.Kr, in.Kr, 12); memcpy(o.Kt, in.Kt, 12); memcpy(o.opacity, in.opacity, 12); o.eta = in.eta;
-        o.roughGlass = 0;
-        if (in.type == 5) {
-            o.alpha = in.roughness;      // glass: the index of refraction, as given
-            // rough dielectric (materials/glass.cpp:61-72): isSpecular is decided on the values as given, the remap applies to both after it
-            if (in.sigma != 0.f || in.Kr[0] != 0.f) {
-                o.roughGlass = 1;
-                o.Kr[0] = in.remap_roughness ? RoughnessToAlpha(in.sigma) : in.sigma;
-                o.Kr[1] = in.remap_roughness ? RoughnessToAlpha(in.Kr[0]) : in.Kr[0];
-            }
-        }
-        // MatteMaterial: sig = Clamp(sigma, 0, 90); sig != 0 -> OrenNayar(r, sig) (materials/matte.cpp:55-61, core/reflection.h:414-420)
-        const float sig = clampf(in.sigma, 0.f, 90.f);
-        o.oren = in.type == 0 && sig != 0.f ? 1 : 0; o.orenA = 1.f; o.orenB = 0.f;
-        if (o.oren) {
-            const float sigma = (HPRT_PI / 180) * sig;
-            const float sigma2 = sigma * sigma;
-            o.orenA = 1.f - (sigma2 / (2.f * (sigma2 + 0.33f)));
-            o.orenB = 0.45f * sigma2 / (sigma2 + 0.09f);
-        }
-    }
-    // image textures: every pyramid level of every texture in one texel array (3 floats per texel)
-    std::vector<DevTexture> textures(d->n_textures);
-    std::vector<DevMipLevel> mipLevels;
-    std::vector<float> texels, weightLut;
-    for (uint32_t t = 0; t < d->n_textures; ++t) {
-        const HprtTextureDesc &in = d->textures[t];
-        if (!in.levels || in.n_levels == 0 || in.n_levels > 32 || !in.weight_lut) return SetError(HPRT_E_INVALID, "texture without levels or weight table");
-        if (in.wrap < 0 || in.wrap > 2) return SetError(HPRT_E_INVALID, "texture wrap mode out of range");
-        DevTexture &o = textures[t];
-        o.firstLevel = (uint32_t)mipLevels.size(); o.nLevels = in.n_levels; o.trilinear = in.trilinear ? 1 : 0; o.wrap = in.wrap;
-        o.maxAniso = in.max_anisotropy; o.su = in.su; o.sv = in.sv; o.du = in.du; o.dv = in.dv;
-        for (uint32_t l = 0; l < in.n_levels; ++l) {
-            const HprtTextureLevel &lv = in.levels[l];
-            if (lv.w <= 0 || lv.h <= 0 || !lv.rgb) return SetError(HPRT_E_INVALID, "empty texture level");
-            const size_t n = 3 * (size_t)lv.w * (size_t)lv.h;
-            if (texels.size() + n > 0xffffffffull) return SetError(HPRT_E_UNSUPPORTED, "more than 2^32 texture floats");
-            mipLevels.push_back(DevMipLevel{(uint32_t)texels.size(), lv.w, lv.h});
-            texels.insert(texels.end(), lv.rgb, lv.rgb + n);
-        }
-        // MIPMap::weightLut is a static table (core/mipmap.h:107, 153-161): identical for every texture
-        if (t == 0) weightLut.assign(in.weight_lut, in.weight_lut + 128);
-        else if (memcmp(weightLut.data(), in.weight_lut, 128 * sizeof(float)) != 0) return SetError(HPRT_E_INVALID, "textures disagree on the EWA weight table");
-    }
-    std::vector<DevLight> lights(d->n_lights);
-    for (uint32_t l = 0; l < d->n_lights; ++l) {
-        const HprtLightDesc &in = d->lights[l];
-        DevLight &o = lights[l];
-        o.type = in.type; memcpy(o.pos, in.pos, 12); memcpy(o.I, in.I, 12); o.shape = in.shape; o.twoSided = in.two_sided;
-        const bool onMesh = in.type == 2 && d->shapes[in.shape].kind == 0;
-        if (onMesh && lightPrim[l] < 0) return SetError(HPRT_E_UNSUPPORTED, "emissive triangle outside the top-level aggregate (area lights are not supported with object instancing, core/api.cpp:1640)");
-        if (onMesh) o.type = 3;
-        o.prim = onMesh ? lightPrim[l] : -1;
-        o.sphere = in.type == 2 && !onMesh ? sphereOfShape[in.shape] : -1;
-        o.shapeFlags = in.type == 2 ? shapes[in.shape].flags : 0u;
-    }
-    // infinite lights: the scalar image of lights/infinite.cpp:66-85 (2w x 2h: luminance of the filtered map times sin theta) and
-    // its Distribution2D, built with the float operations of Distribution1D's constructor (hprt_math.h dist1d_build)
-    std::vector<DevEnvLight> envLights;
-    std::vector<float> envData;
-    for (uint32_t l = 0; l < d->n_lights; ++l) {
-        const HprtLightDesc &in = d->lights[l];
-        if (in.type != 3) continue;
-        const HprtTextureDesc &tx = d->textures[in.texture];
-        DevEnvLight e; memset(&e, 0, sizeof(e));
-        memcpy(&e.l2w, in.light_to_world, 64); memcpy(&e.w2l, in.world_to_light, 64);
-        e.tex = in.texture;
-        const int width = 2 * tx.levels[0].w, height = 2 * tx.levels[0].h;
-        e.nu = width; e.nv = height; e.off = (uint32_t)envData.size();
-        const size_t nFloats = (size_t)height * width + (size_t)height * (width + 1) + (size_t)height + (size_t)height + 1;
-        if (envData.size() + nFloats > 0x7fffffffull) return SetError(HPRT_E_UNSUPPORTED, "infinite light maps too large");
-        envData.resize(envData.size() + nFloats);
-        float *condFunc = envData.data() + e.off, *condCdf = condFunc + (size_t)height * width, *condInt = condCdf + (size_t)height * (width + 1),
-              *margCdf = condInt + height;
-        const float fwidth = 0.5f / std::min(width, height);
-        for (int v = 0; v < height; ++v) {
-            const float vp = (v + .5f) / (float)height;
-            const float sinTheta = det_sinf(HPRT_PI * (v + .5f) / height);
-            for (int u = 0; u < width; ++u) {
-                const float up = (u + .5f) / (float)width;
-                float y = luminance(HostMipLookupWidth(tx, up, vp, fwidth));
-                y *= sinTheta;
-                condFunc[(size_t)v * width + u] = y;
-            }
-            dist1d_build(condFunc + (size_t)v * width, width, condCdf + (size_t)v * (width + 1), &condInt[v]);
-        }
-        dist1d_build(condInt, height, margCdf, &e.margFuncInt);
-        DevLight &o = lights[l];
-        o.type = 4; o.shape = (int32_t)envLights.size();
-        envLights.push_back(e);
-    }
-    // Scene::worldBound + Bounds3::BoundingSphere (core/scene.h:56-66, core/geometry.h:980-983)
-    float worldRadius = 0.f;
-    vec3 wbLo, wbHi;
-    if (d->n_nodes) {
-        const BvhNode &root = ((const BvhNode *)d->nodes)[0];
-        wbLo = vec3(root.bmin[0], root.bmin[1], root.bmin[2]); wbHi = vec3(root.bmax[0], root.bmax[1], root.bmax[2]);
-        vec3 c = div_by(wbLo + wbHi, 2.f);
-        bool inside = c.x >= wbLo.x && c.x <= wbHi.x && c.y >= wbLo.y && c.y <= wbHi.y && c.z >= wbLo.z && c.z <= wbHi.z;
-        worldRadius = inside ? dist(c, wbHi) : 0.f;
-    }
-    // UniformLightDistribution (core/lightdistrib.cpp:68-75) or PowerLightDistribution (:77-82, ComputeLightPowerDistribution,
-    // core/integrator.cpp:219-227: Light::Power().y()) as a Distribution1D (core/sampling.h:57-70)
-    std::vector<float> func(std::max<uint32_t>(1, d->n_lights), 1.f), cdf(d->n_lights + 1, 0.f);
-    if (lightStrategy == 1)
-        for (uint32_t l = 0; l < d->n_lights; ++l) {
-            const HprtLightDesc &in = d->lights[l];
-            const rgb I(in.I[0], in.I[1], in.I[2]);
-            rgb power;
-            if (in.type == 0) power = I * (4 * HPRT_PI);                                      // lights/point.cpp:55
-            else if (in.type == 1) power = I * HPRT_PI * worldRadius * worldRadius;          // lights/distant.cpp:61-63
-            else if (in.type == 3) power = HPRT_PI * worldRadius * worldRadius * HostMipLookupWidth(d->textures[in.texture], .5f, .5f, .5f);   // lights/infinite.cpp:87-91
-            else {                                                                            // lights/diffuse.cpp:64-66, area = shape->Area()
-                const HprtShapeDesc &ls = d->shapes[in.shape];
-                float area;
-                if (ls.kind == 1) area = ls.phi_max * ls.radius * (ls.z_max - ls.z_min);      // Sphere::Area, shapes/sphere.cpp:215
-                else {                                                                        // Triangle::Area, shapes/triangle.cpp:576-582
-                    const int32_t *v = &ls.indices[3 * (size_t)((int32_t)l - ls.area_light)];
-                    const vec3 p0(ls.P[3 * v[0]], ls.P[3 * v[0] + 1], ls.P[3 * v[0] + 2]), p1(ls.P[3 * v[1]], ls.P[3 * v[1] + 1], ls.P[3 * v[1] + 2]),
-                               p2(ls.P[3 * v[2]], ls.P[3 * v[2] + 1], ls.P[3 * v[2] + 2]);
-                    area = (float)(0.5 * (double)length(cross(p1 - p0, p2 - p0)));
-                }
-                power = I * (float)(in.two_sided ? 2 : 1) * area * HPRT_PI;
-            }
-            func[l] = luminance(power);
-        }
-    float funcInt = 0.f;
-    if (d->n_lights) dist1d_build(func.data(), (int)d->n_lights, cdf.data(), &funcInt);
+    if (int rc = CheckDevice(device, &dev)) return rc;
+    std::unique_ptr<HprtScene> sc(new HprtScene());
+    sc->device = dev; sc->nPrims = L.nPrims;
+    sc->topOrder = std::move(L.topOrder); sc->instanced = L.instanced; sc->hasSubstrateBin = L.hasSubstrateBin;
     // Halton tables + 64-bit division magics
     const std::vector<uint16_t> &perms = HaltonPermutations();
-    // ---- child-pair layout of the BVHs (device/dev_scene.h): one run of pairs per aggregate ----
-    std::vector<DevPair> pairs((size_t)pairBase[aggs.size()]);
-    std::vector<DevWide> wide;
-    std::vector<float4> leafBox;
-    std::vector<int32_t> wideBase(aggs.size(), -1);      // first wide record of every aggregate that has a tree
-    bool wideOk = true; int wideNeedTop = 0, wideNeedObject = 0;
-    // The ordered walk keeps at most one pending sibling per level, plus the sentinel of an instance: the kernel's
-    // stack has HPRT_STACK_TOTAL = 64 entries (LDS + HBM part), as the reference's nodesToVisit[64]
-    // (accelerators/bvh.cpp:365).  Deeper trees are refused here rather than walked wrongly.
-    int topDepth = 0, objectDepth = 0;
-    for (size_t ai = 0; ai < aggs.size(); ++ai) {
-        const Agg &g = aggs[ai];
-        if (g.nNodes == 0) continue;
-        const BvhNode *nd = g.nodes;
-        {   // depth of this aggregate's tree (depth-first layout: first child at i + 1, second child at offset)
-            std::vector<std::pair<uint32_t, int>> todo; todo.push_back({0u, 1});
-            int depth = 0;
-            while (!todo.empty()) {
-                auto [i, dpt] = todo.back(); todo.pop_back();
-                if (i >= g.nNodes) return SetError(HPRT_E_INVALID, "BVH node index out of range");
-                depth = std::max(depth, dpt);
-                if ((nd[i].countAxis & 3u) != 3u) {
-                    if ((uint32_t)nd[i].offset <= i || (uint32_t)nd[i].offset >= g.nNodes) return SetError(HPRT_E_INVALID, "BVH second-child offset out of range");
-                    todo.push_back({(uint32_t)nd[i].offset, dpt + 1}); todo.push_back({i + 1u, dpt + 1});
-                }
-            }
-            if (ai == 0) topDepth = depth; else objectDepth = std::max(objectDepth, depth);
-        }
-        std::vector<int32_t> ref(g.nNodes);
-        int32_t nextPair = (int32_t)pairBase[ai] + 1;
-        for (uint32_t i = 0; i < g.nNodes; ++i) {
-            if ((nd[i].countAxis & 3u) == 3u) {
-                ref[i] = ~(int32_t)(primBase[ai] + (uint32_t)nd[i].offset);
-                const size_t last = (size_t)primBase[ai] + (uint32_t)nd[i].offset + (nd[i].countAxis >> 2) - 1u;
-                tris[3 * last].w = u2f(f2u(tris[3 * last].w) | TAG_LAST);
-            } else ref[i] = nextPair++;
-        }
-        auto fill = [&](DevPair &p, uint32_t c0, uint32_t c1, uint32_t meta) {
-            const BvhNode &a = nd[c0], &b = nd[c1];
-            p.x[0] = a.bmin[0]; p.x[1] = b.bmin[0]; p.x[2] = a.bmax[0]; p.x[3] = b.bmax[0];
-            p.y[0] = a.bmin[1]; p.y[1] = b.bmin[1]; p.y[2] = a.bmax[1]; p.y[3] = b.bmax[1];
-            p.z[0] = a.bmin[2]; p.z[1] = b.bmin[2]; p.z[2] = a.bmax[2]; p.z[3] = b.bmax[2];
-            p.ref0 = ref[c0]; p.ref1 = ref[c1]; p.meta = meta; p.pad = 0u;
-        };
-        fill(pairs[pairBase[ai]], 0u, 0u, PAIR_SINGLE);      // synthetic parent of the root: carries the root's bounds test
-        for (uint32_t i = 0; i < g.nNodes; ++i) {
-            if ((nd[i].countAxis & 3u) == 3u) continue;
-            const uint32_t c[2] = {i + 1u, (uint32_t)nd[i].offset};
-            fill(pairs[(size_t)ref[i]], c[0], c[1], nd[i].countAxis & 3u);
-        }
-        // The leaf-exact walk of plain renders (wide_bvh.h): four-wide records over the same leaves, for scenes without object instances.
-        // A leaf that holds exactly one triangle needs no stored box: Triangle::WorldBound is the min / max of its vertices
-        // (shapes/triangle.cpp:180-186) — provided that is, bit for bit, what the node holds (a zero of either sign among the
-        // coordinates would make the minimum's sign a matter of operand order: such leaves read their box like the others).
-        if (wideOk && totalPrims < (1u << 28)) {
-            std::vector<int32_t> leafRefW(g.nNodes, WIDE_NONE);
-            if (leafBox.empty()) leafBox.assign(2 * (size_t)totalPrims, make_float4(0.f, 0.f, 0.f, 0.f));
-            for (uint32_t i = 0; i < g.nNodes; ++i) {
-                if ((nd[i].countAxis & 3u) != 3u) continue;
-                const uint32_t firstPrim = primBase[ai] + (uint32_t)nd[i].offset, count = nd[i].countAxis >> 2;
-                bool single = count == 1u && (f2u(tris[3 * (size_t)firstPrim].w) & TAG_KIND_MASK) == 0u;
-                if (single) {
-                    const float4 *v = &tris[3 * (size_t)firstPrim];
-                    const float c[3][3] = {{v[0].x, v[1].x, v[2].x}, {v[0].y, v[1].y, v[2].y}, {v[0].z, v[1].z, v[2].z}};
-                    for (int a = 0; a < 3 && single; ++a) {
-                        bool posZero = false, negZero = false;
-                        for (int k = 0; k < 3; ++k) { if (c[a][k] != c[a][k]) single = false; if (c[a][k] == 0.f) { if (f2u(c[a][k]) >> 31) negZero = true; else posZero = true; } }
-                        const float mn = std::min(std::min(c[a][0], c[a][1]), c[a][2]), mx = std::max(std::max(c[a][0], c[a][1]), c[a][2]);
-                        if ((posZero && negZero) || f2u(mn) != f2u(nd[i].bmin[a]) || f2u(mx) != f2u(nd[i].bmax[a])) single = false;
-                    }
-                }
-                uint32_t r = ~firstPrim;
-                if (!single) r &= ~WIDE_LEAF_BOXED;
-                leafRefW[i] = (int32_t)r;
-                for (uint32_t k = 0; k < count; ++k) {
-                    leafBox[2 * (size_t)(firstPrim + k)] = make_float4(nd[i].bmin[0], nd[i].bmin[1], nd[i].bmin[2], nd[i].bmax[0]);
-                    leafBox[2 * (size_t)(firstPrim + k) + 1] = make_float4(nd[i].bmax[1], nd[i].bmax[2], 0.f, 0.f);
-                }
-            }
-            int need = 0;
-            wideBase[ai] = (int32_t)wide.size();
-            if (!BuildWide(nd, g.nNodes, leafRefW.data(), &wide, &need)) wideOk = false;
-            if (ai == 0) wideNeedTop = need; else wideNeedObject = std::max(wideNeedObject, need);
-        } else wideOk = false;
-    }
-    // (the wide walk's stack: LDS entries + the scene's deep-stack area; a scene that could need more keeps the binary walk)
-    if (!wideOk || wideNeedTop + (d->n_instances ? 1 + wideNeedObject : 0) > HPRT_WIDE_STACK_MAX || wideBase[0] != 0) { wide.clear(); leafBox.clear(); }
-    if (topDepth + (d->n_instances ? 1 + objectDepth : 0) > HPRT_STACK_TOTAL)
-        return SetError(HPRT_E_UNSUPPORTED, "BVH deeper than the 64-entry traversal stack (accelerators/bvh.cpp:365 reserves the same)");
-    std::vector<DevInstance> instances(d->n_instances);
-    for (uint32_t i = 0; i < d->n_instances; ++i) {
-        const HprtInstanceDesc &in = d->instances[i];
-        DevInstance &o = instances[i];
-        memcpy(o.i2w.m, in.instance_to_world, 64); memcpy(o.w2i.m, in.world_to_instance, 64);
-        const size_t ai = 1 + (size_t)in.object;
-        // more than one primitive: the object's aggregate; one: that primitive itself, without a bounds test (core/api.cpp:1798-1806)
-        o.root = aggs[ai].nPrims > 1 ? (int32_t)pairBase[ai] : ~(int32_t)primBase[ai];
-        bool ident = true;                                   // Transform::IsIdentity, core/transform.h:148-155
-        for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) if (o.i2w.m[r][c] != (r == c ? 1.f : 0.f)) ident = false;
-        o.identity = ident ? 1u : 0u; o.pad[0] = o.pad[1] = 0u;
-        // the entry into the wide records (k_walk4): the object's own tree, or its one primitive as a leaf "already reached" (no bounds test)
-        if (!wide.empty()) o.pad[0] = aggs[ai].nPrims > 1 ? (uint32_t)wideBase[ai] : ((~(uint32_t)primBase[ai]) & ~WIDE_LEAF_FIRST);
-    }
-    // Instance primitives of the top level: the transform moves next to the primitive (dev_scene.h, TAG_INST_INLINE / topEntry)
-    std::vector<float4> topEntry;
-    if (d->n_instances) {
-        topEntry.assign(aggs[0].nPrims, make_float4(0.f, 0.f, 0.f, 0.f));
-        for (uint32_t oi = 0; oi < aggs[0].nPrims; ++oi) {
-            const size_t i = (size_t)primBase[0] + oi;
-            const uint32_t tag = f2u(tris[3 * i].w);
-            if ((tag & TAG_KIND_MASK) != TAG_INSTANCE) continue;
-            const DevInstance &in = instances[f2u(tris[3 * i + 2].w)];
-            const float (*m)[4] = in.w2i.m;
-            if (!(m[3][0] == 0.f && m[3][1] == 0.f && m[3][2] == 0.f && m[3][3] == 1.f)) continue;      // projective: the kernel reads DevInstance
-            tris[3 * i] = make_float4(m[0][0], m[0][1], m[0][2], u2f(tag | TAG_INST_INLINE));
-            tris[3 * i + 1] = make_float4(m[1][0], m[1][1], m[1][2], tris[3 * i + 1].w);
-            tris[3 * i + 2] = make_float4(m[2][0], m[2][1], m[2][2], tris[3 * i + 2].w);
-            topEntry[oi] = make_float4(m[0][3], m[1][3], m[2][3], u2f((uint32_t)in.root));
-        }
-    }
-    std::vector<float4> topEntryWide;
-    if (d->n_instances && !wide.empty()) {
-        topEntryWide = topEntry;
-        for (uint32_t oi = 0; oi < aggs[0].nPrims; ++oi) {
-            const size_t i = (size_t)primBase[0] + oi;
-            const uint32_t tag = f2u(tris[3 * i].w);
-            if ((tag & TAG_KIND_MASK) == TAG_INSTANCE && (tag & TAG_INST_INLINE)) topEntryWide[oi].w = u2f(instances[f2u(tris[3 * i + 2].w)].pad[0]);
-        }
-    }
     std::vector<int32_t> primes(PrimeTable().begin(), PrimeTable().end()), primeSums(PrimeSumTable().begin(), PrimeSumTable().end());
     std::vector<uint64_t> magic(primes.size());
     for (size_t i = 0; i < primes.size(); ++i) magic[i] = 0xffffffffffffffffull / (uint64_t)primes[i] + 1ull;
     // ---- upload ----
-    HIP_TRY(upload(sc->nodes, pairs)); HIP_TRY(upload(sc->tris, tris)); HIP_TRY(upload(sc->primVtx, primVtx));
-    HIP_TRY(upload(sc->primN, primN)); HIP_TRY(upload(sc->vUV, vUV)); HIP_TRY(upload(sc->vS, vS));
-    HIP_TRY(upload(sc->shapes, shapes)); HIP_TRY(upload(sc->materials, mats)); HIP_TRY(upload(sc->lights, lights));
-    HIP_TRY(upload(sc->spheres, spheres)); HIP_TRY(upload(sc->instances, instances)); HIP_TRY(upload(sc->topEntry, topEntry)); HIP_TRY(upload(sc->topEntryWide, topEntryWide)); HIP_TRY(upload(sc->lightFunc, func)); HIP_TRY(upload(sc->lightCdf, cdf));
+    HIP_TRY(upload(sc->nodes, L.pairs)); HIP_TRY(upload(sc->tris, L.tris)); HIP_TRY(upload(sc->primVtx, L.primVtx));
+    HIP_TRY(upload(sc->primN, L.primN)); HIP_TRY(upload(sc->vUV, L.vUV)); HIP_TRY(upload(sc->vS, L.vS));
+    HIP_TRY(upload(sc->shapes, L.shapes)); HIP_TRY(upload(sc->materials, L.materials)); HIP_TRY(upload(sc->lights, L.lights));
+    HIP_TRY(upload(sc->spheres, L.spheres)); HIP_TRY(upload(sc->instances, L.instances)); HIP_TRY(upload(sc->topEntry, L.topEntry));
+    HIP_TRY(upload(sc->topEntryWide, L.topEntryWide)); HIP_TRY(upload(sc->lightFunc, L.lightFunc)); HIP_TRY(upload(sc->lightCdf, L.lightCdf));
     HIP_TRY(upload(sc->perms, perms)); HIP_TRY(upload(sc->primes, primes)); HIP_TRY(upload(sc->primeSums, primeSums));
     HIP_TRY(upload(sc->primeMagic, magic));
-    HIP_TRY(upload(sc->textures, textures)); HIP_TRY(upload(sc->mipLevels, mipLevels)); HIP_TRY(upload(sc->texels, texels)); HIP_TRY(upload(sc->weightLut, weightLut));
-    HIP_TRY(upload(sc->wide, wide)); HIP_TRY(upload(sc->leafBox, leafBox));
+    HIP_TRY(upload(sc->textures, L.textures)); HIP_TRY(upload(sc->mipLevels, L.mipLevels)); HIP_TRY(upload(sc->texels, L.texels)); HIP_TRY(upload(sc->weightLut, L.weightLut));
+    HIP_TRY(upload(sc->wide, L.wide)); HIP_TRY(upload(sc->leafBox, L.leafBox));
+    HIP_TRY(upload(sc->envLights, L.envLights)); HIP_TRY(upload(sc->envData, L.envData));
     HIP_TRY(sc->counters.alloc(sizeof(DevCounters)));
     HIP_TRY(hipMemset(sc->counters.p, 0, sizeof(DevCounters)));
     HIP_TRY(sc->deepStack.alloc((size_t)HPRT_SPILL_STACK * HPRT_DEEP_THREADS * sizeof(uint2)));
     HIP_TRY(sc->workCounter.alloc(256));
     DevScene &dv = sc->dev;
-    dv.pairs = sc->nodes.as<DevPair>(); dv.nPairs = (uint32_t)pairs.size();
-    dv.wide = wide.empty() ? nullptr : sc->wide.as<DevWide>(); dv.nWide = (uint32_t)wide.size(); dv.leafBox = sc->leafBox.as<float4>();
-    dv.tris = sc->tris.as<float4>(); dv.nPrims = totalPrims;
+    dv.pairs = sc->nodes.as<DevPair>(); dv.nPairs = (uint32_t)L.pairs.size();
+    dv.wide = L.wide.empty() ? nullptr : sc->wide.as<DevWide>(); dv.nWide = (uint32_t)L.wide.size(); dv.leafBox = sc->leafBox.as<float4>();
+    dv.tris = sc->tris.as<float4>(); dv.nPrims = L.nPrims;
     dv.primVtx = sc->primVtx.as<uint32_t>();
     dv.primN = sc->primN.as<float4>(); dv.vUV = sc->vUV.as<float>(); dv.vS = sc->vS.as<float>();
     dv.shapes = sc->shapes.as<DevShape>(); dv.nShapes = d->n_shapes;
     dv.materials = sc->materials.as<DevMaterial>();
     dv.lights = sc->lights.as<DevLight>(); dv.nLights = d->n_lights;
-    dv.spheres = sc->spheres.as<DevSphere>(); dv.nSpheres = (uint32_t)spheres.size();
-    HIP_TRY(upload(sc->envLights, envLights)); HIP_TRY(upload(sc->envData, envData));
-    dv.envLights = sc->envLights.as<DevEnvLight>(); dv.envData = sc->envData.as<float>(); dv.nEnvLights = (uint32_t)envLights.size();
+    dv.spheres = sc->spheres.as<DevSphere>(); dv.nSpheres = (uint32_t)L.spheres.size();
+    dv.envLights = sc->envLights.as<DevEnvLight>(); dv.envData = sc->envData.as<float>(); dv.nEnvLights = (uint32_t)L.envLights.size();
     dv.textures = d->n_textures ? sc->textures.as<DevTexture>() : nullptr; dv.mipLevels = sc->mipLevels.as<DevMipLevel>();
     dv.texels = sc->texels.as<float>(); dv.weightLut = sc->weightLut.as<float>();
     dv.instances = sc->instances.as<DevInstance>(); dv.nInstances = d->n_instances;
-    dv.topEntry = topEntry.empty() ? nullptr : sc->topEntry.as<float4>(); dv.nTopPrims = (uint32_t)topEntry.size();
-    dv.topEntryWide = topEntryWide.empty() ? nullptr : sc->topEntryWide.as<float4>();
-    dv.lightFunc = sc->lightFunc.as<float>(); dv.lightCdf = sc->lightCdf.as<float>(); dv.lightFuncInt = funcInt;
+    dv.topEntry = L.topEntry.empty() ? nullptr : sc->topEntry.as<float4>(); dv.nTopPrims = (uint32_t)L.topEntry.size();
+    dv.topEntryWide = L.topEntryWide.empty() ? nullptr : sc->topEntryWide.as<float4>();
+    dv.lightFunc = sc->lightFunc.as<float>(); dv.lightCdf = sc->lightCdf.as<float>(); dv.lightFuncInt = L.funcInt;
     dv.deepStack = sc->deepStack.as<uint2>();
     dv.perms = sc->perms.as<uint16_t>(); dv.primes = sc->primes.as<int32_t>(); dv.primeSums = sc->primeSums.as<int32_t>();
     dv.primeMagic = sc->primeMagic.as<uint64_t>();
-    dv.worldRadius = worldRadius;
-    dv.spatial = 0; dv.voxN[0] = dv.voxN[1] = dv.voxN[2] = 1; dv.voxFunc = dv.voxCdf = dv.voxFuncInt = nullptr;
+    dv.worldRadius = L.worldRadius;
+    dv.spatial = 0; dv.voxFunc = dv.voxCdf = dv.voxFuncInt = nullptr;
     dv.voxSlot = nullptr; dv.voxRequest = nullptr; dv.voxRequestCount = nullptr;
-    for (int a = 0; a < 3; ++a) { dv.wbMin[a] = wbLo.get(a); dv.wbMax[a] = wbHi.get(a); }
-    if (lightStrategy == 2) {
-        // SpatialLightDistribution (core/lightdistrib.cpp:95-120, maxVoxels = 64): the voxel grid over the world bound.  The reference
+    for (int a = 0; a < 3; ++a) { dv.voxN[a] = L.voxN[a]; dv.wbMin[a] = L.wbMin[a]; dv.wbMax[a] = L.wbMax[a]; }
+    if (L.lightStrategy == 2) {
+        // SpatialLightDistribution (core/lightdistrib.cpp:95-120, maxVoxels = 64) over the voxel grid of the layout.  The reference
         // fills a voxel's distribution when a vertex first falls into it; a voxel's distribution being a pure function of the voxel,
         // here every voxel is computed now, on the device (k_voxel_contrib / k_voxel_dist).
-        const vec3 diag = wbHi - wbLo;
-        const int me = (diag.x > diag.y && diag.x > diag.z) ? 0 : (diag.y > diag.z ? 1 : 2);      // Bounds3::MaximumExtent
-        const float bmax = diag.get(me);
-        uint64_t nVox = 1;
-        for (int a = 0; a < 3; ++a) { dv.voxN[a] = std::max(1, int(std::round(diag.get(a) / bmax * 64))); nVox *= (uint64_t)dv.voxN[a]; }
+        const uint64_t nVox = (uint64_t)dv.voxN[0] * (uint64_t)dv.voxN[1] * (uint64_t)dv.voxN[2];
         // The table of every voxel (2 * nLights + 2 floats each) is computed now when it is small: a lookup is then a plain read.  With
         // many lights (every triangle of an emissive mesh is one, core/api.cpp:1609-1636) it is not — 64^3 voxels x 500 lights is
         // already 1 GiB — and the reference never builds it either: it fills a voxel when a vertex first falls into it
@@ -789,11 +244,10 @@ int hprt_scene_create(const HprtSceneDesc *d, int device, HprtScene **out) try {
         HIP_TRY(hipDeviceSynchronize());
     }
     HIP_TRY(hipHostMalloc((void **)&sc->hostCounts, (4096 + 256) * sizeof(uint32_t)));
-    *out = guard.release();
+    *out = sc.release();
     return HPRT_OK;
 } catch (...) { return hprt::HandleException(); }
 
-// Diagnostics hook (not part of include/hprt.h): the 128 sample points of a voxel, RadicalInverse(0..4, i) as [5][128]
 // Diagnostics hook (not part of include/hprt.h): 1 when plain renders of this scene take the leaf-exact wide walk (k_walk4), else 0: the
 // binary walk, or the kd walk once a kd-tree is attached (callers test the value for truth: "is it k_walk4")
 __attribute__((visibility("default"))) int hprt_debug_scene_walk(HprtScene *s) { return s && !s->kdAttached && hprt::WideWalkInUse(s->dev) ? 1 : 0; }
@@ -903,7 +357,6 @@ __attribute__((visibility("default"))) int hprt_debug_gather_probe(int device, i
     *best_grecords_s = best; *mean_grecords_s = sum / launches;
     return HPRT_OK;
 } catch (...) { return hprt::HandleException(); }
-__attribute__((visibility("default"))) int hprt_debug_voxel_points(float out[640]) { if (!out) return HPRT_E_INVALID; VoxelSamplePoints(out); return HPRT_OK; }
 
 // Diagnostics hook (not part of include/hprt.h): the restated libm functions of hprt_math.h evaluated ON THE DEVICE over host
 // arrays, so that a test can hold them against the oracle's (which equal glibc's, tests/test_oracle_pins.py) directly rather
@@ -940,88 +393,6 @@ __attribute__((visibility("default"))) int hprt_debug_device_math(int device, in
     release();
     if (e != hipSuccess) return SetError(HPRT_E_DEVICE, std::string("hprt_debug_device_math: ") + hipGetErrorString(e));
     return HPRT_OK;
-} catch (...) { return hprt::HandleException(); }
-
-int hprt_scene_create_from_model(const HprtModel *m, const HprtBvh *b, int device, HprtScene **out) try {
-    if (!m || !b || !out) return SetError(HPRT_E_INVALID, "hprt_scene_create_from_model: null argument");
-    const SceneModel &sm = m->sc;
-    std::vector<HprtShapeDesc> shapes(sm.shapes.size());
-    for (size_t i = 0; i < sm.shapes.size(); ++i) {
-        const ShapeDesc &s = sm.shapes[i];
-        HprtShapeDesc &o = shapes[i];
-        memset(&o, 0, sizeof(o));
-        o.kind = s.kind; o.material = s.material; o.area_light = s.areaLight;
-        o.reverse_orientation = s.reverseOrientation; o.transform_swaps_handedness = s.transformSwapsHandedness;
-        if (s.kind == kTriangleMesh) {
-            o.n_tris = s.mesh.nTris(); o.n_verts = s.mesh.nVerts();
-            o.indices = s.mesh.indices.data(); o.P = s.mesh.P.data();
-            o.N = s.mesh.N.empty() ? nullptr : s.mesh.N.data();
-            o.UV = s.mesh.UV.empty() ? nullptr : s.mesh.UV.data();
-            o.S = s.mesh.S.empty() ? nullptr : s.mesh.S.data();
-        } else {
-            memcpy(o.object_to_world, s.sphere.objectToWorld.m, 64); memcpy(o.world_to_object, s.sphere.worldToObject.m, 64);
-            o.radius = s.sphere.radius; o.z_min = s.sphere.zMin; o.z_max = s.sphere.zMax;
-            o.theta_min = s.sphere.thetaMin; o.theta_max = s.sphere.thetaMax; o.phi_max = s.sphere.phiMax;
-        }
-    }
-    std::vector<HprtMaterialDesc> mats(sm.materials.size());
-    for (size_t i = 0; i < mats.size(); ++i) {
-        const MaterialDesc &s = sm.materials[i];
-        mats[i].type = s.type; memcpy(mats[i].Kd, s.Kd, 12); mats[i].sigma = s.sigma; memcpy(mats[i].Ks, s.Ks, 12);
-        mats[i].roughness = s.roughness; mats[i].remap_roughness = s.remapRoughness;
-        mats[i].kd_texture = s.KdTex; mats[i].ks_texture = s.KsTex; mats[i].opacity_texture = s.opacityTex;
-        memcpy(mats[i].Kr, s.Kr, 12); memcpy(mats[i].Kt, s.Kt, 12); memcpy(mats[i].opacity, s.opacity, 12); mats[i].eta = s.eta;
-    }
-    std::vector<std::vector<HprtTextureLevel>> texLevels(sm.textures.size());
-    std::vector<HprtTextureDesc> textures(sm.textures.size());
-    for (size_t i = 0; i < textures.size(); ++i) {
-        const TextureDesc &t = sm.textures[i];
-        for (const MipLevel &l : t.levels) texLevels[i].push_back(HprtTextureLevel{l.w, l.h, l.rgb.data()});
-        textures[i].levels = texLevels[i].data(); textures[i].n_levels = (uint32_t)texLevels[i].size();
-        textures[i].trilinear = t.trilinear; textures[i].max_anisotropy = t.maxAniso; textures[i].wrap = t.wrap;
-        textures[i].su = t.su; textures[i].sv = t.sv; textures[i].du = t.du; textures[i].dv = t.dv; textures[i].weight_lut = t.weightLut;
-    }
-    std::vector<HprtLightDesc> lights(sm.lights.size());
-    for (size_t i = 0; i < lights.size(); ++i) {
-        const LightDesc &s = sm.lights[i];
-        lights[i].type = s.type; memcpy(lights[i].pos, s.pos, 12); memcpy(lights[i].I, s.I, 12); lights[i].shape = s.shape; lights[i].two_sided = s.twoSided;
-        lights[i].texture = s.texture; memcpy(lights[i].light_to_world, &s.lightToWorld, 64); memcpy(lights[i].world_to_light, &s.worldToLight, 64);
-    }
-    if (b->objects.size() != sm.nObjects) return SetError(HPRT_E_INVALID, "the BVH was built for another model (object count differs)");
-    // object definitions: their shapes are contiguous (no nesting of definitions, core/api.cpp:1755-1756)
-    std::vector<HprtObjectDesc> objects(sm.nObjects);
-    for (uint32_t k = 0; k < sm.nObjects; ++k) {
-        HprtObjectDesc &o = objects[k];
-        memset(&o, 0, sizeof(o));
-        bool any = false;
-        for (size_t i = 0; i < sm.shapes.size(); ++i)
-            if (sm.shapes[i].object == (int32_t)k) { if (!any) { o.first_shape = (uint32_t)i; any = true; } o.n_shapes = (uint32_t)i + 1u - o.first_shape; }
-        const BvhTree &t = b->objects[k];
-        o.nodes = t.nodes.data(); o.n_nodes = (uint32_t)t.nodes.size(); o.prim_order = t.primOrder.data(); o.n_prims = (uint32_t)t.primOrder.size();
-    }
-    std::vector<HprtInstanceDesc> instances(sm.instances.size());
-    for (size_t i = 0; i < instances.size(); ++i) {
-        instances[i].object = sm.instances[i].object;
-        memcpy(instances[i].instance_to_world, sm.instances[i].instanceToWorld.m, 64);
-        memcpy(instances[i].world_to_instance, sm.instances[i].worldToInstance.m, 64);
-    }
-    std::vector<HprtTopItem> top(sm.top.size());
-    for (size_t i = 0; i < top.size(); ++i) { top[i].kind = sm.top[i].kind; top[i].index = sm.top[i].index; }
-    HprtSceneDesc d;
-    memset(&d, 0, sizeof(d));
-    d.textures = textures.data(); d.n_textures = (uint32_t)textures.size();
-    d.objects = objects.data(); d.n_objects = (uint32_t)objects.size();
-    d.instances = instances.data(); d.n_instances = (uint32_t)instances.size();
-    static const HprtTopItem kNoItems[1] = {{0, 0u}};
-    d.top = top.empty() ? kNoItems : top.data(); d.n_top = (uint32_t)top.size();
-    d.nodes = b->tree.nodes.data(); d.n_nodes = (uint32_t)b->tree.nodes.size();
-    d.prim_order = b->tree.primOrder.data(); d.n_prims = (uint32_t)b->tree.primOrder.size();
-    d.shapes = shapes.data(); d.n_shapes = (uint32_t)shapes.size();
-    d.materials = mats.data(); d.n_materials = (uint32_t)mats.size();
-    d.lights = lights.data(); d.n_lights = (uint32_t)lights.size();
-    // a single light always gets the uniform distribution (core/lightdistrib.cpp:50-52)
-    d.light_strategy = sm.lights.size() <= 1 ? 0 : sm.opt.lightStrategy;
-    return hprt_scene_create(&d, device, out);
 } catch (...) { return hprt::HandleException(); }
 
 // MakeAccelerator("kdtree") (core/api.cpp:790-830): the tree is checked, its creation-order primitive numbers are mapped to the

@@ -1,6 +1,6 @@
 // hprt — host half of the C ABI (include/hprt.h): scene front-end, baked scenes,
-// BVH build, Halton tables, film resolve, PFM writer.  No HIP calls here; the
-// device half lives in capi_device.hip.
+// BVH build, model -> scene description, Halton tables, film resolve, PFM writer.
+// No HIP calls here; the device half lives in capi_device.hip.
 #include <algorithm>
 #include <new>
 #include <stdexcept>
@@ -258,6 +258,89 @@ int hprt_halton_permutations(uint16_t *out, size_t max_entries, size_t *n_entrie
     return HPRT_OK;
 } catch (...) { return hprt::HandleException(); }
 
+// hprt_scene_create over a parsed model and its BVH: the model's records as an HprtSceneDesc of borrowed pointers
+int hprt_scene_create_from_model(const HprtModel *m, const HprtBvh *b, int device, HprtScene **out) try {
+    if (!m || !b || !out) return SetError(HPRT_E_INVALID, "hprt_scene_create_from_model: null argument");
+    const SceneModel &sm = m->sc;
+    std::vector<HprtShapeDesc> shapes(sm.shapes.size());
+    for (size_t i = 0; i < sm.shapes.size(); ++i) {
+        const ShapeDesc &s = sm.shapes[i];
+        HprtShapeDesc &o = shapes[i];
+        memset(&o, 0, sizeof(o));
+        o.kind = s.kind; o.material = s.material; o.area_light = s.areaLight;
+        o.reverse_orientation = s.reverseOrientation; o.transform_swaps_handedness = s.transformSwapsHandedness;
+        if (s.kind == kTriangleMesh) {
+            o.n_tris = s.mesh.nTris(); o.n_verts = s.mesh.nVerts();
+            o.indices = s.mesh.indices.data(); o.P = s.mesh.P.data();
+            o.N = s.mesh.N.empty() ? nullptr : s.mesh.N.data();
+            o.UV = s.mesh.UV.empty() ? nullptr : s.mesh.UV.data();
+            o.S = s.mesh.S.empty() ? nullptr : s.mesh.S.data();
+        } else {
+            memcpy(o.object_to_world, s.sphere.objectToWorld.m, 64); memcpy(o.world_to_object, s.sphere.worldToObject.m, 64);
+            o.radius = s.sphere.radius; o.z_min = s.sphere.zMin; o.z_max = s.sphere.zMax;
+            o.theta_min = s.sphere.thetaMin; o.theta_max = s.sphere.thetaMax; o.phi_max = s.sphere.phiMax;
+        }
+    }
+    std::vector<HprtMaterialDesc> mats(sm.materials.size());
+    for (size_t i = 0; i < mats.size(); ++i) {
+        const MaterialDesc &s = sm.materials[i];
+        mats[i].type = s.type; memcpy(mats[i].Kd, s.Kd, 12); mats[i].sigma = s.sigma; memcpy(mats[i].Ks, s.Ks, 12);
+        mats[i].roughness = s.roughness; mats[i].remap_roughness = s.remapRoughness;
+        mats[i].kd_texture = s.KdTex; mats[i].ks_texture = s.KsTex; mats[i].opacity_texture = s.opacityTex;
+        memcpy(mats[i].Kr, s.Kr, 12); memcpy(mats[i].Kt, s.Kt, 12); memcpy(mats[i].opacity, s.opacity, 12); mats[i].eta = s.eta;
+    }
+    std::vector<std::vector<HprtTextureLevel>> texLevels(sm.textures.size());
+    std::vector<HprtTextureDesc> textures(sm.textures.size());
+    for (size_t i = 0; i < textures.size(); ++i) {
+        const TextureDesc &t = sm.textures[i];
+        for (const MipLevel &l : t.levels) texLevels[i].push_back(HprtTextureLevel{l.w, l.h, l.rgb.data()});
+        textures[i].levels = texLevels[i].data(); textures[i].n_levels = (uint32_t)texLevels[i].size();
+        textures[i].trilinear = t.trilinear; textures[i].max_anisotropy = t.maxAniso; textures[i].wrap = t.wrap;
+        textures[i].su = t.su; textures[i].sv = t.sv; textures[i].du = t.du; textures[i].dv = t.dv; textures[i].weight_lut = t.weightLut;
+    }
+    std::vector<HprtLightDesc> lights(sm.lights.size());
+    for (size_t i = 0; i < lights.size(); ++i) {
+        const LightDesc &s = sm.lights[i];
+        lights[i].type = s.type; memcpy(lights[i].pos, s.pos, 12); memcpy(lights[i].I, s.I, 12); lights[i].shape = s.shape; lights[i].two_sided = s.twoSided;
+        lights[i].texture = s.texture; memcpy(lights[i].light_to_world, &s.lightToWorld, 64); memcpy(lights[i].world_to_light, &s.worldToLight, 64);
+    }
+    if (b->objects.size() != sm.nObjects) return SetError(HPRT_E_INVALID, "the BVH was built for another model (object count differs)");
+    // object definitions: their shapes are contiguous (no nesting of definitions, core/api.cpp:1755-1756)
+    std::vector<HprtObjectDesc> objects(sm.nObjects);
+    for (uint32_t k = 0; k < sm.nObjects; ++k) {
+        HprtObjectDesc &o = objects[k];
+        memset(&o, 0, sizeof(o));
+        bool any = false;
+        for (size_t i = 0; i < sm.shapes.size(); ++i)
+            if (sm.shapes[i].object == (int32_t)k) { if (!any) { o.first_shape = (uint32_t)i; any = true; } o.n_shapes = (uint32_t)i + 1u - o.first_shape; }
+        const BvhTree &t = b->objects[k];
+        o.nodes = t.nodes.data(); o.n_nodes = (uint32_t)t.nodes.size(); o.prim_order = t.primOrder.data(); o.n_prims = (uint32_t)t.primOrder.size();
+    }
+    std::vector<HprtInstanceDesc> instances(sm.instances.size());
+    for (size_t i = 0; i < instances.size(); ++i) {
+        instances[i].object = sm.instances[i].object;
+        memcpy(instances[i].instance_to_world, sm.instances[i].instanceToWorld.m, 64);
+        memcpy(instances[i].world_to_instance, sm.instances[i].worldToInstance.m, 64);
+    }
+    std::vector<HprtTopItem> top(sm.top.size());
+    for (size_t i = 0; i < top.size(); ++i) { top[i].kind = sm.top[i].kind; top[i].index = sm.top[i].index; }
+    HprtSceneDesc d;
+    memset(&d, 0, sizeof(d));
+    d.textures = textures.data(); d.n_textures = (uint32_t)textures.size();
+    d.objects = objects.data(); d.n_objects = (uint32_t)objects.size();
+    d.instances = instances.data(); d.n_instances = (uint32_t)instances.size();
+    static const HprtTopItem kNoItems[1] = {{0, 0u}};
+    d.top = top.empty() ? kNoItems : top.data(); d.n_top = (uint32_t)top.size();
+    d.nodes = b->tree.nodes.data(); d.n_nodes = (uint32_t)b->tree.nodes.size();
+    d.prim_order = b->tree.primOrder.data(); d.n_prims = (uint32_t)b->tree.primOrder.size();
+    d.shapes = shapes.data(); d.n_shapes = (uint32_t)shapes.size();
+    d.materials = mats.data(); d.n_materials = (uint32_t)mats.size();
+    d.lights = lights.data(); d.n_lights = (uint32_t)lights.size();
+    // a single light always gets the uniform distribution (core/lightdistrib.cpp:50-52)
+    d.light_strategy = sm.lights.size() <= 1 ? 0 : sm.opt.lightStrategy;
+    return hprt_scene_create(&d, device, out);
+} catch (...) { return hprt::HandleException(); }
+
 // Film::WriteImage, core/film.cpp:266-303 (no splats)
 int hprt_film_resolve(const float *xyzw, size_t n, float scale, float *rgb) try {
     if (!xyzw || !rgb) return SetError(HPRT_E_INVALID, "hprt_film_resolve: null argument");
@@ -394,10 +477,13 @@ __attribute__((visibility("default"))) int hprt_debug_host_selftest(int failures
 // Diagnostics hook (not part of include/hprt.h; tests/test_wide_walk.py): the four-wide records BuildWide (wide_bvh.h) makes of a
 // linear node array.  Every leaf gets the "boxed" reference ~firstPrimitive & ~WIDE_LEAF_BOXED (the single-triangle shortcut is
 // decided at scene creation, where the vertices are).  out64: cap records of 64 bytes; *n_out: records made; *stack_need: the
-// deepest stack a walk can hold.  HPRT_E_UNSUPPORTED when the tree keeps the binary walk (non-finite box, extent beyond the grid).
+// deepest stack a walk can hold.  HPRT_E_INVALID for a malformed array (CheckBvhNodes); HPRT_E_UNSUPPORTED when the tree keeps the
+// binary walk (non-finite box, extent beyond the grid).
 __attribute__((visibility("default"))) int hprt_debug_wide_build(const void *nodes32, uint32_t n_nodes, void *out64, size_t cap, size_t *n_out, int *stack_need) try {
     if (!nodes32 || !n_out || !stack_need) return SetError(HPRT_E_INVALID, "hprt_debug_wide_build: null argument");
     const BvhNode *nd = (const BvhNode *)nodes32;
+    const char *bad = CheckBvhNodes(nd, n_nodes, UINT32_MAX, nullptr);      // (no primitive count here: leaf ranges are not checked)
+    if (*bad) return SetError(HPRT_E_INVALID, std::string("hprt_debug_wide_build: ") + bad);
     std::vector<int32_t> leafRef(n_nodes, WIDE_NONE);
     for (uint32_t i = 0; i < n_nodes; ++i)
         if ((nd[i].countAxis & 3u) == 3u) leafRef[i] = (int32_t)(~(uint32_t)nd[i].offset & ~WIDE_LEAF_BOXED);
