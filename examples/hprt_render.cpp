@@ -78,6 +78,23 @@ int main(int argc, char **argv) {
             return 1;
         }
     }
+    // Accelerator "rbsp" (core/api.cpp:817-831): the same with an RBSP tree built from the scene's Accelerator parameters.  What
+    // the library does not walk (object instances, an unsupported "nbDirections", a tree deeper than the todo list) keeps the BVH
+    if (std::strcmp(accel, "rbsp") == 0) {
+        HprtRbsp *rb = nullptr;
+        const int rc = hprt_rbsp_build(model, nullptr, &rb);
+        if (rc == HPRT_OK) {
+            int arc = HPRT_OK;
+            for (int g = 0; g < gpus && arc == HPRT_OK; ++g) arc = hprt_scene_attach_rbsp(scenes[(size_t)g], rb);
+            hprt_rbsp_destroy(rb);
+            if (arc != HPRT_OK) { std::fprintf(stderr, "hprt_scene_attach_rbsp failed (%d): %s\n", arc, hprt_last_error()); return 1; }
+        } else if (rc == HPRT_E_UNSUPPORTED) {
+            std::fprintf(stderr, "Warning: %s; \"bvh\" used\n", hprt_last_error());
+        } else {
+            std::fprintf(stderr, "hprt_rbsp_build failed (%d): %s\n", rc, hprt_last_error());
+            return 1;
+        }
+    }
     // one host thread per GPU (the renders are independent; errors are thread-local in the library, so each thread keeps its own)
     std::vector<HprtRenderStats> stats((size_t)gpus);
     std::vector<int> rcs((size_t)gpus, HPRT_OK);

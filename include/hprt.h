@@ -146,6 +146,40 @@ int hprt_kdtree_copy(const HprtKdTree *t, void *nodes8, uint32_t *prim_indices);
 void hprt_kdtree_destroy(HprtKdTree *t);
 
 /* ------------------------------------------------------------------------ */
+/* RBSP tree (Accelerator "rbsp").  Stands in for RBSP::buildTree           */
+/* (accelerators/rbsp.cpp:181-403): a kd-tree whose split planes may also   */
+/* be oblique, chosen from M = 3, 7, 9 or 13 fixed directions, with the     */
+/* node's k-DOP as the surface of the cost model.  Byte-identical to the    */
+/* reference: 8-byte RBSPNode[] (word 0 split / onePrimitive /              */
+/* primitiveIndicesOffset; word 1 flags: leaf M | nPrims << off, interior   */
+/* axis | aboveChild << off, off = 32 - clz(M)), primitiveIndices and the   */
+/* direction table.  splitalpha, alphatype, axisselectiontype and           */
+/* axisselectionamount are never read by buildTree and are ignored.         */
+/* ------------------------------------------------------------------------ */
+typedef struct HprtRbsp HprtRbsp;
+typedef struct HprtRbspParams {
+    int isect_cost;     /* "intersectcost", default 80 */
+    int trav_cost;      /* "traversalcost", default 5 */
+    float empty_bonus;  /* "emptybonus", default 0 */
+    int max_prims;      /* "maxprims", default 1 */
+    int max_depth;      /* "maxdepth", default -1 = round(2 + 1.6 Log2Int(N)) */
+    int n_directions;   /* "nbDirections": 3 (default), 7, 9 or 13; anything else is HPRT_E_UNSUPPORTED */
+    int threads;        /* builder threads (0: OMP_NUM_THREADS, else 16; at most 16); the tree does not depend on it */
+} HprtRbspParams;
+/* params NULL: the scene's Accelerator line (baked models report "bvh" and get the defaults).  Models with object
+ * instances: HPRT_E_UNSUPPORTED (no two-level RBSP walk).  A tree deeper than HPRT_RBSP_MAX_DEPTH: HPRT_E_UNSUPPORTED. */
+int hprt_rbsp_build(const HprtModel *m, const HprtRbspParams *params, HprtRbsp **out);
+/* The same over n triangles (9 floats each: three world-space vertices, creation order); params NULL: the defaults. */
+int hprt_rbsp_build_from_triangles(size_t n_tris, const float *p9, const HprtRbspParams *params, HprtRbsp **out);
+/* info[0..4] = nodes, leaves, primitive references (primitiveIndices entries), depth (interior levels of the deepest
+ * path), M (directions) */
+int hprt_rbsp_info(const HprtRbsp *t, uint32_t info[5]);
+#define HPRT_RBSP_MAX_DEPTH 64     /* the device walk's todo capacity: pbrt's maxTodo (rbsp.cpp:416) */
+/* nodes8: info[0] * 8 bytes; prim_indices: info[2] uint32; directions: 3 * M floats (any may be NULL) */
+int hprt_rbsp_copy(const HprtRbsp *t, void *nodes8, uint32_t *prim_indices, float *directions);
+void hprt_rbsp_destroy(HprtRbsp *t);
+
+/* ------------------------------------------------------------------------ */
 /* Device scene.  Upload step that follows the BVH build: stands in for the  */
 /* `primitives`/`nodes` members BVHAccel keeps (accelerators/bvh.h:69-79) and */
 /* the Scene object (core/scene.h:50-80).  The library copies everything to   */
@@ -261,6 +295,11 @@ void hprt_scene_destroy(HprtScene *s);
  * nodes), [2] triangle tests, [3] sphere tests; HprtRenderStats::nodes_fetched[_p] / nodes_entered[_p] carry [0] / [1],
  * and HPRT_RENDER_PIXEL_STATS slots 5 / 6 hold kdTreeNodeTraversals[P] (write them with hprt_write_pixel_stats_accel). */
 int hprt_scene_attach_kdtree(HprtScene *s, const HprtKdTree *t);
+/* The same for an RBSP tree (RBSP::Intersect / IntersectP, accelerators/rbsp.cpp:405-547).  Attaching either tree
+ * replaces whichever tree was attached before.  Counters of an RBSP scene: [0] nbNodeTraversals, [1]
+ * bspTreeNodeTraversals (interior nodes), [2] triangle tests, [3] sphere tests; HPRT_RENDER_PIXEL_STATS slots 5 / 6 hold
+ * bspTreeNodeTraversals[P] (hprt_write_pixel_stats_accel with HPRT_ACCEL_RBSP). */
+int hprt_scene_attach_rbsp(HprtScene *s, const HprtRbsp *t);
 
 /* ------------------------------------------------------------------------ */
 /* Batched Aggregate interface.  Stand in for                                */
@@ -373,6 +412,7 @@ int hprt_write_pixel_stats(const char *prefix, const uint64_t *stats7, int width
  * BSP matrices stay zero). */
 #define HPRT_ACCEL_BVH 0
 #define HPRT_ACCEL_KDTREE 1
+#define HPRT_ACCEL_RBSP 2          /* slots 5 / 6 go to -bspTreeNodeTraversals[P].txt (core/film.cpp:176-177) */
 int hprt_write_pixel_stats_accel(const char *prefix, const uint64_t *stats7, int width, int height, int accel);
 /* Film::WriteImage arithmetic (core/film.cpp:266-303) on a host copy of a film
  * state: rgb_out = 3*W*H floats, top row first. */

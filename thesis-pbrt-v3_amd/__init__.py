@@ -6,6 +6,7 @@ accelerates:
     Model   <- pbrtParseFile / api.cpp state          (core/parser.cpp, core/api.cpp)
     Bvh     <- CreateBVHAccelerator / BVHAccel ctor   (accelerators/bvh.cpp:155-185,529-535)
     KdTree  <- CreateKdTreeAccelerator / buildTree    (accelerators/kdtreeaccel.cpp:212-380,523-545)
+    Rbsp    <- CreateRBSPTreeAccelerator / buildTree  (accelerators/rbsp.cpp:181-403,549-571)
     Scene   <- Scene + BVHAccel::Intersect/IntersectP (accelerators/bvh.cpp:354-437)
                and SamplerIntegrator::Render with PathIntegrator::Li
                (core/integrator.cpp:230-360, integrators/path.cpp:64-204)
@@ -35,8 +36,9 @@ RENDER_PIXEL_STATS = 2
 RENDER_COUNT_TRACED = 4
 RENDER_TRACE_ALL = 8
 RENDER_EXPORT_FOREIGN = 16
-ACCEL_BVH, ACCEL_KDTREE = 0, 1
+ACCEL_BVH, ACCEL_KDTREE, ACCEL_RBSP = 0, 1, 2
 KD_MAX_DEPTH = 64        # HPRT_KD_MAX_DEPTH: the kd walk's todo capacity
+RBSP_MAX_DEPTH = 64      # HPRT_RBSP_MAX_DEPTH: the RBSP walk's todo capacity
 COMM_ID_BYTES = 128
 # HprtFilmRecord: one cross-tile film contribution (include/hprt.h)
 FILM_RECORD = np.dtype([("dest_pixel", np.uint32), ("src_tile", np.uint32), ("xyz", np.float32, 3), ("weight", np.float32)])
@@ -187,6 +189,12 @@ def _load():
         "hprt_kdtree_destroy": (None, [vp]),
         "hprt_scene_attach_kdtree": (C.c_int, [vp, vp]),
         "hprt_write_pixel_stats_accel": (C.c_int, [cp, vp, C.c_int, C.c_int, C.c_int]),
+        "hprt_rbsp_build": (C.c_int, [vp, vp, P(vp)]),
+        "hprt_rbsp_build_from_triangles": (C.c_int, [sz, vp, vp, P(vp)]),
+        "hprt_rbsp_info": (C.c_int, [vp, P(u32)]),
+        "hprt_rbsp_copy": (C.c_int, [vp, vp, vp, vp]),
+        "hprt_rbsp_destroy": (None, [vp]),
+        "hprt_scene_attach_rbsp": (C.c_int, [vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)   # raises AttributeError if an export is missing
@@ -362,6 +370,62 @@ class KdTree:
             self._h = None
 
 
+class RbspParams(C.Structure):
+    """HprtRbspParams: CreateRBSPTreeAccelerator's parameters plus the builder's thread count."""
+    _fields_ = [("isect_cost", C.c_int), ("trav_cost", C.c_int), ("empty_bonus", C.c_float), ("max_prims", C.c_int),
+                ("max_depth", C.c_int), ("n_directions", C.c_int), ("threads", C.c_int)]
+
+
+def _rbsp_params(n_directions, isect_cost, trav_cost, empty_bonus, max_prims, max_depth, threads):
+    return RbspParams(isect_cost, trav_cost, empty_bonus, max_prims, max_depth, n_directions, threads)
+
+
+class Rbsp:
+    """RBSP tree (host): CreateRBSPTreeAccelerator(prims, params) — RBSPNode[], primitiveIndices and the direction table as
+    the reference builds them.  Rbsp(model) takes the scene's Accelerator line; keyword parameters override it."""
+
+    def __init__(self, model=None, handle=None, n_directions=None, isect_cost=80, trav_cost=5, empty_bonus=0.0, max_prims=1, max_depth=-1,
+                 threads=0):
+        if handle is None:
+            handle = C.c_void_p()
+            prm = None if n_directions is None else C.byref(_rbsp_params(n_directions, isect_cost, trav_cost, empty_bonus, max_prims, max_depth, threads))
+            _check(lib.hprt_rbsp_build(model._h, prm, C.byref(handle)))
+        self._h = handle
+
+    @staticmethod
+    def from_triangles(p9, n_directions=3, isect_cost=80, trav_cost=5, empty_bonus=0.0, max_prims=1, max_depth=-1, threads=0):
+        """p9: [n, 9] (or [n, 3, 3]) float32 world-space triangle vertices in creation order."""
+        p9 = np.ascontiguousarray(p9, np.float32).reshape(-1, 9)
+        h = C.c_void_p()
+        prm = _rbsp_params(n_directions, isect_cost, trav_cost, empty_bonus, max_prims, max_depth, threads)
+        _check(lib.hprt_rbsp_build_from_triangles(p9.shape[0], _ptr(p9), C.byref(prm), C.byref(h)))
+        return Rbsp(handle=h)
+
+    def info(self):
+        i = (C.c_uint32 * 5)()
+        _check(lib.hprt_rbsp_info(self._h, i))
+        return {"nodes": i[0], "leaves": i[1], "prim_refs": i[2], "depth": i[3], "M": i[4]}
+
+    def arrays(self):
+        """(nodes [n, 2] uint32: word 0 split / onePrimitive / primitiveIndicesOffset, word 1 flags; prim_indices uint32)"""
+        inf = self.info()
+        nodes = np.zeros((inf["nodes"], 2), np.uint32)
+        idx = np.zeros(inf["prim_refs"], np.uint32)
+        _check(lib.hprt_rbsp_copy(self._h, _ptr(nodes), _ptr(idx), None))
+        return nodes, idx
+
+    def directions(self):
+        """[M, 3] float32: getDirections(M)"""
+        d = np.zeros((self.info()["M"], 3), np.float32)
+        _check(lib.hprt_rbsp_copy(self._h, None, None, _ptr(d)))
+        return d
+
+    def __del__(self):
+        if getattr(self, "_h", None) and lib is not None:      # (module globals are cleared at interpreter exit)
+            lib.hprt_rbsp_destroy(self._h)
+            self._h = None
+
+
 class Scene:
     """Device-resident scene: Aggregate (Intersect/IntersectP) + Integrator (Render)."""
 
@@ -386,6 +450,12 @@ class Scene:
         """hprt_scene_attach_kdtree: every later trace and render walks `kdtree` (built over this scene's primitives)."""
         _check(lib.hprt_scene_attach_kdtree(self._h, kdtree._h))
         self._kdtree = kdtree
+
+    def attach_rbsp(self, rbsp):
+        """hprt_scene_attach_rbsp: every later trace and render walks `rbsp` (built over this scene's primitives); replaces an
+        attached kd-tree."""
+        _check(lib.hprt_scene_attach_rbsp(self._h, rbsp._h))
+        self._rbsp = rbsp
 
     def intersect(self, o, d, tmax, count=False):
         o = np.ascontiguousarray(o, np.float32); d = np.ascontiguousarray(d, np.float32)
@@ -553,7 +623,8 @@ def write_pixel_stats(prefix, stats7):
 
 
 def write_pixel_stats_accel(prefix, stats7, accel):
-    """The same for a render of either accelerator (ACCEL_BVH, ACCEL_KDTREE: slots 5 / 6 are kdTreeNodeTraversals[P])."""
+    """The same for a render of any accelerator (ACCEL_BVH; ACCEL_KDTREE: slots 5 / 6 are kdTreeNodeTraversals[P];
+    ACCEL_RBSP: slots 5 / 6 are bspTreeNodeTraversals[P])."""
     stats7 = np.ascontiguousarray(stats7, np.uint64)
     _check(lib.hprt_write_pixel_stats_accel(prefix.encode(), _ptr(stats7), stats7.shape[1], stats7.shape[0], accel))
 

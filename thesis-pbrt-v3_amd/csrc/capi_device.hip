@@ -250,7 +250,7 @@ int hprt_scene_create(const HprtSceneDesc *d, int device, HprtScene **out) try {
 
 // Diagnostics hook (not part of include/hprt.h): 1 when plain renders of this scene take the leaf-exact wide walk (k_walk4), else 0: the
 // binary walk, or the kd walk once a kd-tree is attached (callers test the value for truth: "is it k_walk4")
-__attribute__((visibility("default"))) int hprt_debug_scene_walk(HprtScene *s) { return s && !s->kdAttached && hprt::WideWalkInUse(s->dev) ? 1 : 0; }
+__attribute__((visibility("default"))) int hprt_debug_scene_walk(HprtScene *s) { return s && !s->kdAttached && !s->rbspAttached && hprt::WideWalkInUse(s->dev) ? 1 : 0; }
 __attribute__((visibility("default"))) int hprt_debug_poison_workspace(HprtScene *s, int byte) { if (!s) return HPRT_E_INVALID; s->poisonByte = byte < 0 ? -1 : (byte & 255); return HPRT_OK; }
 // Diagnostics hook (not part of include/hprt.h): the first batch of the next hprt_render copies the rays that bounce `bounce` queues
 // (kind 0: the path segments entering bounce + 1, 1: its shadow rays, 2: its BSDF-sampled light rays) into d_out7 ([7][cap] planes:
@@ -261,11 +261,13 @@ __attribute__((visibility("default"))) int hprt_debug_capture_rays(HprtScene *s,
     return HPRT_OK;
 }
 static int ApiStreams(HprtScene *s, size_t n, RayStream *rays, HitStream *hits);
-// Every trace of a scene: the kd walk once a kd-tree is attached (hprt_scene_attach_kdtree), else the BVH walks (LaunchTrace)
+// Every trace of a scene: the kd walk once a kd-tree is attached (hprt_scene_attach_kdtree), the RBSP walk once an RBSP tree is
+// (hprt_scene_attach_rbsp), else the BVH walks (LaunchTrace)
 static void Trace(HprtScene *s, hipStream_t st, bool anyHit, bool count, const uint32_t *queue, const uint32_t *countPtr, uint32_t countImm,
                   uint32_t gridItems, const RayStream &rays, const HitStream &hits, uint8_t *occ, DevCounters *counters, uint32_t *workCounter,
                   uint4 *rayStats = nullptr) {
     if (s->kdAttached) LaunchKdTrace(st, s->dev, s->kd, anyHit, count, queue, countPtr, countImm, gridItems, rays, hits, occ, counters, workCounter, rayStats);
+    else if (s->rbspAttached) LaunchRbspTrace(st, s->dev, s->rbsp, anyHit, count, queue, countPtr, countImm, gridItems, rays, hits, occ, counters, workCounter, rayStats);
     else LaunchTrace(st, s->dev, anyHit, count, queue, countPtr, countImm, gridItems, rays, hits, occ, counters, workCounter, rayStats);
 }
 // Diagnostics (tools/sort_experiment.py): what consuming rays through a PERMUTED index queue costs.  The n rays of d_rays7 stay where
@@ -429,7 +431,48 @@ int hprt_scene_attach_kdtree(HprtScene *s, const HprtKdTree *t) try {
     kd.primIdx = s->kdPrims.as<uint32_t>(); kd.nPrimIdx = (uint32_t)prims.size();
     for (int a = 0; a < 3; ++a) { kd.lo[a] = kt.bounds[a]; kd.hi[a] = kt.bounds[3 + a]; }
     kd.depth = depth;
-    s->kdAttached = true;
+    s->kdAttached = true; s->rbspAttached = false;
+    return HPRT_OK;
+} catch (...) { return hprt::HandleException(); }
+
+// MakeAccelerator("rbsp") (core/api.cpp:817-831): as for the kd-tree — checked, mapped to the ordered indices, walked by every
+// later trace of the scene
+int hprt_scene_attach_rbsp(HprtScene *s, const HprtRbsp *t) try {
+    if (!s || !t) return SetError(HPRT_E_INVALID, "hprt_scene_attach_rbsp: null argument");
+    if (s->instanced) return SetError(HPRT_E_UNSUPPORTED, "RBSP trees over object instances are not supported: the scene keeps its BVH");
+    const RbspTree &rt = t->tree;
+    const uint32_t nTop = (uint32_t)s->topOrder.size();
+    if (rt.nPrims != nTop)
+        return SetError(HPRT_E_INVALID, "the RBSP tree holds " + std::to_string(rt.nPrims) + " primitives, the scene " + std::to_string(nTop));
+    uint32_t depth = 0;
+    const char *bad = CheckRbspTree(rt, &depth);
+    if (*bad) return SetError(HPRT_E_INVALID, std::string("malformed RBSP tree: ") + bad);
+    if (depth > RBSP_TODO_MAX)
+        return SetError(HPRT_E_UNSUPPORTED, "RBSP tree of depth " + std::to_string(depth) + " is deeper than the walk's todo list (" + std::to_string((unsigned)RBSP_TODO_MAX) + ")");
+    const uint32_t M = rt.M, off = RbspBitOffset(M), mask = RbspBitMask(M);
+    std::vector<uint32_t> toOrdered(nTop);
+    for (uint32_t i = 0; i < nTop; ++i) toOrdered[s->topOrder[i]] = i;
+    std::vector<uint2> nodes(rt.nodes.size());
+    for (size_t k = 0; k < nodes.size(); ++k) {
+        const RbspNode &nd = rt.nodes[k];
+        const bool onePrim = (nd.b & mask) == M && (nd.b >> off) == 1u;
+        nodes[k] = make_uint2(onePrim ? toOrdered[nd.a] : nd.a, nd.b);
+    }
+    std::vector<uint32_t> prims(rt.primIndices.size());
+    for (size_t k = 0; k < prims.size(); ++k) prims[k] = toOrdered[rt.primIndices[k]];
+    HIP_TRY(hipSetDevice(s->device));
+    SceneCall call(s, nullptr);
+    HIP_TRY(hipDeviceSynchronize());      // a render or trace of the old tree may still be running
+    HIP_TRY(upload(s->rbspNodes, nodes));
+    HIP_TRY(upload(s->rbspPrims, prims));
+    DevRbsp &rb = s->rbsp;
+    rb = DevRbsp{};
+    rb.nodes = s->rbspNodes.as<uint2>(); rb.nNodes = (uint32_t)nodes.size();
+    rb.primIdx = s->rbspPrims.as<uint32_t>(); rb.nPrimIdx = (uint32_t)prims.size();
+    for (int a = 0; a < 3; ++a) { rb.lo[a] = rt.bounds[a]; rb.hi[a] = rt.bounds[3 + a]; }
+    rb.depth = depth; rb.M = M; rb.off = off; rb.mask = mask;
+    for (uint32_t k = 0; k < 3 * M; ++k) rb.dirs[k] = rt.directions[k];
+    s->rbspAttached = true; s->kdAttached = false;
     return HPRT_OK;
 } catch (...) { return hprt::HandleException(); }
 

@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <string>
 #include "../../include/hprt.h"
 #include "bvh_builder.h"
@@ -50,6 +51,8 @@ int hprt_model_parse(const char *pbrt_path, const char *const *subst, int n_subs
     // a kd-tree over object instances is not built (hprt_kdtree_build: HPRT_E_UNSUPPORTED): such a scene keeps the BVH and the warning
     if (m->sc.opt.accelerator == "kdtree" && m->sc.nObjects == 0 && m->sc.instances.empty())
         m->sc.warnings.push_back("Accelerator \"kdtree\": the host builds the tree (hprt_kdtree_build) and attaches it to the scene (hprt_scene_attach_kdtree); a scene without it walks a BVH");
+    else if (m->sc.opt.accelerator == "rbsp" && m->sc.nObjects == 0 && m->sc.instances.empty())
+        m->sc.warnings.push_back("Accelerator \"rbsp\": the host builds the tree (hprt_rbsp_build) and attaches it to the scene (hprt_scene_attach_rbsp); a scene without it walks a BVH");
     else if (m->sc.opt.accelerator != "bvh") m->sc.warnings.push_back("Accelerator \"" + m->sc.opt.accelerator + "\" is outside the hot-path scope; \"bvh\" used");
     if (m->sc.opt.integrator != "path") m->sc.warnings.push_back("Integrator \"" + m->sc.opt.integrator + "\" is outside the hot-path scope; \"path\" used");
     if (m->sc.opt.sampler != "halton") m->sc.warnings.push_back("Sampler \"" + m->sc.opt.sampler + "\" is outside the hot-path scope; \"halton\" used");
@@ -216,6 +219,79 @@ int hprt_kdtree_copy(const HprtKdTree *t, void *nodes8, uint32_t *primIndices) t
     return HPRT_OK;
 } catch (...) { return hprt::HandleException(); }
 void hprt_kdtree_destroy(HprtKdTree *t) { delete t; }
+
+// ---- RBSP tree (Accelerator "rbsp") ----
+static int BuildRbsp(size_t n, const float *lo, const float *hi, const float *tri9, const uint8_t *isTri, const HprtRbspParams *params,
+                     const RbspParams &dflt, HprtRbsp **out) {
+    RbspParams p = dflt;
+    if (params) {
+        p.isectCost = params->isect_cost; p.travCost = params->trav_cost; p.emptyBonus = params->empty_bonus;
+        p.maxPrims = params->max_prims; p.maxDepth = params->max_depth; p.nDirections = params->n_directions; p.threads = params->threads;
+    }
+    if (p.nDirections != 3 && p.nDirections != 7 && p.nDirections != 9 && p.nDirections != 13)
+        return SetError(HPRT_E_UNSUPPORTED, "nbDirections " + std::to_string(p.nDirections) + " is not supported (3, 7, 9 or 13)");
+    std::unique_ptr<HprtRbsp> t(new HprtRbsp());
+    const std::string err = BuildRbspTree(n, lo, hi, tri9, isTri, p, &t->tree);
+    if (!err.empty()) return SetError(HPRT_E_UNSUPPORTED, err);
+    if (t->tree.depth > RBSP_TODO_MAX)
+        return SetError(HPRT_E_UNSUPPORTED, "RBSP tree of depth " + std::to_string(t->tree.depth) + " is deeper than the device walk's todo list (" +
+                                                std::to_string((unsigned)RBSP_TODO_MAX) + " entries); lower \"maxdepth\"");
+    *out = t.release();
+    return HPRT_OK;
+}
+int hprt_rbsp_build(const HprtModel *m, const HprtRbspParams *params, HprtRbsp **out) try {
+    if (!m || !out) return SetError(HPRT_E_INVALID, "hprt_rbsp_build: null argument");
+    if (m->sc.nObjects != 0 || !m->sc.instances.empty()) return SetError(HPRT_E_UNSUPPORTED, "RBSP trees over object instances are not supported (the scene keeps its BVH)");
+    std::vector<float> lo, hi;
+    ComputePrimBounds(m->sc, {}, &lo, &hi);
+    const size_t n = lo.size() / 3;
+    // Triangle::getBounds projects the three world-space vertices; every other shape projects its world bound's corners
+    std::vector<float> tri9(9 * n, 0.f);
+    std::vector<uint8_t> isTri(n, 0);
+    size_t k = 0;
+    for (const TopItem &ti : m->sc.top) {
+        const ShapeDesc &sh = m->sc.shapes[ti.index];
+        if (sh.kind != kTriangleMesh) { ++k; continue; }
+        const MeshData &md = sh.mesh;
+        for (uint32_t tr = 0; tr < md.nTris(); ++tr, ++k) {
+            for (int v = 0; v < 3; ++v) memcpy(&tri9[9 * k + 3 * v], &md.P[3 * (size_t)md.indices[3 * tr + v]], 12);
+            isTri[k] = 1;
+        }
+    }
+    const RenderOptions &o = m->sc.opt;
+    RbspParams p;
+    p.isectCost = o.rbspIsectCost; p.travCost = o.rbspTravCost; p.emptyBonus = o.rbspEmptyBonus;
+    p.maxPrims = o.rbspMaxPrims; p.maxDepth = o.rbspMaxDepth; p.nDirections = o.rbspDirections;
+    return BuildRbsp(n, lo.data(), hi.data(), tri9.data(), isTri.data(), params, p, out);
+} catch (...) { return hprt::HandleException(); }
+int hprt_rbsp_build_from_triangles(size_t n, const float *p9, const HprtRbspParams *params, HprtRbsp **out) try {
+    if (!out || (n && !p9)) return SetError(HPRT_E_INVALID, "hprt_rbsp_build_from_triangles: null argument");
+    if (n > 0x3fffffffull) return SetError(HPRT_E_UNSUPPORTED, "more than 2^30 primitives");
+    // WorldBound of a triangle: Union(Bounds3f(p0, p1), p2) (shapes/triangle.cpp:180-186)
+    std::vector<float> lo(3 * n), hi(3 * n);
+    for (size_t i = 0; i < n; ++i)
+        for (int d = 0; d < 3; ++d) {
+            const float a = p9[9 * i + d], b = p9[9 * i + 3 + d], c = p9[9 * i + 6 + d];
+            const float l = std::min(a, b), h = std::max(a, b);
+            lo[3 * i + d] = std::min(l, c); hi[3 * i + d] = std::max(h, c);
+        }
+    std::vector<uint8_t> isTri(n, 1);
+    return BuildRbsp(n, lo.data(), hi.data(), p9, isTri.data(), params, RbspParams(), out);
+} catch (...) { return hprt::HandleException(); }
+int hprt_rbsp_info(const HprtRbsp *t, uint32_t info[5]) try {
+    if (!t || !info) return SetError(HPRT_E_INVALID, "hprt_rbsp_info: null argument");
+    info[0] = (uint32_t)t->tree.nodes.size(); info[1] = t->tree.leaves; info[2] = (uint32_t)t->tree.primIndices.size();
+    info[3] = t->tree.depth; info[4] = t->tree.M;
+    return HPRT_OK;
+} catch (...) { return hprt::HandleException(); }
+int hprt_rbsp_copy(const HprtRbsp *t, void *nodes8, uint32_t *primIndices, float *directions) try {
+    if (!t) return SetError(HPRT_E_INVALID, "hprt_rbsp_copy: null argument");
+    if (nodes8) memcpy(nodes8, t->tree.nodes.data(), t->tree.nodes.size() * sizeof(RbspNode));
+    if (primIndices && !t->tree.primIndices.empty()) memcpy(primIndices, t->tree.primIndices.data(), t->tree.primIndices.size() * 4);
+    if (directions) memcpy(directions, t->tree.directions.data(), t->tree.directions.size() * 4);
+    return HPRT_OK;
+} catch (...) { return hprt::HandleException(); }
+void hprt_rbsp_destroy(HprtRbsp *t) { delete t; }
 int hprt_bvh_info(const HprtBvh *b, uint32_t info[4], float bounds6[6]) try {
     if (!b || !info) return SetError(HPRT_E_INVALID, "hprt_bvh_info: null argument");
     info[0] = (uint32_t)b->tree.nodes.size(); info[1] = (uint32_t)b->tree.primOrder.size();
@@ -368,13 +444,14 @@ int hprt_write_pixel_stats(const char *prefix, const uint64_t *stats7, int width
 } catch (...) { return hprt::HandleException(); }
 int hprt_write_pixel_stats_accel(const char *prefix, const uint64_t *stats7, int width, int height, int accel) try {
     if (!prefix || !stats7 || width <= 0 || height <= 0) return SetError(HPRT_E_INVALID, "hprt_write_pixel_stats: bad argument");
-    if (accel != HPRT_ACCEL_BVH && accel != HPRT_ACCEL_KDTREE) return SetError(HPRT_E_INVALID, "hprt_write_pixel_stats_accel: unknown accelerator");
+    if (accel != HPRT_ACCEL_BVH && accel != HPRT_ACCEL_KDTREE && accel != HPRT_ACCEL_RBSP) return SetError(HPRT_E_INVALID, "hprt_write_pixel_stats_accel: unknown accelerator");
     // the matrices Film::WriteGeneralStats writes (core/film.cpp:170-187), with the index of the value in stats7 (-1: zero for this
     // accelerator): a kd render's interior-node counts (slots 5, 6) are its kdTreeNodeTraversals[P]
     const int kd = accel == HPRT_ACCEL_KDTREE ? 5 : -1, kdP = accel == HPRT_ACCEL_KDTREE ? 6 : -1;
+    const int bsp = accel == HPRT_ACCEL_RBSP ? 5 : -1, bspP = accel == HPRT_ACCEL_RBSP ? 6 : -1;   // an RBSP render's: bspTreeNodeTraversals[P]
     const struct { const char *name; int field; } kMatrices[] = {
         {"primitiveIntersections", 1}, {"primitiveIntersectionsP", 2}, {"kdTreeNodeTraversals", kd}, {"kdTreeNodeTraversalsP", kdP},
-        {"bspTreeNodeTraversals", -1}, {"bspTreeNodeTraversalsP", -1}, {"leafNodeTraversals", 3}, {"leafNodeTraversalsP", 4}};
+        {"bspTreeNodeTraversals", bsp}, {"bspTreeNodeTraversalsP", bspP}, {"leafNodeTraversals", 3}, {"leafNodeTraversalsP", 4}};
     for (const auto &m : kMatrices) {
         const std::string path = std::string(prefix) + "-" + m.name + ".txt";
         FILE *fp = fopen(path.c_str(), "w");

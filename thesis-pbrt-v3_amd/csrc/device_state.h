@@ -9,6 +9,7 @@
 #include "../../include/hprt.h"
 #include "device/kernels.h"
 #include "device/kd_walk.h"
+#include "device/rbsp_walk.h"
 #include "hprt_internal.h"
 
 #define HIP_TRY(expr)                                                                                   \
@@ -89,6 +90,8 @@ struct HprtScene {
     // hprt_scene_attach_kdtree: the kd walk replaces the BVH walks of every trace (kdNodes / kdPrims back `kd`); topOrder keeps
     // the top-level prim_order (ordered -> creation number) to map the tree's creation-order primitives; instanced: no kd walk
     hprt::DevBuf kdNodes, kdPrims; hprt::DevKd kd{}; bool kdAttached = false;
+    // hprt_scene_attach_rbsp: the same for an RBSP tree; attaching either tree detaches the other
+    hprt::DevBuf rbspNodes, rbspPrims; hprt::DevRbsp rbsp{}; bool rbspAttached = false;
     std::vector<uint32_t> topOrder; bool instanced = false;
     bool hasSubstrateBin = false;                     // some triangle carries BIN_SUBSTRATE: the substrate shading variant is launched
     ~HprtScene() { if (hostCounts) (void)hipHostFree(hostCounts); if (lastUse) (void)hipEventDestroy(lastUse); }

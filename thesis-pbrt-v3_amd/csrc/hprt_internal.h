@@ -4,6 +4,7 @@
 #include <vector>
 #include "bvh_builder.h"
 #include "kdtree_builder.h"
+#include "rbsp_builder.h"
 #include "scene_model.h"
 
 struct HprtModel { hprt::SceneModel sc; };
@@ -13,6 +14,7 @@ struct HprtBvh {
 };
 
 struct HprtKdTree { hprt::KdTree tree; };
+struct HprtRbsp { hprt::RbspTree tree; };
 
 namespace hprt {
 extern thread_local std::string g_lastError;

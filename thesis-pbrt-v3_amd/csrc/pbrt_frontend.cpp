@@ -628,6 +628,16 @@ struct Frontend {
             o.kdMaxDepth = accelParams.oneInt("maxdepth", -1);
             for (const char *n : {"splitalpha", "alphatype", "axisselectiontype", "axisselectionamount"}) (void)accelParams.find(n, "float", "integer");
         }
+        if (sc->opt.accelerator == "rbsp") {
+            // CreateRBSPTreeAccelerator, accelerators/rbsp.cpp:549-571; the statistics-only four are accepted and ignored, as for kdtree
+            o.rbspIsectCost = accelParams.oneInt("intersectcost", 80);
+            o.rbspTravCost = accelParams.oneInt("traversalcost", 5);
+            o.rbspEmptyBonus = accelParams.oneFloat("emptybonus", 0.f);
+            o.rbspMaxPrims = accelParams.oneInt("maxprims", 1);
+            o.rbspMaxDepth = accelParams.oneInt("maxdepth", -1);
+            o.rbspDirections = accelParams.oneInt("nbDirections", 3);
+            for (const char *n : {"splitalpha", "alphatype", "axisselectiontype", "axisselectionamount"}) (void)accelParams.find(n, "float", "integer");
+        }
         reportUnused(filmParams, "Film", {"diagonal"});
         reportUnused(filterParams, "PixelFilter");
         reportUnused(cameraParams, "Camera");

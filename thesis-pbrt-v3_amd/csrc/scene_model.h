@@ -88,6 +88,8 @@ struct RenderOptions {
     int32_t maxNodePrims = 4, isectCost = 8, travCost = 1;
     // Accelerator "kdtree": CreateKdTreeAccelerator's parameters (accelerators/kdtreeaccel.cpp:523-545); host side only (not baked)
     int32_t kdIsectCost = 80, kdTravCost = 1, kdMaxPrims = 1, kdMaxDepth = -1; float kdEmptyBonus = 0.f;
+    // Accelerator "rbsp": CreateRBSPTreeAccelerator's parameters (accelerators/rbsp.cpp:549-571); host side only (not baked)
+    int32_t rbspIsectCost = 80, rbspTravCost = 5, rbspMaxPrims = 1, rbspMaxDepth = -1, rbspDirections = 3; float rbspEmptyBonus = 0.f;
     std::string filename = "pbrt.exr", accelerator = "bvh", integrator = "path", sampler = "halton";
 };
 struct SceneModel {
