@@ -95,6 +95,22 @@ int main(int argc, char **argv) {
             return 1;
         }
     }
+    // Accelerator "rbspkd": the same with the kd-aware RBSP tree (RBSPKd) and its own walk
+    if (std::strcmp(accel, "rbspkd") == 0) {
+        HprtRbspKd *rk = nullptr;
+        const int rc = hprt_rbspkd_build(model, nullptr, &rk);
+        if (rc == HPRT_OK) {
+            int arc = HPRT_OK;
+            for (int g = 0; g < gpus && arc == HPRT_OK; ++g) arc = hprt_scene_attach_rbspkd(scenes[(size_t)g], rk);
+            hprt_rbspkd_destroy(rk);
+            if (arc != HPRT_OK) { std::fprintf(stderr, "hprt_scene_attach_rbspkd failed (%d): %s\n", arc, hprt_last_error()); return 1; }
+        } else if (rc == HPRT_E_UNSUPPORTED) {
+            std::fprintf(stderr, "Warning: %s; \"bvh\" used\n", hprt_last_error());
+        } else {
+            std::fprintf(stderr, "hprt_rbspkd_build failed (%d): %s\n", rc, hprt_last_error());
+            return 1;
+        }
+    }
     // one host thread per GPU (the renders are independent; errors are thread-local in the library, so each thread keeps its own)
     std::vector<HprtRenderStats> stats((size_t)gpus);
     std::vector<int> rcs((size_t)gpus, HPRT_OK);

@@ -180,6 +180,37 @@ int hprt_rbsp_copy(const HprtRbsp *t, void *nodes8, uint32_t *prim_indices, floa
 void hprt_rbsp_destroy(HprtRbsp *t);
 
 /* ------------------------------------------------------------------------ */
+/* kd-aware RBSP tree (Accelerator "rbspkd").  Stands in for                */
+/* RBSPKd::buildTree (accelerators/rbspKd.cpp:194-488): the RBSP tree's     */
+/* node layout, directions and k-DOP cost model, with axis splits costed    */
+/* kd_trav_cost + C_isect and oblique ones                                  */
+/* 0.1 * isect_cost * (N - 1) + kd_trav_cost + C_isect (a second minimum,   */
+/* trav_cost + C_isect over the oblique splits, takes part in the leaf      */
+/* tests only).  A handle of its own: an rbspkd tree is walked with the kd  */
+/* form at axis nodes and can never be attached to the RBSP walk.           */
+/* ------------------------------------------------------------------------ */
+typedef struct HprtRbspKd HprtRbspKd;
+typedef struct HprtRbspKdParams {
+    int isect_cost;     /* "intersectcost", default 80 */
+    int trav_cost;      /* "traversalcost", default 5 */
+    int kd_trav_cost;   /* "kdtraversalcost", default 1 */
+    float empty_bonus;  /* "emptybonus", default 0 */
+    int max_prims;      /* "maxprims", default 1 */
+    int max_depth;      /* "maxdepth", default -1 = round(2 + 1.6 Log2Int(N)) */
+    int n_directions;   /* "nbDirections": 3 (default), 7, 9 or 13; anything else is HPRT_E_UNSUPPORTED */
+    int threads;        /* builder threads (0: OMP_NUM_THREADS, else 16; at most 16); the tree does not depend on it */
+} HprtRbspKdParams;
+/* As hprt_rbsp_build: params NULL takes the scene's Accelerator line; instanced models, an unsupported M and trees deeper than
+ * HPRT_RBSP_MAX_DEPTH are HPRT_E_UNSUPPORTED, and so is a node where only the fixed-cost minimum is finite (the reference's
+ * build reads edges[-1] there). */
+int hprt_rbspkd_build(const HprtModel *m, const HprtRbspKdParams *params, HprtRbspKd **out);
+int hprt_rbspkd_build_from_triangles(size_t n_tris, const float *p9, const HprtRbspKdParams *params, HprtRbspKd **out);
+/* info[0..6] = nodes, leaves, primitive references, depth, M, kd interior nodes (direction < 3), oblique interior nodes */
+int hprt_rbspkd_info(const HprtRbspKd *t, uint32_t info[7]);
+int hprt_rbspkd_copy(const HprtRbspKd *t, void *nodes8, uint32_t *prim_indices, float *directions);
+void hprt_rbspkd_destroy(HprtRbspKd *t);
+
+/* ------------------------------------------------------------------------ */
 /* Device scene.  Upload step that follows the BVH build: stands in for the  */
 /* `primitives`/`nodes` members BVHAccel keeps (accelerators/bvh.h:69-79) and */
 /* the Scene object (core/scene.h:50-80).  The library copies everything to   */
@@ -300,6 +331,15 @@ int hprt_scene_attach_kdtree(HprtScene *s, const HprtKdTree *t);
  * bspTreeNodeTraversals (interior nodes), [2] triangle tests, [3] sphere tests; HPRT_RENDER_PIXEL_STATS slots 5 / 6 hold
  * bspTreeNodeTraversals[P] (hprt_write_pixel_stats_accel with HPRT_ACCEL_RBSP). */
 int hprt_scene_attach_rbsp(HprtScene *s, const HprtRbsp *t);
+/* The same for a kd-aware RBSP tree (RBSPKd::Intersect / IntersectP, accelerators/rbspKd.cpp:490-638).  Attaching any of the
+ * kd-tree, the RBSP tree and the rbspkd tree replaces whichever was attached before.  Counters of an rbspkd scene: [0]
+ * nbNodeTraversals, [1] every interior node (kdTreeNodeTraversals + bspTreeNodeTraversals), [2] triangle tests, [3] sphere
+ * tests; HPRT_RENDER_PIXEL_STATS slots 5 / 6 hold every interior node too.  The kd share comes from
+ * hprt_scene_kd_counters and hprt_pixel_kd_stats_read. */
+int hprt_scene_attach_rbspkd(HprtScene *s, const HprtRbspKd *t);
+/* kdTreeNodeTraversals (out[0]) and kdTreeNodeTraversalsP (out[1]) of the last counting trace (hprt_intersect / hprt_occluded
+ * with counters) or counting render of an rbspkd scene; zeros for any other scene. */
+int hprt_scene_kd_counters(HprtScene *s, uint64_t out[2]);
 
 /* ------------------------------------------------------------------------ */
 /* Batched Aggregate interface.  Stand in for                                */
@@ -402,6 +442,9 @@ int hprt_scene_reserve(HprtScene *s, const HprtRenderDesc *desc);
  * adds its counters once (core/integrator.cpp:327-328, integrators/path.cpp:92-200, core/light.cpp:62).
  * Pixels of tiles that were not rendered hold zeros, so per-rank results add up like the film. */
 int hprt_pixel_stats_read(HprtScene *s, uint64_t *out7, size_t n_pixels);
+/* For a render of an rbspkd scene with HPRT_RENDER_PIXEL_STATS: the per-pixel kd share of slots 5 / 6, as two planes
+ * (out2[0 .. n) kdTreeNodeTraversals, out2[n .. 2n) kdTreeNodeTraversalsP), row-major like hprt_pixel_stats_read. */
+int hprt_pixel_kd_stats_read(HprtScene *s, uint64_t *out2, size_t n_pixels);
 /* Film::WriteGeneralStats (core/film.cpp:170-264): writes <prefix>-primitiveIntersections.txt,
  * -primitiveIntersectionsP.txt, -leafNodeTraversals.txt, -leafNodeTraversalsP.txt (one row of the
  * image per line, values separated by blanks) and the all-zero kd-tree / BSP matrices the fork
@@ -414,6 +457,9 @@ int hprt_write_pixel_stats(const char *prefix, const uint64_t *stats7, int width
 #define HPRT_ACCEL_KDTREE 1
 #define HPRT_ACCEL_RBSP 2          /* slots 5 / 6 go to -bspTreeNodeTraversals[P].txt (core/film.cpp:176-177) */
 int hprt_write_pixel_stats_accel(const char *prefix, const uint64_t *stats7, int width, int height, int accel);
+/* The same for an rbspkd render: -kdTreeNodeTraversals[P].txt from kd2 (hprt_pixel_kd_stats_read's two planes) and
+ * -bspTreeNodeTraversals[P].txt = slot 5 / 6 minus the kd share, as Film::WriteGeneralStats does (core/film.cpp:174-177). */
+int hprt_write_pixel_stats_rbspkd(const char *prefix, const uint64_t *stats7, const uint64_t *kd2, int width, int height);
 /* Film::WriteImage arithmetic (core/film.cpp:266-303) on a host copy of a film
  * state: rgb_out = 3*W*H floats, top row first. */
 int hprt_film_resolve(const float *xyzw, size_t n_pixels, float film_scale, float *rgb_out);

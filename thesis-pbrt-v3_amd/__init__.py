@@ -7,6 +7,7 @@ accelerates:
     Bvh     <- CreateBVHAccelerator / BVHAccel ctor   (accelerators/bvh.cpp:155-185,529-535)
     KdTree  <- CreateKdTreeAccelerator / buildTree    (accelerators/kdtreeaccel.cpp:212-380,523-545)
     Rbsp    <- CreateRBSPTreeAccelerator / buildTree  (accelerators/rbsp.cpp:181-403,549-571)
+    RbspKd  <- CreateRBSPKdTreeAccelerator / buildTree (accelerators/rbspKd.cpp:194-488,640-665)
     Scene   <- Scene + BVHAccel::Intersect/IntersectP (accelerators/bvh.cpp:354-437)
                and SamplerIntegrator::Render with PathIntegrator::Li
                (core/integrator.cpp:230-360, integrators/path.cpp:64-204)
@@ -117,6 +118,59 @@ class LightDesc(C.Structure):
                 ("texture", C.c_int32), ("light_to_world", C.c_float * 16), ("world_to_light", C.c_float * 16)]
 
 
+class RbspKdParams(C.Structure):
+    """HprtRbspKdParams: CreateRBSPKdTreeAccelerator's parameters plus the builder's thread count."""
+    _fields_ = [("isect_cost", C.c_int), ("trav_cost", C.c_int), ("kd_trav_cost", C.c_int), ("empty_bonus", C.c_float), ("max_prims", C.c_int),
+                ("max_depth", C.c_int), ("n_directions", C.c_int), ("threads", C.c_int)]
+
+
+class RbspKd:
+    """kd-aware RBSP tree (host): CreateRBSPKdTreeAccelerator(prims, params) — the RBSP node layout and direction table, with
+    RBSPKd's cost model.  RbspKd(model) takes the scene's Accelerator line; keyword parameters override it."""
+
+    def __init__(self, model=None, handle=None, n_directions=None, isect_cost=80, trav_cost=5, kd_trav_cost=1, empty_bonus=0.0, max_prims=1,
+                 max_depth=-1, threads=0):
+        if handle is None:
+            handle = C.c_void_p()
+            prm = None if n_directions is None else C.byref(RbspKdParams(isect_cost, trav_cost, kd_trav_cost, empty_bonus, max_prims, max_depth,
+                                                                           n_directions, threads))
+            _check(lib.hprt_rbspkd_build(model._h, prm, C.byref(handle)))
+        self._h = handle
+
+    @staticmethod
+    def from_triangles(p9, n_directions=3, isect_cost=80, trav_cost=5, kd_trav_cost=1, empty_bonus=0.0, max_prims=1, max_depth=-1, threads=0):
+        """p9: [n, 9] (or [n, 3, 3]) float32 world-space triangle vertices in creation order."""
+        p9 = np.ascontiguousarray(p9, np.float32).reshape(-1, 9)
+        h = C.c_void_p()
+        prm = RbspKdParams(isect_cost, trav_cost, kd_trav_cost, empty_bonus, max_prims, max_depth, n_directions, threads)
+        _check(lib.hprt_rbspkd_build_from_triangles(p9.shape[0], _ptr(p9), C.byref(prm), C.byref(h)))
+        return RbspKd(handle=h)
+
+    def info(self):
+        i = (C.c_uint32 * 7)()
+        _check(lib.hprt_rbspkd_info(self._h, i))
+        return {"nodes": i[0], "leaves": i[1], "prim_refs": i[2], "depth": i[3], "M": i[4], "kd_interior": i[5], "bsp_interior": i[6]}
+
+    def arrays(self):
+        """(nodes [n, 2] uint32, prim_indices uint32): the RBSPNode layout of Rbsp.arrays"""
+        inf = self.info()
+        nodes = np.zeros((inf["nodes"], 2), np.uint32)
+        idx = np.zeros(inf["prim_refs"], np.uint32)
+        _check(lib.hprt_rbspkd_copy(self._h, _ptr(nodes), _ptr(idx), None))
+        return nodes, idx
+
+    def directions(self):
+        """[M, 3] float32: getDirections(M)"""
+        d = np.zeros((self.info()["M"], 3), np.float32)
+        _check(lib.hprt_rbspkd_copy(self._h, None, None, _ptr(d)))
+        return d
+
+    def __del__(self):
+        if getattr(self, "_h", None) and lib is not None:      # (module globals are cleared at interpreter exit)
+            lib.hprt_rbspkd_destroy(self._h)
+            self._h = None
+
+
 class SceneDesc(C.Structure):
     _fields_ = [("nodes", C.c_void_p), ("n_nodes", C.c_uint32), ("prim_order", C.c_void_p), ("n_prims", C.c_uint32),
                 ("shapes", C.POINTER(ShapeDesc)), ("n_shapes", C.c_uint32),
@@ -195,6 +249,15 @@ def _load():
         "hprt_rbsp_copy": (C.c_int, [vp, vp, vp, vp]),
         "hprt_rbsp_destroy": (None, [vp]),
         "hprt_scene_attach_rbsp": (C.c_int, [vp, vp]),
+        "hprt_rbspkd_build": (C.c_int, [vp, vp, P(vp)]),
+        "hprt_rbspkd_build_from_triangles": (C.c_int, [sz, vp, vp, P(vp)]),
+        "hprt_rbspkd_info": (C.c_int, [vp, P(u32)]),
+        "hprt_rbspkd_copy": (C.c_int, [vp, vp, vp, vp]),
+        "hprt_rbspkd_destroy": (None, [vp]),
+        "hprt_scene_attach_rbspkd": (C.c_int, [vp, vp]),
+        "hprt_scene_kd_counters": (C.c_int, [vp, vp]),
+        "hprt_pixel_kd_stats_read": (C.c_int, [vp, vp, sz]),
+        "hprt_write_pixel_stats_rbspkd": (C.c_int, [cp, vp, vp, C.c_int, C.c_int]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)   # raises AttributeError if an export is missing
@@ -457,6 +520,19 @@ class Scene:
         _check(lib.hprt_scene_attach_rbsp(self._h, rbsp._h))
         self._rbsp = rbsp
 
+    def attach_rbspkd(self, rbspkd):
+        """hprt_scene_attach_rbspkd: every later trace and render walks `rbspkd` (an RbspKd over this scene's primitives);
+        replaces an attached kd-tree or RBSP tree."""
+        _check(lib.hprt_scene_attach_rbspkd(self._h, rbspkd._h))
+        self._rbspkd = rbspkd
+
+    def kd_counters(self):
+        """(kdTreeNodeTraversals, kdTreeNodeTraversalsP) of the last counting trace or render of an rbspkd scene (zeros
+        otherwise); the counters' [1] / nodes_entered[_p] hold kd and oblique interior nodes together."""
+        out = np.zeros(2, np.uint64)
+        _check(lib.hprt_scene_kd_counters(self._h, _ptr(out)))
+        return int(out[0]), int(out[1])
+
     def intersect(self, o, d, tmax, count=False):
         o = np.ascontiguousarray(o, np.float32); d = np.ascontiguousarray(d, np.float32)
         tmax = np.ascontiguousarray(tmax, np.float32)
@@ -544,6 +620,14 @@ class Scene:
         _check(lib.hprt_pixel_stats_read(self._h, _ptr(out), h * w))
         return out
 
+    def pixel_kd_stats(self):
+        """[2, H, W] uint64: the kd share (kdTreeNodeTraversals, kdTreeNodeTraversalsP) of pixel_stats()' slots 5 / 6 after
+        render(pixel_stats=True) of an rbspkd scene."""
+        h, w = self._film_shape
+        out = np.zeros((2, h, w), np.uint64)
+        _check(lib.hprt_pixel_kd_stats_read(self._h, _ptr(out), h * w))
+        return out
+
     def sample_radiance(self, px, py, sample, opt=None):
         opt = opt or self._model.options
         px = np.ascontiguousarray(px, np.int32); py = np.ascontiguousarray(py, np.int32)
@@ -627,6 +711,16 @@ def write_pixel_stats_accel(prefix, stats7, accel):
     ACCEL_RBSP: slots 5 / 6 are bspTreeNodeTraversals[P])."""
     stats7 = np.ascontiguousarray(stats7, np.uint64)
     _check(lib.hprt_write_pixel_stats_accel(prefix.encode(), _ptr(stats7), stats7.shape[1], stats7.shape[0], accel))
+
+
+def write_pixel_stats_rbspkd(prefix, stats7, kd2):
+    """The same for an rbspkd render: kdTreeNodeTraversals[P] from kd2 (Scene.pixel_kd_stats), bspTreeNodeTraversals[P] =
+    slot 5 / 6 minus that share."""
+    stats7 = np.ascontiguousarray(stats7, np.uint64)
+    kd2 = np.ascontiguousarray(kd2, np.uint64)
+    if kd2.shape != (2,) + stats7.shape[:2]:
+        raise ValueError("kd2 must be [2, H, W] for stats7 of [H, W, 7]")
+    _check(lib.hprt_write_pixel_stats_rbspkd(prefix.encode(), _ptr(stats7), _ptr(kd2), stats7.shape[1], stats7.shape[0]))
 
 
 def write_pfm(path, rgb):

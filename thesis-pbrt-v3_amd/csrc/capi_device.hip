@@ -250,7 +250,7 @@ int hprt_scene_create(const HprtSceneDesc *d, int device, HprtScene **out) try {
 
 // Diagnostics hook (not part of include/hprt.h): 1 when plain renders of this scene take the leaf-exact wide walk (k_walk4), else 0: the
 // binary walk, or the kd walk once a kd-tree is attached (callers test the value for truth: "is it k_walk4")
-__attribute__((visibility("default"))) int hprt_debug_scene_walk(HprtScene *s) { return s && !s->kdAttached && !s->rbspAttached && hprt::WideWalkInUse(s->dev) ? 1 : 0; }
+__attribute__((visibility("default"))) int hprt_debug_scene_walk(HprtScene *s) { return s && !s->kdAttached && !s->rbspAttached && !s->rbspkdAttached && hprt::WideWalkInUse(s->dev) ? 1 : 0; }
 __attribute__((visibility("default"))) int hprt_debug_poison_workspace(HprtScene *s, int byte) { if (!s) return HPRT_E_INVALID; s->poisonByte = byte < 0 ? -1 : (byte & 255); return HPRT_OK; }
 // Diagnostics hook (not part of include/hprt.h): the first batch of the next hprt_render copies the rays that bounce `bounce` queues
 // (kind 0: the path segments entering bounce + 1, 1: its shadow rays, 2: its BSDF-sampled light rays) into d_out7 ([7][cap] planes:
@@ -262,12 +262,13 @@ __attribute__((visibility("default"))) int hprt_debug_capture_rays(HprtScene *s,
 }
 static int ApiStreams(HprtScene *s, size_t n, RayStream *rays, HitStream *hits);
 // Every trace of a scene: the kd walk once a kd-tree is attached (hprt_scene_attach_kdtree), the RBSP walk once an RBSP tree is
-// (hprt_scene_attach_rbsp), else the BVH walks (LaunchTrace)
+// (hprt_scene_attach_rbsp), the rbspkd walk once an rbspkd tree is (hprt_scene_attach_rbspkd), else the BVH walks (LaunchTrace)
 static void Trace(HprtScene *s, hipStream_t st, bool anyHit, bool count, const uint32_t *queue, const uint32_t *countPtr, uint32_t countImm,
                   uint32_t gridItems, const RayStream &rays, const HitStream &hits, uint8_t *occ, DevCounters *counters, uint32_t *workCounter,
                   uint4 *rayStats = nullptr) {
     if (s->kdAttached) LaunchKdTrace(st, s->dev, s->kd, anyHit, count, queue, countPtr, countImm, gridItems, rays, hits, occ, counters, workCounter, rayStats);
     else if (s->rbspAttached) LaunchRbspTrace(st, s->dev, s->rbsp, anyHit, count, queue, countPtr, countImm, gridItems, rays, hits, occ, counters, workCounter, rayStats);
+    else if (s->rbspkdAttached) LaunchRbspKdTrace(st, s->dev, s->rbspkd, anyHit, count, queue, countPtr, countImm, gridItems, rays, hits, occ, counters, workCounter, rayStats);
     else LaunchTrace(st, s->dev, anyHit, count, queue, countPtr, countImm, gridItems, rays, hits, occ, counters, workCounter, rayStats);
 }
 // Diagnostics (tools/sort_experiment.py): what consuming rays through a PERMUTED index queue costs.  The n rays of d_rays7 stay where
@@ -431,24 +432,21 @@ int hprt_scene_attach_kdtree(HprtScene *s, const HprtKdTree *t) try {
     kd.primIdx = s->kdPrims.as<uint32_t>(); kd.nPrimIdx = (uint32_t)prims.size();
     for (int a = 0; a < 3; ++a) { kd.lo[a] = kt.bounds[a]; kd.hi[a] = kt.bounds[3 + a]; }
     kd.depth = depth;
-    s->kdAttached = true; s->rbspAttached = false;
+    s->kdAttached = true; s->rbspAttached = false; s->rbspkdAttached = false;
     return HPRT_OK;
 } catch (...) { return hprt::HandleException(); }
 
-// MakeAccelerator("rbsp") (core/api.cpp:817-831): as for the kd-tree — checked, mapped to the ordered indices, walked by every
-// later trace of the scene
-int hprt_scene_attach_rbsp(HprtScene *s, const HprtRbsp *t) try {
-    if (!s || !t) return SetError(HPRT_E_INVALID, "hprt_scene_attach_rbsp: null argument");
-    if (s->instanced) return SetError(HPRT_E_UNSUPPORTED, "RBSP trees over object instances are not supported: the scene keeps its BVH");
-    const RbspTree &rt = t->tree;
+// The device form of an RBSP tree (either cost model): checked, its creation-order primitive numbers mapped to the ordered
+// indices, uploaded into nodesBuf / primsBuf.  `what` names the tree in messages.
+static int UploadRbsp(HprtScene *s, const RbspTree &rt, const char *what, DevBuf &nodesBuf, DevBuf &primsBuf, DevRbsp *out) {
     const uint32_t nTop = (uint32_t)s->topOrder.size();
     if (rt.nPrims != nTop)
-        return SetError(HPRT_E_INVALID, "the RBSP tree holds " + std::to_string(rt.nPrims) + " primitives, the scene " + std::to_string(nTop));
+        return SetError(HPRT_E_INVALID, std::string("the ") + what + " tree holds " + std::to_string(rt.nPrims) + " primitives, the scene " + std::to_string(nTop));
     uint32_t depth = 0;
     const char *bad = CheckRbspTree(rt, &depth);
-    if (*bad) return SetError(HPRT_E_INVALID, std::string("malformed RBSP tree: ") + bad);
+    if (*bad) return SetError(HPRT_E_INVALID, std::string("malformed ") + what + " tree: " + bad);
     if (depth > RBSP_TODO_MAX)
-        return SetError(HPRT_E_UNSUPPORTED, "RBSP tree of depth " + std::to_string(depth) + " is deeper than the walk's todo list (" + std::to_string((unsigned)RBSP_TODO_MAX) + ")");
+        return SetError(HPRT_E_UNSUPPORTED, std::string(what) + " tree of depth " + std::to_string(depth) + " is deeper than the walk's todo list (" + std::to_string((unsigned)RBSP_TODO_MAX) + ")");
     const uint32_t M = rt.M, off = RbspBitOffset(M), mask = RbspBitMask(M);
     std::vector<uint32_t> toOrdered(nTop);
     for (uint32_t i = 0; i < nTop; ++i) toOrdered[s->topOrder[i]] = i;
@@ -461,18 +459,56 @@ int hprt_scene_attach_rbsp(HprtScene *s, const HprtRbsp *t) try {
     std::vector<uint32_t> prims(rt.primIndices.size());
     for (size_t k = 0; k < prims.size(); ++k) prims[k] = toOrdered[rt.primIndices[k]];
     HIP_TRY(hipSetDevice(s->device));
-    SceneCall call(s, nullptr);
     HIP_TRY(hipDeviceSynchronize());      // a render or trace of the old tree may still be running
-    HIP_TRY(upload(s->rbspNodes, nodes));
-    HIP_TRY(upload(s->rbspPrims, prims));
-    DevRbsp &rb = s->rbsp;
+    HIP_TRY(upload(nodesBuf, nodes));
+    HIP_TRY(upload(primsBuf, prims));
+    DevRbsp &rb = *out;
     rb = DevRbsp{};
-    rb.nodes = s->rbspNodes.as<uint2>(); rb.nNodes = (uint32_t)nodes.size();
-    rb.primIdx = s->rbspPrims.as<uint32_t>(); rb.nPrimIdx = (uint32_t)prims.size();
+    rb.nodes = nodesBuf.as<uint2>(); rb.nNodes = (uint32_t)nodes.size();
+    rb.primIdx = primsBuf.as<uint32_t>(); rb.nPrimIdx = (uint32_t)prims.size();
     for (int a = 0; a < 3; ++a) { rb.lo[a] = rt.bounds[a]; rb.hi[a] = rt.bounds[3 + a]; }
     rb.depth = depth; rb.M = M; rb.off = off; rb.mask = mask;
     for (uint32_t k = 0; k < 3 * M; ++k) rb.dirs[k] = rt.directions[k];
-    s->rbspAttached = true; s->kdAttached = false;
+    return HPRT_OK;
+}
+
+// MakeAccelerator("rbsp") (core/api.cpp:817-831): as for the kd-tree — checked, mapped to the ordered indices, walked by every
+// later trace of the scene
+int hprt_scene_attach_rbsp(HprtScene *s, const HprtRbsp *t) try {
+    if (!s || !t) return SetError(HPRT_E_INVALID, "hprt_scene_attach_rbsp: null argument");
+    if (s->instanced) return SetError(HPRT_E_UNSUPPORTED, "RBSP trees over object instances are not supported: the scene keeps its BVH");
+    HIP_TRY(hipSetDevice(s->device));
+    SceneCall call(s, nullptr);
+    const int rc = UploadRbsp(s, t->tree, "RBSP", s->rbspNodes, s->rbspPrims, &s->rbsp);
+    if (rc != HPRT_OK) return rc;
+    s->rbspAttached = true; s->kdAttached = false; s->rbspkdAttached = false;
+    return HPRT_OK;
+} catch (...) { return hprt::HandleException(); }
+
+// The fork's "rbspkd" accelerator (RBSPKd): the RBSP tree's checks and layout, walked by the rbspkd walk with its kd counter pair
+int hprt_scene_attach_rbspkd(HprtScene *s, const HprtRbspKd *t) try {
+    if (!s || !t) return SetError(HPRT_E_INVALID, "hprt_scene_attach_rbspkd: null argument");
+    if (s->instanced) return SetError(HPRT_E_UNSUPPORTED, "rbspkd trees over object instances are not supported: the scene keeps its BVH");
+    HIP_TRY(hipSetDevice(s->device));
+    SceneCall call(s, nullptr);
+    const int rc = UploadRbsp(s, t->tree, "rbspkd", s->rbspkdNodes, s->rbspkdPrims, &s->rbspkd.t);
+    if (rc != HPRT_OK) return rc;
+    HIP_TRY(s->kdShare.alloc(2 * sizeof(unsigned long long)));
+    HIP_TRY(hipMemset(s->kdShare.p, 0, 2 * sizeof(unsigned long long)));
+    s->rbspkd.kdCounters = s->kdShare.as<unsigned long long>();
+    s->rbspkdAttached = true; s->kdAttached = false; s->rbspAttached = false;
+    return HPRT_OK;
+} catch (...) { return hprt::HandleException(); }
+
+int hprt_scene_kd_counters(HprtScene *s, uint64_t out[2]) try {
+    if (!s || !out) return SetError(HPRT_E_INVALID, "hprt_scene_kd_counters: null argument");
+    HIP_TRY(hipSetDevice(s->device));
+    SceneCall call(s, nullptr);
+    out[0] = out[1] = 0;
+    if (!s->rbspkdAttached) return HPRT_OK;
+    unsigned long long c[2];
+    HIP_TRY(hipMemcpy(c, s->kdShare.p, sizeof(c), hipMemcpyDeviceToHost));
+    out[0] = c[0]; out[1] = c[1];
     return HPRT_OK;
 } catch (...) { return hprt::HandleException(); }
 
@@ -535,6 +571,7 @@ int hprt_occluded_device(HprtScene *s, size_t n, const float *d_rays7, uint8_t *
     return HPRT_OK;
 } catch (...) { return hprt::HandleException(); }
 
+
 static int TraceHost(HprtScene *s, bool anyHit, size_t n, const float *o, const float *d, const float *tmax, float *t_out,
                      int32_t *prim_out, int32_t *inst_out, float *bary_out, uint8_t *occ_out, uint64_t counters[4]) {
     if (!s || (n && (!o || !d || !tmax))) return SetError(HPRT_E_INVALID, "trace: null argument");
@@ -553,6 +590,7 @@ static int TraceHost(HprtScene *s, bool anyHit, size_t n, const float *o, const 
     HIP_TRY(hipMemcpy(rays.a, ra.data(), 16 * n, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(rays.b, rb.data(), 16 * n, hipMemcpyHostToDevice));
     HIP_TRY(hipMemset(s->counters.p, 0, sizeof(DevCounters)));
+    if (s->rbspkdAttached) HIP_TRY(hipMemset(s->kdShare.p, 0, 2 * sizeof(unsigned long long)));
     const bool count = counters != nullptr;
     if (!anyHit) {
         Trace(s, nullptr, false, count, nullptr, nullptr, (uint32_t)n, (uint32_t)n, rays, hits, nullptr, s->counters.as<DevCounters>(), s->workCounter.as<uint32_t>());
@@ -610,6 +648,7 @@ int RunBatch(HprtScene *s, hipStream_t st, const RenderParams &rp, const Workspa
              const BinSet &bins, uint32_t s0, uint32_t nSlots, bool count, EventTimer &ev, BatchTimers *bt, HprtRenderStats *stats,
              uint32_t *pixelStats = nullptr, const IrregularSink *irregular = nullptr) {
     uint4 *rayStats = pixelStats ? s->rayStats.as<uint4>() : nullptr;
+    uint32_t *pixelKd = pixelStats && s->rbspkdAttached ? s->pixelKdLocal.as<uint32_t>() : nullptr;     // the rbspkd walk's kd share
     uint32_t *wcPath = s->workCounter.as<uint32_t>();
     LaunchGenerate(st, s->dev, rp, w.path[0], s0, nSlots, irregular);
     const uint32_t *activeQ = nullptr; uint32_t active = nSlots;
@@ -622,6 +661,7 @@ int RunBatch(HprtScene *s, hipStream_t st, const RenderParams &rp, const Workspa
         HIP_TRY(hipEventRecord(e0, st));
         Trace(s, st, false, count, activeQ, nullptr, active, active, in.ray, w.hit, nullptr, ctr, wcPath, rayStats);
         if (pixelStats) LaunchPixelStats(st, rayStats, bounce == 0 ? nullptr : in.beta, activeQ, nullptr, active, active, rp.nPix, false, pixelStats);
+        if (pixelKd) LaunchPixelKdStats(st, rayStats, bounce == 0 ? nullptr : in.beta, activeQ, nullptr, active, active, rp.nPix, false, pixelKd);
         HIP_TRY(hipEventRecord(e1, st));
         evExt.push_back({e0, e1}); bt->extendRays += active; ++bt->extendLaunches;
         stats->rays += active;
@@ -677,6 +717,7 @@ int RunBatch(HprtScene *s, hipStream_t st, const RenderParams &rp, const Workspa
             HitStream none; none.a = nullptr; none.b = nullptr;
             Trace(s, st, true, count, cur.shadow, nullptr, nShadow, nShadow, w.vs.shadow, none, w.vs.occluded, ctr, wcPath, rayStats);
             if (pixelStats) LaunchPixelStats(st, rayStats, w.vs.pendBeta, cur.shadow, nullptr, nShadow, nShadow, rp.nPix, true, pixelStats);
+            if (pixelKd) LaunchPixelKdStats(st, rayStats, w.vs.pendBeta, cur.shadow, nullptr, nShadow, nShadow, rp.nPix, true, pixelKd);
             HIP_TRY(hipEventRecord(b, st));
             evOcc.push_back({a, b}); bt->occludedRays += nShadow; ++bt->occludedLaunches;
             stats->shadow_rays += nShadow;
@@ -686,6 +727,7 @@ int RunBatch(HprtScene *s, hipStream_t st, const RenderParams &rp, const Workspa
             HIP_TRY(hipEventRecord(a, st));
             Trace(s, st, false, count, cur.mis, nullptr, nMis, nMis, w.vs.mis, w.vs.misHit, nullptr, ctr, wcPath, rayStats);
             if (pixelStats) LaunchPixelStats(st, rayStats, w.vs.pendBeta, cur.mis, nullptr, nMis, nMis, rp.nPix, false, pixelStats);
+            if (pixelKd) LaunchPixelKdStats(st, rayStats, w.vs.pendBeta, cur.mis, nullptr, nMis, nMis, rp.nPix, false, pixelKd);
             HIP_TRY(hipEventRecord(b, st));
             evExt.push_back({a, b}); bt->extendRays += nMis; ++bt->extendLaunches;
             stats->rays += nMis;
@@ -835,9 +877,16 @@ int hprt_render(HprtScene *s, const HprtRenderDesc *desc, float *d_film_xyzw, vo
         HIP_TRY(s->pixelStatsFilm.alloc(7ull * s->filmPixels * sizeof(uint64_t)));
         HIP_TRY(hipMemsetAsync(s->pixelStatsFilm.p, 0, 7ull * s->filmPixels * sizeof(uint64_t), st));
         pixelStats = s->pixelStatsLocal.as<uint32_t>();
+        if (s->rbspkdAttached) {
+            HIP_TRY(s->pixelKdLocal.alloc(2ull * nPix * sizeof(uint32_t)));
+            HIP_TRY(hipMemsetAsync(s->pixelKdLocal.p, 0, 2ull * nPix * sizeof(uint32_t), st));
+            HIP_TRY(s->pixelKdFilm.alloc(2ull * s->filmPixels * sizeof(uint64_t)));
+            HIP_TRY(hipMemsetAsync(s->pixelKdFilm.p, 0, 2ull * s->filmPixels * sizeof(uint64_t), st));
+        }
     }
-    s->pixelStatsValid = false;
+    s->pixelStatsValid = false; s->pixelKdValid = false;
     HIP_TRY(hipMemsetAsync(s->counters.p, 0, sizeof(DevCounters), st));
+    if (s->rbspkdAttached) HIP_TRY(hipMemsetAsync(s->kdShare.p, 0, 2 * sizeof(unsigned long long), st));
 
     auto wall0 = std::chrono::high_resolution_clock::now();
     // ---- film footprint pre-pass ----
@@ -942,6 +991,11 @@ int hprt_render(HprtScene *s, const HprtRenderDesc *desc, float *d_film_xyzw, vo
     if (pixelStats) {
         LaunchPixelStatsToFilm(st, pixelStats, rp.pixelXY, nPix, spp, f.fg.cx0, f.fg.cy0, f.W, s->pixelStatsFilm.as<unsigned long long>());
         s->pixelStatsValid = true;
+        if (s->rbspkdAttached) {
+            LaunchPixelKdStatsToFilm(st, s->pixelKdLocal.as<uint32_t>(), rp.pixelXY, nPix, f.fg.cx0, f.fg.cy0, f.W, s->filmPixels,
+                                     s->pixelKdFilm.as<unsigned long long>());
+            s->pixelKdValid = true;
+        }
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));
@@ -1002,6 +1056,16 @@ int hprt_pixel_stats_read(HprtScene *s, uint64_t *out7, size_t n_pixels) try {
     if (n_pixels != s->filmPixels) return SetError(HPRT_E_INVALID, "hprt_pixel_stats_read: pixel count differs from the last render's film");
     HIP_TRY(hipSetDevice(s->device));
     HIP_TRY(hipMemcpy(out7, s->pixelStatsFilm.p, 7 * n_pixels * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return HPRT_OK;
+} catch (...) { return hprt::HandleException(); }
+// the kd share of slots 5 / 6 of the last rbspkd render with HPRT_RENDER_PIXEL_STATS: [2][film pixels]
+int hprt_pixel_kd_stats_read(HprtScene *s, uint64_t *out2, size_t n_pixels) try {
+    if (!s || !out2) return SetError(HPRT_E_INVALID, "hprt_pixel_kd_stats_read: null argument");
+    SceneCall call(s, nullptr);
+    if (!s->pixelKdValid) return SetError(HPRT_E_INVALID, "no per-pixel kd statistics: render an rbspkd scene with HPRT_RENDER_PIXEL_STATS first");
+    if (n_pixels != s->filmPixels) return SetError(HPRT_E_INVALID, "hprt_pixel_kd_stats_read: pixel count differs from the last render's film");
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipMemcpy(out2, s->pixelKdFilm.p, 2 * n_pixels * sizeof(uint64_t), hipMemcpyDeviceToHost));
     return HPRT_OK;
 } catch (...) { return hprt::HandleException(); }
 int hprt_film_read(HprtScene *s, float *xyzw_out, size_t n_pixels) try {

@@ -53,6 +53,8 @@ int hprt_model_parse(const char *pbrt_path, const char *const *subst, int n_subs
         m->sc.warnings.push_back("Accelerator \"kdtree\": the host builds the tree (hprt_kdtree_build) and attaches it to the scene (hprt_scene_attach_kdtree); a scene without it walks a BVH");
     else if (m->sc.opt.accelerator == "rbsp" && m->sc.nObjects == 0 && m->sc.instances.empty())
         m->sc.warnings.push_back("Accelerator \"rbsp\": the host builds the tree (hprt_rbsp_build) and attaches it to the scene (hprt_scene_attach_rbsp); a scene without it walks a BVH");
+    else if (m->sc.opt.accelerator == "rbspkd" && m->sc.nObjects == 0 && m->sc.instances.empty())
+        m->sc.warnings.push_back("Accelerator \"rbspkd\": the host builds the tree (hprt_rbspkd_build) and attaches it to the scene (hprt_scene_attach_rbspkd); a scene without it walks a BVH");
     else if (m->sc.opt.accelerator != "bvh") m->sc.warnings.push_back("Accelerator \"" + m->sc.opt.accelerator + "\" is outside the hot-path scope; \"bvh\" used");
     if (m->sc.opt.integrator != "path") m->sc.warnings.push_back("Integrator \"" + m->sc.opt.integrator + "\" is outside the hot-path scope; \"path\" used");
     if (m->sc.opt.sampler != "halton") m->sc.warnings.push_back("Sampler \"" + m->sc.opt.sampler + "\" is outside the hot-path scope; \"halton\" used");
@@ -220,7 +222,17 @@ int hprt_kdtree_copy(const HprtKdTree *t, void *nodes8, uint32_t *primIndices) t
 } catch (...) { return hprt::HandleException(); }
 void hprt_kdtree_destroy(HprtKdTree *t) { delete t; }
 
-// ---- RBSP tree (Accelerator "rbsp") ----
+// ---- RBSP tree (Accelerator "rbsp") and kd-aware RBSP tree (Accelerator "rbspkd") ----
+static int BuildRbspChecked(size_t n, const float *lo, const float *hi, const float *tri9, const uint8_t *isTri, const RbspParams &p, RbspTree *out) {
+    if (p.nDirections != 3 && p.nDirections != 7 && p.nDirections != 9 && p.nDirections != 13)
+        return SetError(HPRT_E_UNSUPPORTED, "nbDirections " + std::to_string(p.nDirections) + " is not supported (3, 7, 9 or 13)");
+    const std::string err = BuildRbspTree(n, lo, hi, tri9, isTri, p, out);
+    if (!err.empty()) return SetError(HPRT_E_UNSUPPORTED, err);
+    if (out->depth > RBSP_TODO_MAX)
+        return SetError(HPRT_E_UNSUPPORTED, "RBSP tree of depth " + std::to_string(out->depth) + " is deeper than the device walk's todo list (" +
+                                                std::to_string((unsigned)RBSP_TODO_MAX) + " entries); lower \"maxdepth\"");
+    return HPRT_OK;
+}
 static int BuildRbsp(size_t n, const float *lo, const float *hi, const float *tri9, const uint8_t *isTri, const HprtRbspParams *params,
                      const RbspParams &dflt, HprtRbsp **out) {
     RbspParams p = dflt;
@@ -228,53 +240,71 @@ static int BuildRbsp(size_t n, const float *lo, const float *hi, const float *tr
         p.isectCost = params->isect_cost; p.travCost = params->trav_cost; p.emptyBonus = params->empty_bonus;
         p.maxPrims = params->max_prims; p.maxDepth = params->max_depth; p.nDirections = params->n_directions; p.threads = params->threads;
     }
-    if (p.nDirections != 3 && p.nDirections != 7 && p.nDirections != 9 && p.nDirections != 13)
-        return SetError(HPRT_E_UNSUPPORTED, "nbDirections " + std::to_string(p.nDirections) + " is not supported (3, 7, 9 or 13)");
     std::unique_ptr<HprtRbsp> t(new HprtRbsp());
-    const std::string err = BuildRbspTree(n, lo, hi, tri9, isTri, p, &t->tree);
-    if (!err.empty()) return SetError(HPRT_E_UNSUPPORTED, err);
-    if (t->tree.depth > RBSP_TODO_MAX)
-        return SetError(HPRT_E_UNSUPPORTED, "RBSP tree of depth " + std::to_string(t->tree.depth) + " is deeper than the device walk's todo list (" +
-                                                std::to_string((unsigned)RBSP_TODO_MAX) + " entries); lower \"maxdepth\"");
+    const int rc = BuildRbspChecked(n, lo, hi, tri9, isTri, p, &t->tree);
+    if (rc != HPRT_OK) return rc;
     *out = t.release();
     return HPRT_OK;
 }
-int hprt_rbsp_build(const HprtModel *m, const HprtRbspParams *params, HprtRbsp **out) try {
-    if (!m || !out) return SetError(HPRT_E_INVALID, "hprt_rbsp_build: null argument");
-    if (m->sc.nObjects != 0 || !m->sc.instances.empty()) return SetError(HPRT_E_UNSUPPORTED, "RBSP trees over object instances are not supported (the scene keeps its BVH)");
-    std::vector<float> lo, hi;
-    ComputePrimBounds(m->sc, {}, &lo, &hi);
-    const size_t n = lo.size() / 3;
-    // Triangle::getBounds projects the three world-space vertices; every other shape projects its world bound's corners
-    std::vector<float> tri9(9 * n, 0.f);
-    std::vector<uint8_t> isTri(n, 0);
+static int BuildRbspKd(size_t n, const float *lo, const float *hi, const float *tri9, const uint8_t *isTri, const HprtRbspKdParams *params,
+                       const RbspParams &dflt, HprtRbspKd **out) {
+    RbspParams p = dflt;
+    p.kdAware = true;
+    if (params) {
+        p.isectCost = params->isect_cost; p.travCost = params->trav_cost; p.kdTravCost = params->kd_trav_cost; p.emptyBonus = params->empty_bonus;
+        p.maxPrims = params->max_prims; p.maxDepth = params->max_depth; p.nDirections = params->n_directions; p.threads = params->threads;
+    }
+    std::unique_ptr<HprtRbspKd> t(new HprtRbspKd());
+    const int rc = BuildRbspChecked(n, lo, hi, tri9, isTri, p, &t->tree);
+    if (rc != HPRT_OK) return rc;
+    *out = t.release();
+    return HPRT_OK;
+}
+// The builder's view of a model's top-level primitives: world bounds, and the three world-space vertices of each triangle
+// (Triangle::getBounds projects those; every other shape projects its world bound's corners)
+static void RbspModelPrims(const HprtModel *m, std::vector<float> *lo, std::vector<float> *hi, std::vector<float> *tri9, std::vector<uint8_t> *isTri) {
+    ComputePrimBounds(m->sc, {}, lo, hi);
+    const size_t n = lo->size() / 3;
+    tri9->assign(9 * n, 0.f);
+    isTri->assign(n, 0);
     size_t k = 0;
     for (const TopItem &ti : m->sc.top) {
         const ShapeDesc &sh = m->sc.shapes[ti.index];
         if (sh.kind != kTriangleMesh) { ++k; continue; }
         const MeshData &md = sh.mesh;
         for (uint32_t tr = 0; tr < md.nTris(); ++tr, ++k) {
-            for (int v = 0; v < 3; ++v) memcpy(&tri9[9 * k + 3 * v], &md.P[3 * (size_t)md.indices[3 * tr + v]], 12);
-            isTri[k] = 1;
+            for (int v = 0; v < 3; ++v) memcpy(&(*tri9)[9 * k + 3 * v], &md.P[3 * (size_t)md.indices[3 * tr + v]], 12);
+            (*isTri)[k] = 1;
         }
     }
-    const RenderOptions &o = m->sc.opt;
-    RbspParams p;
-    p.isectCost = o.rbspIsectCost; p.travCost = o.rbspTravCost; p.emptyBonus = o.rbspEmptyBonus;
-    p.maxPrims = o.rbspMaxPrims; p.maxDepth = o.rbspMaxDepth; p.nDirections = o.rbspDirections;
-    return BuildRbsp(n, lo.data(), hi.data(), tri9.data(), isTri.data(), params, p, out);
-} catch (...) { return hprt::HandleException(); }
-int hprt_rbsp_build_from_triangles(size_t n, const float *p9, const HprtRbspParams *params, HprtRbsp **out) try {
-    if (!out || (n && !p9)) return SetError(HPRT_E_INVALID, "hprt_rbsp_build_from_triangles: null argument");
-    if (n > 0x3fffffffull) return SetError(HPRT_E_UNSUPPORTED, "more than 2^30 primitives");
-    // WorldBound of a triangle: Union(Bounds3f(p0, p1), p2) (shapes/triangle.cpp:180-186)
-    std::vector<float> lo(3 * n), hi(3 * n);
+}
+// WorldBound of a triangle: Union(Bounds3f(p0, p1), p2) (shapes/triangle.cpp:180-186)
+static void RbspTriangleBounds(size_t n, const float *p9, std::vector<float> *lo, std::vector<float> *hi) {
+    lo->resize(3 * n); hi->resize(3 * n);
     for (size_t i = 0; i < n; ++i)
         for (int d = 0; d < 3; ++d) {
             const float a = p9[9 * i + d], b = p9[9 * i + 3 + d], c = p9[9 * i + 6 + d];
             const float l = std::min(a, b), h = std::max(a, b);
-            lo[3 * i + d] = std::min(l, c); hi[3 * i + d] = std::max(h, c);
+            (*lo)[3 * i + d] = std::min(l, c); (*hi)[3 * i + d] = std::max(h, c);
         }
+}
+int hprt_rbsp_build(const HprtModel *m, const HprtRbspParams *params, HprtRbsp **out) try {
+    if (!m || !out) return SetError(HPRT_E_INVALID, "hprt_rbsp_build: null argument");
+    if (m->sc.nObjects != 0 || !m->sc.instances.empty()) return SetError(HPRT_E_UNSUPPORTED, "RBSP trees over object instances are not supported (the scene keeps its BVH)");
+    std::vector<float> lo, hi, tri9;
+    std::vector<uint8_t> isTri;
+    RbspModelPrims(m, &lo, &hi, &tri9, &isTri);
+    const RenderOptions &o = m->sc.opt;
+    RbspParams p;
+    p.isectCost = o.rbspIsectCost; p.travCost = o.rbspTravCost; p.emptyBonus = o.rbspEmptyBonus;
+    p.maxPrims = o.rbspMaxPrims; p.maxDepth = o.rbspMaxDepth; p.nDirections = o.rbspDirections;
+    return BuildRbsp(lo.size() / 3, lo.data(), hi.data(), tri9.data(), isTri.data(), params, p, out);
+} catch (...) { return hprt::HandleException(); }
+int hprt_rbsp_build_from_triangles(size_t n, const float *p9, const HprtRbspParams *params, HprtRbsp **out) try {
+    if (!out || (n && !p9)) return SetError(HPRT_E_INVALID, "hprt_rbsp_build_from_triangles: null argument");
+    if (n > 0x3fffffffull) return SetError(HPRT_E_UNSUPPORTED, "more than 2^30 primitives");
+    std::vector<float> lo, hi;
+    RbspTriangleBounds(n, p9, &lo, &hi);
     std::vector<uint8_t> isTri(n, 1);
     return BuildRbsp(n, lo.data(), hi.data(), p9, isTri.data(), params, RbspParams(), out);
 } catch (...) { return hprt::HandleException(); }
@@ -292,6 +322,41 @@ int hprt_rbsp_copy(const HprtRbsp *t, void *nodes8, uint32_t *primIndices, float
     return HPRT_OK;
 } catch (...) { return hprt::HandleException(); }
 void hprt_rbsp_destroy(HprtRbsp *t) { delete t; }
+int hprt_rbspkd_build(const HprtModel *m, const HprtRbspKdParams *params, HprtRbspKd **out) try {
+    if (!m || !out) return SetError(HPRT_E_INVALID, "hprt_rbspkd_build: null argument");
+    if (m->sc.nObjects != 0 || !m->sc.instances.empty()) return SetError(HPRT_E_UNSUPPORTED, "rbspkd trees over object instances are not supported (the scene keeps its BVH)");
+    std::vector<float> lo, hi, tri9;
+    std::vector<uint8_t> isTri;
+    RbspModelPrims(m, &lo, &hi, &tri9, &isTri);
+    const RenderOptions &o = m->sc.opt;
+    RbspParams p;
+    p.isectCost = o.rbspkdIsectCost; p.travCost = o.rbspkdTravCost; p.kdTravCost = o.rbspkdKdTravCost; p.emptyBonus = o.rbspkdEmptyBonus;
+    p.maxPrims = o.rbspkdMaxPrims; p.maxDepth = o.rbspkdMaxDepth; p.nDirections = o.rbspkdDirections;
+    return BuildRbspKd(lo.size() / 3, lo.data(), hi.data(), tri9.data(), isTri.data(), params, p, out);
+} catch (...) { return hprt::HandleException(); }
+int hprt_rbspkd_build_from_triangles(size_t n, const float *p9, const HprtRbspKdParams *params, HprtRbspKd **out) try {
+    if (!out || (n && !p9)) return SetError(HPRT_E_INVALID, "hprt_rbspkd_build_from_triangles: null argument");
+    if (n > 0x3fffffffull) return SetError(HPRT_E_UNSUPPORTED, "more than 2^30 primitives");
+    std::vector<float> lo, hi;
+    RbspTriangleBounds(n, p9, &lo, &hi);
+    std::vector<uint8_t> isTri(n, 1);
+    return BuildRbspKd(n, lo.data(), hi.data(), p9, isTri.data(), params, RbspParams(), out);
+} catch (...) { return hprt::HandleException(); }
+int hprt_rbspkd_info(const HprtRbspKd *t, uint32_t info[7]) try {
+    if (!t || !info) return SetError(HPRT_E_INVALID, "hprt_rbspkd_info: null argument");
+    info[0] = (uint32_t)t->tree.nodes.size(); info[1] = t->tree.leaves; info[2] = (uint32_t)t->tree.primIndices.size();
+    info[3] = t->tree.depth; info[4] = t->tree.M;
+    RbspInteriorCounts(t->tree, &info[5], &info[6]);
+    return HPRT_OK;
+} catch (...) { return hprt::HandleException(); }
+int hprt_rbspkd_copy(const HprtRbspKd *t, void *nodes8, uint32_t *primIndices, float *directions) try {
+    if (!t) return SetError(HPRT_E_INVALID, "hprt_rbspkd_copy: null argument");
+    if (nodes8) memcpy(nodes8, t->tree.nodes.data(), t->tree.nodes.size() * sizeof(RbspNode));
+    if (primIndices && !t->tree.primIndices.empty()) memcpy(primIndices, t->tree.primIndices.data(), t->tree.primIndices.size() * 4);
+    if (directions) memcpy(directions, t->tree.directions.data(), t->tree.directions.size() * 4);
+    return HPRT_OK;
+} catch (...) { return hprt::HandleException(); }
+void hprt_rbspkd_destroy(HprtRbspKd *t) { delete t; }
 int hprt_bvh_info(const HprtBvh *b, uint32_t info[4], float bounds6[6]) try {
     if (!b || !info) return SetError(HPRT_E_INVALID, "hprt_bvh_info: null argument");
     info[0] = (uint32_t)b->tree.nodes.size(); info[1] = (uint32_t)b->tree.primOrder.size();
@@ -460,6 +525,37 @@ int hprt_write_pixel_stats_accel(const char *prefix, const uint64_t *stats7, int
         for (int y = 0; y < height && ok; ++y) {
             for (int x = 0; x < width; ++x) {
                 const unsigned long long v = m.field < 0 ? 0ull : (unsigned long long)stats7[7 * ((size_t)y * width + x) + m.field];
+                ok = ok && fprintf(fp, x ? " %llu" : "%llu", v) > 0;
+            }
+            ok = ok && fputc('\n', fp) != EOF;
+        }
+        if (fclose(fp) != 0) ok = false;
+        if (!ok) return SetError(HPRT_E_IO, "write error on " + path);
+    }
+    return HPRT_OK;
+} catch (...) { return hprt::HandleException(); }
+
+// An rbspkd render's matrices: the kd share of slots 5 / 6 from kd2, the rest of them (oblique interior nodes) as bsp
+int hprt_write_pixel_stats_rbspkd(const char *prefix, const uint64_t *stats7, const uint64_t *kd2, int width, int height) try {
+    if (!prefix || !stats7 || !kd2 || width <= 0 || height <= 0) return SetError(HPRT_E_INVALID, "hprt_write_pixel_stats_rbspkd: bad argument");
+    const size_t nPix = (size_t)width * (size_t)height;
+    for (size_t i = 0; i < nPix; ++i)
+        if (kd2[i] > stats7[7 * i + 5] || kd2[nPix + i] > stats7[7 * i + 6])
+            return SetError(HPRT_E_INVALID, "hprt_write_pixel_stats_rbspkd: a pixel's kd share exceeds its interior-node count");
+    // field: slot of stats7; kdPlane: 0 / 1 the kd plane itself, 2 / 3 slot minus that plane, -1 none
+    const struct { const char *name; int field, kdPlane; } kMatrices[] = {
+        {"primitiveIntersections", 1, -1}, {"primitiveIntersectionsP", 2, -1}, {"kdTreeNodeTraversals", -1, 0}, {"kdTreeNodeTraversalsP", -1, 1},
+        {"bspTreeNodeTraversals", 5, 0}, {"bspTreeNodeTraversalsP", 6, 1}, {"leafNodeTraversals", 3, -1}, {"leafNodeTraversalsP", 4, -1}};
+    for (const auto &m : kMatrices) {
+        const std::string path = std::string(prefix) + "-" + m.name + ".txt";
+        FILE *fp = fopen(path.c_str(), "w");
+        if (!fp) return SetError(HPRT_E_IO, "cannot create " + path);
+        bool ok = true;
+        for (int y = 0; y < height && ok; ++y) {
+            for (int x = 0; x < width; ++x) {
+                const size_t i = (size_t)y * width + x;
+                const unsigned long long kd = m.kdPlane < 0 ? 0ull : (unsigned long long)kd2[(size_t)m.kdPlane * nPix + i];
+                const unsigned long long v = m.field < 0 ? kd : (unsigned long long)stats7[7 * i + m.field] - kd;
                 ok = ok && fprintf(fp, x ? " %llu" : "%llu", v) > 0;
             }
             ok = ok && fputc('\n', fp) != EOF;

@@ -1,9 +1,11 @@
 // hprt device side — the body of a GenericBSP walk (Intersect / IntersectP of accelerators/genericBSP.h's trees) over the
 // reference's 8-byte node arrays: the root interval, the todo list, the leaf loop, the hit word and the counters.  The RBSP walk
-// (rbsp_walk.hip) instantiates it; the kd walk (kd_walk.hip) is the same loop written out, and stays so because moving it here
-// changes its register allocation, and so its code object.  A walk passes its interior step in as `Step`:
+// (rbsp_walk.hip) and the rbspkd walk (rbspkd_walk.hip) instantiate it; the kd walk (kd_walk.hip) is the same loop written out,
+// and stays so because moving it here changes its register allocation, and so its code object.  A walk passes its interior step in as `Step`:
 //   bool leaf(uint32_t flags), uint32_t high(uint32_t flags)   (aboveChild / nPrimitives),
 //   void plane(uint32_t flags, float split, vec3 ro, vec3 rd, vec3 invDir, float *tPlane, bool *belowFirst).
+// KD_SHARE (the rbspkd walk) counts the interior nodes for which the step's `bool kd(uint32_t flags)` holds apart as well: per
+// ray in rayStats.w (0 for every other walk) and per wave through `void kd_count_add(bool anyHit, uint32_t n)`.
 // (The step keeps no per-ray state: values that must survive the sphere test's call would cost scratch.)
 //
 // One ray per lane; persistent waves draw 64 rays at a time from the queue head (one atomic per wave and draw), so the kernels
@@ -46,7 +48,7 @@ __device__ __forceinline__ bool bsp_root_interval(const float *lo, const float *
 // The whole kernel body.  ANY_HIT: IntersectP (no early-out on a closer hit); COUNT: counters and per-ray statistics; QUAD:
 // the scene has spheres.  nodes / primIdx: the attached tree (one-primitive leaves and primIdx hold ORDERED indices); lo / hi:
 // GenericBSP::bounds.  stackMem: the kernel's [LDS][BLOCK] LDS todo entries.
-template <bool ANY_HIT, bool COUNT, bool QUAD, int LDS, int BLOCK, class Step>
+template <bool ANY_HIT, bool COUNT, bool QUAD, int LDS, int BLOCK, class Step, bool KD_SHARE = false>
 __device__ __forceinline__ void bsp_walk(const DevScene &sc, const uint2 *nodes, const uint32_t *primIdx, const float *lo, const float *hi, Step &step,
                                          const uint32_t *queue, const uint32_t *countPtr, uint32_t countImm, const RayStream &rays,
                                          const HitStream &hits, uint8_t *occ, DevCounters *counters, uint4 *rayStats, uint32_t *workCounter,
@@ -63,6 +65,7 @@ __device__ __forceinline__ void bsp_walk(const DevScene &sc, const uint2 *nodes,
     const uint32_t n = countPtr ? *countPtr : countImm;
     const uint32_t lane = __lane_id();
     TraceCount cnt = {0u, 0u, 0u, 0u, 0u};     // fetched: nbNodeTraversals, entered: interior nodes, leaf: leaves
+    uint32_t kdCnt = 0u;                       // KD_SHARE: of the entered interior nodes, kd ones
     while (true) {
         uint32_t base = 0u;
         if (lane == 0) base = atomicAdd(workCounter, 64u);
@@ -75,6 +78,7 @@ __device__ __forceinline__ void bsp_walk(const DevScene &sc, const uint2 *nodes,
         const vec3 ro(ra.x, ra.y, ra.z), rd(rb.x, rb.y, rb.z);
         float rayTMax = ra.w;
         const TraceCount snap = cnt;
+        const uint32_t kdSnap = kdCnt;
         bool hit = false;
         int32_t prim = -1; float hb0 = 0.f, hb1 = 0.f, hb2 = 0.f;
         float tMin, tMax;
@@ -91,6 +95,7 @@ __device__ __forceinline__ void bsp_walk(const DevScene &sc, const uint2 *nodes,
                 const uint2 nd = nodes[node];
                 if (!step.leaf(nd.y)) {
                     if (COUNT) ++cnt.entered;
+                    if constexpr (COUNT && KD_SHARE) kdCnt += step.kd(nd.y) ? 1u : 0u;
                     float tPlane; bool belowFirst;
                     step.plane(nd.y, __uint_as_float(nd.x), ro, rd, invDir, &tPlane, &belowFirst);
                     const uint32_t above = step.high(nd.y);
@@ -143,7 +148,8 @@ __device__ __forceinline__ void bsp_walk(const DevScene &sc, const uint2 *nodes,
                 }
             }
         }
-        if (COUNT && rayStats) rayStats[slot] = make_uint4(cnt.entered - snap.entered, cnt.leaf - snap.leaf, (cnt.tri + cnt.sphere) - (snap.tri + snap.sphere), 0u);
+        if (COUNT && rayStats) rayStats[slot] = make_uint4(cnt.entered - snap.entered, cnt.leaf - snap.leaf, (cnt.tri + cnt.sphere) - (snap.tri + snap.sphere),
+                                                    KD_SHARE ? kdCnt - kdSnap : 0u);
         if (ANY_HIT) occ[slot] = hit ? 1 : 0;
         else {
             hits.a[slot] = make_float4(rayTMax, __int_as_float(hit ? prim : -1), hb0, hb1);
@@ -151,6 +157,7 @@ __device__ __forceinline__ void bsp_walk(const DevScene &sc, const uint2 *nodes,
         }
     }
     if (COUNT) wave_count_add(counters, ANY_HIT, cnt);
+    if constexpr (COUNT && KD_SHARE) step.kd_count_add(ANY_HIT, kdCnt);
 }
 
 }  // namespace hprt

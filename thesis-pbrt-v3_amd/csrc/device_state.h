@@ -10,6 +10,7 @@
 #include "device/kernels.h"
 #include "device/kd_walk.h"
 #include "device/rbsp_walk.h"
+#include "device/rbspkd_walk.h"
 #include "hprt_internal.h"
 
 #define HIP_TRY(expr)                                                                                   \
@@ -92,6 +93,10 @@ struct HprtScene {
     hprt::DevBuf kdNodes, kdPrims; hprt::DevKd kd{}; bool kdAttached = false;
     // hprt_scene_attach_rbsp: the same for an RBSP tree; attaching either tree detaches the other
     hprt::DevBuf rbspNodes, rbspPrims; hprt::DevRbsp rbsp{}; bool rbspAttached = false;
+    // hprt_scene_attach_rbspkd: the same for a kd-aware RBSP tree; attaching any of the three trees detaches the others.  kdShare:
+    // its kd counter pair (DevRbspKd::kdCounters); pixelKdLocal / pixelKdFilm: the per-pixel kd share of HPRT_RENDER_PIXEL_STATS
+    hprt::DevBuf rbspkdNodes, rbspkdPrims, kdShare; hprt::DevRbspKd rbspkd{}; bool rbspkdAttached = false;
+    hprt::DevBuf pixelKdLocal, pixelKdFilm; bool pixelKdValid = false;
     std::vector<uint32_t> topOrder; bool instanced = false;
     bool hasSubstrateBin = false;                     // some triangle carries BIN_SUBSTRATE: the substrate shading variant is launched
     ~HprtScene() { if (hostCounts) (void)hipHostFree(hostCounts); if (lastUse) (void)hipEventDestroy(lastUse); }

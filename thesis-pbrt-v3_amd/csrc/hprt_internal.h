@@ -15,6 +15,7 @@ struct HprtBvh {
 
 struct HprtKdTree { hprt::KdTree tree; };
 struct HprtRbsp { hprt::RbspTree tree; };
+struct HprtRbspKd { hprt::RbspTree tree; };     // built with RbspParams::kdAware
 
 namespace hprt {
 extern thread_local std::string g_lastError;

@@ -638,6 +638,17 @@ struct Frontend {
             o.rbspDirections = accelParams.oneInt("nbDirections", 3);
             for (const char *n : {"splitalpha", "alphatype", "axisselectiontype", "axisselectionamount"}) (void)accelParams.find(n, "float", "integer");
         }
+        if (sc->opt.accelerator == "rbspkd") {
+            // CreateRBSPKdTreeAccelerator, accelerators/rbspKd.cpp:640-665: rbsp's parameters plus "kdtraversalcost"
+            o.rbspkdIsectCost = accelParams.oneInt("intersectcost", 80);
+            o.rbspkdTravCost = accelParams.oneInt("traversalcost", 5);
+            o.rbspkdKdTravCost = accelParams.oneInt("kdtraversalcost", 1);
+            o.rbspkdEmptyBonus = accelParams.oneFloat("emptybonus", 0.f);
+            o.rbspkdMaxPrims = accelParams.oneInt("maxprims", 1);
+            o.rbspkdMaxDepth = accelParams.oneInt("maxdepth", -1);
+            o.rbspkdDirections = accelParams.oneInt("nbDirections", 3);
+            for (const char *n : {"splitalpha", "alphatype", "axisselectiontype", "axisselectionamount"}) (void)accelParams.find(n, "float", "integer");
+        }
         reportUnused(filmParams, "Film", {"diagonal"});
         reportUnused(filterParams, "PixelFilter");
         reportUnused(cameraParams, "Camera");

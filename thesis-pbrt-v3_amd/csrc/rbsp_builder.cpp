@@ -1,10 +1,11 @@
-// hprt — RBSP::buildTree (accelerators/rbsp.cpp:181-403) with KDOPCut / KDOPSurfaceArea (accelerators/kDOPMesh.h), restated
-// operation for operation.  Every float operation is one IEEE rounding in the reference's order (built with -ffp-contract=off).
+// hprt — RBSP::buildTree (accelerators/rbsp.cpp:181-403) and RBSPKd::buildTree (accelerators/rbspKd.cpp:194-488,
+// RbspParams::kdAware) with KDOPCut / KDOPSurfaceArea (accelerators/kDOPMesh.h), restated operation for operation.  Every float
+// operation is one IEEE rounding in the reference's order (built with -ffp-contract=off).
 //
 // The one liberty: the candidates of a node may be costed on several threads.  Each candidate's cost is a pure function of the
 // node's k-DOP and the candidate, and the reduction keeps the first minimum in (direction, edge) order — what the reference's
-// strict `cost < bestCost` scan keeps — so the tree does not depend on the thread count.  The winner's two halves are then cut
-// and measured once more, exactly as the scan left them.
+// strict `cost < bestCost` scan keeps (for RBSPKd, each of its two minima) — so the tree does not depend on the thread count.
+// The winner's two halves are then cut and measured once more, exactly as the scan left them.
 #include "rbsp_builder.h"
 #include <algorithm>
 #include <cmath>
@@ -277,7 +278,9 @@ std::string BuildRbspTree(size_t n, const float *bmin, const float *bmax, const 
     };
 
     std::vector<Cand> cands;
-    std::vector<float> costs;
+    std::vector<float> costs, costsFixed;       // costsFixed: RBSPKd's traversalCost + C_isect of the oblique candidates
+    const float BSP_ALPHA = 0.1;                 // RBSPKd::buildTree's `const Float`
+    const uint32_t kdTraversalCost = (uint32_t)p.kdTravCost;
     std::vector<std::thread> pool;
     uint32_t nodeNum = 0;
     std::vector<BuildNode> stack;
@@ -315,6 +318,7 @@ std::string BuildRbspTree(size_t n, const float *bmin, const float *bmax, const 
             }
         }
         costs.resize(cands.size());
+        if (p.kdAware) costsFixed.resize(cands.size());
         auto costRange = [&](size_t k0, size_t k1, Scratch &s) {
             for (size_t k = k0; k < k1; ++k) {
                 const Cand &c = cands[k];
@@ -324,7 +328,15 @@ std::string BuildRbspTree(size_t n, const float *bmin, const float *bmax, const 
                 const float pBelow = areaBelow * invTotalSA;
                 const float pAbove = areaAbove * invTotalSA;
                 const float eb = (c.nAbove == 0 || c.nBelow == 0) ? emptyBonus : 0;
-                costs[k] = (float)traversalCost + (float)isectCost * (1 - eb) * (pBelow * (float)c.nBelow + pAbove * (float)c.nAbove);
+                if (!p.kdAware) {
+                    costs[k] = (float)traversalCost + (float)isectCost * (1 - eb) * (pBelow * (float)c.nBelow + pAbove * (float)c.nAbove);
+                } else if (c.d < 3) {
+                    costs[k] = (float)kdTraversalCost + (float)isectCost * (1 - eb) * (pBelow * (float)c.nBelow + pAbove * (float)c.nAbove);
+                } else {
+                    const float costIntersection = (float)isectCost * (1 - eb) * (pBelow * (float)c.nBelow + pAbove * (float)c.nAbove);
+                    costsFixed[k] = (float)traversalCost + costIntersection;
+                    costs[k] = BSP_ALPHA * (float)isectCost * (float)(cur.nPrimitives - 1) + (float)kdTraversalCost + costIntersection;
+                }
             }
         };
         if (nThreads > 1 && cands.size() >= kParallelCandidates) {
@@ -343,10 +355,26 @@ std::string BuildRbspTree(size_t n, const float *bmin, const float *bmax, const 
         for (size_t k = 0; k < cands.size(); ++k)
             if (costs[k] < bestCost) { bestCost = costs[k]; bestD = cands[k].d; bestOffset = cands[k].i; }
 
-        // Create leaf if no good splits were found
-        if (bestCost > oldCost) ++cur.badRefines;
-        if ((bestCost > 4 * oldCost && cur.nPrimitives < 16) || bestD == (uint32_t)-1 || cur.badRefines == 3) {
-            initLeaf(&prims[cur.primNums], cur.nPrimitives); ++nodeNum; continue;
+        if (p.kdAware) {
+            // RBSPKd keeps a second minimum over the oblique candidates (costFixed); the leaf tests need both to fail
+            uint32_t bestDFixed = (uint32_t)-1;
+            float bestCostFixed = std::numeric_limits<float>::infinity();
+            for (size_t k = 0; k < cands.size(); ++k)
+                if (cands[k].d >= 3 && costsFixed[k] < bestCostFixed) { bestCostFixed = costsFixed[k]; bestDFixed = cands[k].d; }
+            if (bestCost > oldCost && bestCostFixed > oldCost) ++cur.badRefines;
+            if ((bestCost > 4 * oldCost && bestCostFixed > 4 * oldCost && cur.nPrimitives < 16) || (bestD == (uint32_t)-1 && bestDFixed == (uint32_t)-1) ||
+                cur.badRefines == 3) {
+                initLeaf(&prims[cur.primNums], cur.nPrimitives); ++nodeNum; continue;
+            }
+            // only the fixed minimum beat infinity: the reference classifies by edges[bestD = -1] (rbspKd.cpp:423-432)
+            if (bestD == (uint32_t)-1)
+                return "every kd-aware candidate cost is infinite or NaN while a fixed-cost oblique split exists: the reference's build is undefined there";
+        } else {
+            // Create leaf if no good splits were found
+            if (bestCost > oldCost) ++cur.badRefines;
+            if ((bestCost > 4 * oldCost && cur.nPrimitives < 16) || bestD == (uint32_t)-1 || cur.badRefines == 3) {
+                initLeaf(&prims[cur.primNums], cur.nPrimitives); ++nodeNum; continue;
+            }
         }
 
         // the winner's halves, measured (and so reoriented) as the scan left them
@@ -397,6 +425,17 @@ std::string BuildRbspTree(size_t n, const float *bmin, const float *bmax, const 
     (void)CheckRbspTree(t, &depth);
     t.depth = depth;
     return "";
+}
+
+void RbspInteriorCounts(const RbspTree &t, uint32_t *kd, uint32_t *bsp) {
+    const uint32_t mask = RbspBitMask(t.M);
+    uint32_t k = 0, b = 0;
+    for (const RbspNode &nd : t.nodes) {
+        const uint32_t ax = nd.b & mask;
+        if (ax == t.M) continue;
+        if (ax < 3) ++k; else ++b;
+    }
+    *kd = k; *bsp = b;
 }
 
 const char *CheckRbspTree(const RbspTree &t, uint32_t *depthOut) {

@@ -29,6 +29,11 @@ struct RbspParams {
     int maxPrims = 1, maxDepth = -1;      // "maxprims", "maxdepth" (-1: round(2 + 1.6 Log2Int(N)), core/geometry.h:1845)
     int nDirections = 3;                  // "nbDirections": 3, 7, 9 or 13
     int threads = 0;                      // candidate evaluation threads: 0 = OMP_NUM_THREADS (else 16), at most 16
+    // RBSPKd::buildTree (accelerators/rbspKd.cpp:194-488, CreateRBSPKdTreeAccelerator :640-665): the kd-aware cost model.  Axis
+    // candidates cost kdTravCost + C_isect; oblique ones BSP_ALPHA * isectCost * (N - 1) + kdTravCost + C_isect for the split
+    // chosen, and travCost + C_isect for a second minimum that only the leaf tests read.
+    bool kdAware = false;
+    int kdTravCost = 1;                   // "kdtraversalcost"
 };
 
 struct RbspTree {
@@ -48,6 +53,8 @@ bool RbspDirections(uint32_t M, std::vector<float> *dirs3);
 // Returns "" on success, else what went wrong (unsupported M, a tree outside the reference's primitive buffer).
 std::string BuildRbspTree(size_t n, const float *bmin, const float *bmax, const float *tri9, const uint8_t *isTri, const RbspParams &p,
                           RbspTree *out);
+// The interior nodes of a tree by kind: axis directions (kd, direction < 3) and oblique ones (bsp).
+void RbspInteriorCounts(const RbspTree &t, uint32_t *kd, uint32_t *bsp);
 // Structural check of a tree handed to the device: child offsets, leaf index ranges, primitive numbers, depth.
 // Returns an empty string when the tree is well-formed, else what is wrong.
 const char *CheckRbspTree(const RbspTree &t, uint32_t *depthOut);

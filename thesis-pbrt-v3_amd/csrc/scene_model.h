@@ -90,6 +90,9 @@ struct RenderOptions {
     int32_t kdIsectCost = 80, kdTravCost = 1, kdMaxPrims = 1, kdMaxDepth = -1; float kdEmptyBonus = 0.f;
     // Accelerator "rbsp": CreateRBSPTreeAccelerator's parameters (accelerators/rbsp.cpp:549-571); host side only (not baked)
     int32_t rbspIsectCost = 80, rbspTravCost = 5, rbspMaxPrims = 1, rbspMaxDepth = -1, rbspDirections = 3; float rbspEmptyBonus = 0.f;
+    // Accelerator "rbspkd": CreateRBSPKdTreeAccelerator's parameters (accelerators/rbspKd.cpp:640-665); host side only (not baked)
+    int32_t rbspkdIsectCost = 80, rbspkdTravCost = 5, rbspkdKdTravCost = 1, rbspkdMaxPrims = 1, rbspkdMaxDepth = -1, rbspkdDirections = 3;
+    float rbspkdEmptyBonus = 0.f;
     std::string filename = "pbrt.exr", accelerator = "bvh", integrator = "path", sampler = "halton";
 };
 struct SceneModel {
