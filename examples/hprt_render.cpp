@@ -22,6 +22,26 @@
         if (rc_ != HPRT_OK) { std::fprintf(stderr, "%s failed (%d): %s\n", #call, rc_, hprt_last_error()); return 1; } \
     } while (0)
 
+// Builds the `name` tree (hprt_<name>_build through `build`), attaches it to every scene and destroys it; 1 after printing an error.
+// What the library does not walk (object instances, an unsupported "nbDirections", a tree deeper than the todo list:
+// HPRT_E_UNSUPPORTED) keeps the BVH, with a warning when `warn` (a kd-tree's case is already among the model's warnings).
+template <typename Tree, typename Build>
+static int AttachTree(const std::string &name, Build build, int (*attach)(HprtScene *, const Tree *), void (*destroy)(Tree *),
+                      const std::vector<HprtScene *> &scenes, bool warn) {
+    Tree *t = nullptr;
+    const int rc = build(&t);
+    if (rc == HPRT_E_UNSUPPORTED) {
+        if (warn) std::fprintf(stderr, "Warning: %s; \"bvh\" used\n", hprt_last_error());
+        return 0;
+    }
+    if (rc != HPRT_OK) { std::fprintf(stderr, "hprt_%s_build failed (%d): %s\n", name.c_str(), rc, hprt_last_error()); return 1; }
+    int arc = HPRT_OK;
+    for (size_t g = 0; g < scenes.size() && arc == HPRT_OK; ++g) arc = attach(scenes[g], t);
+    destroy(t);
+    if (arc != HPRT_OK) { std::fprintf(stderr, "hprt_scene_attach_%s failed (%d): %s\n", name.c_str(), arc, hprt_last_error()); return 1; }
+    return 0;
+}
+
 int main(int argc, char **argv) {
     if (argc < 3) { std::fprintf(stderr, "usage: %s scene.pbrt|scene.hprt out.pfm [--spp N] [--gpus N] [--crop x0 x1 y0 y1]\n", argv[0]); return 2; }
     const std::string scenePath = argv[1], outPath = argv[2];
@@ -60,57 +80,16 @@ int main(int argc, char **argv) {
     // one scene per GPU; rank r renders tiles r, r + N, ...
     std::vector<HprtScene *> scenes((size_t)gpus, nullptr);
     for (int g = 0; g < gpus; ++g) TRY(hprt_scene_create_from_model(model, bvh, g, &scenes[(size_t)g]));
-    // Accelerator "kdtree" (MakeAccelerator, core/api.cpp:800-814): the kd-tree is built on the host and every scene walks it.
-    // A scene with object instances keeps its BVH (the library has no two-level kd walk: HPRT_E_UNSUPPORTED; the model's
-    // warnings already say so)
+    // Accelerator "kdtree", "rbsp" or "rbspkd" (MakeAccelerator, core/api.cpp:790-831): the tree is built on the host from the
+    // scene's Accelerator line and every scene walks it
     char accel[64] = "";
     TRY(hprt_model_accelerator(model, accel, sizeof(accel)));
-    if (std::strcmp(accel, "kdtree") == 0) {
-        HprtKdTree *kd = nullptr;
-        const int rc = hprt_kdtree_build(model, &kd);
-        if (rc == HPRT_OK) {
-            int arc = HPRT_OK;
-            for (int g = 0; g < gpus && arc == HPRT_OK; ++g) arc = hprt_scene_attach_kdtree(scenes[(size_t)g], kd);
-            hprt_kdtree_destroy(kd);
-            if (arc != HPRT_OK) { std::fprintf(stderr, "hprt_scene_attach_kdtree failed (%d): %s\n", arc, hprt_last_error()); return 1; }
-        } else if (rc != HPRT_E_UNSUPPORTED) {
-            std::fprintf(stderr, "hprt_kdtree_build failed (%d): %s\n", rc, hprt_last_error());
-            return 1;
-        }
-    }
-    // Accelerator "rbsp" (core/api.cpp:817-831): the same with an RBSP tree built from the scene's Accelerator parameters.  What
-    // the library does not walk (object instances, an unsupported "nbDirections", a tree deeper than the todo list) keeps the BVH
-    if (std::strcmp(accel, "rbsp") == 0) {
-        HprtRbsp *rb = nullptr;
-        const int rc = hprt_rbsp_build(model, nullptr, &rb);
-        if (rc == HPRT_OK) {
-            int arc = HPRT_OK;
-            for (int g = 0; g < gpus && arc == HPRT_OK; ++g) arc = hprt_scene_attach_rbsp(scenes[(size_t)g], rb);
-            hprt_rbsp_destroy(rb);
-            if (arc != HPRT_OK) { std::fprintf(stderr, "hprt_scene_attach_rbsp failed (%d): %s\n", arc, hprt_last_error()); return 1; }
-        } else if (rc == HPRT_E_UNSUPPORTED) {
-            std::fprintf(stderr, "Warning: %s; \"bvh\" used\n", hprt_last_error());
-        } else {
-            std::fprintf(stderr, "hprt_rbsp_build failed (%d): %s\n", rc, hprt_last_error());
-            return 1;
-        }
-    }
-    // Accelerator "rbspkd": the same with the kd-aware RBSP tree (RBSPKd) and its own walk
-    if (std::strcmp(accel, "rbspkd") == 0) {
-        HprtRbspKd *rk = nullptr;
-        const int rc = hprt_rbspkd_build(model, nullptr, &rk);
-        if (rc == HPRT_OK) {
-            int arc = HPRT_OK;
-            for (int g = 0; g < gpus && arc == HPRT_OK; ++g) arc = hprt_scene_attach_rbspkd(scenes[(size_t)g], rk);
-            hprt_rbspkd_destroy(rk);
-            if (arc != HPRT_OK) { std::fprintf(stderr, "hprt_scene_attach_rbspkd failed (%d): %s\n", arc, hprt_last_error()); return 1; }
-        } else if (rc == HPRT_E_UNSUPPORTED) {
-            std::fprintf(stderr, "Warning: %s; \"bvh\" used\n", hprt_last_error());
-        } else {
-            std::fprintf(stderr, "hprt_rbspkd_build failed (%d): %s\n", rc, hprt_last_error());
-            return 1;
-        }
-    }
+    const std::string acc = accel;
+    int arc = 0;
+    if (acc == "kdtree") arc = AttachTree<HprtKdTree>(acc, [&](HprtKdTree **t) { return hprt_kdtree_build(model, t); }, hprt_scene_attach_kdtree, hprt_kdtree_destroy, scenes, false);
+    if (acc == "rbsp") arc = AttachTree<HprtRbsp>(acc, [&](HprtRbsp **t) { return hprt_rbsp_build(model, nullptr, t); }, hprt_scene_attach_rbsp, hprt_rbsp_destroy, scenes, true);
+    if (acc == "rbspkd") arc = AttachTree<HprtRbspKd>(acc, [&](HprtRbspKd **t) { return hprt_rbspkd_build(model, nullptr, t); }, hprt_scene_attach_rbspkd, hprt_rbspkd_destroy, scenes, true);
+    if (arc) return 1;
     // one host thread per GPU (the renders are independent; errors are thread-local in the library, so each thread keeps its own)
     std::vector<HprtRenderStats> stats((size_t)gpus);
     std::vector<int> rcs((size_t)gpus, HPRT_OK);

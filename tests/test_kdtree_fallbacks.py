@@ -151,3 +151,22 @@ def test_example_attaches_the_kdtree(hprt, example, tmp_path):
     sc.attach_kdtree(hprt.KdTree(m))
     film, _ = sc.render(opt)
     assert np.array_equal(_read_pfm(out).view(np.uint32), hprt.film_resolve(film, opt.film_scale).view(np.uint32))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("acc", ["rbsp", "rbspkd"])
+def test_example_attaches_the_rbsp_trees(hprt, example, tmp_path, acc):
+    """The same for Accelerator "rbsp" and "rbspkd": the example's image is Scene.attach_rbsp / attach_rbspkd + render's."""
+    m, path = _parse(hprt, tmp_path, KD.replace('Accelerator "kdtree"', 'Accelerator "%s"' % acc), acc + ".pbrt")
+    out = str(tmp_path / (acc + ".pfm"))
+    r = subprocess.run([example, path, out, "--spp", "2"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr
+    assert '"bvh" used' not in r.stderr, r.stderr
+    opt = m.options.copy(); opt.spp = 2
+    sc = hprt.Scene(m, hprt.Bvh(m), device=0)
+    if acc == "rbsp":
+        sc.attach_rbsp(hprt.Rbsp(m))
+    else:
+        sc.attach_rbspkd(hprt.RbspKd(m))
+    film, _ = sc.render(opt)
+    assert np.array_equal(_read_pfm(out).view(np.uint32), hprt.film_resolve(film, opt.film_scale).view(np.uint32))

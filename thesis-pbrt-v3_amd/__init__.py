@@ -124,9 +124,45 @@ class RbspKdParams(C.Structure):
                 ("max_depth", C.c_int), ("n_directions", C.c_int), ("threads", C.c_int)]
 
 
-class RbspKd:
+class _Tree:
+    """A host tree handle (KdTree, Rbsp, RbspKd) over the C calls hprt_<_prefix>_info / _copy / _destroy: info() names the info
+    words `_info_keys`; the copy of the RBSP trees takes a direction table as well (M in info)."""
+    _prefix = None
+    _info_keys = ()
+
+    def _call(self, name, *args):
+        _check(getattr(lib, "hprt_%s_%s" % (self._prefix, name))(self._h, *args))
+
+    def info(self):
+        i = (C.c_uint32 * len(self._info_keys))()
+        self._call("info", i)
+        return dict(zip(self._info_keys, i))
+
+    def arrays(self):
+        """(nodes [n, 2] uint32: word 0 split / onePrimitive / primitiveIndicesOffset, word 1 flags; prim_indices uint32)"""
+        inf = self.info()
+        nodes = np.zeros((inf["nodes"], 2), np.uint32)
+        idx = np.zeros(inf["prim_refs"], np.uint32)
+        self._call("copy", _ptr(nodes), _ptr(idx), *([None] if "M" in inf else []))
+        return nodes, idx
+
+    def _directions(self):
+        """[M, 3] float32: getDirections(M)"""
+        d = np.zeros((self.info()["M"], 3), np.float32)
+        self._call("copy", None, None, _ptr(d))
+        return d
+
+    def __del__(self):
+        if getattr(self, "_h", None) and lib is not None:      # (module globals are cleared at interpreter exit)
+            getattr(lib, "hprt_%s_destroy" % self._prefix)(self._h)
+            self._h = None
+
+
+class RbspKd(_Tree):
     """kd-aware RBSP tree (host): CreateRBSPKdTreeAccelerator(prims, params) — the RBSP node layout and direction table, with
     RBSPKd's cost model.  RbspKd(model) takes the scene's Accelerator line; keyword parameters override it."""
+    _prefix = "rbspkd"
+    _info_keys = ("nodes", "leaves", "prim_refs", "depth", "M", "kd_interior", "bsp_interior")
 
     def __init__(self, model=None, handle=None, n_directions=None, isect_cost=80, trav_cost=5, kd_trav_cost=1, empty_bonus=0.0, max_prims=1,
                  max_depth=-1, threads=0):
@@ -146,29 +182,7 @@ class RbspKd:
         _check(lib.hprt_rbspkd_build_from_triangles(p9.shape[0], _ptr(p9), C.byref(prm), C.byref(h)))
         return RbspKd(handle=h)
 
-    def info(self):
-        i = (C.c_uint32 * 7)()
-        _check(lib.hprt_rbspkd_info(self._h, i))
-        return {"nodes": i[0], "leaves": i[1], "prim_refs": i[2], "depth": i[3], "M": i[4], "kd_interior": i[5], "bsp_interior": i[6]}
-
-    def arrays(self):
-        """(nodes [n, 2] uint32, prim_indices uint32): the RBSPNode layout of Rbsp.arrays"""
-        inf = self.info()
-        nodes = np.zeros((inf["nodes"], 2), np.uint32)
-        idx = np.zeros(inf["prim_refs"], np.uint32)
-        _check(lib.hprt_rbspkd_copy(self._h, _ptr(nodes), _ptr(idx), None))
-        return nodes, idx
-
-    def directions(self):
-        """[M, 3] float32: getDirections(M)"""
-        d = np.zeros((self.info()["M"], 3), np.float32)
-        _check(lib.hprt_rbspkd_copy(self._h, None, None, _ptr(d)))
-        return d
-
-    def __del__(self):
-        if getattr(self, "_h", None) and lib is not None:      # (module globals are cleared at interpreter exit)
-            lib.hprt_rbspkd_destroy(self._h)
-            self._h = None
+    directions = _Tree._directions
 
 
 class SceneDesc(C.Structure):
@@ -397,8 +411,10 @@ class Bvh:
             self._h = None
 
 
-class KdTree:
+class KdTree(_Tree):
     """kd-tree (host): CreateKdTreeAccelerator(prims, params) — KdAccelNode[] and primitiveIndices as the reference builds them."""
+    _prefix = "kdtree"
+    _info_keys = ("nodes", "leaves", "prim_refs", "depth")
 
     def __init__(self, model=None, handle=None):
         if handle is None:
@@ -414,24 +430,6 @@ class KdTree:
                                                  max_prims, max_depth, C.byref(h)))
         return KdTree(handle=h)
 
-    def info(self):
-        i = (C.c_uint32 * 4)()
-        _check(lib.hprt_kdtree_info(self._h, i))
-        return {"nodes": i[0], "leaves": i[1], "prim_refs": i[2], "depth": i[3]}
-
-    def arrays(self):
-        """(nodes [n, 2] uint32: word 0 split / onePrimitive / primitiveIndicesOffset, word 1 flags; prim_indices uint32)"""
-        inf = self.info()
-        nodes = np.zeros((inf["nodes"], 2), np.uint32)
-        idx = np.zeros(inf["prim_refs"], np.uint32)
-        _check(lib.hprt_kdtree_copy(self._h, _ptr(nodes), _ptr(idx)))
-        return nodes, idx
-
-    def __del__(self):
-        if getattr(self, "_h", None) and lib is not None:      # (module globals are cleared at interpreter exit)
-            lib.hprt_kdtree_destroy(self._h)
-            self._h = None
-
 
 class RbspParams(C.Structure):
     """HprtRbspParams: CreateRBSPTreeAccelerator's parameters plus the builder's thread count."""
@@ -443,9 +441,11 @@ def _rbsp_params(n_directions, isect_cost, trav_cost, empty_bonus, max_prims, ma
     return RbspParams(isect_cost, trav_cost, empty_bonus, max_prims, max_depth, n_directions, threads)
 
 
-class Rbsp:
+class Rbsp(_Tree):
     """RBSP tree (host): CreateRBSPTreeAccelerator(prims, params) — RBSPNode[], primitiveIndices and the direction table as
     the reference builds them.  Rbsp(model) takes the scene's Accelerator line; keyword parameters override it."""
+    _prefix = "rbsp"
+    _info_keys = ("nodes", "leaves", "prim_refs", "depth", "M")
 
     def __init__(self, model=None, handle=None, n_directions=None, isect_cost=80, trav_cost=5, empty_bonus=0.0, max_prims=1, max_depth=-1,
                  threads=0):
@@ -464,29 +464,7 @@ class Rbsp:
         _check(lib.hprt_rbsp_build_from_triangles(p9.shape[0], _ptr(p9), C.byref(prm), C.byref(h)))
         return Rbsp(handle=h)
 
-    def info(self):
-        i = (C.c_uint32 * 5)()
-        _check(lib.hprt_rbsp_info(self._h, i))
-        return {"nodes": i[0], "leaves": i[1], "prim_refs": i[2], "depth": i[3], "M": i[4]}
-
-    def arrays(self):
-        """(nodes [n, 2] uint32: word 0 split / onePrimitive / primitiveIndicesOffset, word 1 flags; prim_indices uint32)"""
-        inf = self.info()
-        nodes = np.zeros((inf["nodes"], 2), np.uint32)
-        idx = np.zeros(inf["prim_refs"], np.uint32)
-        _check(lib.hprt_rbsp_copy(self._h, _ptr(nodes), _ptr(idx), None))
-        return nodes, idx
-
-    def directions(self):
-        """[M, 3] float32: getDirections(M)"""
-        d = np.zeros((self.info()["M"], 3), np.float32)
-        _check(lib.hprt_rbsp_copy(self._h, None, None, _ptr(d)))
-        return d
-
-    def __del__(self):
-        if getattr(self, "_h", None) and lib is not None:      # (module globals are cleared at interpreter exit)
-            lib.hprt_rbsp_destroy(self._h)
-            self._h = None
+    directions = _Tree._directions
 
 
 class Scene:

@@ -8,6 +8,7 @@
 #include <chrono>
 #include <cmath>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <memory>
 #include <string>
@@ -249,8 +250,8 @@ int hprt_scene_create(const HprtSceneDesc *d, int device, HprtScene **out) try {
 } catch (...) { return hprt::HandleException(); }
 
 // Diagnostics hook (not part of include/hprt.h): 1 when plain renders of this scene take the leaf-exact wide walk (k_walk4), else 0: the
-// binary walk, or the kd walk once a kd-tree is attached (callers test the value for truth: "is it k_walk4")
-__attribute__((visibility("default"))) int hprt_debug_scene_walk(HprtScene *s) { return s && !s->kdAttached && !s->rbspAttached && !s->rbspkdAttached && hprt::WideWalkInUse(s->dev) ? 1 : 0; }
+// binary walk, or an attached tree's walk (callers test the value for truth: "is it k_walk4")
+__attribute__((visibility("default"))) int hprt_debug_scene_walk(HprtScene *s) { return s && s->walk == HprtScene::Walk::Bvh && hprt::WideWalkInUse(s->dev) ? 1 : 0; }
 __attribute__((visibility("default"))) int hprt_debug_poison_workspace(HprtScene *s, int byte) { if (!s) return HPRT_E_INVALID; s->poisonByte = byte < 0 ? -1 : (byte & 255); return HPRT_OK; }
 // Diagnostics hook (not part of include/hprt.h): the first batch of the next hprt_render copies the rays that bounce `bounce` queues
 // (kind 0: the path segments entering bounce + 1, 1: its shadow rays, 2: its BSDF-sampled light rays) into d_out7 ([7][cap] planes:
@@ -261,15 +262,19 @@ __attribute__((visibility("default"))) int hprt_debug_capture_rays(HprtScene *s,
     return HPRT_OK;
 }
 static int ApiStreams(HprtScene *s, size_t n, RayStream *rays, HitStream *hits);
-// Every trace of a scene: the kd walk once a kd-tree is attached (hprt_scene_attach_kdtree), the RBSP walk once an RBSP tree is
-// (hprt_scene_attach_rbsp), the rbspkd walk once an rbspkd tree is (hprt_scene_attach_rbspkd), else the BVH walks (LaunchTrace)
+// Every trace of a scene: the walk of the attached tree (AttachTree below), else the BVH walks (LaunchTrace)
 static void Trace(HprtScene *s, hipStream_t st, bool anyHit, bool count, const uint32_t *queue, const uint32_t *countPtr, uint32_t countImm,
                   uint32_t gridItems, const RayStream &rays, const HitStream &hits, uint8_t *occ, DevCounters *counters, uint32_t *workCounter,
                   uint4 *rayStats = nullptr) {
-    if (s->kdAttached) LaunchKdTrace(st, s->dev, s->kd, anyHit, count, queue, countPtr, countImm, gridItems, rays, hits, occ, counters, workCounter, rayStats);
-    else if (s->rbspAttached) LaunchRbspTrace(st, s->dev, s->rbsp, anyHit, count, queue, countPtr, countImm, gridItems, rays, hits, occ, counters, workCounter, rayStats);
-    else if (s->rbspkdAttached) LaunchRbspKdTrace(st, s->dev, s->rbspkd, anyHit, count, queue, countPtr, countImm, gridItems, rays, hits, occ, counters, workCounter, rayStats);
-    else LaunchTrace(st, s->dev, anyHit, count, queue, countPtr, countImm, gridItems, rays, hits, occ, counters, workCounter, rayStats);
+    switch (s->walk) {
+    case HprtScene::Walk::Kd: LaunchKdTrace(st, s->dev, s->kd, anyHit, count, queue, countPtr, countImm, gridItems, rays, hits, occ, counters, workCounter, rayStats); break;
+    case HprtScene::Walk::Rbsp: LaunchRbspTrace(st, s->dev, s->rbsp, anyHit, count, queue, countPtr, countImm, gridItems, rays, hits, occ, counters, workCounter, rayStats); break;
+    case HprtScene::Walk::RbspKd:
+        LaunchRbspKdTrace(st, s->dev, DevRbspKd{s->rbsp, s->kdShare.as<unsigned long long>()}, anyHit, count, queue, countPtr, countImm, gridItems, rays,
+                          hits, occ, counters, workCounter, rayStats);
+        break;
+    case HprtScene::Walk::Bvh: LaunchTrace(st, s->dev, anyHit, count, queue, countPtr, countImm, gridItems, rays, hits, occ, counters, workCounter, rayStats); break;
+    }
 }
 // Diagnostics (tools/sort_experiment.py): what consuming rays through a PERMUTED index queue costs.  The n rays of d_rays7 stay where
 // they are; d_queue lists them in the order to be traced.  ms[0]: a streaming pass that gathers the rays through the queue into
@@ -398,106 +403,85 @@ __attribute__((visibility("default"))) int hprt_debug_device_math(int device, in
     return HPRT_OK;
 } catch (...) { return hprt::HandleException(); }
 
-// MakeAccelerator("kdtree") (core/api.cpp:790-830): the tree is checked, its creation-order primitive numbers are mapped to the
-// scene's ordered indices (the inverse of prim_order), and from now on every trace of the scene walks it (Trace above)
-int hprt_scene_attach_kdtree(HprtScene *s, const HprtKdTree *t) try {
-    if (!s || !t) return SetError(HPRT_E_INVALID, "hprt_scene_attach_kdtree: null argument");
-    if (s->instanced) return SetError(HPRT_E_UNSUPPORTED, "kd-trees over object instances are not supported: the scene keeps its BVH");
-    const KdTree &kt = t->tree;
-    const uint32_t nTop = (uint32_t)s->topOrder.size();
-    if (kt.nPrims != nTop)
-        return SetError(HPRT_E_INVALID, "the kd-tree holds " + std::to_string(kt.nPrims) + " primitives, the scene " + std::to_string(nTop));
-    uint32_t depth = 0;
-    const char *bad = CheckKdTree(kt, &depth);
-    if (*bad) return SetError(HPRT_E_INVALID, std::string("malformed kd-tree: ") + bad);
-    if (depth > KD_TODO_MAX)
-        return SetError(HPRT_E_UNSUPPORTED, "kd-tree of depth " + std::to_string(depth) + " is deeper than the walk's todo list (" + std::to_string((unsigned)KD_TODO_MAX) + ")");
-    std::vector<uint32_t> toOrdered(nTop);
-    for (uint32_t i = 0; i < nTop; ++i) toOrdered[s->topOrder[i]] = i;
-    std::vector<uint2> nodes(kt.nodes.size());
-    for (size_t k = 0; k < nodes.size(); ++k) {
-        const KdNode &nd = kt.nodes[k];
-        const bool onePrim = (nd.b & 3u) == 3u && (nd.b >> 2) == 1u;
-        nodes[k] = make_uint2(onePrim ? toOrdered[nd.a] : nd.a, nd.b);
-    }
-    std::vector<uint32_t> prims(kt.primIndices.size());
-    for (size_t k = 0; k < prims.size(); ++k) prims[k] = toOrdered[kt.primIndices[k]];
+// A host tree as AttachTree takes it: GenericBSP's node array over M directions (bsp_tree.h) with creation-order primitive numbers,
+// its bounds, its direction table (none for the kd-tree), the deepest tree its walk takes and the builder's structural check
+struct TreeView {
+    const char *what;                                       // the tree's name in messages
+    const std::vector<BspNode> &nodes; const std::vector<uint32_t> &primIndices; uint32_t nPrims; const float *bounds;
+    uint32_t M; const std::vector<float> *dirs; uint32_t todoMax;
+    std::function<const char *(uint32_t *depth)> check;     // CheckKdTree, CheckRbspTree
+};
+// MakeAccelerator (core/api.cpp:790-831) for the trees the host builds: the tree is checked, its creation-order primitive numbers are
+// mapped to the scene's ordered indices (the inverse of prim_order), and from now on every trace of the scene takes `walk` over it
+// (Trace above).  Until the upload has succeeded the scene walks its BVH: a failed attach never leaves a half-replaced tree behind.
+static int AttachTree(HprtScene *s, HprtScene::Walk walk, const TreeView &t) {
+    const std::string what = t.what;
+    if (s->instanced) return SetError(HPRT_E_UNSUPPORTED, what + "s over object instances are not supported: the scene keeps its BVH");
     HIP_TRY(hipSetDevice(s->device));
     SceneCall call(s, nullptr);
-    HIP_TRY(hipDeviceSynchronize());      // a render or trace of the old tree may still be running
-    HIP_TRY(upload(s->kdNodes, nodes));
-    HIP_TRY(upload(s->kdPrims, prims));
-    DevKd &kd = s->kd;
-    kd.nodes = s->kdNodes.as<uint2>(); kd.nNodes = (uint32_t)nodes.size();
-    kd.primIdx = s->kdPrims.as<uint32_t>(); kd.nPrimIdx = (uint32_t)prims.size();
-    for (int a = 0; a < 3; ++a) { kd.lo[a] = kt.bounds[a]; kd.hi[a] = kt.bounds[3 + a]; }
-    kd.depth = depth;
-    s->kdAttached = true; s->rbspAttached = false; s->rbspkdAttached = false;
-    return HPRT_OK;
-} catch (...) { return hprt::HandleException(); }
-
-// The device form of an RBSP tree (either cost model): checked, its creation-order primitive numbers mapped to the ordered
-// indices, uploaded into nodesBuf / primsBuf.  `what` names the tree in messages.
-static int UploadRbsp(HprtScene *s, const RbspTree &rt, const char *what, DevBuf &nodesBuf, DevBuf &primsBuf, DevRbsp *out) {
     const uint32_t nTop = (uint32_t)s->topOrder.size();
-    if (rt.nPrims != nTop)
-        return SetError(HPRT_E_INVALID, std::string("the ") + what + " tree holds " + std::to_string(rt.nPrims) + " primitives, the scene " + std::to_string(nTop));
+    if (t.nPrims != nTop)
+        return SetError(HPRT_E_INVALID, "the " + what + " holds " + std::to_string(t.nPrims) + " primitives, the scene " + std::to_string(nTop));
     uint32_t depth = 0;
-    const char *bad = CheckRbspTree(rt, &depth);
-    if (*bad) return SetError(HPRT_E_INVALID, std::string("malformed ") + what + " tree: " + bad);
-    if (depth > RBSP_TODO_MAX)
-        return SetError(HPRT_E_UNSUPPORTED, std::string(what) + " tree of depth " + std::to_string(depth) + " is deeper than the walk's todo list (" + std::to_string((unsigned)RBSP_TODO_MAX) + ")");
-    const uint32_t M = rt.M, off = RbspBitOffset(M), mask = RbspBitMask(M);
+    const char *bad = t.check(&depth);
+    if (*bad) return SetError(HPRT_E_INVALID, "malformed " + what + ": " + bad);
+    if (depth > t.todoMax)
+        return SetError(HPRT_E_UNSUPPORTED, what + " of depth " + std::to_string(depth) + " is deeper than the walk's todo list (" + std::to_string(t.todoMax) + ")");
+    const uint32_t off = RbspBitOffset(t.M), mask = RbspBitMask(t.M);
     std::vector<uint32_t> toOrdered(nTop);
     for (uint32_t i = 0; i < nTop; ++i) toOrdered[s->topOrder[i]] = i;
-    std::vector<uint2> nodes(rt.nodes.size());
+    std::vector<uint2> nodes(t.nodes.size());
     for (size_t k = 0; k < nodes.size(); ++k) {
-        const RbspNode &nd = rt.nodes[k];
-        const bool onePrim = (nd.b & mask) == M && (nd.b >> off) == 1u;
+        const BspNode &nd = t.nodes[k];
+        const bool onePrim = (nd.b & mask) == t.M && (nd.b >> off) == 1u;
         nodes[k] = make_uint2(onePrim ? toOrdered[nd.a] : nd.a, nd.b);
     }
-    std::vector<uint32_t> prims(rt.primIndices.size());
-    for (size_t k = 0; k < prims.size(); ++k) prims[k] = toOrdered[rt.primIndices[k]];
-    HIP_TRY(hipSetDevice(s->device));
+    std::vector<uint32_t> prims(t.primIndices.size());
+    for (size_t k = 0; k < prims.size(); ++k) prims[k] = toOrdered[t.primIndices[k]];
     HIP_TRY(hipDeviceSynchronize());      // a render or trace of the old tree may still be running
-    HIP_TRY(upload(nodesBuf, nodes));
-    HIP_TRY(upload(primsBuf, prims));
-    DevRbsp &rb = *out;
-    rb = DevRbsp{};
-    rb.nodes = nodesBuf.as<uint2>(); rb.nNodes = (uint32_t)nodes.size();
-    rb.primIdx = primsBuf.as<uint32_t>(); rb.nPrimIdx = (uint32_t)prims.size();
-    for (int a = 0; a < 3; ++a) { rb.lo[a] = rt.bounds[a]; rb.hi[a] = rt.bounds[3 + a]; }
-    rb.depth = depth; rb.M = M; rb.off = off; rb.mask = mask;
-    for (uint32_t k = 0; k < 3 * M; ++k) rb.dirs[k] = rt.directions[k];
+    s->walk = HprtScene::Walk::Bvh;
+    HIP_TRY(upload(s->treeNodes, nodes));
+    HIP_TRY(upload(s->treePrims, prims));
+    if (walk == HprtScene::Walk::RbspKd) {
+        HIP_TRY(s->kdShare.alloc(2 * sizeof(unsigned long long)));
+        HIP_TRY(hipMemset(s->kdShare.p, 0, 2 * sizeof(unsigned long long)));
+    }
+    auto fill = [&](auto &d) {      // the fields DevKd and DevRbsp share
+        d.nodes = s->treeNodes.as<uint2>(); d.nNodes = (uint32_t)nodes.size();
+        d.primIdx = s->treePrims.as<uint32_t>(); d.nPrimIdx = (uint32_t)prims.size();
+        for (int a = 0; a < 3; ++a) { d.lo[a] = t.bounds[a]; d.hi[a] = t.bounds[3 + a]; }
+        d.depth = depth;
+    };
+    if (walk == HprtScene::Walk::Kd) fill(s->kd);
+    else {
+        s->rbsp = DevRbsp{};
+        fill(s->rbsp);
+        s->rbsp.M = t.M; s->rbsp.off = off; s->rbsp.mask = mask;
+        for (uint32_t k = 0; k < 3 * t.M; ++k) s->rbsp.dirs[k] = (*t.dirs)[k];
+    }
+    s->walk = walk;
     return HPRT_OK;
 }
 
-// MakeAccelerator("rbsp") (core/api.cpp:817-831): as for the kd-tree — checked, mapped to the ordered indices, walked by every
-// later trace of the scene
+int hprt_scene_attach_kdtree(HprtScene *s, const HprtKdTree *t) try {
+    if (!s || !t) return SetError(HPRT_E_INVALID, "hprt_scene_attach_kdtree: null argument");
+    const KdTree &kt = t->tree;
+    return AttachTree(s, HprtScene::Walk::Kd, {"kd-tree", kt.nodes, kt.primIndices, kt.nPrims, kt.bounds, 3u, nullptr, (uint32_t)KD_TODO_MAX,
+                                               [&](uint32_t *depth) { return CheckKdTree(kt, depth); }});
+} catch (...) { return hprt::HandleException(); }
+// An RBSP tree (either cost model) for the RBSP walk or the rbspkd walk with its kd counter pair; `what` names it in messages
+static int AttachRbsp(HprtScene *s, HprtScene::Walk walk, const char *what, const RbspTree &rt) {
+    return AttachTree(s, walk, {what, rt.nodes, rt.primIndices, rt.nPrims, rt.bounds, rt.M, &rt.directions, (uint32_t)RBSP_TODO_MAX,
+                                [&](uint32_t *depth) { return CheckRbspTree(rt, depth); }});
+}
 int hprt_scene_attach_rbsp(HprtScene *s, const HprtRbsp *t) try {
     if (!s || !t) return SetError(HPRT_E_INVALID, "hprt_scene_attach_rbsp: null argument");
-    if (s->instanced) return SetError(HPRT_E_UNSUPPORTED, "RBSP trees over object instances are not supported: the scene keeps its BVH");
-    HIP_TRY(hipSetDevice(s->device));
-    SceneCall call(s, nullptr);
-    const int rc = UploadRbsp(s, t->tree, "RBSP", s->rbspNodes, s->rbspPrims, &s->rbsp);
-    if (rc != HPRT_OK) return rc;
-    s->rbspAttached = true; s->kdAttached = false; s->rbspkdAttached = false;
-    return HPRT_OK;
+    return AttachRbsp(s, HprtScene::Walk::Rbsp, "RBSP tree", t->tree);
 } catch (...) { return hprt::HandleException(); }
-
 // The fork's "rbspkd" accelerator (RBSPKd): the RBSP tree's checks and layout, walked by the rbspkd walk with its kd counter pair
 int hprt_scene_attach_rbspkd(HprtScene *s, const HprtRbspKd *t) try {
     if (!s || !t) return SetError(HPRT_E_INVALID, "hprt_scene_attach_rbspkd: null argument");
-    if (s->instanced) return SetError(HPRT_E_UNSUPPORTED, "rbspkd trees over object instances are not supported: the scene keeps its BVH");
-    HIP_TRY(hipSetDevice(s->device));
-    SceneCall call(s, nullptr);
-    const int rc = UploadRbsp(s, t->tree, "rbspkd", s->rbspkdNodes, s->rbspkdPrims, &s->rbspkd.t);
-    if (rc != HPRT_OK) return rc;
-    HIP_TRY(s->kdShare.alloc(2 * sizeof(unsigned long long)));
-    HIP_TRY(hipMemset(s->kdShare.p, 0, 2 * sizeof(unsigned long long)));
-    s->rbspkd.kdCounters = s->kdShare.as<unsigned long long>();
-    s->rbspkdAttached = true; s->kdAttached = false; s->rbspAttached = false;
-    return HPRT_OK;
+    return AttachRbsp(s, HprtScene::Walk::RbspKd, "rbspkd tree", t->tree);
 } catch (...) { return hprt::HandleException(); }
 
 int hprt_scene_kd_counters(HprtScene *s, uint64_t out[2]) try {
@@ -505,7 +489,7 @@ int hprt_scene_kd_counters(HprtScene *s, uint64_t out[2]) try {
     HIP_TRY(hipSetDevice(s->device));
     SceneCall call(s, nullptr);
     out[0] = out[1] = 0;
-    if (!s->rbspkdAttached) return HPRT_OK;
+    if (s->walk != HprtScene::Walk::RbspKd) return HPRT_OK;
     unsigned long long c[2];
     HIP_TRY(hipMemcpy(c, s->kdShare.p, sizeof(c), hipMemcpyDeviceToHost));
     out[0] = c[0]; out[1] = c[1];
@@ -590,7 +574,7 @@ static int TraceHost(HprtScene *s, bool anyHit, size_t n, const float *o, const 
     HIP_TRY(hipMemcpy(rays.a, ra.data(), 16 * n, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(rays.b, rb.data(), 16 * n, hipMemcpyHostToDevice));
     HIP_TRY(hipMemset(s->counters.p, 0, sizeof(DevCounters)));
-    if (s->rbspkdAttached) HIP_TRY(hipMemset(s->kdShare.p, 0, 2 * sizeof(unsigned long long)));
+    if (s->walk == HprtScene::Walk::RbspKd) HIP_TRY(hipMemset(s->kdShare.p, 0, 2 * sizeof(unsigned long long)));
     const bool count = counters != nullptr;
     if (!anyHit) {
         Trace(s, nullptr, false, count, nullptr, nullptr, (uint32_t)n, (uint32_t)n, rays, hits, nullptr, s->counters.as<DevCounters>(), s->workCounter.as<uint32_t>());
@@ -648,7 +632,7 @@ int RunBatch(HprtScene *s, hipStream_t st, const RenderParams &rp, const Workspa
              const BinSet &bins, uint32_t s0, uint32_t nSlots, bool count, EventTimer &ev, BatchTimers *bt, HprtRenderStats *stats,
              uint32_t *pixelStats = nullptr, const IrregularSink *irregular = nullptr) {
     uint4 *rayStats = pixelStats ? s->rayStats.as<uint4>() : nullptr;
-    uint32_t *pixelKd = pixelStats && s->rbspkdAttached ? s->pixelKdLocal.as<uint32_t>() : nullptr;     // the rbspkd walk's kd share
+    uint32_t *pixelKd = pixelStats && s->walk == HprtScene::Walk::RbspKd ? s->pixelKdLocal.as<uint32_t>() : nullptr;     // the rbspkd walk's kd share
     uint32_t *wcPath = s->workCounter.as<uint32_t>();
     LaunchGenerate(st, s->dev, rp, w.path[0], s0, nSlots, irregular);
     const uint32_t *activeQ = nullptr; uint32_t active = nSlots;
@@ -877,7 +861,7 @@ int hprt_render(HprtScene *s, const HprtRenderDesc *desc, float *d_film_xyzw, vo
         HIP_TRY(s->pixelStatsFilm.alloc(7ull * s->filmPixels * sizeof(uint64_t)));
         HIP_TRY(hipMemsetAsync(s->pixelStatsFilm.p, 0, 7ull * s->filmPixels * sizeof(uint64_t), st));
         pixelStats = s->pixelStatsLocal.as<uint32_t>();
-        if (s->rbspkdAttached) {
+        if (s->walk == HprtScene::Walk::RbspKd) {
             HIP_TRY(s->pixelKdLocal.alloc(2ull * nPix * sizeof(uint32_t)));
             HIP_TRY(hipMemsetAsync(s->pixelKdLocal.p, 0, 2ull * nPix * sizeof(uint32_t), st));
             HIP_TRY(s->pixelKdFilm.alloc(2ull * s->filmPixels * sizeof(uint64_t)));
@@ -886,7 +870,7 @@ int hprt_render(HprtScene *s, const HprtRenderDesc *desc, float *d_film_xyzw, vo
     }
     s->pixelStatsValid = false; s->pixelKdValid = false;
     HIP_TRY(hipMemsetAsync(s->counters.p, 0, sizeof(DevCounters), st));
-    if (s->rbspkdAttached) HIP_TRY(hipMemsetAsync(s->kdShare.p, 0, 2 * sizeof(unsigned long long), st));
+    if (s->walk == HprtScene::Walk::RbspKd) HIP_TRY(hipMemsetAsync(s->kdShare.p, 0, 2 * sizeof(unsigned long long), st));
 
     auto wall0 = std::chrono::high_resolution_clock::now();
     // ---- film footprint pre-pass ----
@@ -991,7 +975,7 @@ int hprt_render(HprtScene *s, const HprtRenderDesc *desc, float *d_film_xyzw, vo
     if (pixelStats) {
         LaunchPixelStatsToFilm(st, pixelStats, rp.pixelXY, nPix, spp, f.fg.cx0, f.fg.cy0, f.W, s->pixelStatsFilm.as<unsigned long long>());
         s->pixelStatsValid = true;
-        if (s->rbspkdAttached) {
+        if (s->walk == HprtScene::Walk::RbspKd) {
             LaunchPixelKdStatsToFilm(st, s->pixelKdLocal.as<uint32_t>(), rp.pixelXY, nPix, f.fg.cx0, f.fg.cy0, f.W, s->filmPixels,
                                      s->pixelKdFilm.as<unsigned long long>());
             s->pixelKdValid = true;

@@ -12,6 +12,7 @@
 #include <map>
 #include <memory>
 #include <string>
+#include <type_traits>
 #include "../../include/hprt.h"
 #include "bvh_builder.h"
 #include "halton_tables.h"
@@ -35,6 +36,120 @@ int HandleException() {
 }
 }  // namespace hprt
 
+namespace {
+
+// ---- the RBSP handles' builds, info and copies (hprt_rbsp_* and hprt_rbspkd_* below) ----
+// The builder's view of a model's top-level primitives: world bounds, and the three world-space vertices of each triangle
+// (Triangle::getBounds projects those; every other shape projects its world bound's corners)
+void RbspModelPrims(const HprtModel *m, std::vector<float> *lo, std::vector<float> *hi, std::vector<float> *tri9, std::vector<uint8_t> *isTri) {
+    ComputePrimBounds(m->sc, {}, lo, hi);
+    const size_t n = lo->size() / 3;
+    tri9->assign(9 * n, 0.f);
+    isTri->assign(n, 0);
+    size_t k = 0;
+    for (const TopItem &ti : m->sc.top) {
+        const ShapeDesc &sh = m->sc.shapes[ti.index];
+        if (sh.kind != kTriangleMesh) { ++k; continue; }
+        const MeshData &md = sh.mesh;
+        for (uint32_t tr = 0; tr < md.nTris(); ++tr, ++k) {
+            for (int v = 0; v < 3; ++v) memcpy(&(*tri9)[9 * k + 3 * v], &md.P[3 * (size_t)md.indices[3 * tr + v]], 12);
+            (*isTri)[k] = 1;
+        }
+    }
+}
+// WorldBound of a triangle: Union(Bounds3f(p0, p1), p2) (shapes/triangle.cpp:180-186)
+void RbspTriangleBounds(size_t n, const float *p9, std::vector<float> *lo, std::vector<float> *hi) {
+    lo->resize(3 * n); hi->resize(3 * n);
+    for (size_t i = 0; i < n; ++i)
+        for (int d = 0; d < 3; ++d) {
+            const float a = p9[9 * i + d], b = p9[9 * i + 3 + d], c = p9[9 * i + 6 + d];
+            const float l = std::min(a, b), h = std::max(a, b);
+            (*lo)[3 * i + d] = std::min(l, c); (*hi)[3 * i + d] = std::max(h, c);
+        }
+}
+// Handle HprtRbsp with Params HprtRbspParams, or HprtRbspKd (the kd-aware cost model) with HprtRbspKdParams; params NULL keeps p
+template <typename Handle, typename Params>
+int BuildRbsp(size_t n, const float *lo, const float *hi, const float *tri9, const uint8_t *isTri, const Params *params, RbspParams p,
+                     Handle **out) {
+    constexpr bool kdAware = std::is_same<Handle, HprtRbspKd>::value;
+    p.kdAware = kdAware;
+    if (params) {
+        p.isectCost = params->isect_cost; p.travCost = params->trav_cost; p.emptyBonus = params->empty_bonus;
+        p.maxPrims = params->max_prims; p.maxDepth = params->max_depth; p.nDirections = params->n_directions; p.threads = params->threads;
+        if constexpr (kdAware) p.kdTravCost = params->kd_trav_cost;
+    }
+    if (p.nDirections != 3 && p.nDirections != 7 && p.nDirections != 9 && p.nDirections != 13)
+        return SetError(HPRT_E_UNSUPPORTED, "nbDirections " + std::to_string(p.nDirections) + " is not supported (3, 7, 9 or 13)");
+    std::unique_ptr<Handle> t(new Handle());
+    const std::string err = BuildRbspTree(n, lo, hi, tri9, isTri, p, &t->tree);
+    if (!err.empty()) return SetError(HPRT_E_UNSUPPORTED, err);
+    if (t->tree.depth > RBSP_TODO_MAX)
+        return SetError(HPRT_E_UNSUPPORTED, "RBSP tree of depth " + std::to_string(t->tree.depth) + " is deeper than the device walk's todo list (" +
+                                                std::to_string((unsigned)RBSP_TODO_MAX) + " entries); lower \"maxdepth\"");
+    *out = t.release();
+    return HPRT_OK;
+}
+// hprt_rbsp_build / hprt_rbspkd_build: the model's primitives and its Accelerator line (dflt); `what` names the tree in messages
+template <typename Handle, typename Params>
+int BuildRbspFromModel(const char *fn, const char *what, const HprtModel *m, const Params *params, const RbspParams &dflt, Handle **out) {
+    if (!m || !out) return SetError(HPRT_E_INVALID, std::string(fn) + ": null argument");
+    if (m->sc.nObjects != 0 || !m->sc.instances.empty())
+        return SetError(HPRT_E_UNSUPPORTED, std::string(what) + " trees over object instances are not supported (the scene keeps its BVH)");
+    std::vector<float> lo, hi, tri9;
+    std::vector<uint8_t> isTri;
+    RbspModelPrims(m, &lo, &hi, &tri9, &isTri);
+    return BuildRbsp(lo.size() / 3, lo.data(), hi.data(), tri9.data(), isTri.data(), params, dflt, out);
+}
+template <typename Handle, typename Params>
+int BuildRbspFromTriangles(const char *fn, size_t n, const float *p9, const Params *params, Handle **out) {
+    if (!out || (n && !p9)) return SetError(HPRT_E_INVALID, std::string(fn) + ": null argument");
+    if (n > 0x3fffffffull) return SetError(HPRT_E_UNSUPPORTED, "more than 2^30 primitives");
+    std::vector<float> lo, hi;
+    RbspTriangleBounds(n, p9, &lo, &hi);
+    std::vector<uint8_t> isTri(n, 1);
+    return BuildRbsp(n, lo.data(), hi.data(), p9, isTri.data(), params, RbspParams(), out);
+}
+// info[0..4] of either handle; info[5..6] (kd / oblique interior nodes) only for an rbspkd tree
+int RbspInfo(const char *fn, const RbspTree *t, uint32_t *info, bool kdSplit) {
+    if (!t || !info) return SetError(HPRT_E_INVALID, std::string(fn) + ": null argument");
+    info[0] = (uint32_t)t->nodes.size(); info[1] = t->leaves; info[2] = (uint32_t)t->primIndices.size();
+    info[3] = t->depth; info[4] = t->M;
+    if (kdSplit) RbspInteriorCounts(*t, &info[5], &info[6]);
+    return HPRT_OK;
+}
+int RbspCopy(const char *fn, const RbspTree *t, void *nodes8, uint32_t *primIndices, float *directions) {
+    if (!t) return SetError(HPRT_E_INVALID, std::string(fn) + ": null argument");
+    if (nodes8) memcpy(nodes8, t->nodes.data(), t->nodes.size() * sizeof(RbspNode));
+    if (primIndices && !t->primIndices.empty()) memcpy(primIndices, t->primIndices.data(), t->primIndices.size() * 4);
+    if (directions) memcpy(directions, t->directions.data(), t->directions.size() * 4);
+    return HPRT_OK;
+}
+
+// Film::WriteGeneralStats (core/film.cpp:170-187) with WriteGeneralStatMatrix (:189-210): the eight matrices, each to
+// "<prefix>-<name>.txt", one image row per line; value(k, i): matrix k's value at pixel i (row-major)
+template <typename Value>
+int WriteStatMatrices(const char *prefix, int width, int height, Value value) {
+    static const char *const kNames[8] = {"primitiveIntersections", "primitiveIntersectionsP", "kdTreeNodeTraversals", "kdTreeNodeTraversalsP",
+                                          "bspTreeNodeTraversals", "bspTreeNodeTraversalsP", "leafNodeTraversals", "leafNodeTraversalsP"};
+    for (int k = 0; k < 8; ++k) {
+        const std::string path = std::string(prefix) + "-" + kNames[k] + ".txt";
+        FILE *fp = fopen(path.c_str(), "w");
+        if (!fp) return SetError(HPRT_E_IO, "cannot create " + path);
+        bool ok = true;
+        for (int y = 0; y < height && ok; ++y) {
+            for (int x = 0; x < width; ++x) {
+                const unsigned long long v = value(k, (size_t)y * width + x);
+                ok = ok && fprintf(fp, x ? " %llu" : "%llu", v) > 0;
+            }
+            ok = ok && fputc('\n', fp) != EOF;
+        }
+        if (fclose(fp) != 0) ok = false;
+        if (!ok) return SetError(HPRT_E_IO, "write error on " + path);
+    }
+    return HPRT_OK;
+}
+}  // namespace
+
 extern "C" {
 
 const char *hprt_last_error(void) { return g_lastError.c_str(); }
@@ -48,14 +163,13 @@ int hprt_model_parse(const char *pbrt_path, const char *const *subst, int n_subs
     HprtModel *m = new HprtModel();
     std::string err;
     if (!ParsePbrtFile(pbrt_path, sm, &m->sc, &err)) { delete m; return SetError(HPRT_E_PARSE, err); }
-    // a kd-tree over object instances is not built (hprt_kdtree_build: HPRT_E_UNSUPPORTED): such a scene keeps the BVH and the warning
-    if (m->sc.opt.accelerator == "kdtree" && m->sc.nObjects == 0 && m->sc.instances.empty())
-        m->sc.warnings.push_back("Accelerator \"kdtree\": the host builds the tree (hprt_kdtree_build) and attaches it to the scene (hprt_scene_attach_kdtree); a scene without it walks a BVH");
-    else if (m->sc.opt.accelerator == "rbsp" && m->sc.nObjects == 0 && m->sc.instances.empty())
-        m->sc.warnings.push_back("Accelerator \"rbsp\": the host builds the tree (hprt_rbsp_build) and attaches it to the scene (hprt_scene_attach_rbsp); a scene without it walks a BVH");
-    else if (m->sc.opt.accelerator == "rbspkd" && m->sc.nObjects == 0 && m->sc.instances.empty())
-        m->sc.warnings.push_back("Accelerator \"rbspkd\": the host builds the tree (hprt_rbspkd_build) and attaches it to the scene (hprt_scene_attach_rbspkd); a scene without it walks a BVH");
-    else if (m->sc.opt.accelerator != "bvh") m->sc.warnings.push_back("Accelerator \"" + m->sc.opt.accelerator + "\" is outside the hot-path scope; \"bvh\" used");
+    // a tree over object instances is not built (hprt_<accelerator>_build: HPRT_E_UNSUPPORTED): such a scene keeps the BVH and the warning
+    static const char *const kTreeAccelerators[] = {"kdtree", "rbsp", "rbspkd"};
+    const std::string &acc = m->sc.opt.accelerator;
+    if (std::count(std::begin(kTreeAccelerators), std::end(kTreeAccelerators), acc) && m->sc.nObjects == 0 && m->sc.instances.empty())
+        m->sc.warnings.push_back("Accelerator \"" + acc + "\": the host builds the tree (hprt_" + acc + "_build) and attaches it to the scene (hprt_scene_attach_" +
+                                 acc + "); a scene without it walks a BVH");
+    else if (acc != "bvh") m->sc.warnings.push_back("Accelerator \"" + acc + "\" is outside the hot-path scope; \"bvh\" used");
     if (m->sc.opt.integrator != "path") m->sc.warnings.push_back("Integrator \"" + m->sc.opt.integrator + "\" is outside the hot-path scope; \"path\" used");
     if (m->sc.opt.sampler != "halton") m->sc.warnings.push_back("Sampler \"" + m->sc.opt.sampler + "\" is outside the hot-path scope; \"halton\" used");
     *out = m;
@@ -192,11 +306,8 @@ int hprt_kdtree_build(const HprtModel *m, HprtKdTree **out) try {
     if (m->sc.nObjects != 0 || !m->sc.instances.empty()) return SetError(HPRT_E_UNSUPPORTED, "kd-trees over object instances are not supported (the scene keeps its BVH)");
     std::vector<float> lo, hi;
     ComputePrimBounds(m->sc, {}, &lo, &hi);
-    const RenderOptions &o = m->sc.opt;
-    KdParams p;
-    p.isectCost = o.kdIsectCost; p.travCost = o.kdTravCost; p.emptyBonus = o.kdEmptyBonus; p.maxPrims = o.kdMaxPrims; p.maxDepth = o.kdMaxDepth;
     HprtKdTree *t = new HprtKdTree();
-    BuildKdTree(lo.size() / 3, lo.data(), hi.data(), p, &t->tree);
+    BuildKdTree(lo.size() / 3, lo.data(), hi.data(), m->sc.opt.kd, &t->tree);
     return FinishKdTree(t, out);
 } catch (...) { return hprt::HandleException(); }
 int hprt_kdtree_build_from_bounds(size_t n, const float *bmin, const float *bmax, int isectCost, int travCost, float emptyBonus,
@@ -222,139 +333,31 @@ int hprt_kdtree_copy(const HprtKdTree *t, void *nodes8, uint32_t *primIndices) t
 } catch (...) { return hprt::HandleException(); }
 void hprt_kdtree_destroy(HprtKdTree *t) { delete t; }
 
-// ---- RBSP tree (Accelerator "rbsp") and kd-aware RBSP tree (Accelerator "rbspkd") ----
-static int BuildRbspChecked(size_t n, const float *lo, const float *hi, const float *tri9, const uint8_t *isTri, const RbspParams &p, RbspTree *out) {
-    if (p.nDirections != 3 && p.nDirections != 7 && p.nDirections != 9 && p.nDirections != 13)
-        return SetError(HPRT_E_UNSUPPORTED, "nbDirections " + std::to_string(p.nDirections) + " is not supported (3, 7, 9 or 13)");
-    const std::string err = BuildRbspTree(n, lo, hi, tri9, isTri, p, out);
-    if (!err.empty()) return SetError(HPRT_E_UNSUPPORTED, err);
-    if (out->depth > RBSP_TODO_MAX)
-        return SetError(HPRT_E_UNSUPPORTED, "RBSP tree of depth " + std::to_string(out->depth) + " is deeper than the device walk's todo list (" +
-                                                std::to_string((unsigned)RBSP_TODO_MAX) + " entries); lower \"maxdepth\"");
-    return HPRT_OK;
-}
-static int BuildRbsp(size_t n, const float *lo, const float *hi, const float *tri9, const uint8_t *isTri, const HprtRbspParams *params,
-                     const RbspParams &dflt, HprtRbsp **out) {
-    RbspParams p = dflt;
-    if (params) {
-        p.isectCost = params->isect_cost; p.travCost = params->trav_cost; p.emptyBonus = params->empty_bonus;
-        p.maxPrims = params->max_prims; p.maxDepth = params->max_depth; p.nDirections = params->n_directions; p.threads = params->threads;
-    }
-    std::unique_ptr<HprtRbsp> t(new HprtRbsp());
-    const int rc = BuildRbspChecked(n, lo, hi, tri9, isTri, p, &t->tree);
-    if (rc != HPRT_OK) return rc;
-    *out = t.release();
-    return HPRT_OK;
-}
-static int BuildRbspKd(size_t n, const float *lo, const float *hi, const float *tri9, const uint8_t *isTri, const HprtRbspKdParams *params,
-                       const RbspParams &dflt, HprtRbspKd **out) {
-    RbspParams p = dflt;
-    p.kdAware = true;
-    if (params) {
-        p.isectCost = params->isect_cost; p.travCost = params->trav_cost; p.kdTravCost = params->kd_trav_cost; p.emptyBonus = params->empty_bonus;
-        p.maxPrims = params->max_prims; p.maxDepth = params->max_depth; p.nDirections = params->n_directions; p.threads = params->threads;
-    }
-    std::unique_ptr<HprtRbspKd> t(new HprtRbspKd());
-    const int rc = BuildRbspChecked(n, lo, hi, tri9, isTri, p, &t->tree);
-    if (rc != HPRT_OK) return rc;
-    *out = t.release();
-    return HPRT_OK;
-}
-// The builder's view of a model's top-level primitives: world bounds, and the three world-space vertices of each triangle
-// (Triangle::getBounds projects those; every other shape projects its world bound's corners)
-static void RbspModelPrims(const HprtModel *m, std::vector<float> *lo, std::vector<float> *hi, std::vector<float> *tri9, std::vector<uint8_t> *isTri) {
-    ComputePrimBounds(m->sc, {}, lo, hi);
-    const size_t n = lo->size() / 3;
-    tri9->assign(9 * n, 0.f);
-    isTri->assign(n, 0);
-    size_t k = 0;
-    for (const TopItem &ti : m->sc.top) {
-        const ShapeDesc &sh = m->sc.shapes[ti.index];
-        if (sh.kind != kTriangleMesh) { ++k; continue; }
-        const MeshData &md = sh.mesh;
-        for (uint32_t tr = 0; tr < md.nTris(); ++tr, ++k) {
-            for (int v = 0; v < 3; ++v) memcpy(&(*tri9)[9 * k + 3 * v], &md.P[3 * (size_t)md.indices[3 * tr + v]], 12);
-            (*isTri)[k] = 1;
-        }
-    }
-}
-// WorldBound of a triangle: Union(Bounds3f(p0, p1), p2) (shapes/triangle.cpp:180-186)
-static void RbspTriangleBounds(size_t n, const float *p9, std::vector<float> *lo, std::vector<float> *hi) {
-    lo->resize(3 * n); hi->resize(3 * n);
-    for (size_t i = 0; i < n; ++i)
-        for (int d = 0; d < 3; ++d) {
-            const float a = p9[9 * i + d], b = p9[9 * i + 3 + d], c = p9[9 * i + 6 + d];
-            const float l = std::min(a, b), h = std::max(a, b);
-            (*lo)[3 * i + d] = std::min(l, c); (*hi)[3 * i + d] = std::max(h, c);
-        }
-}
+// ---- RBSP tree (Accelerator "rbsp") and kd-aware RBSP tree (Accelerator "rbspkd"): one RbspTree, two handle types (helpers above) ----
 int hprt_rbsp_build(const HprtModel *m, const HprtRbspParams *params, HprtRbsp **out) try {
-    if (!m || !out) return SetError(HPRT_E_INVALID, "hprt_rbsp_build: null argument");
-    if (m->sc.nObjects != 0 || !m->sc.instances.empty()) return SetError(HPRT_E_UNSUPPORTED, "RBSP trees over object instances are not supported (the scene keeps its BVH)");
-    std::vector<float> lo, hi, tri9;
-    std::vector<uint8_t> isTri;
-    RbspModelPrims(m, &lo, &hi, &tri9, &isTri);
-    const RenderOptions &o = m->sc.opt;
-    RbspParams p;
-    p.isectCost = o.rbspIsectCost; p.travCost = o.rbspTravCost; p.emptyBonus = o.rbspEmptyBonus;
-    p.maxPrims = o.rbspMaxPrims; p.maxDepth = o.rbspMaxDepth; p.nDirections = o.rbspDirections;
-    return BuildRbsp(lo.size() / 3, lo.data(), hi.data(), tri9.data(), isTri.data(), params, p, out);
+    return BuildRbspFromModel("hprt_rbsp_build", "RBSP", m, params, m ? m->sc.opt.rbsp : RbspParams(), out);
 } catch (...) { return hprt::HandleException(); }
 int hprt_rbsp_build_from_triangles(size_t n, const float *p9, const HprtRbspParams *params, HprtRbsp **out) try {
-    if (!out || (n && !p9)) return SetError(HPRT_E_INVALID, "hprt_rbsp_build_from_triangles: null argument");
-    if (n > 0x3fffffffull) return SetError(HPRT_E_UNSUPPORTED, "more than 2^30 primitives");
-    std::vector<float> lo, hi;
-    RbspTriangleBounds(n, p9, &lo, &hi);
-    std::vector<uint8_t> isTri(n, 1);
-    return BuildRbsp(n, lo.data(), hi.data(), p9, isTri.data(), params, RbspParams(), out);
+    return BuildRbspFromTriangles("hprt_rbsp_build_from_triangles", n, p9, params, out);
 } catch (...) { return hprt::HandleException(); }
 int hprt_rbsp_info(const HprtRbsp *t, uint32_t info[5]) try {
-    if (!t || !info) return SetError(HPRT_E_INVALID, "hprt_rbsp_info: null argument");
-    info[0] = (uint32_t)t->tree.nodes.size(); info[1] = t->tree.leaves; info[2] = (uint32_t)t->tree.primIndices.size();
-    info[3] = t->tree.depth; info[4] = t->tree.M;
-    return HPRT_OK;
+    return RbspInfo("hprt_rbsp_info", t ? &t->tree : nullptr, info, false);
 } catch (...) { return hprt::HandleException(); }
 int hprt_rbsp_copy(const HprtRbsp *t, void *nodes8, uint32_t *primIndices, float *directions) try {
-    if (!t) return SetError(HPRT_E_INVALID, "hprt_rbsp_copy: null argument");
-    if (nodes8) memcpy(nodes8, t->tree.nodes.data(), t->tree.nodes.size() * sizeof(RbspNode));
-    if (primIndices && !t->tree.primIndices.empty()) memcpy(primIndices, t->tree.primIndices.data(), t->tree.primIndices.size() * 4);
-    if (directions) memcpy(directions, t->tree.directions.data(), t->tree.directions.size() * 4);
-    return HPRT_OK;
+    return RbspCopy("hprt_rbsp_copy", t ? &t->tree : nullptr, nodes8, primIndices, directions);
 } catch (...) { return hprt::HandleException(); }
 void hprt_rbsp_destroy(HprtRbsp *t) { delete t; }
 int hprt_rbspkd_build(const HprtModel *m, const HprtRbspKdParams *params, HprtRbspKd **out) try {
-    if (!m || !out) return SetError(HPRT_E_INVALID, "hprt_rbspkd_build: null argument");
-    if (m->sc.nObjects != 0 || !m->sc.instances.empty()) return SetError(HPRT_E_UNSUPPORTED, "rbspkd trees over object instances are not supported (the scene keeps its BVH)");
-    std::vector<float> lo, hi, tri9;
-    std::vector<uint8_t> isTri;
-    RbspModelPrims(m, &lo, &hi, &tri9, &isTri);
-    const RenderOptions &o = m->sc.opt;
-    RbspParams p;
-    p.isectCost = o.rbspkdIsectCost; p.travCost = o.rbspkdTravCost; p.kdTravCost = o.rbspkdKdTravCost; p.emptyBonus = o.rbspkdEmptyBonus;
-    p.maxPrims = o.rbspkdMaxPrims; p.maxDepth = o.rbspkdMaxDepth; p.nDirections = o.rbspkdDirections;
-    return BuildRbspKd(lo.size() / 3, lo.data(), hi.data(), tri9.data(), isTri.data(), params, p, out);
+    return BuildRbspFromModel("hprt_rbspkd_build", "rbspkd", m, params, m ? m->sc.opt.rbspkd : RbspParams(), out);
 } catch (...) { return hprt::HandleException(); }
 int hprt_rbspkd_build_from_triangles(size_t n, const float *p9, const HprtRbspKdParams *params, HprtRbspKd **out) try {
-    if (!out || (n && !p9)) return SetError(HPRT_E_INVALID, "hprt_rbspkd_build_from_triangles: null argument");
-    if (n > 0x3fffffffull) return SetError(HPRT_E_UNSUPPORTED, "more than 2^30 primitives");
-    std::vector<float> lo, hi;
-    RbspTriangleBounds(n, p9, &lo, &hi);
-    std::vector<uint8_t> isTri(n, 1);
-    return BuildRbspKd(n, lo.data(), hi.data(), p9, isTri.data(), params, RbspParams(), out);
+    return BuildRbspFromTriangles("hprt_rbspkd_build_from_triangles", n, p9, params, out);
 } catch (...) { return hprt::HandleException(); }
 int hprt_rbspkd_info(const HprtRbspKd *t, uint32_t info[7]) try {
-    if (!t || !info) return SetError(HPRT_E_INVALID, "hprt_rbspkd_info: null argument");
-    info[0] = (uint32_t)t->tree.nodes.size(); info[1] = t->tree.leaves; info[2] = (uint32_t)t->tree.primIndices.size();
-    info[3] = t->tree.depth; info[4] = t->tree.M;
-    RbspInteriorCounts(t->tree, &info[5], &info[6]);
-    return HPRT_OK;
+    return RbspInfo("hprt_rbspkd_info", t ? &t->tree : nullptr, info, true);
 } catch (...) { return hprt::HandleException(); }
 int hprt_rbspkd_copy(const HprtRbspKd *t, void *nodes8, uint32_t *primIndices, float *directions) try {
-    if (!t) return SetError(HPRT_E_INVALID, "hprt_rbspkd_copy: null argument");
-    if (nodes8) memcpy(nodes8, t->tree.nodes.data(), t->tree.nodes.size() * sizeof(RbspNode));
-    if (primIndices && !t->tree.primIndices.empty()) memcpy(primIndices, t->tree.primIndices.data(), t->tree.primIndices.size() * 4);
-    if (directions) memcpy(directions, t->tree.directions.data(), t->tree.directions.size() * 4);
-    return HPRT_OK;
+    return RbspCopy("hprt_rbspkd_copy", t ? &t->tree : nullptr, nodes8, primIndices, directions);
 } catch (...) { return hprt::HandleException(); }
 void hprt_rbspkd_destroy(HprtRbspKd *t) { delete t; }
 int hprt_bvh_info(const HprtBvh *b, uint32_t info[4], float bounds6[6]) try {
@@ -503,36 +506,18 @@ int hprt_film_resolve(const float *xyzw, size_t n, float scale, float *rgb) try 
     return HPRT_OK;
 } catch (...) { return hprt::HandleException(); }
 
-// Film::WriteGeneralStatMatrix, core/film.cpp:189-210: "<file minus extension>-<name>.txt", one image row per line
 int hprt_write_pixel_stats(const char *prefix, const uint64_t *stats7, int width, int height) try {
     return hprt_write_pixel_stats_accel(prefix, stats7, width, height, HPRT_ACCEL_BVH);
 } catch (...) { return hprt::HandleException(); }
 int hprt_write_pixel_stats_accel(const char *prefix, const uint64_t *stats7, int width, int height, int accel) try {
     if (!prefix || !stats7 || width <= 0 || height <= 0) return SetError(HPRT_E_INVALID, "hprt_write_pixel_stats: bad argument");
     if (accel != HPRT_ACCEL_BVH && accel != HPRT_ACCEL_KDTREE && accel != HPRT_ACCEL_RBSP) return SetError(HPRT_E_INVALID, "hprt_write_pixel_stats_accel: unknown accelerator");
-    // the matrices Film::WriteGeneralStats writes (core/film.cpp:170-187), with the index of the value in stats7 (-1: zero for this
-    // accelerator): a kd render's interior-node counts (slots 5, 6) are its kdTreeNodeTraversals[P]
+    // per matrix, the index of its value in stats7 (-1: zero for this accelerator): a kd render's interior-node counts (slots 5, 6)
+    // are its kdTreeNodeTraversals[P], an RBSP render's its bspTreeNodeTraversals[P]
     const int kd = accel == HPRT_ACCEL_KDTREE ? 5 : -1, kdP = accel == HPRT_ACCEL_KDTREE ? 6 : -1;
-    const int bsp = accel == HPRT_ACCEL_RBSP ? 5 : -1, bspP = accel == HPRT_ACCEL_RBSP ? 6 : -1;   // an RBSP render's: bspTreeNodeTraversals[P]
-    const struct { const char *name; int field; } kMatrices[] = {
-        {"primitiveIntersections", 1}, {"primitiveIntersectionsP", 2}, {"kdTreeNodeTraversals", kd}, {"kdTreeNodeTraversalsP", kdP},
-        {"bspTreeNodeTraversals", bsp}, {"bspTreeNodeTraversalsP", bspP}, {"leafNodeTraversals", 3}, {"leafNodeTraversalsP", 4}};
-    for (const auto &m : kMatrices) {
-        const std::string path = std::string(prefix) + "-" + m.name + ".txt";
-        FILE *fp = fopen(path.c_str(), "w");
-        if (!fp) return SetError(HPRT_E_IO, "cannot create " + path);
-        bool ok = true;
-        for (int y = 0; y < height && ok; ++y) {
-            for (int x = 0; x < width; ++x) {
-                const unsigned long long v = m.field < 0 ? 0ull : (unsigned long long)stats7[7 * ((size_t)y * width + x) + m.field];
-                ok = ok && fprintf(fp, x ? " %llu" : "%llu", v) > 0;
-            }
-            ok = ok && fputc('\n', fp) != EOF;
-        }
-        if (fclose(fp) != 0) ok = false;
-        if (!ok) return SetError(HPRT_E_IO, "write error on " + path);
-    }
-    return HPRT_OK;
+    const int bsp = accel == HPRT_ACCEL_RBSP ? 5 : -1, bspP = accel == HPRT_ACCEL_RBSP ? 6 : -1;
+    const int field[8] = {1, 2, kd, kdP, bsp, bspP, 3, 4};
+    return WriteStatMatrices(prefix, width, height, [&](int k, size_t i) { return field[k] < 0 ? 0ull : (unsigned long long)stats7[7 * i + field[k]]; });
 } catch (...) { return hprt::HandleException(); }
 
 // An rbspkd render's matrices: the kd share of slots 5 / 6 from kd2, the rest of them (oblique interior nodes) as bsp
@@ -542,28 +527,12 @@ int hprt_write_pixel_stats_rbspkd(const char *prefix, const uint64_t *stats7, co
     for (size_t i = 0; i < nPix; ++i)
         if (kd2[i] > stats7[7 * i + 5] || kd2[nPix + i] > stats7[7 * i + 6])
             return SetError(HPRT_E_INVALID, "hprt_write_pixel_stats_rbspkd: a pixel's kd share exceeds its interior-node count");
-    // field: slot of stats7; kdPlane: 0 / 1 the kd plane itself, 2 / 3 slot minus that plane, -1 none
-    const struct { const char *name; int field, kdPlane; } kMatrices[] = {
-        {"primitiveIntersections", 1, -1}, {"primitiveIntersectionsP", 2, -1}, {"kdTreeNodeTraversals", -1, 0}, {"kdTreeNodeTraversalsP", -1, 1},
-        {"bspTreeNodeTraversals", 5, 0}, {"bspTreeNodeTraversalsP", 6, 1}, {"leafNodeTraversals", 3, -1}, {"leafNodeTraversalsP", 4, -1}};
-    for (const auto &m : kMatrices) {
-        const std::string path = std::string(prefix) + "-" + m.name + ".txt";
-        FILE *fp = fopen(path.c_str(), "w");
-        if (!fp) return SetError(HPRT_E_IO, "cannot create " + path);
-        bool ok = true;
-        for (int y = 0; y < height && ok; ++y) {
-            for (int x = 0; x < width; ++x) {
-                const size_t i = (size_t)y * width + x;
-                const unsigned long long kd = m.kdPlane < 0 ? 0ull : (unsigned long long)kd2[(size_t)m.kdPlane * nPix + i];
-                const unsigned long long v = m.field < 0 ? kd : (unsigned long long)stats7[7 * i + m.field] - kd;
-                ok = ok && fprintf(fp, x ? " %llu" : "%llu", v) > 0;
-            }
-            ok = ok && fputc('\n', fp) != EOF;
-        }
-        if (fclose(fp) != 0) ok = false;
-        if (!ok) return SetError(HPRT_E_IO, "write error on " + path);
-    }
-    return HPRT_OK;
+    // field: slot of stats7; kdPlane: the plane of kd2 that is the matrix (field -1) or is subtracted from the slot, -1 none
+    const int field[8] = {1, 2, -1, -1, 5, 6, 3, 4}, kdPlane[8] = {-1, -1, 0, 1, 0, 1, -1, -1};
+    return WriteStatMatrices(prefix, width, height, [&](int k, size_t i) {
+        const unsigned long long kd = kdPlane[k] < 0 ? 0ull : (unsigned long long)kd2[(size_t)kdPlane[k] * nPix + i];
+        return field[k] < 0 ? kd : (unsigned long long)stats7[7 * i + field[k]] - kd;
+    });
 } catch (...) { return hprt::HandleException(); }
 
 // WritePFM, core/imageio.cpp:437+ : "PF", width height, scale -1 (little endian), rows bottom to top

@@ -171,23 +171,13 @@ __global__ __launch_bounds__(HPRT_KD_BLOCK, QUAD ? HPRT_KD_QUAD_WAVES : HPRT_KD_
     if (COUNT) wave_count_add(counters, ANY_HIT, cnt);
 }
 
-static inline uint32_t kd_blocks_for(size_t n, uint32_t bs) { return (uint32_t)((n + bs - 1) / bs); }
-
 void LaunchKdTrace(hipStream_t st, const DevScene &sc, const DevKd &kd, bool anyHit, bool count, const uint32_t *queue,
                    const uint32_t *countPtr, uint32_t countImm, uint32_t gridItems, const RayStream &rays, const HitStream &hits,
                    uint8_t *occ, DevCounters *counters, uint32_t *workCounter, uint4 *rayStats) {
-    if (gridItems == 0) return;
-    (void)hipMemsetAsync(workCounter, 0, sizeof(uint32_t), st);
-    // persistent waves: as many workgroups per CU on 256 CUs as the variant is compiled for, never more than the rays need
-    const bool quad = sc.nSpheres != 0u;
-    const uint32_t perCu = quad ? HPRT_KD_QUAD_WAVES : HPRT_KD_WAVES;
-    dim3 grid(std::min(kd_blocks_for(gridItems, HPRT_KD_BLOCK), 256u * perCu)), block(HPRT_KD_BLOCK);
-#define HPRT_KD_LAUNCH(A, C, Q) hipLaunchKernelGGL((k_kdwalk<A, C, Q>), grid, block, 0, st, sc, kd, queue, countPtr, countImm, rays, hits, occ, counters, rayStats, workCounter)
-#define HPRT_KD_PICK(A) do { if (count) { if (quad) HPRT_KD_LAUNCH(A, true, true); else HPRT_KD_LAUNCH(A, true, false); } \
-                             else { if (quad) HPRT_KD_LAUNCH(A, false, true); else HPRT_KD_LAUNCH(A, false, false); } } while (0)
-    if (anyHit) HPRT_KD_PICK(true); else HPRT_KD_PICK(false);
-#undef HPRT_KD_PICK
-#undef HPRT_KD_LAUNCH
+    LaunchTreeWalk<HPRT_KD_BLOCK, HPRT_KD_WAVES, HPRT_KD_QUAD_WAVES>(st, sc, anyHit, count, gridItems, workCounter, [&](dim3 grid, dim3 block, auto a, auto c, auto q) {
+        hipLaunchKernelGGL((k_kdwalk<decltype(a)::value, decltype(c)::value, decltype(q)::value>), grid, block, 0, st, sc, kd, queue, countPtr, countImm, rays,
+                           hits, occ, counters, rayStats, workCounter);
+    });
 }
 
 }  // namespace hprt

@@ -1,6 +1,8 @@
 // hprt device side — kernel parameter blocks and launcher prototypes (kernels.hip).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <algorithm>
+#include <type_traits>
 #include "dev_shading.h"
 
 namespace hprt {
@@ -81,6 +83,20 @@ bool WideWalkInUse(const DevScene &sc);      // plain renders of this scene take
 void LaunchTrace(hipStream_t st, const DevScene &sc, bool anyHit, bool count, const uint32_t *queue, const uint32_t *countPtr,
                  uint32_t countImm, uint32_t gridItems, const RayStream &rays, const HitStream &hits, uint8_t *occ,
                  DevCounters *counters, uint32_t *workCounter, uint4 *rayStats = nullptr);
+// Host side of the tree walks' launchers (kd_walk.hip, rbsp_walk.hip, rbspkd_walk.hip), each called from the file that defines its
+// kernel: the work counter reset, the persistent grid (as many BLOCK-thread workgroups per CU on 256 CUs as the variant is
+// compiled for, WAVES or QUAD_WAVES, never more than the rays need) and the pick of the kernel's <ANY_HIT, COUNT, QUAD>
+// instantiation: launch(grid, block, std::integral_constant<bool, ANY_HIT>, ..COUNT, ..QUAD) starts it.
+template <uint32_t BLOCK, uint32_t WAVES, uint32_t QUAD_WAVES, typename Launch>
+void LaunchTreeWalk(hipStream_t st, const DevScene &sc, bool anyHit, bool count, uint32_t gridItems, uint32_t *workCounter, Launch launch) {
+    if (gridItems == 0) return;
+    (void)hipMemsetAsync(workCounter, 0, sizeof(uint32_t), st);
+    const bool quad = sc.nSpheres != 0u;
+    const dim3 grid(std::min((uint32_t)(((size_t)gridItems + BLOCK - 1) / BLOCK), 256u * (quad ? QUAD_WAVES : WAVES))), block(BLOCK);
+    auto pickQuad = [&](auto a, auto c) { if (quad) launch(grid, block, a, c, std::true_type{}); else launch(grid, block, a, c, std::false_type{}); };
+    auto pickCount = [&](auto a) { if (count) pickQuad(a, std::true_type{}); else pickQuad(a, std::false_type{}); };
+    if (anyHit) pickCount(std::true_type{}); else pickCount(std::false_type{});
+}
 void LaunchPixelStats(hipStream_t st, const uint4 *rayStats, const float4 *ids, const uint32_t *queue, const uint32_t *countPtr,
                       uint32_t countImm, uint32_t gridItems, uint32_t nPix, bool anyHit, uint32_t *pix);
 void LaunchPixelStatsToFilm(hipStream_t st, const uint32_t *pix, const uint32_t *pixelXY, uint32_t nPix, uint32_t spp, int cx0, int cy0, int width,

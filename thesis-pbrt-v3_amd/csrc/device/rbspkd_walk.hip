@@ -79,17 +79,10 @@ static inline uint32_t rbspkd_blocks_for(size_t n, uint32_t bs) { return (uint32
 void LaunchRbspKdTrace(hipStream_t st, const DevScene &sc, const DevRbspKd &rb, bool anyHit, bool count, const uint32_t *queue,
                        const uint32_t *countPtr, uint32_t countImm, uint32_t gridItems, const RayStream &rays, const HitStream &hits,
                        uint8_t *occ, DevCounters *counters, uint32_t *workCounter, uint4 *rayStats) {
-    if (gridItems == 0) return;
-    (void)hipMemsetAsync(workCounter, 0, sizeof(uint32_t), st);
-    const bool quad = sc.nSpheres != 0u;
-    const uint32_t perCu = quad ? HPRT_RBSPKD_QUAD_WAVES : HPRT_RBSPKD_WAVES;
-    dim3 grid(std::min(rbspkd_blocks_for(gridItems, HPRT_RBSPKD_BLOCK), 256u * perCu)), block(HPRT_RBSPKD_BLOCK);
-#define HPRT_RBSPKD_LAUNCH(A, C, Q) hipLaunchKernelGGL((k_rbspkdwalk<A, C, Q>), grid, block, 0, st, sc, rb, queue, countPtr, countImm, rays, hits, occ, counters, rayStats, workCounter)
-#define HPRT_RBSPKD_PICK(A) do { if (count) { if (quad) HPRT_RBSPKD_LAUNCH(A, true, true); else HPRT_RBSPKD_LAUNCH(A, true, false); } \
-                                 else { if (quad) HPRT_RBSPKD_LAUNCH(A, false, true); else HPRT_RBSPKD_LAUNCH(A, false, false); } } while (0)
-    if (anyHit) HPRT_RBSPKD_PICK(true); else HPRT_RBSPKD_PICK(false);
-#undef HPRT_RBSPKD_PICK
-#undef HPRT_RBSPKD_LAUNCH
+    LaunchTreeWalk<HPRT_RBSPKD_BLOCK, HPRT_RBSPKD_WAVES, HPRT_RBSPKD_QUAD_WAVES>(st, sc, anyHit, count, gridItems, workCounter, [&](dim3 grid, dim3 block, auto a, auto c, auto q) {
+        hipLaunchKernelGGL((k_rbspkdwalk<decltype(a)::value, decltype(c)::value, decltype(q)::value>), grid, block, 0, st, sc, rb, queue, countPtr, countImm, rays,
+                           hits, occ, counters, rayStats, workCounter);
+    });
 }
 
 // k_pixel_stats (kernels.hip) for the kd share: the same ray -> pixel mapping, rayStats.w added to pixKd[anyHit][p]

@@ -88,15 +88,15 @@ struct HprtScene {
     uint32_t *hostCounts = nullptr;                   // pinned
     size_t filmPixels = 0;
     uint32_t nPrims = 0;
-    // hprt_scene_attach_kdtree: the kd walk replaces the BVH walks of every trace (kdNodes / kdPrims back `kd`); topOrder keeps
-    // the top-level prim_order (ordered -> creation number) to map the tree's creation-order primitives; instanced: no kd walk
-    hprt::DevBuf kdNodes, kdPrims; hprt::DevKd kd{}; bool kdAttached = false;
-    // hprt_scene_attach_rbsp: the same for an RBSP tree; attaching either tree detaches the other
-    hprt::DevBuf rbspNodes, rbspPrims; hprt::DevRbsp rbsp{}; bool rbspAttached = false;
-    // hprt_scene_attach_rbspkd: the same for a kd-aware RBSP tree; attaching any of the three trees detaches the others.  kdShare:
-    // its kd counter pair (DevRbspKd::kdCounters); pixelKdLocal / pixelKdFilm: the per-pixel kd share of HPRT_RENDER_PIXEL_STATS
-    hprt::DevBuf rbspkdNodes, rbspkdPrims, kdShare; hprt::DevRbspKd rbspkd{}; bool rbspkdAttached = false;
-    hprt::DevBuf pixelKdLocal, pixelKdFilm; bool pixelKdValid = false;
+    // The walk every trace of the scene takes (Trace, capi_device.hip): the BVH walks until an hprt_scene_attach_* call attaches a
+    // tree (AttachTree), whose walk then replaces them; attaching a tree replaces the one before.  treeNodes / treePrims back the
+    // attached tree's descriptor: `kd` for the kd walk, `rbsp` for the RBSP and rbspkd walks.  kdShare: the rbspkd walk's kd
+    // counter pair (DevRbspKd::kdCounters); pixelKdLocal / pixelKdFilm: its per-pixel kd share of HPRT_RENDER_PIXEL_STATS.
+    // topOrder keeps the top-level prim_order (ordered -> creation number) to map a tree's creation-order primitives; instanced:
+    // no tree walk
+    enum class Walk { Bvh, Kd, Rbsp, RbspKd } walk = Walk::Bvh;
+    hprt::DevBuf treeNodes, treePrims; hprt::DevKd kd{}; hprt::DevRbsp rbsp{};
+    hprt::DevBuf kdShare, pixelKdLocal, pixelKdFilm; bool pixelKdValid = false;
     std::vector<uint32_t> topOrder; bool instanced = false;
     bool hasSubstrateBin = false;                     // some triangle carries BIN_SUBSTRATE: the substrate shading variant is launched
     ~HprtScene() { if (hostCounts) (void)hipHostFree(hostCounts); if (lastUse) (void)hipEventDestroy(lastUse); }

@@ -155,30 +155,7 @@ void BuildKdTree(size_t n, const float *bmin, const float *bmax, const KdParams 
 }
 
 const char *CheckKdTree(const KdTree &t, uint32_t *depthOut) {
-    const size_t n = t.nodes.size();
-    if (n == 0) return "the tree has no nodes";
-    if (n > 0x3fffffffu) return "too many nodes";
-    // children always follow their parent (below child = next node, above child further on), so depths fill back to front
-    std::vector<uint32_t> depth(n, 0);
-    for (size_t k = n; k-- > 0;) {
-        const KdNode &nd = t.nodes[k];
-        if ((nd.b & 3u) == 3u) {
-            const uint32_t np = nd.b >> 2;
-            if (np == 1) { if (nd.a >= t.nPrims) return "a one-primitive leaf names a primitive that does not exist"; }
-            else if (np > 1) {
-                if ((uint64_t)nd.a + np > t.primIndices.size()) return "a leaf's primitive range runs past primitiveIndices";
-                for (uint32_t i = 0; i < np; ++i)
-                    if (t.primIndices[nd.a + i] >= t.nPrims) return "primitiveIndices names a primitive that does not exist";
-            }
-        } else {
-            const uint32_t above = nd.b >> 2;
-            if (k + 1 >= n) return "an interior node has no below child";
-            if (above <= k + 1 || above >= n) return "an interior node's above child is out of range";
-            depth[k] = 1 + std::max(depth[k + 1], depth[above]);
-        }
-    }
-    if (depthOut) *depthOut = depth[0];
-    return "";
+    return CheckBspNodes(t.nodes, t.primIndices, t.nPrims, 3u, 2u, 3u, depthOut);      // KdAccelNode: M = 3 (bsp_tree.h)
 }
 
 }  // namespace hprt

@@ -5,14 +5,15 @@
 #include <cstddef>
 #include <cstdint>
 #include <vector>
+#include "bsp_tree.h"
 
 namespace hprt {
 
 // KdAccelNode (accelerators/kdtreeaccel.cpp:44-160), 8 bytes:
 //   a: interior split (float bits) | leaf onePrimitive (one primitive) | leaf primitiveIndicesOffset (more than one) | 0 (empty leaf)
 //   b: interior axis | aboveChild << 2;  leaf 3 | nPrimitives << 2
-struct KdNode { uint32_t a, b; };
-static_assert(sizeof(KdNode) == 8, "KdNode must be 8 bytes");
+// (bsp_tree.h's node with M = 3)
+using KdNode = BspNode;
 
 // Deepest tree the device walk takes (its todo list holds at most the tree's depth): pbrt's maxTodo
 // (accelerators/kdtreeaccel.cpp:393).  A deeper tree is refused, never truncated.

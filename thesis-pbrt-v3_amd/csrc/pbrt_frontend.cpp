@@ -618,37 +618,22 @@ struct Frontend {
         o.maxNodePrims = accelParams.oneInt("maxnodeprims", 4);
         o.isectCost = accelParams.oneInt("intersectcost", 8);
         o.travCost = accelParams.oneInt("traversalcost", 1);
-        if (sc->opt.accelerator == "kdtree") {
-            // CreateKdTreeAccelerator, accelerators/kdtreeaccel.cpp:523-545.  splitalpha, alphatype, axisselectiontype and
-            // axisselectionamount feed only statistics there (buildTree never reads them): accepted and ignored
-            o.kdIsectCost = accelParams.oneInt("intersectcost", 80);
-            o.kdTravCost = accelParams.oneInt("traversalcost", 1);
-            o.kdEmptyBonus = accelParams.oneFloat("emptybonus", 0.f);
-            o.kdMaxPrims = accelParams.oneInt("maxprims", 1);
-            o.kdMaxDepth = accelParams.oneInt("maxdepth", -1);
+        // The tree accelerators: CreateKdTreeAccelerator (accelerators/kdtreeaccel.cpp:523-545), CreateRBSPTreeAccelerator
+        // (accelerators/rbsp.cpp:549-571) and CreateRBSPKdTreeAccelerator (accelerators/rbspKd.cpp:640-665, rbsp's parameters plus
+        // "kdtraversalcost"); p holds the accelerator's defaults (KdParams, RbspParams).  splitalpha, alphatype, axisselectiontype
+        // and axisselectionamount feed only statistics there (buildTree never reads them): accepted and ignored
+        auto treeParams = [&](auto &p) {
+            p.isectCost = accelParams.oneInt("intersectcost", p.isectCost);
+            p.travCost = accelParams.oneInt("traversalcost", p.travCost);
+            p.emptyBonus = accelParams.oneFloat("emptybonus", p.emptyBonus);
+            p.maxPrims = accelParams.oneInt("maxprims", p.maxPrims);
+            p.maxDepth = accelParams.oneInt("maxdepth", p.maxDepth);
             for (const char *n : {"splitalpha", "alphatype", "axisselectiontype", "axisselectionamount"}) (void)accelParams.find(n, "float", "integer");
-        }
-        if (sc->opt.accelerator == "rbsp") {
-            // CreateRBSPTreeAccelerator, accelerators/rbsp.cpp:549-571; the statistics-only four are accepted and ignored, as for kdtree
-            o.rbspIsectCost = accelParams.oneInt("intersectcost", 80);
-            o.rbspTravCost = accelParams.oneInt("traversalcost", 5);
-            o.rbspEmptyBonus = accelParams.oneFloat("emptybonus", 0.f);
-            o.rbspMaxPrims = accelParams.oneInt("maxprims", 1);
-            o.rbspMaxDepth = accelParams.oneInt("maxdepth", -1);
-            o.rbspDirections = accelParams.oneInt("nbDirections", 3);
-            for (const char *n : {"splitalpha", "alphatype", "axisselectiontype", "axisselectionamount"}) (void)accelParams.find(n, "float", "integer");
-        }
-        if (sc->opt.accelerator == "rbspkd") {
-            // CreateRBSPKdTreeAccelerator, accelerators/rbspKd.cpp:640-665: rbsp's parameters plus "kdtraversalcost"
-            o.rbspkdIsectCost = accelParams.oneInt("intersectcost", 80);
-            o.rbspkdTravCost = accelParams.oneInt("traversalcost", 5);
-            o.rbspkdKdTravCost = accelParams.oneInt("kdtraversalcost", 1);
-            o.rbspkdEmptyBonus = accelParams.oneFloat("emptybonus", 0.f);
-            o.rbspkdMaxPrims = accelParams.oneInt("maxprims", 1);
-            o.rbspkdMaxDepth = accelParams.oneInt("maxdepth", -1);
-            o.rbspkdDirections = accelParams.oneInt("nbDirections", 3);
-            for (const char *n : {"splitalpha", "alphatype", "axisselectiontype", "axisselectionamount"}) (void)accelParams.find(n, "float", "integer");
-        }
+        };
+        auto rbspParams = [&](RbspParams &p) { treeParams(p); p.nDirections = accelParams.oneInt("nbDirections", p.nDirections); };
+        if (sc->opt.accelerator == "kdtree") treeParams(o.kd);
+        if (sc->opt.accelerator == "rbsp") rbspParams(o.rbsp);
+        if (sc->opt.accelerator == "rbspkd") { rbspParams(o.rbspkd); o.rbspkd.kdTravCost = accelParams.oneInt("kdtraversalcost", o.rbspkd.kdTravCost); }
         reportUnused(filmParams, "Film", {"diagonal"});
         reportUnused(filterParams, "PixelFilter");
         reportUnused(cameraParams, "Camera");

@@ -442,32 +442,7 @@ const char *CheckRbspTree(const RbspTree &t, uint32_t *depthOut) {
     const uint32_t M = t.M;
     if (M != 3 && M != 7 && M != 9 && M != 13) return "the tree's direction count is not 3, 7, 9 or 13";
     if (t.directions.size() != 3 * (size_t)M) return "the direction table does not hold M directions";
-    const uint32_t off = RbspBitOffset(M), mask = RbspBitMask(M);
-    const size_t n = t.nodes.size();
-    if (n == 0) return "the tree has no nodes";
-    if (n >= (1ull << (32 - off))) return "too many nodes for the child offset field";
-    // children always follow their parent (below child = next node, above child further on), so depths fill back to front
-    std::vector<uint32_t> depth(n, 0);
-    for (size_t k = n; k-- > 0;) {
-        const RbspNode &nd = t.nodes[k];
-        if ((nd.b & mask) == M) {
-            const uint32_t np = nd.b >> off;
-            if (np == 1) { if (nd.a >= t.nPrims) return "a one-primitive leaf names a primitive that does not exist"; }
-            else if (np > 1) {
-                if ((uint64_t)nd.a + np > t.primIndices.size()) return "a leaf's primitive range runs past primitiveIndices";
-                for (uint32_t i = 0; i < np; ++i)
-                    if (t.primIndices[nd.a + i] >= t.nPrims) return "primitiveIndices names a primitive that does not exist";
-            }
-        } else {
-            if ((nd.b & mask) > M) return "an interior node's direction is out of range";
-            const uint32_t above = nd.b >> off;
-            if (k + 1 >= n) return "an interior node has no below child";
-            if (above <= k + 1 || above >= n) return "an interior node's above child is out of range";
-            depth[k] = 1 + std::max(depth[k + 1], depth[above]);
-        }
-    }
-    if (depthOut) *depthOut = depth[0];
-    return "";
+    return CheckBspNodes(t.nodes, t.primIndices, t.nPrims, M, RbspBitOffset(M), RbspBitMask(M), depthOut);
 }
 
 }  // namespace hprt

@@ -8,14 +8,14 @@
 #include <cstdint>
 #include <string>
 #include <vector>
+#include "bsp_tree.h"
 
 namespace hprt {
 
 // RBSPNode (accelerators/rbsp.cpp:15-160), 8 bytes; off = 32 - clz(M) (2, 3, 4, 4 for M = 3, 7, 9, 13), mask = (1 << off) - 1:
 //   a: interior split (float bits) | leaf onePrimitive (one primitive) | leaf primitiveIndicesOffset (more than one) | 0 (empty leaf)
 //   b: interior axis | aboveChild << off;  leaf M | nPrimitives << off.  A node is a leaf iff (b & mask) == M.
-struct RbspNode { uint32_t a, b; };
-static_assert(sizeof(RbspNode) == 8, "RbspNode must be 8 bytes");
+using RbspNode = BspNode;                 // (bsp_tree.h)
 
 // Deepest tree the device walk takes: pbrt's maxTodo (accelerators/rbsp.cpp:416).  A deeper tree is refused, never truncated.
 enum : uint32_t { RBSP_TODO_MAX = 64u, RBSP_MAX_DIRECTIONS = 13u };

@@ -8,6 +8,8 @@
 #include <string>
 #include <vector>
 #include "hprt_math.h"
+#include "kdtree_builder.h"
+#include "rbsp_builder.h"
 
 namespace hprt {
 
@@ -86,13 +88,10 @@ struct RenderOptions {
     int32_t spp = 16, samplePixelCenter = 0;
     int32_t maxDepth = 5; float rrThreshold = 1.f; int32_t lightStrategy = kSpatial;
     int32_t maxNodePrims = 4, isectCost = 8, travCost = 1;
-    // Accelerator "kdtree": CreateKdTreeAccelerator's parameters (accelerators/kdtreeaccel.cpp:523-545); host side only (not baked)
-    int32_t kdIsectCost = 80, kdTravCost = 1, kdMaxPrims = 1, kdMaxDepth = -1; float kdEmptyBonus = 0.f;
-    // Accelerator "rbsp": CreateRBSPTreeAccelerator's parameters (accelerators/rbsp.cpp:549-571); host side only (not baked)
-    int32_t rbspIsectCost = 80, rbspTravCost = 5, rbspMaxPrims = 1, rbspMaxDepth = -1, rbspDirections = 3; float rbspEmptyBonus = 0.f;
-    // Accelerator "rbspkd": CreateRBSPKdTreeAccelerator's parameters (accelerators/rbspKd.cpp:640-665); host side only (not baked)
-    int32_t rbspkdIsectCost = 80, rbspkdTravCost = 5, rbspkdKdTravCost = 1, rbspkdMaxPrims = 1, rbspkdMaxDepth = -1, rbspkdDirections = 3;
-    float rbspkdEmptyBonus = 0.f;
+    // Accelerator "kdtree" / "rbsp" / "rbspkd": the parameters of CreateKdTreeAccelerator (accelerators/kdtreeaccel.cpp:523-545),
+    // CreateRBSPTreeAccelerator (accelerators/rbsp.cpp:549-571) and CreateRBSPKdTreeAccelerator (accelerators/rbspKd.cpp:640-665),
+    // each read only for its own accelerator; host side only (not baked)
+    KdParams kd; RbspParams rbsp, rbspkd;
     std::string filename = "pbrt.exr", accelerator = "bvh", integrator = "path", sampler = "halton";
 };
 struct SceneModel {
