@@ -5,7 +5,7 @@ HEADLINE workload (config.workload) = BASELINE.json configs[2], the largest sing
 geometry and textures are git-ignored), so the geometry is a STAND-IN, labelled as such everywhere: the procedural
 312 k-triangle atrium of tools/scene_gen.py (two storeys of arcades, tessellated columns and arches, curtains; matte and
 plastic; one point light as scenes/sponza has), 700x700, Halton 1024 spp, PathIntegrator maxdepth 5, Accelerator "bvh".
-Secondary workloads ride in the same JSON line (`secondary`): configs[1] killeroo-simple 256 spp (the reference's own asset,
+With --full, secondary workloads ride in the same JSON line (`secondary`): configs[1] killeroo-simple 256 spp (the reference's own asset,
 baked), configs[3]'s class — the reference's living-room meshes at 1280x720 with the image textures it ships, at that
 configuration's 2,048 spp — and configs[4] as SURVEY.md §8(d)-5 defines it (the killeroo mesh x 301 ObjectInstances, 10.01 M
 triangles) at its 4,096 spp; each with its own `roofline` and `cpu_baseline`.
@@ -25,7 +25,14 @@ the number of distinct devices the ranks sit on, and `config.film_merge` says wh
 
 Rays = closest-hit + shadow rays, as the reference counts them (core/scene.cpp:40-55), TRACED rays only.
 
-Extra objects in the line:
+A plain run does only what the headline figure needs: it sets up the headline workload, warms up, times the steps, writes
+--dump-outputs / --dump-film if asked and prints the line.  Everything else the bench measures runs only with --full, after the
+timed steps: the `roofline` object (its counting renders, which also give `reference_rays_per_step`, and its in-process
+probes), the frames that trace every reference ray (`with_every_reference_ray_traced`), the `secondary` workloads and the
+`cpu_baseline`; --no-secondary, --no-cpu-baseline and --no-trace-all leave parts of that out.  Without --full these fields are
+null (`secondary` empty) and the line says `"full": false`.
+
+Extra objects in the line (--full):
   roofline      dominant kernel = the closest-hit walk that ran (`kernel`): k_walk4<closest>, the leaf-exact four-wide walk of plain renders
                 (DESIGN.md section 4), or k_trace<closest>, the binary walk (HPRT_WIDE_WALK=0).  `walk` = what k_walk4 fetched per ray, counted by ONE
                 untimed render of its own phase-profile variant: 64-byte wide records stepped, primitive records tested, 16-byte requests.
@@ -144,9 +151,12 @@ def parse_args():
     ap.add_argument("--spp", type=int, default=0, help="samples per pixel of the headline workload (0: the configuration's own)")
     ap.add_argument("--spp-chunk", type=int, default=0)
     ap.add_argument("--weak", action="store_true", help="weak scaling: spp x N (default: fixed total spp, strong scaling)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary workloads")
-    ap.add_argument("--no-trace-all", action="store_true", help="skip the comparison frames that trace every reference ray")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure everything beyond the headline figure: roofline (counting renders, "
+                         "probes, counter summary), the frames that trace every reference ray, the secondary workloads, the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the secondary workloads")
+    ap.add_argument("--no-trace-all", action="store_true", help="with --full: skip the comparison frames that trace every reference ray")
     ap.add_argument("--profile-step", action="store_true",
                     help="profiling runs: ONE plain step of the headline workload and nothing else (no warm-up, counting passes, "
                          "secondary workloads or CPU baseline), so that a rocprofv3 summary of the process is the summary of a step")
@@ -559,7 +569,7 @@ def main():
 
     # ---- on-box HBM stream bandwidth (a float4 copy of 4 GiB, far beyond the 256 MB MALL): the peak a stream kernel reaches HERE ----
     stream_gbs = None
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         import ctypes as C
         try:
             fn = hprt.lib.hprt_debug_stream_copy
@@ -573,7 +583,7 @@ def main():
     # ---- on-box gather ceiling: dependent per-lane fetches of 64-byte records over a BVH-like pick, in k_trace<closest>'s launch
     # shape and with no arithmetic (kernels.hip, k_gather_probe); the table has as many records as the scene's BVH has child pairs ----
     gather_peak = None
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         import ctypes as C
         try:
             bi = head.bvh.info()
@@ -594,7 +604,7 @@ def main():
         except Exception as e:
             gather_peak = {"error": repr(e)}
         torch.cuda.empty_cache()
-    lib_hash = code_object_hash(hprt.LIB_PATH)
+    lib_hash = code_object_hash(hprt.LIB_PATH) if args.full else None
 
     def attach_counters(roof, workload, live):
         """Measured figures of the SAME kernels from the committed rocprofv3 summary (rocprofv3 cannot run inside this process):
@@ -675,8 +685,8 @@ def main():
             roof["counters_error"] = repr(e)
 
     roofline = cpu_baseline = trace_all_info = None
-    ref_over_traced = 1.0
-    if rank == 0 and world == 1:
+    ref_over_traced = None
+    if args.full and rank == 0 and world == 1:
         roofline, ref_over_traced = kernel_figures(head, stats)
         attach_counters(roofline, args.workload, live=True)
         if not args.no_trace_all:
@@ -690,7 +700,7 @@ def main():
     # secondary workloads (same line, not the headline)
     # =========================================================================================
     secondary = []
-    if not args.no_secondary:
+    if args.full and not args.no_secondary:
         for name in [n for n in SECONDARY if n != args.workload] + (["atrium"] if args.workload != "atrium" else []):
             d2, spp2, cpu2, label2 = WORKLOADS[name]
             spp2 = spp2 * (world if args.weak else 1)
@@ -713,7 +723,7 @@ def main():
             del del_w
             torch.cuda.empty_cache()
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu_baseline = cpu_port(args.workload, cpu_spp, spp, sweep=True)
     if dist is not None:
         dist.barrier()
@@ -731,9 +741,9 @@ def main():
             # rays actually traced.  The reference's PathIntegrator traces more: BSDF-sampled light rays that provably cannot reach
             # the emitter and the segment behind a path's last vertex are not traced here (same film, bit for bit), nor counted.
             "rays_per_step": int(total_rays / max(1, args.steps)),
-            "reference_rays_per_step": int(total_rays * ref_over_traced / max(1, args.steps)) if world == 1 else None,
+            "reference_rays_per_step": int(total_rays * ref_over_traced / max(1, args.steps)) if ref_over_traced is not None else None,
             "with_every_reference_ray_traced": trace_all_info,
-            "roofline": roofline, "cpu_baseline": cpu_baseline, "secondary": secondary,
+            "roofline": roofline, "cpu_baseline": cpu_baseline, "secondary": secondary, "full": bool(args.full),
         }
         if cpu_baseline:
             # same frame on both sides: ratio of frame rates (the CPU port traces the reference's full ray set)

@@ -49,3 +49,29 @@ def test_bench_dumps_the_film_of_its_last_timed_step(tmp_path, killeroo_oracle):
     _, film0, _, _, _ = killeroo_oracle.render(spp=4, threads=16)
     killeroo_oracle.set_film(crop=(0, 1, 0, 1), spp=8)
     assert np.array_equal(got.view(np.uint32), film0.view(np.uint32))
+
+
+def test_full_is_off_by_default(monkeypatch):
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1"])
+    assert bench.parse_args().full is False
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--full", "--no-secondary"])
+    a = bench.parse_args()
+    assert a.full is True and a.no_secondary is True
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_measures_the_headline_only():
+    """Without --full the line carries the headline figures and none of the extras: no roofline, secondary workloads, CPU
+    baseline, trace-all frames or reference ray count (that one comes from a counting render)."""
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", "killeroo-simple", "--spp", "4", "--steps", "1",
+           "--warmup", "1"]
+    r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert line["metric"] == "Mrays/s" and line["unit"] == "Mrays/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+    assert line["value"] > 0 and line["ms_per_step"] > 0 and line["steps"] == 1 and line["warmup"] == 1 and line["rays_per_step"] > 0
+    assert line["full"] is False and line["secondary"] == []
+    for k in ("roofline", "cpu_baseline", "with_every_reference_ray_traced", "reference_rays_per_step"):
+        assert line[k] is None, k

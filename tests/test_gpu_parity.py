@@ -518,14 +518,14 @@ def test_few_waves_working_through_many_queue_chunks(tmp_path, killeroo_oracle):
 
 
 def test_bench_line_holds_fractions_of_measured_peaks():
-    """One short single-GPU run of bench.py: every figure the `roofline` object calls a fraction is one (of a peak measured or
+    """One short single-GPU run of bench.py --full: every figure the `roofline` object calls a fraction is one (of a peak measured or
     specified: never above 1), the two probes it runs inside the process report plausible MI355X rates, and the committed counter
     summary carries the stamp that `counters_stale` is decided by."""
     import json, os, subprocess, sys
     from conftest import ROOT
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "killeroo-simple", "--steps", "1", "--warmup", "1", "--no-secondary", "--no-cpu-baseline",
-           "--no-trace-all"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "killeroo-simple", "--steps", "1", "--warmup", "1", "--full", "--no-secondary",
+           "--no-cpu-baseline", "--no-trace-all"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])

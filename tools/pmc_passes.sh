@@ -6,7 +6,7 @@ OUT=$R/gpurun_out/${1:-pmc}
 SPP=${2:-64}
 mkdir -p $OUT
 run() { # name, counters
-  timeout -k 10 300 rocprofv3 --kernel-trace --pmc $2 --output-format csv -d $OUT/$1 -- python3 $R/bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-trace-all --spp $SPP > $OUT/$1.log 2>&1
+  timeout -k 10 300 rocprofv3 --kernel-trace --pmc $2 --output-format csv -d $OUT/$1 -- python3 $R/bench.py --steps 1 --warmup 0 --full --no-cpu-baseline --no-trace-all --spp $SPP > $OUT/$1.log 2>&1
   echo "$1 rc=$?"
 }
 run p1 "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_THREAD_CYCLES_VALU"

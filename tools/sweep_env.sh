@@ -5,7 +5,7 @@ make -s -C oracle
 timeout -k 10 300 python -m pytest tests/test_gpu_parity.py tests/test_gpu_scenes.py -m gpu -x -q 2>&1 | tail -3 || exit 1
 VAR=$1; shift
 for v in "$@"; do
-  env $VAR=$v timeout -k 10 200 python bench.py --steps 2 --warmup 1 --no-cpu-baseline 2>/dev/null | python3 -c "
+  env $VAR=$v timeout -k 10 200 python bench.py --steps 2 --warmup 1 --full --no-cpu-baseline 2>/dev/null | python3 -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):
