@@ -211,6 +211,41 @@ int hprt_rbspkd_copy(const HprtRbspKd *t, void *nodes8, uint32_t *prim_indices, 
 void hprt_rbspkd_destroy(HprtRbspKd *t);
 
 /* ------------------------------------------------------------------------ */
+/* General BSP tree (Accelerator "bsppaper").  Stands in for                */
+/* BSPPaper::buildTree (accelerators/bspPaper.cpp:34-305), the BSP tree of  */
+/* Ize, Wald and Parker (2008): split planes are the three axis planes and, */
+/* per triangle, its own plane and the three planes through its edges       */
+/* perpendicular to it; the node's k-DOP (whose direction list grows along  */
+/* the path) is the surface of the cost model, and a BVH over the node's    */
+/* primitives counts them for a triangle plane.  Byte-identical to the      */
+/* reference's 20-byte BSPNode[] (word 0 split / onePrimitive /             */
+/* primitiveIndicesOffset; word 1 flags: leaf 1 | nPrims << 1, interior     */
+/* aboveChild << 1; words 2-4 the split axis, zero for leaves) and          */
+/* primitiveIndices.  "nbDirections" only feeds a statistic and is ignored. */
+/* ------------------------------------------------------------------------ */
+typedef struct HprtBspPaper HprtBspPaper;
+typedef struct HprtBspPaperParams {
+    int isect_cost;     /* "intersectcost", default 80 */
+    int trav_cost;      /* "traversalcost", default 5 */
+    float empty_bonus;  /* "emptybonus", default 0 */
+    int max_prims;      /* "maxprims", default 1 */
+    int max_depth;      /* "maxdepth", default -1 = round(2 + 1.6 Log2Int(N)) */
+    int threads;        /* builder threads (0: OMP_NUM_THREADS, else 16; at most 16); the tree does not depend on it */
+} HprtBspPaperParams;
+/* params NULL: the scene's Accelerator line (baked models report "bvh" and get the defaults).  Models with object
+ * instances: HPRT_E_UNSUPPORTED.  A tree deeper than HPRT_BSPPAPER_MAX_DEPTH: HPRT_E_UNSUPPORTED. */
+int hprt_bsppaper_build(const HprtModel *m, const HprtBspPaperParams *params, HprtBspPaper **out);
+/* The same over n triangles (9 floats each: three world-space vertices, creation order); params NULL: the defaults. */
+int hprt_bsppaper_build_from_triangles(size_t n_tris, const float *p9, const HprtBspPaperParams *params, HprtBspPaper **out);
+/* info[0..5] = nodes, leaves, depth (interior levels of the deepest path), primitive references (primitiveIndices entries),
+ * interior nodes of the axis sweep, interior nodes on a triangle's plane */
+int hprt_bsppaper_info(const HprtBspPaper *t, uint32_t info[6]);
+#define HPRT_BSPPAPER_MAX_DEPTH 64     /* the device walk's todo capacity: pbrt's maxTodo (BSP.cpp) */
+/* nodes20: info[0] * 20 bytes (5 words per node, the reference's BSPNode); prim_indices: info[3] uint32 (either may be NULL) */
+int hprt_bsppaper_copy(const HprtBspPaper *t, void *nodes20, uint32_t *prim_indices);
+void hprt_bsppaper_destroy(HprtBspPaper *t);
+
+/* ------------------------------------------------------------------------ */
 /* Device scene.  Upload step that follows the BVH build: stands in for the  */
 /* `primitives`/`nodes` members BVHAccel keeps (accelerators/bvh.h:69-79) and */
 /* the Scene object (core/scene.h:50-80).  The library copies everything to   */
@@ -337,6 +372,11 @@ int hprt_scene_attach_rbsp(HprtScene *s, const HprtRbsp *t);
  * tests; HPRT_RENDER_PIXEL_STATS slots 5 / 6 hold every interior node too.  The kd share comes from
  * hprt_scene_kd_counters and hprt_pixel_kd_stats_read. */
 int hprt_scene_attach_rbspkd(HprtScene *s, const HprtRbspKd *t);
+/* The same for a general BSP tree (BSP::Intersect / IntersectP, accelerators/BSP.cpp:27-165).  Attaching any tree replaces
+ * whichever was attached before.  Counters of a bsppaper scene: [0] nbNodeTraversals, [1] bspTreeNodeTraversals (interior
+ * nodes), [2] triangle tests, [3] sphere tests; HPRT_RENDER_PIXEL_STATS slots 5 / 6 hold bspTreeNodeTraversals[P]
+ * (hprt_write_pixel_stats_accel with HPRT_ACCEL_BSP). */
+int hprt_scene_attach_bsppaper(HprtScene *s, const HprtBspPaper *t);
 /* kdTreeNodeTraversals (out[0]) and kdTreeNodeTraversalsP (out[1]) of the last counting trace (hprt_intersect / hprt_occluded
  * with counters) or counting render of an rbspkd scene; zeros for any other scene. */
 int hprt_scene_kd_counters(HprtScene *s, uint64_t out[2]);
@@ -456,6 +496,7 @@ int hprt_write_pixel_stats(const char *prefix, const uint64_t *stats7, int width
 #define HPRT_ACCEL_BVH 0
 #define HPRT_ACCEL_KDTREE 1
 #define HPRT_ACCEL_RBSP 2          /* slots 5 / 6 go to -bspTreeNodeTraversals[P].txt (core/film.cpp:176-177) */
+#define HPRT_ACCEL_BSP HPRT_ACCEL_RBSP     /* the general BSP tree (bsppaper): its interior nodes are bspTreeNodeTraversals too */
 int hprt_write_pixel_stats_accel(const char *prefix, const uint64_t *stats7, int width, int height, int accel);
 /* The same for an rbspkd render: -kdTreeNodeTraversals[P].txt from kd2 (hprt_pixel_kd_stats_read's two planes) and
  * -bspTreeNodeTraversals[P].txt = slot 5 / 6 minus the kd share, as Film::WriteGeneralStats does (core/film.cpp:174-177). */

@@ -8,6 +8,7 @@ accelerates:
     KdTree  <- CreateKdTreeAccelerator / buildTree    (accelerators/kdtreeaccel.cpp:212-380,523-545)
     Rbsp    <- CreateRBSPTreeAccelerator / buildTree  (accelerators/rbsp.cpp:181-403,549-571)
     RbspKd  <- CreateRBSPKdTreeAccelerator / buildTree (accelerators/rbspKd.cpp:194-488,640-665)
+    BspPaper <- CreateBSPPaperTreeAccelerator / buildTree (accelerators/bspPaper.cpp:34-319)
     Scene   <- Scene + BVHAccel::Intersect/IntersectP (accelerators/bvh.cpp:354-437)
                and SamplerIntegrator::Render with PathIntegrator::Li
                (core/integrator.cpp:230-360, integrators/path.cpp:64-204)
@@ -38,6 +39,7 @@ RENDER_COUNT_TRACED = 4
 RENDER_TRACE_ALL = 8
 RENDER_EXPORT_FOREIGN = 16
 ACCEL_BVH, ACCEL_KDTREE, ACCEL_RBSP = 0, 1, 2
+ACCEL_BSP = ACCEL_RBSP      # the general BSP tree (bsppaper): its interior nodes are bspTreeNodeTraversals too
 KD_MAX_DEPTH = 64        # HPRT_KD_MAX_DEPTH: the kd walk's todo capacity
 RBSP_MAX_DEPTH = 64      # HPRT_RBSP_MAX_DEPTH: the RBSP walk's todo capacity
 COMM_ID_BYTES = 128
@@ -125,7 +127,7 @@ class RbspKdParams(C.Structure):
 
 
 class _Tree:
-    """A host tree handle (KdTree, Rbsp, RbspKd) over the C calls hprt_<_prefix>_info / _copy / _destroy: info() names the info
+    """A host tree handle (KdTree, Rbsp, RbspKd, BspPaper) over the C calls hprt_<_prefix>_info / _copy / _destroy: info() names the info
     words `_info_keys`; the copy of the RBSP trees takes a direction table as well (M in info)."""
     _prefix = None
     _info_keys = ()
@@ -269,6 +271,12 @@ def _load():
         "hprt_rbspkd_copy": (C.c_int, [vp, vp, vp, vp]),
         "hprt_rbspkd_destroy": (None, [vp]),
         "hprt_scene_attach_rbspkd": (C.c_int, [vp, vp]),
+        "hprt_bsppaper_build": (C.c_int, [vp, vp, P(vp)]),
+        "hprt_bsppaper_build_from_triangles": (C.c_int, [sz, vp, vp, P(vp)]),
+        "hprt_bsppaper_info": (C.c_int, [vp, P(u32)]),
+        "hprt_bsppaper_copy": (C.c_int, [vp, vp, vp]),
+        "hprt_bsppaper_destroy": (None, [vp]),
+        "hprt_scene_attach_bsppaper": (C.c_int, [vp, vp]),
         "hprt_scene_kd_counters": (C.c_int, [vp, vp]),
         "hprt_pixel_kd_stats_read": (C.c_int, [vp, vp, sz]),
         "hprt_write_pixel_stats_rbspkd": (C.c_int, [cp, vp, vp, C.c_int, C.c_int]),
@@ -467,6 +475,45 @@ class Rbsp(_Tree):
     directions = _Tree._directions
 
 
+class BspPaperParams(C.Structure):
+    """HprtBspPaperParams: CreateBSPPaperTreeAccelerator's parameters plus the builder's thread count."""
+    _fields_ = [("isect_cost", C.c_int), ("trav_cost", C.c_int), ("empty_bonus", C.c_float), ("max_prims", C.c_int),
+                ("max_depth", C.c_int), ("threads", C.c_int)]
+
+
+class BspPaper(_Tree):
+    """General BSP tree (host): CreateBSPPaperTreeAccelerator(prims, params) — BSPNode[] (20 bytes: flags word pair and split
+    axis) and primitiveIndices as the reference builds them.  BspPaper(model) takes the scene's Accelerator line; given
+    isect_cost, the keyword parameters replace it (as n_directions does for Rbsp)."""
+    _prefix = "bsppaper"
+    _info_keys = ("nodes", "leaves", "depth", "prim_refs", "axis_interior", "plane_interior")
+
+    def __init__(self, model=None, handle=None, isect_cost=None, trav_cost=5, empty_bonus=0.0, max_prims=1, max_depth=-1, threads=0):
+        if handle is None:
+            handle = C.c_void_p()
+            prm = None if isect_cost is None else C.byref(BspPaperParams(isect_cost, trav_cost, empty_bonus, max_prims, max_depth, threads))
+            _check(lib.hprt_bsppaper_build(model._h, prm, C.byref(handle)))
+        self._h = handle
+
+    @staticmethod
+    def from_triangles(p9, isect_cost=80, trav_cost=5, empty_bonus=0.0, max_prims=1, max_depth=-1, threads=0):
+        """p9: [n, 9] (or [n, 3, 3]) float32 world-space triangle vertices in creation order."""
+        p9 = np.ascontiguousarray(p9, np.float32).reshape(-1, 9)
+        h = C.c_void_p()
+        prm = BspPaperParams(isect_cost, trav_cost, empty_bonus, max_prims, max_depth, threads)
+        _check(lib.hprt_bsppaper_build_from_triangles(p9.shape[0], _ptr(p9), C.byref(prm), C.byref(h)))
+        return BspPaper(handle=h)
+
+    def arrays(self):
+        """(nodes [n, 5] uint32: the reference's BSPNode — word 0 split / onePrimitive / primitiveIndicesOffset, word 1 flags,
+        words 2-4 splitAxis as float bits (zero for leaves); prim_indices uint32)"""
+        inf = self.info()
+        nodes = np.zeros((inf["nodes"], 5), np.uint32)
+        idx = np.zeros(inf["prim_refs"], np.uint32)
+        self._call("copy", _ptr(nodes), _ptr(idx))
+        return nodes, idx
+
+
 class Scene:
     """Device-resident scene: Aggregate (Intersect/IntersectP) + Integrator (Render)."""
 
@@ -503,6 +550,12 @@ class Scene:
         replaces an attached kd-tree or RBSP tree."""
         _check(lib.hprt_scene_attach_rbspkd(self._h, rbspkd._h))
         self._rbspkd = rbspkd
+
+    def attach_bsppaper(self, bsppaper):
+        """hprt_scene_attach_bsppaper: every later trace and render walks `bsppaper` (a BspPaper over this scene's primitives);
+        replaces any attached tree.  Pixel statistics are bspTreeNodeTraversals[P] (ACCEL_BSP)."""
+        _check(lib.hprt_scene_attach_bsppaper(self._h, bsppaper._h))
+        self._bsppaper = bsppaper
 
     def kd_counters(self):
         """(kdTreeNodeTraversals, kdTreeNodeTraversalsP) of the last counting trace or render of an rbspkd scene (zeros
@@ -686,7 +739,7 @@ def write_pixel_stats(prefix, stats7):
 
 def write_pixel_stats_accel(prefix, stats7, accel):
     """The same for a render of any accelerator (ACCEL_BVH; ACCEL_KDTREE: slots 5 / 6 are kdTreeNodeTraversals[P];
-    ACCEL_RBSP: slots 5 / 6 are bspTreeNodeTraversals[P])."""
+    ACCEL_RBSP / ACCEL_BSP: slots 5 / 6 are bspTreeNodeTraversals[P])."""
     stats7 = np.ascontiguousarray(stats7, np.uint64)
     _check(lib.hprt_write_pixel_stats_accel(prefix.encode(), _ptr(stats7), stats7.shape[1], stats7.shape[0], accel))
 

@@ -273,6 +273,9 @@ static void Trace(HprtScene *s, hipStream_t st, bool anyHit, bool count, const u
         LaunchRbspKdTrace(st, s->dev, DevRbspKd{s->rbsp, s->kdShare.as<unsigned long long>()}, anyHit, count, queue, countPtr, countImm, gridItems, rays,
                           hits, occ, counters, workCounter, rayStats);
         break;
+    case HprtScene::Walk::BspPaper:
+        LaunchBspPaperTrace(st, s->dev, s->bsppaper, anyHit, count, queue, countPtr, countImm, gridItems, rays, hits, occ, counters, workCounter, rayStats);
+        break;
     case HprtScene::Walk::Bvh: LaunchTrace(st, s->dev, anyHit, count, queue, countPtr, countImm, gridItems, rays, hits, occ, counters, workCounter, rayStats); break;
     }
 }
@@ -404,12 +407,14 @@ __attribute__((visibility("default"))) int hprt_debug_device_math(int device, in
 } catch (...) { return hprt::HandleException(); }
 
 // A host tree as AttachTree takes it: GenericBSP's node array over M directions (bsp_tree.h) with creation-order primitive numbers,
-// its bounds, its direction table (none for the kd-tree), the deepest tree its walk takes and the builder's structural check
+// its bounds, its direction table (none for the kd-tree), the deepest tree its walk takes and the builder's structural check, and
+// for a tree whose nodes carry their own split axis (bsppaper) those axes, 3 floats per node
 struct TreeView {
     const char *what;                                       // the tree's name in messages
     const std::vector<BspNode> &nodes; const std::vector<uint32_t> &primIndices; uint32_t nPrims; const float *bounds;
     uint32_t M; const std::vector<float> *dirs; uint32_t todoMax;
-    std::function<const char *(uint32_t *depth)> check;     // CheckKdTree, CheckRbspTree
+    std::function<const char *(uint32_t *depth)> check;     // CheckKdTree, CheckRbspTree, CheckBspPaperTree
+    const std::vector<float> *axes = nullptr;
 };
 // MakeAccelerator (core/api.cpp:790-831) for the trees the host builds: the tree is checked, its creation-order primitive numbers are
 // mapped to the scene's ordered indices (the inverse of prim_order), and from now on every trace of the scene takes `walk` over it
@@ -442,6 +447,11 @@ static int AttachTree(HprtScene *s, HprtScene::Walk walk, const TreeView &t) {
     s->walk = HprtScene::Walk::Bvh;
     HIP_TRY(upload(s->treeNodes, nodes));
     HIP_TRY(upload(s->treePrims, prims));
+    if (t.axes) {       // 16 bytes per node (hipMalloc aligns far beyond), leaves zero as the builder holds them
+        std::vector<float4> axes(t.nodes.size());
+        for (size_t k = 0; k < axes.size(); ++k) axes[k] = make_float4((*t.axes)[3 * k], (*t.axes)[3 * k + 1], (*t.axes)[3 * k + 2], 0.f);
+        HIP_TRY(upload(s->treeAxes, axes));
+    }
     if (walk == HprtScene::Walk::RbspKd) {
         HIP_TRY(s->kdShare.alloc(2 * sizeof(unsigned long long)));
         HIP_TRY(hipMemset(s->kdShare.p, 0, 2 * sizeof(unsigned long long)));
@@ -453,7 +463,11 @@ static int AttachTree(HprtScene *s, HprtScene::Walk walk, const TreeView &t) {
         d.depth = depth;
     };
     if (walk == HprtScene::Walk::Kd) fill(s->kd);
-    else {
+    else if (walk == HprtScene::Walk::BspPaper) {
+        s->bsppaper = DevBspPaper{};
+        fill(s->bsppaper);
+        s->bsppaper.axes = s->treeAxes.as<float4>();
+    } else {
         s->rbsp = DevRbsp{};
         fill(s->rbsp);
         s->rbsp.M = t.M; s->rbsp.off = off; s->rbsp.mask = mask;
@@ -482,6 +496,15 @@ int hprt_scene_attach_rbsp(HprtScene *s, const HprtRbsp *t) try {
 int hprt_scene_attach_rbspkd(HprtScene *s, const HprtRbspKd *t) try {
     if (!s || !t) return SetError(HPRT_E_INVALID, "hprt_scene_attach_rbspkd: null argument");
     return AttachRbsp(s, HprtScene::Walk::RbspKd, "rbspkd tree", t->tree);
+} catch (...) { return hprt::HandleException(); }
+
+// The fork's "bsppaper" accelerator (BSPPaper): GenericBSP's node array with M = 1 and a split axis per node, walked by the general
+// BSP walk (device/bsppaper_walk.hip)
+int hprt_scene_attach_bsppaper(HprtScene *s, const HprtBspPaper *t) try {
+    if (!s || !t) return SetError(HPRT_E_INVALID, "hprt_scene_attach_bsppaper: null argument");
+    const BspPaperTree &bt = t->tree;
+    return AttachTree(s, HprtScene::Walk::BspPaper, {"bsppaper tree", bt.nodes, bt.primIndices, bt.nPrims, bt.bounds, BSPPAPER_M, nullptr,
+                                                     (uint32_t)BSPPAPER_TODO_MAX, [&](uint32_t *depth) { return CheckBspPaperTree(bt, depth); }, &bt.axes});
 } catch (...) { return hprt::HandleException(); }
 
 int hprt_scene_kd_counters(HprtScene *s, uint64_t out[2]) try {

@@ -164,7 +164,7 @@ int hprt_model_parse(const char *pbrt_path, const char *const *subst, int n_subs
     std::string err;
     if (!ParsePbrtFile(pbrt_path, sm, &m->sc, &err)) { delete m; return SetError(HPRT_E_PARSE, err); }
     // a tree over object instances is not built (hprt_<accelerator>_build: HPRT_E_UNSUPPORTED): such a scene keeps the BVH and the warning
-    static const char *const kTreeAccelerators[] = {"kdtree", "rbsp", "rbspkd"};
+    static const char *const kTreeAccelerators[] = {"kdtree", "rbsp", "rbspkd", "bsppaper"};
     const std::string &acc = m->sc.opt.accelerator;
     if (std::count(std::begin(kTreeAccelerators), std::end(kTreeAccelerators), acc) && m->sc.nObjects == 0 && m->sc.instances.empty())
         m->sc.warnings.push_back("Accelerator \"" + acc + "\": the host builds the tree (hprt_" + acc + "_build) and attaches it to the scene (hprt_scene_attach_" +
@@ -360,6 +360,90 @@ int hprt_rbspkd_copy(const HprtRbspKd *t, void *nodes8, uint32_t *primIndices, f
     return RbspCopy("hprt_rbspkd_copy", t ? &t->tree : nullptr, nodes8, primIndices, directions);
 } catch (...) { return hprt::HandleException(); }
 void hprt_rbspkd_destroy(HprtRbspKd *t) { delete t; }
+
+// ---- general BSP tree (Accelerator "bsppaper") ----
+namespace {
+int BuildBspPaper(size_t n, const float *lo, const float *hi, const float *tri9, const uint8_t *isTri, const HprtBspPaperParams *params,
+                  BspPaperParams p, HprtBspPaper **out) {
+    if (params) {
+        p.isectCost = params->isect_cost; p.travCost = params->trav_cost; p.emptyBonus = params->empty_bonus;
+        p.maxPrims = params->max_prims; p.maxDepth = params->max_depth; p.threads = params->threads;
+    }
+    std::unique_ptr<HprtBspPaper> t(new HprtBspPaper());
+    const std::string err = BuildBspPaperTree(n, lo, hi, tri9, isTri, p, &t->tree);
+    if (!err.empty()) return SetError(HPRT_E_UNSUPPORTED, err);
+    if (t->tree.depth > BSPPAPER_TODO_MAX)
+        return SetError(HPRT_E_UNSUPPORTED, "bsppaper tree of depth " + std::to_string(t->tree.depth) + " is deeper than the device walk's todo list (" +
+                                                std::to_string((unsigned)BSPPAPER_TODO_MAX) + " entries); lower \"maxdepth\"");
+    *out = t.release();
+    return HPRT_OK;
+}
+}  // namespace
+int hprt_bsppaper_build(const HprtModel *m, const HprtBspPaperParams *params, HprtBspPaper **out) try {
+    if (!m || !out) return SetError(HPRT_E_INVALID, "hprt_bsppaper_build: null argument");
+    if (m->sc.nObjects != 0 || !m->sc.instances.empty())
+        return SetError(HPRT_E_UNSUPPORTED, "bsppaper trees over object instances are not supported (the scene keeps its BVH)");
+    std::vector<float> lo, hi, tri9;
+    std::vector<uint8_t> isTri;
+    RbspModelPrims(m, &lo, &hi, &tri9, &isTri);
+    return BuildBspPaper(lo.size() / 3, lo.data(), hi.data(), tri9.data(), isTri.data(), params, m->sc.opt.bsppaper, out);
+} catch (...) { return hprt::HandleException(); }
+int hprt_bsppaper_build_from_triangles(size_t n, const float *p9, const HprtBspPaperParams *params, HprtBspPaper **out) try {
+    if (!out || (n && !p9)) return SetError(HPRT_E_INVALID, "hprt_bsppaper_build_from_triangles: null argument");
+    if (n > 0x3fffffffull) return SetError(HPRT_E_UNSUPPORTED, "more than 2^30 primitives");
+    std::vector<float> lo, hi;
+    RbspTriangleBounds(n, p9, &lo, &hi);
+    std::vector<uint8_t> isTri(n, 1);
+    return BuildBspPaper(n, lo.data(), hi.data(), p9, isTri.data(), params, BspPaperParams(), out);
+} catch (...) { return hprt::HandleException(); }
+int hprt_bsppaper_info(const HprtBspPaper *t, uint32_t info[6]) try {
+    if (!t || !info) return SetError(HPRT_E_INVALID, "hprt_bsppaper_info: null argument");
+    const BspPaperTree &b = t->tree;
+    info[0] = (uint32_t)b.nodes.size(); info[1] = b.leaves; info[2] = b.depth; info[3] = (uint32_t)b.primIndices.size();
+    info[4] = b.axisNodes; info[5] = b.planeNodes;
+    return HPRT_OK;
+} catch (...) { return hprt::HandleException(); }
+int hprt_bsppaper_copy(const HprtBspPaper *t, void *nodes20, uint32_t *primIndices) try {
+    if (!t) return SetError(HPRT_E_INVALID, "hprt_bsppaper_copy: null argument");
+    const BspPaperTree &b = t->tree;
+    if (nodes20)
+        for (size_t k = 0; k < b.nodes.size(); ++k) {
+            uint32_t w[5] = {b.nodes[k].a, b.nodes[k].b, 0, 0, 0};
+            memcpy(&w[2], &b.axes[3 * k], 12);
+            memcpy((char *)nodes20 + 20 * k, w, 20);
+        }
+    if (primIndices && !b.primIndices.empty()) memcpy(primIndices, b.primIndices.data(), b.primIndices.size() * 4);
+    return HPRT_OK;
+} catch (...) { return hprt::HandleException(); }
+void hprt_bsppaper_destroy(HprtBspPaper *t) { delete t; }
+// Diagnostics hooks (not part of include/hprt.h; tests/test_bsppaper_host.py), the bsppaper builder's views of the triangles p9
+// (9 floats each, creation order).  hprt_debug_bsppaper_planes: getBSPPaperPlanes of triangle 0, planes_out[4 k ..] = {t, axis}
+// of its k-th plane (room for 4); returns how many in *n_planes.
+__attribute__((visibility("default"))) int hprt_debug_bsppaper_planes(const float *p9, float *planes_out, uint32_t *n_planes) try {
+    if (!p9 || !planes_out || !n_planes) return SetError(HPRT_E_INVALID, "hprt_debug_bsppaper_planes: null argument");
+    const std::vector<BspPlane> pl = BspPaperTrianglePlanes(p9);
+    *n_planes = (uint32_t)pl.size();
+    for (size_t k = 0; k < pl.size(); ++k) memcpy(planes_out + 4 * k, &pl[k], 16);
+    return HPRT_OK;
+} catch (...) { return hprt::HandleException(); }
+// hprt_debug_bsppaper_classify: the plane plane4 = {t, axis} over a BVH of the n triangles (isectCost 4, travCost 8, maxPrims 1):
+// counts[2] from getAmountToLeftAndRight, and the left / right lists of getPrimnumsToLeftAndRight (local numbers, up to cap
+// entries each; sizes[2] their full lengths).
+__attribute__((visibility("default"))) int hprt_debug_bsppaper_classify(size_t n, const float *p9, const float *plane4, uint32_t counts[2],
+                                                                        uint32_t *left, uint32_t *right, size_t cap, uint32_t sizes[2]) try {
+    if (n == 0 || !p9 || !plane4 || !counts || !left || !right || !sizes) return SetError(HPRT_E_INVALID, "hprt_debug_bsppaper_classify: bad argument");
+    std::vector<float> lo, hi;
+    RbspTriangleBounds(n, p9, &lo, &hi);
+    std::vector<uint8_t> isTri(n, 1);
+    BspPlane plane;
+    memcpy(&plane, plane4, 16);
+    std::vector<uint32_t> l, r;
+    BspPaperClassify(n, lo.data(), hi.data(), p9, isTri.data(), plane, counts, &l, &r);
+    sizes[0] = (uint32_t)l.size(); sizes[1] = (uint32_t)r.size();
+    for (size_t k = 0; k < l.size() && k < cap; ++k) left[k] = l[k];
+    for (size_t k = 0; k < r.size() && k < cap; ++k) right[k] = r[k];
+    return HPRT_OK;
+} catch (...) { return hprt::HandleException(); }
 int hprt_bvh_info(const HprtBvh *b, uint32_t info[4], float bounds6[6]) try {
     if (!b || !info) return SetError(HPRT_E_INVALID, "hprt_bvh_info: null argument");
     info[0] = (uint32_t)b->tree.nodes.size(); info[1] = (uint32_t)b->tree.primOrder.size();

@@ -1,11 +1,14 @@
 // hprt device side — the body of a GenericBSP walk (Intersect / IntersectP of accelerators/genericBSP.h's trees) over the
 // reference's 8-byte node arrays: the root interval, the todo list, the leaf loop, the hit word and the counters.  The RBSP walk
-// (rbsp_walk.hip) and the rbspkd walk (rbspkd_walk.hip) instantiate it; the kd walk (kd_walk.hip) is the same loop written out,
+// (rbsp_walk.hip), the rbspkd walk (rbspkd_walk.hip) and the bsppaper walk (bsppaper_walk.hip) instantiate it; the kd walk (kd_walk.hip) is the same loop written out,
 // and stays so because moving it here changes its register allocation, and so its code object.  A walk passes its interior step in as `Step`:
 //   bool leaf(uint32_t flags), uint32_t high(uint32_t flags)   (aboveChild / nPrimitives),
 //   void plane(uint32_t flags, float split, vec3 ro, vec3 rd, vec3 invDir, float *tPlane, bool *belowFirst).
 // KD_SHARE (the rbspkd walk) counts the interior nodes for which the step's `bool kd(uint32_t flags)` holds apart as well: per
 // ray in rayStats.w (0 for every other walk) and per wave through `void kd_count_add(bool anyHit, uint32_t n)`.
+// NODE_AXIS (the bsppaper walk) gives the step per-node data: the step's `float4 axis(uint32_t node)` is fetched for every node and
+// passed to `void plane(float4 axis, uint32_t flags, ...)` in front of the other arguments — requested together with the node's
+// 8-byte word (1), or only once the node has turned out to be interior (2).  0: the step has no per-node data (every other walk).
 // (The step keeps no per-ray state: values that must survive the sphere test's call would cost scratch.)
 //
 // One ray per lane; persistent waves draw 64 rays at a time from the queue head (one atomic per wave and draw), so the kernels
@@ -48,7 +51,7 @@ __device__ __forceinline__ bool bsp_root_interval(const float *lo, const float *
 // The whole kernel body.  ANY_HIT: IntersectP (no early-out on a closer hit); COUNT: counters and per-ray statistics; QUAD:
 // the scene has spheres.  nodes / primIdx: the attached tree (one-primitive leaves and primIdx hold ORDERED indices); lo / hi:
 // GenericBSP::bounds.  stackMem: the kernel's [LDS][BLOCK] LDS todo entries.
-template <bool ANY_HIT, bool COUNT, bool QUAD, int LDS, int BLOCK, class Step, bool KD_SHARE = false>
+template <bool ANY_HIT, bool COUNT, bool QUAD, int LDS, int BLOCK, class Step, bool KD_SHARE = false, int NODE_AXIS = 0>
 __device__ __forceinline__ void bsp_walk(const DevScene &sc, const uint2 *nodes, const uint32_t *primIdx, const float *lo, const float *hi, Step &step,
                                          const uint32_t *queue, const uint32_t *countPtr, uint32_t countImm, const RayStream &rays,
                                          const HitStream &hits, uint8_t *occ, DevCounters *counters, uint4 *rayStats, uint32_t *workCounter,
@@ -92,12 +95,22 @@ __device__ __forceinline__ void bsp_walk(const DevScene &sc, const uint2 *nodes,
             while (!done) {
                 if (!ANY_HIT && rayTMax < tMin) break;      // a hit closer than the current node
                 if (COUNT) ++cnt.fetched;
-                const uint2 nd = nodes[node];
+                uint2 nd = nodes[node];
+                [[maybe_unused]] float4 axis;
+                if constexpr (NODE_AXIS == 1) {
+                    axis = step.axis(node);
+                    // an empty asm that takes the node word and the whole entry: both requests are issued before one wait, the
+                    // entry as one 16-byte load, where the compiler would otherwise split it and sink the pieces into the branches
+                    // that read them (the form of 2)
+                    asm volatile("" : "+v"(nd.x), "+v"(nd.y), "+v"(axis.x), "+v"(axis.y), "+v"(axis.z), "+v"(axis.w));
+                }
                 if (!step.leaf(nd.y)) {
                     if (COUNT) ++cnt.entered;
                     if constexpr (COUNT && KD_SHARE) kdCnt += step.kd(nd.y) ? 1u : 0u;
                     float tPlane; bool belowFirst;
-                    step.plane(nd.y, __uint_as_float(nd.x), ro, rd, invDir, &tPlane, &belowFirst);
+                    if constexpr (NODE_AXIS == 2) axis = step.axis(node);
+                    if constexpr (NODE_AXIS != 0) step.plane(axis, nd.y, __uint_as_float(nd.x), ro, rd, invDir, &tPlane, &belowFirst);
+                    else step.plane(nd.y, __uint_as_float(nd.x), ro, rd, invDir, &tPlane, &belowFirst);
                     const uint32_t above = step.high(nd.y);
                     const uint32_t first = belowFirst ? node + 1u : above, second = belowFirst ? above : node + 1u;
                     if (tPlane > tMax || tPlane <= 0) node = first;

@@ -5,6 +5,7 @@
 #include "bvh_builder.h"
 #include "kdtree_builder.h"
 #include "rbsp_builder.h"
+#include "bsppaper_builder.h"
 #include "scene_model.h"
 
 struct HprtModel { hprt::SceneModel sc; };
@@ -16,6 +17,7 @@ struct HprtBvh {
 struct HprtKdTree { hprt::KdTree tree; };
 struct HprtRbsp { hprt::RbspTree tree; };
 struct HprtRbspKd { hprt::RbspTree tree; };     // built with RbspParams::kdAware
+struct HprtBspPaper { hprt::BspPaperTree tree; };
 
 namespace hprt {
 extern thread_local std::string g_lastError;

@@ -634,6 +634,8 @@ struct Frontend {
         if (sc->opt.accelerator == "kdtree") treeParams(o.kd);
         if (sc->opt.accelerator == "rbsp") rbspParams(o.rbsp);
         if (sc->opt.accelerator == "rbspkd") { rbspParams(o.rbspkd); o.rbspkd.kdTravCost = accelParams.oneInt("kdtraversalcost", o.rbspkd.kdTravCost); }
+        // CreateBSPPaperTreeAccelerator (accelerators/bspPaper.cpp:308-319): the tree parameters; its "nbDirections" only feeds a statistic
+        if (sc->opt.accelerator == "bsppaper") treeParams(o.bsppaper);
         reportUnused(filmParams, "Film", {"diagonal"});
         reportUnused(filterParams, "PixelFilter");
         reportUnused(cameraParams, "Camera");

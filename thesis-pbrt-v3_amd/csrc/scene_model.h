@@ -10,6 +10,7 @@
 #include "hprt_math.h"
 #include "kdtree_builder.h"
 #include "rbsp_builder.h"
+#include "bsppaper_builder.h"
 
 namespace hprt {
 
@@ -88,10 +89,10 @@ struct RenderOptions {
     int32_t spp = 16, samplePixelCenter = 0;
     int32_t maxDepth = 5; float rrThreshold = 1.f; int32_t lightStrategy = kSpatial;
     int32_t maxNodePrims = 4, isectCost = 8, travCost = 1;
-    // Accelerator "kdtree" / "rbsp" / "rbspkd": the parameters of CreateKdTreeAccelerator (accelerators/kdtreeaccel.cpp:523-545),
-    // CreateRBSPTreeAccelerator (accelerators/rbsp.cpp:549-571) and CreateRBSPKdTreeAccelerator (accelerators/rbspKd.cpp:640-665),
-    // each read only for its own accelerator; host side only (not baked)
-    KdParams kd; RbspParams rbsp, rbspkd;
+    // Accelerator "kdtree" / "rbsp" / "rbspkd" / "bsppaper": the parameters of CreateKdTreeAccelerator (accelerators/kdtreeaccel.cpp:523-545),
+    // CreateRBSPTreeAccelerator (accelerators/rbsp.cpp:549-571), CreateRBSPKdTreeAccelerator (accelerators/rbspKd.cpp:640-665) and
+    // CreateBSPPaperTreeAccelerator (accelerators/bspPaper.cpp:308-319), each read only for its own accelerator; host side only (not baked)
+    KdParams kd; RbspParams rbsp, rbspkd; BspPaperParams bsppaper;
     std::string filename = "pbrt.exr", accelerator = "bvh", integrator = "path", sampler = "halton";
 };
 struct SceneModel {
