@@ -1,118 +1,22 @@
 // Test-side restatement of the fork's general BSP tree (accelerators/bspPaper.cpp, BSP.h, BSP.cpp, kDOPMesh.h, bvh.cpp:439-527,
-// shapes/triangle.cpp:584-594 and 678-720): BSPPaper::buildTree and the two walks, BSP::Intersect and BSP::IntersectP, written
-// independently of thesis-pbrt-v3_amd/csrc/ over the oracle's vector type, BVH builder and primitive tests (oracle/orc_accel.h,
-// included read-only).  It follows the reference's own shape — a single-threaded scan that keeps the best candidate's k-DOP halves,
-// a k-DOP that carries its own direction list, the node's BVH built by the oracle's BVHAccel restatement — where the library costs
-// candidates in parallel and cuts the winner again.  Compiled with g++ at test time (tests/bsppaper_ref.py), driven through ctypes.
+// shapes/triangle.cpp:584-594 and 678-720): BSPPaper::buildTree and the interior step of the two walks, BSP::Intersect and
+// BSP::IntersectP, written independently of thesis-pbrt-v3_amd/csrc/ over the oracle's vector type, BVH builder and primitive
+// tests (oracle/orc_accel.h, included read-only).  The k-DOP mesh, the walks and the scene plumbing are tests/tree_reference.h's,
+// shared with the other tree accelerators' restatements.  The build follows the reference's own shape — a single-threaded scan
+// that keeps the best candidate's k-DOP halves, a k-DOP that carries its own direction list, the node's BVH built by the oracle's
+// BVHAccel restatement — where the library costs candidates in parallel and cuts the winner again.  Compiled with g++ at test
+// time (tests/tree_ref.py), driven through ctypes.
 // It pins nothing against a reference binary: the device walk is held to THIS walk ("parity unpinned").
-#include <algorithm>
-#include <cmath>
-#include <cstring>
-#include <limits>
-#include <string>
-#include <utility>
-#include <vector>
-#include "orc_accel.h"
-
-namespace orc { bool g_use_libm = false; }
-using namespace orc;
+#include "tree_reference.h"
 
 namespace {
 
-struct Node {                       // BSPNode (BSP.h:122-184): 20 bytes
+struct BSPNode {                    // BSPNode (BSP.h:122-184): 20 bytes
     union { float split; uint32_t onePrimitive; uint32_t primitiveIndicesOffset; };
     union { uint32_t flags; uint32_t nPrims; uint32_t aboveChild; };
     float splitAxis[3];
 };
-static_assert(sizeof(Node) == 20, "BSPNode is 20 bytes");
-
-struct Bnds { Float min = std::numeric_limits<Float>::max(), max = std::numeric_limits<Float>::lowest(); };
-Bnds Union(const Bnds &a, const Bnds &b) { Bnds r; r.min = std::min(a.min, b.min); r.max = std::max(a.max, b.max); return r; }
-
-struct KEdge {
-    V3 v1, v2; uint32_t faceId1, faceId2;
-    Bnds getBounds(const V3 &d) const { Bnds b; const Float t1 = Dot(d, v1), t2 = Dot(d, v2); b.max = std::max(t1, t2); b.min = std::min(t1, t2); return b; }
-};
-struct KMesh { std::vector<KEdge> edges; };
-
-void AddIfNeeded(KMesh &m, const KEdge &e) {
-    for (auto &x : m.edges) if ((x.v1 == e.v2 && x.v2 == e.v1) || (x.v1 == e.v1 && x.v2 == e.v2)) return;
-    m.edges.push_back(e);
-}
-void Helper(std::vector<V3> &pts, const V3 &p) { if (std::find(pts.begin(), pts.end(), p) == pts.end()) pts.push_back(p); }
-
-void AddEdge(KMesh &left, KMesh &right, KEdge edge, std::vector<KEdge> &coincident, std::vector<std::vector<V3>> &fv, Float t, Float t1, Float t2) {
-    V3 d = edge.v2 - edge.v1;
-    if (t1 < t && t2 < t) left.edges.push_back(edge);
-    else if (t1 > t && t2 > t) right.edges.push_back(edge);
-    else if (t1 < t && t == t2) { left.edges.push_back(edge); Helper(fv[edge.faceId1], edge.v2); Helper(fv[edge.faceId2], edge.v2); }
-    else if (t1 == t && t < t2) { right.edges.push_back(edge); Helper(fv[edge.faceId1], edge.v1); Helper(fv[edge.faceId2], edge.v1); }
-    else if (t1 < t && t < t2) {
-        Float tAlongEdge = (-(t1 - t)) / (t2 - t1);
-        V3 vs(edge.v1 + tAlongEdge * d);
-        left.edges.push_back(KEdge{edge.v1, vs, edge.faceId1, edge.faceId2});
-        right.edges.push_back(KEdge{vs, edge.v2, edge.faceId1, edge.faceId2});
-        Helper(fv[edge.faceId1], vs); Helper(fv[edge.faceId2], vs);
-    } else if (t1 == t && t == t2) coincident.push_back(edge);
-}
-
-std::pair<KMesh, KMesh> CutMesh(const std::vector<KEdge> &edges, uint32_t M, Float t, const V3 &direction, uint32_t dId) {
-    KMesh left, right;
-    std::vector<std::vector<V3>> fv(2 * M);
-    std::vector<KEdge> coincident;
-    for (auto &edge : edges) {
-        Float t1 = Dot(direction, edge.v1), t2 = Dot(direction, edge.v2);
-        if (t1 > t2) AddEdge(left, right, KEdge{edge.v2, edge.v1, edge.faceId1, edge.faceId2}, coincident, fv, t, t2, t1);
-        else AddEdge(left, right, edge, coincident, fv, t, t1, t2);
-    }
-    for (auto &edge : coincident) {
-        for (auto &le : left.edges) {
-            if (le.faceId1 == edge.faceId1 || le.faceId2 == edge.faceId1) {
-                left.edges.push_back(KEdge{edge.v1, edge.v2, edge.faceId1, 2 * dId});
-                right.edges.push_back(KEdge{edge.v1, edge.v2, edge.faceId2, 2 * dId + 1});
-                break;
-            } else if (le.faceId1 == edge.faceId2 || le.faceId2 == edge.faceId2) {
-                left.edges.push_back(KEdge{edge.v1, edge.v2, edge.faceId2, 2 * dId});
-                right.edges.push_back(KEdge{edge.v1, edge.v2, edge.faceId1, 2 * dId + 1});
-                break;
-            }
-        }
-    }
-    for (uint32_t i = 0; i < 2 * M; ++i)
-        if (fv[i].size() == 2) {
-            AddIfNeeded(left, KEdge{fv[i][0], fv[i][1], i, 2 * dId});
-            AddIfNeeded(right, KEdge{fv[i][0], fv[i][1], i, 2 * dId + 1});
-        }
-    return std::make_pair(left, right);
-}
-
-Float MeshArea(std::vector<KEdge> &edges, const std::vector<V3> &dirs) {
-    std::vector<std::vector<KEdge *>> faces(2 * dirs.size());
-    for (auto &e : edges) { faces[e.faceId1].push_back(&e); faces[e.faceId2].push_back(&e); }
-    Float SA = 0;
-    for (uint32_t i = 0; i < 2 * dirs.size(); ++i) {
-        V3 FSA;
-        const std::vector<KEdge *> &face = faces[i];
-        if (!face.empty()) {
-            std::vector<bool> used(face.size(), false);
-            uint32_t edgeId = 0;
-            do {
-                if (used[edgeId]) break;
-                used[edgeId] = true;
-                KEdge *cur = face[edgeId];
-                FSA += Cross(cur->v1, cur->v2);
-                for (uint32_t j = 0; j < face.size(); ++j) {
-                    if (j == edgeId) continue;
-                    if (face[j]->v2 == cur->v2) std::swap(face[j]->v1, face[j]->v2);
-                    if (face[j]->v1 == cur->v2 && !used[j]) { edgeId = j; break; }
-                }
-            } while (edgeId != 0);
-        }
-        SA += std::abs(Dot(dirs[i / 2], FSA));
-    }
-    return SA / 2.0f;
-}
-
+static_assert(sizeof(BSPNode) == 20, "BSPNode is 20 bytes");
 
 // KDOPMeshWithDirections (kDOPMesh.h:238-266)
 struct DMesh {
@@ -143,9 +47,6 @@ V3 PositiveX(V3 v) {
     }
     return Normalize(V3(-v.x, -v.y, -v.z));
 }
-
-// A primitive as the builder sees it: a triangle's three world vertices, or (tri == false) a world bound
-struct Prim { bool tri; V3 p[3]; B3 wb; };
 
 // Triangle::Normal (shapes/triangle.cpp:584-594) and getBSPPaperPlanes (:678-720)
 std::vector<Plane> Planes(const Prim &pr) {
@@ -268,11 +169,7 @@ struct BvhScene {
     }
 };
 
-struct Tree {
-    std::vector<Node> nodes;
-    std::vector<uint32_t> primitiveIndices;
-    B3 bounds;
-};
+typedef TreeT<BSPNode> Tree;
 
 enum class EdgeType { Start, End };
 struct BoundEdge { Float t; uint32_t primNum; EdgeType type; };
@@ -301,7 +198,7 @@ void Build(const std::vector<Prim> &prims, uint32_t isectCost, uint32_t traversa
     std::vector<std::vector<BoundEdge>> edges(3, std::vector<BoundEdge>(2 * N));
     std::vector<uint32_t> primsBuf((size_t)(maxDepth + 1) * N + 1);
     for (uint32_t i = 0; i < N; ++i) primsBuf[i] = i;
-    std::vector<Node> &nodes = tree->nodes;
+    std::vector<BSPNode> &nodes = tree->nodes;
     auto InitLeaf = [&](uint32_t nodeNum, uint32_t *primNums, uint32_t np) {
         nodes[nodeNum].flags = 1u;
         nodes[nodeNum].nPrims |= (np << 1u);
@@ -321,7 +218,7 @@ void Build(const std::vector<Prim> &prims, uint32_t isectCost, uint32_t traversa
         stack.pop_back();
         if (cur.parentNum != (uint32_t)-1) nodes[cur.parentNum].aboveChild |= (nodeNum << 1u);
         nodes.emplace_back();
-        memset(&nodes.back(), 0, sizeof(Node));
+        memset(&nodes.back(), 0, sizeof(BSPNode));
         if (cur.nPrimitives <= maxPrims || cur.depth == 0) { InitLeaf(nodeNum++, cur.primNums, cur.nPrimitives); continue; }
         uint32_t bestK = (uint32_t)-1, bestOffset = (uint32_t)-1;
         Float bestSplitT = 0; V3 bestSplitAxis;
@@ -415,138 +312,21 @@ void Build(const std::vector<Prim> &prims, uint32_t isectCost, uint32_t traversa
     }
 }
 
-// Bounds3::IntersectP(const Ray &, Float *, Float *), core/geometry.h:1730-1751
-bool RootInterval(const B3 &b, const Ray &ray, Float *hitt0, Float *hitt1) {
-    Float t0 = 0, t1 = ray.tMax;
-    for (int i = 0; i < 3; ++i) {
-        Float invRayDir = 1 / ray.d[i];
-        Float tNear = (b.pMin[i] - ray.o[i]) * invRayDir;
-        Float tFar = (b.pMax[i] - ray.o[i]) * invRayDir;
-        if (tNear > tFar) std::swap(tNear, tFar);
-        tFar *= 1 + 2 * gamma(3);
-        t0 = tNear > t0 ? tNear : t0;
-        t1 = tFar < t1 ? tFar : t1;
-        if (t0 > t1) return false;
-    }
-    *hitt0 = t0; *hitt1 = t1;
-    return true;
-}
-
-struct WalkCount { uint64_t nodes = 0, interior = 0, leaves = 0; };
-struct ToDo { const Node *node; Float tMin, tMax; };
-
-struct SceneRef {
-    Scene scene;
-    std::vector<BVH> objectBvh;
-    BVH bvh;                       // primOrder: ordered -> creation number (the device numbering), and the primitive tests
-    std::vector<uint32_t> toOrdered;
-    Tree tree;
-
-    // treeIntersectInterior with planeDistance (BSP.h:66-78, core/geometry.h:1837-1843)
-    void Interior(const Node *node, const Ray &ray, Float *tPlane, bool *belowFirst) const {
+// BSPNode: the low bit a leaf; treeIntersectInterior with planeDistance (BSP.h:66-78, core/geometry.h:1837-1843)
+struct BspStep {
+    typedef BSPNode NodeT;
+    static uint32_t Shift(const Tree &) { return 1; }
+    static bool IsLeaf(const Tree &, const BSPNode *n) { return (n->flags & 1u) == 1u; }
+    static bool Kd(const Tree &, const BSPNode *) { return false; }    // (only rbspkd counts its axis nodes apart)
+    static void Interior(const Tree &, const BSPNode *node, const Ray &ray, const V3 &, Float *tPlane, bool *belowFirst) {
         const V3 axis(node->splitAxis[0], node->splitAxis[1], node->splitAxis[2]);
         const Float projectedO = Dot(axis, ray.o);
         const Float inverseProjectedD = 1 / Dot(axis, ray.d);
         *tPlane = (node->split - projectedO) * inverseProjectedD;
         *belowFirst = (projectedO < node->split) || (projectedO == node->split && inverseProjectedD <= 0);
     }
-    static bool IsLeaf(const Node *n) { return (n->flags & 1u) == 1u; }
-
-    // BSP::Intersect (accelerators/BSP.cpp)
-    bool Intersect(const Ray &ray, SurfaceInteraction *isect, Counters &ctr, WalkCount &wc) const {
-        Float tMin, tMax;
-        if (!RootInterval(tree.bounds, ray, &tMin, &tMax)) return false;
-        ToDo todo[64];
-        uint32_t todoPos = 0;
-        bool hit = false;
-        const Node *node = &tree.nodes[0];
-        while (node != nullptr) {
-            if (ray.tMax < tMin) break;
-            ++wc.nodes;
-            if (!IsLeaf(node)) {
-                ++wc.interior;
-                Float tPlane; bool belowFirst;
-                Interior(node, ray, &tPlane, &belowFirst);
-                const Node *first, *second;
-                if (belowFirst) { first = node + 1; second = &tree.nodes[node->aboveChild >> 1]; }
-                else { first = &tree.nodes[node->aboveChild >> 1]; second = node + 1; }
-                if (tPlane > tMax || tPlane <= 0) node = first;
-                else if (tPlane < tMin) node = second;
-                else { todo[todoPos].node = second; todo[todoPos].tMin = tPlane; todo[todoPos].tMax = tMax; ++todoPos; node = first; tMax = tPlane; }
-            } else {
-                ++wc.leaves;
-                const uint32_t np = node->nPrims >> 1;
-                for (uint32_t i = 0; i < np; ++i) {
-                    const uint32_t p = np == 1 ? node->onePrimitive : tree.primitiveIndices[node->primitiveIndicesOffset + i];
-                    if (bvh.PrimIntersect(toOrdered[p], ray, isect, ctr)) hit = true;
-                }
-                if (todoPos > 0) { --todoPos; node = todo[todoPos].node; tMin = todo[todoPos].tMin; tMax = todo[todoPos].tMax; }
-                else break;
-            }
-        }
-        return hit;
-    }
-    // BSP::IntersectP
-    bool IntersectP(const Ray &ray, Counters &ctr, WalkCount &wc) const {
-        Float tMin, tMax;
-        if (!RootInterval(tree.bounds, ray, &tMin, &tMax)) return false;
-        ToDo todo[64];
-        uint32_t todoPos = 0;
-        const Node *node = &tree.nodes[0];
-        while (node != nullptr) {
-            ++wc.nodes;
-            if (IsLeaf(node)) {
-                ++wc.leaves;
-                const uint32_t np = node->nPrims >> 1;
-                for (uint32_t i = 0; i < np; ++i) {
-                    const uint32_t p = np == 1 ? node->onePrimitive : tree.primitiveIndices[node->primitiveIndicesOffset + i];
-                    if (bvh.PrimIntersectP(toOrdered[p], ray, ctr)) return true;
-                }
-                if (todoPos > 0) { --todoPos; node = todo[todoPos].node; tMin = todo[todoPos].tMin; tMax = todo[todoPos].tMax; }
-                else break;
-            } else {
-                ++wc.interior;
-                Float tPlane; bool belowFirst;
-                Interior(node, ray, &tPlane, &belowFirst);
-                const Node *first, *second;
-                if (belowFirst) { first = node + 1; second = &tree.nodes[node->aboveChild >> 1]; }
-                else { first = &tree.nodes[node->aboveChild >> 1]; second = node + 1; }
-                if (tPlane > tMax || tPlane <= 0) node = first;
-                else if (tPlane < tMin) node = second;
-                else { todo[todoPos].node = second; todo[todoPos].tMin = tPlane; todo[todoPos].tMax = tMax; ++todoPos; node = first; tMax = tPlane; }
-            }
-        }
-        return false;
-    }
-
-    std::vector<Prim> Prims() const {
-        std::vector<Prim> out(scene.prims.size());
-        for (size_t i = 0; i < out.size(); ++i) {
-            const PrimRef &pr = scene.prims[i];
-            out[i].wb = bvh.PrimWorldBound((uint32_t)i);
-            const ShapeRec &sh = scene.shapes[pr.shape];
-            out[i].tri = sh.kind == SHAPE_MESH;
-            if (out[i].tri) {
-                const Mesh &m = scene.meshes[sh.meshIndex];
-                for (int k = 0; k < 3; ++k) out[i].p[k] = m.p[m.idx[3 * pr.local + k]];
-            }
-        }
-        return out;
-    }
 };
-
-std::string g_err;
-
-std::vector<Prim> TrianglePrims(size_t n, const float *p9) {
-    std::vector<Prim> prims(n);
-    for (size_t i = 0; i < n; ++i) {
-        Prim &p = prims[i];
-        p.tri = true;
-        for (int k = 0; k < 3; ++k) p.p[k] = V3(p9[9 * i + 3 * k], p9[9 * i + 3 * k + 1], p9[9 * i + 3 * k + 2]);
-        p.wb = Union(B3(p.p[0], p.p[1]), p.p[2]);
-    }
-    return prims;
-}
+typedef SceneRef<BspStep> BspScene;
 
 }  // namespace
 
@@ -562,11 +342,7 @@ void *bspref_build(size_t n, const float *p9, int isectCost, int travCost, float
     return t;
 }
 // nodes20: 5 words per node (leaves' axis words zero)
-void bspref_copy(void *h, void *nodes20, uint32_t *idx) {
-    const Tree &t = *(const Tree *)h;
-    if (nodes20) memcpy(nodes20, t.nodes.data(), t.nodes.size() * sizeof(Node));
-    if (idx && !t.primitiveIndices.empty()) memcpy(idx, t.primitiveIndices.data(), t.primitiveIndices.size() * 4);
-}
+void bspref_copy(void *h, void *nodes20, uint32_t *idx) { CopyTree(*(const Tree *)h, nodes20, idx, nullptr); }
 void bspref_free(void *h) { delete (Tree *)h; }
 // getBSPPaperPlanes of one triangle: planes4[4 k ..] = {t, axis}; returns how many
 size_t bspref_planes(const float *p9, float *planes4) {
@@ -595,60 +371,21 @@ void bspref_classify(size_t n, const float *p9, const float *plane4, uint32_t co
 
 // a baked scene (no instances) and its BVH (for the ordered numbering); build != 0: the restated default tree, else set_tree
 void *bspref_scene_load(const char *path, int build) {
-    SceneRef *r = new SceneRef();
-    std::string err;
-    if (!LoadScene(path, &r->scene, &err)) { g_err = err; delete r; return nullptr; }
-    if (!r->scene.instances.empty()) { g_err = "instanced scene"; delete r; return nullptr; }
-    r->bvh.Build(&r->scene, &r->scene.prims, &r->objectBvh, 0);
-    const size_t n = r->scene.prims.size();
-    r->toOrdered.resize(n);
-    for (size_t i = 0; i < n; ++i) r->toOrdered[r->bvh.primOrder[i]] = (uint32_t)i;
-    r->tree.bounds = B3();
-    for (size_t i = 0; i < n; ++i) r->tree.bounds = Union(r->tree.bounds, r->bvh.PrimWorldBound((uint32_t)i));
-    if (build) Build(r->Prims(), 80, 5, 0.f, 1, (uint32_t)-1, &r->tree);
+    BspScene *r = LoadSceneRef<BspStep>(path);
+    if (r && build) Build(r->Prims(), 80, 5, 0.f, 1, (uint32_t)-1, &r->tree);
     return r;
 }
-void bspref_scene_set_tree(void *h, size_t nNodes, const void *nodes20, size_t nIdx, const uint32_t *idx) {
-    SceneRef *r = (SceneRef *)h;
-    r->tree.nodes.resize(nNodes);
-    memcpy(r->tree.nodes.data(), nodes20, nNodes * sizeof(Node));
-    r->tree.primitiveIndices.assign(idx, idx + nIdx);
-}
-void bspref_scene_free(void *h) { delete (SceneRef *)h; }
-size_t bspref_scene_prims(void *h) { return ((SceneRef *)h)->scene.prims.size(); }
-// the scene's triangles in creation order (9 floats each; other primitives are skipped); returns how many
-size_t bspref_scene_triangles(void *h, float *p9) {
-    size_t k = 0;
-    for (const Prim &p : ((SceneRef *)h)->Prims())
-        if (p.tri) { for (int v = 0; v < 3; ++v) { p9[9 * k + 3 * v] = p.p[v].x; p9[9 * k + 3 * v + 1] = p.p[v].y; p9[9 * k + 3 * v + 2] = p.p[v].z; } ++k; }
-    return k;
-}
-void bspref_scene_tree(void *h, uint32_t sizes[2], void *nodes20, uint32_t *idx) {
-    SceneRef *r = (SceneRef *)h;
-    sizes[0] = (uint32_t)r->tree.nodes.size(); sizes[1] = (uint32_t)r->tree.primitiveIndices.size();
-    if (nodes20) bspref_copy(&r->tree, nodes20, idx);
-}
-// counters4 per ray: nodes (nbNodeTraversals), interior (bspTreeNodeTraversals), triangle tests, sphere tests
+void bspref_scene_set_tree(void *h, size_t nNodes, const void *nodes20, size_t nIdx, const uint32_t *idx) { SceneSetTree((BspScene *)h, nNodes, nodes20, nIdx, idx); }
+void bspref_scene_free(void *h) { delete (BspScene *)h; }
+size_t bspref_scene_prims(void *h) { return ((BspScene *)h)->scene.prims.size(); }
+size_t bspref_scene_triangles(void *h, float *p9) { return SceneTriangles((const BspScene *)h, p9); }
+void bspref_scene_tree(void *h, uint32_t sizes[2], void *nodes20, uint32_t *idx) { SceneTree((const BspScene *)h, sizes, nodes20, idx); }
 void bspref_intersect(void *h, size_t n, const float *o, const float *d, const float *tmax, float *tOut, int32_t *primOut, float *bary,
                       uint64_t *counters4) {
-    SceneRef *r = (SceneRef *)h;
-    for (size_t i = 0; i < n; ++i) {
-        Ray ray(V3(o[3 * i], o[3 * i + 1], o[3 * i + 2]), V3(d[3 * i], d[3 * i + 1], d[3 * i + 2]), tmax[i]);
-        SurfaceInteraction si; Counters c; WalkCount wc;
-        const bool hit = r->Intersect(ray, &si, c, wc);
-        tOut[i] = ray.tMax; primOut[i] = hit ? si.ordered : -1;
-        bary[3 * i] = hit ? si.b0 : 0.f; bary[3 * i + 1] = hit ? si.b1 : 0.f; bary[3 * i + 2] = hit ? si.b2 : 0.f;
-        counters4[4 * i] = wc.nodes; counters4[4 * i + 1] = wc.interior; counters4[4 * i + 2] = c.triTests; counters4[4 * i + 3] = c.sphereTests;
-    }
+    IntersectRays((const BspScene *)h, n, o, d, tmax, tOut, primOut, bary, counters4, 4);
 }
 void bspref_occluded(void *h, size_t n, const float *o, const float *d, const float *tmax, uint8_t *occ, uint64_t *counters4) {
-    SceneRef *r = (SceneRef *)h;
-    for (size_t i = 0; i < n; ++i) {
-        Ray ray(V3(o[3 * i], o[3 * i + 1], o[3 * i + 2]), V3(d[3 * i], d[3 * i + 1], d[3 * i + 2]), tmax[i]);
-        Counters c; WalkCount wc;
-        occ[i] = r->IntersectP(ray, c, wc) ? 1 : 0;
-        counters4[4 * i] = wc.nodes; counters4[4 * i + 1] = wc.interior; counters4[4 * i + 2] = c.triTestsP; counters4[4 * i + 3] = c.sphereTestsP;
-    }
+    OccludedRays((const BspScene *)h, n, o, d, tmax, occ, counters4, 4);
 }
 
 }  // extern "C"

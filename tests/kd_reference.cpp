@@ -1,31 +1,13 @@
-// Test-side restatement of the fork's kd-tree (accelerators/kdtreeaccel.cpp:212-521): KdTreeAccel::buildTree and the two
-// walks, Intersect and IntersectP, written independently of thesis-pbrt-v3_amd/csrc/ over the oracle's primitive tests
-// (oracle/orc_accel.h, included read-only).  Compiled with g++ at test time (tests/kd_ref.py) and driven through ctypes.
+// Test-side restatement of the fork's kd-tree (accelerators/kdtreeaccel.cpp:212-521): KdTreeAccel::buildTree and the interior
+// step of the two walks, Intersect and IntersectP, which tests/tree_reference.h holds for the four tree accelerators, written
+// independently of thesis-pbrt-v3_amd/csrc/ over the oracle's primitive tests (oracle/orc_accel.h, included read-only).
+// Compiled with g++ at test time (tests/tree_ref.py) and driven through ctypes.
 // It pins nothing against a reference binary: the device walk is held to THIS walk ("parity unpinned").
-#include <algorithm>
-#include <cmath>
-#include <cstring>
-#include <limits>
-#include <string>
-#include <vector>
-#include "orc_accel.h"
-
-namespace orc { bool g_use_libm = false; }
-using namespace orc;
+#include "tree_reference.h"
 
 namespace {
 
-struct Node {                       // KdAccelNode: union { split, onePrimitive, primitiveIndicesOffset }; union { flags, nPrims, aboveChild }
-    union { float split; uint32_t onePrimitive; uint32_t primitiveIndicesOffset; };
-    union { uint32_t flags; uint32_t nPrims; uint32_t aboveChild; };
-};
-static_assert(sizeof(Node) == 8, "KdAccelNode is 8 bytes");
-
-struct Tree {
-    std::vector<Node> nodes;
-    std::vector<uint32_t> primitiveIndices;
-    B3 bounds;
-};
+typedef TreeT<Node> Tree;
 
 enum class EdgeType { Start, End };
 struct BoundEdge { Float t; uint32_t primNum; EdgeType type; };
@@ -120,106 +102,20 @@ void Build(const std::vector<B3> &allPrimBounds, uint32_t isectCost, uint32_t tr
     }
 }
 
-// Bounds3::IntersectP(const Ray &, Float *, Float *), core/geometry.h:1730-1751
-bool RootInterval(const B3 &b, const Ray &ray, Float *hitt0, Float *hitt1) {
-    Float t0 = 0, t1 = ray.tMax;
-    for (int i = 0; i < 3; ++i) {
-        Float invRayDir = 1 / ray.d[i];
-        Float tNear = (b.pMin[i] - ray.o[i]) * invRayDir;
-        Float tFar = (b.pMax[i] - ray.o[i]) * invRayDir;
-        if (tNear > tFar) std::swap(tNear, tFar);
-        tFar *= 1 + 2 * gamma(3);
-        t0 = tNear > t0 ? tNear : t0;
-        t1 = tFar < t1 ? tFar : t1;
-        if (t0 > t1) return false;
-    }
-    *hitt0 = t0; *hitt1 = t1;
-    return true;
-}
-
-struct WalkCount { uint64_t nodes = 0, interior = 0, leaves = 0; };
-struct ToDo { const Node *node; Float tMin, tMax; };
-
-struct SceneRef {
-    Scene scene;
-    std::vector<BVH> objectBvh;
-    BVH bvh;                       // primOrder: ordered -> creation number (the device numbering), and the primitive tests
-    std::vector<uint32_t> toOrdered;
-    Tree tree;
-
-    // KdTreeAccel::Intersect, accelerators/kdtreeaccel.cpp:381-457
-    bool Intersect(const Ray &ray, SurfaceInteraction *isect, Counters &ctr, WalkCount &wc) const {
-        Float tMin, tMax;
-        if (!RootInterval(tree.bounds, ray, &tMin, &tMax)) return false;
-        V3 invDir(1 / ray.d.x, 1 / ray.d.y, 1 / ray.d.z);
-        ToDo todo[64];
-        uint32_t todoPos = 0;
-        bool hit = false;
-        const Node *node = &tree.nodes[0];
-        while (node != nullptr) {
-            if (ray.tMax < tMin) break;
-            ++wc.nodes;
-            if ((node->flags & 3u) != 3u) {
-                ++wc.interior;
-                const uint32_t axis = node->flags & 3u;
-                const Float tPlane = (node->split - ray.o[axis]) * invDir[axis];
-                const bool belowFirst = (ray.o[axis] < node->split) || (ray.o[axis] == node->split && ray.d[axis] <= 0);
-                const Node *first, *second;
-                if (belowFirst) { first = node + 1; second = &tree.nodes[node->aboveChild >> 2]; }
-                else { first = &tree.nodes[node->aboveChild >> 2]; second = node + 1; }
-                if (tPlane > tMax || tPlane <= 0) node = first;
-                else if (tPlane < tMin) node = second;
-                else { todo[todoPos].node = second; todo[todoPos].tMin = tPlane; todo[todoPos].tMax = tMax; ++todoPos; node = first; tMax = tPlane; }
-            } else {
-                ++wc.leaves;
-                const uint32_t np = node->nPrims >> 2;
-                for (uint32_t i = 0; i < np; ++i) {
-                    const uint32_t p = np == 1 ? node->onePrimitive : tree.primitiveIndices[node->primitiveIndicesOffset + i];
-                    if (bvh.PrimIntersect(toOrdered[p], ray, isect, ctr)) hit = true;
-                }
-                if (todoPos > 0) { --todoPos; node = todo[todoPos].node; tMin = todo[todoPos].tMin; tMax = todo[todoPos].tMax; }
-                else break;
-            }
-        }
-        return hit;
-    }
-    // KdTreeAccel::IntersectP, :459-521
-    bool IntersectP(const Ray &ray, Counters &ctr, WalkCount &wc) const {
-        Float tMin, tMax;
-        if (!RootInterval(tree.bounds, ray, &tMin, &tMax)) return false;
-        V3 invDir(1 / ray.d.x, 1 / ray.d.y, 1 / ray.d.z);
-        ToDo todo[64];
-        uint32_t todoPos = 0;
-        const Node *node = &tree.nodes[0];
-        while (node != nullptr) {
-            ++wc.nodes;
-            if ((node->flags & 3u) == 3u) {
-                ++wc.leaves;
-                const uint32_t np = node->nPrims >> 2;
-                for (uint32_t i = 0; i < np; ++i) {
-                    const uint32_t p = np == 1 ? node->onePrimitive : tree.primitiveIndices[node->primitiveIndicesOffset + i];
-                    if (bvh.PrimIntersectP(toOrdered[p], ray, ctr)) return true;
-                }
-                if (todoPos > 0) { --todoPos; node = todo[todoPos].node; tMin = todo[todoPos].tMin; tMax = todo[todoPos].tMax; }
-                else break;
-            } else {
-                ++wc.interior;
-                const uint32_t axis = node->flags & 3u;
-                const Float tPlane = (node->split - ray.o[axis]) * invDir[axis];
-                const bool belowFirst = (ray.o[axis] < node->split) || (ray.o[axis] == node->split && ray.d[axis] <= 0);
-                const Node *first, *second;
-                if (belowFirst) { first = node + 1; second = &tree.nodes[node->aboveChild >> 2]; }
-                else { first = &tree.nodes[node->aboveChild >> 2]; second = node + 1; }
-                if (tPlane > tMax || tPlane <= 0) node = first;
-                else if (tPlane < tMin) node = second;
-                else { todo[todoPos].node = second; todo[todoPos].tMin = tPlane; todo[todoPos].tMax = tMax; ++todoPos; node = first; tMax = tPlane; }
-            }
-        }
-        return false;
+// KdAccelNode: the axis in the two low bits, 3 a leaf; the interior step of kdtreeaccel.cpp:403-417
+struct KdStep {
+    typedef Node NodeT;
+    static uint32_t Shift(const Tree &) { return 2; }
+    static uint32_t Axis(const Tree &, const Node *n) { return n->flags & 3u; }
+    static bool IsLeaf(const Tree &, const Node *n) { return (n->flags & 3u) == 3u; }
+    static bool Kd(const Tree &, const Node *) { return false; }       // (only rbspkd counts its axis nodes apart)
+    static void Interior(const Tree &, const Node *node, const Ray &ray, const V3 &invDir, Float *tPlane, bool *belowFirst) {
+        const uint32_t axis = node->flags & 3u;
+        *tPlane = (node->split - ray.o[axis]) * invDir[axis];
+        *belowFirst = (ray.o[axis] < node->split) || (ray.o[axis] == node->split && ray.d[axis] <= 0);
     }
 };
-
-std::string g_err;
+typedef SceneRef<KdStep> KdScene;
 
 }  // namespace
 
@@ -240,70 +136,37 @@ void *kdref_build(size_t n, const float *bmin, const float *bmax, int isectCost,
     sizes[0] = (uint32_t)t->nodes.size(); sizes[1] = (uint32_t)t->primitiveIndices.size();
     return t;
 }
-void kdref_copy(void *h, void *nodes8, uint32_t *idx) {
-    const Tree *t = (const Tree *)h;
-    memcpy(nodes8, t->nodes.data(), t->nodes.size() * 8);
-    if (!t->primitiveIndices.empty()) memcpy(idx, t->primitiveIndices.data(), t->primitiveIndices.size() * 4);
-}
+void kdref_copy(void *h, void *nodes8, uint32_t *idx) { CopyTree(*(const Tree *)h, nodes8, idx, nullptr); }
 void kdref_free(void *h) { delete (Tree *)h; }
 
 // a baked scene (no instances), its BVH (for the ordered numbering) and the default kd-tree over its primitives
 void *kdref_scene_load(const char *path) {
-    SceneRef *r = new SceneRef();
-    std::string err;
-    if (!LoadScene(path, &r->scene, &err)) { g_err = err; delete r; return nullptr; }
-    if (!r->scene.instances.empty()) { g_err = "instanced scene"; delete r; return nullptr; }
-    r->bvh.Build(&r->scene, &r->scene.prims, &r->objectBvh, 0);
+    KdScene *r = LoadSceneRef<KdStep>(path);
+    if (!r) return nullptr;
     const size_t n = r->scene.prims.size();
-    r->toOrdered.resize(n);
-    for (size_t i = 0; i < n; ++i) r->toOrdered[r->bvh.primOrder[i]] = (uint32_t)i;
     std::vector<B3> b(n);
     for (size_t i = 0; i < n; ++i) b[i] = r->bvh.PrimWorldBound((uint32_t)i);
     Build(b, 80, 1, 0.f, 1, (uint32_t)-1, &r->tree);
     return r;
 }
-void kdref_scene_free(void *h) { delete (SceneRef *)h; }
-size_t kdref_scene_prims(void *h) { return ((SceneRef *)h)->scene.prims.size(); }
+void kdref_scene_free(void *h) { delete (KdScene *)h; }
+size_t kdref_scene_prims(void *h) { return ((KdScene *)h)->scene.prims.size(); }
 void kdref_scene_bounds(void *h, float *bmin, float *bmax) {
-    SceneRef *r = (SceneRef *)h;
+    KdScene *r = (KdScene *)h;
     for (size_t i = 0; i < r->scene.prims.size(); ++i) {
         const B3 b = r->bvh.PrimWorldBound((uint32_t)i);
         for (int k = 0; k < 3; ++k) { bmin[3 * i + k] = b.pMin[k]; bmax[3 * i + k] = b.pMax[k]; }
     }
 }
-void kdref_scene_tree(void *h, uint32_t sizes[2], void *nodes8, uint32_t *idx) {
-    SceneRef *r = (SceneRef *)h;
-    sizes[0] = (uint32_t)r->tree.nodes.size(); sizes[1] = (uint32_t)r->tree.primitiveIndices.size();
-    if (nodes8) kdref_copy(&r->tree, nodes8, idx);
-}
-// the split planes of the scene's tree (axis, position) of the first `cap` interior nodes: rays with o[axis] == split
-size_t kdref_scene_splits(void *h, int32_t *axis, float *pos, size_t cap) {
-    SceneRef *r = (SceneRef *)h;
-    size_t k = 0;
-    for (const Node &nd : r->tree.nodes) if ((nd.flags & 3u) != 3u && k < cap) { axis[k] = (int32_t)(nd.flags & 3u); pos[k] = nd.split; ++k; }
-    return k;
-}
-// counters4 per ray: nodes (nbNodeTraversals), interior (kdTreeNodeTraversals), triangle tests, sphere tests
+void kdref_scene_tree(void *h, uint32_t sizes[2], void *nodes8, uint32_t *idx) { SceneTree((const KdScene *)h, sizes, nodes8, idx); }
+// rays with o[axis] == split
+size_t kdref_scene_splits(void *h, int32_t *axis, float *pos, size_t cap) { return SceneSplits((const KdScene *)h, axis, pos, cap); }
 void kdref_intersect(void *h, size_t n, const float *o, const float *d, const float *tmax, float *tOut, int32_t *primOut, float *bary,
                      uint64_t *counters4) {
-    SceneRef *r = (SceneRef *)h;
-    for (size_t i = 0; i < n; ++i) {
-        Ray ray(V3(o[3 * i], o[3 * i + 1], o[3 * i + 2]), V3(d[3 * i], d[3 * i + 1], d[3 * i + 2]), tmax[i]);
-        SurfaceInteraction si; Counters c; WalkCount wc;
-        const bool hit = r->Intersect(ray, &si, c, wc);
-        tOut[i] = ray.tMax; primOut[i] = hit ? si.ordered : -1;
-        bary[3 * i] = hit ? si.b0 : 0.f; bary[3 * i + 1] = hit ? si.b1 : 0.f; bary[3 * i + 2] = hit ? si.b2 : 0.f;
-        counters4[4 * i] = wc.nodes; counters4[4 * i + 1] = wc.interior; counters4[4 * i + 2] = c.triTests; counters4[4 * i + 3] = c.sphereTests;
-    }
+    IntersectRays((const KdScene *)h, n, o, d, tmax, tOut, primOut, bary, counters4, 4);
 }
 void kdref_occluded(void *h, size_t n, const float *o, const float *d, const float *tmax, uint8_t *occ, uint64_t *counters4) {
-    SceneRef *r = (SceneRef *)h;
-    for (size_t i = 0; i < n; ++i) {
-        Ray ray(V3(o[3 * i], o[3 * i + 1], o[3 * i + 2]), V3(d[3 * i], d[3 * i + 1], d[3 * i + 2]), tmax[i]);
-        Counters c; WalkCount wc;
-        occ[i] = r->IntersectP(ray, c, wc) ? 1 : 0;
-        counters4[4 * i] = wc.nodes; counters4[4 * i + 1] = wc.interior; counters4[4 * i + 2] = c.triTestsP; counters4[4 * i + 3] = c.sphereTestsP;
-    }
+    OccludedRays((const KdScene *)h, n, o, d, tmax, occ, counters4, 4);
 }
 
 }  // extern "C"

@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, KILLEROO, ROOT
-import bsppaper_ref
+from tree_ref import bsppaper as bsppaper_ref
 
 DODECA = os.path.join(GOLDEN, "dodecahedron.hprt")
 

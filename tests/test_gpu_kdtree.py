@@ -1,15 +1,15 @@
 """The kd walk on the GPU (Accelerator "kdtree"): closest and any hit held bit for bit to the test-side restatement of
-KdTreeAccel::Intersect / IntersectP (tests/kd_reference.cpp) — t, primitive, barycentrics and all four counters — on camera,
-random, degenerate and on-the-split-plane rays; renders against the reference's images; per-pixel statistics; tile sharding;
-kernel resources."""
+KdTreeAccel::Intersect / IntersectP (tests/kd_reference.cpp over tests/tree_reference.h) — t, primitive, barycentrics and all four
+counters — on camera, random, degenerate and on-the-split-plane rays; renders against the reference's images; per-pixel
+statistics; tile sharding; kernel resources.  The checks shared with the other tree walks are tests/tree_walk_checks.py's."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, KILLEROO, ROOT
-import kd_ref
+from conftest import GOLDEN, KILLEROO
+from tree_ref import kd as kd_ref
+import tree_walk_checks as twc
 
 pytestmark = pytest.mark.gpu
 DODECA = os.path.join(GOLDEN, "dodecahedron.hprt")
@@ -29,15 +29,7 @@ def _rays(ref, oracle, n, seed):
     lo, hi = ref.bounds()
     blo, bhi = lo.min(0), hi.max(0)
     ext = bhi - blo
-    out = []
-    # camera rays
-    o, d = oracle.camera_rays(rng.integers(0, 700, n).astype(np.int32), rng.integers(0, 700, n).astype(np.int32), rng.integers(0, 8, n).astype(np.int64))
-    out.append((o, d, np.full(n, np.inf, np.float32)))
-    # random rays from inside and around the scene, finite and infinite
-    o = (blo + rng.uniform(-0.2, 1.2, (n, 3)) * ext).astype(np.float32)
-    d = rng.normal(size=(n, 3)).astype(np.float32)
-    tm = np.where(rng.uniform(size=n) < 0.5, np.inf, rng.uniform(0, 1, n) * np.linalg.norm(ext)).astype(np.float32)
-    out.append((o, d, tm))
+    out = [twc.camera_rays(rng, oracle, n), twc.random_rays(rng, blo, ext, n)]
     # zero direction components of either sign (1 / 0 = inf, 0 * inf = NaN), NaN / inf directions, rays aimed at primitives
     o = (blo + rng.uniform(-0.2, 1.2, (n, 3)) * ext).astype(np.float32)
     d = rng.normal(size=(n, 3)).astype(np.float32)
@@ -59,107 +51,37 @@ def _rays(ref, oracle, n, seed):
     return out
 
 
-def _bits(a):
-    """float bits with every NaN made one: a NaN direction gives a NaN "hit" in both walks (every comparison of the triangle
-    test is false), but the host's and the device's NaNs carry different sign / payload bits"""
-    a = np.where(np.isnan(a), np.float32(np.nan), a).astype(np.float32)
-    return a.view(np.uint32)
-
-
 def test_closest_hit_equals_the_reference_walk(kd):
     _, _, sc, ref, oracle = kd
-    for i, (o, d, tm) in enumerate(_rays(ref, oracle, 20000, 1)):
-        t0, p0, b0, c0 = ref.intersect(o, d, tm)
-        t1, p1, b1, c1 = sc.intersect(o, d, tm, count=True)
-        assert np.array_equal(p0, p1), (i, int((p0 != p1).sum()))
-        assert np.array_equal(_bits(t0), _bits(t1)), i
-        assert np.array_equal(_bits(b0), _bits(b1)), i
-        assert c1.tolist() == c0.sum(0).tolist(), (i, c1, c0.sum(0))
-        assert c1[1] > 0 and c1[0] > c1[1]
+    twc.check_closest(sc, ref, _rays(ref, oracle, 20000, 1))
 
 
 def test_any_hit_equals_the_reference_walk(kd):
     _, _, sc, ref, oracle = kd
-    for i, (o, d, tm) in enumerate(_rays(ref, oracle, 20000, 2)):
-        occ0, c0 = ref.occluded(o, d, tm)
-        occ1, c1 = sc.occluded(o, d, tm, count=True)
-        assert np.array_equal(occ0, occ1), (i, int((occ0 != occ1).sum()))
-        assert c1.tolist() == c0.sum(0).tolist(), (i, c1, c0.sum(0))
+    twc.check_any(sc, ref, _rays(ref, oracle, 20000, 2))
 
 
 def test_device_entry_points_agree_with_the_host_ones(kd):
-    import torch
     _, _, sc, ref, oracle = kd
-    o, d, tm = _rays(ref, oracle, 4096, 3)[1]
-    t0, p0, b0 = sc.intersect(o, d, tm)
-    occ0 = sc.occluded(o, d, tm)
-    n = tm.shape[0]
-    rays7 = torch.from_numpy(np.concatenate([o.T, d.T, tm[None]], 0).astype(np.float32).copy()).cuda()
-    t = torch.zeros(n, dtype=torch.float32, device="cuda"); p = torch.zeros(n, dtype=torch.int32, device="cuda")
-    b = torch.zeros(3 * n, dtype=torch.float32, device="cuda"); occ = torch.zeros(n, dtype=torch.uint8, device="cuda")
-    sc.intersect_device(n, rays7.data_ptr(), t.data_ptr(), p.data_ptr(), b.data_ptr())
-    sc.occluded_device(n, rays7.data_ptr(), occ.data_ptr())
-    torch.cuda.synchronize()
-    assert np.array_equal(p.cpu().numpy(), p0) and np.array_equal(t.cpu().numpy().view(np.uint32), t0.view(np.uint32))
-    assert np.array_equal(np.ascontiguousarray(b.cpu().numpy().reshape(3, n).T).view(np.uint32), b0.view(np.uint32))
-    assert np.array_equal(occ.cpu().numpy(), occ0)
-
-
-def _srgb8(rgb):
-    v = rgb.astype(np.float64)
-    g = np.where(v <= 0.0031308, 12.92 * v, 1.055 * np.power(np.maximum(v, 1e-30), 1 / 2.4) - 0.055)
-    return np.clip(255.0 * g + 0.5, 0, 255).astype(np.int32)
+    twc.check_device_entry_points(sc, *_rays(ref, oracle, 4096, 3)[1])
 
 
 def test_kd_renders_match_the_reference_images(hprt, kd):
     path, m, sc, _, _ = kd
-    opt = m.options.copy()
-    opt.spp = 8
-    film, st = sc.render(opt)
-    rgb = hprt.film_resolve(film, opt.film_scale)
-    name = "killeroo_simple" if path == KILLEROO else "dodecahedron"
-    ref = np.load(os.path.join(GOLDEN, name + "_8spp_srgb8.npz"))["srgb8"].astype(np.int32)
-    d = np.abs(_srgb8(rgb) - ref).astype(np.float64)
-    # the tolerances the BVH films are held to (tests/test_oracle_pins.py)
-    if name == "killeroo_simple":
-        assert d.mean() < 0.002 and d.max() <= 9 and (d > 2).mean() < 3e-4, (d.mean(), d.max(), (d > 2).mean())
-    else:
-        assert d.max() == 0, (d.max(), int((d != 0).sum()))
+    twc.check_reference_image(hprt, sc, m, path)
 
 
 def test_counting_render_pixel_stats(hprt, kd, tmp_path):
     _, m, sc, _, _ = kd
-    opt = m.options.copy()
-    opt.spp = 2
-    for i, c in enumerate((0.4, 0.4 + 48 / 700.0, 0.45, 0.45 + 40 / 700.0)):
-        opt.crop[i] = c
-    film, st = sc.render(opt, count_work=True, pixel_stats=True)
-    px = sc.pixel_stats()
-    s = px.reshape(-1, 7).sum(0)
-    assert s[5] > 0 and s[6] > 0 and s[3] > 0
-    assert s[5] == st["nodes_entered"] and s[6] == st["nodes_entered_p"]
-    assert s[3] + s[5] == st["nodes_fetched"] and s[4] + s[6] == st["nodes_fetched_p"]
-    assert s[1] == st["tri_tests"] + st["sphere_tests"] and s[2] == st["tri_tests_p"] + st["sphere_tests_p"]
+    st, px, check_plain_film = twc.check_counting_render(sc, m)
     hprt.write_pixel_stats_accel(str(tmp_path / "kd"), px, hprt.ACCEL_KDTREE)
     assert np.array_equal(np.loadtxt(tmp_path / "kd-kdTreeNodeTraversals.txt", dtype=np.uint64).reshape(px.shape[:2]), px[:, :, 5])
-    # the counted render's film is the plain render's
-    film2, _ = sc.render(opt)
-    assert np.array_equal(film.view(np.uint32), film2.view(np.uint32))
+    check_plain_film()
 
 
 def test_tile_sharded_kd_render_merges_bit_identically(hprt, kd):
     _, m, sc, _, _ = kd
-    opt = m.options.copy()
-    opt.spp = 2
-    for i, c in enumerate((0.3, 0.3 + 96 / 700.0, 0.35, 0.35 + 80 / 700.0)):
-        opt.crop[i] = c
-    full, _ = sc.render(opt)
-    parts, recs = [], []
-    for r in range(3):
-        f, _ = sc.render(opt, tile_begin=r, tile_stride=3, export_foreign=True)
-        parts.append(f); recs.append(sc.film_records())
-    merged = hprt.film_records_merge(np.sum(parts, 0).astype(np.float32), np.concatenate(recs))
-    assert np.array_equal(merged.view(np.uint32), full.view(np.uint32))
+    twc.check_tile_sharding(hprt, sc, m)
 
 
 def test_attach_refusals(hprt):
@@ -183,34 +105,4 @@ def test_attach_refusals(hprt):
 def test_kd_walk_resources(hprt, tmp_path):
     """Triangle-only kernels: <= 80 registers (six workgroups per CU), nothing in scratch; quadric kernels <= 128 (four);
     LDS: eight 8-byte todo entries per lane of a 256-thread workgroup."""
-    import yaml
-    llvm = "/opt/rocm/lib/llvm/bin"
-    lib = os.path.join(ROOT, "thesis-pbrt-v3_amd", "lib", "libhprt.so")
-    fat = str(tmp_path / "fat.bin")
-    subprocess.run([llvm + "/llvm-objcopy", "--dump-section", ".hip_fatbin=" + fat, lib], check=True)
-    data = open(fat, "rb").read()
-    # one offload bundle per translation unit: kd_walk.hip's is not the first
-    magic = b"__CLANG_OFFLOAD_BUNDLE__"
-    starts = []
-    pos = data.find(magic)
-    while pos >= 0:
-        starts.append(pos); pos = data.find(magic, pos + 1)
-    ks = {}
-    for j, s0 in enumerate(starts):
-        part, co = str(tmp_path / ("b%d.bin" % j)), str(tmp_path / ("b%d.co" % j))
-        open(part, "wb").write(data[s0:starts[j + 1] if j + 1 < len(starts) else len(data)])
-        if subprocess.run([llvm + "/clang-offload-bundler", "--unbundle", "--type=o", "--input=" + part, "--targets=hipv4-amdgcn-amd-amdhsa--gfx950",
-                           "--output=" + co], capture_output=True).returncode != 0 or os.path.getsize(co) == 0:
-            continue
-        notes = subprocess.run([llvm + "/llvm-readelf", "--notes", co], check=True, capture_output=True, text=True).stdout
-        if "---" not in notes:
-            continue
-        meta = yaml.safe_load(notes[notes.index("---"):notes.rindex("...")])
-        ks.update({k[".name"]: k for k in meta.get("amdhsa.kernels", []) if "k_kdwalk" in k[".name"]})
-    assert len(ks) == 8, sorted(ks)
-    for name, k in ks.items():
-        quad = name.split("k_kdwalkI")[1].split("Lb")[3].startswith("1")      # <ANY_HIT, COUNT, QUAD>
-        assert k[".group_segment_fixed_size"] == 8 * 256 * 8, name
-        assert k[".vgpr_count"] <= (128 if quad else 80) and k[".vgpr_spill_count"] == 0, (name, k[".vgpr_count"])
-        if not quad:
-            assert k[".private_segment_fixed_size"] == 0, name
+    twc.check_walk_resources(tmp_path, "k_kdwalk", 8 * 256 * 8)

@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, KILLEROO
-import kd_ref
+from tree_ref import kd as kd_ref
 
 DODECA = os.path.join(GOLDEN, "dodecahedron.hprt")
 

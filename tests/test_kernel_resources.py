@@ -3,28 +3,14 @@ needed).  DESIGN.md §4 (f), (g): the plain closest-hit kernel of triangle-only 
 80 registers and 24 KB of LDS stack, the any-hit kernel seven (72 registers, 20 KB), the any-hit kernel with quadric code five
 (96 registers, 24 KB).  hipcc's register allocation is fragile — an unrelated edit has turned 3 spilled dwords into 11, inside the
 loop — so the numbers the launch code relies on are pinned here."""
-import os
-import subprocess
-
 import pytest
-import yaml
 
-from conftest import ROOT
-
-LLVM = "/opt/rocm/lib/llvm/bin"
+from tree_walk_checks import LIBHPRT, kernel_metadata
 
 
 @pytest.fixture(scope="module")
 def kernels(hprt, tmp_path_factory):
-    d = tmp_path_factory.mktemp("co")
-    lib = os.path.join(ROOT, "thesis-pbrt-v3_amd", "lib", "libhprt.so")
-    fat, co = str(d / "fat.bin"), str(d / "dev.co")
-    subprocess.run([LLVM + "/llvm-objcopy", "--dump-section", ".hip_fatbin=" + fat, lib], check=True)
-    subprocess.run([LLVM + "/clang-offload-bundler", "--unbundle", "--type=o", "--input=" + fat, "--targets=hipv4-amdgcn-amd-amdhsa--gfx950",
-                    "--output=" + co], check=True)
-    notes = subprocess.run([LLVM + "/llvm-readelf", "--notes", co], check=True, capture_output=True, text=True).stdout
-    meta = yaml.safe_load(notes[notes.index("---"):notes.rindex("...")])
-    return {k[".name"]: k for k in meta["amdhsa.kernels"]}
+    return kernel_metadata(LIBHPRT, tmp_path_factory.mktemp("co"))
 
 
 def _trace(kernels, any_hit, mode, inst, quad):

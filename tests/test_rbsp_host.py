@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, KILLEROO, ROOT
-import rbsp_ref
+from tree_ref import rbsp as rbsp_ref
 
 DODECA = os.path.join(GOLDEN, "dodecahedron.hprt")
 

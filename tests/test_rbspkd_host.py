@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, KILLEROO, ROOT
-import rbspkd_ref
+from tree_ref import rbspkd as rbspkd_ref
 
 DODECA = os.path.join(GOLDEN, "dodecahedron.hprt")
 

@@ -3,83 +3,26 @@ hprt_intersect_device / hprt_occluded_device.  Scenes: killeroo-simple and the a
 Ray sets: camera rays (closest hit, 700x700 x 4 samples, tile order) and shadow rays from their hit points to a point above
 the scene's centre (any hit).  Prints one JSON line per scene; DESIGN.md quotes them.
 usage: python tools/bench_kdtree.py [iters]"""
-import importlib, json, os, sys, tempfile
-import numpy as np
-import torch
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests")); sys.path.insert(0, os.path.join(ROOT, "tools"))
-hprt = importlib.import_module("thesis-pbrt-v3_amd")
-import orc
-import scene_gen
+import json, sys
+import walk_bench as wb
+from walk_bench import hprt
 
 iters = int(sys.argv[1]) if len(sys.argv) > 1 else 5
-dev = torch.device("cuda", 0)
 
-
-def scene_model(name):
-    if name == "killeroo-simple":
-        path = os.path.join(ROOT, "tests", "golden", "killeroo_simple.hprt")
-        return hprt.Model.load(path), path
-    d = tempfile.mkdtemp(prefix="hprt_kd_")
-    p = os.path.join(d, "atrium.pbrt")
-    open(p, "w").write(scene_gen.atrium(1.0)[0])
-    m = hprt.Model.parse(p)
-    baked = os.path.join(d, "atrium.hprt")
-    m.save(baked)
-    return m, baked
-
-
-def to7(o, d, tmax):
-    return torch.from_numpy(np.concatenate([o.T, d.T, tmax[None]], 0).astype(np.float32).copy()).to(dev)
-
-
-def timed(fn):
-    fn(); torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    best = 1e30
-    for _ in range(iters):
-        e0.record(); fn(); e1.record(); torch.cuda.synchronize()
-        best = min(best, e0.elapsed_time(e1))
-    return best
-
-
-out = {}
 for name in ("killeroo-simple", "atrium"):
-    m, baked = scene_model(name)
-    oracle = orc.OracleScene(baked)
-    px, py = [], []
-    for ty in range(44):
-        for tx in range(44):
-            X, Y = np.meshgrid(np.arange(tx * 16, min(tx * 16 + 16, 700)), np.arange(ty * 16, min(ty * 16 + 16, 700)))
-            px.append(X.ravel()); py.append(Y.ravel())
-    px = np.tile(np.concatenate(px).astype(np.int32), 4); py = np.tile(np.concatenate(py).astype(np.int32), 4)
-    s = np.repeat(np.arange(4), px.shape[0] // 4).astype(np.int64)
-    o, d = oracle.camera_rays(px, py, s)
-    n = o.shape[0]
-    inf = np.full(n, np.inf, np.float32)
+    m, baked = wb.scene_model(name)
     bvh_scene = hprt.Scene(m, hprt.Bvh(m), device=0)
     kd_scene = hprt.Scene(m, hprt.Bvh(m), device=0)
     tree = hprt.KdTree(m)
     kd_scene.attach_kdtree(tree)
-    t, prim, _ = kd_scene.intersect(o, d, inf)
-    hitm = prim >= 0
-    p = (o + d * np.where(np.isfinite(t), t, 0)[:, None]).astype(np.float32)[hitm]
-    light = np.array([np.mean(p[:, 0]), np.mean(p[:, 1]), np.max(p[:, 2]) + 1.0], np.float32)
-    sd = (light - p).astype(np.float32)
-    so = p + sd * np.float32(1e-4)
-    stm = np.full(so.shape[0], 1 - 1e-4, np.float32)
-    R = to7(o, d, inf); S = to7(so, sd, stm)
-    ns = so.shape[0]
-    tt = torch.empty(n, dtype=torch.float32, device=dev); pp = torch.empty(n, dtype=torch.int32, device=dev)
-    bb = torch.empty(3 * n, dtype=torch.float32, device=dev); occ = torch.empty(ns, dtype=torch.uint8, device=dev)
-    res = {"closest_rays": n, "any_rays": ns, "kd_nodes": tree.info()["nodes"], "kd_depth": tree.info()["depth"]}
+    rays = wb.RaySets(baked, kd_scene)
+    res = {"closest_rays": rays.n, "any_rays": rays.ns, "kd_nodes": tree.info()["nodes"], "kd_depth": tree.info()["depth"]}
     for label, sc in (("kd", kd_scene), ("walk4", bvh_scene)):
-        mc = timed(lambda: sc.intersect_device(n, R.data_ptr(), tt.data_ptr(), pp.data_ptr(), bb.data_ptr()))
-        ma = timed(lambda: sc.occluded_device(ns, S.data_ptr(), occ.data_ptr()))
-        res[label + "_closest_grays"] = round(n / mc / 1e6, 3)
-        res[label + "_any_grays"] = round(ns / ma / 1e6, 3)
+        mc = wb.timed(lambda: rays.closest(sc), iters)
+        ma = wb.timed(lambda: rays.any(sc), iters)
+        res[label + "_closest_grays"] = round(rays.n / mc / 1e6, 3)
+        res[label + "_any_grays"] = round(rays.ns / ma / 1e6, 3)
     # the two walks answer the same rays the same way up to ties between equally distant hits
-    t1, p1, _ = bvh_scene.intersect(o, d, inf)
-    res["closest_same_prim_frac"] = float((p1 == prim).mean())
-    out[name] = res
+    t1, p1, _ = bvh_scene.intersect(rays.o, rays.d, rays.inf)
+    res["closest_same_prim_frac"] = float((p1 == rays.prim).mean())
     print(json.dumps({name: res}), flush=True)
