@@ -246,6 +246,45 @@ int hprt_bsppaper_copy(const HprtBspPaper *t, void *nodes20, uint32_t *prim_indi
 void hprt_bsppaper_destroy(HprtBspPaper *t);
 
 /* ------------------------------------------------------------------------ */
+/* kd-aware general BSP tree (Accelerator "bsppaperkd").  Stands in for     */
+/* BSPPaperKd::buildTree (accelerators/bspPaperKd.cpp:34-339) over BSPKd    */
+/* and BSPKdNode (accelerators/BSPKd.h:11-193): the bsppaper tree's         */
+/* candidates and k-DOP cost model, with axis splits costed                 */
+/* kd_trav_cost + C_isect and triangle-plane splits                         */
+/* 0.1 * isect_cost * (N - 1) + kd_trav_cost + C_isect; a second minimum,   */
+/* trav_cost + C_isect over the plane splits, takes part in the leaf tests  */
+/* and supplies the split only where the first minimum is unset.  Nodes are */
+/* the reference's 20-byte BSPKdNode[]: word 0 as bsppaper's; word 1 flags, */
+/* whose low 3 bits are 0-2 a kd interior node with that axis, 3 a leaf,    */
+/* 4 a plane interior node, with aboveChild / nPrims << 3; words 2-4 the    */
+/* split axis of a plane node, zero for kd nodes and leaves (the reference  */
+/* leaves those uninitialised).  A handle of its own: a bsppaperkd tree is  */
+/* walked with the kd form at kd nodes and can never reach the bsppaper     */
+/* walk.  "nbDirections" only feeds a statistic and is ignored.             */
+/* ------------------------------------------------------------------------ */
+typedef struct HprtBspPaperKd HprtBspPaperKd;
+typedef struct HprtBspPaperKdParams {
+    int isect_cost;     /* "intersectcost", default 80 */
+    int trav_cost;      /* "traversalcost", default 5 */
+    int kd_trav_cost;   /* "kdtraversalcost", default 1 */
+    float empty_bonus;  /* "emptybonus", default 0 */
+    int max_prims;      /* "maxprims", default 1 */
+    int max_depth;      /* "maxdepth", default -1 = round(2 + 1.6 Log2Int(N)) */
+    int threads;        /* builder threads (0: OMP_NUM_THREADS, else 16; at most 16); the tree does not depend on it */
+} HprtBspPaperKdParams;
+/* As hprt_bsppaper_build (CreateBSPPaperKdTreeAccelerator, accelerators/bspPaperKd.cpp:341-353): params NULL takes the scene's
+ * Accelerator line; instanced models and trees deeper than HPRT_BSPPAPERKD_MAX_DEPTH are HPRT_E_UNSUPPORTED. */
+int hprt_bsppaperkd_build(const HprtModel *m, const HprtBspPaperKdParams *params, HprtBspPaperKd **out);
+int hprt_bsppaperkd_build_from_triangles(size_t n_tris, const float *p9, const HprtBspPaperKdParams *params, HprtBspPaperKd **out);
+/* info[0..5] = nodes, leaves, depth, primitive references (hprt_bsppaper_info's slots), kd interior nodes (nbKdNodes), plane
+ * interior nodes (nbBSPNodes) */
+int hprt_bsppaperkd_info(const HprtBspPaperKd *t, uint32_t info[6]);
+#define HPRT_BSPPAPERKD_MAX_DEPTH 64   /* the device walk's todo capacity: pbrt's maxTodo (BSPKd.cpp:36) */
+/* nodes20: info[0] * 20 bytes (5 words per node, the reference's BSPKdNode); prim_indices: info[3] uint32 (either may be NULL) */
+int hprt_bsppaperkd_copy(const HprtBspPaperKd *t, void *nodes20, uint32_t *prim_indices);
+void hprt_bsppaperkd_destroy(HprtBspPaperKd *t);
+
+/* ------------------------------------------------------------------------ */
 /* Device scene.  Upload step that follows the BVH build: stands in for the  */
 /* `primitives`/`nodes` members BVHAccel keeps (accelerators/bvh.h:69-79) and */
 /* the Scene object (core/scene.h:50-80).  The library copies everything to   */
@@ -377,8 +416,14 @@ int hprt_scene_attach_rbspkd(HprtScene *s, const HprtRbspKd *t);
  * nodes), [2] triangle tests, [3] sphere tests; HPRT_RENDER_PIXEL_STATS slots 5 / 6 hold bspTreeNodeTraversals[P]
  * (hprt_write_pixel_stats_accel with HPRT_ACCEL_BSP). */
 int hprt_scene_attach_bsppaper(HprtScene *s, const HprtBspPaper *t);
+/* The same for a kd-aware general BSP tree (BSPKd::Intersect / IntersectP, accelerators/BSPKd.cpp:25-171).  Attaching any of the
+ * five trees replaces whichever was attached before; a refused attach leaves the previous walk in place.  Counters of a
+ * bsppaperkd scene follow the rbspkd scene's: [1] and HPRT_RENDER_PIXEL_STATS slots 5 / 6 hold every interior node
+ * (kdTreeNodeTraversals + bspTreeNodeTraversals), and the kd share comes from hprt_scene_kd_counters and
+ * hprt_pixel_kd_stats_read. */
+int hprt_scene_attach_bsppaperkd(HprtScene *s, const HprtBspPaperKd *t);
 /* kdTreeNodeTraversals (out[0]) and kdTreeNodeTraversalsP (out[1]) of the last counting trace (hprt_intersect / hprt_occluded
- * with counters) or counting render of an rbspkd scene; zeros for any other scene. */
+ * with counters) or counting render of an rbspkd or bsppaperkd scene; zeros for any other scene. */
 int hprt_scene_kd_counters(HprtScene *s, uint64_t out[2]);
 
 /* ------------------------------------------------------------------------ */
@@ -482,7 +527,7 @@ int hprt_scene_reserve(HprtScene *s, const HprtRenderDesc *desc);
  * adds its counters once (core/integrator.cpp:327-328, integrators/path.cpp:92-200, core/light.cpp:62).
  * Pixels of tiles that were not rendered hold zeros, so per-rank results add up like the film. */
 int hprt_pixel_stats_read(HprtScene *s, uint64_t *out7, size_t n_pixels);
-/* For a render of an rbspkd scene with HPRT_RENDER_PIXEL_STATS: the per-pixel kd share of slots 5 / 6, as two planes
+/* For a render of an rbspkd or bsppaperkd scene with HPRT_RENDER_PIXEL_STATS: the per-pixel kd share of slots 5 / 6, as two planes
  * (out2[0 .. n) kdTreeNodeTraversals, out2[n .. 2n) kdTreeNodeTraversalsP), row-major like hprt_pixel_stats_read. */
 int hprt_pixel_kd_stats_read(HprtScene *s, uint64_t *out2, size_t n_pixels);
 /* Film::WriteGeneralStats (core/film.cpp:170-264): writes <prefix>-primitiveIntersections.txt,
@@ -498,7 +543,7 @@ int hprt_write_pixel_stats(const char *prefix, const uint64_t *stats7, int width
 #define HPRT_ACCEL_RBSP 2          /* slots 5 / 6 go to -bspTreeNodeTraversals[P].txt (core/film.cpp:176-177) */
 #define HPRT_ACCEL_BSP HPRT_ACCEL_RBSP     /* the general BSP tree (bsppaper): its interior nodes are bspTreeNodeTraversals too */
 int hprt_write_pixel_stats_accel(const char *prefix, const uint64_t *stats7, int width, int height, int accel);
-/* The same for an rbspkd render: -kdTreeNodeTraversals[P].txt from kd2 (hprt_pixel_kd_stats_read's two planes) and
+/* The same for an rbspkd or bsppaperkd render: -kdTreeNodeTraversals[P].txt from kd2 (hprt_pixel_kd_stats_read's two planes) and
  * -bspTreeNodeTraversals[P].txt = slot 5 / 6 minus the kd share, as Film::WriteGeneralStats does (core/film.cpp:174-177). */
 int hprt_write_pixel_stats_rbspkd(const char *prefix, const uint64_t *stats7, const uint64_t *kd2, int width, int height);
 /* Film::WriteImage arithmetic (core/film.cpp:266-303) on a host copy of a film

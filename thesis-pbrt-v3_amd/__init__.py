@@ -9,6 +9,7 @@ accelerates:
     Rbsp    <- CreateRBSPTreeAccelerator / buildTree  (accelerators/rbsp.cpp:181-403,549-571)
     RbspKd  <- CreateRBSPKdTreeAccelerator / buildTree (accelerators/rbspKd.cpp:194-488,640-665)
     BspPaper <- CreateBSPPaperTreeAccelerator / buildTree (accelerators/bspPaper.cpp:34-319)
+    BspPaperKd <- CreateBSPPaperKdTreeAccelerator / buildTree (accelerators/bspPaperKd.cpp:34-353)
     Scene   <- Scene + BVHAccel::Intersect/IntersectP (accelerators/bvh.cpp:354-437)
                and SamplerIntegrator::Render with PathIntegrator::Li
                (core/integrator.cpp:230-360, integrators/path.cpp:64-204)
@@ -127,7 +128,7 @@ class RbspKdParams(C.Structure):
 
 
 class _Tree:
-    """A host tree handle (KdTree, Rbsp, RbspKd, BspPaper) over the C calls hprt_<_prefix>_info / _copy / _destroy: info() names the info
+    """A host tree handle (KdTree, Rbsp, RbspKd, BspPaper, BspPaperKd) over the C calls hprt_<_prefix>_info / _copy / _destroy: info() names the info
     words `_info_keys`; the copy of the RBSP trees takes a direction table as well (M in info)."""
     _prefix = None
     _info_keys = ()
@@ -277,6 +278,12 @@ def _load():
         "hprt_bsppaper_copy": (C.c_int, [vp, vp, vp]),
         "hprt_bsppaper_destroy": (None, [vp]),
         "hprt_scene_attach_bsppaper": (C.c_int, [vp, vp]),
+        "hprt_bsppaperkd_build": (C.c_int, [vp, vp, P(vp)]),
+        "hprt_bsppaperkd_build_from_triangles": (C.c_int, [sz, vp, vp, P(vp)]),
+        "hprt_bsppaperkd_info": (C.c_int, [vp, P(u32)]),
+        "hprt_bsppaperkd_copy": (C.c_int, [vp, vp, vp]),
+        "hprt_bsppaperkd_destroy": (None, [vp]),
+        "hprt_scene_attach_bsppaperkd": (C.c_int, [vp, vp]),
         "hprt_scene_kd_counters": (C.c_int, [vp, vp]),
         "hprt_pixel_kd_stats_read": (C.c_int, [vp, vp, sz]),
         "hprt_write_pixel_stats_rbspkd": (C.c_int, [cp, vp, vp, C.c_int, C.c_int]),
@@ -514,6 +521,46 @@ class BspPaper(_Tree):
         return nodes, idx
 
 
+class BspPaperKdParams(C.Structure):
+    """HprtBspPaperKdParams: CreateBSPPaperKdTreeAccelerator's parameters plus the builder's thread count."""
+    _fields_ = [("isect_cost", C.c_int), ("trav_cost", C.c_int), ("kd_trav_cost", C.c_int), ("empty_bonus", C.c_float), ("max_prims", C.c_int),
+                ("max_depth", C.c_int), ("threads", C.c_int)]
+
+
+class BspPaperKd(_Tree):
+    """kd-aware general BSP tree (host): CreateBSPPaperKdTreeAccelerator(prims, params) — BSPKdNode[] (20 bytes) and
+    primitiveIndices as the reference builds them.  BspPaperKd(model) takes the scene's Accelerator line; given isect_cost, the
+    keyword parameters replace it."""
+    _prefix = "bsppaperkd"
+    _info_keys = ("nodes", "leaves", "depth", "prim_refs", "kd_interior", "plane_interior")
+
+    def __init__(self, model=None, handle=None, isect_cost=None, trav_cost=5, kd_trav_cost=1, empty_bonus=0.0, max_prims=1, max_depth=-1, threads=0):
+        if handle is None:
+            handle = C.c_void_p()
+            prm = None if isect_cost is None else C.byref(BspPaperKdParams(isect_cost, trav_cost, kd_trav_cost, empty_bonus, max_prims, max_depth, threads))
+            _check(lib.hprt_bsppaperkd_build(model._h, prm, C.byref(handle)))
+        self._h = handle
+
+    @staticmethod
+    def from_triangles(p9, isect_cost=80, trav_cost=5, kd_trav_cost=1, empty_bonus=0.0, max_prims=1, max_depth=-1, threads=0):
+        """p9: [n, 9] (or [n, 3, 3]) float32 world-space triangle vertices in creation order."""
+        p9 = np.ascontiguousarray(p9, np.float32).reshape(-1, 9)
+        h = C.c_void_p()
+        prm = BspPaperKdParams(isect_cost, trav_cost, kd_trav_cost, empty_bonus, max_prims, max_depth, threads)
+        _check(lib.hprt_bsppaperkd_build_from_triangles(p9.shape[0], _ptr(p9), C.byref(prm), C.byref(h)))
+        return BspPaperKd(handle=h)
+
+    def arrays(self):
+        """(nodes [n, 5] uint32: the reference's BSPKdNode — word 0 split / onePrimitive / primitiveIndicesOffset, word 1 flags
+        (low 3 bits: 0-2 kd axis, 3 leaf, 4 plane node; aboveChild / nPrims << 3), words 2-4 splitAxis as float bits (zero for kd
+        nodes and leaves); prim_indices uint32)"""
+        inf = self.info()
+        nodes = np.zeros((inf["nodes"], 5), np.uint32)
+        idx = np.zeros(inf["prim_refs"], np.uint32)
+        self._call("copy", _ptr(nodes), _ptr(idx))
+        return nodes, idx
+
+
 class Scene:
     """Device-resident scene: Aggregate (Intersect/IntersectP) + Integrator (Render)."""
 
@@ -557,9 +604,16 @@ class Scene:
         _check(lib.hprt_scene_attach_bsppaper(self._h, bsppaper._h))
         self._bsppaper = bsppaper
 
+    def attach_bsppaperkd(self, bsppaperkd):
+        """hprt_scene_attach_bsppaperkd: every later trace and render walks `bsppaperkd` (a BspPaperKd over this scene's
+        primitives); replaces any attached tree.  Counters and pixel statistics follow the rbspkd scene's (kd_counters,
+        pixel_kd_stats, write_pixel_stats_rbspkd)."""
+        _check(lib.hprt_scene_attach_bsppaperkd(self._h, bsppaperkd._h))
+        self._bsppaperkd = bsppaperkd
+
     def kd_counters(self):
-        """(kdTreeNodeTraversals, kdTreeNodeTraversalsP) of the last counting trace or render of an rbspkd scene (zeros
-        otherwise); the counters' [1] / nodes_entered[_p] hold kd and oblique interior nodes together."""
+        """(kdTreeNodeTraversals, kdTreeNodeTraversalsP) of the last counting trace or render of an rbspkd or bsppaperkd scene
+        (zeros otherwise); the counters' [1] / nodes_entered[_p] hold kd and oblique interior nodes together."""
         out = np.zeros(2, np.uint64)
         _check(lib.hprt_scene_kd_counters(self._h, _ptr(out)))
         return int(out[0]), int(out[1])
@@ -653,7 +707,7 @@ class Scene:
 
     def pixel_kd_stats(self):
         """[2, H, W] uint64: the kd share (kdTreeNodeTraversals, kdTreeNodeTraversalsP) of pixel_stats()' slots 5 / 6 after
-        render(pixel_stats=True) of an rbspkd scene."""
+        render(pixel_stats=True) of an rbspkd or bsppaperkd scene."""
         h, w = self._film_shape
         out = np.zeros((2, h, w), np.uint64)
         _check(lib.hprt_pixel_kd_stats_read(self._h, _ptr(out), h * w))
@@ -745,7 +799,7 @@ def write_pixel_stats_accel(prefix, stats7, accel):
 
 
 def write_pixel_stats_rbspkd(prefix, stats7, kd2):
-    """The same for an rbspkd render: kdTreeNodeTraversals[P] from kd2 (Scene.pixel_kd_stats), bspTreeNodeTraversals[P] =
+    """The same for an rbspkd or bsppaperkd render: kdTreeNodeTraversals[P] from kd2 (Scene.pixel_kd_stats), bspTreeNodeTraversals[P] =
     slot 5 / 6 minus that share."""
     stats7 = np.ascontiguousarray(stats7, np.uint64)
     kd2 = np.ascontiguousarray(kd2, np.uint64)

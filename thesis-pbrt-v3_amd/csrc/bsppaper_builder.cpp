@@ -7,6 +7,9 @@
 // pure function of the node's k-DOP, its BVH and the candidate, and the reduction keeps the first minimum in the reference's scan
 // order (axis candidates by axis and edge, then plane candidates by primitive and plane), so the tree does not depend on the
 // thread count.  The winner's two halves are then cut and measured once more, exactly as the scan left them.
+//
+// BspPaperParams::kdAware selects BSPPaperKd::buildTree (accelerators/bspPaperKd.cpp:34-339) over BSPKdNode (BSPKd.h:11-174): the
+// same scan with the kd-aware costs, a second minimum over the plane candidates alone, and the 3-bit node flags.
 #include "bsppaper_builder.h"
 #include <algorithm>
 #include <cmath>
@@ -224,6 +227,11 @@ std::string BuildBspPaperTree(size_t n, const float *bmin, const float *bmax, co
     t = BspPaperTree();
     // CreateBSPPaperTreeAccelerator / GenericBSP: the parameters as the reference holds them (uint32_t, Float)
     const uint32_t isectCost = (uint32_t)p.isectCost, traversalCost = (uint32_t)p.travCost, maxPrims = (uint32_t)p.maxPrims;
+    const bool kdAware = p.kdAware;
+    const uint32_t kdTraversalCost = (uint32_t)p.kdTravCost;
+    const float BSP_ALPHA = 0.1f;                                    // bspPaperKd.cpp:35
+    t.kdAware = kdAware;
+    const uint32_t off = kdAware ? (uint32_t)BSPPAPERKD_OFF : (uint32_t)BSPPAPER_OFF;
     const float emptyBonus = p.emptyBonus;
     uint32_t maxDepth = (uint32_t)p.maxDepth;
     if (maxDepth == (uint32_t)-1) maxDepth = (uint32_t)std::round(2 + 1.6f * (float)Log2Int64((uint64_t)n));   // calculateMaxDepth
@@ -266,7 +274,7 @@ std::string BuildBspPaperTree(size_t n, const float *bmin, const float *bmax, co
     std::vector<BspNode> &nodes = t.nodes;
     auto initLeaf = [&](const uint32_t *primNums, uint32_t np) {     // treeInitLeaf (BSP.h:11-24)
         BspNode nd;
-        nd.b = 1u | (np << 1);
+        nd.b = kdAware ? (BSPPAPERKD_LEAF | (np << BSPPAPERKD_OFF)) : (1u | (np << 1));     // BSPKdNode::initLeaf (BSPKd.h:21-34)
         if (np == 0) nd.a = 0u;
         else if (np == 1) nd.a = primNums[0];
         else {
@@ -279,7 +287,7 @@ std::string BuildBspPaperTree(size_t n, const float *bmin, const float *bmax, co
     };
 
     std::vector<Cand> cands;
-    std::vector<float> costs;
+    std::vector<float> costs, costsFixed;                            // costsFixed: kdAware only, traversalCost + C_isect of a plane candidate
     std::vector<std::vector<uint32_t>> bvhStacks((size_t)nThreads);
     std::vector<std::vector<float>> candDirs((size_t)nThreads);
     std::vector<std::thread> pool;
@@ -289,7 +297,7 @@ std::string BuildBspPaperTree(size_t n, const float *bmin, const float *bmax, co
     while (!stack.empty()) {
         BuildNode cur = std::move(stack.back());
         stack.pop_back();
-        if (cur.parentNum != (uint32_t)-1) nodes[cur.parentNum].b |= (nodeNum << 1);      // treeSetAboveChild
+        if (cur.parentNum != (uint32_t)-1) nodes[cur.parentNum].b |= (nodeNum << off);    // treeSetAboveChild
 
         if (cur.nPrimitives <= maxPrims || cur.depth == 0) { initLeaf(&prims[cur.primNums], cur.nPrimitives); ++nodeNum; continue; }
 
@@ -331,6 +339,7 @@ std::string BuildBspPaperTree(size_t n, const float *bmin, const float *bmax, co
         NodeBvh nb{bmin, bmax, tri9, isTri, primNums, {}, {}, {}};
         if (planeBegin.back() != 0) nb.build(cur.nPrimitives);
         costs.resize(cands.size());
+        if (kdAware) costsFixed.assign(cands.size(), std::numeric_limits<float>::infinity());
         auto costRange = [&](size_t k0, size_t k1, int w) {
             Scratch &s = scratch[(size_t)w];
             for (size_t k = k0; k < k1; ++k) {
@@ -349,7 +358,13 @@ std::string BuildBspPaperTree(size_t n, const float *bmin, const float *bmax, co
                 const float pAbove = areaAbove * invTotalSA;
                 if (c.k == 33u) nb.count(c.plane, &c.nBelow, &c.nAbove, bvhStacks[(size_t)w]);
                 const float eb = (c.nAbove == 0 || c.nBelow == 0) ? emptyBonus : 0;
-                costs[k] = (float)traversalCost + (float)isectCost * (1 - eb) * (pBelow * (float)c.nBelow + pAbove * (float)c.nAbove);
+                if (!kdAware) costs[k] = (float)traversalCost + (float)isectCost * (1 - eb) * (pBelow * (float)c.nBelow + pAbove * (float)c.nAbove);
+                else if (c.k != 33u) costs[k] = (float)kdTraversalCost + (float)isectCost * (1 - eb) * (pBelow * (float)c.nBelow + pAbove * (float)c.nAbove);
+                else {                                               // bspPaperKd.cpp:215-218
+                    const float costIntersection = (float)isectCost * (1 - eb) * (pBelow * (float)c.nBelow + pAbove * (float)c.nAbove);
+                    costsFixed[k] = (float)traversalCost + costIntersection;
+                    costs[k] = BSP_ALPHA * (float)isectCost * (float)(cur.nPrimitives - 1) + (float)kdTraversalCost + costIntersection;
+                }
             }
         };
         if (nThreads > 1 && cands.size() >= kParallelCandidates) {
@@ -367,15 +382,23 @@ std::string BuildBspPaperTree(size_t n, const float *bmin, const float *bmax, co
         float bestCost = std::numeric_limits<float>::infinity();
         for (size_t k = 0; k < cands.size(); ++k)
             if (costs[k] < bestCost) { bestCost = costs[k]; best = k; }
+        // kdAware: the second minimum (bestCostFixed / bestKFixed), over the plane candidates only; else it stays unset
+        size_t bestFixed = (size_t)-1;
+        float bestCostFixed = std::numeric_limits<float>::infinity();
+        if (kdAware)
+            for (size_t k = 0; k < cands.size(); ++k)
+                if (cands[k].k == 33u && costsFixed[k] < bestCostFixed) { bestCostFixed = costsFixed[k]; bestFixed = k; }
 
         // Create leaf if no good splits were found
-        if (bestCost > oldCost) ++cur.badRefines;
-        if ((bestCost > 4 * oldCost && cur.nPrimitives < 16) || best == (size_t)-1 || cur.badRefines == 3) {
+        if (bestCost > oldCost && bestCostFixed > oldCost) ++cur.badRefines;
+        if ((bestCost > 4 * oldCost && bestCostFixed > 4 * oldCost && cur.nPrimitives < 16) || (best == (size_t)-1 && bestFixed == (size_t)-1) ||
+            cur.badRefines == 3) {
             initLeaf(&prims[cur.primNums], cur.nPrimitives); ++nodeNum; continue;
         }
 
-        // the winner's halves, measured (and so reoriented) as the scan left them
-        const Cand win = cands[best];
+        // the winner's halves, measured (and so reoriented) as the scan left them; the fixed minimum's split only where the first
+        // minimum is unset (bspPaperKd.cpp:275-278, :318-329: reachable only when no candidate's first cost is finite)
+        const Cand win = cands[best != (size_t)-1 ? best : bestFixed];
         Scratch &s = scratch[0];
         std::vector<float> childDirs;
         float areaBelow, areaAbove;
@@ -415,15 +438,16 @@ std::string BuildBspPaperTree(size_t n, const float *bmin, const float *bmax, co
 
         BspNode nd;                                    // treeInitInterior (BSP.h:32-37)
         std::memcpy(&nd.a, &win.plane.t, 4);
-        nd.b = 0u;
+        nd.b = !kdAware ? 0u : (win.k != 33u ? win.k : BSPPAPERKD_PLANE);     // BSPKdNode::initInteriorKd / initInterior (BSPKd.h:40-49)
         nodes.push_back(nd);
-        t.axes.insert(t.axes.end(), win.plane.axis, win.plane.axis + 3);
+        if (kdAware && win.k != 33u) t.axes.insert(t.axes.end(), 3, 0.f);     // a kd node holds no axis (the reference leaves it unset)
+        else t.axes.insert(t.axes.end(), win.plane.axis, win.plane.axis + 3);
         stack.push_back(BuildNode{cur.depth - 1, n1, cur.badRefines, std::move(above), childDirs, areaAbove, prims1, nodeNum});
         stack.push_back(BuildNode{cur.depth - 1, n0, cur.badRefines, std::move(below), std::move(childDirs), areaBelow, prims0, (uint32_t)-1});
         ++nodeNum;
     }
     uint32_t depth = 0;
-    (void)CheckBspPaperTree(t, &depth);
+    (void)(kdAware ? CheckBspPaperKdTree(t, &depth) : CheckBspPaperTree(t, &depth));
     t.depth = depth;
     return "";
 }
@@ -439,4 +463,22 @@ const char *CheckBspPaperTree(const BspPaperTree &t, uint32_t *depthOut) {
     return CheckBspNodes(t.nodes, t.primIndices, t.nPrims, BSPPAPER_M, BSPPAPER_OFF, BSPPAPER_MASK, depthOut);
 }
 
+}  // namespace hprt
+
+namespace hprt {
+const char *CheckBspPaperKdTree(const BspPaperTree &t, uint32_t *depthOut) {
+    if (t.axes.size() != 3 * t.nodes.size()) return "the axis array does not hold one axis per node";
+    // CheckBspNodes over M = 3 takes directions 0-2 and the leaf tag 3: a plane node stands in as direction 0 once its axis is checked
+    std::vector<BspNode> nodes(t.nodes);
+    for (size_t k = 0; k < nodes.size(); ++k) {
+        const uint32_t kind = nodes[k].b & BSPPAPERKD_MASK;
+        if (kind > BSPPAPERKD_PLANE) return "a node's flags name no node kind";
+        if (kind != BSPPAPERKD_PLANE) continue;
+        const float *a = &t.axes[3 * k];
+        if (!std::isfinite(a[0]) || !std::isfinite(a[1]) || !std::isfinite(a[2])) return "an interior node's axis is not finite";
+        if (a[0] == 0 && a[1] == 0 && a[2] == 0) return "an interior node's axis is zero";
+        nodes[k].b &= ~BSPPAPERKD_MASK;
+    }
+    return CheckBspNodes(nodes, t.primIndices, t.nPrims, BSPPAPERKD_LEAF, BSPPAPERKD_OFF, BSPPAPERKD_MASK, depthOut);
+}
 }  // namespace hprt

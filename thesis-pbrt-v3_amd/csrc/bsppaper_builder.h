@@ -18,12 +18,21 @@ namespace hprt {
 // BSPNode's first 8 bytes: a = split (float bits) | onePrimitive | primitiveIndicesOffset; b = flags: leaf 1 | nPrims << 1, interior
 // 0 | aboveChild << 1 (treeInitLeaf / treeInitInterior, BSP.h:11-35) — bsp_tree.h's node with M = 1 (off 1, mask 1).
 enum : uint32_t { BSPPAPER_TODO_MAX = 64u, BSPPAPER_M = 1u, BSPPAPER_OFF = 1u, BSPPAPER_MASK = 1u };
+// BSPKdNode's flags (BSPKd.h:11-57), the kd-aware tree's: the low 3 bits are 0-2 a kd interior node with that axis, 3 a leaf, 4 a
+// plane interior node; aboveChild / nPrims << 3
+enum : uint32_t { BSPPAPERKD_TODO_MAX = 64u, BSPPAPERKD_LEAF = 3u, BSPPAPERKD_PLANE = 4u, BSPPAPERKD_OFF = 3u, BSPPAPERKD_MASK = 7u };
 
 struct BspPaperParams {
     int isectCost = 80, travCost = 5;     // "intersectcost", "traversalcost"
     float emptyBonus = 0.f;               // "emptybonus"
     int maxPrims = 1, maxDepth = -1;      // "maxprims", "maxdepth" (-1: round(2 + 1.6 Log2Int(N)), core/geometry.h:1845)
     int threads = 0;                      // candidate evaluation threads: 0 = OMP_NUM_THREADS (else 16), at most 16
+    // Accelerator "bsppaperkd": BSPPaperKd::buildTree (accelerators/bspPaperKd.cpp:34-339) with the defaults of
+    // CreateBSPPaperKdTreeAccelerator (:341-353).  Axis candidates cost kdTravCost + C_isect, plane candidates
+    // 0.1f * isectCost * (N - 1) + kdTravCost + C_isect; a second minimum, travCost + C_isect over the plane candidates, takes part in
+    // the leaf tests and supplies the split only where the first is unset; nodes carry BSPKdNode's flags (BSPPAPERKD_*)
+    bool kdAware = false;
+    int kdTravCost = 1;                   // "kdtraversalcost"
 };
 
 struct BspPaperTree {
@@ -33,6 +42,7 @@ struct BspPaperTree {
     float bounds[6] = {0, 0, 0, 0, 0, 0}; // GenericBSP::bounds (the union of the primitives' world bounds): pMin, pMax
     uint32_t nPrims = 0, leaves = 0, depth = 0, maxDepth = 0;   // depth: interior levels of the deepest path
     uint32_t axisNodes = 0, planeNodes = 0;                     // interior nodes of the axis sweep (nbKdNodes) / of a triangle's plane (nbBSPNodes)
+    bool kdAware = false;                                       // nodes hold BSPKdNode's flags; axes of kd nodes are zero like the leaves'
 };
 
 // One candidate plane of a primitive: Plane {t, axis} (core/geometry.h:1864-1868)
@@ -55,5 +65,8 @@ std::string BuildBspPaperTree(size_t n, const float *bmin, const float *bmax, co
 // Structural check of a tree handed to the device: CheckBspNodes with M = 1, one axis per node, every interior axis finite and
 // non-zero.  Returns an empty string when the tree is well-formed, else what is wrong.
 const char *CheckBspPaperTree(const BspPaperTree &t, uint32_t *depthOut);
+// The same for a kd-aware tree: every node's kind is 0-4, child offsets and leaf ranges as CheckBspNodes with 3 flag bits, and
+// every plane node's axis finite and non-zero.
+const char *CheckBspPaperKdTree(const BspPaperTree &t, uint32_t *depthOut);
 
 }  // namespace hprt

@@ -262,6 +262,8 @@ __attribute__((visibility("default"))) int hprt_debug_capture_rays(HprtScene *s,
     return HPRT_OK;
 }
 static int ApiStreams(HprtScene *s, size_t n, RayStream *rays, HitStream *hits);
+// The walks that count their kd interior nodes apart (kdShare, pixelKdLocal / pixelKdFilm)
+static bool CountsKdShare(const HprtScene *s) { return s->walk == HprtScene::Walk::RbspKd || s->walk == HprtScene::Walk::BspPaperKd; }
 // Every trace of a scene: the walk of the attached tree (AttachTree below), else the BVH walks (LaunchTrace)
 static void Trace(HprtScene *s, hipStream_t st, bool anyHit, bool count, const uint32_t *queue, const uint32_t *countPtr, uint32_t countImm,
                   uint32_t gridItems, const RayStream &rays, const HitStream &hits, uint8_t *occ, DevCounters *counters, uint32_t *workCounter,
@@ -275,6 +277,10 @@ static void Trace(HprtScene *s, hipStream_t st, bool anyHit, bool count, const u
         break;
     case HprtScene::Walk::BspPaper:
         LaunchBspPaperTrace(st, s->dev, s->bsppaper, anyHit, count, queue, countPtr, countImm, gridItems, rays, hits, occ, counters, workCounter, rayStats);
+        break;
+    case HprtScene::Walk::BspPaperKd:
+        LaunchBspPaperKdTrace(st, s->dev, DevBspPaperKd{s->bsppaper, s->kdShare.as<unsigned long long>()}, anyHit, count, queue, countPtr, countImm,
+                              gridItems, rays, hits, occ, counters, workCounter, rayStats);
         break;
     case HprtScene::Walk::Bvh: LaunchTrace(st, s->dev, anyHit, count, queue, countPtr, countImm, gridItems, rays, hits, occ, counters, workCounter, rayStats); break;
     }
@@ -408,13 +414,15 @@ __attribute__((visibility("default"))) int hprt_debug_device_math(int device, in
 
 // A host tree as AttachTree takes it: GenericBSP's node array over M directions (bsp_tree.h) with creation-order primitive numbers,
 // its bounds, its direction table (none for the kd-tree), the deepest tree its walk takes and the builder's structural check, and
-// for a tree whose nodes carry their own split axis (bsppaper) those axes, 3 floats per node
+// for a tree whose nodes carry their own split axis (bsppaper, bsppaperkd) those axes, 3 floats per node.  flagBits / leafTag: a
+// node layout that is not GenericBSP's over M directions (bsppaperkd: 3 flag bits, leaves tagged 3); 0 flagBits: derived from M
 struct TreeView {
     const char *what;                                       // the tree's name in messages
     const std::vector<BspNode> &nodes; const std::vector<uint32_t> &primIndices; uint32_t nPrims; const float *bounds;
     uint32_t M; const std::vector<float> *dirs; uint32_t todoMax;
     std::function<const char *(uint32_t *depth)> check;     // CheckKdTree, CheckRbspTree, CheckBspPaperTree
     const std::vector<float> *axes = nullptr;
+    uint32_t flagBits = 0, leafTag = 0;
 };
 // MakeAccelerator (core/api.cpp:790-831) for the trees the host builds: the tree is checked, its creation-order primitive numbers are
 // mapped to the scene's ordered indices (the inverse of prim_order), and from now on every trace of the scene takes `walk` over it
@@ -432,13 +440,14 @@ static int AttachTree(HprtScene *s, HprtScene::Walk walk, const TreeView &t) {
     if (*bad) return SetError(HPRT_E_INVALID, "malformed " + what + ": " + bad);
     if (depth > t.todoMax)
         return SetError(HPRT_E_UNSUPPORTED, what + " of depth " + std::to_string(depth) + " is deeper than the walk's todo list (" + std::to_string(t.todoMax) + ")");
-    const uint32_t off = RbspBitOffset(t.M), mask = RbspBitMask(t.M);
+    const uint32_t off = t.flagBits ? t.flagBits : RbspBitOffset(t.M), mask = t.flagBits ? (1u << t.flagBits) - 1u : RbspBitMask(t.M);
+    const uint32_t leafTag = t.flagBits ? t.leafTag : t.M;
     std::vector<uint32_t> toOrdered(nTop);
     for (uint32_t i = 0; i < nTop; ++i) toOrdered[s->topOrder[i]] = i;
     std::vector<uint2> nodes(t.nodes.size());
     for (size_t k = 0; k < nodes.size(); ++k) {
         const BspNode &nd = t.nodes[k];
-        const bool onePrim = (nd.b & mask) == t.M && (nd.b >> off) == 1u;
+        const bool onePrim = (nd.b & mask) == leafTag && (nd.b >> off) == 1u;
         nodes[k] = make_uint2(onePrim ? toOrdered[nd.a] : nd.a, nd.b);
     }
     std::vector<uint32_t> prims(t.primIndices.size());
@@ -452,7 +461,7 @@ static int AttachTree(HprtScene *s, HprtScene::Walk walk, const TreeView &t) {
         for (size_t k = 0; k < axes.size(); ++k) axes[k] = make_float4((*t.axes)[3 * k], (*t.axes)[3 * k + 1], (*t.axes)[3 * k + 2], 0.f);
         HIP_TRY(upload(s->treeAxes, axes));
     }
-    if (walk == HprtScene::Walk::RbspKd) {
+    if (walk == HprtScene::Walk::RbspKd || walk == HprtScene::Walk::BspPaperKd) {
         HIP_TRY(s->kdShare.alloc(2 * sizeof(unsigned long long)));
         HIP_TRY(hipMemset(s->kdShare.p, 0, 2 * sizeof(unsigned long long)));
     }
@@ -463,7 +472,7 @@ static int AttachTree(HprtScene *s, HprtScene::Walk walk, const TreeView &t) {
         d.depth = depth;
     };
     if (walk == HprtScene::Walk::Kd) fill(s->kd);
-    else if (walk == HprtScene::Walk::BspPaper) {
+    else if (walk == HprtScene::Walk::BspPaper || walk == HprtScene::Walk::BspPaperKd) {
         s->bsppaper = DevBspPaper{};
         fill(s->bsppaper);
         s->bsppaper.axes = s->treeAxes.as<float4>();
@@ -507,12 +516,22 @@ int hprt_scene_attach_bsppaper(HprtScene *s, const HprtBspPaper *t) try {
                                                      (uint32_t)BSPPAPER_TODO_MAX, [&](uint32_t *depth) { return CheckBspPaperTree(bt, depth); }, &bt.axes});
 } catch (...) { return hprt::HandleException(); }
 
+// The fork's "bsppaperkd" accelerator (BSPPaperKd): the general BSP tree's layout with BSPKdNode's flags, walked by the kd-aware
+// general BSP walk (device/bsppaperkd_walk.hip) with its kd counter pair
+int hprt_scene_attach_bsppaperkd(HprtScene *s, const HprtBspPaperKd *t) try {
+    if (!s || !t) return SetError(HPRT_E_INVALID, "hprt_scene_attach_bsppaperkd: null argument");
+    const BspPaperTree &bt = t->tree;
+    return AttachTree(s, HprtScene::Walk::BspPaperKd, {"bsppaperkd tree", bt.nodes, bt.primIndices, bt.nPrims, bt.bounds, 3u, nullptr,
+                                                       (uint32_t)BSPPAPERKD_TODO_MAX, [&](uint32_t *depth) { return CheckBspPaperKdTree(bt, depth); }, &bt.axes,
+                                                       BSPPAPERKD_OFF, BSPPAPERKD_LEAF});
+} catch (...) { return hprt::HandleException(); }
+
 int hprt_scene_kd_counters(HprtScene *s, uint64_t out[2]) try {
     if (!s || !out) return SetError(HPRT_E_INVALID, "hprt_scene_kd_counters: null argument");
     HIP_TRY(hipSetDevice(s->device));
     SceneCall call(s, nullptr);
     out[0] = out[1] = 0;
-    if (s->walk != HprtScene::Walk::RbspKd) return HPRT_OK;
+    if (!CountsKdShare(s)) return HPRT_OK;
     unsigned long long c[2];
     HIP_TRY(hipMemcpy(c, s->kdShare.p, sizeof(c), hipMemcpyDeviceToHost));
     out[0] = c[0]; out[1] = c[1];
@@ -597,7 +616,7 @@ static int TraceHost(HprtScene *s, bool anyHit, size_t n, const float *o, const 
     HIP_TRY(hipMemcpy(rays.a, ra.data(), 16 * n, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(rays.b, rb.data(), 16 * n, hipMemcpyHostToDevice));
     HIP_TRY(hipMemset(s->counters.p, 0, sizeof(DevCounters)));
-    if (s->walk == HprtScene::Walk::RbspKd) HIP_TRY(hipMemset(s->kdShare.p, 0, 2 * sizeof(unsigned long long)));
+    if (CountsKdShare(s)) HIP_TRY(hipMemset(s->kdShare.p, 0, 2 * sizeof(unsigned long long)));
     const bool count = counters != nullptr;
     if (!anyHit) {
         Trace(s, nullptr, false, count, nullptr, nullptr, (uint32_t)n, (uint32_t)n, rays, hits, nullptr, s->counters.as<DevCounters>(), s->workCounter.as<uint32_t>());
@@ -655,7 +674,7 @@ int RunBatch(HprtScene *s, hipStream_t st, const RenderParams &rp, const Workspa
              const BinSet &bins, uint32_t s0, uint32_t nSlots, bool count, EventTimer &ev, BatchTimers *bt, HprtRenderStats *stats,
              uint32_t *pixelStats = nullptr, const IrregularSink *irregular = nullptr) {
     uint4 *rayStats = pixelStats ? s->rayStats.as<uint4>() : nullptr;
-    uint32_t *pixelKd = pixelStats && s->walk == HprtScene::Walk::RbspKd ? s->pixelKdLocal.as<uint32_t>() : nullptr;     // the rbspkd walk's kd share
+    uint32_t *pixelKd = pixelStats && CountsKdShare(s) ? s->pixelKdLocal.as<uint32_t>() : nullptr;     // the rbspkd / bsppaperkd walk's kd share
     uint32_t *wcPath = s->workCounter.as<uint32_t>();
     LaunchGenerate(st, s->dev, rp, w.path[0], s0, nSlots, irregular);
     const uint32_t *activeQ = nullptr; uint32_t active = nSlots;
@@ -884,7 +903,7 @@ int hprt_render(HprtScene *s, const HprtRenderDesc *desc, float *d_film_xyzw, vo
         HIP_TRY(s->pixelStatsFilm.alloc(7ull * s->filmPixels * sizeof(uint64_t)));
         HIP_TRY(hipMemsetAsync(s->pixelStatsFilm.p, 0, 7ull * s->filmPixels * sizeof(uint64_t), st));
         pixelStats = s->pixelStatsLocal.as<uint32_t>();
-        if (s->walk == HprtScene::Walk::RbspKd) {
+        if (CountsKdShare(s)) {
             HIP_TRY(s->pixelKdLocal.alloc(2ull * nPix * sizeof(uint32_t)));
             HIP_TRY(hipMemsetAsync(s->pixelKdLocal.p, 0, 2ull * nPix * sizeof(uint32_t), st));
             HIP_TRY(s->pixelKdFilm.alloc(2ull * s->filmPixels * sizeof(uint64_t)));
@@ -893,7 +912,7 @@ int hprt_render(HprtScene *s, const HprtRenderDesc *desc, float *d_film_xyzw, vo
     }
     s->pixelStatsValid = false; s->pixelKdValid = false;
     HIP_TRY(hipMemsetAsync(s->counters.p, 0, sizeof(DevCounters), st));
-    if (s->walk == HprtScene::Walk::RbspKd) HIP_TRY(hipMemsetAsync(s->kdShare.p, 0, 2 * sizeof(unsigned long long), st));
+    if (CountsKdShare(s)) HIP_TRY(hipMemsetAsync(s->kdShare.p, 0, 2 * sizeof(unsigned long long), st));
 
     auto wall0 = std::chrono::high_resolution_clock::now();
     // ---- film footprint pre-pass ----
@@ -998,7 +1017,7 @@ int hprt_render(HprtScene *s, const HprtRenderDesc *desc, float *d_film_xyzw, vo
     if (pixelStats) {
         LaunchPixelStatsToFilm(st, pixelStats, rp.pixelXY, nPix, spp, f.fg.cx0, f.fg.cy0, f.W, s->pixelStatsFilm.as<unsigned long long>());
         s->pixelStatsValid = true;
-        if (s->walk == HprtScene::Walk::RbspKd) {
+        if (CountsKdShare(s)) {
             LaunchPixelKdStatsToFilm(st, s->pixelKdLocal.as<uint32_t>(), rp.pixelXY, nPix, f.fg.cx0, f.fg.cy0, f.W, s->filmPixels,
                                      s->pixelKdFilm.as<unsigned long long>());
             s->pixelKdValid = true;
@@ -1065,11 +1084,11 @@ int hprt_pixel_stats_read(HprtScene *s, uint64_t *out7, size_t n_pixels) try {
     HIP_TRY(hipMemcpy(out7, s->pixelStatsFilm.p, 7 * n_pixels * sizeof(uint64_t), hipMemcpyDeviceToHost));
     return HPRT_OK;
 } catch (...) { return hprt::HandleException(); }
-// the kd share of slots 5 / 6 of the last rbspkd render with HPRT_RENDER_PIXEL_STATS: [2][film pixels]
+// the kd share of slots 5 / 6 of the last rbspkd or bsppaperkd render with HPRT_RENDER_PIXEL_STATS: [2][film pixels]
 int hprt_pixel_kd_stats_read(HprtScene *s, uint64_t *out2, size_t n_pixels) try {
     if (!s || !out2) return SetError(HPRT_E_INVALID, "hprt_pixel_kd_stats_read: null argument");
     SceneCall call(s, nullptr);
-    if (!s->pixelKdValid) return SetError(HPRT_E_INVALID, "no per-pixel kd statistics: render an rbspkd scene with HPRT_RENDER_PIXEL_STATS first");
+    if (!s->pixelKdValid) return SetError(HPRT_E_INVALID, "no per-pixel kd statistics: render an rbspkd or bsppaperkd scene with HPRT_RENDER_PIXEL_STATS first");
     if (n_pixels != s->filmPixels) return SetError(HPRT_E_INVALID, "hprt_pixel_kd_stats_read: pixel count differs from the last render's film");
     HIP_TRY(hipSetDevice(s->device));
     HIP_TRY(hipMemcpy(out2, s->pixelKdFilm.p, 2 * n_pixels * sizeof(uint64_t), hipMemcpyDeviceToHost));

@@ -125,6 +125,42 @@ int RbspCopy(const char *fn, const RbspTree *t, void *nodes8, uint32_t *primIndi
     return HPRT_OK;
 }
 
+// ---- the general BSP handles' builds and copies (hprt_bsppaper_* and hprt_bsppaperkd_* below) ----
+// Handle HprtBspPaper with Params HprtBspPaperParams, or HprtBspPaperKd (the kd-aware cost model and node flags) with
+// HprtBspPaperKdParams; params NULL keeps p
+template <typename Handle, typename Params>
+int BuildBspPaper(size_t n, const float *lo, const float *hi, const float *tri9, const uint8_t *isTri, const Params *params,
+                  BspPaperParams p, Handle **out) {
+    constexpr bool kdAware = std::is_same<Handle, HprtBspPaperKd>::value;
+    p.kdAware = kdAware;
+    if (params) {
+        p.isectCost = params->isect_cost; p.travCost = params->trav_cost; p.emptyBonus = params->empty_bonus;
+        p.maxPrims = params->max_prims; p.maxDepth = params->max_depth; p.threads = params->threads;
+        if constexpr (kdAware) p.kdTravCost = params->kd_trav_cost;
+    }
+    const std::string what = kdAware ? "bsppaperkd" : "bsppaper";
+    constexpr uint32_t todoMax = kdAware ? BSPPAPERKD_TODO_MAX : BSPPAPER_TODO_MAX;
+    std::unique_ptr<Handle> t(new Handle());
+    const std::string err = BuildBspPaperTree(n, lo, hi, tri9, isTri, p, &t->tree);
+    if (!err.empty()) return SetError(HPRT_E_UNSUPPORTED, err);
+    if (t->tree.depth > todoMax)
+        return SetError(HPRT_E_UNSUPPORTED, what + " tree of depth " + std::to_string(t->tree.depth) + " is deeper than the device walk's todo list (" +
+                                                std::to_string((unsigned)todoMax) + " entries); lower \"maxdepth\"");
+    *out = t.release();
+    return HPRT_OK;
+}
+// nodes20: the reference's 5 words per node (BSPNode / BSPKdNode)
+int BspPaperCopy(const BspPaperTree &b, void *nodes20, uint32_t *primIndices) {
+    if (nodes20)
+        for (size_t k = 0; k < b.nodes.size(); ++k) {
+            uint32_t w[5] = {b.nodes[k].a, b.nodes[k].b, 0, 0, 0};
+            memcpy(&w[2], &b.axes[3 * k], 12);
+            memcpy((char *)nodes20 + 20 * k, w, 20);
+        }
+    if (primIndices && !b.primIndices.empty()) memcpy(primIndices, b.primIndices.data(), b.primIndices.size() * 4);
+    return HPRT_OK;
+}
+
 // Film::WriteGeneralStats (core/film.cpp:170-187) with WriteGeneralStatMatrix (:189-210): the eight matrices, each to
 // "<prefix>-<name>.txt", one image row per line; value(k, i): matrix k's value at pixel i (row-major)
 template <typename Value>
@@ -164,7 +200,7 @@ int hprt_model_parse(const char *pbrt_path, const char *const *subst, int n_subs
     std::string err;
     if (!ParsePbrtFile(pbrt_path, sm, &m->sc, &err)) { delete m; return SetError(HPRT_E_PARSE, err); }
     // a tree over object instances is not built (hprt_<accelerator>_build: HPRT_E_UNSUPPORTED): such a scene keeps the BVH and the warning
-    static const char *const kTreeAccelerators[] = {"kdtree", "rbsp", "rbspkd", "bsppaper"};
+    static const char *const kTreeAccelerators[] = {"kdtree", "rbsp", "rbspkd", "bsppaper", "bsppaperkd"};
     const std::string &acc = m->sc.opt.accelerator;
     if (std::count(std::begin(kTreeAccelerators), std::end(kTreeAccelerators), acc) && m->sc.nObjects == 0 && m->sc.instances.empty())
         m->sc.warnings.push_back("Accelerator \"" + acc + "\": the host builds the tree (hprt_" + acc + "_build) and attaches it to the scene (hprt_scene_attach_" +
@@ -361,24 +397,7 @@ int hprt_rbspkd_copy(const HprtRbspKd *t, void *nodes8, uint32_t *primIndices, f
 } catch (...) { return hprt::HandleException(); }
 void hprt_rbspkd_destroy(HprtRbspKd *t) { delete t; }
 
-// ---- general BSP tree (Accelerator "bsppaper") ----
-namespace {
-int BuildBspPaper(size_t n, const float *lo, const float *hi, const float *tri9, const uint8_t *isTri, const HprtBspPaperParams *params,
-                  BspPaperParams p, HprtBspPaper **out) {
-    if (params) {
-        p.isectCost = params->isect_cost; p.travCost = params->trav_cost; p.emptyBonus = params->empty_bonus;
-        p.maxPrims = params->max_prims; p.maxDepth = params->max_depth; p.threads = params->threads;
-    }
-    std::unique_ptr<HprtBspPaper> t(new HprtBspPaper());
-    const std::string err = BuildBspPaperTree(n, lo, hi, tri9, isTri, p, &t->tree);
-    if (!err.empty()) return SetError(HPRT_E_UNSUPPORTED, err);
-    if (t->tree.depth > BSPPAPER_TODO_MAX)
-        return SetError(HPRT_E_UNSUPPORTED, "bsppaper tree of depth " + std::to_string(t->tree.depth) + " is deeper than the device walk's todo list (" +
-                                                std::to_string((unsigned)BSPPAPER_TODO_MAX) + " entries); lower \"maxdepth\"");
-    *out = t.release();
-    return HPRT_OK;
-}
-}  // namespace
+// ---- general BSP tree (Accelerator "bsppaper"; helpers above) ----
 int hprt_bsppaper_build(const HprtModel *m, const HprtBspPaperParams *params, HprtBspPaper **out) try {
     if (!m || !out) return SetError(HPRT_E_INVALID, "hprt_bsppaper_build: null argument");
     if (m->sc.nObjects != 0 || !m->sc.instances.empty())
@@ -405,17 +424,40 @@ int hprt_bsppaper_info(const HprtBspPaper *t, uint32_t info[6]) try {
 } catch (...) { return hprt::HandleException(); }
 int hprt_bsppaper_copy(const HprtBspPaper *t, void *nodes20, uint32_t *primIndices) try {
     if (!t) return SetError(HPRT_E_INVALID, "hprt_bsppaper_copy: null argument");
-    const BspPaperTree &b = t->tree;
-    if (nodes20)
-        for (size_t k = 0; k < b.nodes.size(); ++k) {
-            uint32_t w[5] = {b.nodes[k].a, b.nodes[k].b, 0, 0, 0};
-            memcpy(&w[2], &b.axes[3 * k], 12);
-            memcpy((char *)nodes20 + 20 * k, w, 20);
-        }
-    if (primIndices && !b.primIndices.empty()) memcpy(primIndices, b.primIndices.data(), b.primIndices.size() * 4);
-    return HPRT_OK;
+    return BspPaperCopy(t->tree, nodes20, primIndices);
 } catch (...) { return hprt::HandleException(); }
 void hprt_bsppaper_destroy(HprtBspPaper *t) { delete t; }
+
+// ---- kd-aware general BSP tree (Accelerator "bsppaperkd"): the same BspPaperTree with BSPKdNode's flags, a handle type of its own ----
+int hprt_bsppaperkd_build(const HprtModel *m, const HprtBspPaperKdParams *params, HprtBspPaperKd **out) try {
+    if (!m || !out) return SetError(HPRT_E_INVALID, "hprt_bsppaperkd_build: null argument");
+    if (m->sc.nObjects != 0 || !m->sc.instances.empty())
+        return SetError(HPRT_E_UNSUPPORTED, "bsppaperkd trees over object instances are not supported (the scene keeps its BVH)");
+    std::vector<float> lo, hi, tri9;
+    std::vector<uint8_t> isTri;
+    RbspModelPrims(m, &lo, &hi, &tri9, &isTri);
+    return BuildBspPaper(lo.size() / 3, lo.data(), hi.data(), tri9.data(), isTri.data(), params, m->sc.opt.bsppaperkd, out);
+} catch (...) { return hprt::HandleException(); }
+int hprt_bsppaperkd_build_from_triangles(size_t n, const float *p9, const HprtBspPaperKdParams *params, HprtBspPaperKd **out) try {
+    if (!out || (n && !p9)) return SetError(HPRT_E_INVALID, "hprt_bsppaperkd_build_from_triangles: null argument");
+    if (n > 0x0fffffffull) return SetError(HPRT_E_UNSUPPORTED, "more than 2^28 primitives");
+    std::vector<float> lo, hi;
+    RbspTriangleBounds(n, p9, &lo, &hi);
+    std::vector<uint8_t> isTri(n, 1);
+    return BuildBspPaper(n, lo.data(), hi.data(), p9, isTri.data(), params, BspPaperParams(), out);
+} catch (...) { return hprt::HandleException(); }
+int hprt_bsppaperkd_info(const HprtBspPaperKd *t, uint32_t info[6]) try {
+    if (!t || !info) return SetError(HPRT_E_INVALID, "hprt_bsppaperkd_info: null argument");
+    const BspPaperTree &b = t->tree;
+    info[0] = (uint32_t)b.nodes.size(); info[1] = b.leaves; info[2] = b.depth; info[3] = (uint32_t)b.primIndices.size();
+    info[4] = b.axisNodes; info[5] = b.planeNodes;
+    return HPRT_OK;
+} catch (...) { return hprt::HandleException(); }
+int hprt_bsppaperkd_copy(const HprtBspPaperKd *t, void *nodes20, uint32_t *primIndices) try {
+    if (!t) return SetError(HPRT_E_INVALID, "hprt_bsppaperkd_copy: null argument");
+    return BspPaperCopy(t->tree, nodes20, primIndices);
+} catch (...) { return hprt::HandleException(); }
+void hprt_bsppaperkd_destroy(HprtBspPaperKd *t) { delete t; }
 // Diagnostics hooks (not part of include/hprt.h; tests/test_bsppaper_host.py), the bsppaper builder's views of the triangles p9
 // (9 floats each, creation order).  hprt_debug_bsppaper_planes: getBSPPaperPlanes of triangle 0, planes_out[4 k ..] = {t, axis}
 // of its k-th plane (room for 4); returns how many in *n_planes.

@@ -1,6 +1,6 @@
 // hprt device side — the body of a GenericBSP walk (Intersect / IntersectP of accelerators/genericBSP.h's trees) over the
 // reference's 8-byte node arrays: the root interval, the todo list, the leaf loop, the hit word and the counters.  The RBSP walk
-// (rbsp_walk.hip), the rbspkd walk (rbspkd_walk.hip) and the bsppaper walk (bsppaper_walk.hip) instantiate it; the kd walk (kd_walk.hip) is the same loop written out,
+// (rbsp_walk.hip), the rbspkd walk (rbspkd_walk.hip), the bsppaper walk (bsppaper_walk.hip) and the bsppaperkd walk (bsppaperkd_walk.hip) instantiate it; the kd walk (kd_walk.hip) is the same loop written out,
 // and stays so because moving it here changes its register allocation, and so its code object.  A walk passes its interior step in as `Step`:
 //   bool leaf(uint32_t flags), uint32_t high(uint32_t flags)   (aboveChild / nPrimitives),
 //   void plane(uint32_t flags, float split, vec3 ro, vec3 rd, vec3 invDir, float *tPlane, bool *belowFirst).
@@ -8,7 +8,9 @@
 // ray in rayStats.w (0 for every other walk) and per wave through `void kd_count_add(bool anyHit, uint32_t n)`.
 // NODE_AXIS (the bsppaper walk) gives the step per-node data: the step's `float4 axis(uint32_t node)` is fetched for every node and
 // passed to `void plane(float4 axis, uint32_t flags, ...)` in front of the other arguments — requested together with the node's
-// 8-byte word (1), or only once the node has turned out to be interior (2).  0: the step has no per-node data (every other walk).
+// 8-byte word (1), or only once the node has turned out to be interior (2), or only for the interior nodes for which the step's
+// `bool has_axis(uint32_t flags)` holds (3, the bsppaperkd walk: its kd nodes have none; `plane` gets zeros there).  0: the step
+// has no per-node data (every other walk).
 // (The step keeps no per-ray state: values that must survive the sphere test's call would cost scratch.)
 //
 // One ray per lane; persistent waves draw 64 rays at a time from the queue head (one atomic per wave and draw), so the kernels
@@ -109,6 +111,7 @@ __device__ __forceinline__ void bsp_walk(const DevScene &sc, const uint2 *nodes,
                     if constexpr (COUNT && KD_SHARE) kdCnt += step.kd(nd.y) ? 1u : 0u;
                     float tPlane; bool belowFirst;
                     if constexpr (NODE_AXIS == 2) axis = step.axis(node);
+                    if constexpr (NODE_AXIS == 3) { axis = make_float4(0.f, 0.f, 0.f, 0.f); if (step.has_axis(nd.y)) axis = step.axis(node); }
                     if constexpr (NODE_AXIS != 0) step.plane(axis, nd.y, __uint_as_float(nd.x), ro, rd, invDir, &tPlane, &belowFirst);
                     else step.plane(nd.y, __uint_as_float(nd.x), ro, rd, invDir, &tPlane, &belowFirst);
                     const uint32_t above = step.high(nd.y);

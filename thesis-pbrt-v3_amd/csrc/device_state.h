@@ -12,6 +12,7 @@
 #include "device/rbsp_walk.h"
 #include "device/rbspkd_walk.h"
 #include "device/bsppaper_walk.h"
+#include "device/bsppaperkd_walk.h"
 #include "hprt_internal.h"
 
 #define HIP_TRY(expr)                                                                                   \
@@ -92,11 +93,11 @@ struct HprtScene {
     // The walk every trace of the scene takes (Trace, capi_device.hip): the BVH walks until an hprt_scene_attach_* call attaches a
     // tree (AttachTree), whose walk then replaces them; attaching a tree replaces the one before.  treeNodes / treePrims back the
     // attached tree's descriptor: `kd` for the kd walk, `rbsp` for the RBSP and rbspkd walks, `bsppaper` (with its per-node axes in
-    // treeAxes) for the general BSP walk.  kdShare: the rbspkd walk's kd
-    // counter pair (DevRbspKd::kdCounters); pixelKdLocal / pixelKdFilm: its per-pixel kd share of HPRT_RENDER_PIXEL_STATS.
+    // treeAxes) for the general BSP walk and the kd-aware one (bsppaperkd).  kdShare: the rbspkd and bsppaperkd walks' kd
+    // counter pair (DevRbspKd / DevBspPaperKd::kdCounters); pixelKdLocal / pixelKdFilm: their per-pixel kd share of HPRT_RENDER_PIXEL_STATS.
     // topOrder keeps the top-level prim_order (ordered -> creation number) to map a tree's creation-order primitives; instanced:
     // no tree walk
-    enum class Walk { Bvh, Kd, Rbsp, RbspKd, BspPaper } walk = Walk::Bvh;
+    enum class Walk { Bvh, Kd, Rbsp, RbspKd, BspPaper, BspPaperKd } walk = Walk::Bvh;
     hprt::DevBuf treeNodes, treePrims, treeAxes; hprt::DevKd kd{}; hprt::DevRbsp rbsp{}; hprt::DevBspPaper bsppaper{};
     hprt::DevBuf kdShare, pixelKdLocal, pixelKdFilm; bool pixelKdValid = false;
     std::vector<uint32_t> topOrder; bool instanced = false;

@@ -18,6 +18,7 @@ struct HprtKdTree { hprt::KdTree tree; };
 struct HprtRbsp { hprt::RbspTree tree; };
 struct HprtRbspKd { hprt::RbspTree tree; };     // built with RbspParams::kdAware
 struct HprtBspPaper { hprt::BspPaperTree tree; };
+struct HprtBspPaperKd { hprt::BspPaperTree tree; };     // built with BspPaperParams::kdAware
 
 namespace hprt {
 extern thread_local std::string g_lastError;

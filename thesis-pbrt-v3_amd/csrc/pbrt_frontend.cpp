@@ -636,6 +636,8 @@ struct Frontend {
         if (sc->opt.accelerator == "rbspkd") { rbspParams(o.rbspkd); o.rbspkd.kdTravCost = accelParams.oneInt("kdtraversalcost", o.rbspkd.kdTravCost); }
         // CreateBSPPaperTreeAccelerator (accelerators/bspPaper.cpp:308-319): the tree parameters; its "nbDirections" only feeds a statistic
         if (sc->opt.accelerator == "bsppaper") treeParams(o.bsppaper);
+        // CreateBSPPaperKdTreeAccelerator (accelerators/bspPaperKd.cpp:341-353): the same plus "kdtraversalcost"
+        if (sc->opt.accelerator == "bsppaperkd") { treeParams(o.bsppaperkd); o.bsppaperkd.kdTravCost = accelParams.oneInt("kdtraversalcost", o.bsppaperkd.kdTravCost); }
         reportUnused(filmParams, "Film", {"diagonal"});
         reportUnused(filterParams, "PixelFilter");
         reportUnused(cameraParams, "Camera");

@@ -89,10 +89,10 @@ struct RenderOptions {
     int32_t spp = 16, samplePixelCenter = 0;
     int32_t maxDepth = 5; float rrThreshold = 1.f; int32_t lightStrategy = kSpatial;
     int32_t maxNodePrims = 4, isectCost = 8, travCost = 1;
-    // Accelerator "kdtree" / "rbsp" / "rbspkd" / "bsppaper": the parameters of CreateKdTreeAccelerator (accelerators/kdtreeaccel.cpp:523-545),
+    // Accelerator "kdtree" / "rbsp" / "rbspkd" / "bsppaper" / "bsppaperkd": the parameters of CreateKdTreeAccelerator (accelerators/kdtreeaccel.cpp:523-545),
     // CreateRBSPTreeAccelerator (accelerators/rbsp.cpp:549-571), CreateRBSPKdTreeAccelerator (accelerators/rbspKd.cpp:640-665) and
     // CreateBSPPaperTreeAccelerator (accelerators/bspPaper.cpp:308-319), each read only for its own accelerator; host side only (not baked)
-    KdParams kd; RbspParams rbsp, rbspkd; BspPaperParams bsppaper;
+    KdParams kd; RbspParams rbsp, rbspkd; BspPaperParams bsppaper, bsppaperkd;
     std::string filename = "pbrt.exr", accelerator = "bvh", integrator = "path", sampler = "halton";
 };
 struct SceneModel {
