@@ -80,7 +80,7 @@ int main(int argc, char **argv) {
     // one scene per GPU; rank r renders tiles r, r + N, ...
     std::vector<HprtScene *> scenes((size_t)gpus, nullptr);
     for (int g = 0; g < gpus; ++g) TRY(hprt_scene_create_from_model(model, bvh, g, &scenes[(size_t)g]));
-    // Accelerator "kdtree", "rbsp", "rbspkd", "bsppaper" or "bsppaperkd" (MakeAccelerator, core/api.cpp:790-831): the tree is built on the host from the
+    // Accelerator "kdtree", "rbsp", "rbspkd", "bsppaper", "bsppaperkd" or a node-based BSP tree (MakeAccelerator, core/api.cpp:790-831): the tree is built on the host from the
     // scene's Accelerator line and every scene walks it
     char accel[64] = "";
     TRY(hprt_model_accelerator(model, accel, sizeof(accel)));
@@ -91,6 +91,12 @@ int main(int argc, char **argv) {
     if (acc == "rbspkd") arc = AttachTree<HprtRbspKd>(acc, [&](HprtRbspKd **t) { return hprt_rbspkd_build(model, nullptr, t); }, hprt_scene_attach_rbspkd, hprt_rbspkd_destroy, scenes, true);
     if (acc == "bsppaper") arc = AttachTree<HprtBspPaper>(acc, [&](HprtBspPaper **t) { return hprt_bsppaper_build(model, nullptr, t); }, hprt_scene_attach_bsppaper, hprt_bsppaper_destroy, scenes, true);
     if (acc == "bsppaperkd") arc = AttachTree<HprtBspPaperKd>(acc, [&](HprtBspPaperKd **t) { return hprt_bsppaperkd_build(model, nullptr, t); }, hprt_scene_attach_bsppaperkd, hprt_bsppaperkd_destroy, scenes, true);
+    // the node-based BSP trees ("bspcluster", "bsprandomwithkd", "bsparbitraryfastkd", ...: Create...TreeAccelerator of
+    // accelerators/bsp{Arbitrary,Cluster,Random}{,WithKd,FastKd}.cpp): a fastkd tree is a bsppaperkd tree, the others bsppaper trees
+    const bool nodeBased = acc.rfind("bsparbitrary", 0) == 0 || acc.rfind("bspcluster", 0) == 0 || acc.rfind("bsprandom", 0) == 0;
+    const bool fastKd = acc.size() > 6 && acc.compare(acc.size() - 6, 6, "fastkd") == 0;
+    if (nodeBased && fastKd) arc = AttachTree<HprtBspPaperKd>(acc, [&](HprtBspPaperKd **t) { return hprt_bspnodekd_build(model, nullptr, t); }, hprt_scene_attach_bsppaperkd, hprt_bsppaperkd_destroy, scenes, true);
+    if (nodeBased && !fastKd) arc = AttachTree<HprtBspPaper>(acc, [&](HprtBspPaper **t) { return hprt_bspnode_build(model, nullptr, t); }, hprt_scene_attach_bsppaper, hprt_bsppaper_destroy, scenes, true);
     if (arc) return 1;
     // one host thread per GPU (the renders are independent; errors are thread-local in the library, so each thread keeps its own)
     std::vector<HprtRenderStats> stats((size_t)gpus);

@@ -285,6 +285,63 @@ int hprt_bsppaperkd_copy(const HprtBspPaperKd *t, void *nodes20, uint32_t *prim_
 void hprt_bsppaperkd_destroy(HprtBspPaperKd *t);
 
 /* ------------------------------------------------------------------------ */
+/* Node-based BSP trees (Accelerator "bsparbitrary", "bspcluster",          */
+/* "bsprandom", and each with "withkd" or "fastkd" appended).  Stand in for */
+/* BSPNodeBased::buildTree (accelerators/bspNodeBased.cpp:27-223),          */
+/* BSPNodeBasedWithKd::buildTree (bspNodeBasedWithKd.cpp) and               */
+/* BSPNodeBasedFastKd::buildTree (bspNodeBasedFastKd.cpp:28-330): at every  */
+/* node K split directions are chosen — the PositiveX normals of K drawn    */
+/* primitives (chooseArbitraryNormals, randomNormals.h:13-26), the k-means  */
+/* of the node's normals (calculateClusterMeans, clustering.h:53-112) or K  */
+/* uniform directions (chooseRandomDirections, randomNormals.h:28-46) — and */
+/* each is swept like a kd axis over a k-DOP cost model.  The withkd form   */
+/* puts the three axes in front of K - 3 chosen directions; the fastkd form */
+/* costs the axes kd_trav_cost + C_isect and the chosen directions          */
+/* 0.1 * isect_cost * (N - 1) + kd_trav_cost + C_isect, with a second       */
+/* minimum trav_cost + C_isect over the chosen directions.  No handles of   */
+/* their own: a plain or withkd tree is the reference's BSP over BSPNode,   */
+/* structurally a bsppaper tree (HprtBspPaper); a fastkd tree is its BSPKd  */
+/* over BSPKdNode, structurally a bsppaperkd tree (HprtBspPaperKd).  Info,  */
+/* copy, destroy, attach, counters and pixel maps are those handles'.       */
+/* THE ONE DELIBERATE DEPARTURE FROM THE REFERENCE: it seeds std::mt19937    */
+/* from std::random_device (bspNodeBased.cpp:28-29), so no two of its       */
+/* builds agree; here the engine takes `seed`, default                      */
+/* HPRT_BSPNODE_DEFAULT_SEED, so a scene file renders the same tree every   */
+/* time.  Everything else is drawn from the engine as the reference draws.  */
+/* ------------------------------------------------------------------------ */
+#define HPRT_BSPNODE_ARBITRARY 0
+#define HPRT_BSPNODE_CLUSTER 1
+#define HPRT_BSPNODE_RANDOM 2
+#define HPRT_BSPNODE_PLAIN 0
+#define HPRT_BSPNODE_WITHKD 1
+#define HPRT_BSPNODE_FASTKD 2
+#define HPRT_BSPNODE_DEFAULT_SEED 5489u   /* std::mt19937::default_seed */
+typedef struct HprtBspNodeParams {
+    int chooser;        /* HPRT_BSPNODE_ARBITRARY / _CLUSTER / _RANDOM: the accelerator's name */
+    int form;           /* HPRT_BSPNODE_PLAIN / _WITHKD / _FASTKD: the name's suffix */
+    int n_directions;   /* "nbDirections" (K), default 3; withkd and fastkd need K >= 3 */
+    uint32_t seed;      /* "seed", default HPRT_BSPNODE_DEFAULT_SEED */
+    int isect_cost;     /* "intersectcost", default 80 */
+    int trav_cost;      /* "traversalcost", default 5 */
+    int kd_trav_cost;   /* "kdtraversalcost", default 1 (fastkd only) */
+    float empty_bonus;  /* "emptybonus", default 0 */
+    int max_prims;      /* "maxprims", default 1 */
+    int max_depth;      /* "maxdepth", default -1 = round(2 + 1.6 Log2Int(N)) */
+    int threads;        /* builder threads (0: OMP_NUM_THREADS, else 16; at most 16); the tree does not depend on it */
+} HprtBspNodeParams;
+/* Create{BSPArbitrary,BSPCluster,BSPRandom}[WithKd]TreeAccelerator (accelerators/bspCluster.cpp:36-48 and siblings): the plain and
+ * withkd forms.  params NULL takes chooser, form and parameters from the scene's Accelerator line.  HPRT_E_UNSUPPORTED where the
+ * reference's build is undefined — K < 3 for withkd (its K - 3 wraps), a drawn primitive index equal to the node's primitive
+ * count — and for instanced models and trees deeper than HPRT_BSPPAPER_MAX_DEPTH. */
+int hprt_bspnode_build(const HprtModel *m, const HprtBspNodeParams *params, HprtBspPaper **out);
+int hprt_bspnode_build_from_triangles(size_t n_tris, const float *p9, const HprtBspNodeParams *params, HprtBspPaper **out);
+/* Create{BSPArbitrary,BSPCluster,BSPRandom}FastKdTreeAccelerator (accelerators/bspClusterFastKd.cpp:37-50 and siblings): the fastkd
+ * form.  As above; also HPRT_E_UNSUPPORTED where only the second minimum is set (the reference then reads edges[-1]) and for trees
+ * deeper than HPRT_BSPPAPERKD_MAX_DEPTH. */
+int hprt_bspnodekd_build(const HprtModel *m, const HprtBspNodeParams *params, HprtBspPaperKd **out);
+int hprt_bspnodekd_build_from_triangles(size_t n_tris, const float *p9, const HprtBspNodeParams *params, HprtBspPaperKd **out);
+
+/* ------------------------------------------------------------------------ */
 /* Device scene.  Upload step that follows the BVH build: stands in for the  */
 /* `primitives`/`nodes` members BVHAccel keeps (accelerators/bvh.h:69-79) and */
 /* the Scene object (core/scene.h:50-80).  The library copies everything to   */

@@ -10,6 +10,8 @@ accelerates:
     RbspKd  <- CreateRBSPKdTreeAccelerator / buildTree (accelerators/rbspKd.cpp:194-488,640-665)
     BspPaper <- CreateBSPPaperTreeAccelerator / buildTree (accelerators/bspPaper.cpp:34-319)
     BspPaperKd <- CreateBSPPaperKdTreeAccelerator / buildTree (accelerators/bspPaperKd.cpp:34-353)
+    BspNode, BspNodeKd <- Create{BSPArbitrary,BSPCluster,BSPRandom}{,WithKd,FastKd}TreeAccelerator / buildTree
+               (accelerators/bspNodeBased.cpp:27-223, bspNodeBasedWithKd.cpp, bspNodeBasedFastKd.cpp:28-330)
     Scene   <- Scene + BVHAccel::Intersect/IntersectP (accelerators/bvh.cpp:354-437)
                and SamplerIntegrator::Render with PathIntegrator::Li
                (core/integrator.cpp:230-360, integrators/path.cpp:64-204)
@@ -284,6 +286,10 @@ def _load():
         "hprt_bsppaperkd_copy": (C.c_int, [vp, vp, vp]),
         "hprt_bsppaperkd_destroy": (None, [vp]),
         "hprt_scene_attach_bsppaperkd": (C.c_int, [vp, vp]),
+        "hprt_bspnode_build": (C.c_int, [vp, vp, P(vp)]),
+        "hprt_bspnode_build_from_triangles": (C.c_int, [sz, vp, vp, P(vp)]),
+        "hprt_bspnodekd_build": (C.c_int, [vp, vp, P(vp)]),
+        "hprt_bspnodekd_build_from_triangles": (C.c_int, [sz, vp, vp, P(vp)]),
         "hprt_scene_kd_counters": (C.c_int, [vp, vp]),
         "hprt_pixel_kd_stats_read": (C.c_int, [vp, vp, sz]),
         "hprt_write_pixel_stats_rbspkd": (C.c_int, [cp, vp, vp, C.c_int, C.c_int]),
@@ -559,6 +565,91 @@ class BspPaperKd(_Tree):
         idx = np.zeros(inf["prim_refs"], np.uint32)
         self._call("copy", _ptr(nodes), _ptr(idx))
         return nodes, idx
+
+
+class BspNodeParams(C.Structure):
+    """HprtBspNodeParams: chooser and form (the accelerator's name), K, the seed, the parameters of the nine
+    Create...TreeAccelerator functions and the builder's thread count."""
+    _fields_ = [("chooser", C.c_int), ("form", C.c_int), ("n_directions", C.c_int), ("seed", C.c_uint32), ("isect_cost", C.c_int), ("trav_cost", C.c_int),
+                ("kd_trav_cost", C.c_int), ("empty_bonus", C.c_float), ("max_prims", C.c_int), ("max_depth", C.c_int), ("threads", C.c_int)]
+
+
+BSPNODE_CHOOSERS = ("arbitrary", "cluster", "random")      # HPRT_BSPNODE_ARBITRARY / _CLUSTER / _RANDOM
+BSPNODE_FORMS = ("", "withkd", "fastkd")                   # HPRT_BSPNODE_PLAIN / _WITHKD / _FASTKD
+BSPNODE_DEFAULT_SEED = 5489                                # HPRT_BSPNODE_DEFAULT_SEED: std::mt19937's own default
+BSPNODE_ACCELERATORS = tuple("bsp" + c + f for c in BSPNODE_CHOOSERS for f in BSPNODE_FORMS)
+
+
+def _bspnode_params(accelerator, fastkd, n_directions, seed, isect_cost, trav_cost, kd_trav_cost, empty_bonus, max_prims, max_depth, threads):
+    """HprtBspNodeParams of an accelerator name ("bspcluster", "bsprandomwithkd", ...); fastkd: the form the builder takes"""
+    if accelerator not in BSPNODE_ACCELERATORS:
+        raise ValueError("%r is no node-based BSP accelerator (%s)" % (accelerator, ", ".join(BSPNODE_ACCELERATORS)))
+    k = BSPNODE_ACCELERATORS.index(accelerator)
+    if (k % 3 == 2) != fastkd:
+        raise ValueError("%r is built by %s" % (accelerator, "BspNode" if fastkd else "BspNodeKd"))
+    return BspNodeParams(k // 3, k % 3, n_directions, seed, isect_cost, trav_cost, kd_trav_cost, empty_bonus, max_prims, max_depth, threads)
+
+
+class BspNode(BspPaper):
+    """Node-based BSP tree, plain or withkd form (host): Create{BSPArbitrary,BSPCluster,BSPRandom}[WithKd]TreeAccelerator(prims,
+    params) — the reference's BSP over BSPNode, so a BspPaper in all but its builder: info(), arrays() and Scene.attach_bsppaper
+    take it unchanged.  BspNode(model) takes accelerator and parameters from the scene's Accelerator line; given `accelerator`
+    ("bspcluster", "bsprandomwithkd", ...), the keyword parameters replace it.  `seed` seeds the direction chooser's std::mt19937
+    (the reference seeds from std::random_device): the same seed gives the same tree."""
+
+    def __init__(self, model=None, accelerator=None, handle=None, n_directions=3, seed=BSPNODE_DEFAULT_SEED, isect_cost=80, trav_cost=5,
+                 empty_bonus=0.0, max_prims=1, max_depth=-1, threads=0):
+        if handle is None:
+            handle = C.c_void_p()
+            prm = None if accelerator is None else C.byref(_bspnode_params(accelerator, False, n_directions, seed, isect_cost, trav_cost, 1, empty_bonus,
+                                                                          max_prims, max_depth, threads))
+            _check(lib.hprt_bspnode_build(model._h, prm, C.byref(handle)))
+        self._h = handle
+
+    @staticmethod
+    def from_triangles(p9, accelerator, n_directions=3, seed=BSPNODE_DEFAULT_SEED, isect_cost=80, trav_cost=5, empty_bonus=0.0, max_prims=1,
+                       max_depth=-1, threads=0):
+        """p9: [n, 9] (or [n, 3, 3]) float32 world-space triangle vertices in creation order."""
+        p9 = np.ascontiguousarray(p9, np.float32).reshape(-1, 9)
+        h = C.c_void_p()
+        prm = _bspnode_params(accelerator, False, n_directions, seed, isect_cost, trav_cost, 1, empty_bonus, max_prims, max_depth, threads)
+        _check(lib.hprt_bspnode_build_from_triangles(p9.shape[0], _ptr(p9), C.byref(prm), C.byref(h)))
+        return BspNode(handle=h)
+
+
+class BspNodeKd(BspPaperKd):
+    """Node-based BSP tree, fastkd form (host): Create{BSPArbitrary,BSPCluster,BSPRandom}FastKdTreeAccelerator(prims, params) — the
+    reference's BSPKd over BSPKdNode, so a BspPaperKd in all but its builder: Scene.attach_bsppaperkd takes it unchanged.
+    Arguments as BspNode's, plus kd_trav_cost."""
+
+    def __init__(self, model=None, accelerator=None, handle=None, n_directions=3, seed=BSPNODE_DEFAULT_SEED, isect_cost=80, trav_cost=5,
+                 kd_trav_cost=1, empty_bonus=0.0, max_prims=1, max_depth=-1, threads=0):
+        if handle is None:
+            handle = C.c_void_p()
+            prm = None if accelerator is None else C.byref(_bspnode_params(accelerator, True, n_directions, seed, isect_cost, trav_cost, kd_trav_cost,
+                                                                          empty_bonus, max_prims, max_depth, threads))
+            _check(lib.hprt_bspnodekd_build(model._h, prm, C.byref(handle)))
+        self._h = handle
+
+    @staticmethod
+    def from_triangles(p9, accelerator, n_directions=3, seed=BSPNODE_DEFAULT_SEED, isect_cost=80, trav_cost=5, kd_trav_cost=1, empty_bonus=0.0,
+                       max_prims=1, max_depth=-1, threads=0):
+        """p9: [n, 9] (or [n, 3, 3]) float32 world-space triangle vertices in creation order."""
+        p9 = np.ascontiguousarray(p9, np.float32).reshape(-1, 9)
+        h = C.c_void_p()
+        prm = _bspnode_params(accelerator, True, n_directions, seed, isect_cost, trav_cost, kd_trav_cost, empty_bonus, max_prims, max_depth, threads)
+        _check(lib.hprt_bspnodekd_build_from_triangles(p9.shape[0], _ptr(p9), C.byref(prm), C.byref(h)))
+        return BspNodeKd(handle=h)
+
+
+def bspnode_tree(model, accelerator=None, **kw):
+    """The node-based BSP tree of `accelerator` (default: the scene's Accelerator line) and the Scene method that attaches it:
+    (BspNodeKd, "attach_bsppaperkd") for the fastkd forms, (BspNode, "attach_bsppaper") for the others."""
+    name = accelerator if accelerator is not None else model.accelerator
+    fastkd = name.endswith("fastkd")
+    if not fastkd:
+        kw.pop("kd_trav_cost", None)
+    return (BspNodeKd if fastkd else BspNode)(model, accelerator, **kw), ("attach_bsppaperkd" if fastkd else "attach_bsppaper")
 
 
 class Scene:

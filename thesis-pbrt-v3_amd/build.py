@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "lib")
-HOST_SRCS = ["pbrt_frontend.cpp", "loop_subdiv.cpp", "scene_io.cpp", "texture_io.cpp", "bvh_builder.cpp", "kdtree_builder.cpp", "rbsp_builder.cpp", "bsppaper_builder.cpp", "wide_bvh.cpp", "halton_tables.cpp", "capi_host.cpp"]
+HOST_SRCS = ["pbrt_frontend.cpp", "loop_subdiv.cpp", "scene_io.cpp", "texture_io.cpp", "bvh_builder.cpp", "kdtree_builder.cpp", "rbsp_builder.cpp", "bsppaper_builder.cpp", "bspnode_builder.cpp", "wide_bvh.cpp", "halton_tables.cpp", "capi_host.cpp"]
 # host code built by hipcc without an offload target (no code object): the float operations of the scene layout keep the code
 # generator they had when they sat in capi_device.hip
 HIPCC_HOST_SRCS = ["scene_layout.cpp"]

@@ -14,6 +14,7 @@
 #include <string>
 #include <type_traits>
 #include "../../include/hprt.h"
+#include "bspnode_builder.h"
 #include "bvh_builder.h"
 #include "halton_tables.h"
 #include "hprt_internal.h"
@@ -161,6 +162,53 @@ int BspPaperCopy(const BspPaperTree &b, void *nodes20, uint32_t *primIndices) {
     return HPRT_OK;
 }
 
+// ---- the node-based BSP trees' builds (hprt_bspnode_* and hprt_bspnodekd_* below): Handle HprtBspPaper for the plain and withkd
+// forms, HprtBspPaperKd for the fastkd form; params NULL keeps p (the scene's Accelerator line)
+template <typename Handle>
+int BuildBspNode(const char *fn, size_t n, const float *lo, const float *hi, const float *tri9, const uint8_t *isTri, const HprtBspNodeParams *params,
+                 BspNodeParams p, Handle **out) {
+    constexpr bool fastKd = std::is_same<Handle, HprtBspPaperKd>::value;
+    if (params) {
+        p.chooser = params->chooser; p.form = params->form; p.nDirections = params->n_directions; p.seed = params->seed;
+        p.isectCost = params->isect_cost; p.travCost = params->trav_cost; p.kdTravCost = params->kd_trav_cost; p.emptyBonus = params->empty_bonus;
+        p.maxPrims = params->max_prims; p.maxDepth = params->max_depth; p.threads = params->threads;
+    }
+    if ((p.form == BSPNODE_FASTKD) != fastKd)
+        return SetError(HPRT_E_INVALID, std::string(fn) + (fastKd ? ": takes the fastkd form only (the plain and withkd forms are hprt_bspnode_build's)"
+                                                                  : ": takes the plain and withkd forms only (the fastkd form is hprt_bspnodekd_build's)"));
+    constexpr uint32_t todoMax = fastKd ? (uint32_t)BSPPAPERKD_TODO_MAX : (uint32_t)BSPPAPER_TODO_MAX;
+    std::unique_ptr<Handle> t(new Handle());
+    const std::string err = BuildBspNodeTree(n, lo, hi, tri9, isTri, p, &t->tree);
+    if (!err.empty()) return SetError(HPRT_E_UNSUPPORTED, err);
+    if (t->tree.depth > todoMax)
+        return SetError(HPRT_E_UNSUPPORTED, "node-based BSP tree of depth " + std::to_string(t->tree.depth) + " is deeper than the device walk's todo list (" +
+                                                std::to_string((unsigned)todoMax) + " entries); lower \"maxdepth\"");
+    *out = t.release();
+    return HPRT_OK;
+}
+template <typename Handle>
+int BuildBspNodeFromModel(const char *fn, const HprtModel *m, const HprtBspNodeParams *params, Handle **out) {
+    if (!m || !out) return SetError(HPRT_E_INVALID, std::string(fn) + ": null argument");
+    if (m->sc.nObjects != 0 || !m->sc.instances.empty())
+        return SetError(HPRT_E_UNSUPPORTED, "node-based BSP trees over object instances are not supported (the scene keeps its BVH)");
+    BspNodeParams p = m->sc.opt.bspnode;
+    if (!params && !BspNodeAccelerator(m->sc.opt.accelerator, &p.chooser, &p.form))
+        return SetError(HPRT_E_INVALID, std::string(fn) + ": the scene's Accelerator \"" + m->sc.opt.accelerator + "\" is no node-based BSP tree; pass params");
+    std::vector<float> lo, hi, tri9;
+    std::vector<uint8_t> isTri;
+    RbspModelPrims(m, &lo, &hi, &tri9, &isTri);
+    return BuildBspNode(fn, lo.size() / 3, lo.data(), hi.data(), tri9.data(), isTri.data(), params, p, out);
+}
+template <typename Handle>
+int BuildBspNodeFromTriangles(const char *fn, size_t n, const float *p9, const HprtBspNodeParams *params, Handle **out) {
+    if (!out || !params || (n && !p9)) return SetError(HPRT_E_INVALID, std::string(fn) + ": null argument");
+    if (n > 0x0fffffffull) return SetError(HPRT_E_UNSUPPORTED, "more than 2^28 primitives");
+    std::vector<float> lo, hi;
+    RbspTriangleBounds(n, p9, &lo, &hi);
+    std::vector<uint8_t> isTri(n, 1);
+    return BuildBspNode(fn, n, lo.data(), hi.data(), p9, isTri.data(), params, BspNodeParams(), out);
+}
+
 // Film::WriteGeneralStats (core/film.cpp:170-187) with WriteGeneralStatMatrix (:189-210): the eight matrices, each to
 // "<prefix>-<name>.txt", one image row per line; value(k, i): matrix k's value at pixel i (row-major)
 template <typename Value>
@@ -201,8 +249,14 @@ int hprt_model_parse(const char *pbrt_path, const char *const *subst, int n_subs
     if (!ParsePbrtFile(pbrt_path, sm, &m->sc, &err)) { delete m; return SetError(HPRT_E_PARSE, err); }
     // a tree over object instances is not built (hprt_<accelerator>_build: HPRT_E_UNSUPPORTED): such a scene keeps the BVH and the warning
     static const char *const kTreeAccelerators[] = {"kdtree", "rbsp", "rbspkd", "bsppaper", "bsppaperkd"};
+    int nodeChooser, nodeForm;     // the node-based BSP trees: hprt_bspnode[kd]_build, attached as bsppaper / bsppaperkd trees
     const std::string &acc = m->sc.opt.accelerator;
-    if (std::count(std::begin(kTreeAccelerators), std::end(kTreeAccelerators), acc) && m->sc.nObjects == 0 && m->sc.instances.empty())
+    const bool plainScene = m->sc.nObjects == 0 && m->sc.instances.empty();
+    if (BspNodeAccelerator(acc, &nodeChooser, &nodeForm) && plainScene) {
+        const std::string as = nodeForm == BSPNODE_FASTKD ? "bsppaperkd" : "bsppaper";
+        m->sc.warnings.push_back("Accelerator \"" + acc + "\": the host builds the tree (hprt_bspnode" + (nodeForm == BSPNODE_FASTKD ? "kd" : "") +
+                                 "_build) and attaches it to the scene (hprt_scene_attach_" + as + "); a scene without it walks a BVH");
+    } else if (std::count(std::begin(kTreeAccelerators), std::end(kTreeAccelerators), acc) && plainScene)
         m->sc.warnings.push_back("Accelerator \"" + acc + "\": the host builds the tree (hprt_" + acc + "_build) and attaches it to the scene (hprt_scene_attach_" +
                                  acc + "); a scene without it walks a BVH");
     else if (acc != "bvh") m->sc.warnings.push_back("Accelerator \"" + acc + "\" is outside the hot-path scope; \"bvh\" used");
@@ -458,6 +512,49 @@ int hprt_bsppaperkd_copy(const HprtBspPaperKd *t, void *nodes20, uint32_t *primI
     return BspPaperCopy(t->tree, nodes20, primIndices);
 } catch (...) { return hprt::HandleException(); }
 void hprt_bsppaperkd_destroy(HprtBspPaperKd *t) { delete t; }
+// ---- node-based BSP trees (Accelerator "bsparbitrary", "bspcluster", "bsprandom" and their withkd / fastkd forms; helpers above):
+// no handles of their own — a tree over BSPNode is an HprtBspPaper, a tree over BSPKdNode an HprtBspPaperKd ----
+int hprt_bspnode_build(const HprtModel *m, const HprtBspNodeParams *params, HprtBspPaper **out) try {
+    return BuildBspNodeFromModel("hprt_bspnode_build", m, params, out);
+} catch (...) { return hprt::HandleException(); }
+int hprt_bspnode_build_from_triangles(size_t n, const float *p9, const HprtBspNodeParams *params, HprtBspPaper **out) try {
+    return BuildBspNodeFromTriangles("hprt_bspnode_build_from_triangles", n, p9, params, out);
+} catch (...) { return hprt::HandleException(); }
+int hprt_bspnodekd_build(const HprtModel *m, const HprtBspNodeParams *params, HprtBspPaperKd **out) try {
+    return BuildBspNodeFromModel("hprt_bspnodekd_build", m, params, out);
+} catch (...) { return hprt::HandleException(); }
+int hprt_bspnodekd_build_from_triangles(size_t n, const float *p9, const HprtBspNodeParams *params, HprtBspPaperKd **out) try {
+    return BuildBspNodeFromTriangles("hprt_bspnodekd_build_from_triangles", n, p9, params, out);
+} catch (...) { return hprt::HandleException(); }
+// Diagnostics hooks (not part of include/hprt.h; tests/test_bspnode_host.py).  hprt_debug_bspnode_choose: `draws` calls of a
+// direction chooser over the triangles p9 from one engine seeded with `seed`; counts[k] = directions of call k, dirs their
+// components in order (room for draws * max(K, n) * 3 floats).  hprt_debug_bspnode_check: the structural check of a tree given as
+// 20-byte nodes (kd_aware: BSPKdNode's flags), its depth in *depth; returns HPRT_E_UNSUPPORTED past the walks' 64 levels.
+__attribute__((visibility("default"))) int hprt_debug_bspnode_choose(int chooser, uint32_t K, uint32_t seed, size_t n, const float *p9, uint32_t draws,
+                                                                      uint32_t *counts, float *dirs) try {
+    std::vector<uint32_t> c; std::vector<float> d;
+    const std::string err = BspNodeChoose(chooser, K, seed, n, p9, draws, &c, &d);
+    if (!err.empty()) return SetError(HPRT_E_UNSUPPORTED, err);
+    std::copy(c.begin(), c.end(), counts);
+    std::copy(d.begin(), d.end(), dirs);
+    return HPRT_OK;
+} catch (...) { return hprt::HandleException(); }
+__attribute__((visibility("default"))) int hprt_debug_bspnode_check(size_t n_nodes, const uint32_t *nodes20, size_t n_idx, const uint32_t *idx, uint32_t n_prims,
+                                                                     int kd_aware, uint32_t *depth) try {
+    BspPaperTree t;
+    t.kdAware = kd_aware != 0; t.nPrims = n_prims;
+    for (size_t k = 0; k < n_nodes; ++k) {
+        t.nodes.push_back(BspNode{nodes20[5 * k], nodes20[5 * k + 1]});
+        float a[3]; memcpy(a, &nodes20[5 * k + 2], 12);
+        t.axes.insert(t.axes.end(), a, a + 3);
+    }
+    t.primIndices.assign(idx, idx + n_idx);
+    const char *bad = t.kdAware ? CheckBspPaperKdTree(t, depth) : CheckBspPaperTree(t, depth);
+    if (*bad) return SetError(HPRT_E_INVALID, std::string("malformed tree: ") + bad);
+    if (*depth > (t.kdAware ? (uint32_t)BSPPAPERKD_TODO_MAX : (uint32_t)BSPPAPER_TODO_MAX))
+        return SetError(HPRT_E_UNSUPPORTED, "node-based BSP tree of depth " + std::to_string(*depth) + " is deeper than the device walk's todo list");
+    return HPRT_OK;
+} catch (...) { return hprt::HandleException(); }
 // Diagnostics hooks (not part of include/hprt.h; tests/test_bsppaper_host.py), the bsppaper builder's views of the triangles p9
 // (9 floats each, creation order).  hprt_debug_bsppaper_planes: getBSPPaperPlanes of triangle 0, planes_out[4 k ..] = {t, axis}
 // of its k-th plane (room for 4); returns how many in *n_planes.

@@ -638,6 +638,16 @@ struct Frontend {
         if (sc->opt.accelerator == "bsppaper") treeParams(o.bsppaper);
         // CreateBSPPaperKdTreeAccelerator (accelerators/bspPaperKd.cpp:341-353): the same plus "kdtraversalcost"
         if (sc->opt.accelerator == "bsppaperkd") { treeParams(o.bsppaperkd); o.bsppaperkd.kdTravCost = accelParams.oneInt("kdtraversalcost", o.bsppaperkd.kdTravCost); }
+        // The node-based BSP trees, Create{BSPArbitrary,BSPCluster,BSPRandom}{,WithKd,FastKd}TreeAccelerator (accelerators/bspCluster.cpp:36-48,
+        // bspClusterFastKd.cpp:37-50 and their siblings): the tree parameters and "nbDirections" (K), the fastkd forms "kdtraversalcost"
+        // as well; "seed" is this library's (the reference seeds from std::random_device) and is read for these nine names only
+        int nodeChooser, nodeForm;
+        if (BspNodeAccelerator(sc->opt.accelerator, &nodeChooser, &nodeForm)) {
+            treeParams(o.bspnode);
+            o.bspnode.nDirections = accelParams.oneInt("nbDirections", o.bspnode.nDirections);
+            o.bspnode.seed = (uint32_t)accelParams.oneInt("seed", (int)o.bspnode.seed);
+            if (nodeForm == BSPNODE_FASTKD) o.bspnode.kdTravCost = accelParams.oneInt("kdtraversalcost", o.bspnode.kdTravCost);
+        }
         reportUnused(filmParams, "Film", {"diagonal"});
         reportUnused(filterParams, "PixelFilter");
         reportUnused(cameraParams, "Camera");

@@ -11,6 +11,7 @@
 #include "kdtree_builder.h"
 #include "rbsp_builder.h"
 #include "bsppaper_builder.h"
+#include "bspnode_builder.h"
 
 namespace hprt {
 
@@ -93,6 +94,10 @@ struct RenderOptions {
     // CreateRBSPTreeAccelerator (accelerators/rbsp.cpp:549-571), CreateRBSPKdTreeAccelerator (accelerators/rbspKd.cpp:640-665) and
     // CreateBSPPaperTreeAccelerator (accelerators/bspPaper.cpp:308-319), each read only for its own accelerator; host side only (not baked)
     KdParams kd; RbspParams rbsp, rbspkd; BspPaperParams bsppaper, bsppaperkd;
+    // Accelerator "bsparbitrary" / "bspcluster" / "bsprandom" and their "withkd" / "fastkd" forms: the parameters of the nine
+    // Create...TreeAccelerator functions (accelerators/bsp{Arbitrary,Cluster,Random}{,WithKd,FastKd}.cpp) plus "seed"; chooser and form
+    // come from the accelerator's name (BspNodeAccelerator)
+    BspNodeParams bspnode;
     std::string filename = "pbrt.exr", accelerator = "bvh", integrator = "path", sampler = "halton";
 };
 struct SceneModel {
