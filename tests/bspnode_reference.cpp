@@ -473,6 +473,7 @@ void *bspnoderef_scene_load(const char *path, int chooser, int form, int K, uint
     if (!ok) { delete s->plain; delete s->kd; delete s; return nullptr; }
     return s;
 }
+size_t bspnoderef_scene_max_todo(void *h, uint32_t *out) { const BuiltScene *s = (const BuiltScene *)h; return s->kd ? SceneMaxTodo(s->kd, out) : SceneMaxTodo(s->plain, out); }
 void bspnoderef_scene_free(void *h) { BuiltScene *s = (BuiltScene *)h; delete s->plain; delete s->kd; delete s; }
 size_t bspnoderef_scene_prims(void *h) { const BuiltScene *s = (const BuiltScene *)h; return s->kd ? s->kd->scene.prims.size() : s->plain->scene.prims.size(); }
 size_t bspnoderef_scene_triangles(void *h, float *p9) { const BuiltScene *s = (const BuiltScene *)h; return s->kd ? SceneTriangles(s->kd, p9) : SceneTriangles(s->plain, p9); }

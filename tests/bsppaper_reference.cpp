@@ -376,6 +376,7 @@ void *bspref_scene_load(const char *path, int build) {
     return r;
 }
 void bspref_scene_set_tree(void *h, size_t nNodes, const void *nodes20, size_t nIdx, const uint32_t *idx) { SceneSetTree((BspScene *)h, nNodes, nodes20, nIdx, idx); }
+size_t bspref_scene_max_todo(void *h, uint32_t *out) { return SceneMaxTodo((const BspScene *)h, out); }
 void bspref_scene_free(void *h) { delete (BspScene *)h; }
 size_t bspref_scene_prims(void *h) { return ((BspScene *)h)->scene.prims.size(); }
 size_t bspref_scene_triangles(void *h, float *p9) { return SceneTriangles((const BspScene *)h, p9); }

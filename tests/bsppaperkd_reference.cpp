@@ -227,6 +227,7 @@ void *bspkdref_scene_load(const char *path, int build) {
     return r;
 }
 void bspkdref_scene_set_tree(void *h, size_t nNodes, const void *nodes20, size_t nIdx, const uint32_t *idx) { SceneSetTree((BspKdScene *)h, nNodes, nodes20, nIdx, idx); }
+size_t bspkdref_scene_max_todo(void *h, uint32_t *out) { return SceneMaxTodo((const BspKdScene *)h, out); }
 void bspkdref_scene_free(void *h) { delete (BspKdScene *)h; }
 size_t bspkdref_scene_prims(void *h) { return ((BspKdScene *)h)->scene.prims.size(); }
 size_t bspkdref_scene_triangles(void *h, float *p9) { return SceneTriangles((const BspKdScene *)h, p9); }

@@ -149,8 +149,12 @@ void *kdref_scene_load(const char *path) {
     Build(b, 80, 1, 0.f, 1, (uint32_t)-1, &r->tree);
     return r;
 }
+// the tree is given instead (a tree made by hand, or the library's)
+void kdref_scene_set_tree(void *h, size_t nNodes, const void *nodes8, size_t nIdx, const uint32_t *idx) { SceneSetTree((KdScene *)h, nNodes, nodes8, nIdx, idx); }
+size_t kdref_scene_max_todo(void *h, uint32_t *out) { return SceneMaxTodo((const KdScene *)h, out); }
 void kdref_scene_free(void *h) { delete (KdScene *)h; }
 size_t kdref_scene_prims(void *h) { return ((KdScene *)h)->scene.prims.size(); }
+size_t kdref_scene_triangles(void *h, float *p9) { return SceneTriangles((const KdScene *)h, p9); }
 void kdref_scene_bounds(void *h, float *bmin, float *bmax) {
     KdScene *r = (KdScene *)h;
     for (size_t i = 0; i < r->scene.prims.size(); ++i) {

@@ -191,6 +191,7 @@ void rbspref_scene_set_tree(void *h, int M, size_t nNodes, const void *nodes8, s
     r->tree.dirs = Directions((uint32_t)M);
     SceneSetTree(r, nNodes, nodes8, nIdx, idx);
 }
+size_t rbspref_scene_max_todo(void *h, uint32_t *out) { return SceneMaxTodo((const RbspScene *)h, out); }
 void rbspref_scene_free(void *h) { delete (RbspScene *)h; }
 size_t rbspref_scene_prims(void *h) { return ((RbspScene *)h)->scene.prims.size(); }
 size_t rbspref_scene_triangles(void *h, float *p9) { return SceneTriangles((const RbspScene *)h, p9); }

@@ -218,6 +218,8 @@ void rbspkdref_scene_set_tree(void *h, int M, size_t nNodes, const void *nodes8,
     r->tree.dirs = Directions((uint32_t)M);
     SceneSetTree(r, nNodes, nodes8, nIdx, idx);
 }
+size_t rbspkdref_scene_max_todo_dot(void *h, uint32_t *out) { return SceneMaxTodoDot((const RbspKdScene *)h, out); }
+size_t rbspkdref_scene_max_todo(void *h, uint32_t *out) { return SceneMaxTodo((const RbspKdScene *)h, out); }
 void rbspkdref_scene_free(void *h) { delete (RbspKdScene *)h; }
 size_t rbspkdref_scene_prims(void *h) { return ((RbspKdScene *)h)->scene.prims.size(); }
 size_t rbspkdref_scene_triangles(void *h, float *p9) { return SceneTriangles((const RbspKdScene *)h, p9); }

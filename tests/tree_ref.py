@@ -24,11 +24,14 @@ _SHARED = {
     "scene_splits": (_SZ, [_VP, _VP, _VP, _SZ]),
     "intersect": (None, [_VP, _SZ, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "occluded": (None, [_VP, _SZ, _VP, _VP, _VP, _VP, _VP]),
+    "scene_max_todo": (_SZ, [_VP, _VP]),
+    "scene_max_todo_dot": (_SZ, [_VP, _VP]),
 }
 # and those whose arguments are an accelerator's own
 _OWN = {
     "kd": ("kdref", {"build": (_VP, [_SZ, _VP, _VP, _INT, _INT, _FLT, _INT, _INT, _U32P]), "copy": (None, [_VP, _VP, _VP]),
-                     "scene_load": (_VP, [C.c_char_p]), "scene_bounds": (None, [_VP, _VP, _VP])}),
+                     "scene_load": (_VP, [C.c_char_p]), "scene_bounds": (None, [_VP, _VP, _VP]),
+                     "scene_set_tree": (None, [_VP, _SZ, _VP, _SZ, _VP])}),
     "rbsp": ("rbspref", {"build": (_VP, [_SZ, _VP, _INT, _INT, _INT, _FLT, _INT, _INT, _U32P]), "copy": (None, [_VP, _VP, _VP, _VP]),
                          "scene_load": (_VP, [C.c_char_p, _INT, _INT]), "scene_set_tree": (None, [_VP, _INT, _SZ, _VP, _SZ, _VP])}),
     "rbspkd": ("rbspkdref", {"build": (_VP, [_SZ, _VP, _INT, _INT, _INT, _INT, _FLT, _INT, _INT, _U32P]), "copy": (None, [_VP, _VP, _VP, _VP]),
@@ -133,6 +136,20 @@ class _TreeScene:
         self._lib.occluded(self._h, n, _p(o), _p(d), _p(tmax), _p(occ), _p(c))
         return occ, c
 
+    def max_todo(self):
+        """per ray of the last intersect() / occluded() call, the largest todoPos the walk reached: the todo entries it held at once"""
+        n = self._lib.scene_max_todo(self._h, None)
+        out = np.zeros(n, np.uint32)
+        self._lib.scene_max_todo(self._h, _p(out))
+        return out
+
+    def max_todo_dot(self):
+        """as max_todo, over the pushes made at interior nodes the walk does not take as kd nodes (rbspkd: the dot-product step)"""
+        n = self._lib.scene_max_todo_dot(self._h, None)
+        out = np.zeros(n, np.uint32)
+        self._lib.scene_max_todo_dot(self._h, _p(out))
+        return out
+
     def __del__(self):
         # the library hangs off the instance: module globals are cleared at interpreter exit
         if getattr(self, "_h", None) and getattr(self, "_lib", None) is not None:
@@ -141,11 +158,15 @@ class _TreeScene:
 
 
 class KdScene(_TreeScene):
-    """A baked scene with the default kd-tree (intersectcost 80, traversalcost 1, emptybonus 0, maxprims 1, maxdepth -1)."""
+    """A baked scene with the default kd-tree (intersectcost 80, traversalcost 1, emptybonus 0, maxprims 1, maxdepth -1), or a
+    tree given by set_tree()."""
     NAME = "kd"
 
     def __init__(self, path):
         self._open(path)
+
+    def set_tree(self, nodes, idx):
+        self._set_tree(nodes, idx)
 
     def bounds(self):
         lo = np.zeros((self.n, 3), np.float32); hi = np.zeros((self.n, 3), np.float32)

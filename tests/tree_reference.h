@@ -173,7 +173,8 @@ bool RootInterval(const B3 &b, const Ray &ray, Float *hitt0, Float *hitt1) {
     return true;
 }
 
-struct WalkCount { uint64_t nodes = 0, interior = 0, leaves = 0, kd = 0; };     // kd: the interior nodes a step calls Kd (rbspkd's axis nodes)
+// kd: the interior nodes a step calls Kd (rbspkd's axis nodes); maxTodo: the largest todoPos the ray reached (the entries it held at once)
+struct WalkCount { uint64_t nodes = 0, interior = 0, leaves = 0, kd = 0; uint32_t maxTodo = 0, maxTodoDot = 0; };      // maxTodoDot: the same over the pushes made at interior nodes the step does not call Kd
 
 // A baked scene (no instances), its BVH (for the ordered numbering and the primitive tests) and a tree walked with Step's
 // interior step.  A Step names its node type (NodeT: the two leading words are the 8-byte node's) and supplies
@@ -191,6 +192,8 @@ template <class Step> struct SceneRef {
     std::vector<uint32_t> toOrdered;
     TreeT<NodeT> tree;
     Step step;
+    mutable std::vector<uint32_t> maxTodoDot;   // and WalkCount::maxTodoDot
+    mutable std::vector<uint32_t> maxTodo;      // per ray of the last IntersectRays / OccludedRays: WalkCount::maxTodo
 
     // KdTreeAccel::Intersect (accelerators/kdtreeaccel.cpp:381-457), RBSP::Intersect (rbsp.cpp:405-477), RBSPKd::Intersect
     // (rbspKd.cpp:490-565), BSP::Intersect (BSP.cpp)
@@ -216,7 +219,12 @@ template <class Step> struct SceneRef {
                 else { first = &tree.nodes[node->aboveChild >> off]; second = node + 1; }
                 if (tPlane > tMax || tPlane <= 0) node = first;
                 else if (tPlane < tMin) node = second;
-                else { todo[todoPos].node = second; todo[todoPos].tMin = tPlane; todo[todoPos].tMax = tMax; ++todoPos; node = first; tMax = tPlane; }
+                else {
+                    todo[todoPos].node = second; todo[todoPos].tMin = tPlane; todo[todoPos].tMax = tMax; ++todoPos;
+                    wc.maxTodo = std::max(wc.maxTodo, todoPos);
+                    if (!step.Kd(tree, node)) wc.maxTodoDot = std::max(wc.maxTodoDot, todoPos);
+                    node = first; tMax = tPlane;
+                }
             } else {
                 ++wc.leaves;
                 const uint32_t np = node->nPrims >> off;
@@ -261,7 +269,12 @@ template <class Step> struct SceneRef {
                 else { first = &tree.nodes[node->aboveChild >> off]; second = node + 1; }
                 if (tPlane > tMax || tPlane <= 0) node = first;
                 else if (tPlane < tMin) node = second;
-                else { todo[todoPos].node = second; todo[todoPos].tMin = tPlane; todo[todoPos].tMax = tMax; ++todoPos; node = first; tMax = tPlane; }
+                else {
+                    todo[todoPos].node = second; todo[todoPos].tMin = tPlane; todo[todoPos].tMax = tMax; ++todoPos;
+                    wc.maxTodo = std::max(wc.maxTodo, todoPos);
+                    if (!step.Kd(tree, node)) wc.maxTodoDot = std::max(wc.maxTodoDot, todoPos);
+                    node = first; tMax = tPlane;
+                }
             }
         }
         return false;
@@ -332,10 +345,12 @@ template <class Step> size_t SceneSplits(const SceneRef<Step> *r, int32_t *axis,
 // triangle tests, sphere tests and, in a fifth column, the interior nodes the step calls Kd
 template <class Step> void IntersectRays(const SceneRef<Step> *r, size_t n, const float *o, const float *d, const float *tmax, float *tOut,
                                          int32_t *primOut, float *bary, uint64_t *counters, int W) {
+    r->maxTodo.assign(n, 0u); r->maxTodoDot.assign(n, 0u);
     for (size_t i = 0; i < n; ++i) {
         Ray ray(V3(o[3 * i], o[3 * i + 1], o[3 * i + 2]), V3(d[3 * i], d[3 * i + 1], d[3 * i + 2]), tmax[i]);
         SurfaceInteraction si; Counters c; WalkCount wc;
         const bool hit = r->Intersect(ray, &si, c, wc);
+        r->maxTodo[i] = wc.maxTodo; r->maxTodoDot[i] = wc.maxTodoDot;
         tOut[i] = ray.tMax; primOut[i] = hit ? si.ordered : -1;
         bary[3 * i] = hit ? si.b0 : 0.f; bary[3 * i + 1] = hit ? si.b1 : 0.f; bary[3 * i + 2] = hit ? si.b2 : 0.f;
         counters[W * i] = wc.nodes; counters[W * i + 1] = wc.interior; counters[W * i + 2] = c.triTests; counters[W * i + 3] = c.sphereTests;
@@ -344,13 +359,25 @@ template <class Step> void IntersectRays(const SceneRef<Step> *r, size_t n, cons
 }
 template <class Step> void OccludedRays(const SceneRef<Step> *r, size_t n, const float *o, const float *d, const float *tmax, uint8_t *occ,
                                         uint64_t *counters, int W) {
+    r->maxTodo.assign(n, 0u); r->maxTodoDot.assign(n, 0u);
     for (size_t i = 0; i < n; ++i) {
         Ray ray(V3(o[3 * i], o[3 * i + 1], o[3 * i + 2]), V3(d[3 * i], d[3 * i + 1], d[3 * i + 2]), tmax[i]);
         Counters c; WalkCount wc;
         occ[i] = r->IntersectP(ray, c, wc) ? 1 : 0;
+        r->maxTodo[i] = wc.maxTodo; r->maxTodoDot[i] = wc.maxTodoDot;
         counters[W * i] = wc.nodes; counters[W * i + 1] = wc.interior; counters[W * i + 2] = c.triTestsP; counters[W * i + 3] = c.sphereTestsP;
         if (W == 5) counters[W * i + 4] = wc.kd;
     }
+}
+// the optional per-ray output of the two walks: the largest todoPos of each ray of the last IntersectRays / OccludedRays call;
+// returns how many
+template <class Step> size_t SceneMaxTodo(const SceneRef<Step> *r, uint32_t *out) {
+    if (out) std::copy(r->maxTodo.begin(), r->maxTodo.end(), out);
+    return r->maxTodo.size();
+}
+template <class Step> size_t SceneMaxTodoDot(const SceneRef<Step> *r, uint32_t *out) {
+    if (out) std::copy(r->maxTodoDot.begin(), r->maxTodoDot.end(), out);
+    return r->maxTodoDot.size();
 }
 
 }  // namespace

@@ -151,6 +151,21 @@ class _Tree:
         self._call("copy", _ptr(nodes), _ptr(idx), *([None] if "M" in inf else []))
         return nodes, idx
 
+    @classmethod
+    def _from_arrays(cls, nodes, prim_indices, n_prims, bounds, *head):
+        """The handle of a tree made by hand (diagnostics hook hprt_debug_<_prefix>_from_arrays, not part of include/hprt.h): nodes
+        and prim_indices as arrays() gives them, n_prims the primitives the tree is over, bounds its six floats pMin, pMax; head:
+        the arguments in front (M).  The tree passes the checks a built tree passes (HprtError E_INVALID / E_UNSUPPORTED)."""
+        nodes = np.ascontiguousarray(nodes, np.uint32); idx = np.ascontiguousarray(prim_indices, np.uint32).ravel()
+        b = np.ascontiguousarray(bounds, np.float32).ravel()
+        assert nodes.ndim == 2 and b.shape[0] == 6
+        fn = getattr(lib, "hprt_debug_%s_from_arrays" % cls._prefix)
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_uint32] * len(head) + [C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_void_p)]
+        h = C.c_void_p()
+        _check(fn(*head, nodes.shape[0], _ptr(nodes), idx.shape[0], _ptr(idx), int(n_prims), _ptr(b), C.byref(h)))
+        return cls(handle=h)
+
     def _directions(self):
         """[M, 3] float32: getDirections(M)"""
         d = np.zeros((self.info()["M"], 3), np.float32)
@@ -186,6 +201,11 @@ class RbspKd(_Tree):
         prm = RbspKdParams(isect_cost, trav_cost, kd_trav_cost, empty_bonus, max_prims, max_depth, n_directions, threads)
         _check(lib.hprt_rbspkd_build_from_triangles(p9.shape[0], _ptr(p9), C.byref(prm), C.byref(h)))
         return RbspKd(handle=h)
+
+    @staticmethod
+    def from_arrays(nodes, prim_indices, n_prims, bounds, n_directions=3):
+        """A tree made by hand (see _Tree._from_arrays); n_directions: 3, 7, 9 or 13, the library's own direction table."""
+        return RbspKd._from_arrays(nodes, prim_indices, n_prims, bounds, n_directions)
 
     directions = _Tree._directions
 
@@ -451,6 +471,11 @@ class KdTree(_Tree):
                                                  max_prims, max_depth, C.byref(h)))
         return KdTree(handle=h)
 
+    @staticmethod
+    def from_arrays(nodes, prim_indices, n_prims, bounds):
+        """A tree made by hand (see _Tree._from_arrays)."""
+        return KdTree._from_arrays(nodes, prim_indices, n_prims, bounds)
+
 
 class RbspParams(C.Structure):
     """HprtRbspParams: CreateRBSPTreeAccelerator's parameters plus the builder's thread count."""
@@ -485,6 +510,11 @@ class Rbsp(_Tree):
         _check(lib.hprt_rbsp_build_from_triangles(p9.shape[0], _ptr(p9), C.byref(prm), C.byref(h)))
         return Rbsp(handle=h)
 
+    @staticmethod
+    def from_arrays(nodes, prim_indices, n_prims, bounds, n_directions=3):
+        """A tree made by hand (see _Tree._from_arrays); n_directions: 3, 7, 9 or 13, the library's own direction table."""
+        return Rbsp._from_arrays(nodes, prim_indices, n_prims, bounds, n_directions)
+
     directions = _Tree._directions
 
 
@@ -516,6 +546,11 @@ class BspPaper(_Tree):
         prm = BspPaperParams(isect_cost, trav_cost, empty_bonus, max_prims, max_depth, threads)
         _check(lib.hprt_bsppaper_build_from_triangles(p9.shape[0], _ptr(p9), C.byref(prm), C.byref(h)))
         return BspPaper(handle=h)
+
+    @staticmethod
+    def from_arrays(nodes, prim_indices, n_prims, bounds):
+        """A tree made by hand (see _Tree._from_arrays)."""
+        return BspPaper._from_arrays(nodes, prim_indices, n_prims, bounds)
 
     def arrays(self):
         """(nodes [n, 5] uint32: the reference's BSPNode — word 0 split / onePrimitive / primitiveIndicesOffset, word 1 flags,
@@ -555,6 +590,11 @@ class BspPaperKd(_Tree):
         prm = BspPaperKdParams(isect_cost, trav_cost, kd_trav_cost, empty_bonus, max_prims, max_depth, threads)
         _check(lib.hprt_bsppaperkd_build_from_triangles(p9.shape[0], _ptr(p9), C.byref(prm), C.byref(h)))
         return BspPaperKd(handle=h)
+
+    @staticmethod
+    def from_arrays(nodes, prim_indices, n_prims, bounds):
+        """A tree made by hand (see _Tree._from_arrays)."""
+        return BspPaperKd._from_arrays(nodes, prim_indices, n_prims, bounds)
 
     def arrays(self):
         """(nodes [n, 5] uint32: the reference's BSPKdNode — word 0 split / onePrimitive / primitiveIndicesOffset, word 1 flags

@@ -209,6 +209,67 @@ int BuildBspNodeFromTriangles(const char *fn, size_t n, const float *p9, const H
     return BuildBspNode(fn, n, lo.data(), hi.data(), p9, isTri.data(), params, BspNodeParams(), out);
 }
 
+// ---- trees given as arrays (the hprt_debug_*_from_arrays hooks below): what a builder would have filled in, then the builder's own
+// structural check and the walk's depth limit, so that the handle is an ordinary one ----
+uint32_t CountLeaves(const std::vector<BspNode> &nodes, uint32_t mask, uint32_t leafTag) {
+    return (uint32_t)std::count_if(nodes.begin(), nodes.end(), [&](const BspNode &nd) { return (nd.b & mask) == leafTag; });
+}
+template <typename Handle>
+int RbspFromArrays(const char *fn, uint32_t M, size_t nNodes, const uint32_t *nodes8, size_t nIdx, const uint32_t *idx, uint32_t nPrims,
+                   const float *bounds6, Handle **out) {
+    if (!out || !nodes8 || !bounds6 || (nIdx && !idx)) return SetError(HPRT_E_INVALID, std::string(fn) + ": null argument");
+    std::unique_ptr<Handle> t(new Handle());
+    RbspTree &r = t->tree;
+    if (!RbspDirections(M, &r.directions)) return SetError(HPRT_E_UNSUPPORTED, "nbDirections " + std::to_string(M) + " is not supported (3, 7, 9 or 13)");
+    r.M = M; r.nPrims = nPrims;
+    r.nodes.resize(nNodes);
+    memcpy(r.nodes.data(), nodes8, nNodes * sizeof(RbspNode));
+    r.primIndices.assign(idx, idx + nIdx);
+    memcpy(r.bounds, bounds6, sizeof(r.bounds));
+    const char *bad = CheckRbspTree(r, &r.depth);
+    if (*bad) return SetError(HPRT_E_INVALID, std::string("malformed tree: ") + bad);
+    r.maxDepth = r.depth; r.leaves = CountLeaves(r.nodes, RbspBitMask(M), M);
+    if (r.depth > RBSP_TODO_MAX)
+        return SetError(HPRT_E_UNSUPPORTED, "RBSP tree of depth " + std::to_string(r.depth) + " is deeper than the device walk's todo list (" +
+                                                std::to_string((unsigned)RBSP_TODO_MAX) + " entries); lower \"maxdepth\"");
+    *out = t.release();
+    return HPRT_OK;
+}
+// nodes20: 5 words per node, as BspPaperCopy writes them
+template <typename Handle>
+int BspPaperFromArrays(const char *fn, size_t nNodes, const uint32_t *nodes20, size_t nIdx, const uint32_t *idx, uint32_t nPrims, const float *bounds6,
+                       Handle **out) {
+    constexpr bool kdAware = std::is_same<Handle, HprtBspPaperKd>::value;
+    if (!out || !nodes20 || !bounds6 || (nIdx && !idx)) return SetError(HPRT_E_INVALID, std::string(fn) + ": null argument");
+    std::unique_ptr<Handle> t(new Handle());
+    BspPaperTree &b = t->tree;
+    b.kdAware = kdAware; b.nPrims = nPrims;
+    b.nodes.resize(nNodes); b.axes.resize(3 * nNodes);
+    for (size_t k = 0; k < nNodes; ++k) {
+        b.nodes[k] = BspNode{nodes20[5 * k], nodes20[5 * k + 1]};
+        memcpy(&b.axes[3 * k], &nodes20[5 * k + 2], 12);
+    }
+    b.primIndices.assign(idx, idx + nIdx);
+    memcpy(b.bounds, bounds6, sizeof(b.bounds));
+    const char *bad = kdAware ? CheckBspPaperKdTree(b, &b.depth) : CheckBspPaperTree(b, &b.depth);
+    if (*bad) return SetError(HPRT_E_INVALID, std::string("malformed tree: ") + bad);
+    b.maxDepth = b.depth;
+    b.leaves = kdAware ? CountLeaves(b.nodes, BSPPAPERKD_MASK, BSPPAPERKD_LEAF) : CountLeaves(b.nodes, BSPPAPER_MASK, 1u);
+    for (size_t k = 0; k < nNodes; ++k) {       // a hand-made tree has no sweep: its axis nodes are the kd nodes, or those along a coordinate axis
+        const uint32_t kind = b.nodes[k].b & (kdAware ? (uint32_t)BSPPAPERKD_MASK : (uint32_t)BSPPAPER_MASK);
+        if (kind == (kdAware ? (uint32_t)BSPPAPERKD_LEAF : 1u)) continue;
+        const float *a = &b.axes[3 * k];
+        const bool axisNode = kdAware ? kind < BSPPAPERKD_LEAF : (a[0] != 0) + (a[1] != 0) + (a[2] != 0) == 1;
+        ++(axisNode ? b.axisNodes : b.planeNodes);
+    }
+    constexpr uint32_t todoMax = kdAware ? BSPPAPERKD_TODO_MAX : BSPPAPER_TODO_MAX;
+    if (b.depth > todoMax)
+        return SetError(HPRT_E_UNSUPPORTED, std::string(kdAware ? "bsppaperkd" : "bsppaper") + " tree of depth " + std::to_string(b.depth) +
+                                                " is deeper than the device walk's todo list (" + std::to_string((unsigned)todoMax) + " entries); lower \"maxdepth\"");
+    *out = t.release();
+    return HPRT_OK;
+}
+
 // Film::WriteGeneralStats (core/film.cpp:170-187) with WriteGeneralStatMatrix (:189-210): the eight matrices, each to
 // "<prefix>-<name>.txt", one image row per line; value(k, i): matrix k's value at pixel i (row-major)
 template <typename Value>
@@ -554,6 +615,42 @@ __attribute__((visibility("default"))) int hprt_debug_bspnode_check(size_t n_nod
     if (*depth > (t.kdAware ? (uint32_t)BSPPAPERKD_TODO_MAX : (uint32_t)BSPPAPER_TODO_MAX))
         return SetError(HPRT_E_UNSUPPORTED, "node-based BSP tree of depth " + std::to_string(*depth) + " is deeper than the device walk's todo list");
     return HPRT_OK;
+} catch (...) { return hprt::HandleException(); }
+// Diagnostics hooks (not part of include/hprt.h; tests/deep_todo.py): a tree made by hand as an ordinary handle, so that a tree with a
+// known todo depth reaches the walks.  nodes8 / nodes20: the node words as hprt_<tree>_copy writes them; idx: primitiveIndices; n_prims:
+// the primitives the tree is over (creation-order numbers); bounds6: the tree's bounds, pMin then pMax; M: the direction set of the
+// library's own table.  The tree passes the structural check and the depth limit a built tree passes (HPRT_E_INVALID,
+// HPRT_E_UNSUPPORTED), and hprt_scene_attach_* checks it again like any other.
+__attribute__((visibility("default"))) int hprt_debug_kdtree_from_arrays(size_t n_nodes, const uint32_t *nodes8, size_t n_idx, const uint32_t *idx, uint32_t n_prims,
+                                                                          const float *bounds6, HprtKdTree **out) try {
+    if (!out || !nodes8 || !bounds6 || (n_idx && !idx)) return SetError(HPRT_E_INVALID, "hprt_debug_kdtree_from_arrays: null argument");
+    std::unique_ptr<HprtKdTree> t(new HprtKdTree());
+    KdTree &k = t->tree;
+    k.nPrims = n_prims;
+    k.nodes.resize(n_nodes);
+    memcpy(k.nodes.data(), nodes8, n_nodes * sizeof(KdNode));
+    k.primIndices.assign(idx, idx + n_idx);
+    memcpy(k.bounds, bounds6, sizeof(k.bounds));
+    const char *bad = CheckKdTree(k, &k.depth);
+    if (*bad) return SetError(HPRT_E_INVALID, std::string("malformed tree: ") + bad);
+    k.maxDepth = k.depth; k.leaves = CountLeaves(k.nodes, 3u, 3u);
+    return FinishKdTree(t.release(), out);
+} catch (...) { return hprt::HandleException(); }
+__attribute__((visibility("default"))) int hprt_debug_rbsp_from_arrays(uint32_t M, size_t n_nodes, const uint32_t *nodes8, size_t n_idx, const uint32_t *idx,
+                                                                        uint32_t n_prims, const float *bounds6, HprtRbsp **out) try {
+    return RbspFromArrays("hprt_debug_rbsp_from_arrays", M, n_nodes, nodes8, n_idx, idx, n_prims, bounds6, out);
+} catch (...) { return hprt::HandleException(); }
+__attribute__((visibility("default"))) int hprt_debug_rbspkd_from_arrays(uint32_t M, size_t n_nodes, const uint32_t *nodes8, size_t n_idx, const uint32_t *idx,
+                                                                          uint32_t n_prims, const float *bounds6, HprtRbspKd **out) try {
+    return RbspFromArrays("hprt_debug_rbspkd_from_arrays", M, n_nodes, nodes8, n_idx, idx, n_prims, bounds6, out);
+} catch (...) { return hprt::HandleException(); }
+__attribute__((visibility("default"))) int hprt_debug_bsppaper_from_arrays(size_t n_nodes, const uint32_t *nodes20, size_t n_idx, const uint32_t *idx, uint32_t n_prims,
+                                                                            const float *bounds6, HprtBspPaper **out) try {
+    return BspPaperFromArrays("hprt_debug_bsppaper_from_arrays", n_nodes, nodes20, n_idx, idx, n_prims, bounds6, out);
+} catch (...) { return hprt::HandleException(); }
+__attribute__((visibility("default"))) int hprt_debug_bsppaperkd_from_arrays(size_t n_nodes, const uint32_t *nodes20, size_t n_idx, const uint32_t *idx, uint32_t n_prims,
+                                                                              const float *bounds6, HprtBspPaperKd **out) try {
+    return BspPaperFromArrays("hprt_debug_bsppaperkd_from_arrays", n_nodes, nodes20, n_idx, idx, n_prims, bounds6, out);
 } catch (...) { return hprt::HandleException(); }
 // Diagnostics hooks (not part of include/hprt.h; tests/test_bsppaper_host.py), the bsppaper builder's views of the triangles p9
 // (9 floats each, creation order).  hprt_debug_bsppaper_planes: getBSPPaperPlanes of triangle 0, planes_out[4 k ..] = {t, axis}
