@@ -146,6 +146,35 @@ int hprt_kdtree_copy(const HprtKdTree *t, void *nodes8, uint32_t *prim_indices);
 void hprt_kdtree_destroy(HprtKdTree *t);
 
 /* ------------------------------------------------------------------------ */
+/* Two-level kd-trees (Accelerator "kdtree" on a model with object           */
+/* instances).  Stands in for pbrtObjectInstance (core/api.cpp:1794-1819):   */
+/* MakeAccelerator(renderOptions->AcceleratorName, ...) over the primitives  */
+/* of every object that has more than one (an object with exactly one is     */
+/* wrapped as it is, :1798), each wrapped in a TransformedPrimitive, and     */
+/* pbrtWorldEnd's top-level accelerator over those wrappers: a kd-tree whose */
+/* leaves hold kd-trees.  Opt-in: hprt_kdtree_build keeps refusing such      */
+/* models and the front end keeps their BVH and its warning.                 */
+/* ------------------------------------------------------------------------ */
+typedef struct HprtKdInst HprtKdInst;
+/* One KdTreeAccel per object with more than one primitive, over the object's primitive bounds in object space, and the
+ * top-level KdTreeAccel over the top-level items in creation order; an instance is bounded by
+ * TransformedPrimitive::WorldBound (core/primitive.h:116-118).  Every tree takes the parameters of the scene's Accelerator
+ * line; maxdepth -1 resolves per tree from its own primitive count, as in hprt_kdtree_build.
+ * HPRT_E_UNSUPPORTED for a model without instances (hprt_kdtree_build's job) and when depth(top) + deepest object depth + 1
+ * exceeds HPRT_KD_MAX_DEPTH: the walk keeps both levels' todo entries and one saved top-level position in one list. */
+int hprt_kdinst_build(const HprtModel *m, HprtKdInst **out);
+/* info[0..3] = nodes, leaves, primitive references, depth of the top-level tree; info[4] = object definitions, info[5] =
+ * object trees (objects with more than one primitive), info[6] = the deepest object tree's depth, info[7] = instances. */
+int hprt_kdinst_info(const HprtKdInst *t, uint32_t info[8]);
+/* info[0..3] as hprt_kdtree_info for the tree of object definition `object`; all zero for an object of one primitive,
+ * which has no tree (core/api.cpp:1798). */
+int hprt_kdinst_object_info(const HprtKdInst *t, uint32_t object, uint32_t info[4]);
+/* The arrays of the top-level tree / of one object's tree, as hprt_kdtree_copy returns them (either may be NULL). */
+int hprt_kdinst_copy(const HprtKdInst *t, void *nodes8, uint32_t *prim_indices);
+int hprt_kdinst_object_copy(const HprtKdInst *t, uint32_t object, void *nodes8, uint32_t *prim_indices);
+void hprt_kdinst_destroy(HprtKdInst *t);
+
+/* ------------------------------------------------------------------------ */
 /* RBSP tree (Accelerator "rbsp").  Stands in for RBSP::buildTree           */
 /* (accelerators/rbsp.cpp:181-403): a kd-tree whose split planes may also   */
 /* be oblique, chosen from M = 3, 7, 9 or 13 fixed directions, with the     */
@@ -479,6 +508,16 @@ int hprt_scene_attach_bsppaper(HprtScene *s, const HprtBspPaper *t);
  * (kdTreeNodeTraversals + bspTreeNodeTraversals), and the kd share comes from hprt_scene_kd_counters and
  * hprt_pixel_kd_stats_read. */
 int hprt_scene_attach_bsppaperkd(HprtScene *s, const HprtBspPaperKd *t);
+/* Makes a scene WITH object instances walk two-level kd-trees: KdTreeAccel::Intersect / IntersectP on both levels, joined by
+ * TransformedPrimitive::Intersect / IntersectP (core/primitive.cpp:77-102).  The handle must be built from the model the
+ * scene was made of: its object and instance counts and every tree's primitive count are checked against the scene's
+ * (HPRT_E_INVALID), every tree passes the kd-tree's structural check, and depth(top) + deepest object depth + 1 must not
+ * exceed HPRT_KD_MAX_DEPTH (HPRT_E_UNSUPPORTED).  Hit records are the BVH walk's of an instanced scene (ordered primitive
+ * over all aggregates, instance index).  Counters follow the kd scene's contract, summed over both levels as r.stats +=
+ * ray.stats (core/primitive.cpp:84,100) sums them; an instance entry is not itself a primitive test.  Attaching replaces
+ * whichever tree was attached before; an attach refused by these checks leaves the previous walk in place (a device failure
+ * during the upload that follows them leaves the scene on its BVH). */
+int hprt_scene_attach_kdinst(HprtScene *s, const HprtKdInst *t);
 /* kdTreeNodeTraversals (out[0]) and kdTreeNodeTraversalsP (out[1]) of the last counting trace (hprt_intersect / hprt_occluded
  * with counters) or counting render of an rbspkd or bsppaperkd scene; zeros for any other scene. */
 int hprt_scene_kd_counters(HprtScene *s, uint64_t out[2]);

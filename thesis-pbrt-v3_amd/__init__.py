@@ -281,6 +281,13 @@ def _load():
         "hprt_kdtree_copy": (C.c_int, [vp, vp, vp]),
         "hprt_kdtree_destroy": (None, [vp]),
         "hprt_scene_attach_kdtree": (C.c_int, [vp, vp]),
+        "hprt_kdinst_build": (C.c_int, [vp, P(vp)]),
+        "hprt_kdinst_info": (C.c_int, [vp, P(u32)]),
+        "hprt_kdinst_object_info": (C.c_int, [vp, u32, P(u32)]),
+        "hprt_kdinst_copy": (C.c_int, [vp, vp, vp]),
+        "hprt_kdinst_object_copy": (C.c_int, [vp, u32, vp, vp]),
+        "hprt_kdinst_destroy": (None, [vp]),
+        "hprt_scene_attach_kdinst": (C.c_int, [vp, vp]),
         "hprt_write_pixel_stats_accel": (C.c_int, [cp, vp, C.c_int, C.c_int, C.c_int]),
         "hprt_rbsp_build": (C.c_int, [vp, vp, P(vp)]),
         "hprt_rbsp_build_from_triangles": (C.c_int, [sz, vp, vp, P(vp)]),
@@ -475,6 +482,70 @@ class KdTree(_Tree):
     def from_arrays(nodes, prim_indices, n_prims, bounds):
         """A tree made by hand (see _Tree._from_arrays)."""
         return KdTree._from_arrays(nodes, prim_indices, n_prims, bounds)
+
+
+class KdInst:
+    """Two-level kd-trees (host) of a model WITH object instances, as pbrtObjectInstance and pbrtWorldEnd build them under
+    Accelerator "kdtree" (core/api.cpp:1794-1819): one kd-tree per object of more than one primitive and the top-level kd-tree
+    over the top-level items, all with the parameters of the scene's Accelerator line.  Scene.attach_kdinst walks them."""
+    _KEYS = ("nodes", "leaves", "prim_refs", "depth")
+
+    def __init__(self, model):
+        h = C.c_void_p()
+        _check(lib.hprt_kdinst_build(model._h, C.byref(h)))
+        self._h = h
+
+    def info(self):
+        """the top-level tree's nodes, leaves, prim_refs and depth; objects (definitions), object_trees (those with more than one
+        primitive), object_depth (the deepest object tree's) and instances"""
+        i = (C.c_uint32 * 8)()
+        _check(lib.hprt_kdinst_info(self._h, i))
+        return dict(zip(self._KEYS + ("objects", "object_trees", "object_depth", "instances"), i))
+
+    def object_info(self, obj):
+        """nodes, leaves, prim_refs and depth of the tree of object definition `obj`: all zero for an object of one primitive"""
+        i = (C.c_uint32 * 4)()
+        _check(lib.hprt_kdinst_object_info(self._h, obj, i))
+        return dict(zip(self._KEYS, i))
+
+    def copy(self):
+        """(nodes [n, 2] uint32, prim_indices uint32) of the top-level tree, as KdTree.arrays() gives them"""
+        inf = self.info()
+        nodes = np.zeros((inf["nodes"], 2), np.uint32); idx = np.zeros(inf["prim_refs"], np.uint32)
+        _check(lib.hprt_kdinst_copy(self._h, _ptr(nodes), _ptr(idx)))
+        return nodes, idx
+
+    def object_copy(self, obj):
+        """the same for the tree of object definition `obj` (empty arrays for an object of one primitive)"""
+        inf = self.object_info(obj)
+        nodes = np.zeros((inf["nodes"], 2), np.uint32); idx = np.zeros(inf["prim_refs"], np.uint32)
+        _check(lib.hprt_kdinst_object_copy(self._h, obj, _ptr(nodes), _ptr(idx)))
+        return nodes, idx
+
+    def bounds(self, obj=-1):
+        """Diagnostics hook (not part of include/hprt.h): the six floats pMin, pMax of the top-level tree (obj < 0) or of one
+        object's tree."""
+        b = np.zeros(6, np.float32)
+        lib.hprt_debug_kdinst_bounds.restype = C.c_int
+        lib.hprt_debug_kdinst_bounds.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        _check(lib.hprt_debug_kdinst_bounds(self._h, int(obj), _ptr(b)))
+        return b
+
+    def set_tree(self, obj, nodes, prim_indices, bounds):
+        """Diagnostics hook (not part of include/hprt.h): a tree made by hand in place of the top-level tree (obj < 0) or of one
+        object's tree; it passes the checks a built handle passes (HprtError E_INVALID / E_UNSUPPORTED, the handle unchanged)."""
+        nodes = np.ascontiguousarray(nodes, np.uint32); idx = np.ascontiguousarray(prim_indices, np.uint32).ravel()
+        b = np.ascontiguousarray(bounds, np.float32).ravel()
+        assert nodes.ndim == 2 and nodes.shape[1] == 2 and b.shape[0] == 6
+        fn = lib.hprt_debug_kdinst_set_tree
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        _check(fn(self._h, int(obj), nodes.shape[0], _ptr(nodes), idx.shape[0], _ptr(idx), _ptr(b)))
+
+    def __del__(self):
+        if getattr(self, "_h", None) and lib is not None:      # (module globals are cleared at interpreter exit)
+            lib.hprt_kdinst_destroy(self._h)
+            self._h = None
 
 
 class RbspParams(C.Structure):
@@ -716,6 +787,12 @@ class Scene:
         """hprt_scene_attach_kdtree: every later trace and render walks `kdtree` (built over this scene's primitives)."""
         _check(lib.hprt_scene_attach_kdtree(self._h, kdtree._h))
         self._kdtree = kdtree
+
+    def attach_kdinst(self, kdinst):
+        """hprt_scene_attach_kdinst: every later trace and render of this INSTANCED scene walks the two-level kd-trees `kdinst`
+        (a KdInst of the model the scene was made of).  Counters and pixel statistics follow the kd scene's, summed over both levels."""
+        _check(lib.hprt_scene_attach_kdinst(self._h, kdinst._h))
+        self._kdinst = kdinst
 
     def attach_rbsp(self, rbsp):
         """hprt_scene_attach_rbsp: every later trace and render walks `rbsp` (built over this scene's primitives); replaces an

@@ -33,6 +33,8 @@ struct BvhTree {
 // shapes/triangle.cpp:180-186; Shape::WorldBound for spheres, core/shape.cpp:53;
 // TransformedPrimitive::WorldBound for instances, which needs the objects' trees).
 void ComputeObjectPrimBounds(const SceneModel &sc, int object, std::vector<float> *bmin, std::vector<float> *bmax);
+// (Of an object's tree ComputePrimBounds reads the root box, nodes[0].bmin / bmax, and nothing else: hprt_kdinst_build relies on it
+// and passes one-node trees that hold the objects' bounds.)
 void ComputePrimBounds(const SceneModel &sc, const std::vector<BvhTree> &objectTrees, std::vector<float> *bmin,
                        std::vector<float> *bmax);
 

@@ -159,7 +159,8 @@ int hprt_scene_create(const HprtSceneDesc *d, int device, HprtScene **out) try {
     if (int rc = CheckDevice(device, &dev)) return rc;
     std::unique_ptr<HprtScene> sc(new HprtScene());
     sc->device = dev; sc->nPrims = L.nPrims;
-    sc->topOrder = std::move(L.topOrder); sc->instanced = L.instanced; sc->hasSubstrateBin = L.hasSubstrateBin;
+    sc->topOrder = std::move(L.topOrder); sc->objectOrder = std::move(L.objectOrder); sc->objectPrimBase = std::move(L.objectPrimBase);
+    sc->instanceObject = std::move(L.instanceObject); sc->instanced = L.instanced; sc->hasSubstrateBin = L.hasSubstrateBin;
     // Halton tables + 64-bit division magics
     const std::vector<uint16_t> &perms = HaltonPermutations();
     std::vector<int32_t> primes(PrimeTable().begin(), PrimeTable().end()), primeSums(PrimeSumTable().begin(), PrimeSumTable().end());
@@ -281,6 +282,9 @@ static void Trace(HprtScene *s, hipStream_t st, bool anyHit, bool count, const u
     case HprtScene::Walk::BspPaperKd:
         LaunchBspPaperKdTrace(st, s->dev, DevBspPaperKd{s->bsppaper, s->kdShare.as<unsigned long long>()}, anyHit, count, queue, countPtr, countImm,
                               gridItems, rays, hits, occ, counters, workCounter, rayStats);
+        break;
+    case HprtScene::Walk::KdInst:
+        LaunchKdInstTrace(st, s->dev, s->kdinst, anyHit, count, queue, countPtr, countImm, gridItems, rays, hits, occ, counters, workCounter, rayStats);
         break;
     case HprtScene::Walk::Bvh: LaunchTrace(st, s->dev, anyHit, count, queue, countPtr, countImm, gridItems, rays, hits, occ, counters, workCounter, rayStats); break;
     }
@@ -427,6 +431,43 @@ struct TreeView {
 // MakeAccelerator (core/api.cpp:790-831) for the trees the host builds: the tree is checked, its creation-order primitive numbers are
 // mapped to the scene's ordered indices (the inverse of prim_order), and from now on every trace of the scene takes `walk` over it
 // (Trace above).  Until the upload has succeeded the scene walks its BVH: a failed attach never leaves a half-replaced tree behind.
+// The steps every attach shares (AttachTree, hprt_scene_attach_kdinst).
+// InvertOrder: a prim_order (ordered position -> creation number) turned round, with the aggregate's first ordered index added.
+static std::vector<uint32_t> InvertOrder(const std::vector<uint32_t> &order, uint32_t primBase) {
+    std::vector<uint32_t> toOrdered(order.size());
+    for (uint32_t i = 0; i < (uint32_t)order.size(); ++i) toOrdered[order[i]] = primBase + i;
+    return toOrdered;
+}
+// AppendTree: one host tree behind whatever the upload arrays hold already — its creation-order primitive numbers mapped to ordered
+// indices (one-primitive leaves and primitiveIndices), and, where trees share the arrays, aboveChild and primitiveIndicesOffset
+// rebased (by nothing for the first tree).  off / mask / leafTag: the node layout.  Returns the tree's root.
+static uint32_t AppendTree(const std::vector<BspNode> &tree, const std::vector<uint32_t> &primIndices, const std::vector<uint32_t> &toOrdered,
+                           uint32_t off, uint32_t mask, uint32_t leafTag, std::vector<uint2> *nodes, std::vector<uint32_t> *prims) {
+    const uint32_t nodeBase = (uint32_t)nodes->size(), idxBase = (uint32_t)prims->size();
+    for (const BspNode &nd : tree) {
+        const uint32_t high = nd.b >> off;
+        if ((nd.b & mask) != leafTag) nodes->push_back(make_uint2(nd.a, (nd.b & mask) | ((high + nodeBase) << off)));
+        else nodes->push_back(make_uint2(high == 1u ? toOrdered[nd.a] : high == 0u ? nd.a : nd.a + idxBase, nd.b));
+    }
+    for (uint32_t p : primIndices) prims->push_back(toOrdered[p]);
+    return nodeBase;
+}
+// UploadTree: the arrays replace the attached tree's.  From here until the caller sets its walk the scene walks its BVH: a failed
+// upload never leaves a half-replaced tree behind (it does leave the BVH, not the tree that was attached before).
+static int UploadTree(HprtScene *s, const std::vector<uint2> &nodes, const std::vector<uint32_t> &prims) {
+    HIP_TRY(hipDeviceSynchronize());      // a render or trace of the old tree may still be running
+    s->walk = HprtScene::Walk::Bvh;
+    HIP_TRY(upload(s->treeNodes, nodes));
+    HIP_TRY(upload(s->treePrims, prims));
+    return HPRT_OK;
+}
+// FillTree: the fields every walk's descriptor shares (DevKd, DevRbsp, DevBspPaper, DevKdInst)
+extern "C++" template <class Dev> static void FillTree(Dev &d, const HprtScene *s, size_t nNodes, size_t nPrims, const float *bounds, uint32_t depth) {
+    d.nodes = s->treeNodes.as<uint2>(); d.nNodes = (uint32_t)nNodes;
+    d.primIdx = s->treePrims.as<uint32_t>(); d.nPrimIdx = (uint32_t)nPrims;
+    for (int a = 0; a < 3; ++a) { d.lo[a] = bounds[a]; d.hi[a] = bounds[3 + a]; }
+    d.depth = depth;
+}
 static int AttachTree(HprtScene *s, HprtScene::Walk walk, const TreeView &t) {
     const std::string what = t.what;
     if (s->instanced) return SetError(HPRT_E_UNSUPPORTED, what + "s over object instances are not supported: the scene keeps its BVH");
@@ -442,20 +483,9 @@ static int AttachTree(HprtScene *s, HprtScene::Walk walk, const TreeView &t) {
         return SetError(HPRT_E_UNSUPPORTED, what + " of depth " + std::to_string(depth) + " is deeper than the walk's todo list (" + std::to_string(t.todoMax) + ")");
     const uint32_t off = t.flagBits ? t.flagBits : RbspBitOffset(t.M), mask = t.flagBits ? (1u << t.flagBits) - 1u : RbspBitMask(t.M);
     const uint32_t leafTag = t.flagBits ? t.leafTag : t.M;
-    std::vector<uint32_t> toOrdered(nTop);
-    for (uint32_t i = 0; i < nTop; ++i) toOrdered[s->topOrder[i]] = i;
-    std::vector<uint2> nodes(t.nodes.size());
-    for (size_t k = 0; k < nodes.size(); ++k) {
-        const BspNode &nd = t.nodes[k];
-        const bool onePrim = (nd.b & mask) == leafTag && (nd.b >> off) == 1u;
-        nodes[k] = make_uint2(onePrim ? toOrdered[nd.a] : nd.a, nd.b);
-    }
-    std::vector<uint32_t> prims(t.primIndices.size());
-    for (size_t k = 0; k < prims.size(); ++k) prims[k] = toOrdered[t.primIndices[k]];
-    HIP_TRY(hipDeviceSynchronize());      // a render or trace of the old tree may still be running
-    s->walk = HprtScene::Walk::Bvh;
-    HIP_TRY(upload(s->treeNodes, nodes));
-    HIP_TRY(upload(s->treePrims, prims));
+    std::vector<uint2> nodes; std::vector<uint32_t> prims;
+    AppendTree(t.nodes, t.primIndices, InvertOrder(s->topOrder, 0u), off, mask, leafTag, &nodes, &prims);
+    if (int rc = UploadTree(s, nodes, prims)) return rc;
     if (t.axes) {       // 16 bytes per node (hipMalloc aligns far beyond), leaves zero as the builder holds them
         std::vector<float4> axes(t.nodes.size());
         for (size_t k = 0; k < axes.size(); ++k) axes[k] = make_float4((*t.axes)[3 * k], (*t.axes)[3 * k + 1], (*t.axes)[3 * k + 2], 0.f);
@@ -465,12 +495,7 @@ static int AttachTree(HprtScene *s, HprtScene::Walk walk, const TreeView &t) {
         HIP_TRY(s->kdShare.alloc(2 * sizeof(unsigned long long)));
         HIP_TRY(hipMemset(s->kdShare.p, 0, 2 * sizeof(unsigned long long)));
     }
-    auto fill = [&](auto &d) {      // the fields DevKd and DevRbsp share
-        d.nodes = s->treeNodes.as<uint2>(); d.nNodes = (uint32_t)nodes.size();
-        d.primIdx = s->treePrims.as<uint32_t>(); d.nPrimIdx = (uint32_t)prims.size();
-        for (int a = 0; a < 3; ++a) { d.lo[a] = t.bounds[a]; d.hi[a] = t.bounds[3 + a]; }
-        d.depth = depth;
-    };
+    auto fill = [&](auto &d) { FillTree(d, s, nodes.size(), prims.size(), t.bounds, depth); };
     if (walk == HprtScene::Walk::Kd) fill(s->kd);
     else if (walk == HprtScene::Walk::BspPaper || walk == HprtScene::Walk::BspPaperKd) {
         s->bsppaper = DevBspPaper{};
@@ -524,6 +549,73 @@ int hprt_scene_attach_bsppaperkd(HprtScene *s, const HprtBspPaperKd *t) try {
     return AttachTree(s, HprtScene::Walk::BspPaperKd, {"bsppaperkd tree", bt.nodes, bt.primIndices, bt.nPrims, bt.bounds, 3u, nullptr,
                                                        (uint32_t)BSPPAPERKD_TODO_MAX, [&](uint32_t *depth) { return CheckBspPaperKdTree(bt, depth); }, &bt.axes,
                                                        BSPPAPERKD_OFF, BSPPAPERKD_LEAF});
+} catch (...) { return hprt::HandleException(); }
+
+// Two-level kd-trees (pbrtObjectInstance, core/api.cpp:1794-1819, under Accelerator "kdtree"): the top-level tree and every
+// object's tree go through AttachTree's steps — CheckKdTree, the todo-list rule (here over both levels), AppendTree, UploadTree,
+// FillTree — into ONE node array and ONE primitiveIndices array (device/kdinst_walk.h), with one entry per instance.
+int hprt_scene_attach_kdinst(HprtScene *s, const HprtKdInst *t) try {
+    if (!s || !t) return SetError(HPRT_E_INVALID, "hprt_scene_attach_kdinst: null argument");
+    if (!s->instanced) return SetError(HPRT_E_UNSUPPORTED, "hprt_scene_attach_kdinst: the scene has no object instances; attach its kd-tree with hprt_scene_attach_kdtree");
+    HIP_TRY(hipSetDevice(s->device));
+    SceneCall call(s, nullptr);
+    const size_t nObjects = s->objectOrder.size();
+    if (t->objects.size() != nObjects || t->instanceObject != s->instanceObject)
+        return SetError(HPRT_E_INVALID, "the two-level kd-tree holds " + std::to_string(t->objects.size()) + " objects and " + std::to_string(t->instanceObject.size()) +
+                                        " instances, the scene " + std::to_string(nObjects) + " and " + std::to_string(s->instanceObject.size()) + " (or they name other objects)");
+    if (t->top.nPrims != s->topOrder.size())
+        return SetError(HPRT_E_INVALID, "the top-level kd-tree holds " + std::to_string(t->top.nPrims) + " primitives, the scene " + std::to_string(s->topOrder.size()));
+    uint32_t topDepth = 0, objectDepth = 0;
+    uint64_t nNodes = t->top.nodes.size(), nIdx = t->top.primIndices.size();
+    const char *bad = CheckKdTree(t->top, &topDepth);
+    if (*bad) return SetError(HPRT_E_INVALID, std::string("malformed top-level kd-tree: ") + bad);
+    for (size_t o = 0; o < nObjects; ++o) {
+        const KdTree &k = t->objects[o];
+        if (k.nPrims != s->objectOrder[o].size())
+            return SetError(HPRT_E_INVALID, "the kd-tree of object " + std::to_string(o) + " holds " + std::to_string(k.nPrims) + " primitives, the scene's object " + std::to_string(s->objectOrder[o].size()));
+        if ((k.nPrims > 1) != !k.nodes.empty()) return SetError(HPRT_E_INVALID, "object " + std::to_string(o) + ": exactly the objects of more than one primitive have a tree");
+        nNodes += k.nodes.empty() ? 1u : k.nodes.size(); nIdx += k.primIndices.size();
+        if (k.nodes.empty()) continue;
+        uint32_t depth = 0;
+        bad = CheckKdTree(k, &depth);
+        if (*bad) return SetError(HPRT_E_INVALID, "malformed kd-tree of object " + std::to_string(o) + ": " + bad);
+        objectDepth = std::max(objectDepth, depth);
+    }
+    if ((uint64_t)topDepth + objectDepth + 1u > KD_TODO_MAX)
+        return SetError(HPRT_E_UNSUPPORTED, "two-level kd-tree: top-level depth " + std::to_string(topDepth) + " + deepest object depth " + std::to_string(objectDepth) +
+                                            " + 1 is more than the walk's todo list holds (" + std::to_string((unsigned)KD_TODO_MAX) + ")");
+    if (nNodes > 0x3fffffffull || nIdx > 0xffffffffull) return SetError(HPRT_E_UNSUPPORTED, "two-level kd-tree: more than 2^30 nodes over all trees");
+    std::vector<uint2> nodes; std::vector<uint32_t> prims;
+    nodes.reserve((size_t)nNodes); prims.reserve((size_t)nIdx);
+    auto append = [&](const KdTree &k, const std::vector<uint32_t> &order, uint32_t primBase) {      // (KdAccelNode: two flag bits, leaves tagged 3)
+        return AppendTree(k.nodes, k.primIndices, InvertOrder(order, primBase), 2u, 3u, 3u, &nodes, &prims);
+    };
+    append(t->top, s->topOrder, 0u);
+    std::vector<uint32_t> objectRoot(nObjects);
+    for (size_t o = 0; o < nObjects; ++o) {
+        const KdTree &k = t->objects[o];
+        if (!k.nodes.empty()) objectRoot[o] = append(k, s->objectOrder[o], s->objectPrimBase[o]);
+        else {      // the lone primitive (or nothing: no instance names an empty object) as a one-primitive leaf
+            objectRoot[o] = (uint32_t)nodes.size();
+            nodes.push_back(make_uint2(s->objectPrimBase[o], 3u | ((k.nPrims ? 1u : 0u) << 2)));
+        }
+    }
+    std::vector<DevKdInstEntry> entries(t->instanceObject.size());
+    for (size_t i = 0; i < entries.size(); ++i) {
+        const size_t o = (size_t)t->instanceObject[i];
+        const KdTree &k = t->objects[o];
+        DevKdInstEntry &e = entries[i];
+        for (int a = 0; a < 3; ++a) { e.lo[a] = k.bounds[a]; e.hi[a] = k.bounds[3 + a]; }
+        e.root = objectRoot[o];
+        e.prim = k.nodes.empty() ? (int32_t)s->objectPrimBase[o] : -1;
+    }
+    if (int rc = UploadTree(s, nodes, prims)) return rc;
+    HIP_TRY(upload(s->kdInstEntries, entries));
+    DevKdInst &d = s->kdinst;
+    FillTree(d, s, nodes.size(), prims.size(), t->top.bounds, topDepth + objectDepth + 1u);
+    d.entries = s->kdInstEntries.as<DevKdInstEntry>(); d.nEntries = (uint32_t)entries.size();
+    s->walk = HprtScene::Walk::KdInst;
+    return HPRT_OK;
 } catch (...) { return hprt::HandleException(); }
 
 int hprt_scene_kd_counters(HprtScene *s, uint64_t out[2]) try {

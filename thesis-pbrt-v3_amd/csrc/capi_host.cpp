@@ -484,6 +484,112 @@ int hprt_kdtree_copy(const HprtKdTree *t, void *nodes8, uint32_t *primIndices) t
 } catch (...) { return hprt::HandleException(); }
 void hprt_kdtree_destroy(HprtKdTree *t) { delete t; }
 
+// ---- two-level kd-trees (Accelerator "kdtree" over object instances, core/api.cpp:1794-1819) ----
+// The walk keeps the top-level tree's todo entries, one saved top-level position and the object tree's entries in one list of
+// KD_TODO_MAX entries (device/kdinst_walk.hip)
+static int CheckKdInstDepth(const HprtKdInst &t) {
+    uint32_t deepest = 0;
+    for (const KdTree &o : t.objects) deepest = std::max(deepest, o.depth);
+    if ((uint64_t)t.top.depth + deepest + 1u > KD_TODO_MAX)
+        return SetError(HPRT_E_UNSUPPORTED, "two-level kd-tree: top-level depth " + std::to_string(t.top.depth) + " + deepest object depth " + std::to_string(deepest) +
+                                            " + 1 is more than the device walk's todo list holds (" + std::to_string((unsigned)KD_TODO_MAX) + " entries); lower \"maxdepth\"");
+    return HPRT_OK;
+}
+int hprt_kdinst_build(const HprtModel *m, HprtKdInst **out) try {
+    if (!m || !out) return SetError(HPRT_E_INVALID, "hprt_kdinst_build: null argument");
+    const SceneModel &sc = m->sc;
+    if (sc.instances.empty())
+        return SetError(HPRT_E_UNSUPPORTED, "hprt_kdinst_build: the model has no object instances; build its kd-tree with hprt_kdtree_build");
+    std::unique_ptr<HprtKdInst> t(new HprtKdInst());
+    for (const InstanceDesc &in : sc.instances) t->instanceObject.push_back(in.object);
+    t->objects.resize(sc.nObjects);
+    // TransformedPrimitive::WorldBound needs the wrapped primitive's bounds: the object accelerator's (the union of its primitives'
+    // bounds), or the lone primitive's own — the boxes the objects' BVH roots hold, which ComputePrimBounds reads
+    std::vector<BvhTree> objectBounds(sc.nObjects);
+    std::vector<float> lo, hi;
+    for (uint32_t o = 0; o < sc.nObjects; ++o) {
+        ComputeObjectPrimBounds(sc, (int)o, &lo, &hi);
+        const size_t n = lo.size() / 3;
+        if (n > 0x3fffffffull) return SetError(HPRT_E_UNSUPPORTED, "more than 2^30 primitives");
+        KdTree &k = t->objects[o];
+        if (n > 1) BuildKdTree(n, lo.data(), hi.data(), sc.opt.kd, &k);      // (core/api.cpp:1798: only more than one primitive gets an accelerator)
+        k.nPrims = (uint32_t)n;
+        if (n == 0) continue;
+        BvhNode box;
+        for (int a = 0; a < 3; ++a) { box.bmin[a] = lo[a]; box.bmax[a] = hi[a]; }
+        for (size_t i = 1; i < n; ++i)
+            for (int a = 0; a < 3; ++a) { box.bmin[a] = sel_min(box.bmin[a], lo[3 * i + a]); box.bmax[a] = sel_max(box.bmax[a], hi[3 * i + a]); }
+        box.offset = 0; box.countAxis = 3u;
+        objectBounds[o].nodes.push_back(box);
+    }
+    ComputePrimBounds(sc, objectBounds, &lo, &hi);
+    if (lo.size() / 3 > 0x3fffffffull) return SetError(HPRT_E_UNSUPPORTED, "more than 2^30 primitives");
+    BuildKdTree(lo.size() / 3, lo.data(), hi.data(), sc.opt.kd, &t->top);
+    if (int rc = CheckKdInstDepth(*t)) return rc;
+    *out = t.release();
+    return HPRT_OK;
+} catch (...) { return hprt::HandleException(); }
+static void KdTreeInfo(const KdTree &k, uint32_t info[4]) {
+    info[0] = (uint32_t)k.nodes.size(); info[1] = k.nodes.empty() ? 0u : k.leaves; info[2] = (uint32_t)k.primIndices.size(); info[3] = k.nodes.empty() ? 0u : k.depth;
+}
+static void KdTreeCopy(const KdTree &k, void *nodes8, uint32_t *primIndices) {
+    if (nodes8 && !k.nodes.empty()) memcpy(nodes8, k.nodes.data(), k.nodes.size() * sizeof(KdNode));
+    if (primIndices && !k.primIndices.empty()) memcpy(primIndices, k.primIndices.data(), k.primIndices.size() * 4);
+}
+int hprt_kdinst_info(const HprtKdInst *t, uint32_t info[8]) try {
+    if (!t || !info) return SetError(HPRT_E_INVALID, "hprt_kdinst_info: null argument");
+    KdTreeInfo(t->top, info);
+    info[4] = (uint32_t)t->objects.size(); info[5] = 0; info[6] = 0; info[7] = (uint32_t)t->instanceObject.size();
+    for (const KdTree &o : t->objects) if (!o.nodes.empty()) { ++info[5]; info[6] = std::max(info[6], o.depth); }
+    return HPRT_OK;
+} catch (...) { return hprt::HandleException(); }
+int hprt_kdinst_object_info(const HprtKdInst *t, uint32_t object, uint32_t info[4]) try {
+    if (!t || !info) return SetError(HPRT_E_INVALID, "hprt_kdinst_object_info: null argument");
+    if (object >= t->objects.size()) return SetError(HPRT_E_INVALID, "hprt_kdinst_object_info: object index out of range");
+    KdTreeInfo(t->objects[object], info);
+    return HPRT_OK;
+} catch (...) { return hprt::HandleException(); }
+int hprt_kdinst_copy(const HprtKdInst *t, void *nodes8, uint32_t *primIndices) try {
+    if (!t) return SetError(HPRT_E_INVALID, "hprt_kdinst_copy: null argument");
+    KdTreeCopy(t->top, nodes8, primIndices);
+    return HPRT_OK;
+} catch (...) { return hprt::HandleException(); }
+int hprt_kdinst_object_copy(const HprtKdInst *t, uint32_t object, void *nodes8, uint32_t *primIndices) try {
+    if (!t) return SetError(HPRT_E_INVALID, "hprt_kdinst_object_copy: null argument");
+    if (object >= t->objects.size()) return SetError(HPRT_E_INVALID, "hprt_kdinst_object_copy: object index out of range");
+    KdTreeCopy(t->objects[object], nodes8, primIndices);
+    return HPRT_OK;
+} catch (...) { return hprt::HandleException(); }
+void hprt_kdinst_destroy(HprtKdInst *t) { delete t; }
+// Diagnostics hooks (not part of include/hprt.h; tests): the bounds of the top-level tree (object < 0) or of one object's tree, and
+// a tree made by hand in place of the built one — nodes8 / idx as hprt_kdinst_copy writes them, bounds6 pMin then pMax — so that
+// trees with a known todo depth reach the walk.  The tree keeps its primitive count and passes the structural check and the
+// two-level depth rule a built handle passes (HPRT_E_INVALID, HPRT_E_UNSUPPORTED; the handle is unchanged when refused).
+__attribute__((visibility("default"))) int hprt_debug_kdinst_bounds(const HprtKdInst *t, int object, float bounds6[6]) try {
+    if (!t || !bounds6 || object >= (int)t->objects.size()) return SetError(HPRT_E_INVALID, "hprt_debug_kdinst_bounds: bad argument");
+    memcpy(bounds6, (object < 0 ? t->top : t->objects[object]).bounds, 6 * sizeof(float));
+    return HPRT_OK;
+} catch (...) { return hprt::HandleException(); }
+__attribute__((visibility("default"))) int hprt_debug_kdinst_set_tree(HprtKdInst *t, int object, size_t n_nodes, const uint32_t *nodes8, size_t n_idx,
+                                                                       const uint32_t *idx, const float *bounds6) try {
+    if (!t || !nodes8 || !bounds6 || (n_idx && !idx) || object >= (int)t->objects.size()) return SetError(HPRT_E_INVALID, "hprt_debug_kdinst_set_tree: bad argument");
+    KdTree &dst = object < 0 ? t->top : t->objects[object];
+    if (object >= 0 && dst.nPrims < 2) return SetError(HPRT_E_INVALID, "hprt_debug_kdinst_set_tree: an object of one primitive has no tree");
+    KdTree k;
+    k.nPrims = dst.nPrims;
+    k.nodes.resize(n_nodes);
+    memcpy(k.nodes.data(), nodes8, n_nodes * sizeof(KdNode));
+    k.primIndices.assign(idx, idx + n_idx);
+    memcpy(k.bounds, bounds6, sizeof(k.bounds));
+    const char *bad = CheckKdTree(k, &k.depth);
+    if (*bad) return SetError(HPRT_E_INVALID, std::string("malformed tree: ") + bad);
+    k.maxDepth = k.depth; k.leaves = CountLeaves(k.nodes, 3u, 3u);
+    KdTree old = std::move(dst);
+    dst = std::move(k);
+    if (int rc = CheckKdInstDepth(*t)) { dst = std::move(old); return rc; }
+    return HPRT_OK;
+} catch (...) { return hprt::HandleException(); }
+
 // ---- RBSP tree (Accelerator "rbsp") and kd-aware RBSP tree (Accelerator "rbspkd"): one RbspTree, two handle types (helpers above) ----
 int hprt_rbsp_build(const HprtModel *m, const HprtRbspParams *params, HprtRbsp **out) try {
     return BuildRbspFromModel("hprt_rbsp_build", "RBSP", m, params, m ? m->sc.opt.rbsp : RbspParams(), out);

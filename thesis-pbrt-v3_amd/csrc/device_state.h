@@ -13,6 +13,7 @@
 #include "device/rbspkd_walk.h"
 #include "device/bsppaper_walk.h"
 #include "device/bsppaperkd_walk.h"
+#include "device/kdinst_walk.h"
 #include "hprt_internal.h"
 
 #define HIP_TRY(expr)                                                                                   \
@@ -97,11 +98,17 @@ struct HprtScene {
     // counter pair (DevRbspKd / DevBspPaperKd::kdCounters); pixelKdLocal / pixelKdFilm: their per-pixel kd share of HPRT_RENDER_PIXEL_STATS.
     // topOrder keeps the top-level prim_order (ordered -> creation number) to map a tree's creation-order primitives; instanced:
     // no tree walk
-    enum class Walk { Bvh, Kd, Rbsp, RbspKd, BspPaper, BspPaperKd } walk = Walk::Bvh;
+    enum class Walk { Bvh, Kd, Rbsp, RbspKd, BspPaper, BspPaperKd, KdInst } walk = Walk::Bvh;
     hprt::DevBuf treeNodes, treePrims, treeAxes; hprt::DevKd kd{}; hprt::DevRbsp rbsp{}; hprt::DevBspPaper bsppaper{};
     hprt::DevBuf kdShare, pixelKdLocal, pixelKdFilm; bool pixelKdValid = false;
     std::vector<uint32_t> topOrder; bool instanced = false;
     bool hasSubstrateBin = false;                     // some triangle carries BIN_SUBSTRATE: the substrate shading variant is launched
+    // Two-level kd-trees (hprt_scene_attach_kdinst, the one tree walk of an instanced scene): treeNodes / treePrims hold the nodes and
+    // primitiveIndices of the top-level tree followed by every object tree's, kdInstEntries one DevKdInstEntry per instance;
+    // objectOrder / objectPrimBase map an object tree's creation-order primitives as topOrder maps the top level's; instanceObject:
+    // each instance's object definition
+    hprt::DevBuf kdInstEntries; hprt::DevKdInst kdinst{};
+    std::vector<std::vector<uint32_t>> objectOrder; std::vector<uint32_t> objectPrimBase; std::vector<int32_t> instanceObject;
     ~HprtScene() { if (hostCounts) (void)hipHostFree(hostCounts); if (lastUse) (void)hipEventDestroy(lastUse); }
 };
 

@@ -15,6 +15,13 @@ struct HprtBvh {
 };
 
 struct HprtKdTree { hprt::KdTree tree; };
+// Two-level kd-trees (pbrtObjectInstance, core/api.cpp:1794-1819): the top-level tree over the top-level items, and per object
+// definition its own tree — none (no nodes) for an object of one primitive, which is wrapped as it is (:1798)
+struct HprtKdInst {
+    hprt::KdTree top;
+    std::vector<hprt::KdTree> objects;        // objects[o].nPrims: the object's primitives, tree or not
+    std::vector<int32_t> instanceObject;      // per instance, its object definition
+};
 struct HprtRbsp { hprt::RbspTree tree; };
 struct HprtRbspKd { hprt::RbspTree tree; };     // built with RbspParams::kdAware
 struct HprtBspPaper { hprt::BspPaperTree tree; };

@@ -609,6 +609,11 @@ int BuildSceneLayout(const HprtSceneDesc &d, SceneLayout *out) {
     out->nPrims = w.primBase.back();
     out->topOrder.assign(d.prim_order, d.prim_order + d.n_prims);
     out->instanced = d.n_instances != 0;
+    for (uint32_t k = 0; k < d.n_objects; ++k) {
+        out->objectOrder.emplace_back(d.objects[k].prim_order, d.objects[k].prim_order + d.objects[k].n_prims);
+        out->objectPrimBase.push_back(w.primBase[1 + (size_t)k]);
+    }
+    for (uint32_t i = 0; i < d.n_instances; ++i) out->instanceObject.push_back(d.instances[i].object);
     for (int (*stage)(Work &) : {LayoutShapes, LayoutPrimitives, LayoutMaterials, LayoutTextures, LayoutLights, LayoutEnvLights,
                                  LayoutLightDistribution, LayoutPairs, LayoutWide, LayoutInstances})
         if (int rc = stage(w)) return rc;

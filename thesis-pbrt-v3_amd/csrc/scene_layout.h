@@ -35,6 +35,11 @@ struct SceneLayout {
     int voxN[3] = {1, 1, 1};
     uint32_t nPrims = 0;                           // over all aggregates
     std::vector<uint32_t> topOrder;                // the top level's prim_order
+    // per object definition: its prim_order and where its ordered primitives start in `tris` (a tree over an object's
+    // creation-order primitives is mapped through them, as a top-level tree is through topOrder)
+    std::vector<std::vector<uint32_t>> objectOrder;
+    std::vector<uint32_t> objectPrimBase;
+    std::vector<int32_t> instanceObject;           // per instance, its object definition
     bool instanced = false, hasSubstrateBin = false;
 };
 
