@@ -240,6 +240,38 @@ int hprt_rbspkd_copy(const HprtRbspKd *t, void *nodes8, uint32_t *prim_indices, 
 void hprt_rbspkd_destroy(HprtRbspKd *t);
 
 /* ------------------------------------------------------------------------ */
+/* Device-assisted builds of the two RBSP trees (opt-in).  They stand in    */
+/* for the same RBSP::buildTree / RBSPKd::buildTree and return the same     */
+/* bytes as hprt_rbsp_build / hprt_rbspkd_build: the tree logic (sorts, the */
+/* first-minimum scan, leaf tests, the winner's cut, classification) stays  */
+/* on the host; what moves to the GPU is the costing of a node's split      */
+/* candidates (KDOPCut + KDOPSurfaceArea of accelerators/kDOPMesh.h and the */
+/* cost formulas of rbsp.cpp:262-283 / rbspKd.cpp:283-318), one candidate   */
+/* per lane, for nodes with at least min_candidates candidates.  A          */
+/* candidate whose half-meshes outgrow the kernel's fixed capacity is       */
+/* costed again on the host.  Same handles: info, copy, attach and the      */
+/* walks are unchanged.  Refusals are those of the host entries; without a  */
+/* HIP device: HPRT_E_NO_DEVICE and *out stays NULL.                        */
+/* ------------------------------------------------------------------------ */
+typedef struct HprtBuildDeviceOpts {
+    int device;               /* HIP device ordinal */
+    uint32_t min_candidates;  /* nodes with fewer candidates are costed on the host; 0 = default */
+    uint32_t max_edges;       /* edges per half-mesh on the device; 0 = default (the compiled capacity); may only lower it */
+} HprtBuildDeviceOpts;
+typedef struct HprtBuildDeviceStats {
+    uint64_t nodes_device, candidates_device, candidates_recosted_on_host, nodes_host;   /* nodes_host: costed nodes that took the host path */
+    double seconds_device;    /* wall time of the device costing calls, staging and repair included */
+} HprtBuildDeviceStats;
+/* opts NULL: device 0 and the defaults; stats may be NULL */
+int hprt_rbsp_build_device(const HprtModel *m, const HprtRbspParams *params, const HprtBuildDeviceOpts *opts, HprtBuildDeviceStats *stats, HprtRbsp **out);
+int hprt_rbsp_build_from_triangles_device(size_t n_tris, const float *p9, const HprtRbspParams *params, const HprtBuildDeviceOpts *opts,
+                                          HprtBuildDeviceStats *stats, HprtRbsp **out);
+int hprt_rbspkd_build_device(const HprtModel *m, const HprtRbspKdParams *params, const HprtBuildDeviceOpts *opts, HprtBuildDeviceStats *stats,
+                             HprtRbspKd **out);
+int hprt_rbspkd_build_from_triangles_device(size_t n_tris, const float *p9, const HprtRbspKdParams *params, const HprtBuildDeviceOpts *opts,
+                                            HprtBuildDeviceStats *stats, HprtRbspKd **out);
+
+/* ------------------------------------------------------------------------ */
 /* General BSP tree (Accelerator "bsppaper").  Stands in for                */
 /* BSPPaper::buildTree (accelerators/bspPaper.cpp:34-305), the BSP tree of  */
 /* Ize, Wald and Parker (2008): split planes are the three axis planes and, */

@@ -129,6 +129,31 @@ class RbspKdParams(C.Structure):
                 ("max_depth", C.c_int), ("n_directions", C.c_int), ("threads", C.c_int)]
 
 
+class BuildDeviceOpts(C.Structure):
+    """HprtBuildDeviceOpts: the device-assisted RBSP / RBSPKd build (0 = default)."""
+    _fields_ = [("device", C.c_int), ("min_candidates", C.c_uint32), ("max_edges", C.c_uint32)]
+
+
+class BuildDeviceStats(C.Structure):
+    """HprtBuildDeviceStats"""
+    _fields_ = [("nodes_device", C.c_uint64), ("candidates_device", C.c_uint64), ("candidates_recosted_on_host", C.c_uint64),
+                ("nodes_host", C.c_uint64), ("seconds_device", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+def _build_tree(prefix, how, head, prm, device, min_candidates, max_edges):
+    """hprt_<prefix>_<how> or, with device not None, hprt_<prefix>_<how>_device: (handle, build stats dict or None)"""
+    h = C.c_void_p()
+    if device is None:
+        _check(getattr(lib, "hprt_%s_%s" % (prefix, how))(*head, prm, C.byref(h)))
+        return h, None
+    opts, st = BuildDeviceOpts(int(device), min_candidates, max_edges), BuildDeviceStats()
+    _check(getattr(lib, "hprt_%s_%s_device" % (prefix, how))(*head, prm, C.byref(opts), C.byref(st), C.byref(h)))
+    return h, st.as_dict()
+
+
 class _Tree:
     """A host tree handle (KdTree, Rbsp, RbspKd, BspPaper, BspPaperKd) over the C calls hprt_<_prefix>_info / _copy / _destroy: info() names the info
     words `_info_keys`; the copy of the RBSP trees takes a direction table as well (M in info)."""
@@ -185,22 +210,24 @@ class RbspKd(_Tree):
     _info_keys = ("nodes", "leaves", "prim_refs", "depth", "M", "kd_interior", "bsp_interior")
 
     def __init__(self, model=None, handle=None, n_directions=None, isect_cost=80, trav_cost=5, kd_trav_cost=1, empty_bonus=0.0, max_prims=1,
-                 max_depth=-1, threads=0):
+                 max_depth=-1, threads=0, device=None, min_candidates=0, max_edges=0, build_stats=None):
+        """device: None builds on the host; a HIP device ordinal costs the split candidates of nodes with at least min_candidates
+        candidates on that GPU (the same tree, byte for byte) and leaves HprtBuildDeviceStats as a dict in self.build_stats."""
+        self.build_stats = build_stats
         if handle is None:
-            handle = C.c_void_p()
             prm = None if n_directions is None else C.byref(RbspKdParams(isect_cost, trav_cost, kd_trav_cost, empty_bonus, max_prims, max_depth,
                                                                            n_directions, threads))
-            _check(lib.hprt_rbspkd_build(model._h, prm, C.byref(handle)))
+            handle, self.build_stats = _build_tree("rbspkd", "build", (model._h,), prm, device, min_candidates, max_edges)
         self._h = handle
 
     @staticmethod
-    def from_triangles(p9, n_directions=3, isect_cost=80, trav_cost=5, kd_trav_cost=1, empty_bonus=0.0, max_prims=1, max_depth=-1, threads=0):
-        """p9: [n, 9] (or [n, 3, 3]) float32 world-space triangle vertices in creation order."""
+    def from_triangles(p9, n_directions=3, isect_cost=80, trav_cost=5, kd_trav_cost=1, empty_bonus=0.0, max_prims=1, max_depth=-1, threads=0,
+                       device=None, min_candidates=0, max_edges=0):
+        """p9: [n, 9] (or [n, 3, 3]) float32 world-space triangle vertices in creation order.  device: as in the constructor."""
         p9 = np.ascontiguousarray(p9, np.float32).reshape(-1, 9)
-        h = C.c_void_p()
         prm = RbspKdParams(isect_cost, trav_cost, kd_trav_cost, empty_bonus, max_prims, max_depth, n_directions, threads)
-        _check(lib.hprt_rbspkd_build_from_triangles(p9.shape[0], _ptr(p9), C.byref(prm), C.byref(h)))
-        return RbspKd(handle=h)
+        h, st = _build_tree("rbspkd", "build_from_triangles", (p9.shape[0], _ptr(p9)), C.byref(prm), device, min_candidates, max_edges)
+        return RbspKd(handle=h, build_stats=st)
 
     @staticmethod
     def from_arrays(nodes, prim_indices, n_prims, bounds, n_directions=3):
@@ -301,6 +328,10 @@ def _load():
         "hprt_rbspkd_copy": (C.c_int, [vp, vp, vp, vp]),
         "hprt_rbspkd_destroy": (None, [vp]),
         "hprt_scene_attach_rbspkd": (C.c_int, [vp, vp]),
+        "hprt_rbsp_build_device": (C.c_int, [vp, vp, vp, vp, P(vp)]),
+        "hprt_rbsp_build_from_triangles_device": (C.c_int, [sz, vp, vp, vp, vp, P(vp)]),
+        "hprt_rbspkd_build_device": (C.c_int, [vp, vp, vp, vp, P(vp)]),
+        "hprt_rbspkd_build_from_triangles_device": (C.c_int, [sz, vp, vp, vp, vp, P(vp)]),
         "hprt_bsppaper_build": (C.c_int, [vp, vp, P(vp)]),
         "hprt_bsppaper_build_from_triangles": (C.c_int, [sz, vp, vp, P(vp)]),
         "hprt_bsppaper_info": (C.c_int, [vp, P(u32)]),
@@ -565,21 +596,23 @@ class Rbsp(_Tree):
     _info_keys = ("nodes", "leaves", "prim_refs", "depth", "M")
 
     def __init__(self, model=None, handle=None, n_directions=None, isect_cost=80, trav_cost=5, empty_bonus=0.0, max_prims=1, max_depth=-1,
-                 threads=0):
+                 threads=0, device=None, min_candidates=0, max_edges=0, build_stats=None):
+        """device: None builds on the host; a HIP device ordinal costs the split candidates of nodes with at least min_candidates
+        candidates on that GPU (the same tree, byte for byte) and leaves HprtBuildDeviceStats as a dict in self.build_stats."""
+        self.build_stats = build_stats
         if handle is None:
-            handle = C.c_void_p()
             prm = None if n_directions is None else C.byref(_rbsp_params(n_directions, isect_cost, trav_cost, empty_bonus, max_prims, max_depth, threads))
-            _check(lib.hprt_rbsp_build(model._h, prm, C.byref(handle)))
+            handle, self.build_stats = _build_tree("rbsp", "build", (model._h,), prm, device, min_candidates, max_edges)
         self._h = handle
 
     @staticmethod
-    def from_triangles(p9, n_directions=3, isect_cost=80, trav_cost=5, empty_bonus=0.0, max_prims=1, max_depth=-1, threads=0):
-        """p9: [n, 9] (or [n, 3, 3]) float32 world-space triangle vertices in creation order."""
+    def from_triangles(p9, n_directions=3, isect_cost=80, trav_cost=5, empty_bonus=0.0, max_prims=1, max_depth=-1, threads=0,
+                       device=None, min_candidates=0, max_edges=0):
+        """p9: [n, 9] (or [n, 3, 3]) float32 world-space triangle vertices in creation order.  device: as in the constructor."""
         p9 = np.ascontiguousarray(p9, np.float32).reshape(-1, 9)
-        h = C.c_void_p()
         prm = _rbsp_params(n_directions, isect_cost, trav_cost, empty_bonus, max_prims, max_depth, threads)
-        _check(lib.hprt_rbsp_build_from_triangles(p9.shape[0], _ptr(p9), C.byref(prm), C.byref(h)))
-        return Rbsp(handle=h)
+        h, st = _build_tree("rbsp", "build_from_triangles", (p9.shape[0], _ptr(p9)), C.byref(prm), device, min_candidates, max_edges)
+        return Rbsp(handle=h, build_stats=st)
 
     @staticmethod
     def from_arrays(nodes, prim_indices, n_prims, bounds, n_directions=3):

@@ -18,6 +18,7 @@
 #include "bvh_builder.h"
 #include "halton_tables.h"
 #include "hprt_internal.h"
+#include "kdop_cost_device.h"
 #include "scene_model.h"
 #include "hprt_math.h"
 #include "wide_bvh.h"
@@ -69,11 +70,27 @@ void RbspTriangleBounds(size_t n, const float *p9, std::vector<float> *lo, std::
         }
 }
 // Handle HprtRbsp with Params HprtRbspParams, or HprtRbspKd (the kd-aware cost model) with HprtRbspKdParams; params NULL keeps p
+// What a build does besides the host build (NULL: nothing).  device: the device-assisted build (hprt_*_build*_device) — nodes of
+// at least min_candidates candidates are costed by k_kdopcost.  sink: the diagnostics hook hprt_debug_rbsp_root_mesh — the first
+// maxNodes costed nodes are handed to the sink with the costs the builder's own code gave them.
+typedef void (*RbspNodeSink)(void *user, uint32_t node, const void *edges, uint32_t n_edges, const void *scalars, const void *cands, size_t n,
+                             const float *costs, const float *costs_fixed);
+struct RbspHook {
+    bool device = false;
+    const HprtBuildDeviceOpts *opts = nullptr;
+    HprtBuildDeviceStats *stats = nullptr;
+    RbspNodeSink sink = nullptr; void *user = nullptr; uint32_t maxNodes = 0;
+};
+// Below this many candidates a node of a device-assisted build stays on the host: a launch and two copies cost more than the
+// candidates do
+constexpr uint32_t kDeviceMinCandidates = 1024;
+
 template <typename Handle, typename Params>
 int BuildRbsp(size_t n, const float *lo, const float *hi, const float *tri9, const uint8_t *isTri, const Params *params, RbspParams p,
-                     Handle **out) {
+                     Handle **out, const RbspHook *hook = nullptr) {
     constexpr bool kdAware = std::is_same<Handle, HprtRbspKd>::value;
     p.kdAware = kdAware;
+    *out = nullptr;
     if (params) {
         p.isectCost = params->isect_cost; p.travCost = params->trav_cost; p.emptyBonus = params->empty_bonus;
         p.maxPrims = params->max_prims; p.maxDepth = params->max_depth; p.nDirections = params->n_directions; p.threads = params->threads;
@@ -82,7 +99,37 @@ int BuildRbsp(size_t n, const float *lo, const float *hi, const float *tri9, con
     if (p.nDirections != 3 && p.nDirections != 7 && p.nDirections != 9 && p.nDirections != 13)
         return SetError(HPRT_E_UNSUPPORTED, "nbDirections " + std::to_string(p.nDirections) + " is not supported (3, 7, 9 or 13)");
     std::unique_ptr<Handle> t(new Handle());
+    struct DeviceGuard { KdopCostDevice *d = nullptr; ~DeviceGuard() { KdopCostDeviceDestroy(d); } } dev;      // freed when the build ends or fails
+    RbspBuildStats bs;
+    int hookRc = HPRT_OK;
+    uint32_t seen = 0;
+    if (hook && hook->device) {
+        if (hook->stats) *hook->stats = HprtBuildDeviceStats{0, 0, 0, 0, 0.0};
+        std::string derr;
+        const int rc = KdopCostDeviceCreate(hook->opts ? hook->opts->device : 0, hook->opts ? hook->opts->max_edges : 0u, &dev.d, &derr);
+        if (rc != HPRT_OK) return SetError(rc, derr);
+        p.costMinCandidates = hook->opts && hook->opts->min_candidates ? hook->opts->min_candidates : kDeviceMinCandidates;
+        p.stats = &bs;
+        p.costFn = [&](const RbspCostRequest &rq, std::string *e) -> int {
+            if (rq.nEdges > KdopCostDeviceCapacity(dev.d)) return 1;      // the whole node on the host
+            hookRc = KdopCostDeviceRun(dev.d, rq.mesh, rq.nEdges, rq.dirs, rq.M, rq.kdAware, rq.sc, rq.cands, rq.n, rq.costs, rq.costsFixed, rq.overflow, e);
+            return hookRc == HPRT_OK ? 0 : -1;
+        };
+    } else if (hook && hook->sink) {
+        p.costMinCandidates = 1;
+        p.costFn = [&](const RbspCostRequest &rq, std::string *) -> int {
+            if (seen >= hook->maxNodes) return 1;
+            memset(rq.overflow, 1, rq.n);          // every candidate "flagged": the builder costs them all with its own code
+            return 0;
+        };
+        p.costDone = [&](const RbspCostRequest &rq) {
+            hook->sink(hook->user, seen++, rq.mesh, rq.nEdges, &rq.sc, rq.cands, rq.n, rq.costs, rq.costsFixed);
+        };
+    }
     const std::string err = BuildRbspTree(n, lo, hi, tri9, isTri, p, &t->tree);
+    if (hook && hook->stats)
+        *hook->stats = HprtBuildDeviceStats{bs.nodesDevice, bs.candidatesDevice, bs.candidatesRecosted, bs.nodesHost, bs.secondsDevice};
+    if (hookRc != HPRT_OK) return SetError(hookRc, err);
     if (!err.empty()) return SetError(HPRT_E_UNSUPPORTED, err);
     if (t->tree.depth > RBSP_TODO_MAX)
         return SetError(HPRT_E_UNSUPPORTED, "RBSP tree of depth " + std::to_string(t->tree.depth) + " is deeper than the device walk's todo list (" +
@@ -92,23 +139,26 @@ int BuildRbsp(size_t n, const float *lo, const float *hi, const float *tri9, con
 }
 // hprt_rbsp_build / hprt_rbspkd_build: the model's primitives and its Accelerator line (dflt); `what` names the tree in messages
 template <typename Handle, typename Params>
-int BuildRbspFromModel(const char *fn, const char *what, const HprtModel *m, const Params *params, const RbspParams &dflt, Handle **out) {
+int BuildRbspFromModel(const char *fn, const char *what, const HprtModel *m, const Params *params, const RbspParams &dflt, Handle **out,
+                       const RbspHook *hook = nullptr) {
+    if (out) *out = nullptr;
     if (!m || !out) return SetError(HPRT_E_INVALID, std::string(fn) + ": null argument");
     if (m->sc.nObjects != 0 || !m->sc.instances.empty())
         return SetError(HPRT_E_UNSUPPORTED, std::string(what) + " trees over object instances are not supported (the scene keeps its BVH)");
     std::vector<float> lo, hi, tri9;
     std::vector<uint8_t> isTri;
     RbspModelPrims(m, &lo, &hi, &tri9, &isTri);
-    return BuildRbsp(lo.size() / 3, lo.data(), hi.data(), tri9.data(), isTri.data(), params, dflt, out);
+    return BuildRbsp(lo.size() / 3, lo.data(), hi.data(), tri9.data(), isTri.data(), params, dflt, out, hook);
 }
 template <typename Handle, typename Params>
-int BuildRbspFromTriangles(const char *fn, size_t n, const float *p9, const Params *params, Handle **out) {
+int BuildRbspFromTriangles(const char *fn, size_t n, const float *p9, const Params *params, Handle **out, const RbspHook *hook = nullptr) {
+    if (out) *out = nullptr;
     if (!out || (n && !p9)) return SetError(HPRT_E_INVALID, std::string(fn) + ": null argument");
     if (n > 0x3fffffffull) return SetError(HPRT_E_UNSUPPORTED, "more than 2^30 primitives");
     std::vector<float> lo, hi;
     RbspTriangleBounds(n, p9, &lo, &hi);
     std::vector<uint8_t> isTri(n, 1);
-    return BuildRbsp(n, lo.data(), hi.data(), p9, isTri.data(), params, RbspParams(), out);
+    return BuildRbsp(n, lo.data(), hi.data(), p9, isTri.data(), params, RbspParams(), out, hook);
 }
 // info[0..4] of either handle; info[5..6] (kd / oblique interior nodes) only for an rbspkd tree
 int RbspInfo(const char *fn, const RbspTree *t, uint32_t *info, bool kdSplit) {
@@ -617,6 +667,25 @@ int hprt_rbspkd_copy(const HprtRbspKd *t, void *nodes8, uint32_t *primIndices, f
     return RbspCopy("hprt_rbspkd_copy", t ? &t->tree : nullptr, nodes8, primIndices, directions);
 } catch (...) { return hprt::HandleException(); }
 void hprt_rbspkd_destroy(HprtRbspKd *t) { delete t; }
+// ---- the device-assisted builds: the same builder with its candidates costed by k_kdopcost (device/kdop_cost.hip) ----
+int hprt_rbsp_build_device(const HprtModel *m, const HprtRbspParams *params, const HprtBuildDeviceOpts *opts, HprtBuildDeviceStats *stats, HprtRbsp **out) try {
+    RbspHook h; h.device = true; h.opts = opts; h.stats = stats;
+    return BuildRbspFromModel("hprt_rbsp_build_device", "RBSP", m, params, m ? m->sc.opt.rbsp : RbspParams(), out, &h);
+} catch (...) { return hprt::HandleException(); }
+int hprt_rbsp_build_from_triangles_device(size_t n, const float *p9, const HprtRbspParams *params, const HprtBuildDeviceOpts *opts, HprtBuildDeviceStats *stats,
+                                          HprtRbsp **out) try {
+    RbspHook h; h.device = true; h.opts = opts; h.stats = stats;
+    return BuildRbspFromTriangles("hprt_rbsp_build_from_triangles_device", n, p9, params, out, &h);
+} catch (...) { return hprt::HandleException(); }
+int hprt_rbspkd_build_device(const HprtModel *m, const HprtRbspKdParams *params, const HprtBuildDeviceOpts *opts, HprtBuildDeviceStats *stats, HprtRbspKd **out) try {
+    RbspHook h; h.device = true; h.opts = opts; h.stats = stats;
+    return BuildRbspFromModel("hprt_rbspkd_build_device", "rbspkd", m, params, m ? m->sc.opt.rbspkd : RbspParams(), out, &h);
+} catch (...) { return hprt::HandleException(); }
+int hprt_rbspkd_build_from_triangles_device(size_t n, const float *p9, const HprtRbspKdParams *params, const HprtBuildDeviceOpts *opts,
+                                            HprtBuildDeviceStats *stats, HprtRbspKd **out) try {
+    RbspHook h; h.device = true; h.opts = opts; h.stats = stats;
+    return BuildRbspFromTriangles("hprt_rbspkd_build_from_triangles_device", n, p9, params, out, &h);
+} catch (...) { return hprt::HandleException(); }
 
 // ---- general BSP tree (Accelerator "bsppaper"; helpers above) ----
 int hprt_bsppaper_build(const HprtModel *m, const HprtBspPaperParams *params, HprtBspPaper **out) try {
@@ -741,6 +810,84 @@ __attribute__((visibility("default"))) int hprt_debug_kdtree_from_arrays(size_t 
     if (*bad) return SetError(HPRT_E_INVALID, std::string("malformed tree: ") + bad);
     k.maxDepth = k.depth; k.leaves = CountLeaves(k.nodes, 3u, 3u);
     return FinishKdTree(t.release(), out);
+} catch (...) { return hprt::HandleException(); }
+// Diagnostics hooks of the candidate costing (tests/test_kdop_cost_host.py, tests/test_gpu_kdop_cost.py).
+// hprt_debug_kdop_cost costs a caller's mesh and candidates with impl 0 (the vector code of kdop_mesh.h, RbspCostVector), 1
+// (kdop_cost.h on the host) or 2 (k_kdopcost).  edges: n_edges records of 32 bytes (v1, v2, f1, f2); scalars: kdopcost::Scalars (7
+// words: invTotalSA, emptyBonus, isectCost, traversalCost, kdTraversalCost, nPrimitives, maxEdges); cands: n records of 20 bytes
+// (d, i, nBelow, nAbove, t).  Everything the costing indexes by is checked first: M, n_edges, every face id, every candidate's d,
+// maxEdges (HPRT_E_INVALID).  A mesh of more edges than maxEdges allows is not costed by impl 1 / 2: every candidate is flagged.
+__attribute__((visibility("default"))) int hprt_debug_kdop_cost(const void *edges, uint32_t n_edges, uint32_t M, int kd_aware, const void *scalars,
+                                                                 const void *cands, size_t n, int impl, float *costs, float *costs_fixed,
+                                                                 uint8_t *overflow) try {
+    using namespace kdopcost;
+    if (!scalars || !costs || !costs_fixed || !overflow || (n && !cands) || (n_edges && !edges))
+        return SetError(HPRT_E_INVALID, "hprt_debug_kdop_cost: null argument");
+    if (M != 3 && M != 7 && M != 9 && M != 13) return SetError(HPRT_E_INVALID, "hprt_debug_kdop_cost: M is not 3, 7, 9 or 13");
+    if (impl < 0 || impl > 2) return SetError(HPRT_E_INVALID, "hprt_debug_kdop_cost: impl is not 0, 1 or 2");
+    if (n_edges > 65536u || n > 0xffffffffull) return SetError(HPRT_E_INVALID, "hprt_debug_kdop_cost: a size that cannot be real");
+    Scalars sc;
+    memcpy(&sc, scalars, sizeof(sc));
+    if (sc.maxEdges > KDOP_MAX_EDGES) return SetError(HPRT_E_INVALID, "hprt_debug_kdop_cost: maxEdges may only lower the compiled capacity");
+    const uint32_t cap = sc.maxEdges ? sc.maxEdges : (uint32_t)KDOP_MAX_EDGES;
+    std::vector<Edge> mesh(n_edges);
+    if (n_edges) memcpy(static_cast<void *>(mesh.data()), edges, (size_t)n_edges * sizeof(Edge));
+    for (const Edge &e : mesh)
+        if (e.f1 >= 2 * M || e.f2 >= 2 * M) return SetError(HPRT_E_INVALID, "hprt_debug_kdop_cost: a face id is not below 2 M");
+    std::vector<Cand> cs(n);
+    if (n) memcpy(static_cast<void *>(cs.data()), cands, n * sizeof(Cand));
+    for (const Cand &c : cs)
+        if (c.d >= M) return SetError(HPRT_E_INVALID, "hprt_debug_kdop_cost: a candidate's direction is not below M");
+    std::vector<float> dirs;
+    RbspDirections(M, &dirs);
+    for (size_t k = 0; k < n; ++k) { costs[k] = 0; costs_fixed[k] = 0; overflow[k] = 1; }
+    if (impl == 0) {
+        RbspCostRequest rq{mesh.data(), n_edges, dirs.data(), M, kd_aware != 0, sc, cs.data(), n, costs, costs_fixed, overflow};
+        RbspCostVector(rq);
+        return HPRT_OK;
+    }
+    if (n_edges > cap) return HPRT_OK;      // every candidate flagged
+    if (impl == 1) {
+        std::vector<Q> words(kStoreWords);
+        uint8_t list[KDOP_MAX_FACE_EDGES];
+        Store st;
+        st.left = words.data(); st.right = words.data() + 2 * KDOP_MAX_EDGES; st.fv = words.data() + 4 * KDOP_MAX_EDGES; st.stride = 1;
+        st.flist = list; st.fstride = 1; st.cap = cap;
+        for (size_t k = 0; k < n; ++k) CostCandidate(mesh.data(), n_edges, dirs.data(), M, kd_aware != 0, sc, cs[k], st, &costs[k], &costs_fixed[k], &overflow[k]);
+        return HPRT_OK;
+    }
+    struct DeviceGuard { KdopCostDevice *d = nullptr; ~DeviceGuard() { KdopCostDeviceDestroy(d); } } dev;
+    std::string err;
+    int rc = KdopCostDeviceCreate(0, sc.maxEdges, &dev.d, &err);
+    if (rc != HPRT_OK) return SetError(rc, err);
+    rc = KdopCostDeviceRun(dev.d, mesh.data(), n_edges, dirs.data(), M, kd_aware != 0, sc, cs.data(), n, costs, costs_fixed, overflow, &err);
+    if (rc != HPRT_OK) return SetError(rc, err);
+    if (!kd_aware) for (size_t k = 0; k < n; ++k) costs_fixed[k] = 0;
+    return HPRT_OK;
+} catch (...) { return hprt::HandleException(); }
+// The mesh, the scalars and the candidates of the first max_nodes nodes a build costs, in build order, each with the costs the
+// builder's own code (costRange) gave them; the meshes are the builder's, reoriented as its SurfaceArea calls left them.  m != NULL:
+// the model's primitives (hprt_rbsp_build / hprt_rbspkd_build); else n triangles.  params: HprtRbspKdParams for both trees
+// (kd_trav_cost is not read when kd_aware is 0).  sink(user, node, edges, n_edges, scalars, cands, n, costs, costs_fixed):
+// costs_fixed is NULL unless kd_aware; the pointers are valid during the call only.
+__attribute__((visibility("default"))) int hprt_debug_rbsp_root_mesh(const HprtModel *m, size_t n, const float *p9, int kd_aware, const HprtRbspKdParams *params,
+                                                                      uint32_t max_nodes, RbspNodeSink sink, void *user) try {
+    if (!params || !sink) return SetError(HPRT_E_INVALID, "hprt_debug_rbsp_root_mesh: null argument");
+    RbspHook h; h.sink = sink; h.user = user; h.maxNodes = max_nodes;
+    int rc;
+    if (kd_aware) {
+        HprtRbspKd *t = nullptr;
+        rc = m ? BuildRbspFromModel("hprt_debug_rbsp_root_mesh", "rbspkd", m, params, RbspParams(), &t, &h)
+               : BuildRbspFromTriangles("hprt_debug_rbsp_root_mesh", n, p9, params, &t, &h);
+        delete t;
+    } else {
+        const HprtRbspParams q{params->isect_cost, params->trav_cost, params->empty_bonus, params->max_prims, params->max_depth, params->n_directions, params->threads};
+        HprtRbsp *t = nullptr;
+        rc = m ? BuildRbspFromModel("hprt_debug_rbsp_root_mesh", "RBSP", m, &q, RbspParams(), &t, &h)
+               : BuildRbspFromTriangles("hprt_debug_rbsp_root_mesh", n, p9, &q, &t, &h);
+        delete t;
+    }
+    return rc;
 } catch (...) { return hprt::HandleException(); }
 __attribute__((visibility("default"))) int hprt_debug_rbsp_from_arrays(uint32_t M, size_t n_nodes, const uint32_t *nodes8, size_t n_idx, const uint32_t *idx,
                                                                         uint32_t n_prims, const float *bounds6, HprtRbsp **out) try {

@@ -8,6 +8,7 @@
 // The winner's two halves are then cut and measured once more, exactly as the scan left them.
 #include "rbsp_builder.h"
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -30,7 +31,8 @@ struct BuildNode {                                                  // RBSPBuild
     Mesh mesh; float meshArea;
     size_t primNums; uint32_t parentNum;                            // primNums: offset into `prims`
 };
-struct Cand { uint32_t d, i, nBelow, nAbove; float t; };
+using Cand = kdopcost::Cand;                                       // {d, i, nBelow, nAbove, t}
+static_assert(sizeof(KEdge) == sizeof(kdopcost::Edge) && sizeof(KEdge) == 32, "kdop_cost.h restates KEdge");
 
 // Log2Int(int64_t) (core/pbrt.h:345-362): 63 - clz
 inline int Log2Int64(uint64_t v) { return v ? 63 - __builtin_clzll(v) : -1; }
@@ -146,6 +148,7 @@ std::string BuildRbspTree(size_t n, const float *bmin, const float *bmax, const 
     };
 
     std::vector<Cand> cands;
+    std::vector<uint8_t> overflow;              // per candidate: the costing hook could not cost it (RbspParams::costFn)
     std::vector<float> costs, costsFixed;       // costsFixed: RBSPKd's traversalCost + C_isect of the oblique candidates
     const float BSP_ALPHA = 0.1;                 // RBSPKd::buildTree's `const Float`
     const uint32_t kdTraversalCost = (uint32_t)p.kdTravCost;
@@ -207,7 +210,36 @@ std::string BuildRbspTree(size_t n, const float *bmin, const float *bmax, const 
                 }
             }
         };
-        if (nThreads > 1 && cands.size() >= kParallelCandidates) {
+        // the costing hook (RbspParams::costFn): the node's candidates costed elsewhere, the flagged ones repaired here
+        bool costed = false;
+        if (p.costFn && !cands.empty() && cands.size() >= p.costMinCandidates) {
+            overflow.assign(cands.size(), 0);
+            RbspCostRequest rq;
+            rq.mesh = reinterpret_cast<const kdopcost::Edge *>(cur.mesh.data()); rq.nEdges = (uint32_t)cur.mesh.size();
+            rq.dirs = dirs; rq.M = M; rq.kdAware = p.kdAware;
+            rq.sc = kdopcost::Scalars{invTotalSA, emptyBonus, isectCost, traversalCost, kdTraversalCost, cur.nPrimitives, 0u};
+            rq.cands = cands.data(); rq.n = cands.size();
+            rq.costs = costs.data(); rq.costsFixed = p.kdAware ? costsFixed.data() : nullptr; rq.overflow = overflow.data();
+            std::string err;
+            const auto t0 = std::chrono::steady_clock::now();
+            const int rc = p.costFn(rq, &err);
+            if (rc < 0) return err.empty() ? std::string("the costing hook failed") : err;
+            if (rc == 0) {
+                costed = true;
+                uint64_t redo = 0;
+                for (size_t k = 0; k < cands.size(); ++k)
+                    if (overflow[k]) { costRange(k, k + 1, scratch[0]); ++redo; }
+                if (p.stats) {
+                    p.stats->secondsDevice += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+                    ++p.stats->nodesDevice; p.stats->candidatesDevice += cands.size() - redo; p.stats->candidatesRecosted += redo;
+                }
+                if (p.costDone) p.costDone(rq);
+            }
+        }
+        if (!costed && p.stats) ++p.stats->nodesHost;
+        if (costed) {
+            // (costs[] is complete)
+        } else if (nThreads > 1 && cands.size() >= kParallelCandidates) {
             const size_t chunk = (cands.size() + nThreads - 1) / nThreads;
             pool.clear();
             for (int w = 1; w < nThreads; ++w) {
@@ -293,6 +325,36 @@ std::string BuildRbspTree(size_t n, const float *bmin, const float *bmax, const 
     (void)CheckRbspTree(t, &depth);
     t.depth = depth;
     return "";
+}
+
+void RbspCostVector(const RbspCostRequest &rq) {
+    // costRange of BuildRbspTree over a caller's mesh: the same calls and the same formulas, in the same order
+    Mesh mesh(rq.nEdges);
+    if (rq.nEdges) std::memcpy(static_cast<void *>(mesh.data()), rq.mesh, (size_t)rq.nEdges * sizeof(KEdge));
+    Scratch s;
+    const uint32_t M = rq.M, isectCost = rq.sc.isectCost, traversalCost = rq.sc.traversalCost, kdTraversalCost = rq.sc.kdTraversalCost;
+    const float invTotalSA = rq.sc.invTotalSA, emptyBonus = rq.sc.emptyBonus;
+    const float BSP_ALPHA = 0.1;
+    for (size_t k = 0; k < rq.n; ++k) {
+        const Cand &c = rq.cands[k];
+        Cut(mesh, M, c.t, rq.dirs + 3 * c.d, c.d, s);
+        const float areaBelow = SurfaceArea(s.left, rq.dirs, M, s);
+        const float areaAbove = SurfaceArea(s.right, rq.dirs, M, s);
+        const float pBelow = areaBelow * invTotalSA;
+        const float pAbove = areaAbove * invTotalSA;
+        const float eb = (c.nAbove == 0 || c.nBelow == 0) ? emptyBonus : 0;
+        if (rq.costsFixed) rq.costsFixed[k] = 0;
+        if (!rq.kdAware) {
+            rq.costs[k] = (float)traversalCost + (float)isectCost * (1 - eb) * (pBelow * (float)c.nBelow + pAbove * (float)c.nAbove);
+        } else if (c.d < 3) {
+            rq.costs[k] = (float)kdTraversalCost + (float)isectCost * (1 - eb) * (pBelow * (float)c.nBelow + pAbove * (float)c.nAbove);
+        } else {
+            const float costIntersection = (float)isectCost * (1 - eb) * (pBelow * (float)c.nBelow + pAbove * (float)c.nAbove);
+            if (rq.costsFixed) rq.costsFixed[k] = (float)traversalCost + costIntersection;
+            rq.costs[k] = BSP_ALPHA * (float)isectCost * (float)(rq.sc.nPrimitives - 1) + (float)kdTraversalCost + costIntersection;
+        }
+        rq.overflow[k] = 0;
+    }
 }
 
 void RbspInteriorCounts(const RbspTree &t, uint32_t *kd, uint32_t *bsp) {

@@ -6,9 +6,11 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <functional>
 #include <string>
 #include <vector>
 #include "bsp_tree.h"
+#include "kdop_cost.h"
 
 namespace hprt {
 
@@ -23,6 +25,18 @@ enum : uint32_t { RBSP_TODO_MAX = 64u, RBSP_MAX_DIRECTIONS = 13u };
 inline uint32_t RbspBitOffset(uint32_t M) { return 32u - (uint32_t)__builtin_clz(M); }   // getBitOffset: log2_fast(M + 1)
 inline uint32_t RbspBitMask(uint32_t M) { return (1u << RbspBitOffset(M)) - 1u; }
 
+// One node's candidates, as costFn sees them (kdop_cost.h: Edge is kdop::KEdge field for field, Cand the builder's candidate)
+struct RbspCostRequest {
+    const kdopcost::Edge *mesh; uint32_t nEdges;
+    const float *dirs; uint32_t M;
+    bool kdAware;
+    kdopcost::Scalars sc;
+    const kdopcost::Cand *cands; size_t n;
+    float *costs, *costsFixed;            // costsFixed: NULL unless kdAware
+    uint8_t *overflow;
+};
+struct RbspBuildStats { uint64_t nodesDevice = 0, candidatesDevice = 0, candidatesRecosted = 0, nodesHost = 0; double secondsDevice = 0; };
+
 struct RbspParams {
     int isectCost = 80, travCost = 5;     // "intersectcost", "traversalcost"
     float emptyBonus = 0.f;               // "emptybonus"
@@ -34,6 +48,16 @@ struct RbspParams {
     // chosen, and travCost + C_isect for a second minimum that only the leaf tests read.
     bool kdAware = false;
     int kdTravCost = 1;                   // "kdtraversalcost"
+    // Optional costing hook (the device-assisted build, hprt_rbsp_build_device): a node with at least costMinCandidates
+    // candidates is handed to costFn instead of the thread pool.  It fills costs / costsFixed / overflow for every candidate
+    // and returns 0; the builder then re-costs the candidates flagged in overflow with costRange's own code.  1: the hook
+    // declines the node (a mesh beyond its capacity) and the node takes the host path; < 0: the build fails with *err.
+    // Smaller nodes, and all nodes when costFn is empty, take the host path.  The scan over costs[] is the same either way.
+    std::function<int(const RbspCostRequest &, std::string *err)> costFn;
+    uint32_t costMinCandidates = 1024;    // (kdop::kParallelCandidates)
+    RbspBuildStats *stats = nullptr;      // filled when costFn is set
+    // Diagnostics: called for a node costFn has handled, after the repair, with the costs the scan is about to read
+    std::function<void(const RbspCostRequest &)> costDone;
 };
 
 struct RbspTree {
@@ -53,6 +77,9 @@ bool RbspDirections(uint32_t M, std::vector<float> *dirs3);
 // Returns "" on success, else what went wrong (unsupported M, a tree outside the reference's primitive buffer).
 std::string BuildRbspTree(size_t n, const float *bmin, const float *bmax, const float *tri9, const uint8_t *isTri, const RbspParams &p,
                           RbspTree *out);
+// The candidates of rq costed with the vector code of kdop_mesh.h (Cut + SurfaceArea) and costRange's formulas, on the calling
+// thread: what the diagnostics hook hprt_debug_kdop_cost calls impl 0.  overflow is cleared.
+void RbspCostVector(const RbspCostRequest &rq);
 // The interior nodes of a tree by kind: axis directions (kd, direction < 3) and oblique ones (bsp).
 void RbspInteriorCounts(const RbspTree &t, uint32_t *kd, uint32_t *bsp);
 // Structural check of a tree handed to the device: child offsets, leaf index ranges, primitive numbers, depth.

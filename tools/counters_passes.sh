@@ -15,7 +15,9 @@ mkdir -p $OUT
 run() { # name, rocprof flags
   n=$1; shift
   timeout -k 10 500 rocprofv3 --kernel-trace "$@" --output-format csv -d $OUT/$n -- python3 $R/bench.py --profile-step --workload $W $EXTRA > $OUT/$n.log 2>&1
-  echo "$W $n rc=$? $(grep -h profile_step $OUT/$n.log | cut -c1-120)"
+  rc=$?
+  echo "$W $n rc=$rc $(grep -h profile_step $OUT/$n.log | cut -c1-120)"
+  return $rc      # a pass that failed or ran into its time limit ends the chain below: nothing more is started on the GPU
 }
 EXTRA="$*"
 run stats --stats &&
