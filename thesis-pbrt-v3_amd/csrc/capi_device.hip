@@ -253,6 +253,15 @@ int hprt_scene_create(const HprtSceneDesc *d, int device, HprtScene **out) try {
 // Diagnostics hook (not part of include/hprt.h): 1 when plain renders of this scene take the leaf-exact wide walk (k_walk4), else 0: the
 // binary walk, or an attached tree's walk (callers test the value for truth: "is it k_walk4")
 __attribute__((visibility("default"))) int hprt_debug_scene_walk(HprtScene *s) { return s && s->walk == HprtScene::Walk::Bvh && hprt::WideWalkInUse(s->dev) ? 1 : 0; }
+// Diagnostics hook (not part of include/hprt.h; tests/test_gpu_shade_chain.py): on != 0 starts counting (from zero) the vertices deferred to the
+// generic bin and the vertices shaded again by a retry pass; out2, if given, receives {deferred, retried} so far.
+__attribute__((visibility("default"))) int hprt_debug_shade_counts(HprtScene *s, int on, uint64_t *out2) {
+    if (!s) return HPRT_E_INVALID;
+    if (out2) { out2[0] = s->shadeDeferred; out2[1] = s->shadeRetried; }
+    if (on && !s->shadeCountsOn) s->shadeDeferred = s->shadeRetried = 0;
+    s->shadeCountsOn = on != 0;
+    return HPRT_OK;
+}
 __attribute__((visibility("default"))) int hprt_debug_poison_workspace(HprtScene *s, int byte) { if (!s) return HPRT_E_INVALID; s->poisonByte = byte < 0 ? -1 : (byte & 255); return HPRT_OK; }
 // Diagnostics hook (not part of include/hprt.h): the first batch of the next hprt_render copies the rays that bounce `bounce` queues
 // (kind 0: the path segments entering bounce + 1, 1: its shadow rays, 2: its BSDF-sampled light rays) into d_out7 ([7][cap] planes:
@@ -802,11 +811,16 @@ int RunBatch(HprtScene *s, hipStream_t st, const RenderParams &rp, const Workspa
             LaunchShade(st, mode, s->dev, rp, in, w.hit, active, s0, out, w.vs, cur, bins, w.Lfinal, bounce == 0);
         }
         HIP_TRY(hipMemcpyAsync(s->hostCounts + 4096, cur.nextCount, 256 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        if (s->shadeCountsOn) {      // (tests only) bin 2 after the deferrals and as binned
+            HIP_TRY(hipMemcpyAsync(s->hostCounts + 12, bins.count + 2 * BIN_STRIDE, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(s->hostCounts + 13, bins.count + 5 * BIN_STRIDE, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        }
         if (s->dev.voxSlot) {      // on-demand SpatialLightDistribution: vertices whose voxel had no distribution yet wait in the retry lists
             HIP_TRY(hipMemcpyAsync(s->hostCounts + 16, bins.count + 6 * BIN_STRIDE, 2 * BIN_STRIDE * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
             HIP_TRY(hipMemcpyAsync(s->hostCounts + 15, s->dev.voxRequestCount, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
             HIP_TRY(hipStreamSynchronize(st));
             const uint32_t nRetry[2] = {s->hostCounts[16], s->hostCounts[16 + BIN_STRIDE]}, nReq = s->hostCounts[15];
+            if (s->shadeCountsOn) s->shadeRetried += (uint64_t)nRetry[0] + nRetry[1];
             if (nRetry[0] + nRetry[1] > 0) {
                 if ((uint64_t)s->voxRowsUsed + nReq > s->voxRows)
                     return SetError(HPRT_E_UNSUPPORTED, "spatial light distribution: the paths touch more voxels than the row pool holds (" + std::to_string(s->voxRows) +
@@ -821,6 +835,7 @@ int RunBatch(HprtScene *s, hipStream_t st, const RenderParams &rp, const Workspa
             }
         }
         HIP_TRY(hipStreamSynchronize(st));
+        if (s->shadeCountsOn) s->shadeDeferred += s->hostCounts[12] - s->hostCounts[13];
         const uint32_t nNext = s->hostCounts[4096], nShadow = s->hostCounts[4096 + 64], nMis = s->hostCounts[4096 + 128], nResolve = s->hostCounts[4096 + 192];
         if (s->capture.out7 && s->capture.bounce == bounce && s0 == 0) {      // diagnostics (hprt_debug_capture_rays)
             const uint32_t *cq = s->capture.kind == 0 ? cur.next : s->capture.kind == 1 ? cur.shadow : cur.mis;
@@ -864,10 +879,12 @@ int RunBatch(HprtScene *s, hipStream_t st, const RenderParams &rp, const Workspa
     return HPRT_OK;
 }
 
+// words of s->queues per path: two QueueSets of four index queues, the deferral indices (BinSet::aux) and five bins of 8-byte entries
+constexpr size_t kQueueWordsPerSlot = 8 + 1 + 2 * N_BINS;
 int EnsureWorkspace(HprtScene *s, size_t nSlots, Workspace *ps, QueueSet *qa, QueueSet *qb, BinSet *bins) {
     HIP_TRY(s->planes.alloc(PlaneBytes(nSlots)));
     CarvePlanes(s->planes.as<char>(), nSlots, ps);
-    HIP_TRY(s->queues.alloc(14 * nSlots * sizeof(uint32_t) + 4096));
+    HIP_TRY(s->queues.alloc(kQueueWordsPerSlot * nSlots * sizeof(uint32_t) + 4096));
     HIP_TRY(s->queueCounts.alloc(2048 * sizeof(uint32_t)));
     uint32_t *qbase = s->queues.as<uint32_t>(), *cbase = s->queueCounts.as<uint32_t>();
     QueueSet *qs[2] = {qa, qb};
@@ -877,8 +894,8 @@ int EnsureWorkspace(HprtScene *s, size_t nSlots, Workspace *ps, QueueSet *qa, Qu
         // one counter per 256-byte line: atomics of different queues do not serialise on a shared line
         qs[k]->nextCount = cbase + 256 * k; qs[k]->shadowCount = cbase + 256 * k + 64; qs[k]->misCount = cbase + 256 * k + 128; qs[k]->resolveCount = cbase + 256 * k + 192;
     }
-    for (int k = 0; k < (int)N_BINS; ++k) bins->q[k] = qbase + (8 + k) * nSlots;
-    bins->aux = qbase + 13 * nSlots;
+    bins->aux = qbase + 8 * nSlots;
+    for (int k = 0; k < (int)N_BINS; ++k) bins->q[k] = reinterpret_cast<uint2 *>(qbase + (9 + 2 * k) * nSlots + (nSlots & 1u));      // (8-byte entries, 8-byte aligned)
     bins->count = cbase + 512;
     bins->retry[0] = bins->retry[1] = nullptr;
     if (s->dev.voxSlot) {      // (on-demand voxel tables only)
@@ -906,7 +923,7 @@ int ChooseBatch(HprtScene *s, int32_t sppChunk, uint32_t nPix, uint32_t spp, uin
         size_t freeB = 0, totalB = 0;
         HIP_TRY(hipMemGetInfo(&freeB, &totalB));
         freeB += s->planes.bytes + s->queues.bytes;                 // this scene's previous workspace is reused or released
-        const size_t perPath = kPlaneBytesPerSlot + 14 * sizeof(uint32_t);
+        const size_t perPath = kPlaneBytesPerSlot + kQueueWordsPerSlot * sizeof(uint32_t);
         static const size_t capM = [] { const char *e = getenv("HPRT_BATCH_MPATHS"); return e ? (size_t)atoi(e) : (size_t)256; }();
         const size_t budget = std::min<size_t>(capM << 20, std::max<size_t>(freeB / 2 / perPath, 1ull << 20));
         chunk = std::max<uint32_t>(1u, (uint32_t)(budget / std::max<uint32_t>(nPix, 1u)));
@@ -962,7 +979,7 @@ int hprt_render(HprtScene *s, const HprtRenderDesc *desc, float *d_film_xyzw, vo
     const size_t lallBytes = 3ull * spp * nPix * sizeof(float);
     if (lallBytes > (96ull << 30)) return SetError(HPRT_E_UNSUPPORTED, "per-sample radiance store would exceed 96 GiB; render in several tile ranges");
     // Paths per wavefront batch.  Every launch ends with a tail of half-empty waves and every bounce with a host
-    // read-back, so batches are as large as memory allows: up to 256 M paths (393 B per path of streams and queues = 100 GB
+    // read-back, so batches are as large as memory allows: up to 256 M paths (413 B per path of streams and queues = 111 GB
     // of the 288 GB), less if the device has less free (half of what is free now), and of EQUAL size (1,024 spp of the atrium:
     // two batches of 512 instead of 522 + 502 or, at the old 128 M cap, four of 256: -1 % per frame).  killeroo-simple
     // at 256 spp is one batch of 125 M paths: 6.5 % faster than two batches of 64 M.  (HPRT_BATCH_MPATHS changes the cap.)
@@ -1131,8 +1148,8 @@ int hprt_render(HprtScene *s, const HprtRenderDesc *desc, float *d_film_xyzw, vo
     return HPRT_OK;
 } catch (...) { return hprt::HandleException(); }
 
-// Pays for the coming hprt_render(s, desc, ...) at load time: the wavefront workspace (path streams and queues: ~393 B per path of
-// a batch, 105 GB for a 256 M-path batch) and the per-sample radiance store are allocated now, so that the render itself starts
+// Pays for the coming hprt_render(s, desc, ...) at load time: the wavefront workspace (path streams and queues: ~413 B per path of
+// a batch, 111 GB for a 256 M-path batch) and the per-sample radiance store are allocated now, so that the render itself starts
 // with its first kernel.  (A fresh process gets 100 GB in under a millisecond, but right after another process released as much the
 // driver may spend seconds reclaiming it inside hipMalloc — DESIGN.md §7; a pbrt host renders once and would pay that inside Render().)
 int hprt_scene_reserve(HprtScene *s, const HprtRenderDesc *desc) try {

@@ -1209,4 +1209,19 @@ __attribute__((visibility("default"))) int hprt_debug_wide_build(const void *nod
     return HPRT_OK;
 } catch (...) { return hprt::HandleException(); }
 
+// Diagnostics hook (not part of include/hprt.h; tests/test_shape_inline_host.py): BuildSceneLayout on a description, no device.  Per
+// ordered primitive the tag word of its record and the word beside it (the shape of a triangle or sphere), per shape the flags and the
+// material index of its DevShape.  A null or short array is not written; the counts always are.
+__attribute__((visibility("default"))) int hprt_debug_shape_inline(const HprtSceneDesc *d, uint32_t *tags, uint32_t *prim_shape, size_t prim_cap, size_t *n_prims,
+                                                                    uint32_t *shape_flags, int32_t *shape_material, size_t shape_cap, size_t *n_shapes) try {
+    if (!d || !n_prims || !n_shapes) return SetError(HPRT_E_INVALID, "hprt_debug_shape_inline: null argument");
+    std::vector<uint32_t> t, ps, sf;
+    std::vector<int32_t> smat;
+    if (int rc = LayoutTagsForDebug(*d, &t, &ps, &sf, &smat)) return rc;
+    *n_prims = t.size(); *n_shapes = sf.size();
+    if (tags && prim_shape && prim_cap >= t.size()) { memcpy(tags, t.data(), 4 * t.size()); memcpy(prim_shape, ps.data(), 4 * ps.size()); }
+    if (shape_flags && shape_material && shape_cap >= sf.size()) { memcpy(shape_flags, sf.data(), 4 * sf.size()); memcpy(shape_material, smat.data(), 4 * smat.size()); }
+    return HPRT_OK;
+} catch (...) { return hprt::HandleException(); }
+
 }  // extern "C"

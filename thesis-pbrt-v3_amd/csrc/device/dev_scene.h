@@ -61,9 +61,13 @@ enum : uint32_t { TAG_KIND_MASK = 3u, TAG_SPHERE = 1u, TAG_INSTANCE = 2u, TAG_BO
                   TAG_BIN_SHIFT = 4u, TAG_BIN_MASK = 7u << 4,      // bits 4-6: the primitive's shading bin (BIN_*), decided on the host
                   // an instance primitive whose world-to-instance matrix is affine (last row exactly 0 0 0 1) carries the matrix's 3x3
                   // part in the x, y, z words of its three record words; translation and entry sit in DevScene::topEntry[primitive]
-                  TAG_INST_INLINE = 128u };
+                  TAG_INST_INLINE = 128u,
+                  // a triangle record whose shape's material index fits carries what shading needs of shapes[shape]: the SHAPE_* flags in
+                  // bits 9-13 and the material index in bits 14-31, so that the normals and the material are requested as soon as the
+                  // record is there.  Every reader of a tag masks it; records without the bit are looked up in shapes[] as before.
+                  TAG_SHAPE_INLINE = 256u, TAG_SHAPE_FLAGS_SHIFT = 9u, TAG_MATERIAL_SHIFT = 14u, TAG_MATERIAL_MAX = (1u << 18) - 1u };
 // (tag & TAG_BIN_MASK) << 24 is the bin field of the hit word: k_bin needs nothing but that word
-enum : uint32_t { SHAPE_FLIP = 1u, SHAPE_HAS_N = 2u, SHAPE_HAS_UV = 4u, SHAPE_HAS_S = 8u, SHAPE_REVERSE = 16u };
+enum : uint32_t { SHAPE_FLIP = 1u, SHAPE_HAS_N = 2u, SHAPE_HAS_UV = 4u, SHAPE_HAS_S = 8u, SHAPE_REVERSE = 16u, SHAPE_FLAGS_MASK = 31u };
 
 struct DevShape { int32_t material, areaLight; uint32_t flags; int32_t sphere; };
 struct DevMaterial { int32_t type; float Kd[3]; float Ks[3]; float alpha; int32_t KdTex, KsTex; float orenA, orenB; int32_t oren; float alphaY;

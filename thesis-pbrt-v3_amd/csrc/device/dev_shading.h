@@ -192,7 +192,8 @@ __device__ __forceinline__ void camera_ray_diff(const DevCamera &cam, float fx, 
 // ---------------------------------------------------------------------------
 // Surface interaction
 // ---------------------------------------------------------------------------
-struct DevSI { vec3 p, pErr, wo, n, ns, sdpdu; int32_t shape; };   // ns = shading.n, sdpdu = shading.dpdu
+struct DevSI { vec3 p, pErr, wo, n, ns, sdpdu; int32_t shape; int32_t material; };   // ns = shading.n, sdpdu = shading.dpdu; material: from the primitive's tag, or -1 = shapes[shape].material
+__device__ __forceinline__ int si_material(const DevScene &sc, const DevSI &si) { return si.material >= 0 ? si.material : sc.shapes[si.shape].material; }
 // what image textures additionally need of the interaction: (u,v) and the parametric derivatives
 struct DevTexGeom { vec3 dpdu, dpdv; float u, v; };
 
@@ -205,17 +206,23 @@ __device__ __forceinline__ void set_shading(DevSI *si, vec3 dpdus, vec3 dpdvs, b
 }
 // Triangle::Intersect fill part, shapes/triangle.cpp:294-425.  The degenerate
 // (bogus) case was rejected during traversal via TAG_BOGUS.
-__device__ __forceinline__ void fill_triangle(const DevScene &sc, uint32_t prim, float b0, float b1, float b2, vec3 rayD, DevSI *si,
-                                              DevTexGeom *tg = nullptr) {
-    const float4 v0 = sc.tris[3 * prim], v1 = sc.tris[3 * prim + 1], v2 = sc.tris[3 * prim + 2];
+// v0, v1, v2: the primitive's record.  A tag with TAG_SHAPE_INLINE carries the shape's flags and material (dev_scene.h): the normals and
+// the material are then requested as soon as the record is there, without the round trip through shapes[].
+// (inlineTag false reads shapes[] and gives the same flags: it exists only so that the callers outside k_shade — k_resolve and the area-light pdf,
+// whose triangle is not on a vertex's dependent chain — compile to the code they had)
+__device__ __forceinline__ void fill_triangle(const DevScene &sc, uint32_t prim, float4 v0, float4 v1, float4 v2, float b0, float b1, float b2, vec3 rayD,
+                                              DevSI *si, DevTexGeom *tg = nullptr, bool inlineTag = true) {
     const vec3 p0(v0.x, v0.y, v0.z), p1(v1.x, v1.y, v1.z), p2(v2.x, v2.y, v2.z);
     const int shapeId = (int)__float_as_uint(v1.w);
-    const DevShape sh = sc.shapes[shapeId];
-    const bool flip = (sh.flags & SHAPE_FLIP) != 0;
+    const uint32_t tag = __float_as_uint(v0.w);
+    uint32_t flags;
+    if (inlineTag && (tag & TAG_SHAPE_INLINE)) { flags = (tag >> TAG_SHAPE_FLAGS_SHIFT) & SHAPE_FLAGS_MASK; si->material = (int32_t)(tag >> TAG_MATERIAL_SHIFT); }
+    else { flags = sc.shapes[shapeId].flags; si->material = -1; }
+    const bool flip = (flags & SHAPE_FLIP) != 0;
     uint32_t i0 = 0u, i1 = 0u, i2 = 0u;      // vertex ids: only the rare uv / tangent attributes are reached through them
-    if (sh.flags & (SHAPE_HAS_UV | SHAPE_HAS_S)) { i0 = sc.primVtx[3 * prim]; i1 = sc.primVtx[3 * prim + 1]; i2 = sc.primVtx[3 * prim + 2]; }
+    if (flags & (SHAPE_HAS_UV | SHAPE_HAS_S)) { i0 = sc.primVtx[3 * prim]; i1 = sc.primVtx[3 * prim + 1]; i2 = sc.primVtx[3 * prim + 2]; }
     float uv0x = 0, uv0y = 0, uv1x = 1, uv1y = 0, uv2x = 1, uv2y = 1;   // triangle.h:114-118
-    if (sh.flags & SHAPE_HAS_UV) {
+    if (flags & SHAPE_HAS_UV) {
         uv0x = sc.vUV[2 * i0]; uv0y = sc.vUV[2 * i0 + 1]; uv1x = sc.vUV[2 * i1]; uv1y = sc.vUV[2 * i1 + 1];
         uv2x = sc.vUV[2 * i2]; uv2y = sc.vUV[2 * i2 + 1];
     }
@@ -247,16 +254,16 @@ __device__ __forceinline__ void fill_triangle(const DevScene &sc, uint32_t prim,
         tg->dpdu = dpdu; tg->dpdv = dpdv;
         tg->u = b0 * uv0x + b1 * uv1x + b2 * uv2x; tg->v = b0 * uv0y + b1 * uv1y + b2 * uv2y;
     }
-    if (sh.flags & (SHAPE_HAS_N | SHAPE_HAS_S)) {
+    if (flags & (SHAPE_HAS_N | SHAPE_HAS_S)) {
         vec3 ns;
-        if (sh.flags & SHAPE_HAS_N) {
+        if (flags & SHAPE_HAS_N) {
             const float4 m0 = sc.primN[3 * prim], m1 = sc.primN[3 * prim + 1], m2 = sc.primN[3 * prim + 2];
             const vec3 n0(m0.x, m0.y, m0.z), n1(m1.x, m1.y, m1.z), n2(m2.x, m2.y, m2.z);
             ns = (b0 * n0 + b1 * n1 + b2 * n2);
             if (length2(ns) > 0) ns = normalize(ns); else ns = si->n;
         } else ns = si->n;
         vec3 ss;
-        if (sh.flags & SHAPE_HAS_S) {
+        if (flags & SHAPE_HAS_S) {
             vec3 s0(sc.vS[3 * i0], sc.vS[3 * i0 + 1], sc.vS[3 * i0 + 2]), s1(sc.vS[3 * i1], sc.vS[3 * i1 + 1], sc.vS[3 * i1 + 2]),
                 s2(sc.vS[3 * i2], sc.vS[3 * i2 + 1], sc.vS[3 * i2 + 2]);
             ss = (b0 * s0 + b1 * s1 + b2 * s2);
@@ -267,8 +274,12 @@ __device__ __forceinline__ void fill_triangle(const DevScene &sc, uint32_t prim,
         else coordinate_system(ns, &ss, &ts);
         set_shading(si, ss, ts, flip);
     }
-    if (sh.flags & SHAPE_HAS_N) si->n = face_forward(si->n, si->ns);
+    if (flags & SHAPE_HAS_N) si->n = face_forward(si->n, si->ns);
     else if (flip) { si->n = -si->n; si->ns = si->n; }
+}
+__device__ __forceinline__ void fill_triangle(const DevScene &sc, uint32_t prim, float b0, float b1, float b2, vec3 rayD, DevSI *si,
+                                              DevTexGeom *tg = nullptr) {
+    fill_triangle(sc, prim, sc.tris[3 * prim], sc.tris[3 * prim + 1], sc.tris[3 * prim + 2], b0, b1, b2, rayD, si, tg, false);
 }
 // Sphere::Intersect fill part + (*ObjectToWorld)(SurfaceInteraction)
 // (shapes/sphere.cpp:106-157, core/transform.cpp:262-297).  Returns false if the
@@ -297,7 +308,7 @@ __device__ __noinline__ bool fill_sphere(const DevScene &sc, int shapeId, const 
     si->ns = normalize(xf_normal(s.w2o, nsObj));
     si->sdpdu = xf_vector(s.o2w, dpdu);
     si->ns = face_forward(si->ns, si->n);
-    si->shape = shapeId;
+    si->shape = shapeId; si->material = -1;
     if (tg) {      // u = phi / phiMax, v = (theta - thetaMin) / (thetaMax - thetaMin) (shapes/sphere.cpp:108-110)
         phi = det_atan2f(pHit.y, pHit.x);      // sphere_test skips phi where the clipping test does not need it
         if (phi < 0) phi += 2 * HPRT_PI;
@@ -644,13 +655,14 @@ __device__ __forceinline__ void bsdf_init(const DevScene &sc, const DevSI &si, D
     b->ts = cross(b->ns, b->ss);
     b->alpha = 0; b->hasD = false; b->hasS = false; b->Rd = rgb(0.f); b->Rs = rgb(0.f);
     b->hasR = false; b->hasT = false; b->Rr = rgb(0.f); b->oren = false; b->orenA = 1.f; b->orenB = 0.f;
-    const DevMaterial m = sc.materials[sc.shapes[si.shape].material];
+    const int mi = si_material(sc, si);
+    const DevMaterial m = sc.materials[mi];
     b->alphaY = 0; b->kind = 0; b->eta = 1.f; b->frI = 1.5f; b->frT = 1.f; b->uber = nullptr;
     if (m.type == 6) {      // UberMaterial, materials/uber.cpp:45-108: Lambertian + microfacet (FresnelDielectric(1, e)) as the plastic pair, and up to
                             // three specular lobes (1 - opacity straight through, Kr, Kt) that only the next-segment sampling sees (bsdf_sample all = true)
         const rgb op = clamp0(opOverride ? *opOverride : rgb(m.opacity[0], m.opacity[1], m.opacity[2]));
         const rgb t = clamp0(-op + rgb(1.f));
-        b->kind = 5; b->uber = &sc.materials[sc.shapes[si.shape].material]; b->op = op;
+        b->kind = 5; b->uber = &sc.materials[mi]; b->op = op;
         b->eta = is_black(t) ? m.eta : 1.f;
         const rgb kd = op * clamp0(kdOverride ? *kdOverride : rgb(m.Kd[0], m.Kd[1], m.Kd[2]));
         if (!is_black(kd)) { b->hasD = true; b->Rd = kd; }

@@ -38,11 +38,12 @@ struct QueueSet {
 // with the MIPMap lookups: scenes with textures only), 4 substrate.  count[k * BIN_STRIDE], k = 0..4: sizes; k = 5: size of bin 2
 // before the specialised variants deferred vertices to it (counters 256 bytes apart: atomics on different bins do not share a line);
 // k = 6, 7: the retry lists; aux[k] = output index of a deferred entry k of bin 2.  Output indices: bin 0 occupies [0, n0), then
-// bins 1, 4, 2 (as binned) and 3.
+// bins 1, 4, 2 (as binned) and 3.  A bin entry is {stream index, the hit's primitive word}: k_bin has the word in registers, and k_shade
+// then requests the primitive record together with the path's streams instead of one memory round trip after them.
 enum : uint32_t { BIN_STRIDE = 64u };
 // retry[b - 2], b = 2, 3: {stream index, output index} pairs of vertices whose light-distribution voxel was not there yet
 // (on-demand SpatialLightDistribution): shaded again by bin b's variant after the voxels have been filled; count[(6 + b - 2) * BIN_STRIDE]
-struct BinSet { uint32_t *q[5]; uint32_t *aux; uint32_t *count; uint2 *retry[2]; };
+struct BinSet { uint2 *q[5]; uint32_t *aux; uint32_t *count; uint2 *retry[2]; };
 struct RenderParams {
     DevCamera cam;
     DevHalton hal;

@@ -1194,7 +1194,7 @@ __global__ __launch_bounds__(1024) void k_bin(DevScene sc, PathStream in, HitStr
         const int b = bin[k];
         const unsigned long long m = b == 0 ? mask[k][0] : b == 1 ? mask[k][1] : b == 2 ? mask[k][2] : b == 3 ? mask[k][3] : mask[k][4];
         const uint32_t pos = binBase[b] + waveCount[b][k * 16 + wave] + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-        bins.q[b][pos] = slot[k];
+        bins.q[b][pos] = make_uint2(slot[k], __float_as_uint(hitA[k].y));      // the primitive word travels with the entry (kernels.h, BinSet)
     }
 }
 
@@ -1208,8 +1208,8 @@ __global__ __launch_bounds__(1024) void k_bin(DevScene sc, PathStream in, HitStr
 // registers than a larger workgroup can have).
 // TEX: scenes with image textures get their own instance of the generic variant (the lookups cost registers and a
 // call stack that every other scene would pay for in occupancy).
-// Waves per SIMD the register allocation of each variant is held to (second __launch_bounds__ argument): matte 111 and plastic
-// 120 registers -> four, generic 164 -> three, which is what the allocator picks on its own; the knobs exist for A/B builds
+// Waves per SIMD the register allocation of each variant is held to (second __launch_bounds__ argument): matte 112, plastic
+// 124 and substrate 118 registers -> four, generic 168 -> three, which is what the allocator picks on its own; the knobs exist for A/B builds
 // (tools/build_variant.sh).
 #ifndef HPRT_SHADE_WAVES_MATTE
 #define HPRT_SHADE_WAVES_MATTE 4
@@ -1245,18 +1245,35 @@ __global__ __launch_bounds__(BS, MODE == 0 ? HPRT_SHADE_WAVES_MATTE : MODE == 1 
     uint32_t j = 0;             // index in the output streams
     // The vertex's queue entry and path words are requested BEFORE the Halton tables are staged: the staging (20 KB per workgroup and a
     // barrier, in front of everything) and the first two round trips of the vertex's own dependent chain then overlap.
-    float4 rayA = make_float4(0.f, 0.f, 0.f, 0.f), rayB = rayA, hitA = rayA, beta4 = rayA, L4 = rayA;
+    // The entry carries the hit's primitive word, so the primitive record (and the rest of the hit) is requested in the same round as the
+    // path streams, not one round trip after hit.a.
+    float4 rayA = make_float4(0.f, 0.f, 0.f, 0.f), rayB = rayA, hitA = rayA, beta4 = rayA, L4 = rayA, tv0 = rayA, tv1 = rayA, tv2 = rayA;
+    float2 hitB = make_float2(0.f, __int_as_float(-1));
+    int32_t word = -1;          // the hit's primitive word (dev_scene.h)
+    // One light and no spatial distribution (kernel-uniform): Distribution1D::SampleDiscrete returns light 0 for every u (its offset is
+    // clamped to [0, size - 2] = [0, 0]), so the light is fetched here through the scalar path, ahead of the vertex's own chain.
+    const bool oneLight = sc.nLights == 1u && !sc.spatial;
+    DevLight light0 = {};
+    if (oneLight) light0 = sc.lights[0];
     if (i < n) {
-        if (retryPass) { const uint2 e = bins.retry[RETRY][i]; slot = e.x; j = e.y; }
+        // (one 8-byte request from either list; the retry lists keep {stream index, output index}: there the word comes from the hit — rare)
+        const uint2 e = (retryPass ? bins.retry[RETRY] : bins.q[BIN])[i];
+        slot = e.x;
+        word = retryPass ? __float_as_int(hit.a[slot].y) : (int32_t)e.y;
+        if (retryPass) j = e.y;
         else {
-        slot = bins.q[BIN][i];
-        // output index: bins in the order matte, plastic, substrate, generic (as binned), textured
-        j = (BIN == (int)BIN_MATTE ? 0u : BIN == (int)BIN_PLASTIC ? bins.count[0] : BIN == (int)BIN_SUBSTRATE ? bins.count[0] + bins.count[BIN_STRIDE]
-             : BIN == (int)BIN_GENERIC ? bins.count[0] + bins.count[BIN_STRIDE] + bins.count[4 * BIN_STRIDE]
-             : bins.count[0] + bins.count[BIN_STRIDE] + bins.count[4 * BIN_STRIDE] + bins.count[5 * BIN_STRIDE]) + i;
-        if (BIN == (int)BIN_GENERIC && i >= bins.count[5 * BIN_STRIDE]) j = bins.aux[i];       // deferred by a specialised variant: keeps that variant's index
+            // output index: bins in the order matte, plastic, substrate, generic (as binned), textured
+            j = (BIN == (int)BIN_MATTE ? 0u : BIN == (int)BIN_PLASTIC ? bins.count[0] : BIN == (int)BIN_SUBSTRATE ? bins.count[0] + bins.count[BIN_STRIDE]
+                 : BIN == (int)BIN_GENERIC ? bins.count[0] + bins.count[BIN_STRIDE] + bins.count[4 * BIN_STRIDE]
+                 : bins.count[0] + bins.count[BIN_STRIDE] + bins.count[4 * BIN_STRIDE] + bins.count[5 * BIN_STRIDE]) + i;
+            if (BIN == (int)BIN_GENERIC && i >= bins.count[5 * BIN_STRIDE]) j = bins.aux[i];       // deferred by a specialised variant: keeps that variant's index
         }
-        rayA = in.ray.a[slot]; rayB = in.ray.b[slot]; hitA = hit.a[slot];
+        // One round of requests, all addressed by the entry alone (the record first: the wait for the entry then covers nothing younger).
+        // The generic bin also holds escaped rays (word < 0): no record to fetch.  Every slot of hit.b has an entry; a miss does not use it.
+        const int32_t p = hit_prim(word);
+        if (MODE != 2 || p >= 0) { tv0 = sc.tris[3 * p]; tv1 = sc.tris[3 * p + 1]; tv2 = sc.tris[3 * p + 2]; }
+        hitA = hit.a[slot]; rayA = in.ray.a[slot]; rayB = in.ray.b[slot];
+        if (hit.b) hitB = hit.b[slot];
         // a fresh path's throughput and radiance are constants (k_generate does not store them)
         beta4 = firstBounce ? make_float4(1.f, 1.f, 1.f, __uint_as_float(slot)) : in.beta[slot];
         L4 = firstBounce ? make_float4(0.f, 0.f, 0.f, 1.f) : in.L[slot];
@@ -1271,7 +1288,7 @@ __global__ __launch_bounds__(BS, MODE == 0 ? HPRT_SHADE_WAVES_MATTE : MODE == 1 
         const uint32_t pathId = __float_as_uint(beta4.w);
         const uint32_t pix = pathId % rp.nPix, sIdx = pathId / rp.nPix;
         const uint64_t index = (uint64_t)rp.pixelOffset[pix] + (uint64_t)(s0 + sIdx) * (uint64_t)rp.hal.sampleStride;
-        const int32_t prim = hit_prim(__float_as_int(hitA.y));
+        const int32_t prim = hit_prim(word);
         const vec3 rayO(rayA.x, rayA.y, rayA.z);
         const vec3 rayD(rayB.x, rayB.y, rayB.z);
         rgb beta(beta4.x, beta4.y, beta4.z);
@@ -1282,8 +1299,7 @@ __global__ __launch_bounds__(BS, MODE == 0 ? HPRT_SHADE_WAVES_MATTE : MODE == 1 
         DevTexGeom tg;
         constexpr bool texScene = MODE == 2 && TEX;      // image textures: the generic variant only
         if (found) {
-            const float4 v0 = sc.tris[3 * prim];
-            const float2 hitB = hit.b[slot];
+            const float4 v0 = tv0;
             // A hit inside an object instance was found by the instance-space ray: the surface interaction is
             // filled there and transformed back (TransformedPrimitive::Intersect, core/primitive.cpp:77-93)
             const int inst = (MODE == 2 || INSTS) ? __float_as_int(hitB.y) : -1;
@@ -1301,10 +1317,10 @@ __global__ __launch_bounds__(BS, MODE == 0 ? HPRT_SHADE_WAVES_MATTE : MODE == 1 
                 }
             }
             if (MODE != 2 || (__float_as_uint(v0.w) & TAG_KIND_MASK) == 0u)
-                fill_triangle(sc, (uint32_t)prim, hitA.z, hitA.w, hitB.x, r0.d, &si, texScene ? &tg : nullptr);
+                fill_triangle(sc, (uint32_t)prim, tv0, tv1, tv2, hitA.z, hitA.w, hitB.x, r0.d, &si, texScene ? &tg : nullptr);
             else {
                 float tt;
-                fill_sphere(sc, (int)__float_as_uint(sc.tris[3 * prim + 1].w), r0, &si, &tt, texScene ? &tg : nullptr);
+                fill_sphere(sc, (int)__float_as_uint(tv1.w), r0, &si, &tt, texScene ? &tg : nullptr);
             }
             if ((MODE == 2 || INSTS) && inst >= 0 && !sc.instances[inst].identity) {
                 // Transform::operator()(const SurfaceInteraction &), core/transform.cpp:262-297
@@ -1344,7 +1360,7 @@ __global__ __launch_bounds__(BS, MODE == 0 ? HPRT_SHADE_WAVES_MATTE : MODE == 1 
             bool useKd = false, useKs = false, useOp = false;
             rgb kdTex, ksTex, opTex;
             if (texScene) {
-                const DevMaterial m = sc.materials[sc.shapes[si.shape].material];
+                const DevMaterial m = sc.materials[si_material(sc, si)];
                 const int opTexId = m.type == 6 ? m.opTex : -1;
                 if (m.KdTex >= 0 || m.KsTex >= 0 || opTexId >= 0) {
                     // SurfaceInteraction::ComputeDifferentials (core/interaction.cpp:103-149): only the camera ray carries
@@ -1385,11 +1401,14 @@ __global__ __launch_bounds__(BS, MODE == 0 ? HPRT_SHADE_WAVES_MATTE : MODE == 1 
                 // every pick value selects light 0 with pdf 1, and point / distant lights ignore uLight (lights/point.cpp:44-53,
                 // lights/distant.cpp:49-59) and never reach the BSDF-sampling branch (core/integrator.cpp:168).
                 float pickPdf;
-                const int lightNum = light_pick(sc, si.p, sc.nLights > 1u ? halton_dim(sc, rp.hal, index, dim, &hl) : 0.f, &pickPdf, &voxelMiss);
+                int lightNum = 0;
+                // (one light: the pdf Distribution1D::SampleDiscrete forms for offset 0 with n = 1, from the same table words)
+                if (oneLight) pickPdf = (sc.lightFuncInt > 0) ? sc.lightFunc[0] / (sc.lightFuncInt * 1) : 0;
+                else lightNum = light_pick(sc, si.p, sc.nLights > 1u ? halton_dim(sc, rp.hal, index, dim, &hl) : 0.f, &pickPdf, &voxelMiss);
                 dim += 1;
                 if (voxelMiss) defer = true;      // nothing has been written for this vertex: it is shaded again once its voxel is there
                 if (pickPdf != 0) {
-                    const DevLight light = sc.lights[lightNum];
+                    const DevLight light = oneLight ? light0 : sc.lights[lightNum];
                     const bool isDelta = light.type < 2;
                     float ul0 = 0.f, ul1 = 0.f, us0 = 0.f, us1 = 0.f;
                     if (!isDelta) {
@@ -1536,7 +1555,7 @@ __global__ __launch_bounds__(BS, MODE == 0 ? HPRT_SHADE_WAVES_MATTE : MODE == 1 
     if (MODE != 2) {   // (almost) never
         const bool toGeneric = defer && !voxelMiss;
         const uint32_t p2 = wave_append(bins.count + 2 * BIN_STRIDE, toGeneric);
-        if (toGeneric) { bins.q[2][p2] = slot; bins.aux[p2] = j; }
+        if (toGeneric) { bins.q[2][p2] = make_uint2(slot, (uint32_t)word); bins.aux[p2] = j; }
     }
     if (sc.voxSlot) {   // (kernel-uniform) on-demand voxel tables: the vertices that missed, for the pass after the fill
         const uint32_t pr = wave_append(bins.count + (6 + RETRY) * BIN_STRIDE, voxelMiss && !retryPass);

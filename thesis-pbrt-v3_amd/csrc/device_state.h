@@ -72,6 +72,9 @@ struct HprtScene {
     hprt::DevBuf counters, workCounter, deepStack;
     // hprt_debug_capture_rays (tools/sort_experiment.py): the next render copies the rays one bounce queues into a caller buffer
     struct Capture { int bounce = -1, kind = 0; float *out7 = nullptr; size_t cap = 0, n = 0; } capture;
+    // hprt_debug_shade_counts (tests): while on, every bounce also reads how many vertices the specialised shading variants deferred to the
+    // generic bin and how many waited in the retry lists; sums since it was switched on
+    bool shadeCountsOn = false; uint64_t shadeDeferred = 0, shadeRetried = 0;
     int poisonByte = -1;      // hprt_debug_poison_workspace (tests): fill every stream, queue and stack with this byte before each render
     hprt::DevBuf voxFunc, voxCdf, voxFuncInt, voxRi;      // SpatialLightDistribution tables (lightsamplestrategy "spatial")
     hprt::DevBuf voxSlot, voxRequest, voxRequestCount, retryQueues;      // on-demand mode: voxel -> table row, the request list, the vertices to shade again

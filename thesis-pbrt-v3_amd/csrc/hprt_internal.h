@@ -2,6 +2,7 @@
 #pragma once
 #include <string>
 #include <vector>
+#include "../../include/hprt.h"
 #include "bvh_builder.h"
 #include "kdtree_builder.h"
 #include "rbsp_builder.h"
@@ -31,4 +32,8 @@ namespace hprt {
 extern thread_local std::string g_lastError;
 int SetError(int code, const std::string &msg);
 int HandleException();      // maps the exception in flight to an HPRT_E_* code + message (capi_host.cpp)
+// BuildSceneLayout (scene_layout.cpp) on *d, for hprt_debug_shape_inline: per ordered primitive the tag word and the word beside it (a
+// triangle's or sphere's shape), per shape its DevShape flags and material
+int LayoutTagsForDebug(const HprtSceneDesc &d, std::vector<uint32_t> *tags, std::vector<uint32_t> *primShape, std::vector<uint32_t> *shapeFlags,
+                       std::vector<int32_t> *shapeMaterial);
 }  // namespace hprt

@@ -3,6 +3,7 @@
 // when they sat in capi_device.hip.
 #include <algorithm>
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 #include <utility>
 #include "scene_layout.h"
@@ -90,6 +91,7 @@ struct Work {
     std::vector<int> sphereOfShape;
     std::vector<int32_t> lightPrim;         // triangle lights: ordered index of their triangle
     std::vector<int32_t> wideBase;          // first wide record of every aggregate that has a tree
+    uint32_t inlineMaterialMax;             // largest material index a triangle's tag carries (TAG_SHAPE_INLINE)
 };
 
 int ValidateArrays(Work &w) {
@@ -293,6 +295,9 @@ int LayoutPrimitives(Work &w) {
                     const uint32_t bin = Textured(md) ? BIN_TEXTURED : triLight >= 0 ? BIN_GENERIC : md.type == 1 ? BIN_PLASTIC : md.type == 3 ? BIN_SUBSTRATE :
                                          (md.type == 0 && clampf(md.sigma, 0.f, 90.f) == 0.f) ? BIN_MATTE : BIN_GENERIC;
                     uint32_t tag = (bogus ? TAG_BOGUS : 0u) | (bin << TAG_BIN_SHIFT);
+                    // what shading reads of shapes[s] travels in the tag when the material index fits (dev_scene.h)
+                    if ((uint32_t)sh.material <= w.inlineMaterialMax)
+                        tag |= TAG_SHAPE_INLINE | ((L.shapes[s].flags & SHAPE_FLAGS_MASK) << TAG_SHAPE_FLAGS_SHIFT) | ((uint32_t)sh.material << TAG_MATERIAL_SHIFT);
                     if (bin == BIN_SUBSTRATE) L.hasSubstrateBin = true;
                     r0 = make_float4(a[0], a[1], a[2], u2f(tag)); r1 = make_float4(b[0], b[1], b[2], u2f(s)); r2 = make_float4(c[0], c[1], c[2], u2f((uint32_t)(triLight + 1)));
                     for (int k = 0; k < 3; ++k) {
@@ -604,6 +609,9 @@ int LayoutInstances(Work &w) {
 
 int BuildSceneLayout(const HprtSceneDesc &d, SceneLayout *out) {
     Work w{d, *out};
+    // HPRT_INLINE_MATERIAL_MAX can only lower the limit: the tests reach the shapes[] lookup of larger indices with it
+    w.inlineMaterialMax = TAG_MATERIAL_MAX;
+    if (const char *e = getenv("HPRT_INLINE_MATERIAL_MAX")) { const long v = atol(e); w.inlineMaterialMax = v < 0 ? 0u : (uint32_t)std::min<long>(v, (long)TAG_MATERIAL_MAX); }
     // validation first (nothing below reads past what it has checked), then the layout in dependency order
     for (int (*stage)(Work &) : {ValidateArrays, ValidateShapes, GatherAggregates, CheckAggregates, ValidateLights}) if (int rc = stage(w)) return rc;
     out->nPrims = w.primBase.back();
@@ -617,6 +625,15 @@ int BuildSceneLayout(const HprtSceneDesc &d, SceneLayout *out) {
     for (int (*stage)(Work &) : {LayoutShapes, LayoutPrimitives, LayoutMaterials, LayoutTextures, LayoutLights, LayoutEnvLights,
                                  LayoutLightDistribution, LayoutPairs, LayoutWide, LayoutInstances})
         if (int rc = stage(w)) return rc;
+    return HPRT_OK;
+}
+
+int LayoutTagsForDebug(const HprtSceneDesc &d, std::vector<uint32_t> *tags, std::vector<uint32_t> *primShape, std::vector<uint32_t> *shapeFlags,
+                       std::vector<int32_t> *shapeMaterial) {
+    SceneLayout L;
+    if (int rc = BuildSceneLayout(d, &L)) return rc;
+    for (uint32_t i = 0; i < L.nPrims; ++i) { tags->push_back(f2u(L.tris[3 * (size_t)i].w)); primShape->push_back(f2u(L.tris[3 * (size_t)i + 1].w)); }
+    for (const DevShape &s : L.shapes) { shapeFlags->push_back(s.flags); shapeMaterial->push_back(s.material); }
     return HPRT_OK;
 }
 
