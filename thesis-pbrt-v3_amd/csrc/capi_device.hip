@@ -5,6 +5,7 @@
 // HIP device is usable.
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <cassert>
 #include <chrono>
 #include <cmath>
 #include <cstring>
@@ -258,10 +259,26 @@ __attribute__((visibility("default"))) int hprt_debug_scene_walk(HprtScene *s) {
 __attribute__((visibility("default"))) int hprt_debug_shade_counts(HprtScene *s, int on, uint64_t *out2) {
     if (!s) return HPRT_E_INVALID;
     if (out2) { out2[0] = s->shadeDeferred; out2[1] = s->shadeRetried; }
-    if (on && !s->shadeCountsOn) s->shadeDeferred = s->shadeRetried = 0;
+    if (on && !s->shadeCountsOn) s->shadeDeferred = s->shadeRetried = s->shadeSpeculated = s->shadeRepaired = s->shadeFull = 0;
     s->shadeCountsOn = on != 0;
     return HPRT_OK;
 }
+// Diagnostics hook (not part of include/hprt.h; tests/test_gpu_speculated_light.py): the sums, since hprt_debug_shade_counts switched counting
+// on, of the vertices whose light sample k_shade added at once, of those k_repair then set back (their shadow ray was blocked), and of
+// the full vertices (pending streams + k_resolve)
+__attribute__((visibility("default"))) int hprt_debug_speculated_counts(HprtScene *s, uint64_t *out3) {
+    if (!s || !out3) return HPRT_E_INVALID;
+    out3[0] = s->shadeSpeculated; out3[1] = s->shadeRepaired; out3[2] = s->shadeFull;
+    return HPRT_OK;
+}
+// HPRT_SPECULATE_LIGHT=0 in the environment, or hprt_debug_speculate_light(0) at run time (diagnostics hook, not part of include/hprt.h):
+// renders keep the full path for every vertex — all pending terms through k_resolve (A/B runs, tests).  Returns the setting before.
+static int g_speculateLight = -1;
+static bool SpeculateLightEnabled() {
+    static const bool fromEnv = [] { const char *e = getenv("HPRT_SPECULATE_LIGHT"); return !(e && atoi(e) == 0); }();
+    return g_speculateLight < 0 ? fromEnv : g_speculateLight != 0;
+}
+__attribute__((visibility("default"))) int hprt_debug_speculate_light(int on) { const int was = SpeculateLightEnabled() ? 1 : 0; g_speculateLight = on; return was; }
 __attribute__((visibility("default"))) int hprt_debug_poison_workspace(HprtScene *s, int byte) { if (!s) return HPRT_E_INVALID; s->poisonByte = byte < 0 ? -1 : (byte & 255); return HPRT_OK; }
 // Diagnostics hook (not part of include/hprt.h): the first batch of the next hprt_render copies the rays that bounce `bounce` queues
 // (kind 0: the path segments entering bounce + 1, 1: its shadow rays, 2: its BSDF-sampled light rays) into d_out7 ([7][cap] planes:
@@ -759,22 +776,31 @@ int hprt_occluded(HprtScene *s, size_t n, const float *o, const float *d, const 
 // ---------------------------------------------------------------------------
 namespace {
 
+// words of s->queueCounts (EnsureWorkspace): the two QueueSets' counters [0, 512), the bins' [512, 1024), then k_repair's two test counters
+constexpr size_t kSpecCountsAt = 1024;
 struct BatchTimers { double extendMs = 0, occludedMs = 0; uint64_t extendLaunches = 0, occludedLaunches = 0, extendRays = 0, occludedRays = 0; };
 
 // Runs the bounce loop for one batch of nSlots freshly generated paths.
 // pixelStats (or null): [6][nPix] per-pixel counters of the local pixels, fed from the per-ray counts of every trace
 //
 // Per bounce b:   trace(path b) -> bin -> shade x3 -> [counts to the host] -> trace(shadow b) | trace(MIS b) | trace(path b+1)
-//                 -> resolve(b) -> bin(b+1) ...
+//                 -> resolve(b) (vertices with an MIS ray, if any) -> repair(b) (occluded speculated vertices) -> bin(b+1) ...
 // The three traces that follow a shading pass depend on nothing but that pass.  Running them on three HIP streams (so that
 // each fills the tails of the others' persistent kernels) was built and measured in round 2: SLOWER — atrium 1024 spp
 // 1064 -> 1119 ms, living room 455 -> 478 ms, killeroo-simple 90.6 -> 91.8 ms (every persistent kernel is sized to fill the
 // machine, so the second and third only get wave slots as the first one's blocks drain, and the cross-stream waits add
 // bubbles) — and removed again: every kernel runs on the caller's stream, where HIP-event times are exclusive.
-int RunBatch(HprtScene *s, hipStream_t st, const RenderParams &rp, const Workspace &w, const QueueSet &qa, const QueueSet &qb,
+int RunBatch(HprtScene *s, hipStream_t st, const RenderParams &rpIn, const Workspace &w, const QueueSet &qa, const QueueSet &qb,
              const BinSet &bins, uint32_t s0, uint32_t nSlots, bool count, EventTimer &ev, BatchTimers *bt, HprtRenderStats *stats,
              uint32_t *pixelStats = nullptr, const IrregularSink *irregular = nullptr) {
     uint4 *rayStats = pixelStats ? s->rayStats.as<uint4>() : nullptr;
+    // Speculated light samples (k_shade, k_repair).  Per-pixel-statistics renders keep the full path: they read pendBeta.w of every shadow
+    // ray as a plain path id.  So does a batch whose path ids would reach the record's flag bits.
+    RenderParams rp = rpIn;
+    rp.speculate = SpeculateLightEnabled() && !pixelStats && !rayStats && nSlots <= SPEC_MAX_PATHS ? 1 : 0;
+    assert(!rp.speculate || nSlots <= SPEC_MAX_PATHS);
+    uint32_t *specCounts = rp.speculate && s->shadeCountsOn ? s->queueCounts.as<uint32_t>() + kSpecCountsAt : nullptr;
+    if (specCounts) HIP_TRY(hipMemsetAsync(specCounts, 0, 2 * sizeof(uint32_t), st));
     uint32_t *pixelKd = pixelStats && CountsKdShare(s) ? s->pixelKdLocal.as<uint32_t>() : nullptr;     // the rbspkd / bsppaperkd walk's kd share
     uint32_t *wcPath = s->workCounter.as<uint32_t>();
     LaunchGenerate(st, s->dev, rp, w.path[0], s0, nSlots, irregular);
@@ -868,11 +894,16 @@ int RunBatch(HprtScene *s, hipStream_t st, const RenderParams &rp, const Workspa
         activeQ = cur.next; active = nNext;
         // (maxDepth is bounded by CheckDepth, and no path outlives bounce maxDepth)
         if (active > 0 && bounce > rp.maxDepth) return SetError(HPRT_E_DEVICE, "internal error: paths are still active beyond maxdepth");
+        // the full vertices' direct lighting, then the speculated vertices whose shadow ray was blocked (disjoint sets of vertices)
         if (nResolve) LaunchResolve(st, s->dev, w.vs, out.L, w.Lfinal, cur.resolve, cur.resolveCount, nResolve);
+        if (rp.speculate && nShadow) LaunchRepair(st, w.vs, out.L, w.Lfinal, cur.shadow, nShadow, specCounts);
+        if (s->shadeCountsOn) s->shadeFull += nResolve;
         if (active > 0) { int rc = tracePath(bounce + 1); if (rc != HPRT_OK) return rc; }
     }
     HIP_TRY(hipGetLastError());
+    if (specCounts) HIP_TRY(hipMemcpyAsync(s->hostCounts + 256, specCounts, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
+    if (specCounts) { s->shadeSpeculated += s->hostCounts[256]; s->shadeRepaired += s->hostCounts[257]; }
     for (auto &p : evExt) { float ms = 0; if (hipEventElapsedTime(&ms, p.first, p.second) == hipSuccess) bt->extendMs += ms; }
     for (auto &p : evOcc) { float ms = 0; if (hipEventElapsedTime(&ms, p.first, p.second) == hipSuccess) bt->occludedMs += ms; }
     ev.reset();
@@ -1003,6 +1034,7 @@ int hprt_render(HprtScene *s, const HprtRenderDesc *desc, float *d_film_xyzw, vo
     const bool wantPixelStats = (desc->flags & HPRT_RENDER_PIXEL_STATS) != 0;
     const bool count = (desc->flags & HPRT_RENDER_COUNT_WORK) != 0 || wantPixelStats;
     // a counting render traces exactly the reference's rays (its counters are the reference's) unless asked to count what a plain render traces
+    rp.speculate = 0;      // (RunBatch decides, batch by batch)
     rp.cullMis = (!count || (desc->flags & HPRT_RENDER_COUNT_TRACED) != 0) && !(desc->flags & HPRT_RENDER_TRACE_ALL) ? 1 : 0;
     uint32_t *pixelStats = nullptr;
     if (wantPixelStats) {
@@ -1244,7 +1276,7 @@ int hprt_sample_radiance(HprtScene *s, const HprtRenderOptions *opt, size_t n, c
     rp.hal.samplePixelCenter = opt->sample_pixel_center;
     rp.pixelXY = s->pixelXY.as<uint32_t>(); rp.pixelOffset = s->pixelOffset.as<uint64_t>(); rp.nPix = (uint32_t)n;
     rp.maxDepth = opt->max_depth; rp.rrThreshold = opt->rr_threshold;
-    rp.invSqrtSpp = 1 / std::sqrt((float)std::max(1, opt->spp)); rp.cullMis = 1;
+    rp.invSqrtSpp = 1 / std::sqrt((float)std::max(1, opt->spp)); rp.cullMis = 1; rp.speculate = 0;      // (RunBatch decides)
     EventTimer ev; BatchTimers bt; HprtRenderStats stats; memset(&stats, 0, sizeof(stats));
     rc = RunBatch(s, nullptr, rp, ps, qa, qb, bins, 0, (uint32_t)n, false, ev, &bt, &stats);
     if (rc != HPRT_OK) return rc;

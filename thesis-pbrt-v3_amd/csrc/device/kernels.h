@@ -26,10 +26,19 @@ struct PathStream {
 struct VertexStreams {
     RayStream shadow; uint8_t *occluded;             // shadow ray of the light sample, its any-hit result
     RayStream mis; HitStream misHit;                 // BSDF-sampled MIS ray, its closest hit (b2 unused)
+    // A vertex with an MIS ray — every vertex with a pending term where RenderParams::speculate is off — is a FULL vertex: it leaves the
+    // three pending streams and a resolve entry, and k_resolve adds its direct lighting once the rays are traced.
     float4 *pendLight;      // {light-sampling term rgb, info}   info: light number | bit30 shadow ray issued | bit31 MIS ray issued
     float4 *pendMis;        // {BSDF-sampling term rgb, light pick pdf}
     float4 *pendBeta;       // {beta before this vertex rgb, path id}
+    // A SPECULATED vertex (a shadow ray and no MIS ray, RenderParams::speculate on) leaves one record in pendBeta instead and nothing in the
+    // other two streams or the resolve queue: {radiance if the shadow ray is blocked rgb, path id | SPEC_RECORD | SPEC_END if the path ends
+    // here}.  Its radiance if the ray is not blocked is already in out.L[j] (in Lfinal[path id] if the path ends here); k_repair puts the
+    // record's value there once the ray has turned out blocked.
 };
+// Flag bits of a speculated vertex's record word.  Path ids stay below 2^28: a batch holds at most 256 M paths (ChooseBatch), and RunBatch
+// keeps a larger one (a caller's spp_chunk) on the full path.
+enum : uint32_t { SPEC_RECORD = 0x80000000u, SPEC_END = 0x40000000u, SPEC_ID_MASK = 0x0fffffffu, SPEC_MAX_PATHS = 1u << 28 };
 struct QueueSet {
     uint32_t *next, *shadow, *mis, *resolve;
     uint32_t *nextCount, *shadowCount, *misCount, *resolveCount;
@@ -55,6 +64,8 @@ struct RenderParams {
     float invSqrtSpp;               // 1 / sqrt(samplesPerPixel): ray differential scale (image textures only)
     int32_t cullMis;                // do not trace rays whose result provably changes nothing (k_shade): a BSDF-sampled light ray that
                                     // cannot reach its emitter, the segment behind the last vertex of a path
+    int32_t speculate;              // k_shade adds the light sample of a vertex with a shadow ray and no MIS ray at once (k_repair undoes the
+                                    // blocked ones); 0: every such vertex goes through the pending streams and k_resolve
 };
 struct FilmGeom {
     int32_t cx0, cy0, cx1, cy1;     // croppedPixelBounds
@@ -112,6 +123,8 @@ void LaunchShade(hipStream_t st, int mode, const DevScene &sc, const RenderParam
                  const BinSet &bins, float4 *Lfinal, bool firstBounce, bool retryPass = false);
 void LaunchResolve(hipStream_t st, const DevScene &sc, const VertexStreams &vs, float4 *L, float4 *Lfinal, const uint32_t *queue,
                    const uint32_t *countPtr, uint32_t gridItems);
+// counts (tests only, else null): {speculated, repaired} += this launch's
+void LaunchRepair(hipStream_t st, const VertexStreams &vs, float4 *L, float4 *Lfinal, const uint32_t *queue, uint32_t n, uint32_t *counts);
 void LaunchStoreRadiance(hipStream_t st, const float4 *Lfinal, float *LallR, float *LallG, float *LallB, uint32_t nPix, uint32_t s0,
                          uint32_t nSlots);
 // the *_device entry points of include/hprt.h keep their plane layouts: [7][n] rays in, t / prim / [3][n] barycentrics out

@@ -9,7 +9,8 @@
 //                                            (core/integrator.cpp:86-217)
 //     k_trace<any>      shadow rays          BVHAccel::IntersectP (VisibilityTester::Unoccluded)
 //     k_trace<closest>  MIS rays             scene.Intersect at core/integrator.cpp:195
-//     k_resolve         L += beta * Ld / lightPdf, in bounce order
+//     k_resolve         L += beta * Ld / lightPdf, in bounce order (vertices with an MIS ray; every vertex on the old path)
+//     k_repair          the dark value for the speculated vertices whose shadow ray was blocked
 // and once per batch k_generate (Render loop head, core/integrator.cpp:281-293) and
 // k_store_radiance (radiance guards, :300-321).  The film (FilmTile::AddSample /
 // MergeFilmTile, core/film.h:130-170, core/film.cpp:118-132) is folded per pixel in
@@ -1208,8 +1209,8 @@ __global__ __launch_bounds__(1024) void k_bin(DevScene sc, PathStream in, HitStr
 // registers than a larger workgroup can have).
 // TEX: scenes with image textures get their own instance of the generic variant (the lookups cost registers and a
 // call stack that every other scene would pay for in occupancy).
-// Waves per SIMD the register allocation of each variant is held to (second __launch_bounds__ argument): matte 112, plastic
-// 124 and substrate 118 registers -> four, generic 168 -> three, which is what the allocator picks on its own; the knobs exist for A/B builds
+// Waves per SIMD the register allocation of each variant is held to (second __launch_bounds__ argument): matte 114, plastic
+// 127 and substrate 121 registers -> four, generic 168 -> three, which is what the allocator picks on its own; the knobs exist for A/B builds
 // (tools/build_variant.sh).
 #ifndef HPRT_SHADE_WAVES_MATTE
 #define HPRT_SHADE_WAVES_MATTE 4
@@ -1241,6 +1242,7 @@ __global__ __launch_bounds__(BS, MODE == 0 ? HPRT_SHADE_WAVES_MATTE : MODE == 1 
     bool spFull = false;
 #endif
     bool wantNext = false, wantShadow = false, wantMis = false, wantResolve = false, defer = false, voxelMiss = false;
+    bool speculated = false;    // the vertex's light sample is already in L (rp.speculate)
     uint32_t slot = 0;          // index in the input streams
     uint32_t j = 0;             // index in the output streams
     // The vertex's queue entry and path words are requested BEFORE the Halton tables are staged: the staging (20 KB per workgroup and a
@@ -1292,7 +1294,7 @@ __global__ __launch_bounds__(BS, MODE == 0 ? HPRT_SHADE_WAVES_MATTE : MODE == 1 
         const vec3 rayO(rayA.x, rayA.y, rayA.z);
         const vec3 rayD(rayB.x, rayB.y, rayB.z);
         rgb beta(beta4.x, beta4.y, beta4.z);
-        rgb L(L4.x, L4.y, L4.z);
+        rgb L(L4.x, L4.y, L4.z), Ldark(0.f);
         float etaScale = L4.w;      // (a stored path continues, so its w word is its etaScale; fresh paths: 1)
         const bool found = prim >= 0;
         DevSI si;
@@ -1477,7 +1479,18 @@ __global__ __launch_bounds__(BS, MODE == 0 ? HPRT_SHADE_WAVES_MATTE : MODE == 1 
                             }
                         }
                     }
-                    if (wantShadow || wantMis) {
+                    if (rp.speculate && wantShadow && !wantMis) {
+                        // The light sample is this vertex's only pending term: its radiance is one of two values, told apart by the shadow ray alone.
+                        // Both are formed here with k_resolve's operations in k_resolve's order (pickPdf is what it re-derives, word for word:
+                        // dist1d_sample_discrete forms func[n] / (funcInt * n)); the lit one goes where the final value belongs, the dark one waits
+                        // in the record for k_repair.  No pending streams, no resolve entry.
+                        rgb LdLit(0.f);
+                        LdLit = LdLit + pendLight;
+                        const rgb addLit = beta * (LdLit / pickPdf), addDark = beta * (rgb(0.f) / pickPdf);
+                        Ldark = rgb(L.r + addDark.r, L.g + addDark.g, L.b + addDark.b);
+                        L = rgb(L.r + addLit.r, L.g + addLit.g, L.b + addLit.b);
+                        speculated = true;
+                    } else if (wantShadow || wantMis) {
                         vs.pendLight[j] = make_float4(pendLight.r, pendLight.g, pendLight.b,
                                                       __uint_as_float((uint32_t)lightNum | (wantShadow ? 0x40000000u : 0u) | (wantMis ? 0x80000000u : 0u)));
                         // (k_resolve re-derives pickPdf from the light number — except with the spatial distribution, where it depends on the vertex)
@@ -1493,7 +1506,7 @@ __global__ __launch_bounds__(BS, MODE == 0 ? HPRT_SHADE_WAVES_MATTE : MODE == 1 
             // is Spectrum(0) (no light, pick pdf 0, black f, zero light pdf): beta * 0 is +-0 for a finite throughput — which is why such a vertex
             // queues no resolve work — but NaN for an infinite or NaN one (a degenerate microfacet alpha, a vanishing pdf), and the
             // reference's NaN guard then zeroes the whole sample.  Found by the random scenes (rough glass with alpha 0 along one axis).
-            if (!defer && !wantResolve && bsdf_num(bsdf) > 0) L = rgb(L.r + beta.r * 0.f, L.g + beta.g * 0.f, L.b + beta.b * 0.f);
+            if (!defer && !wantResolve && !speculated && bsdf_num(bsdf) > 0) L = rgb(L.r + beta.r * 0.f, L.g + beta.g * 0.f, L.b + beta.b * 0.f);
             SP_MARK(4);      // BSDF-sampled light term + pending stores
             // ---- sample the BSDF for the next path segment (path.cpp:141-164) ----
             if (!defer) {
@@ -1536,7 +1549,9 @@ __global__ __launch_bounds__(BS, MODE == 0 ? HPRT_SHADE_WAVES_MATTE : MODE == 1 
         }
         // Radiance so far: k_resolve adds this vertex's direct lighting to out.L[j] and, if the path
         // stops here (w == 0), passes the sum on to Lfinal; without a pending term this lane does it.
+        // (A speculated vertex has no pending term: L holds its lit value, and k_repair puts the dark one in its place if the shadow ray is blocked.)
         if (!defer) {
+            if (speculated) vs.pendBeta[j] = make_float4(Ldark.r, Ldark.g, Ldark.b, __uint_as_float(pathId | SPEC_RECORD | (wantNext ? 0u : SPEC_END)));
             if (wantNext || wantResolve) out.L[j] = make_float4(L.r, L.g, L.b, wantNext ? etaScale : 0.f);      // w: 0 = the path ends at this vertex, else its etaScale
             else Lfinal[pathId] = make_float4(L.r, L.g, L.b, 0.f);
         }
@@ -1613,6 +1628,31 @@ __global__ __launch_bounds__(256) void k_resolve(DevScene sc, VertexStreams vs, 
     const float4 Lnew = make_float4(L4.x + add.r, L4.y + add.g, L4.z + add.b, L4.w);
     if (L4.w != 0.f) Lio[j] = Lnew;                                   // the path goes on: radiance travels with it
     else Lfinal[__float_as_uint(pb.w)] = Lnew;                        // last vertex of the path
+}
+
+// ---------------------------------------------------------------------------
+// k_repair: one lane per shadow ray.  A speculated vertex (k_shade, rp.speculate) carries its lit radiance already; where the ray
+// turned out blocked, the dark value of its record replaces it.  Vertices that are not speculated are k_resolve's.
+// COUNT (tests only): counts[0] += speculated vertices, counts[1] += repaired ones.
+// ---------------------------------------------------------------------------
+template <bool COUNT>
+__global__ __launch_bounds__(256) void k_repair(VertexStreams vs, float4 *Lio, float4 *Lfinal, const uint32_t *queue, uint32_t n, uint32_t *counts) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t j = queue[i];
+    const bool occluded = vs.occluded[j] != 0;
+    if (!COUNT && !occluded) return;
+    const float4 rec = vs.pendBeta[j];
+    const uint32_t w = __float_as_uint(rec.w);
+    if (!(w & SPEC_RECORD)) return;
+    if (COUNT) atomicAdd(counts, 1u);
+    if (!occluded) return;
+    if (COUNT) atomicAdd(counts + 1, 1u);
+    if (w & SPEC_END) Lfinal[w & SPEC_ID_MASK] = make_float4(rec.x, rec.y, rec.z, 0.f);      // last vertex of the path
+    else {      // the path goes on: the w word is its etaScale and stays
+        float *const Lj = reinterpret_cast<float *>(Lio + j);
+        Lj[0] = rec.x; Lj[1] = rec.y; Lj[2] = rec.z;
+    }
 }
 
 // ---------------------------------------------------------------------------
@@ -1962,6 +2002,11 @@ void LaunchShade(hipStream_t st, int mode, const DevScene &sc, const RenderParam
 void LaunchResolve(hipStream_t st, const DevScene &sc, const VertexStreams &vs, float4 *L, float4 *Lfinal, const uint32_t *queue,
                    const uint32_t *countPtr, uint32_t gridItems) {
     if (gridItems) hipLaunchKernelGGL(k_resolve, dim3(blocks_for(gridItems, 256)), dim3(256), 0, st, sc, vs, L, Lfinal, queue, countPtr);
+}
+void LaunchRepair(hipStream_t st, const VertexStreams &vs, float4 *L, float4 *Lfinal, const uint32_t *queue, uint32_t n, uint32_t *counts) {
+    if (n == 0) return;
+    if (counts) hipLaunchKernelGGL(k_repair<true>, dim3(blocks_for(n, 256)), dim3(256), 0, st, vs, L, Lfinal, queue, n, counts);
+    else hipLaunchKernelGGL(k_repair<false>, dim3(blocks_for(n, 256)), dim3(256), 0, st, vs, L, Lfinal, queue, n, counts);
 }
 void LaunchStoreRadiance(hipStream_t st, const float4 *Lfinal, float *LallR, float *LallG, float *LallB, uint32_t nPix, uint32_t s0,
                          uint32_t nSlots) {

@@ -75,6 +75,8 @@ struct HprtScene {
     // hprt_debug_shade_counts (tests): while on, every bounce also reads how many vertices the specialised shading variants deferred to the
     // generic bin and how many waited in the retry lists; sums since it was switched on
     bool shadeCountsOn = false; uint64_t shadeDeferred = 0, shadeRetried = 0;
+    // (the same switch) vertices whose light sample k_shade added at once, those of them k_repair set back, and full vertices (k_resolve)
+    uint64_t shadeSpeculated = 0, shadeRepaired = 0, shadeFull = 0;
     int poisonByte = -1;      // hprt_debug_poison_workspace (tests): fill every stream, queue and stack with this byte before each render
     hprt::DevBuf voxFunc, voxCdf, voxFuncInt, voxRi;      // SpatialLightDistribution tables (lightsamplestrategy "spatial")
     hprt::DevBuf voxSlot, voxRequest, voxRequestCount, retryQueues;      // on-demand mode: voxel -> table row, the request list, the vertices to shade again
