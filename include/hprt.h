@@ -196,7 +196,7 @@ typedef struct HprtRbspParams {
     int threads;        /* builder threads (0: OMP_NUM_THREADS, else 16; at most 16); the tree does not depend on it */
 } HprtRbspParams;
 /* params NULL: the scene's Accelerator line (baked models report "bvh" and get the defaults).  Models with object
- * instances: HPRT_E_UNSUPPORTED (no two-level RBSP walk).  A tree deeper than HPRT_RBSP_MAX_DEPTH: HPRT_E_UNSUPPORTED. */
+ * instances: HPRT_E_UNSUPPORTED (their two-level trees are opt-in: hprt_rbspinst_build).  A tree deeper than HPRT_RBSP_MAX_DEPTH: HPRT_E_UNSUPPORTED. */
 int hprt_rbsp_build(const HprtModel *m, const HprtRbspParams *params, HprtRbsp **out);
 /* The same over n triangles (9 floats each: three world-space vertices, creation order); params NULL: the defaults. */
 int hprt_rbsp_build_from_triangles(size_t n_tris, const float *p9, const HprtRbspParams *params, HprtRbsp **out);
@@ -270,6 +270,42 @@ int hprt_rbspkd_build_device(const HprtModel *m, const HprtRbspKdParams *params,
                              HprtRbspKd **out);
 int hprt_rbspkd_build_from_triangles_device(size_t n_tris, const float *p9, const HprtRbspKdParams *params, const HprtBuildDeviceOpts *opts,
                                             HprtBuildDeviceStats *stats, HprtRbspKd **out);
+
+/* ------------------------------------------------------------------------ */
+/* Two-level RBSP trees (Accelerator "rbsp" / "rbspkd" on a model with       */
+/* object instances).  Stands in for pbrtObjectInstance                      */
+/* (core/api.cpp:1794-1819): MakeAccelerator(renderOptions->AcceleratorName, */
+/* ...) over the primitives of every object that has more than one (an       */
+/* object with exactly one is wrapped as it is, :1798), each wrapped in a    */
+/* TransformedPrimitive, and pbrtWorldEnd's top-level accelerator over those */
+/* wrappers: an RBSP tree whose leaves hold RBSP trees.  Opt-in:             */
+/* hprt_rbsp_build and hprt_rbspkd_build keep refusing such models and the   */
+/* front end keeps their BVH and its warning.                                */
+/* ------------------------------------------------------------------------ */
+typedef struct HprtRbspInst HprtRbspInst;
+/* One RBSP tree per object with more than one primitive, over the object's primitives in object space, and the top-level tree
+ * over the top-level items in creation order; an instance is bounded by TransformedPrimitive::WorldBound
+ * (core/primitive.h:116-118) and projected through the 8 corners of that bound (Primitive::getBounds, core/primitive.h:72-80).
+ * Every tree takes the same parameters — params, or with NULL those of the scene's Accelerator line; maxdepth -1 resolves per
+ * tree from its own primitive count — so all share M and one direction table.  hprt_rbspkdinst_build builds kd-aware trees
+ * (RBSPKd's cost model); the handle remembers which.  HPRT_E_UNSUPPORTED for a model without instances (the job of
+ * hprt_rbsp_build / hprt_rbspkd_build), for an M that is not 3, 7, 9 or 13, and when depth(top) + deepest object depth + 1
+ * exceeds HPRT_RBSP_MAX_DEPTH: the walk keeps both levels' todo entries and one saved top-level position in one list.  The
+ * device-assisted build is not offered for these trees. */
+int hprt_rbspinst_build(const HprtModel *m, const HprtRbspParams *params, HprtRbspInst **out);
+int hprt_rbspkdinst_build(const HprtModel *m, const HprtRbspKdParams *params, HprtRbspInst **out);
+/* info[0..3] = nodes, leaves, primitive references, depth of the top-level tree; info[4] = object definitions, info[5] =
+ * object trees (objects with more than one primitive), info[6] = the deepest object tree's depth, info[7] = instances,
+ * info[8] = M (directions), info[9] = 1 for kd-aware trees */
+int hprt_rbspinst_info(const HprtRbspInst *t, uint32_t info[10]);
+/* info[0..3] as above for the tree of object definition `object`; all zero for an object of one primitive, which has no
+ * tree (core/api.cpp:1798). */
+int hprt_rbspinst_object_info(const HprtRbspInst *t, uint32_t object, uint32_t info[4]);
+/* The arrays of the top-level tree / of one object's tree, as hprt_rbsp_copy returns them (any may be NULL); the direction
+ * table is every tree's. */
+int hprt_rbspinst_copy(const HprtRbspInst *t, void *nodes8, uint32_t *prim_indices, float *directions);
+int hprt_rbspinst_object_copy(const HprtRbspInst *t, uint32_t object, void *nodes8, uint32_t *prim_indices);
+void hprt_rbspinst_destroy(HprtRbspInst *t);
 
 /* ------------------------------------------------------------------------ */
 /* General BSP tree (Accelerator "bsppaper").  Stands in for                */
@@ -550,8 +586,16 @@ int hprt_scene_attach_bsppaperkd(HprtScene *s, const HprtBspPaperKd *t);
  * whichever tree was attached before; an attach refused by these checks leaves the previous walk in place (a device failure
  * during the upload that follows them leaves the scene on its BVH). */
 int hprt_scene_attach_kdinst(HprtScene *s, const HprtKdInst *t);
+/* The same for two-level RBSP trees: RBSP::Intersect / IntersectP — for a handle of hprt_rbspkdinst_build RBSPKd::Intersect /
+ * IntersectP — on both levels, joined by TransformedPrimitive.  The checks are hprt_scene_attach_kdinst's with the RBSP tree's
+ * structural check and HPRT_RBSP_MAX_DEPTH; a scene without instances is HPRT_E_UNSUPPORTED.  Counters follow the rbsp scene's
+ * contract ([0] every node either walk visits, [1] the interior ones), summed over both levels; for kd-aware trees the kd
+ * share (interior nodes of direction < 3, both levels) comes from hprt_scene_kd_counters and hprt_pixel_kd_stats_read exactly
+ * as for an rbspkd scene, for plain trees those report zeros. */
+int hprt_scene_attach_rbspinst(HprtScene *s, const HprtRbspInst *t);
 /* kdTreeNodeTraversals (out[0]) and kdTreeNodeTraversalsP (out[1]) of the last counting trace (hprt_intersect / hprt_occluded
- * with counters) or counting render of an rbspkd or bsppaperkd scene; zeros for any other scene. */
+ * with counters) or counting render of an rbspkd or bsppaperkd scene, or of a scene with kd-aware two-level RBSP trees; zeros
+ * for any other scene. */
 int hprt_scene_kd_counters(HprtScene *s, uint64_t out[2]);
 
 /* ------------------------------------------------------------------------ */

@@ -328,6 +328,14 @@ def _load():
         "hprt_rbspkd_copy": (C.c_int, [vp, vp, vp, vp]),
         "hprt_rbspkd_destroy": (None, [vp]),
         "hprt_scene_attach_rbspkd": (C.c_int, [vp, vp]),
+        "hprt_rbspinst_build": (C.c_int, [vp, vp, P(vp)]),
+        "hprt_rbspkdinst_build": (C.c_int, [vp, vp, P(vp)]),
+        "hprt_rbspinst_info": (C.c_int, [vp, P(u32)]),
+        "hprt_rbspinst_object_info": (C.c_int, [vp, u32, P(u32)]),
+        "hprt_rbspinst_copy": (C.c_int, [vp, vp, vp, vp]),
+        "hprt_rbspinst_object_copy": (C.c_int, [vp, u32, vp, vp]),
+        "hprt_rbspinst_destroy": (None, [vp]),
+        "hprt_scene_attach_rbspinst": (C.c_int, [vp, vp]),
         "hprt_rbsp_build_device": (C.c_int, [vp, vp, vp, vp, P(vp)]),
         "hprt_rbsp_build_from_triangles_device": (C.c_int, [sz, vp, vp, vp, vp, P(vp)]),
         "hprt_rbspkd_build_device": (C.c_int, [vp, vp, vp, vp, P(vp)]),
@@ -622,6 +630,85 @@ class Rbsp(_Tree):
     directions = _Tree._directions
 
 
+class RbspInst:
+    """Two-level RBSP trees (host) of a model WITH object instances, as pbrtObjectInstance and pbrtWorldEnd build them under
+    Accelerator "rbsp" — or, with kd_aware, "rbspkd" — (core/api.cpp:1794-1819): one tree per object of more than one primitive
+    and the top-level tree over the top-level items, all with the same parameters.  RbspInst(model) takes the scene's Accelerator
+    line; giving n_directions makes the keyword parameters replace it, as for Rbsp / RbspKd.  Scene.attach_rbspinst walks them."""
+    _KEYS = ("nodes", "leaves", "prim_refs", "depth")
+
+    def __init__(self, model, kd_aware=False, n_directions=None, isect_cost=80, trav_cost=5, kd_trav_cost=1, empty_bonus=0.0, max_prims=1,
+                 max_depth=-1, threads=0):
+        h = C.c_void_p()
+        if kd_aware:
+            prm = None if n_directions is None else C.byref(RbspKdParams(isect_cost, trav_cost, kd_trav_cost, empty_bonus, max_prims, max_depth,
+                                                                           n_directions, threads))
+            _check(lib.hprt_rbspkdinst_build(model._h, prm, C.byref(h)))
+        else:
+            prm = None if n_directions is None else C.byref(_rbsp_params(n_directions, isect_cost, trav_cost, empty_bonus, max_prims, max_depth, threads))
+            _check(lib.hprt_rbspinst_build(model._h, prm, C.byref(h)))
+        self._h = h
+
+    def info(self):
+        """the top-level tree's nodes, leaves, prim_refs and depth; objects (definitions), object_trees (those with more than one
+        primitive), object_depth (the deepest object tree's), instances, M (directions of every tree) and kd_aware"""
+        i = (C.c_uint32 * 10)()
+        _check(lib.hprt_rbspinst_info(self._h, i))
+        return dict(zip(self._KEYS + ("objects", "object_trees", "object_depth", "instances", "M", "kd_aware"), i))
+
+    def object_info(self, obj):
+        """nodes, leaves, prim_refs and depth of the tree of object definition `obj`: all zero for an object of one primitive"""
+        i = (C.c_uint32 * 4)()
+        _check(lib.hprt_rbspinst_object_info(self._h, obj, i))
+        return dict(zip(self._KEYS, i))
+
+    def copy(self):
+        """(nodes [n, 2] uint32, prim_indices uint32) of the top-level tree, as Rbsp.arrays() gives them"""
+        inf = self.info()
+        nodes = np.zeros((inf["nodes"], 2), np.uint32); idx = np.zeros(inf["prim_refs"], np.uint32)
+        _check(lib.hprt_rbspinst_copy(self._h, _ptr(nodes), _ptr(idx), None))
+        return nodes, idx
+
+    def object_copy(self, obj):
+        """the same for the tree of object definition `obj` (empty arrays for an object of one primitive)"""
+        inf = self.object_info(obj)
+        nodes = np.zeros((inf["nodes"], 2), np.uint32); idx = np.zeros(inf["prim_refs"], np.uint32)
+        _check(lib.hprt_rbspinst_object_copy(self._h, obj, _ptr(nodes), _ptr(idx)))
+        return nodes, idx
+
+    def directions(self):
+        """[M, 3] float32: getDirections(M), the one table of every tree"""
+        d = np.zeros((self.info()["M"], 3), np.float32)
+        _check(lib.hprt_rbspinst_copy(self._h, None, None, _ptr(d)))
+        return d
+
+    def bounds(self, obj=-1):
+        """Diagnostics hook (not part of include/hprt.h): the six floats pMin, pMax of the top-level tree (obj < 0) or of one
+        object's tree."""
+        b = np.zeros(6, np.float32)
+        lib.hprt_debug_rbspinst_bounds.restype = C.c_int
+        lib.hprt_debug_rbspinst_bounds.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        _check(lib.hprt_debug_rbspinst_bounds(self._h, int(obj), _ptr(b)))
+        return b
+
+    def set_tree(self, obj, nodes, prim_indices, bounds):
+        """Diagnostics hook (not part of include/hprt.h): a tree made by hand in place of the top-level tree (obj < 0) or of one
+        object's tree, over the handle's M directions; it passes the checks a built handle passes (HprtError E_INVALID /
+        E_UNSUPPORTED, the handle unchanged)."""
+        nodes = np.ascontiguousarray(nodes, np.uint32); idx = np.ascontiguousarray(prim_indices, np.uint32).ravel()
+        b = np.ascontiguousarray(bounds, np.float32).ravel()
+        assert nodes.ndim == 2 and nodes.shape[1] == 2 and b.shape[0] == 6
+        fn = lib.hprt_debug_rbspinst_set_tree
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        _check(fn(self._h, int(obj), nodes.shape[0], _ptr(nodes), idx.shape[0], _ptr(idx), _ptr(b)))
+
+    def __del__(self):
+        if getattr(self, "_h", None) and lib is not None:      # (module globals are cleared at interpreter exit)
+            lib.hprt_rbspinst_destroy(self._h)
+            self._h = None
+
+
 class BspPaperParams(C.Structure):
     """HprtBspPaperParams: CreateBSPPaperTreeAccelerator's parameters plus the builder's thread count."""
     _fields_ = [("isect_cost", C.c_int), ("trav_cost", C.c_int), ("empty_bonus", C.c_float), ("max_prims", C.c_int),
@@ -826,6 +913,13 @@ class Scene:
         (a KdInst of the model the scene was made of).  Counters and pixel statistics follow the kd scene's, summed over both levels."""
         _check(lib.hprt_scene_attach_kdinst(self._h, kdinst._h))
         self._kdinst = kdinst
+
+    def attach_rbspinst(self, rbspinst):
+        """hprt_scene_attach_rbspinst: every later trace and render of this INSTANCED scene walks the two-level RBSP trees `rbspinst`
+        (an RbspInst of the model the scene was made of).  Counters and pixel statistics follow the rbsp scene's — for kd-aware trees
+        the rbspkd scene's, with kd_counters() and pixel_kd_stats() — summed over both levels."""
+        _check(lib.hprt_scene_attach_rbspinst(self._h, rbspinst._h))
+        self._rbspinst = rbspinst
 
     def attach_rbsp(self, rbsp):
         """hprt_scene_attach_rbsp: every later trace and render walks `rbsp` (built over this scene's primitives); replaces an

@@ -290,7 +290,9 @@ __attribute__((visibility("default"))) int hprt_debug_capture_rays(HprtScene *s,
 }
 static int ApiStreams(HprtScene *s, size_t n, RayStream *rays, HitStream *hits);
 // The walks that count their kd interior nodes apart (kdShare, pixelKdLocal / pixelKdFilm)
-static bool CountsKdShare(const HprtScene *s) { return s->walk == HprtScene::Walk::RbspKd || s->walk == HprtScene::Walk::BspPaperKd; }
+static bool CountsKdShare(const HprtScene *s) {
+    return s->walk == HprtScene::Walk::RbspKd || s->walk == HprtScene::Walk::BspPaperKd || s->walk == HprtScene::Walk::RbspKdInst;
+}
 // Every trace of a scene: the walk of the attached tree (AttachTree below), else the BVH walks (LaunchTrace)
 static void Trace(HprtScene *s, hipStream_t st, bool anyHit, bool count, const uint32_t *queue, const uint32_t *countPtr, uint32_t countImm,
                   uint32_t gridItems, const RayStream &rays, const HitStream &hits, uint8_t *occ, DevCounters *counters, uint32_t *workCounter,
@@ -311,6 +313,11 @@ static void Trace(HprtScene *s, hipStream_t st, bool anyHit, bool count, const u
         break;
     case HprtScene::Walk::KdInst:
         LaunchKdInstTrace(st, s->dev, s->kdinst, anyHit, count, queue, countPtr, countImm, gridItems, rays, hits, occ, counters, workCounter, rayStats);
+        break;
+    case HprtScene::Walk::RbspInst:
+    case HprtScene::Walk::RbspKdInst:
+        LaunchRbspInstTrace(st, s->dev, s->rbspinst, s->walk == HprtScene::Walk::RbspKdInst, anyHit, count, queue, countPtr, countImm, gridItems, rays, hits, occ,
+                            counters, workCounter, rayStats);
         break;
     case HprtScene::Walk::Bvh: LaunchTrace(st, s->dev, anyHit, count, queue, countPtr, countImm, gridItems, rays, hits, occ, counters, workCounter, rayStats); break;
     }
@@ -641,6 +648,85 @@ int hprt_scene_attach_kdinst(HprtScene *s, const HprtKdInst *t) try {
     FillTree(d, s, nodes.size(), prims.size(), t->top.bounds, topDepth + objectDepth + 1u);
     d.entries = s->kdInstEntries.as<DevKdInstEntry>(); d.nEntries = (uint32_t)entries.size();
     s->walk = HprtScene::Walk::KdInst;
+    return HPRT_OK;
+} catch (...) { return hprt::HandleException(); }
+
+// Two-level RBSP trees (pbrtObjectInstance under Accelerator "rbsp" / "rbspkd"): hprt_scene_attach_kdinst's steps with the RBSP
+// tree's check and node layout (M directions: off flag bits, leaves tagged M), the shared direction table and, for kd-aware trees,
+// the rbspkd walk's kd counter pair (device/rbspinst_walk.h).
+int hprt_scene_attach_rbspinst(HprtScene *s, const HprtRbspInst *t) try {
+    if (!s || !t) return SetError(HPRT_E_INVALID, "hprt_scene_attach_rbspinst: null argument");
+    if (!s->instanced)
+        return SetError(HPRT_E_UNSUPPORTED, "hprt_scene_attach_rbspinst: the scene has no object instances; attach its tree with hprt_scene_attach_rbsp / hprt_scene_attach_rbspkd");
+    HIP_TRY(hipSetDevice(s->device));
+    SceneCall call(s, nullptr);
+    const size_t nObjects = s->objectOrder.size();
+    if (t->objects.size() != nObjects || t->instanceObject != s->instanceObject)
+        return SetError(HPRT_E_INVALID, "the two-level RBSP tree holds " + std::to_string(t->objects.size()) + " objects and " + std::to_string(t->instanceObject.size()) +
+                                        " instances, the scene " + std::to_string(nObjects) + " and " + std::to_string(s->instanceObject.size()) + " (or they name other objects)");
+    if (t->top.nPrims != s->topOrder.size())
+        return SetError(HPRT_E_INVALID, "the top-level RBSP tree holds " + std::to_string(t->top.nPrims) + " primitives, the scene " + std::to_string(s->topOrder.size()));
+    const uint32_t M = t->top.M;
+    uint32_t topDepth = 0, objectDepth = 0;
+    uint64_t nNodes = t->top.nodes.size(), nIdx = t->top.primIndices.size();
+    const char *bad = CheckRbspTree(t->top, &topDepth);
+    if (*bad) return SetError(HPRT_E_INVALID, std::string("malformed top-level RBSP tree: ") + bad);
+    for (size_t o = 0; o < nObjects; ++o) {
+        const RbspTree &r = t->objects[o];
+        if (r.nPrims != s->objectOrder[o].size())
+            return SetError(HPRT_E_INVALID, "the RBSP tree of object " + std::to_string(o) + " holds " + std::to_string(r.nPrims) + " primitives, the scene's object " + std::to_string(s->objectOrder[o].size()));
+        if ((r.nPrims > 1) != !r.nodes.empty()) return SetError(HPRT_E_INVALID, "object " + std::to_string(o) + ": exactly the objects of more than one primitive have a tree");
+        if (r.M != M) return SetError(HPRT_E_INVALID, "object " + std::to_string(o) + ": its tree is over " + std::to_string(r.M) + " directions, the top-level tree over " + std::to_string(M));
+        nNodes += r.nodes.empty() ? 1u : r.nodes.size(); nIdx += r.primIndices.size();
+        if (r.nodes.empty()) continue;
+        uint32_t depth = 0;
+        bad = CheckRbspTree(r, &depth);
+        if (*bad) return SetError(HPRT_E_INVALID, "malformed RBSP tree of object " + std::to_string(o) + ": " + bad);
+        objectDepth = std::max(objectDepth, depth);
+    }
+    if ((uint64_t)topDepth + objectDepth + 1u > RBSP_TODO_MAX)
+        return SetError(HPRT_E_UNSUPPORTED, "two-level RBSP tree: top-level depth " + std::to_string(topDepth) + " + deepest object depth " + std::to_string(objectDepth) +
+                                            " + 1 is more than the walk's todo list holds (" + std::to_string((unsigned)RBSP_TODO_MAX) + ")");
+    const uint32_t off = RbspBitOffset(M), mask = RbspBitMask(M);
+    if (nNodes > (0xffffffffull >> off) || nIdx > 0xffffffffull) return SetError(HPRT_E_UNSUPPORTED, "two-level RBSP tree: more nodes over all trees than aboveChild can name");
+    std::vector<uint2> nodes; std::vector<uint32_t> prims;
+    nodes.reserve((size_t)nNodes); prims.reserve((size_t)nIdx);
+    auto append = [&](const RbspTree &r, const std::vector<uint32_t> &order, uint32_t primBase) {
+        return AppendTree(r.nodes, r.primIndices, InvertOrder(order, primBase), off, mask, M, &nodes, &prims);
+    };
+    append(t->top, s->topOrder, 0u);
+    std::vector<uint32_t> objectRoot(nObjects);
+    for (size_t o = 0; o < nObjects; ++o) {
+        const RbspTree &r = t->objects[o];
+        if (!r.nodes.empty()) objectRoot[o] = append(r, s->objectOrder[o], s->objectPrimBase[o]);
+        else {      // the lone primitive (or nothing: no instance names an empty object) as a one-primitive leaf
+            objectRoot[o] = (uint32_t)nodes.size();
+            nodes.push_back(make_uint2(s->objectPrimBase[o], M | ((r.nPrims ? 1u : 0u) << off)));
+        }
+    }
+    std::vector<DevRbspInstEntry> entries(t->instanceObject.size());
+    for (size_t i = 0; i < entries.size(); ++i) {
+        const size_t o = (size_t)t->instanceObject[i];
+        const RbspTree &r = t->objects[o];
+        DevRbspInstEntry &e = entries[i];
+        for (int a = 0; a < 3; ++a) { e.lo[a] = r.bounds[a]; e.hi[a] = r.bounds[3 + a]; }
+        e.root = objectRoot[o];
+        e.prim = r.nodes.empty() ? (int32_t)s->objectPrimBase[o] : -1;
+    }
+    if (int rc = UploadTree(s, nodes, prims)) return rc;
+    HIP_TRY(upload(s->kdInstEntries, entries));
+    if (t->kdAware) {
+        HIP_TRY(s->kdShare.alloc(2 * sizeof(unsigned long long)));
+        HIP_TRY(hipMemset(s->kdShare.p, 0, 2 * sizeof(unsigned long long)));
+    }
+    s->rbspinst = DevRbspInst{};
+    DevRbspInst &d = s->rbspinst;
+    FillTree(d, s, nodes.size(), prims.size(), t->top.bounds, topDepth + objectDepth + 1u);
+    d.entries = s->kdInstEntries.as<DevRbspInstEntry>(); d.nEntries = (uint32_t)entries.size();
+    d.M = M; d.off = off; d.mask = mask;
+    for (uint32_t k = 0; k < 3 * M; ++k) d.dirs[k] = t->top.directions[k];
+    d.kdCounters = t->kdAware ? s->kdShare.as<unsigned long long>() : nullptr;
+    s->walk = t->kdAware ? HprtScene::Walk::RbspKdInst : HprtScene::Walk::RbspInst;
     return HPRT_OK;
 } catch (...) { return hprt::HandleException(); }
 
@@ -1229,6 +1315,11 @@ int hprt_pixel_stats_read(HprtScene *s, uint64_t *out7, size_t n_pixels) try {
 int hprt_pixel_kd_stats_read(HprtScene *s, uint64_t *out2, size_t n_pixels) try {
     if (!s || !out2) return SetError(HPRT_E_INVALID, "hprt_pixel_kd_stats_read: null argument");
     SceneCall call(s, nullptr);
+    if (!s->pixelKdValid && s->walk == HprtScene::Walk::RbspInst && s->pixelStatsValid) {      // plain two-level RBSP trees: no node is a kd node
+        if (n_pixels != s->filmPixels) return SetError(HPRT_E_INVALID, "hprt_pixel_kd_stats_read: pixel count differs from the last render's film");
+        memset(out2, 0, 2 * n_pixels * sizeof(uint64_t));
+        return HPRT_OK;
+    }
     if (!s->pixelKdValid) return SetError(HPRT_E_INVALID, "no per-pixel kd statistics: render an rbspkd or bsppaperkd scene with HPRT_RENDER_PIXEL_STATS first");
     if (n_pixels != s->filmPixels) return SetError(HPRT_E_INVALID, "hprt_pixel_kd_stats_read: pixel count differs from the last render's film");
     HIP_TRY(hipSetDevice(s->device));

@@ -85,17 +85,21 @@ struct RbspHook {
 // candidates do
 constexpr uint32_t kDeviceMinCandidates = 1024;
 
+// HprtRbspParams / HprtRbspKdParams over the Accelerator line's (or the defaults'); params NULL keeps *p
+template <typename Params>
+void ApplyRbspParams(const Params *params, RbspParams *p) {
+    if (!params) return;
+    p->isectCost = params->isect_cost; p->travCost = params->trav_cost; p->emptyBonus = params->empty_bonus;
+    p->maxPrims = params->max_prims; p->maxDepth = params->max_depth; p->nDirections = params->n_directions; p->threads = params->threads;
+    if constexpr (std::is_same<Params, HprtRbspKdParams>::value) p->kdTravCost = params->kd_trav_cost;
+}
 template <typename Handle, typename Params>
 int BuildRbsp(size_t n, const float *lo, const float *hi, const float *tri9, const uint8_t *isTri, const Params *params, RbspParams p,
                      Handle **out, const RbspHook *hook = nullptr) {
     constexpr bool kdAware = std::is_same<Handle, HprtRbspKd>::value;
     p.kdAware = kdAware;
     *out = nullptr;
-    if (params) {
-        p.isectCost = params->isect_cost; p.travCost = params->trav_cost; p.emptyBonus = params->empty_bonus;
-        p.maxPrims = params->max_prims; p.maxDepth = params->max_depth; p.nDirections = params->n_directions; p.threads = params->threads;
-        if constexpr (kdAware) p.kdTravCost = params->kd_trav_cost;
-    }
+    ApplyRbspParams(params, &p);
     if (p.nDirections != 3 && p.nDirections != 7 && p.nDirections != 9 && p.nDirections != 13)
         return SetError(HPRT_E_UNSUPPORTED, "nbDirections " + std::to_string(p.nDirections) + " is not supported (3, 7, 9 or 13)");
     std::unique_ptr<Handle> t(new Handle());
@@ -174,6 +178,97 @@ int RbspCopy(const char *fn, const RbspTree *t, void *nodes8, uint32_t *primIndi
     if (primIndices && !t->primIndices.empty()) memcpy(primIndices, t->primIndices.data(), t->primIndices.size() * 4);
     if (directions) memcpy(directions, t->directions.data(), t->directions.size() * 4);
     return HPRT_OK;
+}
+
+// ---- two-level RBSP trees (hprt_rbspinst_* below; pbrtObjectInstance, core/api.cpp:1794-1819, under Accelerator "rbsp" / "rbspkd") ----
+// tri9 / isTri as BuildRbspTree takes them, for the n primitives of the top level (object < 0; an instance is no triangle: its
+// projections are those of its world bound's corners, Primitive::getBounds, core/primitive.h:72-80) or of one object, in the order
+// of ComputePrimBounds / ComputeObjectPrimBounds
+void RbspPrimTriangles(const SceneModel &sc, int object, size_t n, std::vector<float> *tri9, std::vector<uint8_t> *isTri) {
+    tri9->assign(9 * n, 0.f);
+    isTri->assign(n, 0);
+    size_t k = 0;
+    auto shape = [&](const ShapeDesc &sh) {
+        if (sh.kind != kTriangleMesh) { ++k; return; }
+        const MeshData &md = sh.mesh;
+        for (uint32_t tr = 0; tr < md.nTris(); ++tr, ++k) {
+            for (int v = 0; v < 3; ++v) memcpy(&(*tri9)[9 * k + 3 * v], &md.P[3 * (size_t)md.indices[3 * tr + v]], 12);
+            (*isTri)[k] = 1;
+        }
+    };
+    if (object < 0) {
+        for (const TopItem &ti : sc.top) { if (ti.kind == 0) shape(sc.shapes[ti.index]); else ++k; }
+    } else {
+        for (const ShapeDesc &sh : sc.shapes) if (sh.object == object) shape(sh);
+    }
+}
+// The walk keeps the top-level tree's todo entries, one saved top-level position and the object tree's entries in one list of
+// RBSP_TODO_MAX entries (device/bspinst_walk.h)
+int CheckRbspInstDepth(const HprtRbspInst &t) {
+    uint32_t deepest = 0;
+    for (const RbspTree &o : t.objects) if (!o.nodes.empty()) deepest = std::max(deepest, o.depth);
+    if ((uint64_t)t.top.depth + deepest + 1u > RBSP_TODO_MAX)
+        return SetError(HPRT_E_UNSUPPORTED, "two-level RBSP tree: top-level depth " + std::to_string(t.top.depth) + " + deepest object depth " + std::to_string(deepest) +
+                                            " + 1 is more than the device walk's todo list holds (" + std::to_string((unsigned)RBSP_TODO_MAX) + " entries); lower \"maxdepth\"");
+    return HPRT_OK;
+}
+// hprt_rbspinst_build / hprt_rbspkdinst_build: one RbspTree per object of more than one primitive, over the object's primitives in
+// object space, and the top-level tree over the top-level items, an instance bounded by TransformedPrimitive::WorldBound; p: the
+// Accelerator line.  The device-assisted build (costFn) is not wired in.
+template <typename Params>
+int BuildRbspInst(const char *fn, const HprtModel *m, const Params *params, RbspParams p, HprtRbspInst **out) {
+    if (out) *out = nullptr;
+    if (!m || !out) return SetError(HPRT_E_INVALID, std::string(fn) + ": null argument");
+    const SceneModel &sc = m->sc;
+    if (sc.instances.empty())
+        return SetError(HPRT_E_UNSUPPORTED, std::string(fn) + ": the model has no object instances; build its tree with hprt_rbsp_build / hprt_rbspkd_build");
+    p.kdAware = std::is_same<Params, HprtRbspKdParams>::value;
+    ApplyRbspParams(params, &p);
+    if (p.nDirections != 3 && p.nDirections != 7 && p.nDirections != 9 && p.nDirections != 13)
+        return SetError(HPRT_E_UNSUPPORTED, "nbDirections " + std::to_string(p.nDirections) + " is not supported (3, 7, 9 or 13)");
+    std::unique_ptr<HprtRbspInst> t(new HprtRbspInst());
+    t->kdAware = p.kdAware;
+    for (const InstanceDesc &in : sc.instances) t->instanceObject.push_back(in.object);
+    t->objects.resize(sc.nObjects);
+    // TransformedPrimitive::WorldBound needs the wrapped primitive's bounds: the object accelerator's (the union of its primitives'
+    // bounds), or the lone primitive's own — one-node trees that hold them, which is all ComputePrimBounds reads (bvh_builder.h)
+    std::vector<BvhTree> objectBounds(sc.nObjects);
+    std::vector<float> lo, hi, tri9;
+    std::vector<uint8_t> isTri;
+    for (uint32_t o = 0; o < sc.nObjects; ++o) {
+        ComputeObjectPrimBounds(sc, (int)o, &lo, &hi);
+        const size_t n = lo.size() / 3;
+        if (n > 0x3fffffffull) return SetError(HPRT_E_UNSUPPORTED, "more than 2^30 primitives");
+        RbspTree &r = t->objects[o];
+        if (n > 1) {      // (core/api.cpp:1798: only more than one primitive gets an accelerator)
+            RbspPrimTriangles(sc, (int)o, n, &tri9, &isTri);
+            const std::string err = BuildRbspTree(n, lo.data(), hi.data(), tri9.data(), isTri.data(), p, &r);
+            if (!err.empty()) return SetError(HPRT_E_UNSUPPORTED, "object " + std::to_string(o) + ": " + err);
+        } else {
+            r.nPrims = (uint32_t)n; r.M = (uint32_t)p.nDirections;
+            RbspDirections(r.M, &r.directions);
+            for (int a = 0; a < 3 && n; ++a) { r.bounds[a] = lo[a]; r.bounds[3 + a] = hi[a]; }
+        }
+        if (n == 0) continue;
+        BvhNode box;
+        for (int a = 0; a < 3; ++a) { box.bmin[a] = lo[a]; box.bmax[a] = hi[a]; }
+        for (size_t i = 1; i < n; ++i)
+            for (int a = 0; a < 3; ++a) { box.bmin[a] = sel_min(box.bmin[a], lo[3 * i + a]); box.bmax[a] = sel_max(box.bmax[a], hi[3 * i + a]); }
+        box.offset = 0; box.countAxis = 3u;
+        objectBounds[o].nodes.push_back(box);
+    }
+    ComputePrimBounds(sc, objectBounds, &lo, &hi);
+    const size_t n = lo.size() / 3;
+    if (n > 0x3fffffffull) return SetError(HPRT_E_UNSUPPORTED, "more than 2^30 primitives");
+    RbspPrimTriangles(sc, -1, n, &tri9, &isTri);
+    const std::string err = BuildRbspTree(n, lo.data(), hi.data(), tri9.data(), isTri.data(), p, &t->top);
+    if (!err.empty()) return SetError(HPRT_E_UNSUPPORTED, "top level: " + err);
+    if (int rc = CheckRbspInstDepth(*t)) return rc;
+    *out = t.release();
+    return HPRT_OK;
+}
+void RbspTreeInfo(const RbspTree &r, uint32_t info[4]) {
+    info[0] = (uint32_t)r.nodes.size(); info[1] = r.nodes.empty() ? 0u : r.leaves; info[2] = (uint32_t)r.primIndices.size(); info[3] = r.nodes.empty() ? 0u : r.depth;
 }
 
 // ---- the general BSP handles' builds and copies (hprt_bsppaper_* and hprt_bsppaperkd_* below) ----
@@ -668,6 +763,66 @@ int hprt_rbspkd_copy(const HprtRbspKd *t, void *nodes8, uint32_t *primIndices, f
 } catch (...) { return hprt::HandleException(); }
 void hprt_rbspkd_destroy(HprtRbspKd *t) { delete t; }
 // ---- the device-assisted builds: the same builder with its candidates costed by k_kdopcost (device/kdop_cost.hip) ----
+// ---- two-level RBSP trees (Accelerator "rbsp" / "rbspkd" over object instances; helpers above) ----
+int hprt_rbspinst_build(const HprtModel *m, const HprtRbspParams *params, HprtRbspInst **out) try {
+    return BuildRbspInst("hprt_rbspinst_build", m, params, m ? m->sc.opt.rbsp : RbspParams(), out);
+} catch (...) { return hprt::HandleException(); }
+int hprt_rbspkdinst_build(const HprtModel *m, const HprtRbspKdParams *params, HprtRbspInst **out) try {
+    return BuildRbspInst("hprt_rbspkdinst_build", m, params, m ? m->sc.opt.rbspkd : RbspParams(), out);
+} catch (...) { return hprt::HandleException(); }
+int hprt_rbspinst_info(const HprtRbspInst *t, uint32_t info[10]) try {
+    if (!t || !info) return SetError(HPRT_E_INVALID, "hprt_rbspinst_info: null argument");
+    RbspTreeInfo(t->top, info);
+    info[4] = (uint32_t)t->objects.size(); info[5] = 0; info[6] = 0; info[7] = (uint32_t)t->instanceObject.size();
+    for (const RbspTree &o : t->objects) if (!o.nodes.empty()) { ++info[5]; info[6] = std::max(info[6], o.depth); }
+    info[8] = t->top.M; info[9] = t->kdAware ? 1u : 0u;
+    return HPRT_OK;
+} catch (...) { return hprt::HandleException(); }
+int hprt_rbspinst_object_info(const HprtRbspInst *t, uint32_t object, uint32_t info[4]) try {
+    if (!t || !info) return SetError(HPRT_E_INVALID, "hprt_rbspinst_object_info: null argument");
+    if (object >= t->objects.size()) return SetError(HPRT_E_INVALID, "hprt_rbspinst_object_info: object index out of range");
+    RbspTreeInfo(t->objects[object], info);
+    return HPRT_OK;
+} catch (...) { return hprt::HandleException(); }
+int hprt_rbspinst_copy(const HprtRbspInst *t, void *nodes8, uint32_t *primIndices, float *directions) try {
+    return RbspCopy("hprt_rbspinst_copy", t ? &t->top : nullptr, nodes8, primIndices, directions);
+} catch (...) { return hprt::HandleException(); }
+int hprt_rbspinst_object_copy(const HprtRbspInst *t, uint32_t object, void *nodes8, uint32_t *primIndices) try {
+    if (!t) return SetError(HPRT_E_INVALID, "hprt_rbspinst_object_copy: null argument");
+    if (object >= t->objects.size()) return SetError(HPRT_E_INVALID, "hprt_rbspinst_object_copy: object index out of range");
+    return RbspCopy("hprt_rbspinst_object_copy", &t->objects[object], nodes8, primIndices, nullptr);
+} catch (...) { return hprt::HandleException(); }
+void hprt_rbspinst_destroy(HprtRbspInst *t) { delete t; }
+// Diagnostics hooks (not part of include/hprt.h; tests): the bounds of the top-level tree (object < 0) or of one object's tree, and
+// a tree made by hand in place of the built one — nodes8 / idx as hprt_rbspinst_copy writes them, bounds6 pMin then pMax — so that
+// trees with a known todo depth reach the walk.  The tree keeps its primitive count, M and direction table and passes the
+// structural check and the two-level depth rule a built handle passes (HPRT_E_INVALID, HPRT_E_UNSUPPORTED; the handle is unchanged
+// when refused).
+__attribute__((visibility("default"))) int hprt_debug_rbspinst_bounds(const HprtRbspInst *t, int object, float bounds6[6]) try {
+    if (!t || !bounds6 || object >= (int)t->objects.size()) return SetError(HPRT_E_INVALID, "hprt_debug_rbspinst_bounds: bad argument");
+    memcpy(bounds6, (object < 0 ? t->top : t->objects[object]).bounds, 6 * sizeof(float));
+    return HPRT_OK;
+} catch (...) { return hprt::HandleException(); }
+__attribute__((visibility("default"))) int hprt_debug_rbspinst_set_tree(HprtRbspInst *t, int object, size_t n_nodes, const uint32_t *nodes8, size_t n_idx,
+                                                                         const uint32_t *idx, const float *bounds6) try {
+    if (!t || !nodes8 || !bounds6 || (n_idx && !idx) || object >= (int)t->objects.size()) return SetError(HPRT_E_INVALID, "hprt_debug_rbspinst_set_tree: bad argument");
+    RbspTree &dst = object < 0 ? t->top : t->objects[object];
+    if (object >= 0 && dst.nPrims < 2) return SetError(HPRT_E_INVALID, "hprt_debug_rbspinst_set_tree: an object of one primitive has no tree");
+    RbspTree r;
+    r.nPrims = dst.nPrims; r.M = dst.M; r.directions = dst.directions;
+    r.nodes.resize(n_nodes);
+    memcpy(r.nodes.data(), nodes8, n_nodes * sizeof(RbspNode));
+    r.primIndices.assign(idx, idx + n_idx);
+    memcpy(r.bounds, bounds6, sizeof(r.bounds));
+    const char *bad = CheckRbspTree(r, &r.depth);
+    if (*bad) return SetError(HPRT_E_INVALID, std::string("malformed tree: ") + bad);
+    r.maxDepth = r.depth; r.leaves = CountLeaves(r.nodes, RbspBitMask(r.M), r.M);
+    RbspTree old = std::move(dst);
+    dst = std::move(r);
+    if (int rc = CheckRbspInstDepth(*t)) { dst = std::move(old); return rc; }
+    return HPRT_OK;
+} catch (...) { return hprt::HandleException(); }
+
 int hprt_rbsp_build_device(const HprtModel *m, const HprtRbspParams *params, const HprtBuildDeviceOpts *opts, HprtBuildDeviceStats *stats, HprtRbsp **out) try {
     RbspHook h; h.device = true; h.opts = opts; h.stats = stats;
     return BuildRbspFromModel("hprt_rbsp_build_device", "RBSP", m, params, m ? m->sc.opt.rbsp : RbspParams(), out, &h);

@@ -14,6 +14,7 @@
 #include "device/bsppaper_walk.h"
 #include "device/bsppaperkd_walk.h"
 #include "device/kdinst_walk.h"
+#include "device/rbspinst_walk.h"
 #include "hprt_internal.h"
 
 #define HIP_TRY(expr)                                                                                   \
@@ -103,7 +104,7 @@ struct HprtScene {
     // counter pair (DevRbspKd / DevBspPaperKd::kdCounters); pixelKdLocal / pixelKdFilm: their per-pixel kd share of HPRT_RENDER_PIXEL_STATS.
     // topOrder keeps the top-level prim_order (ordered -> creation number) to map a tree's creation-order primitives; instanced:
     // no tree walk
-    enum class Walk { Bvh, Kd, Rbsp, RbspKd, BspPaper, BspPaperKd, KdInst } walk = Walk::Bvh;
+    enum class Walk { Bvh, Kd, Rbsp, RbspKd, BspPaper, BspPaperKd, KdInst, RbspInst, RbspKdInst } walk = Walk::Bvh;
     hprt::DevBuf treeNodes, treePrims, treeAxes; hprt::DevKd kd{}; hprt::DevRbsp rbsp{}; hprt::DevBspPaper bsppaper{};
     hprt::DevBuf kdShare, pixelKdLocal, pixelKdFilm; bool pixelKdValid = false;
     std::vector<uint32_t> topOrder; bool instanced = false;
@@ -113,6 +114,9 @@ struct HprtScene {
     // objectOrder / objectPrimBase map an object tree's creation-order primitives as topOrder maps the top level's; instanceObject:
     // each instance's object definition
     hprt::DevBuf kdInstEntries; hprt::DevKdInst kdinst{};
+    // Two-level RBSP trees (hprt_scene_attach_rbspinst; Walk::RbspInst, or Walk::RbspKdInst for kd-aware trees): the same layout with
+    // one DevRbspInstEntry per instance in kdInstEntries; kd-aware trees count their kd share in kdShare as the rbspkd walk does
+    hprt::DevRbspInst rbspinst{};
     std::vector<std::vector<uint32_t>> objectOrder; std::vector<uint32_t> objectPrimBase; std::vector<int32_t> instanceObject;
     ~HprtScene() { if (hostCounts) (void)hipHostFree(hostCounts); if (lastUse) (void)hipEventDestroy(lastUse); }
 };

@@ -25,6 +25,14 @@ struct HprtKdInst {
 };
 struct HprtRbsp { hprt::RbspTree tree; };
 struct HprtRbspKd { hprt::RbspTree tree; };     // built with RbspParams::kdAware
+// Two-level RBSP trees (pbrtObjectInstance under Accelerator "rbsp" / "rbspkd"): HprtKdInst's shape over RbspTrees.  One handle
+// type for both cost models; every tree is built with the same parameters, so all share M and the direction table.
+struct HprtRbspInst {
+    hprt::RbspTree top;
+    std::vector<hprt::RbspTree> objects;      // objects[o].nPrims: the object's primitives, tree (nodes) or not
+    std::vector<int32_t> instanceObject;      // per instance, its object definition
+    bool kdAware = false;                     // built by hprt_rbspkdinst_build: walked with the kd form at axis nodes
+};
 struct HprtBspPaper { hprt::BspPaperTree tree; };
 struct HprtBspPaperKd { hprt::BspPaperTree tree; };     // built with BspPaperParams::kdAware
 
