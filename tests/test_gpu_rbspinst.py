@@ -1,7 +1,8 @@
 """The two-level RBSP walks on the GPU (hprt_scene_attach_rbspinst, k_rbspinstwalk): closest and any hit held bit for bit to the
 test-side restatement of RBSP / RBSPKd on both levels joined by TransformedPrimitive (tests/rbspinst_reference.cpp) — t, primitive,
 instance, barycentrics, the four counters, the kd share — on a scene of our own, on tests/golden/simple_instanced.hprt, on a scene
-of ties and on the deep pair of staircases; a render against the BVH's film and the restatement's per-pixel sums; kernel resources.
+of ties and on the deep pair of staircases; a render against the BVH's film and the restatement's per-pixel sums; kernel resources;
+and, on one scene, the two-level kd-trees, RBSP trees and kd-trees again, for what the two attaches share.
 Every case runs plain at M = 13 and kd-aware at M = 9."""
 import os
 
@@ -10,9 +11,12 @@ import pytest
 
 from conftest import GOLDEN
 import deep_todo
+import kdinst_ref
+import kdinst_scenes as ks
 import rbspinst_ref
 import rbspinst_scenes as rs
 import tree_walk_checks as twc
+from test_gpu_kdinst import check_parity as check_kd_parity
 
 pytestmark = pytest.mark.gpu
 SIMPLE_INSTANCED = os.path.join(GOLDEN, "simple_instanced.hprt")
@@ -30,14 +34,18 @@ class _Case:
         self.oracle = orc.OracleScene(path)
 
     def rays(self, n, seed):
-        """n camera rays and n random rays from inside and around the top-level bounds, finite and infinite (test_gpu_kdinst._Case.rays)"""
-        rng = np.random.default_rng(seed)
-        b = self.ref.tree_bounds()
-        blo, ext = b[:3], b[3:] - b[:3]
-        x0, y0, x1, y1 = self.m.options.film_bounds()
-        oc, dc = self.oracle.camera_rays(rng.integers(x0, x1, n).astype(np.int32), rng.integers(y0, y1, n).astype(np.int32), rng.integers(0, 2, n).astype(np.int64))
-        o, d, tm = twc.random_rays(rng, blo, ext, n)
-        return np.concatenate([oc, o]).astype(np.float32), np.concatenate([dc, d]).astype(np.float32), np.concatenate([np.full(n, np.inf, np.float32), tm])
+        return _rays(self.m, self.ref, self.oracle, n, seed)
+
+
+def _rays(m, ref, oracle, n, seed):
+    """n camera rays and n random rays from inside and around the top-level bounds, finite and infinite (test_gpu_kdinst._Case.rays)"""
+    rng = np.random.default_rng(seed)
+    b = ref.tree_bounds()
+    blo, ext = b[:3], b[3:] - b[:3]
+    x0, y0, x1, y1 = m.options.film_bounds()
+    oc, dc = oracle.camera_rays(rng.integers(x0, x1, n).astype(np.int32), rng.integers(y0, y1, n).astype(np.int32), rng.integers(0, 2, n).astype(np.int64))
+    o, d, tm = twc.random_rays(rng, blo, ext, n)
+    return np.concatenate([oc, o]).astype(np.float32), np.concatenate([dc, d]).astype(np.float32), np.concatenate([np.full(n, np.inf, np.float32), tm])
 
 
 def check_parity(sc, ref, o, d, tm):
@@ -181,6 +189,25 @@ def test_attach_refusals(hprt, own, tmp_path):
     with pytest.raises(hprt.HprtError) as e:
         hprt.Scene(plain, hprt.Bvh(plain), device=0).attach_rbspinst(own.trees)
     assert e.value.code == hprt.E_UNSUPPORTED
+
+
+def test_kd_then_rbspkd_then_kd_trees_on_one_scene(hprt, orc, tmp_path):
+    """What the two attaches share — the entry buffer, the kd counter pair, the reset descriptor — across a change of walk: on ONE
+    scene (tests/kdinst_scenes.py's) the two-level kd-trees, then kd-aware two-level RBSP trees over the same model, then the
+    kd-trees again, each held to its restatement bit for bit"""
+    m, path = ks.bake(hprt, tmp_path, ks.scene_text(), "scene")
+    kd, rb = hprt.KdInst(m), hprt.RbspInst(m, kd_aware=True, n_directions=9)
+    kd_ref = kdinst_ref.KdInstScene(path).take(kd)
+    rb_ref = rbspinst_ref.RbspInstScene(path, 9, True).take(rb)
+    o, d, tm = _rays(m, rb_ref, orc.OracleScene(path), 256, 6)
+    sc = hprt.Scene(m, hprt.Bvh(m), device=0)
+    sc.attach_kdinst(kd)
+    check_kd_parity(sc, kd_ref, o, d, tm)
+    sc.attach_rbspinst(rb)
+    check_parity(sc, rb_ref, o, d, tm)
+    sc.attach_kdinst(kd)
+    check_kd_parity(sc, kd_ref, o, d, tm)
+    assert sc.kd_counters() == (0, 0)
 
 
 def _flags(name, kernel):

@@ -360,7 +360,12 @@ def _load():
         "hprt_pixel_kd_stats_read": (C.c_int, [vp, vp, sz]),
         "hprt_write_pixel_stats_rbspkd": (C.c_int, [cp, vp, vp, C.c_int, C.c_int]),
     }
-    for name, (res, args) in sig.items():
+    # the two-level handles' diagnostics hooks (not part of include/hprt.h, so not among EXPORTS)
+    debug = {}
+    for prefix in ("kdinst", "rbspinst"):
+        debug["hprt_debug_%s_bounds" % prefix] = (C.c_int, [vp, C.c_int, vp])
+        debug["hprt_debug_%s_set_tree" % prefix] = (C.c_int, [vp, C.c_int, sz, vp, sz, vp, vp])
+    for name, (res, args) in list(sig.items()) + list(debug.items()):
         fn = getattr(lib, name)   # raises AttributeError if an export is missing
         fn.restype = res
         fn.argtypes = args
@@ -523,68 +528,77 @@ class KdTree(_Tree):
         return KdTree._from_arrays(nodes, prim_indices, n_prims, bounds)
 
 
-class KdInst:
-    """Two-level kd-trees (host) of a model WITH object instances, as pbrtObjectInstance and pbrtWorldEnd build them under
-    Accelerator "kdtree" (core/api.cpp:1794-1819): one kd-tree per object of more than one primitive and the top-level kd-tree
-    over the top-level items, all with the parameters of the scene's Accelerator line.  Scene.attach_kdinst walks them."""
+class _TwoLevel:
+    """Two-level trees (host) of a model WITH object instances (KdInst, RbspInst) over the C calls hprt_<_prefix>_info /
+    _object_info / _copy / _object_copy / _destroy and the diagnostics hooks hprt_debug_<_prefix>_bounds / _set_tree; info() names
+    the words after the eight every handle has `_extra_keys`, and the copy of the RBSP trees takes a direction table as well."""
+    _prefix = None
+    _extra_keys = ()
     _KEYS = ("nodes", "leaves", "prim_refs", "depth")
 
-    def __init__(self, model):
-        h = C.c_void_p()
-        _check(lib.hprt_kdinst_build(model._h, C.byref(h)))
-        self._h = h
+    def _fn(self, name, debug=False):
+        return getattr(lib, "hprt_%s%s_%s" % ("debug_" if debug else "", self._prefix, name))
 
     def info(self):
         """the top-level tree's nodes, leaves, prim_refs and depth; objects (definitions), object_trees (those with more than one
-        primitive), object_depth (the deepest object tree's) and instances"""
-        i = (C.c_uint32 * 8)()
-        _check(lib.hprt_kdinst_info(self._h, i))
-        return dict(zip(self._KEYS + ("objects", "object_trees", "object_depth", "instances"), i))
+        primitive), object_depth (the deepest object tree's) and instances; RbspInst: M (directions of every tree) and kd_aware"""
+        keys = self._KEYS + ("objects", "object_trees", "object_depth", "instances") + self._extra_keys
+        i = (C.c_uint32 * len(keys))()
+        _check(self._fn("info")(self._h, i))
+        return dict(zip(keys, i))
 
     def object_info(self, obj):
         """nodes, leaves, prim_refs and depth of the tree of object definition `obj`: all zero for an object of one primitive"""
         i = (C.c_uint32 * 4)()
-        _check(lib.hprt_kdinst_object_info(self._h, obj, i))
+        _check(self._fn("object_info")(self._h, obj, i))
         return dict(zip(self._KEYS, i))
 
     def copy(self):
-        """(nodes [n, 2] uint32, prim_indices uint32) of the top-level tree, as KdTree.arrays() gives them"""
+        """(nodes [n, 2] uint32, prim_indices uint32) of the top-level tree, as KdTree.arrays() / Rbsp.arrays() give them"""
         inf = self.info()
         nodes = np.zeros((inf["nodes"], 2), np.uint32); idx = np.zeros(inf["prim_refs"], np.uint32)
-        _check(lib.hprt_kdinst_copy(self._h, _ptr(nodes), _ptr(idx)))
+        _check(self._fn("copy")(self._h, _ptr(nodes), _ptr(idx), *([None] if "M" in inf else [])))
         return nodes, idx
 
     def object_copy(self, obj):
         """the same for the tree of object definition `obj` (empty arrays for an object of one primitive)"""
         inf = self.object_info(obj)
         nodes = np.zeros((inf["nodes"], 2), np.uint32); idx = np.zeros(inf["prim_refs"], np.uint32)
-        _check(lib.hprt_kdinst_object_copy(self._h, obj, _ptr(nodes), _ptr(idx)))
+        _check(self._fn("object_copy")(self._h, obj, _ptr(nodes), _ptr(idx)))
         return nodes, idx
 
     def bounds(self, obj=-1):
         """Diagnostics hook (not part of include/hprt.h): the six floats pMin, pMax of the top-level tree (obj < 0) or of one
         object's tree."""
         b = np.zeros(6, np.float32)
-        lib.hprt_debug_kdinst_bounds.restype = C.c_int
-        lib.hprt_debug_kdinst_bounds.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-        _check(lib.hprt_debug_kdinst_bounds(self._h, int(obj), _ptr(b)))
+        _check(self._fn("bounds", debug=True)(self._h, int(obj), _ptr(b)))
         return b
 
     def set_tree(self, obj, nodes, prim_indices, bounds):
         """Diagnostics hook (not part of include/hprt.h): a tree made by hand in place of the top-level tree (obj < 0) or of one
-        object's tree; it passes the checks a built handle passes (HprtError E_INVALID / E_UNSUPPORTED, the handle unchanged)."""
+        object's tree — for an RbspInst over the handle's M directions; it passes the checks a built handle passes (HprtError
+        E_INVALID / E_UNSUPPORTED, the handle unchanged)."""
         nodes = np.ascontiguousarray(nodes, np.uint32); idx = np.ascontiguousarray(prim_indices, np.uint32).ravel()
         b = np.ascontiguousarray(bounds, np.float32).ravel()
         assert nodes.ndim == 2 and nodes.shape[1] == 2 and b.shape[0] == 6
-        fn = lib.hprt_debug_kdinst_set_tree
-        fn.restype = C.c_int
-        fn.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
-        _check(fn(self._h, int(obj), nodes.shape[0], _ptr(nodes), idx.shape[0], _ptr(idx), _ptr(b)))
+        _check(self._fn("set_tree", debug=True)(self._h, int(obj), nodes.shape[0], _ptr(nodes), idx.shape[0], _ptr(idx), _ptr(b)))
 
     def __del__(self):
         if getattr(self, "_h", None) and lib is not None:      # (module globals are cleared at interpreter exit)
-            lib.hprt_kdinst_destroy(self._h)
+            self._fn("destroy")(self._h)
             self._h = None
+
+
+class KdInst(_TwoLevel):
+    """Two-level kd-trees (host) of a model WITH object instances, as pbrtObjectInstance and pbrtWorldEnd build them under
+    Accelerator "kdtree" (core/api.cpp:1794-1819): one kd-tree per object of more than one primitive and the top-level kd-tree
+    over the top-level items, all with the parameters of the scene's Accelerator line.  Scene.attach_kdinst walks them."""
+    _prefix = "kdinst"
+
+    def __init__(self, model):
+        h = C.c_void_p()
+        _check(lib.hprt_kdinst_build(model._h, C.byref(h)))
+        self._h = h
 
 
 class RbspParams(C.Structure):
@@ -630,12 +644,13 @@ class Rbsp(_Tree):
     directions = _Tree._directions
 
 
-class RbspInst:
+class RbspInst(_TwoLevel):
     """Two-level RBSP trees (host) of a model WITH object instances, as pbrtObjectInstance and pbrtWorldEnd build them under
     Accelerator "rbsp" — or, with kd_aware, "rbspkd" — (core/api.cpp:1794-1819): one tree per object of more than one primitive
     and the top-level tree over the top-level items, all with the same parameters.  RbspInst(model) takes the scene's Accelerator
     line; giving n_directions makes the keyword parameters replace it, as for Rbsp / RbspKd.  Scene.attach_rbspinst walks them."""
-    _KEYS = ("nodes", "leaves", "prim_refs", "depth")
+    _prefix = "rbspinst"
+    _extra_keys = ("M", "kd_aware")
 
     def __init__(self, model, kd_aware=False, n_directions=None, isect_cost=80, trav_cost=5, kd_trav_cost=1, empty_bonus=0.0, max_prims=1,
                  max_depth=-1, threads=0):
@@ -649,64 +664,11 @@ class RbspInst:
             _check(lib.hprt_rbspinst_build(model._h, prm, C.byref(h)))
         self._h = h
 
-    def info(self):
-        """the top-level tree's nodes, leaves, prim_refs and depth; objects (definitions), object_trees (those with more than one
-        primitive), object_depth (the deepest object tree's), instances, M (directions of every tree) and kd_aware"""
-        i = (C.c_uint32 * 10)()
-        _check(lib.hprt_rbspinst_info(self._h, i))
-        return dict(zip(self._KEYS + ("objects", "object_trees", "object_depth", "instances", "M", "kd_aware"), i))
-
-    def object_info(self, obj):
-        """nodes, leaves, prim_refs and depth of the tree of object definition `obj`: all zero for an object of one primitive"""
-        i = (C.c_uint32 * 4)()
-        _check(lib.hprt_rbspinst_object_info(self._h, obj, i))
-        return dict(zip(self._KEYS, i))
-
-    def copy(self):
-        """(nodes [n, 2] uint32, prim_indices uint32) of the top-level tree, as Rbsp.arrays() gives them"""
-        inf = self.info()
-        nodes = np.zeros((inf["nodes"], 2), np.uint32); idx = np.zeros(inf["prim_refs"], np.uint32)
-        _check(lib.hprt_rbspinst_copy(self._h, _ptr(nodes), _ptr(idx), None))
-        return nodes, idx
-
-    def object_copy(self, obj):
-        """the same for the tree of object definition `obj` (empty arrays for an object of one primitive)"""
-        inf = self.object_info(obj)
-        nodes = np.zeros((inf["nodes"], 2), np.uint32); idx = np.zeros(inf["prim_refs"], np.uint32)
-        _check(lib.hprt_rbspinst_object_copy(self._h, obj, _ptr(nodes), _ptr(idx)))
-        return nodes, idx
-
     def directions(self):
         """[M, 3] float32: getDirections(M), the one table of every tree"""
         d = np.zeros((self.info()["M"], 3), np.float32)
         _check(lib.hprt_rbspinst_copy(self._h, None, None, _ptr(d)))
         return d
-
-    def bounds(self, obj=-1):
-        """Diagnostics hook (not part of include/hprt.h): the six floats pMin, pMax of the top-level tree (obj < 0) or of one
-        object's tree."""
-        b = np.zeros(6, np.float32)
-        lib.hprt_debug_rbspinst_bounds.restype = C.c_int
-        lib.hprt_debug_rbspinst_bounds.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-        _check(lib.hprt_debug_rbspinst_bounds(self._h, int(obj), _ptr(b)))
-        return b
-
-    def set_tree(self, obj, nodes, prim_indices, bounds):
-        """Diagnostics hook (not part of include/hprt.h): a tree made by hand in place of the top-level tree (obj < 0) or of one
-        object's tree, over the handle's M directions; it passes the checks a built handle passes (HprtError E_INVALID /
-        E_UNSUPPORTED, the handle unchanged)."""
-        nodes = np.ascontiguousarray(nodes, np.uint32); idx = np.ascontiguousarray(prim_indices, np.uint32).ravel()
-        b = np.ascontiguousarray(bounds, np.float32).ravel()
-        assert nodes.ndim == 2 and nodes.shape[1] == 2 and b.shape[0] == 6
-        fn = lib.hprt_debug_rbspinst_set_tree
-        fn.restype = C.c_int
-        fn.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
-        _check(fn(self._h, int(obj), nodes.shape[0], _ptr(nodes), idx.shape[0], _ptr(idx), _ptr(b)))
-
-    def __del__(self):
-        if getattr(self, "_h", None) and lib is not None:      # (module globals are cleared at interpreter exit)
-            lib.hprt_rbspinst_destroy(self._h)
-            self._h = None
 
 
 class BspPaperParams(C.Structure):

@@ -464,7 +464,7 @@ struct TreeView {
 // MakeAccelerator (core/api.cpp:790-831) for the trees the host builds: the tree is checked, its creation-order primitive numbers are
 // mapped to the scene's ordered indices (the inverse of prim_order), and from now on every trace of the scene takes `walk` over it
 // (Trace above).  Until the upload has succeeded the scene walks its BVH: a failed attach never leaves a half-replaced tree behind.
-// The steps every attach shares (AttachTree, hprt_scene_attach_kdinst).
+// The steps every attach shares (AttachTree, AttachTwoLevel).
 // InvertOrder: a prim_order (ordered position -> creation number) turned round, with the aggregate's first ordered index added.
 static std::vector<uint32_t> InvertOrder(const std::vector<uint32_t> &order, uint32_t primBase) {
     std::vector<uint32_t> toOrdered(order.size());
@@ -494,12 +494,18 @@ static int UploadTree(HprtScene *s, const std::vector<uint2> &nodes, const std::
     HIP_TRY(upload(s->treePrims, prims));
     return HPRT_OK;
 }
-// FillTree: the fields every walk's descriptor shares (DevKd, DevRbsp, DevBspPaper, DevKdInst)
+// FillTree: the fields every walk's descriptor shares (DevKd, DevRbsp, DevBspPaper, DevKdInst, DevRbspInst)
 extern "C++" template <class Dev> static void FillTree(Dev &d, const HprtScene *s, size_t nNodes, size_t nPrims, const float *bounds, uint32_t depth) {
     d.nodes = s->treeNodes.as<uint2>(); d.nNodes = (uint32_t)nNodes;
     d.primIdx = s->treePrims.as<uint32_t>(); d.nPrimIdx = (uint32_t)nPrims;
     for (int a = 0; a < 3; ++a) { d.lo[a] = bounds[a]; d.hi[a] = bounds[3 + a]; }
     d.depth = depth;
+}
+// ResetKdShare: the kd counter pair of a walk that counts its kd interior nodes apart (CountsKdShare), allocated and zeroed
+static int ResetKdShare(HprtScene *s) {
+    HIP_TRY(s->kdShare.alloc(2 * sizeof(unsigned long long)));
+    HIP_TRY(hipMemset(s->kdShare.p, 0, 2 * sizeof(unsigned long long)));
+    return HPRT_OK;
 }
 static int AttachTree(HprtScene *s, HprtScene::Walk walk, const TreeView &t) {
     const std::string what = t.what;
@@ -524,10 +530,8 @@ static int AttachTree(HprtScene *s, HprtScene::Walk walk, const TreeView &t) {
         for (size_t k = 0; k < axes.size(); ++k) axes[k] = make_float4((*t.axes)[3 * k], (*t.axes)[3 * k + 1], (*t.axes)[3 * k + 2], 0.f);
         HIP_TRY(upload(s->treeAxes, axes));
     }
-    if (walk == HprtScene::Walk::RbspKd || walk == HprtScene::Walk::BspPaperKd) {
-        HIP_TRY(s->kdShare.alloc(2 * sizeof(unsigned long long)));
-        HIP_TRY(hipMemset(s->kdShare.p, 0, 2 * sizeof(unsigned long long)));
-    }
+    if (walk == HprtScene::Walk::RbspKd || walk == HprtScene::Walk::BspPaperKd)
+        if (int rc = ResetKdShare(s)) return rc;
     auto fill = [&](auto &d) { FillTree(d, s, nodes.size(), prims.size(), t.bounds, depth); };
     if (walk == HprtScene::Walk::Kd) fill(s->kd);
     else if (walk == HprtScene::Walk::BspPaper || walk == HprtScene::Walk::BspPaperKd) {
@@ -584,145 +588,112 @@ int hprt_scene_attach_bsppaperkd(HprtScene *s, const HprtBspPaperKd *t) try {
                                                        BSPPAPERKD_OFF, BSPPAPERKD_LEAF});
 } catch (...) { return hprt::HandleException(); }
 
-// Two-level kd-trees (pbrtObjectInstance, core/api.cpp:1794-1819, under Accelerator "kdtree"): the top-level tree and every
-// object's tree go through AttachTree's steps — CheckKdTree, the todo-list rule (here over both levels), AppendTree, UploadTree,
-// FillTree — into ONE node array and ONE primitiveIndices array (device/kdinst_walk.h), with one entry per instance.
-int hprt_scene_attach_kdinst(HprtScene *s, const HprtKdInst *t) try {
-    if (!s || !t) return SetError(HPRT_E_INVALID, "hprt_scene_attach_kdinst: null argument");
-    if (!s->instanced) return SetError(HPRT_E_UNSUPPORTED, "hprt_scene_attach_kdinst: the scene has no object instances; attach its kd-tree with hprt_scene_attach_kdtree");
-    HIP_TRY(hipSetDevice(s->device));
-    SceneCall call(s, nullptr);
+// Two-level trees (pbrtObjectInstance, core/api.cpp:1794-1819): what AttachTwoLevel takes besides the handle's trees, which it
+// reads as TreeView names a tree — through nodes, primIndices, nPrims and bounds
+extern "C++" template <class Tree> struct TwoLevelView {
+    const char *what;                                           // the tree's name in messages: "kd-tree", "RBSP tree"
+    const HprtTwoLevel<Tree> &t;
+    const char *(*check)(const Tree &, uint32_t *depth);        // CheckKdTree, CheckRbspTree
+    uint32_t off, mask, leafTag;                                // the node layout: flag bits, their mask, a leaf's tag
+    uint32_t todoMax;                                           // the entries the walk's one todo list holds
+    std::function<std::string(const Tree &)> objectCheck;       // optional: what else is wrong with an object's tree ("": nothing)
+};
+// The top-level tree and every object's tree go through AttachTree's steps — the structural check, the todo-list rule (here over
+// both levels), AppendTree, UploadTree, FillTree — into ONE node array and ONE primitiveIndices array with one DevInstEntry per
+// instance (device/two_level.h); d: the walk's descriptor (DevKdInst, DevRbspInst), of which the shared fields are filled.  A
+// refusal leaves the attached walk in place, a failed upload the BVH; on success the scene still walks its BVH and the caller,
+// having filled the descriptor's own fields, sets its walk.
+extern "C++" template <class Tree, class Dev> static int AttachTwoLevel(HprtScene *s, const TwoLevelView<Tree> &v, Dev &d) {
+    const HprtTwoLevel<Tree> &t = v.t;
+    const std::string what = v.what;
     const size_t nObjects = s->objectOrder.size();
-    if (t->objects.size() != nObjects || t->instanceObject != s->instanceObject)
-        return SetError(HPRT_E_INVALID, "the two-level kd-tree holds " + std::to_string(t->objects.size()) + " objects and " + std::to_string(t->instanceObject.size()) +
+    if (t.objects.size() != nObjects || t.instanceObject != s->instanceObject)
+        return SetError(HPRT_E_INVALID, "the two-level " + what + " holds " + std::to_string(t.objects.size()) + " objects and " + std::to_string(t.instanceObject.size()) +
                                         " instances, the scene " + std::to_string(nObjects) + " and " + std::to_string(s->instanceObject.size()) + " (or they name other objects)");
-    if (t->top.nPrims != s->topOrder.size())
-        return SetError(HPRT_E_INVALID, "the top-level kd-tree holds " + std::to_string(t->top.nPrims) + " primitives, the scene " + std::to_string(s->topOrder.size()));
+    if (t.top.nPrims != s->topOrder.size())
+        return SetError(HPRT_E_INVALID, "the top-level " + what + " holds " + std::to_string(t.top.nPrims) + " primitives, the scene " + std::to_string(s->topOrder.size()));
     uint32_t topDepth = 0, objectDepth = 0;
-    uint64_t nNodes = t->top.nodes.size(), nIdx = t->top.primIndices.size();
-    const char *bad = CheckKdTree(t->top, &topDepth);
-    if (*bad) return SetError(HPRT_E_INVALID, std::string("malformed top-level kd-tree: ") + bad);
+    uint64_t nNodes = t.top.nodes.size(), nIdx = t.top.primIndices.size();
+    const char *bad = v.check(t.top, &topDepth);
+    if (*bad) return SetError(HPRT_E_INVALID, "malformed top-level " + what + ": " + bad);
     for (size_t o = 0; o < nObjects; ++o) {
-        const KdTree &k = t->objects[o];
+        const Tree &k = t.objects[o];
         if (k.nPrims != s->objectOrder[o].size())
-            return SetError(HPRT_E_INVALID, "the kd-tree of object " + std::to_string(o) + " holds " + std::to_string(k.nPrims) + " primitives, the scene's object " + std::to_string(s->objectOrder[o].size()));
+            return SetError(HPRT_E_INVALID, "the " + what + " of object " + std::to_string(o) + " holds " + std::to_string(k.nPrims) + " primitives, the scene's object " + std::to_string(s->objectOrder[o].size()));
         if ((k.nPrims > 1) != !k.nodes.empty()) return SetError(HPRT_E_INVALID, "object " + std::to_string(o) + ": exactly the objects of more than one primitive have a tree");
+        const std::string wrong = v.objectCheck ? v.objectCheck(k) : std::string();
+        if (!wrong.empty()) return SetError(HPRT_E_INVALID, "object " + std::to_string(o) + ": " + wrong);
         nNodes += k.nodes.empty() ? 1u : k.nodes.size(); nIdx += k.primIndices.size();
         if (k.nodes.empty()) continue;
         uint32_t depth = 0;
-        bad = CheckKdTree(k, &depth);
-        if (*bad) return SetError(HPRT_E_INVALID, "malformed kd-tree of object " + std::to_string(o) + ": " + bad);
+        bad = v.check(k, &depth);
+        if (*bad) return SetError(HPRT_E_INVALID, "malformed " + what + " of object " + std::to_string(o) + ": " + bad);
         objectDepth = std::max(objectDepth, depth);
     }
-    if ((uint64_t)topDepth + objectDepth + 1u > KD_TODO_MAX)
-        return SetError(HPRT_E_UNSUPPORTED, "two-level kd-tree: top-level depth " + std::to_string(topDepth) + " + deepest object depth " + std::to_string(objectDepth) +
-                                            " + 1 is more than the walk's todo list holds (" + std::to_string((unsigned)KD_TODO_MAX) + ")");
-    if (nNodes > 0x3fffffffull || nIdx > 0xffffffffull) return SetError(HPRT_E_UNSUPPORTED, "two-level kd-tree: more than 2^30 nodes over all trees");
+    if ((uint64_t)topDepth + objectDepth + 1u > v.todoMax)
+        return SetError(HPRT_E_UNSUPPORTED, "two-level " + what + ": top-level depth " + std::to_string(topDepth) + " + deepest object depth " + std::to_string(objectDepth) +
+                                            " + 1 is more than the walk's todo list holds (" + std::to_string(v.todoMax) + ")");
+    if (nNodes > (0xffffffffull >> v.off) || nIdx > 0xffffffffull)
+        return SetError(HPRT_E_UNSUPPORTED, "two-level " + what + ": more nodes over all trees than aboveChild can name");
     std::vector<uint2> nodes; std::vector<uint32_t> prims;
     nodes.reserve((size_t)nNodes); prims.reserve((size_t)nIdx);
-    auto append = [&](const KdTree &k, const std::vector<uint32_t> &order, uint32_t primBase) {      // (KdAccelNode: two flag bits, leaves tagged 3)
-        return AppendTree(k.nodes, k.primIndices, InvertOrder(order, primBase), 2u, 3u, 3u, &nodes, &prims);
+    auto append = [&](const Tree &k, const std::vector<uint32_t> &order, uint32_t primBase) {
+        return AppendTree(k.nodes, k.primIndices, InvertOrder(order, primBase), v.off, v.mask, v.leafTag, &nodes, &prims);
     };
-    append(t->top, s->topOrder, 0u);
+    append(t.top, s->topOrder, 0u);
     std::vector<uint32_t> objectRoot(nObjects);
     for (size_t o = 0; o < nObjects; ++o) {
-        const KdTree &k = t->objects[o];
+        const Tree &k = t.objects[o];
         if (!k.nodes.empty()) objectRoot[o] = append(k, s->objectOrder[o], s->objectPrimBase[o]);
         else {      // the lone primitive (or nothing: no instance names an empty object) as a one-primitive leaf
             objectRoot[o] = (uint32_t)nodes.size();
-            nodes.push_back(make_uint2(s->objectPrimBase[o], 3u | ((k.nPrims ? 1u : 0u) << 2)));
+            nodes.push_back(make_uint2(s->objectPrimBase[o], v.leafTag | ((k.nPrims ? 1u : 0u) << v.off)));
         }
     }
-    std::vector<DevKdInstEntry> entries(t->instanceObject.size());
+    std::vector<DevInstEntry> entries(t.instanceObject.size());
     for (size_t i = 0; i < entries.size(); ++i) {
-        const size_t o = (size_t)t->instanceObject[i];
-        const KdTree &k = t->objects[o];
-        DevKdInstEntry &e = entries[i];
+        const size_t o = (size_t)t.instanceObject[i];
+        const Tree &k = t.objects[o];
+        DevInstEntry &e = entries[i];
         for (int a = 0; a < 3; ++a) { e.lo[a] = k.bounds[a]; e.hi[a] = k.bounds[3 + a]; }
         e.root = objectRoot[o];
         e.prim = k.nodes.empty() ? (int32_t)s->objectPrimBase[o] : -1;
     }
     if (int rc = UploadTree(s, nodes, prims)) return rc;
-    HIP_TRY(upload(s->kdInstEntries, entries));
-    DevKdInst &d = s->kdinst;
-    FillTree(d, s, nodes.size(), prims.size(), t->top.bounds, topDepth + objectDepth + 1u);
-    d.entries = s->kdInstEntries.as<DevKdInstEntry>(); d.nEntries = (uint32_t)entries.size();
+    HIP_TRY(upload(s->instEntries, entries));
+    d = Dev{};
+    FillTree(d, s, nodes.size(), prims.size(), t.top.bounds, topDepth + objectDepth + 1u);
+    d.entries = s->instEntries.as<DevInstEntry>(); d.nEntries = (uint32_t)entries.size();
+    return HPRT_OK;
+}
+
+// Two-level kd-trees (under Accelerator "kdtree"; device/kdinst_walk.h).  KdAccelNode: two flag bits, leaves tagged 3.
+int hprt_scene_attach_kdinst(HprtScene *s, const HprtKdInst *t) try {
+    if (!s || !t) return SetError(HPRT_E_INVALID, "hprt_scene_attach_kdinst: null argument");
+    if (!s->instanced) return SetError(HPRT_E_UNSUPPORTED, "hprt_scene_attach_kdinst: the scene has no object instances; attach its kd-tree with hprt_scene_attach_kdtree");
+    HIP_TRY(hipSetDevice(s->device));
+    SceneCall call(s, nullptr);
+    if (int rc = AttachTwoLevel(s, TwoLevelView<KdTree>{"kd-tree", *t, CheckKdTree, 2u, 3u, 3u, (uint32_t)KD_TODO_MAX, nullptr}, s->kdinst)) return rc;
     s->walk = HprtScene::Walk::KdInst;
     return HPRT_OK;
 } catch (...) { return hprt::HandleException(); }
 
-// Two-level RBSP trees (pbrtObjectInstance under Accelerator "rbsp" / "rbspkd"): hprt_scene_attach_kdinst's steps with the RBSP
-// tree's check and node layout (M directions: off flag bits, leaves tagged M), the shared direction table and, for kd-aware trees,
-// the rbspkd walk's kd counter pair (device/rbspinst_walk.h).
+// Two-level RBSP trees (under Accelerator "rbsp" / "rbspkd"; device/rbspinst_walk.h): M directions — off flag bits, leaves tagged
+// M — for every tree, the shared direction table and, for kd-aware trees, the rbspkd walk's kd counter pair.
 int hprt_scene_attach_rbspinst(HprtScene *s, const HprtRbspInst *t) try {
     if (!s || !t) return SetError(HPRT_E_INVALID, "hprt_scene_attach_rbspinst: null argument");
     if (!s->instanced)
         return SetError(HPRT_E_UNSUPPORTED, "hprt_scene_attach_rbspinst: the scene has no object instances; attach its tree with hprt_scene_attach_rbsp / hprt_scene_attach_rbspkd");
     HIP_TRY(hipSetDevice(s->device));
     SceneCall call(s, nullptr);
-    const size_t nObjects = s->objectOrder.size();
-    if (t->objects.size() != nObjects || t->instanceObject != s->instanceObject)
-        return SetError(HPRT_E_INVALID, "the two-level RBSP tree holds " + std::to_string(t->objects.size()) + " objects and " + std::to_string(t->instanceObject.size()) +
-                                        " instances, the scene " + std::to_string(nObjects) + " and " + std::to_string(s->instanceObject.size()) + " (or they name other objects)");
-    if (t->top.nPrims != s->topOrder.size())
-        return SetError(HPRT_E_INVALID, "the top-level RBSP tree holds " + std::to_string(t->top.nPrims) + " primitives, the scene " + std::to_string(s->topOrder.size()));
-    const uint32_t M = t->top.M;
-    uint32_t topDepth = 0, objectDepth = 0;
-    uint64_t nNodes = t->top.nodes.size(), nIdx = t->top.primIndices.size();
-    const char *bad = CheckRbspTree(t->top, &topDepth);
-    if (*bad) return SetError(HPRT_E_INVALID, std::string("malformed top-level RBSP tree: ") + bad);
-    for (size_t o = 0; o < nObjects; ++o) {
-        const RbspTree &r = t->objects[o];
-        if (r.nPrims != s->objectOrder[o].size())
-            return SetError(HPRT_E_INVALID, "the RBSP tree of object " + std::to_string(o) + " holds " + std::to_string(r.nPrims) + " primitives, the scene's object " + std::to_string(s->objectOrder[o].size()));
-        if ((r.nPrims > 1) != !r.nodes.empty()) return SetError(HPRT_E_INVALID, "object " + std::to_string(o) + ": exactly the objects of more than one primitive have a tree");
-        if (r.M != M) return SetError(HPRT_E_INVALID, "object " + std::to_string(o) + ": its tree is over " + std::to_string(r.M) + " directions, the top-level tree over " + std::to_string(M));
-        nNodes += r.nodes.empty() ? 1u : r.nodes.size(); nIdx += r.primIndices.size();
-        if (r.nodes.empty()) continue;
-        uint32_t depth = 0;
-        bad = CheckRbspTree(r, &depth);
-        if (*bad) return SetError(HPRT_E_INVALID, "malformed RBSP tree of object " + std::to_string(o) + ": " + bad);
-        objectDepth = std::max(objectDepth, depth);
-    }
-    if ((uint64_t)topDepth + objectDepth + 1u > RBSP_TODO_MAX)
-        return SetError(HPRT_E_UNSUPPORTED, "two-level RBSP tree: top-level depth " + std::to_string(topDepth) + " + deepest object depth " + std::to_string(objectDepth) +
-                                            " + 1 is more than the walk's todo list holds (" + std::to_string((unsigned)RBSP_TODO_MAX) + ")");
-    const uint32_t off = RbspBitOffset(M), mask = RbspBitMask(M);
-    if (nNodes > (0xffffffffull >> off) || nIdx > 0xffffffffull) return SetError(HPRT_E_UNSUPPORTED, "two-level RBSP tree: more nodes over all trees than aboveChild can name");
-    std::vector<uint2> nodes; std::vector<uint32_t> prims;
-    nodes.reserve((size_t)nNodes); prims.reserve((size_t)nIdx);
-    auto append = [&](const RbspTree &r, const std::vector<uint32_t> &order, uint32_t primBase) {
-        return AppendTree(r.nodes, r.primIndices, InvertOrder(order, primBase), off, mask, M, &nodes, &prims);
+    const uint32_t M = t->top.M, off = RbspBitOffset(M), mask = RbspBitMask(M);
+    auto sameM = [M](const RbspTree &r) {
+        return r.M == M ? std::string() : "its tree is over " + std::to_string(r.M) + " directions, the top-level tree over " + std::to_string(M);
     };
-    append(t->top, s->topOrder, 0u);
-    std::vector<uint32_t> objectRoot(nObjects);
-    for (size_t o = 0; o < nObjects; ++o) {
-        const RbspTree &r = t->objects[o];
-        if (!r.nodes.empty()) objectRoot[o] = append(r, s->objectOrder[o], s->objectPrimBase[o]);
-        else {      // the lone primitive (or nothing: no instance names an empty object) as a one-primitive leaf
-            objectRoot[o] = (uint32_t)nodes.size();
-            nodes.push_back(make_uint2(s->objectPrimBase[o], M | ((r.nPrims ? 1u : 0u) << off)));
-        }
-    }
-    std::vector<DevRbspInstEntry> entries(t->instanceObject.size());
-    for (size_t i = 0; i < entries.size(); ++i) {
-        const size_t o = (size_t)t->instanceObject[i];
-        const RbspTree &r = t->objects[o];
-        DevRbspInstEntry &e = entries[i];
-        for (int a = 0; a < 3; ++a) { e.lo[a] = r.bounds[a]; e.hi[a] = r.bounds[3 + a]; }
-        e.root = objectRoot[o];
-        e.prim = r.nodes.empty() ? (int32_t)s->objectPrimBase[o] : -1;
-    }
-    if (int rc = UploadTree(s, nodes, prims)) return rc;
-    HIP_TRY(upload(s->kdInstEntries, entries));
-    if (t->kdAware) {
-        HIP_TRY(s->kdShare.alloc(2 * sizeof(unsigned long long)));
-        HIP_TRY(hipMemset(s->kdShare.p, 0, 2 * sizeof(unsigned long long)));
-    }
-    s->rbspinst = DevRbspInst{};
     DevRbspInst &d = s->rbspinst;
-    FillTree(d, s, nodes.size(), prims.size(), t->top.bounds, topDepth + objectDepth + 1u);
-    d.entries = s->kdInstEntries.as<DevRbspInstEntry>(); d.nEntries = (uint32_t)entries.size();
+    if (int rc = AttachTwoLevel(s, TwoLevelView<RbspTree>{"RBSP tree", *t, CheckRbspTree, off, mask, M, (uint32_t)RBSP_TODO_MAX, sameM}, d)) return rc;
+    if (t->kdAware)
+        if (int rc = ResetKdShare(s)) return rc;
     d.M = M; d.off = off; d.mask = mask;
     for (uint32_t k = 0; k < 3 * M; ++k) d.dirs[k] = t->top.directions[k];
     d.kdCounters = t->kdAware ? s->kdShare.as<unsigned long long>() : nullptr;

@@ -180,7 +180,7 @@ int RbspCopy(const char *fn, const RbspTree *t, void *nodes8, uint32_t *primIndi
     return HPRT_OK;
 }
 
-// ---- two-level RBSP trees (hprt_rbspinst_* below; pbrtObjectInstance, core/api.cpp:1794-1819, under Accelerator "rbsp" / "rbspkd") ----
+// ---- two-level RBSP trees (BuildRbspInst below; pbrtObjectInstance, core/api.cpp:1794-1819, under Accelerator "rbsp" / "rbspkd") ----
 // tri9 / isTri as BuildRbspTree takes them, for the n primitives of the top level (object < 0; an instance is no triangle: its
 // projections are those of its world bound's corners, Primitive::getBounds, core/primitive.h:72-80) or of one object, in the order
 // of ComputePrimBounds / ComputeObjectPrimBounds
@@ -201,74 +201,6 @@ void RbspPrimTriangles(const SceneModel &sc, int object, size_t n, std::vector<f
     } else {
         for (const ShapeDesc &sh : sc.shapes) if (sh.object == object) shape(sh);
     }
-}
-// The walk keeps the top-level tree's todo entries, one saved top-level position and the object tree's entries in one list of
-// RBSP_TODO_MAX entries (device/bspinst_walk.h)
-int CheckRbspInstDepth(const HprtRbspInst &t) {
-    uint32_t deepest = 0;
-    for (const RbspTree &o : t.objects) if (!o.nodes.empty()) deepest = std::max(deepest, o.depth);
-    if ((uint64_t)t.top.depth + deepest + 1u > RBSP_TODO_MAX)
-        return SetError(HPRT_E_UNSUPPORTED, "two-level RBSP tree: top-level depth " + std::to_string(t.top.depth) + " + deepest object depth " + std::to_string(deepest) +
-                                            " + 1 is more than the device walk's todo list holds (" + std::to_string((unsigned)RBSP_TODO_MAX) + " entries); lower \"maxdepth\"");
-    return HPRT_OK;
-}
-// hprt_rbspinst_build / hprt_rbspkdinst_build: one RbspTree per object of more than one primitive, over the object's primitives in
-// object space, and the top-level tree over the top-level items, an instance bounded by TransformedPrimitive::WorldBound; p: the
-// Accelerator line.  The device-assisted build (costFn) is not wired in.
-template <typename Params>
-int BuildRbspInst(const char *fn, const HprtModel *m, const Params *params, RbspParams p, HprtRbspInst **out) {
-    if (out) *out = nullptr;
-    if (!m || !out) return SetError(HPRT_E_INVALID, std::string(fn) + ": null argument");
-    const SceneModel &sc = m->sc;
-    if (sc.instances.empty())
-        return SetError(HPRT_E_UNSUPPORTED, std::string(fn) + ": the model has no object instances; build its tree with hprt_rbsp_build / hprt_rbspkd_build");
-    p.kdAware = std::is_same<Params, HprtRbspKdParams>::value;
-    ApplyRbspParams(params, &p);
-    if (p.nDirections != 3 && p.nDirections != 7 && p.nDirections != 9 && p.nDirections != 13)
-        return SetError(HPRT_E_UNSUPPORTED, "nbDirections " + std::to_string(p.nDirections) + " is not supported (3, 7, 9 or 13)");
-    std::unique_ptr<HprtRbspInst> t(new HprtRbspInst());
-    t->kdAware = p.kdAware;
-    for (const InstanceDesc &in : sc.instances) t->instanceObject.push_back(in.object);
-    t->objects.resize(sc.nObjects);
-    // TransformedPrimitive::WorldBound needs the wrapped primitive's bounds: the object accelerator's (the union of its primitives'
-    // bounds), or the lone primitive's own — one-node trees that hold them, which is all ComputePrimBounds reads (bvh_builder.h)
-    std::vector<BvhTree> objectBounds(sc.nObjects);
-    std::vector<float> lo, hi, tri9;
-    std::vector<uint8_t> isTri;
-    for (uint32_t o = 0; o < sc.nObjects; ++o) {
-        ComputeObjectPrimBounds(sc, (int)o, &lo, &hi);
-        const size_t n = lo.size() / 3;
-        if (n > 0x3fffffffull) return SetError(HPRT_E_UNSUPPORTED, "more than 2^30 primitives");
-        RbspTree &r = t->objects[o];
-        if (n > 1) {      // (core/api.cpp:1798: only more than one primitive gets an accelerator)
-            RbspPrimTriangles(sc, (int)o, n, &tri9, &isTri);
-            const std::string err = BuildRbspTree(n, lo.data(), hi.data(), tri9.data(), isTri.data(), p, &r);
-            if (!err.empty()) return SetError(HPRT_E_UNSUPPORTED, "object " + std::to_string(o) + ": " + err);
-        } else {
-            r.nPrims = (uint32_t)n; r.M = (uint32_t)p.nDirections;
-            RbspDirections(r.M, &r.directions);
-            for (int a = 0; a < 3 && n; ++a) { r.bounds[a] = lo[a]; r.bounds[3 + a] = hi[a]; }
-        }
-        if (n == 0) continue;
-        BvhNode box;
-        for (int a = 0; a < 3; ++a) { box.bmin[a] = lo[a]; box.bmax[a] = hi[a]; }
-        for (size_t i = 1; i < n; ++i)
-            for (int a = 0; a < 3; ++a) { box.bmin[a] = sel_min(box.bmin[a], lo[3 * i + a]); box.bmax[a] = sel_max(box.bmax[a], hi[3 * i + a]); }
-        box.offset = 0; box.countAxis = 3u;
-        objectBounds[o].nodes.push_back(box);
-    }
-    ComputePrimBounds(sc, objectBounds, &lo, &hi);
-    const size_t n = lo.size() / 3;
-    if (n > 0x3fffffffull) return SetError(HPRT_E_UNSUPPORTED, "more than 2^30 primitives");
-    RbspPrimTriangles(sc, -1, n, &tri9, &isTri);
-    const std::string err = BuildRbspTree(n, lo.data(), hi.data(), tri9.data(), isTri.data(), p, &t->top);
-    if (!err.empty()) return SetError(HPRT_E_UNSUPPORTED, "top level: " + err);
-    if (int rc = CheckRbspInstDepth(*t)) return rc;
-    *out = t.release();
-    return HPRT_OK;
-}
-void RbspTreeInfo(const RbspTree &r, uint32_t info[4]) {
-    info[0] = (uint32_t)r.nodes.size(); info[1] = r.nodes.empty() ? 0u : r.leaves; info[2] = (uint32_t)r.primIndices.size(); info[3] = r.nodes.empty() ? 0u : r.depth;
 }
 
 // ---- the general BSP handles' builds and copies (hprt_bsppaper_* and hprt_bsppaperkd_* below) ----
@@ -412,6 +344,154 @@ int BspPaperFromArrays(const char *fn, size_t nNodes, const uint32_t *nodes20, s
         return SetError(HPRT_E_UNSUPPORTED, std::string(kdAware ? "bsppaperkd" : "bsppaper") + " tree of depth " + std::to_string(b.depth) +
                                                 " is deeper than the device walk's todo list (" + std::to_string((unsigned)todoMax) + " entries); lower \"maxdepth\"");
     *out = t.release();
+    return HPRT_OK;
+}
+
+// ---- two-level trees (hprt_kdinst_* and hprt_rbspinst_* below; pbrtObjectInstance, core/api.cpp:1794-1819): Handle is HprtKdInst
+// or HprtRbspInst (HprtTwoLevel, hprt_internal.h), Tree its KdTree or RbspTree ----
+// The walk keeps the top-level tree's todo entries, one saved top-level position and the object tree's entries in one list of
+// todoMax entries (device/kdinst_walk.hip, device/bspinst_walk.h); what: the tree's name in the message
+template <typename Tree>
+int CheckTwoLevelDepth(const HprtTwoLevel<Tree> &t, const char *what, uint32_t todoMax) {
+    uint32_t deepest = 0;
+    for (const Tree &o : t.objects) if (!o.nodes.empty()) deepest = std::max(deepest, o.depth);
+    if ((uint64_t)t.top.depth + deepest + 1u > todoMax)
+        return SetError(HPRT_E_UNSUPPORTED, std::string("two-level ") + what + ": top-level depth " + std::to_string(t.top.depth) + " + deepest object depth " +
+                                            std::to_string(deepest) + " + 1 is more than the device walk's todo list holds (" + std::to_string(todoMax) +
+                                            " entries); lower \"maxdepth\"");
+    return HPRT_OK;
+}
+int CheckTwoLevelDepth(const HprtKdInst &t) { return CheckTwoLevelDepth(t, "kd-tree", KD_TODO_MAX); }
+int CheckTwoLevelDepth(const HprtRbspInst &t) { return CheckTwoLevelDepth(t, "RBSP tree", RBSP_TODO_MAX); }
+// The build of either handle: one tree per object of more than one primitive, over the object's primitives in object space, and the
+// top-level tree over the top-level items, an instance bounded by TransformedPrimitive::WorldBound.  buildTree(object, n, lo, hi,
+// &tree): the tree over the n primitives of one object or (object < 0) of the top level, returning what went wrong ("": nothing);
+// bareObject(n, lo, hi, &tree): what the handle holds of an object of n < 2 primitives, which gets no tree.
+template <typename Handle, typename BuildTree, typename BareObject>
+int BuildTwoLevel(const SceneModel &sc, std::unique_ptr<Handle> t, BuildTree buildTree, BareObject bareObject, Handle **out) {
+    for (const InstanceDesc &in : sc.instances) t->instanceObject.push_back(in.object);
+    t->objects.resize(sc.nObjects);
+    // TransformedPrimitive::WorldBound needs the wrapped primitive's bounds: the object accelerator's (the union of its primitives'
+    // bounds), or the lone primitive's own — one-node trees that hold them, which is all ComputePrimBounds reads (bvh_builder.h)
+    std::vector<BvhTree> objectBounds(sc.nObjects);
+    std::vector<float> lo, hi;
+    for (uint32_t o = 0; o < sc.nObjects; ++o) {
+        ComputeObjectPrimBounds(sc, (int)o, &lo, &hi);
+        const size_t n = lo.size() / 3;
+        if (n > 0x3fffffffull) return SetError(HPRT_E_UNSUPPORTED, "more than 2^30 primitives");
+        if (n > 1) {      // (core/api.cpp:1798: only more than one primitive gets an accelerator)
+            const std::string err = buildTree((int)o, n, lo.data(), hi.data(), &t->objects[o]);
+            if (!err.empty()) return SetError(HPRT_E_UNSUPPORTED, "object " + std::to_string(o) + ": " + err);
+        } else bareObject(n, lo.data(), hi.data(), &t->objects[o]);
+        if (n == 0) continue;
+        BvhNode box;
+        for (int a = 0; a < 3; ++a) { box.bmin[a] = lo[a]; box.bmax[a] = hi[a]; }
+        for (size_t i = 1; i < n; ++i)
+            for (int a = 0; a < 3; ++a) { box.bmin[a] = sel_min(box.bmin[a], lo[3 * i + a]); box.bmax[a] = sel_max(box.bmax[a], hi[3 * i + a]); }
+        box.offset = 0; box.countAxis = 3u;
+        objectBounds[o].nodes.push_back(box);
+    }
+    ComputePrimBounds(sc, objectBounds, &lo, &hi);
+    const size_t n = lo.size() / 3;
+    if (n > 0x3fffffffull) return SetError(HPRT_E_UNSUPPORTED, "more than 2^30 primitives");
+    const std::string err = buildTree(-1, n, lo.data(), hi.data(), &t->top);
+    if (!err.empty()) return SetError(HPRT_E_UNSUPPORTED, "top level: " + err);
+    if (int rc = CheckTwoLevelDepth(*t)) return rc;
+    *out = t.release();
+    return HPRT_OK;
+}
+// hprt_rbspinst_build / hprt_rbspkdinst_build; p: the Accelerator line.  The device-assisted build (costFn) is not wired in.
+template <typename Params>
+int BuildRbspInst(const char *fn, const HprtModel *m, const Params *params, RbspParams p, HprtRbspInst **out) {
+    if (out) *out = nullptr;
+    if (!m || !out) return SetError(HPRT_E_INVALID, std::string(fn) + ": null argument");
+    const SceneModel &sc = m->sc;
+    if (sc.instances.empty())
+        return SetError(HPRT_E_UNSUPPORTED, std::string(fn) + ": the model has no object instances; build its tree with hprt_rbsp_build / hprt_rbspkd_build");
+    p.kdAware = std::is_same<Params, HprtRbspKdParams>::value;
+    ApplyRbspParams(params, &p);
+    if (p.nDirections != 3 && p.nDirections != 7 && p.nDirections != 9 && p.nDirections != 13)
+        return SetError(HPRT_E_UNSUPPORTED, "nbDirections " + std::to_string(p.nDirections) + " is not supported (3, 7, 9 or 13)");
+    std::unique_ptr<HprtRbspInst> t(new HprtRbspInst());
+    t->kdAware = p.kdAware;
+    std::vector<float> tri9;
+    std::vector<uint8_t> isTri;
+    return BuildTwoLevel(sc, std::move(t),
+                         [&](int object, size_t n, const float *lo, const float *hi, RbspTree *r) {
+                             RbspPrimTriangles(sc, object, n, &tri9, &isTri);
+                             return BuildRbspTree(n, lo, hi, tri9.data(), isTri.data(), p, r);
+                         },
+                         [&](size_t n, const float *lo, const float *hi, RbspTree *r) {
+                             r->nPrims = (uint32_t)n; r->M = (uint32_t)p.nDirections;
+                             RbspDirections(r->M, &r->directions);
+                             for (int a = 0; a < 3 && n; ++a) { r->bounds[a] = lo[a]; r->bounds[3 + a] = hi[a]; }
+                         },
+                         out);
+}
+// info[0..3] of one tree of a handle: an object without a tree has no leaves and no depth
+template <typename Tree>
+void TwoLevelTreeInfo(const Tree &t, uint32_t info[4]) {
+    info[0] = (uint32_t)t.nodes.size(); info[1] = t.nodes.empty() ? 0u : t.leaves; info[2] = (uint32_t)t.primIndices.size(); info[3] = t.nodes.empty() ? 0u : t.depth;
+}
+// info[0..7] of either handle
+template <typename Handle>
+int TwoLevelInfo(const char *fn, const Handle *t, uint32_t *info) {
+    if (!t || !info) return SetError(HPRT_E_INVALID, std::string(fn) + ": null argument");
+    TwoLevelTreeInfo(t->top, info);
+    info[4] = (uint32_t)t->objects.size(); info[5] = 0; info[6] = 0; info[7] = (uint32_t)t->instanceObject.size();
+    for (const auto &o : t->objects) if (!o.nodes.empty()) { ++info[5]; info[6] = std::max(info[6], o.depth); }
+    return HPRT_OK;
+}
+// The tree of object definition `object` (object_info, object_copy); NULL with the error set when there is none
+template <typename Handle>
+auto TwoLevelObject(const char *fn, const Handle *t, uint32_t object) -> decltype(&t->top) {
+    if (!t) SetError(HPRT_E_INVALID, std::string(fn) + ": null argument");
+    else if (object >= t->objects.size()) SetError(HPRT_E_INVALID, std::string(fn) + ": object index out of range");
+    else return &t->objects[object];
+    return nullptr;
+}
+template <typename Handle>
+int TwoLevelObjectInfo(const char *fn, const Handle *t, uint32_t object, uint32_t *info) {
+    if (!t || !info) return SetError(HPRT_E_INVALID, std::string(fn) + ": null argument");
+    const auto *o = TwoLevelObject(fn, t, object);
+    if (!o) return HPRT_E_INVALID;
+    TwoLevelTreeInfo(*o, info);
+    return HPRT_OK;
+}
+// The diagnostics hooks hprt_debug_*_bounds and hprt_debug_*_set_tree (below)
+template <typename Handle>
+int TwoLevelBounds(const char *fn, const Handle *t, int object, float *bounds6) {
+    if (!t || !bounds6 || object >= (int)t->objects.size()) return SetError(HPRT_E_INVALID, std::string(fn) + ": bad argument");
+    memcpy(bounds6, (object < 0 ? t->top : t->objects[object]).bounds, 6 * sizeof(float));
+    return HPRT_OK;
+}
+// What a hand-made tree keeps of the tree it replaces — its primitive count; an RBSP tree its M and direction table too — then its
+// structural check, which gives its depth, and its leaves
+const char *FinishHandMadeTree(const KdTree &old, KdTree *k) {
+    k->nPrims = old.nPrims;
+    k->leaves = CountLeaves(k->nodes, 3u, 3u);
+    return CheckKdTree(*k, &k->depth);
+}
+const char *FinishHandMadeTree(const RbspTree &old, RbspTree *r) {
+    r->nPrims = old.nPrims; r->M = old.M; r->directions = old.directions;
+    r->leaves = CountLeaves(r->nodes, RbspBitMask(r->M), r->M);
+    return CheckRbspTree(*r, &r->depth);
+}
+template <typename Handle>
+int TwoLevelSetTree(const char *fn, Handle *t, int object, size_t nNodes, const uint32_t *nodes8, size_t nIdx, const uint32_t *idx, const float *bounds6) {
+    if (!t || !nodes8 || !bounds6 || (nIdx && !idx) || object >= (int)t->objects.size()) return SetError(HPRT_E_INVALID, std::string(fn) + ": bad argument");
+    auto &dst = object < 0 ? t->top : t->objects[object];
+    if (object >= 0 && dst.nPrims < 2) return SetError(HPRT_E_INVALID, std::string(fn) + ": an object of one primitive has no tree");
+    typename std::remove_reference<decltype(dst)>::type tree;
+    tree.nodes.resize(nNodes);
+    memcpy(tree.nodes.data(), nodes8, nNodes * sizeof(BspNode));
+    tree.primIndices.assign(idx, idx + nIdx);
+    memcpy(tree.bounds, bounds6, sizeof(tree.bounds));
+    const char *bad = FinishHandMadeTree(dst, &tree);
+    if (*bad) return SetError(HPRT_E_INVALID, std::string("malformed tree: ") + bad);
+    tree.maxDepth = tree.depth;
+    std::swap(dst, tree);
+    if (int rc = CheckTwoLevelDepth(*t)) { std::swap(dst, tree); return rc; }
     return HPRT_OK;
 }
 
@@ -629,70 +709,25 @@ int hprt_kdtree_copy(const HprtKdTree *t, void *nodes8, uint32_t *primIndices) t
 } catch (...) { return hprt::HandleException(); }
 void hprt_kdtree_destroy(HprtKdTree *t) { delete t; }
 
-// ---- two-level kd-trees (Accelerator "kdtree" over object instances, core/api.cpp:1794-1819) ----
-// The walk keeps the top-level tree's todo entries, one saved top-level position and the object tree's entries in one list of
-// KD_TODO_MAX entries (device/kdinst_walk.hip)
-static int CheckKdInstDepth(const HprtKdInst &t) {
-    uint32_t deepest = 0;
-    for (const KdTree &o : t.objects) deepest = std::max(deepest, o.depth);
-    if ((uint64_t)t.top.depth + deepest + 1u > KD_TODO_MAX)
-        return SetError(HPRT_E_UNSUPPORTED, "two-level kd-tree: top-level depth " + std::to_string(t.top.depth) + " + deepest object depth " + std::to_string(deepest) +
-                                            " + 1 is more than the device walk's todo list holds (" + std::to_string((unsigned)KD_TODO_MAX) + " entries); lower \"maxdepth\"");
-    return HPRT_OK;
-}
+// ---- two-level kd-trees (Accelerator "kdtree" over object instances, core/api.cpp:1794-1819; helpers above) ----
 int hprt_kdinst_build(const HprtModel *m, HprtKdInst **out) try {
     if (!m || !out) return SetError(HPRT_E_INVALID, "hprt_kdinst_build: null argument");
     const SceneModel &sc = m->sc;
     if (sc.instances.empty())
         return SetError(HPRT_E_UNSUPPORTED, "hprt_kdinst_build: the model has no object instances; build its kd-tree with hprt_kdtree_build");
-    std::unique_ptr<HprtKdInst> t(new HprtKdInst());
-    for (const InstanceDesc &in : sc.instances) t->instanceObject.push_back(in.object);
-    t->objects.resize(sc.nObjects);
-    // TransformedPrimitive::WorldBound needs the wrapped primitive's bounds: the object accelerator's (the union of its primitives'
-    // bounds), or the lone primitive's own — the boxes the objects' BVH roots hold, which ComputePrimBounds reads
-    std::vector<BvhTree> objectBounds(sc.nObjects);
-    std::vector<float> lo, hi;
-    for (uint32_t o = 0; o < sc.nObjects; ++o) {
-        ComputeObjectPrimBounds(sc, (int)o, &lo, &hi);
-        const size_t n = lo.size() / 3;
-        if (n > 0x3fffffffull) return SetError(HPRT_E_UNSUPPORTED, "more than 2^30 primitives");
-        KdTree &k = t->objects[o];
-        if (n > 1) BuildKdTree(n, lo.data(), hi.data(), sc.opt.kd, &k);      // (core/api.cpp:1798: only more than one primitive gets an accelerator)
-        k.nPrims = (uint32_t)n;
-        if (n == 0) continue;
-        BvhNode box;
-        for (int a = 0; a < 3; ++a) { box.bmin[a] = lo[a]; box.bmax[a] = hi[a]; }
-        for (size_t i = 1; i < n; ++i)
-            for (int a = 0; a < 3; ++a) { box.bmin[a] = sel_min(box.bmin[a], lo[3 * i + a]); box.bmax[a] = sel_max(box.bmax[a], hi[3 * i + a]); }
-        box.offset = 0; box.countAxis = 3u;
-        objectBounds[o].nodes.push_back(box);
-    }
-    ComputePrimBounds(sc, objectBounds, &lo, &hi);
-    if (lo.size() / 3 > 0x3fffffffull) return SetError(HPRT_E_UNSUPPORTED, "more than 2^30 primitives");
-    BuildKdTree(lo.size() / 3, lo.data(), hi.data(), sc.opt.kd, &t->top);
-    if (int rc = CheckKdInstDepth(*t)) return rc;
-    *out = t.release();
-    return HPRT_OK;
+    return BuildTwoLevel(sc, std::unique_ptr<HprtKdInst>(new HprtKdInst()),
+                         [&](int, size_t n, const float *lo, const float *hi, KdTree *k) { BuildKdTree(n, lo, hi, sc.opt.kd, k); return std::string(); },
+                         [](size_t n, const float *, const float *, KdTree *k) { k->nPrims = (uint32_t)n; }, out);
 } catch (...) { return hprt::HandleException(); }
-static void KdTreeInfo(const KdTree &k, uint32_t info[4]) {
-    info[0] = (uint32_t)k.nodes.size(); info[1] = k.nodes.empty() ? 0u : k.leaves; info[2] = (uint32_t)k.primIndices.size(); info[3] = k.nodes.empty() ? 0u : k.depth;
-}
 static void KdTreeCopy(const KdTree &k, void *nodes8, uint32_t *primIndices) {
     if (nodes8 && !k.nodes.empty()) memcpy(nodes8, k.nodes.data(), k.nodes.size() * sizeof(KdNode));
     if (primIndices && !k.primIndices.empty()) memcpy(primIndices, k.primIndices.data(), k.primIndices.size() * 4);
 }
 int hprt_kdinst_info(const HprtKdInst *t, uint32_t info[8]) try {
-    if (!t || !info) return SetError(HPRT_E_INVALID, "hprt_kdinst_info: null argument");
-    KdTreeInfo(t->top, info);
-    info[4] = (uint32_t)t->objects.size(); info[5] = 0; info[6] = 0; info[7] = (uint32_t)t->instanceObject.size();
-    for (const KdTree &o : t->objects) if (!o.nodes.empty()) { ++info[5]; info[6] = std::max(info[6], o.depth); }
-    return HPRT_OK;
+    return TwoLevelInfo("hprt_kdinst_info", t, info);
 } catch (...) { return hprt::HandleException(); }
 int hprt_kdinst_object_info(const HprtKdInst *t, uint32_t object, uint32_t info[4]) try {
-    if (!t || !info) return SetError(HPRT_E_INVALID, "hprt_kdinst_object_info: null argument");
-    if (object >= t->objects.size()) return SetError(HPRT_E_INVALID, "hprt_kdinst_object_info: object index out of range");
-    KdTreeInfo(t->objects[object], info);
-    return HPRT_OK;
+    return TwoLevelObjectInfo("hprt_kdinst_object_info", t, object, info);
 } catch (...) { return hprt::HandleException(); }
 int hprt_kdinst_copy(const HprtKdInst *t, void *nodes8, uint32_t *primIndices) try {
     if (!t) return SetError(HPRT_E_INVALID, "hprt_kdinst_copy: null argument");
@@ -700,9 +735,9 @@ int hprt_kdinst_copy(const HprtKdInst *t, void *nodes8, uint32_t *primIndices) t
     return HPRT_OK;
 } catch (...) { return hprt::HandleException(); }
 int hprt_kdinst_object_copy(const HprtKdInst *t, uint32_t object, void *nodes8, uint32_t *primIndices) try {
-    if (!t) return SetError(HPRT_E_INVALID, "hprt_kdinst_object_copy: null argument");
-    if (object >= t->objects.size()) return SetError(HPRT_E_INVALID, "hprt_kdinst_object_copy: object index out of range");
-    KdTreeCopy(t->objects[object], nodes8, primIndices);
+    const KdTree *o = TwoLevelObject("hprt_kdinst_object_copy", t, object);
+    if (!o) return HPRT_E_INVALID;
+    KdTreeCopy(*o, nodes8, primIndices);
     return HPRT_OK;
 } catch (...) { return hprt::HandleException(); }
 void hprt_kdinst_destroy(HprtKdInst *t) { delete t; }
@@ -711,28 +746,11 @@ void hprt_kdinst_destroy(HprtKdInst *t) { delete t; }
 // trees with a known todo depth reach the walk.  The tree keeps its primitive count and passes the structural check and the
 // two-level depth rule a built handle passes (HPRT_E_INVALID, HPRT_E_UNSUPPORTED; the handle is unchanged when refused).
 __attribute__((visibility("default"))) int hprt_debug_kdinst_bounds(const HprtKdInst *t, int object, float bounds6[6]) try {
-    if (!t || !bounds6 || object >= (int)t->objects.size()) return SetError(HPRT_E_INVALID, "hprt_debug_kdinst_bounds: bad argument");
-    memcpy(bounds6, (object < 0 ? t->top : t->objects[object]).bounds, 6 * sizeof(float));
-    return HPRT_OK;
+    return TwoLevelBounds("hprt_debug_kdinst_bounds", t, object, bounds6);
 } catch (...) { return hprt::HandleException(); }
 __attribute__((visibility("default"))) int hprt_debug_kdinst_set_tree(HprtKdInst *t, int object, size_t n_nodes, const uint32_t *nodes8, size_t n_idx,
                                                                        const uint32_t *idx, const float *bounds6) try {
-    if (!t || !nodes8 || !bounds6 || (n_idx && !idx) || object >= (int)t->objects.size()) return SetError(HPRT_E_INVALID, "hprt_debug_kdinst_set_tree: bad argument");
-    KdTree &dst = object < 0 ? t->top : t->objects[object];
-    if (object >= 0 && dst.nPrims < 2) return SetError(HPRT_E_INVALID, "hprt_debug_kdinst_set_tree: an object of one primitive has no tree");
-    KdTree k;
-    k.nPrims = dst.nPrims;
-    k.nodes.resize(n_nodes);
-    memcpy(k.nodes.data(), nodes8, n_nodes * sizeof(KdNode));
-    k.primIndices.assign(idx, idx + n_idx);
-    memcpy(k.bounds, bounds6, sizeof(k.bounds));
-    const char *bad = CheckKdTree(k, &k.depth);
-    if (*bad) return SetError(HPRT_E_INVALID, std::string("malformed tree: ") + bad);
-    k.maxDepth = k.depth; k.leaves = CountLeaves(k.nodes, 3u, 3u);
-    KdTree old = std::move(dst);
-    dst = std::move(k);
-    if (int rc = CheckKdInstDepth(*t)) { dst = std::move(old); return rc; }
-    return HPRT_OK;
+    return TwoLevelSetTree("hprt_debug_kdinst_set_tree", t, object, n_nodes, nodes8, n_idx, idx, bounds6);
 } catch (...) { return hprt::HandleException(); }
 
 // ---- RBSP tree (Accelerator "rbsp") and kd-aware RBSP tree (Accelerator "rbspkd"): one RbspTree, two handle types (helpers above) ----
@@ -771,26 +789,20 @@ int hprt_rbspkdinst_build(const HprtModel *m, const HprtRbspKdParams *params, Hp
     return BuildRbspInst("hprt_rbspkdinst_build", m, params, m ? m->sc.opt.rbspkd : RbspParams(), out);
 } catch (...) { return hprt::HandleException(); }
 int hprt_rbspinst_info(const HprtRbspInst *t, uint32_t info[10]) try {
-    if (!t || !info) return SetError(HPRT_E_INVALID, "hprt_rbspinst_info: null argument");
-    RbspTreeInfo(t->top, info);
-    info[4] = (uint32_t)t->objects.size(); info[5] = 0; info[6] = 0; info[7] = (uint32_t)t->instanceObject.size();
-    for (const RbspTree &o : t->objects) if (!o.nodes.empty()) { ++info[5]; info[6] = std::max(info[6], o.depth); }
+    if (int rc = TwoLevelInfo("hprt_rbspinst_info", t, info)) return rc;
     info[8] = t->top.M; info[9] = t->kdAware ? 1u : 0u;
     return HPRT_OK;
 } catch (...) { return hprt::HandleException(); }
 int hprt_rbspinst_object_info(const HprtRbspInst *t, uint32_t object, uint32_t info[4]) try {
-    if (!t || !info) return SetError(HPRT_E_INVALID, "hprt_rbspinst_object_info: null argument");
-    if (object >= t->objects.size()) return SetError(HPRT_E_INVALID, "hprt_rbspinst_object_info: object index out of range");
-    RbspTreeInfo(t->objects[object], info);
-    return HPRT_OK;
+    return TwoLevelObjectInfo("hprt_rbspinst_object_info", t, object, info);
 } catch (...) { return hprt::HandleException(); }
 int hprt_rbspinst_copy(const HprtRbspInst *t, void *nodes8, uint32_t *primIndices, float *directions) try {
     return RbspCopy("hprt_rbspinst_copy", t ? &t->top : nullptr, nodes8, primIndices, directions);
 } catch (...) { return hprt::HandleException(); }
 int hprt_rbspinst_object_copy(const HprtRbspInst *t, uint32_t object, void *nodes8, uint32_t *primIndices) try {
-    if (!t) return SetError(HPRT_E_INVALID, "hprt_rbspinst_object_copy: null argument");
-    if (object >= t->objects.size()) return SetError(HPRT_E_INVALID, "hprt_rbspinst_object_copy: object index out of range");
-    return RbspCopy("hprt_rbspinst_object_copy", &t->objects[object], nodes8, primIndices, nullptr);
+    const RbspTree *o = TwoLevelObject("hprt_rbspinst_object_copy", t, object);
+    if (!o) return HPRT_E_INVALID;
+    return RbspCopy("hprt_rbspinst_object_copy", o, nodes8, primIndices, nullptr);
 } catch (...) { return hprt::HandleException(); }
 void hprt_rbspinst_destroy(HprtRbspInst *t) { delete t; }
 // Diagnostics hooks (not part of include/hprt.h; tests): the bounds of the top-level tree (object < 0) or of one object's tree, and
@@ -799,28 +811,11 @@ void hprt_rbspinst_destroy(HprtRbspInst *t) { delete t; }
 // structural check and the two-level depth rule a built handle passes (HPRT_E_INVALID, HPRT_E_UNSUPPORTED; the handle is unchanged
 // when refused).
 __attribute__((visibility("default"))) int hprt_debug_rbspinst_bounds(const HprtRbspInst *t, int object, float bounds6[6]) try {
-    if (!t || !bounds6 || object >= (int)t->objects.size()) return SetError(HPRT_E_INVALID, "hprt_debug_rbspinst_bounds: bad argument");
-    memcpy(bounds6, (object < 0 ? t->top : t->objects[object]).bounds, 6 * sizeof(float));
-    return HPRT_OK;
+    return TwoLevelBounds("hprt_debug_rbspinst_bounds", t, object, bounds6);
 } catch (...) { return hprt::HandleException(); }
 __attribute__((visibility("default"))) int hprt_debug_rbspinst_set_tree(HprtRbspInst *t, int object, size_t n_nodes, const uint32_t *nodes8, size_t n_idx,
                                                                          const uint32_t *idx, const float *bounds6) try {
-    if (!t || !nodes8 || !bounds6 || (n_idx && !idx) || object >= (int)t->objects.size()) return SetError(HPRT_E_INVALID, "hprt_debug_rbspinst_set_tree: bad argument");
-    RbspTree &dst = object < 0 ? t->top : t->objects[object];
-    if (object >= 0 && dst.nPrims < 2) return SetError(HPRT_E_INVALID, "hprt_debug_rbspinst_set_tree: an object of one primitive has no tree");
-    RbspTree r;
-    r.nPrims = dst.nPrims; r.M = dst.M; r.directions = dst.directions;
-    r.nodes.resize(n_nodes);
-    memcpy(r.nodes.data(), nodes8, n_nodes * sizeof(RbspNode));
-    r.primIndices.assign(idx, idx + n_idx);
-    memcpy(r.bounds, bounds6, sizeof(r.bounds));
-    const char *bad = CheckRbspTree(r, &r.depth);
-    if (*bad) return SetError(HPRT_E_INVALID, std::string("malformed tree: ") + bad);
-    r.maxDepth = r.depth; r.leaves = CountLeaves(r.nodes, RbspBitMask(r.M), r.M);
-    RbspTree old = std::move(dst);
-    dst = std::move(r);
-    if (int rc = CheckRbspInstDepth(*t)) { dst = std::move(old); return rc; }
-    return HPRT_OK;
+    return TwoLevelSetTree("hprt_debug_rbspinst_set_tree", t, object, n_nodes, nodes8, n_idx, idx, bounds6);
 } catch (...) { return hprt::HandleException(); }
 
 int hprt_rbsp_build_device(const HprtModel *m, const HprtRbspParams *params, const HprtBuildDeviceOpts *opts, HprtBuildDeviceStats *stats, HprtRbsp **out) try {

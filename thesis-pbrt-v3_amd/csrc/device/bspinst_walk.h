@@ -25,32 +25,13 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "kernels.h"
+#include "two_level.h"
 
 namespace hprt {
 
-// Bounds3::IntersectP(const Ray &, Float *hitt0, Float *hitt1) (core/geometry.h:1730-1751): the root interval of either level
-// (bsp_walk.h's bsp_root_interval over bounds passed by value)
-__device__ __forceinline__ bool bspinst_root_interval(vec3 lo, vec3 hi, vec3 ro, vec3 rd, float rayTMax, float *hitt0, float *hitt1) {
-    float t0 = 0, t1 = rayTMax;
-    const float robust = 1 + 2 * gamma_n(3);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        const float invRayDir = 1 / rd.get(i);
-        float tNear = (lo.get(i) - ro.get(i)) * invRayDir;
-        float tFar = (hi.get(i) - ro.get(i)) * invRayDir;
-        if (tNear > tFar) { const float s = tNear; tNear = tFar; tFar = s; }
-        tFar *= robust;
-        t0 = tNear > t0 ? tNear : t0;
-        t1 = tFar < t1 ? tFar : t1;
-        if (t0 > t1) return false;
-    }
-    *hitt0 = t0; *hitt1 = t1;
-    return true;
-}
-
 // The whole kernel body.  ANY_HIT: IntersectP (no early-out on a closer hit); COUNT: counters and per-ray statistics; QUAD: the
 // scene has spheres.  nodes / primIdx: the attached trees (one-primitive leaves and primIdx hold ORDERED indices over all
-// aggregates); entries: two float4 per instance, {lo, root} {hi, prim} (DevRbspInstEntry); lo / hi: the top-level tree's bounds.
+// aggregates); entries: two float4 per instance, {lo, root} {hi, prim} (DevInstEntry, two_level.h); lo / hi: the top-level tree's bounds.
 // stackMem: the kernel's [LDS][BLOCK] LDS todo entries.
 template <bool ANY_HIT, bool COUNT, bool QUAD, int LDS, int BLOCK, class Step, bool KD_SHARE = false>
 __device__ __forceinline__ void bspinst_walk(const DevScene &sc, const uint2 *nodes, const uint32_t *primIdx, const float4 *entries, const float *lo,
@@ -90,7 +71,7 @@ __device__ __forceinline__ void bspinst_walk(const DevScene &sc, const uint2 *no
         bool hit = false;
         int32_t prim = -1, hitInst = -1; float hb0 = 0.f, hb1 = 0.f, hb2 = 0.f;
         float tMin, tMax;
-        if (bspinst_root_interval(vec3(lo[0], lo[1], lo[2]), vec3(hi[0], hi[1], hi[2]), ro, rd, rayTMax, &tMin, &tMax)) {
+        if (inst_root_interval(vec3(lo[0], lo[1], lo[2]), vec3(hi[0], hi[1], hi[2]), ro, rd, rayTMax, &tMin, &tMax)) {
             vec3 invDir(1 / rd.x, 1 / rd.y, 1 / rd.z);
             RayShear shear = ray_shear(rd, invDir);
             const float rootTMax = tMax;
@@ -197,7 +178,7 @@ __device__ __forceinline__ void bspinst_walk(const DevScene &sc, const uint2 *no
                             shear = ray_shear(d2, invDir);
                             node = __float_as_uint(e0.w);
                             if (__float_as_int(e1.w) >= 0) direct = true;      // a lone primitive, wrapped as it is: no bounds test, no node
-                            else if (bspinst_root_interval(vec3(e0.x, e0.y, e0.z), vec3(e1.x, e1.y, e1.z), ro, rd, rayTMax, &tMin, &tMax)) objRootTMax = tMax;
+                            else if (inst_root_interval(vec3(e0.x, e0.y, e0.z), vec3(e1.x, e1.y, e1.z), ro, rd, rayTMax, &tMin, &tMax)) objRootTMax = tMax;
                             else leave = true;                                  // the ray misses the object's bounds
                             entered = true;
                             break;

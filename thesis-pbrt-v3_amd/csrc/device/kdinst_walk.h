@@ -4,15 +4,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "kernels.h"
+#include "two_level.h"
 
 namespace hprt {
-
-// What a TransformedPrimitive wraps, per instance (32 bytes, two 16-byte reads).  prim < 0: the object's KdTreeAccel — root is its
-// root node in DevKdInst::nodes, lo / hi are KdTreeAccel::bounds in object space.  prim >= 0: the object's one primitive, wrapped as
-// it is (core/api.cpp:1798) and tested without a bounds test — root is a one-primitive leaf the attach step made for it (its
-// primitive word is prim), which the walk enters without counting a node.
-struct DevKdInstEntry { float lo[3]; uint32_t root; float hi[3]; int32_t prim; };
-static_assert(sizeof(DevKdInstEntry) == 32, "DevKdInstEntry is two 16-byte words");
 
 // The attached trees in HBM.  nodes: the reference's 8-byte KdAccelNode[] of the top-level tree (root 0) followed by every object
 // tree's, with three changes: aboveChild and primitiveIndicesOffset of an object tree are rebased to the shared arrays, and the
@@ -21,7 +15,7 @@ static_assert(sizeof(DevKdInstEntry) == 32, "DevKdInstEntry is two 16-byte words
 struct DevKdInst {
     const uint2 *nodes; uint32_t nNodes;
     const uint32_t *primIdx; uint32_t nPrimIdx;
-    const DevKdInstEntry *entries; uint32_t nEntries;      // one per instance (DevScene::instances numbering)
+    const DevInstEntry *entries; uint32_t nEntries;      // one per instance (DevScene::instances numbering)
     float lo[3], hi[3];                 // the top-level KdTreeAccel::bounds
     uint32_t depth;                     // top-level depth + deepest object depth + 1: the most todo entries a ray can hold
 };

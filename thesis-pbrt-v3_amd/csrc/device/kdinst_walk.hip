@@ -47,26 +47,6 @@ static_assert(HPRT_KDINST_LDS + HPRT_SPILL_STACK >= (int)KD_TODO_MAX, "LDS + dee
 static_assert(HPRT_DEEP_THREADS >= 256u * HPRT_KDINST_BLOCK * HPRT_KDINST_WAVES && HPRT_DEEP_THREADS >= 256u * HPRT_KDINST_BLOCK * HPRT_KDINST_QUAD_WAVES,
               "the deep-stack area must cover the two-level kd walk's grids");
 
-// Bounds3::IntersectP(const Ray &, Float *hitt0, Float *hitt1) (core/geometry.h:1730-1751): the root interval of either level
-// (kd_walk.hip's kd_root_interval over bounds passed by value)
-__device__ __forceinline__ bool kdinst_root_interval(vec3 lo, vec3 hi, vec3 ro, vec3 rd, float rayTMax, float *hitt0, float *hitt1) {
-    float t0 = 0, t1 = rayTMax;
-    const float robust = 1 + 2 * gamma_n(3);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        const float invRayDir = 1 / rd.get(i);
-        float tNear = (lo.get(i) - ro.get(i)) * invRayDir;
-        float tFar = (hi.get(i) - ro.get(i)) * invRayDir;
-        if (tNear > tFar) { const float s = tNear; tNear = tFar; tFar = s; }
-        tFar *= robust;
-        t0 = tNear > t0 ? tNear : t0;
-        t1 = tFar < t1 ? tFar : t1;
-        if (t0 > t1) return false;
-    }
-    *hitt0 = t0; *hitt1 = t1;
-    return true;
-}
-
 // ANY_HIT: IntersectP; COUNT: counters and per-ray statistics; QUAD: the scene has spheres (the interval-arithmetic test is
 // compiled in only then).
 template <bool ANY_HIT, bool COUNT, bool QUAD>
@@ -105,7 +85,7 @@ __global__ __launch_bounds__(HPRT_KDINST_BLOCK, QUAD ? HPRT_KDINST_QUAD_WAVES : 
         bool hit = false;
         int32_t prim = -1, hitInst = -1; float hb0 = 0.f, hb1 = 0.f, hb2 = 0.f;
         float tMin, tMax;
-        if (kdinst_root_interval(vec3(kd.lo[0], kd.lo[1], kd.lo[2]), vec3(kd.hi[0], kd.hi[1], kd.hi[2]), ro, rd, rayTMax, &tMin, &tMax)) {
+        if (inst_root_interval(vec3(kd.lo[0], kd.lo[1], kd.lo[2]), vec3(kd.hi[0], kd.hi[1], kd.hi[2]), ro, rd, rayTMax, &tMin, &tMax)) {
             vec3 invDir(1 / rd.x, 1 / rd.y, 1 / rd.z);
             RayShear shear = ray_shear(rd, invDir);
             const float rootTMax = tMax;
@@ -217,7 +197,7 @@ __global__ __launch_bounds__(HPRT_KDINST_BLOCK, QUAD ? HPRT_KDINST_QUAD_WAVES : 
                             shear = ray_shear(d2, invDir);
                             node = __float_as_uint(e0.w);
                             if (__float_as_int(e1.w) >= 0) direct = true;      // a lone primitive, wrapped as it is: no bounds test, no node
-                            else if (kdinst_root_interval(vec3(e0.x, e0.y, e0.z), vec3(e1.x, e1.y, e1.z), ro, rd, rayTMax, &tMin, &tMax)) objRootTMax = tMax;
+                            else if (inst_root_interval(vec3(e0.x, e0.y, e0.z), vec3(e1.x, e1.y, e1.z), ro, rd, rayTMax, &tMin, &tMax)) objRootTMax = tMax;
                             else leave = true;                                  // the ray misses the object's bounds
                             entered = true;
                             break;

@@ -4,15 +4,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "kernels.h"
+#include "two_level.h"
 
 namespace hprt {
-
-// What a TransformedPrimitive wraps, per instance (32 bytes, two 16-byte reads).  prim < 0: the object's RBSP tree — root is its
-// root node in DevRbspInst::nodes, lo / hi are GenericBSP::bounds in object space.  prim >= 0: the object's one primitive, wrapped
-// as it is (core/api.cpp:1798) and tested without a bounds test — root is a one-primitive leaf the attach step made for it (its
-// primitive word is prim), which the walk enters without counting a node.
-struct DevRbspInstEntry { float lo[3]; uint32_t root; float hi[3]; int32_t prim; };
-static_assert(sizeof(DevRbspInstEntry) == 32, "DevRbspInstEntry is two 16-byte words");
 
 // The attached trees in HBM.  nodes: the reference's 8-byte RBSPNode[] of the top-level tree (root 0) followed by every object
 // tree's, with three changes: aboveChild and primitiveIndicesOffset of an object tree are rebased to the shared arrays, and the
@@ -22,7 +16,7 @@ static_assert(sizeof(DevRbspInstEntry) == 32, "DevRbspInstEntry is two 16-byte w
 struct DevRbspInst {
     const uint2 *nodes; uint32_t nNodes;
     const uint32_t *primIdx; uint32_t nPrimIdx;
-    const DevRbspInstEntry *entries; uint32_t nEntries;      // one per instance (DevScene::instances numbering)
+    const DevInstEntry *entries; uint32_t nEntries;      // one per instance (DevScene::instances numbering)
     float lo[3], hi[3];                 // the top-level GenericBSP::bounds
     uint32_t depth;                     // top-level depth + deepest object depth + 1: the most todo entries a ray can hold
     uint32_t M, off, mask;              // directions; flags: leaf M | nPrims << off, interior axis | aboveChild << off

@@ -109,14 +109,13 @@ struct HprtScene {
     hprt::DevBuf kdShare, pixelKdLocal, pixelKdFilm; bool pixelKdValid = false;
     std::vector<uint32_t> topOrder; bool instanced = false;
     bool hasSubstrateBin = false;                     // some triangle carries BIN_SUBSTRATE: the substrate shading variant is launched
-    // Two-level kd-trees (hprt_scene_attach_kdinst, the one tree walk of an instanced scene): treeNodes / treePrims hold the nodes and
-    // primitiveIndices of the top-level tree followed by every object tree's, kdInstEntries one DevKdInstEntry per instance;
-    // objectOrder / objectPrimBase map an object tree's creation-order primitives as topOrder maps the top level's; instanceObject:
-    // each instance's object definition
-    hprt::DevBuf kdInstEntries; hprt::DevKdInst kdinst{};
-    // Two-level RBSP trees (hprt_scene_attach_rbspinst; Walk::RbspInst, or Walk::RbspKdInst for kd-aware trees): the same layout with
-    // one DevRbspInstEntry per instance in kdInstEntries; kd-aware trees count their kd share in kdShare as the rbspkd walk does
-    hprt::DevRbspInst rbspinst{};
+    // Two-level trees, the tree walks of an instanced scene (AttachTwoLevel, capi_device.hip): treeNodes / treePrims hold the nodes and
+    // primitiveIndices of the top-level tree followed by every object tree's, instEntries one DevInstEntry per instance
+    // (device/two_level.h).  kdinst: two-level kd-trees (hprt_scene_attach_kdinst, Walk::KdInst); rbspinst: two-level RBSP trees
+    // (hprt_scene_attach_rbspinst; Walk::RbspInst, or Walk::RbspKdInst for kd-aware trees, which count their kd share in kdShare as
+    // the rbspkd walk does).  objectOrder / objectPrimBase map an object tree's creation-order primitives as topOrder maps the top
+    // level's; instanceObject: each instance's object definition
+    hprt::DevBuf instEntries; hprt::DevKdInst kdinst{}; hprt::DevRbspInst rbspinst{};
     std::vector<std::vector<uint32_t>> objectOrder; std::vector<uint32_t> objectPrimBase; std::vector<int32_t> instanceObject;
     ~HprtScene() { if (hostCounts) (void)hipHostFree(hostCounts); if (lastUse) (void)hipEventDestroy(lastUse); }
 };

@@ -16,21 +16,20 @@ struct HprtBvh {
 };
 
 struct HprtKdTree { hprt::KdTree tree; };
-// Two-level kd-trees (pbrtObjectInstance, core/api.cpp:1794-1819): the top-level tree over the top-level items, and per object
-// definition its own tree — none (no nodes) for an object of one primitive, which is wrapped as it is (:1798)
-struct HprtKdInst {
-    hprt::KdTree top;
-    std::vector<hprt::KdTree> objects;        // objects[o].nPrims: the object's primitives, tree or not
+// Two-level trees (pbrtObjectInstance, core/api.cpp:1794-1819): the top-level tree over the top-level items, and per object
+// definition its own tree — none (no nodes) for an object of one primitive, which is wrapped as it is (:1798).  Tree: KdTree
+// (HprtKdInst), RbspTree (HprtRbspInst); what a further tree type has to supply: DESIGN.md §8k
+template <typename Tree> struct HprtTwoLevel {
+    Tree top;
+    std::vector<Tree> objects;                // objects[o].nPrims: the object's primitives, tree (nodes) or not
     std::vector<int32_t> instanceObject;      // per instance, its object definition
 };
+struct HprtKdInst : HprtTwoLevel<hprt::KdTree> {};
 struct HprtRbsp { hprt::RbspTree tree; };
 struct HprtRbspKd { hprt::RbspTree tree; };     // built with RbspParams::kdAware
-// Two-level RBSP trees (pbrtObjectInstance under Accelerator "rbsp" / "rbspkd"): HprtKdInst's shape over RbspTrees.  One handle
-// type for both cost models; every tree is built with the same parameters, so all share M and the direction table.
-struct HprtRbspInst {
-    hprt::RbspTree top;
-    std::vector<hprt::RbspTree> objects;      // objects[o].nPrims: the object's primitives, tree (nodes) or not
-    std::vector<int32_t> instanceObject;      // per instance, its object definition
+// Two-level RBSP trees (Accelerator "rbsp" / "rbspkd"): one handle type for both cost models; every tree is built with the same
+// parameters, so all share M and the direction table.
+struct HprtRbspInst : HprtTwoLevel<hprt::RbspTree> {
     bool kdAware = false;                     // built by hprt_rbspkdinst_build: walked with the kd form at axis nodes
 };
 struct HprtBspPaper { hprt::BspPaperTree tree; };
