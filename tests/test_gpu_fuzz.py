@@ -111,7 +111,7 @@ def _shape(rng):
     return pre + 'Shape "trianglemesh" ' + mesh + "\n"
 
 
-def random_scene(seed):
+def random_scene(seed, objects=None, twins=True):
     rng = np.random.default_rng(1000 + seed)
     body = ""
     # ---- textures ----
@@ -162,14 +162,16 @@ def random_scene(seed):
             body += "ReverseOrientation\n"
         shape = _shape(rng)
         body += shape
-        if rng.random() < .2:      # the same surface once more with another material: ties in t, settled by the traversal order alone
+        if rng.random() < .2 and twins:      # the same surface once more with another material: ties in t, settled by the traversal order alone
             body += _material(rng, textures) + shape
         body += "AttributeEnd\n"
     nobj = int(rng.choice([0, 0, 1, 2]))
+    if objects is not None:
+        nobj = objects
     for k in range(nobj):
         body += 'ObjectBegin "o%d"\n' % k
         for _ in range(int(rng.integers(1, 4))):
-            body += "AttributeBegin\n" + _material(rng, textures) + (_transform(rng) if rng.random() < .5 else "") + _shape(rng) + "AttributeEnd\n"
+            body += "AttributeBegin\n" + _material(rng, textures) + (_transform(rng) if rng.random() < .5 or not twins else "") + _shape(rng) + "AttributeEnd\n"
         body += "ObjectEnd\n"
         for _ in range(int(rng.integers(1, 4))):
             body += "AttributeBegin\n" + (_material(rng, textures) if rng.random() < .3 else "") + _transform(rng) + 'ObjectInstance "o%d"\nAttributeEnd\n' % k
