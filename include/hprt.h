@@ -382,6 +382,44 @@ int hprt_bsppaperkd_copy(const HprtBspPaperKd *t, void *nodes20, uint32_t *prim_
 void hprt_bsppaperkd_destroy(HprtBspPaperKd *t);
 
 /* ------------------------------------------------------------------------ */
+/* Two-level general BSP trees (Accelerator "bsppaper" / "bsppaperkd" on a  */
+/* model with object instances).  Stands in for pbrtObjectInstance          */
+/* (core/api.cpp:1794-1819): MakeAccelerator(renderOptions->AcceleratorName,*/
+/* ...) over the primitives of every object that has more than one (an      */
+/* object with exactly one is wrapped as it is, :1798), each wrapped in a   */
+/* TransformedPrimitive, and pbrtWorldEnd's top-level accelerator over      */
+/* those wrappers: a general BSP tree whose leaves hold general BSP trees.  */
+/* Opt-in: hprt_bsppaper_build and hprt_bsppaperkd_build keep refusing such */
+/* models and the front end keeps their BVH and its warning.                */
+/* ------------------------------------------------------------------------ */
+typedef struct HprtBspPaperInst HprtBspPaperInst;
+/* One tree per object with more than one primitive, over the object's primitives in object space (BSPPaper::buildTree,
+ * accelerators/bspPaper.cpp:34-305; a triangle offers its object-space planes), and the top-level tree over the top-level items in
+ * creation order.  There an instance is a TransformedPrimitive bounded by its WorldBound (core/primitive.h:116-118): it inherits
+ * Primitive::getBSPPaperPlanes (core/primitive.h:92-95: no planes) and Primitive::getBounds (core/primitive.h:72-80: the 8 corners
+ * of that bound), so it contributes axis candidates only and is classified under a triangle's plane by those corners.  Every tree
+ * takes the same parameters — params, or with NULL those of the scene's Accelerator line; maxdepth -1 resolves per tree from its
+ * own primitive count.  hprt_bsppaperkdinst_build builds kd-aware trees (BSPPaperKd::buildTree, accelerators/bspPaperKd.cpp:34-339,
+ * over BSPKdNode); the handle remembers which.  HPRT_E_UNSUPPORTED for a model without instances (the job of hprt_bsppaper_build /
+ * hprt_bsppaperkd_build) and when depth(top) + deepest object depth + 1 exceeds HPRT_BSPPAPER_MAX_DEPTH (=
+ * HPRT_BSPPAPERKD_MAX_DEPTH): the walk keeps both levels' todo entries and one saved top-level position in one list. */
+int hprt_bsppaperinst_build(const HprtModel *m, const HprtBspPaperParams *params, HprtBspPaperInst **out);
+int hprt_bsppaperkdinst_build(const HprtModel *m, const HprtBspPaperKdParams *params, HprtBspPaperInst **out);
+/* info[0..7] as hprt_rbspinst_info's: nodes, leaves, primitive references, depth of the top-level tree; object definitions, object
+ * trees, the deepest object tree's depth, instances.  info[8] = 1 for kd-aware trees, info[9] = interior nodes of the axis sweep
+ * (kd-aware: kd interior nodes, nbKdNodes) over all trees, info[10] = interior nodes on a triangle's plane (nbBSPNodes) over all
+ * trees, info[11] = 0 (reserved) */
+int hprt_bsppaperinst_info(const HprtBspPaperInst *t, uint32_t info[12]);
+/* info[0..3] as above for the tree of object definition `object`; all zero for an object of one primitive, which has no
+ * tree (core/api.cpp:1798). */
+int hprt_bsppaperinst_object_info(const HprtBspPaperInst *t, uint32_t object, uint32_t info[4]);
+/* The arrays of the top-level tree / of one object's tree, as hprt_bsppaper_copy / hprt_bsppaperkd_copy return them: nodes20 is
+ * 5 words per node, the reference's BSPNode (BSP.h:122-184) or BSPKdNode (BSPKd.h:11-57); either may be NULL. */
+int hprt_bsppaperinst_copy(const HprtBspPaperInst *t, void *nodes20, uint32_t *prim_indices);
+int hprt_bsppaperinst_object_copy(const HprtBspPaperInst *t, uint32_t object, void *nodes20, uint32_t *prim_indices);
+void hprt_bsppaperinst_destroy(HprtBspPaperInst *t);
+
+/* ------------------------------------------------------------------------ */
 /* Node-based BSP trees (Accelerator "bsparbitrary", "bspcluster",          */
 /* "bsprandom", and each with "withkd" or "fastkd" appended).  Stand in for */
 /* BSPNodeBased::buildTree (accelerators/bspNodeBased.cpp:27-223),          */
@@ -593,8 +631,16 @@ int hprt_scene_attach_kdinst(HprtScene *s, const HprtKdInst *t);
  * share (interior nodes of direction < 3, both levels) comes from hprt_scene_kd_counters and hprt_pixel_kd_stats_read exactly
  * as for an rbspkd scene, for plain trees those report zeros. */
 int hprt_scene_attach_rbspinst(HprtScene *s, const HprtRbspInst *t);
+/* The same for two-level general BSP trees: BSP::Intersect / IntersectP (accelerators/BSP.cpp:27-165) — for a handle of
+ * hprt_bsppaperkdinst_build BSPKd::Intersect / IntersectP (accelerators/BSPKd.cpp:25-171) — on both levels, joined by
+ * TransformedPrimitive (core/primitive.cpp:77-102); an object's split axes are object-space vectors and meet the instance's
+ * transformed ray.  The checks are hprt_scene_attach_kdinst's with CheckBspPaperTree / CheckBspPaperKdTree and
+ * HPRT_BSPPAPER_MAX_DEPTH; a scene without instances is HPRT_E_UNSUPPORTED.  Counters follow the bsppaper scene's contract, summed
+ * over both levels; for kd-aware trees the kd share (kd interior nodes, both levels) comes from hprt_scene_kd_counters and
+ * hprt_pixel_kd_stats_read exactly as for a bsppaperkd scene, for plain trees those report zeros. */
+int hprt_scene_attach_bsppaperinst(HprtScene *s, const HprtBspPaperInst *t);
 /* kdTreeNodeTraversals (out[0]) and kdTreeNodeTraversalsP (out[1]) of the last counting trace (hprt_intersect / hprt_occluded
- * with counters) or counting render of an rbspkd or bsppaperkd scene, or of a scene with kd-aware two-level RBSP trees; zeros
+ * with counters) or counting render of an rbspkd or bsppaperkd scene, or of a scene with kd-aware two-level RBSP or general BSP trees; zeros
  * for any other scene. */
 int hprt_scene_kd_counters(HprtScene *s, uint64_t out[2]);
 

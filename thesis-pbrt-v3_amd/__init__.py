@@ -352,6 +352,14 @@ def _load():
         "hprt_bsppaperkd_copy": (C.c_int, [vp, vp, vp]),
         "hprt_bsppaperkd_destroy": (None, [vp]),
         "hprt_scene_attach_bsppaperkd": (C.c_int, [vp, vp]),
+        "hprt_bsppaperinst_build": (C.c_int, [vp, vp, P(vp)]),
+        "hprt_bsppaperkdinst_build": (C.c_int, [vp, vp, P(vp)]),
+        "hprt_bsppaperinst_info": (C.c_int, [vp, P(u32)]),
+        "hprt_bsppaperinst_object_info": (C.c_int, [vp, u32, P(u32)]),
+        "hprt_bsppaperinst_copy": (C.c_int, [vp, vp, vp]),
+        "hprt_bsppaperinst_object_copy": (C.c_int, [vp, u32, vp, vp]),
+        "hprt_bsppaperinst_destroy": (None, [vp]),
+        "hprt_scene_attach_bsppaperinst": (C.c_int, [vp, vp]),
         "hprt_bspnode_build": (C.c_int, [vp, vp, P(vp)]),
         "hprt_bspnode_build_from_triangles": (C.c_int, [sz, vp, vp, P(vp)]),
         "hprt_bspnodekd_build": (C.c_int, [vp, vp, P(vp)]),
@@ -362,7 +370,7 @@ def _load():
     }
     # the two-level handles' diagnostics hooks (not part of include/hprt.h, so not among EXPORTS)
     debug = {}
-    for prefix in ("kdinst", "rbspinst"):
+    for prefix in ("kdinst", "rbspinst", "bsppaperinst"):
         debug["hprt_debug_%s_bounds" % prefix] = (C.c_int, [vp, C.c_int, vp])
         debug["hprt_debug_%s_set_tree" % prefix] = (C.c_int, [vp, C.c_int, sz, vp, sz, vp, vp])
     for name, (res, args) in list(sig.items()) + list(debug.items()):
@@ -529,11 +537,13 @@ class KdTree(_Tree):
 
 
 class _TwoLevel:
-    """Two-level trees (host) of a model WITH object instances (KdInst, RbspInst) over the C calls hprt_<_prefix>_info /
+    """Two-level trees (host) of a model WITH object instances (KdInst, RbspInst, BspPaperInst) over the C calls hprt_<_prefix>_info /
     _object_info / _copy / _object_copy / _destroy and the diagnostics hooks hprt_debug_<_prefix>_bounds / _set_tree; info() names
-    the words after the eight every handle has `_extra_keys`, and the copy of the RBSP trees takes a direction table as well."""
+    the words after the eight every handle has `_extra_keys`, and the copy of the RBSP trees takes a direction table as well.
+    `_node_words`: the uint32 words of a node in copy() / object_copy() / set_tree() — 2, or the general BSP trees' 5."""
     _prefix = None
     _extra_keys = ()
+    _node_words = 2
     _KEYS = ("nodes", "leaves", "prim_refs", "depth")
 
     def _fn(self, name, debug=False):
@@ -541,7 +551,8 @@ class _TwoLevel:
 
     def info(self):
         """the top-level tree's nodes, leaves, prim_refs and depth; objects (definitions), object_trees (those with more than one
-        primitive), object_depth (the deepest object tree's) and instances; RbspInst: M (directions of every tree) and kd_aware"""
+        primitive), object_depth (the deepest object tree's) and instances; RbspInst: M (directions of every tree) and kd_aware;
+        BspPaperInst: kd_aware, axis_interior (kd-aware: kd interior nodes) and plane_interior over all trees, reserved (0)"""
         keys = self._KEYS + ("objects", "object_trees", "object_depth", "instances") + self._extra_keys
         i = (C.c_uint32 * len(keys))()
         _check(self._fn("info")(self._h, i))
@@ -554,16 +565,17 @@ class _TwoLevel:
         return dict(zip(self._KEYS, i))
 
     def copy(self):
-        """(nodes [n, 2] uint32, prim_indices uint32) of the top-level tree, as KdTree.arrays() / Rbsp.arrays() give them"""
+        """(nodes [n, 2] uint32, prim_indices uint32) of the top-level tree, as KdTree.arrays() / Rbsp.arrays() give them
+        (BspPaperInst: nodes [n, 5], as BspPaper.arrays() / BspPaperKd.arrays())"""
         inf = self.info()
-        nodes = np.zeros((inf["nodes"], 2), np.uint32); idx = np.zeros(inf["prim_refs"], np.uint32)
+        nodes = np.zeros((inf["nodes"], self._node_words), np.uint32); idx = np.zeros(inf["prim_refs"], np.uint32)
         _check(self._fn("copy")(self._h, _ptr(nodes), _ptr(idx), *([None] if "M" in inf else [])))
         return nodes, idx
 
     def object_copy(self, obj):
         """the same for the tree of object definition `obj` (empty arrays for an object of one primitive)"""
         inf = self.object_info(obj)
-        nodes = np.zeros((inf["nodes"], 2), np.uint32); idx = np.zeros(inf["prim_refs"], np.uint32)
+        nodes = np.zeros((inf["nodes"], self._node_words), np.uint32); idx = np.zeros(inf["prim_refs"], np.uint32)
         _check(self._fn("object_copy")(self._h, obj, _ptr(nodes), _ptr(idx)))
         return nodes, idx
 
@@ -580,7 +592,7 @@ class _TwoLevel:
         E_INVALID / E_UNSUPPORTED, the handle unchanged)."""
         nodes = np.ascontiguousarray(nodes, np.uint32); idx = np.ascontiguousarray(prim_indices, np.uint32).ravel()
         b = np.ascontiguousarray(bounds, np.float32).ravel()
-        assert nodes.ndim == 2 and nodes.shape[1] == 2 and b.shape[0] == 6
+        assert nodes.ndim == 2 and nodes.shape[1] == self._node_words and b.shape[0] == 6
         _check(self._fn("set_tree", debug=True)(self._h, int(obj), nodes.shape[0], _ptr(nodes), idx.shape[0], _ptr(idx), _ptr(b)))
 
     def __del__(self):
@@ -760,6 +772,27 @@ class BspPaperKd(_Tree):
         return nodes, idx
 
 
+class BspPaperInst(_TwoLevel):
+    """Two-level general BSP trees (host) of a model WITH object instances, as pbrtObjectInstance and pbrtWorldEnd build them under
+    Accelerator "bsppaper" — or, with kd_aware, "bsppaperkd" — (core/api.cpp:1794-1819): one tree per object of more than one
+    primitive and the top-level tree over the top-level items, all with the same parameters.  BspPaperInst(model) takes the scene's
+    Accelerator line; given isect_cost, the keyword parameters replace it, as for BspPaper / BspPaperKd.  copy() / object_copy()
+    return, and set_tree takes, the 5-word nodes of BspPaper.arrays() / BspPaperKd.arrays().  Scene.attach_bsppaperinst walks them."""
+    _prefix = "bsppaperinst"
+    _extra_keys = ("kd_aware", "axis_interior", "plane_interior", "reserved")
+    _node_words = 5
+
+    def __init__(self, model, kd_aware=False, isect_cost=None, trav_cost=5, kd_trav_cost=1, empty_bonus=0.0, max_prims=1, max_depth=-1, threads=0):
+        h = C.c_void_p()
+        if kd_aware:
+            prm = None if isect_cost is None else C.byref(BspPaperKdParams(isect_cost, trav_cost, kd_trav_cost, empty_bonus, max_prims, max_depth, threads))
+            _check(lib.hprt_bsppaperkdinst_build(model._h, prm, C.byref(h)))
+        else:
+            prm = None if isect_cost is None else C.byref(BspPaperParams(isect_cost, trav_cost, empty_bonus, max_prims, max_depth, threads))
+            _check(lib.hprt_bsppaperinst_build(model._h, prm, C.byref(h)))
+        self._h = h
+
+
 class BspNodeParams(C.Structure):
     """HprtBspNodeParams: chooser and form (the accelerator's name), K, the seed, the parameters of the nine
     Create...TreeAccelerator functions and the builder's thread count."""
@@ -882,6 +915,12 @@ class Scene:
         the rbspkd scene's, with kd_counters() and pixel_kd_stats() — summed over both levels."""
         _check(lib.hprt_scene_attach_rbspinst(self._h, rbspinst._h))
         self._rbspinst = rbspinst
+
+    def attach_bsppaperinst(self, bsppaperinst):
+        """hprt_scene_attach_bsppaperinst: every later trace and render of this INSTANCED scene walks the two-level general BSP trees
+        `bsppaperinst` (a BspPaperInst of this scene's model); kd-aware trees count their kd share like a bsppaperkd scene."""
+        _check(lib.hprt_scene_attach_bsppaperinst(self._h, bsppaperinst._h))
+        self._bsppaperinst = bsppaperinst
 
     def attach_rbsp(self, rbsp):
         """hprt_scene_attach_rbsp: every later trace and render walks `rbsp` (built over this scene's primitives); replaces an

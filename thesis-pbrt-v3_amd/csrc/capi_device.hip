@@ -291,7 +291,8 @@ __attribute__((visibility("default"))) int hprt_debug_capture_rays(HprtScene *s,
 static int ApiStreams(HprtScene *s, size_t n, RayStream *rays, HitStream *hits);
 // The walks that count their kd interior nodes apart (kdShare, pixelKdLocal / pixelKdFilm)
 static bool CountsKdShare(const HprtScene *s) {
-    return s->walk == HprtScene::Walk::RbspKd || s->walk == HprtScene::Walk::BspPaperKd || s->walk == HprtScene::Walk::RbspKdInst;
+    return s->walk == HprtScene::Walk::RbspKd || s->walk == HprtScene::Walk::BspPaperKd || s->walk == HprtScene::Walk::RbspKdInst ||
+           s->walk == HprtScene::Walk::BspPaperKdInst;
 }
 // Every trace of a scene: the walk of the attached tree (AttachTree below), else the BVH walks (LaunchTrace)
 static void Trace(HprtScene *s, hipStream_t st, bool anyHit, bool count, const uint32_t *queue, const uint32_t *countPtr, uint32_t countImm,
@@ -318,6 +319,11 @@ static void Trace(HprtScene *s, hipStream_t st, bool anyHit, bool count, const u
     case HprtScene::Walk::RbspKdInst:
         LaunchRbspInstTrace(st, s->dev, s->rbspinst, s->walk == HprtScene::Walk::RbspKdInst, anyHit, count, queue, countPtr, countImm, gridItems, rays, hits, occ,
                             counters, workCounter, rayStats);
+        break;
+    case HprtScene::Walk::BspPaperInst:
+    case HprtScene::Walk::BspPaperKdInst:
+        LaunchBspPaperInstTrace(st, s->dev, s->bsppaperinst, s->walk == HprtScene::Walk::BspPaperKdInst, anyHit, count, queue, countPtr, countImm, gridItems, rays,
+                                hits, occ, counters, workCounter, rayStats);
         break;
     case HprtScene::Walk::Bvh: LaunchTrace(st, s->dev, anyHit, count, queue, countPtr, countImm, gridItems, rays, hits, occ, counters, workCounter, rayStats); break;
     }
@@ -597,10 +603,16 @@ extern "C++" template <class Tree> struct TwoLevelView {
     uint32_t off, mask, leafTag;                                // the node layout: flag bits, their mask, a leaf's tag
     uint32_t todoMax;                                           // the entries the walk's one todo list holds
     std::function<std::string(const Tree &)> objectCheck;       // optional: what else is wrong with an object's tree ("": nothing)
+    // optional: a tree's per-node split axes, 3 floats per node (bsppaper, bsppaperkd: BspPaperTree::axes).  When present the
+    // attach uploads one float4 {x, y, z, 0} per node of the shared node array into HprtScene::treeAxes, in the array's order
+    std::function<const std::vector<float> &(const Tree &)> axes;
 };
 // The top-level tree and every object's tree go through AttachTree's steps — the structural check, the todo-list rule (here over
 // both levels), AppendTree, UploadTree, FillTree — into ONE node array and ONE primitiveIndices array with one DevInstEntry per
 // instance (device/two_level.h); d: the walk's descriptor (DevKdInst, DevRbspInst), of which the shared fields are filled.  A
+// view with axes concatenates them as it concatenates the nodes — the top-level tree's first, then each object's, and a zero entry
+// of its own for the one-primitive leaf that stands for a tree-less object, so that the array has exactly as many entries as the
+// node array and a 16-byte fetch beside ANY node's word, that leaf's included (it may be the array's last), stays inside it.  A
 // refusal leaves the attached walk in place, a failed upload the BVH; on success the scene still walks its BVH and the caller,
 // having filled the descriptor's own fields, sets its walk.
 extern "C++" template <class Tree, class Dev> static int AttachTwoLevel(HprtScene *s, const TwoLevelView<Tree> &v, Dev &d) {
@@ -612,6 +624,7 @@ extern "C++" template <class Tree, class Dev> static int AttachTwoLevel(HprtScen
                                         " instances, the scene " + std::to_string(nObjects) + " and " + std::to_string(s->instanceObject.size()) + " (or they name other objects)");
     if (t.top.nPrims != s->topOrder.size())
         return SetError(HPRT_E_INVALID, "the top-level " + what + " holds " + std::to_string(t.top.nPrims) + " primitives, the scene " + std::to_string(s->topOrder.size()));
+    if (v.axes && v.axes(t.top).size() != 3 * t.top.nodes.size()) return SetError(HPRT_E_INVALID, "the top-level " + what + " has not one split axis per node");
     uint32_t topDepth = 0, objectDepth = 0;
     uint64_t nNodes = t.top.nodes.size(), nIdx = t.top.primIndices.size();
     const char *bad = v.check(t.top, &topDepth);
@@ -621,6 +634,7 @@ extern "C++" template <class Tree, class Dev> static int AttachTwoLevel(HprtScen
         if (k.nPrims != s->objectOrder[o].size())
             return SetError(HPRT_E_INVALID, "the " + what + " of object " + std::to_string(o) + " holds " + std::to_string(k.nPrims) + " primitives, the scene's object " + std::to_string(s->objectOrder[o].size()));
         if ((k.nPrims > 1) != !k.nodes.empty()) return SetError(HPRT_E_INVALID, "object " + std::to_string(o) + ": exactly the objects of more than one primitive have a tree");
+        if (v.axes && v.axes(k).size() != 3 * k.nodes.size()) return SetError(HPRT_E_INVALID, "object " + std::to_string(o) + ": not one split axis per node");
         const std::string wrong = v.objectCheck ? v.objectCheck(k) : std::string();
         if (!wrong.empty()) return SetError(HPRT_E_INVALID, "object " + std::to_string(o) + ": " + wrong);
         nNodes += k.nodes.empty() ? 1u : k.nodes.size(); nIdx += k.primIndices.size();
@@ -637,7 +651,13 @@ extern "C++" template <class Tree, class Dev> static int AttachTwoLevel(HprtScen
         return SetError(HPRT_E_UNSUPPORTED, "two-level " + what + ": more nodes over all trees than aboveChild can name");
     std::vector<uint2> nodes; std::vector<uint32_t> prims;
     nodes.reserve((size_t)nNodes); prims.reserve((size_t)nIdx);
+    std::vector<float4> axes;
+    if (v.axes) axes.reserve((size_t)nNodes);
     auto append = [&](const Tree &k, const std::vector<uint32_t> &order, uint32_t primBase) {
+        if (v.axes) {
+            const std::vector<float> &a = v.axes(k);
+            for (size_t n = 0; n < k.nodes.size(); ++n) axes.push_back(make_float4(a[3 * n], a[3 * n + 1], a[3 * n + 2], 0.f));
+        }
         return AppendTree(k.nodes, k.primIndices, InvertOrder(order, primBase), v.off, v.mask, v.leafTag, &nodes, &prims);
     };
     append(t.top, s->topOrder, 0u);
@@ -648,8 +668,10 @@ extern "C++" template <class Tree, class Dev> static int AttachTwoLevel(HprtScen
         else {      // the lone primitive (or nothing: no instance names an empty object) as a one-primitive leaf
             objectRoot[o] = (uint32_t)nodes.size();
             nodes.push_back(make_uint2(s->objectPrimBase[o], v.leafTag | ((k.nPrims ? 1u : 0u) << v.off)));
+            if (v.axes) axes.push_back(make_float4(0.f, 0.f, 0.f, 0.f));
         }
     }
+    if (v.axes && axes.size() != nodes.size()) return SetError(HPRT_E_INVALID, "two-level " + what + ": " + std::to_string(axes.size()) + " split axes for " + std::to_string(nodes.size()) + " nodes");
     std::vector<DevInstEntry> entries(t.instanceObject.size());
     for (size_t i = 0; i < entries.size(); ++i) {
         const size_t o = (size_t)t.instanceObject[i];
@@ -661,6 +683,7 @@ extern "C++" template <class Tree, class Dev> static int AttachTwoLevel(HprtScen
     }
     if (int rc = UploadTree(s, nodes, prims)) return rc;
     HIP_TRY(upload(s->instEntries, entries));
+    if (v.axes) HIP_TRY(upload(s->treeAxes, axes));
     d = Dev{};
     FillTree(d, s, nodes.size(), prims.size(), t.top.bounds, topDepth + objectDepth + 1u);
     d.entries = s->instEntries.as<DevInstEntry>(); d.nEntries = (uint32_t)entries.size();
@@ -698,6 +721,34 @@ int hprt_scene_attach_rbspinst(HprtScene *s, const HprtRbspInst *t) try {
     for (uint32_t k = 0; k < 3 * M; ++k) d.dirs[k] = t->top.directions[k];
     d.kdCounters = t->kdAware ? s->kdShare.as<unsigned long long>() : nullptr;
     s->walk = t->kdAware ? HprtScene::Walk::RbspKdInst : HprtScene::Walk::RbspInst;
+    return HPRT_OK;
+} catch (...) { return hprt::HandleException(); }
+
+// Two-level general BSP trees (under Accelerator "bsppaper" / "bsppaperkd"; device/bsppaperinst_walk.h): BSPNode's layout (one flag
+// bit, leaves tagged 1) or, kd-aware, BSPKdNode's (three flag bits, leaves tagged 3) for every tree, one split axis per node of the
+// shared array in treeAxes and, for kd-aware trees, the bsppaperkd walk's kd counter pair.
+int hprt_scene_attach_bsppaperinst(HprtScene *s, const HprtBspPaperInst *t) try {
+    if (!s || !t) return SetError(HPRT_E_INVALID, "hprt_scene_attach_bsppaperinst: null argument");
+    if (!s->instanced)
+        return SetError(HPRT_E_UNSUPPORTED, "hprt_scene_attach_bsppaperinst: the scene has no object instances; attach its tree with hprt_scene_attach_bsppaper / hprt_scene_attach_bsppaperkd");
+    HIP_TRY(hipSetDevice(s->device));
+    SceneCall call(s, nullptr);
+    const bool kd = t->kdAware;
+    auto sameLayout = [kd](const BspPaperTree &b) {
+        return b.kdAware == kd ? std::string() : std::string(b.kdAware ? "its tree holds BSPKdNode's flags, the handle is not kd-aware" : "its tree holds BSPNode's flags, the handle is kd-aware");
+    };
+    if (t->top.kdAware != kd) return SetError(HPRT_E_INVALID, "the top-level tree's node layout is not the handle's");
+    const TwoLevelView<BspPaperTree> view{kd ? "bsppaperkd tree" : "bsppaper tree", *t, kd ? CheckBspPaperKdTree : CheckBspPaperTree,
+                                          kd ? (uint32_t)BSPPAPERKD_OFF : (uint32_t)BSPPAPER_OFF, kd ? (uint32_t)BSPPAPERKD_MASK : (uint32_t)BSPPAPER_MASK,
+                                          kd ? (uint32_t)BSPPAPERKD_LEAF : 1u, kd ? (uint32_t)BSPPAPERKD_TODO_MAX : (uint32_t)BSPPAPER_TODO_MAX, sameLayout,
+                                          [](const BspPaperTree &b) -> const std::vector<float> & { return b.axes; }};
+    DevBspPaperInst &d = s->bsppaperinst;
+    if (int rc = AttachTwoLevel(s, view, d)) return rc;
+    if (kd)
+        if (int rc = ResetKdShare(s)) return rc;
+    d.axes = s->treeAxes.as<float4>();
+    d.kdCounters = kd ? s->kdShare.as<unsigned long long>() : nullptr;
+    s->walk = kd ? HprtScene::Walk::BspPaperKdInst : HprtScene::Walk::BspPaperInst;
     return HPRT_OK;
 } catch (...) { return hprt::HandleException(); }
 
@@ -1286,7 +1337,7 @@ int hprt_pixel_stats_read(HprtScene *s, uint64_t *out7, size_t n_pixels) try {
 int hprt_pixel_kd_stats_read(HprtScene *s, uint64_t *out2, size_t n_pixels) try {
     if (!s || !out2) return SetError(HPRT_E_INVALID, "hprt_pixel_kd_stats_read: null argument");
     SceneCall call(s, nullptr);
-    if (!s->pixelKdValid && s->walk == HprtScene::Walk::RbspInst && s->pixelStatsValid) {      // plain two-level RBSP trees: no node is a kd node
+    if (!s->pixelKdValid && (s->walk == HprtScene::Walk::RbspInst || s->walk == HprtScene::Walk::BspPaperInst) && s->pixelStatsValid) {      // plain two-level RBSP / general BSP trees: no node is a kd node
         if (n_pixels != s->filmPixels) return SetError(HPRT_E_INVALID, "hprt_pixel_kd_stats_read: pixel count differs from the last render's film");
         memset(out2, 0, 2 * n_pixels * sizeof(uint64_t));
         return HPRT_OK;

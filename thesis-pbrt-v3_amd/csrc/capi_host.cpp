@@ -312,6 +312,19 @@ int RbspFromArrays(const char *fn, uint32_t M, size_t nNodes, const uint32_t *no
     *out = t.release();
     return HPRT_OK;
 }
+// axisNodes / planeNodes of a hand-made general BSP tree (one axis per node), which has no sweep: its axis nodes are the kd nodes, or
+// those along a coordinate axis
+void CountHandMadeInterior(BspPaperTree *b) {
+    const uint32_t mask = b->kdAware ? (uint32_t)BSPPAPERKD_MASK : (uint32_t)BSPPAPER_MASK, leafTag = b->kdAware ? (uint32_t)BSPPAPERKD_LEAF : 1u;
+    b->axisNodes = b->planeNodes = 0;
+    for (size_t k = 0; k < b->nodes.size(); ++k) {
+        const uint32_t kind = b->nodes[k].b & mask;
+        if (kind == leafTag) continue;
+        const float *a = &b->axes[3 * k];
+        const bool axisNode = b->kdAware ? kind < BSPPAPERKD_LEAF : (a[0] != 0) + (a[1] != 0) + (a[2] != 0) == 1;
+        ++(axisNode ? b->axisNodes : b->planeNodes);
+    }
+}
 // nodes20: 5 words per node, as BspPaperCopy writes them
 template <typename Handle>
 int BspPaperFromArrays(const char *fn, size_t nNodes, const uint32_t *nodes20, size_t nIdx, const uint32_t *idx, uint32_t nPrims, const float *bounds6,
@@ -332,13 +345,7 @@ int BspPaperFromArrays(const char *fn, size_t nNodes, const uint32_t *nodes20, s
     if (*bad) return SetError(HPRT_E_INVALID, std::string("malformed tree: ") + bad);
     b.maxDepth = b.depth;
     b.leaves = kdAware ? CountLeaves(b.nodes, BSPPAPERKD_MASK, BSPPAPERKD_LEAF) : CountLeaves(b.nodes, BSPPAPER_MASK, 1u);
-    for (size_t k = 0; k < nNodes; ++k) {       // a hand-made tree has no sweep: its axis nodes are the kd nodes, or those along a coordinate axis
-        const uint32_t kind = b.nodes[k].b & (kdAware ? (uint32_t)BSPPAPERKD_MASK : (uint32_t)BSPPAPER_MASK);
-        if (kind == (kdAware ? (uint32_t)BSPPAPERKD_LEAF : 1u)) continue;
-        const float *a = &b.axes[3 * k];
-        const bool axisNode = kdAware ? kind < BSPPAPERKD_LEAF : (a[0] != 0) + (a[1] != 0) + (a[2] != 0) == 1;
-        ++(axisNode ? b.axisNodes : b.planeNodes);
-    }
+    CountHandMadeInterior(&b);
     constexpr uint32_t todoMax = kdAware ? BSPPAPERKD_TODO_MAX : BSPPAPER_TODO_MAX;
     if (b.depth > todoMax)
         return SetError(HPRT_E_UNSUPPORTED, std::string(kdAware ? "bsppaperkd" : "bsppaper") + " tree of depth " + std::to_string(b.depth) +
@@ -347,8 +354,8 @@ int BspPaperFromArrays(const char *fn, size_t nNodes, const uint32_t *nodes20, s
     return HPRT_OK;
 }
 
-// ---- two-level trees (hprt_kdinst_* and hprt_rbspinst_* below; pbrtObjectInstance, core/api.cpp:1794-1819): Handle is HprtKdInst
-// or HprtRbspInst (HprtTwoLevel, hprt_internal.h), Tree its KdTree or RbspTree ----
+// ---- two-level trees (hprt_kdinst_*, hprt_rbspinst_* and hprt_bsppaperinst_* below; pbrtObjectInstance, core/api.cpp:1794-1819):
+// Handle is HprtKdInst, HprtRbspInst or HprtBspPaperInst (HprtTwoLevel, hprt_internal.h), Tree its KdTree, RbspTree or BspPaperTree ----
 // The walk keeps the top-level tree's todo entries, one saved top-level position and the object tree's entries in one list of
 // todoMax entries (device/kdinst_walk.hip, device/bspinst_walk.h); what: the tree's name in the message
 template <typename Tree>
@@ -363,6 +370,9 @@ int CheckTwoLevelDepth(const HprtTwoLevel<Tree> &t, const char *what, uint32_t t
 }
 int CheckTwoLevelDepth(const HprtKdInst &t) { return CheckTwoLevelDepth(t, "kd-tree", KD_TODO_MAX); }
 int CheckTwoLevelDepth(const HprtRbspInst &t) { return CheckTwoLevelDepth(t, "RBSP tree", RBSP_TODO_MAX); }
+int CheckTwoLevelDepth(const HprtBspPaperInst &t) {
+    return t.kdAware ? CheckTwoLevelDepth(t, "bsppaperkd tree", BSPPAPERKD_TODO_MAX) : CheckTwoLevelDepth(t, "bsppaper tree", BSPPAPER_TODO_MAX);
+}
 // The build of either handle: one tree per object of more than one primitive, over the object's primitives in object space, and the
 // top-level tree over the top-level items, an instance bounded by TransformedPrimitive::WorldBound.  buildTree(object, n, lo, hi,
 // &tree): the tree over the n primitives of one object or (object < 0) of the top level, returning what went wrong ("": nothing);
@@ -428,6 +438,42 @@ int BuildRbspInst(const char *fn, const HprtModel *m, const Params *params, Rbsp
                          },
                          out);
 }
+// hprt_bsppaperinst_build / hprt_bsppaperkdinst_build; p: the Accelerator line.  Every tree is BuildBspPaperTree over RbspPrimTriangles'
+// view of its primitives: an object's triangles by their object-space vertices, a sphere as isTri = 0.  On the top level an instance
+// is a TransformedPrimitive, which inherits Primitive::getBSPPaperPlanes (core/primitive.h:92-95: no planes) and
+// Primitive::getBounds (the 8 corners of its WorldBound): isTri = 0 again, so an instance contributes axis candidates only and is
+// classified under a plane exactly as the builder classifies every other non-triangle.
+template <typename Params>
+int BuildBspPaperInst(const char *fn, const HprtModel *m, const Params *params, BspPaperParams p, HprtBspPaperInst **out) {
+    constexpr bool kdAware = std::is_same<Params, HprtBspPaperKdParams>::value;
+    if (out) *out = nullptr;
+    if (!m || !out) return SetError(HPRT_E_INVALID, std::string(fn) + ": null argument");
+    const SceneModel &sc = m->sc;
+    if (sc.instances.empty())
+        return SetError(HPRT_E_UNSUPPORTED, std::string(fn) + ": the model has no object instances; build its tree with hprt_bsppaper_build / hprt_bsppaperkd_build");
+    p.kdAware = kdAware;
+    if (params) {
+        p.isectCost = params->isect_cost; p.travCost = params->trav_cost; p.emptyBonus = params->empty_bonus;
+        p.maxPrims = params->max_prims; p.maxDepth = params->max_depth; p.threads = params->threads;
+        if constexpr (kdAware) p.kdTravCost = params->kd_trav_cost;
+    }
+    std::unique_ptr<HprtBspPaperInst> t(new HprtBspPaperInst());
+    t->kdAware = kdAware;
+    t->top.kdAware = kdAware;
+    std::vector<float> tri9;
+    std::vector<uint8_t> isTri;
+    return BuildTwoLevel(sc, std::move(t),
+                         [&](int object, size_t n, const float *lo, const float *hi, BspPaperTree *b) {      // maxDepth -1 resolves per tree, from its n
+                             if (n > (kdAware ? 0x0fffffffull : 0x3fffffffull)) return std::string("more primitives than a node's flags can count");
+                             RbspPrimTriangles(sc, object, n, &tri9, &isTri);
+                             return BuildBspPaperTree(n, lo, hi, tri9.data(), isTri.data(), p, b);
+                         },
+                         [&](size_t n, const float *lo, const float *hi, BspPaperTree *b) {
+                             b->nPrims = (uint32_t)n; b->kdAware = kdAware;
+                             for (int a = 0; a < 3 && n; ++a) { b->bounds[a] = lo[a]; b->bounds[3 + a] = hi[a]; }
+                         },
+                         out);
+}
 // info[0..3] of one tree of a handle: an object without a tree has no leaves and no depth
 template <typename Tree>
 void TwoLevelTreeInfo(const Tree &t, uint32_t info[4]) {
@@ -477,14 +523,32 @@ const char *FinishHandMadeTree(const RbspTree &old, RbspTree *r) {
     r->leaves = CountLeaves(r->nodes, RbspBitMask(r->M), r->M);
     return CheckRbspTree(*r, &r->depth);
 }
+// a general BSP tree keeps its node layout; its axis / plane node counts are a hand-made tree's (CountHandMadeInterior)
+const char *FinishHandMadeTree(const BspPaperTree &old, BspPaperTree *b) {
+    b->nPrims = old.nPrims; b->kdAware = old.kdAware;
+    const uint32_t mask = b->kdAware ? (uint32_t)BSPPAPERKD_MASK : (uint32_t)BSPPAPER_MASK, leafTag = b->kdAware ? (uint32_t)BSPPAPERKD_LEAF : 1u;
+    b->leaves = CountLeaves(b->nodes, mask, leafTag);
+    CountHandMadeInterior(b);
+    return b->kdAware ? CheckBspPaperKdTree(*b, &b->depth) : CheckBspPaperTree(*b, &b->depth);
+}
+// The node words of a hand-made tree: 8 bytes per node, or (a general BSP tree) the 20 bytes BspPaperCopy writes, whose axes the
+// 8-byte form cannot carry
+void SetTreeNodes(KdTree *k, size_t nNodes, const uint32_t *nodes8) { k->nodes.resize(nNodes); memcpy(k->nodes.data(), nodes8, nNodes * sizeof(BspNode)); }
+void SetTreeNodes(RbspTree *r, size_t nNodes, const uint32_t *nodes8) { r->nodes.resize(nNodes); memcpy(r->nodes.data(), nodes8, nNodes * sizeof(BspNode)); }
+void SetTreeNodes(BspPaperTree *b, size_t nNodes, const uint32_t *nodes20) {
+    b->nodes.resize(nNodes); b->axes.resize(3 * nNodes);
+    for (size_t k = 0; k < nNodes; ++k) {
+        b->nodes[k] = BspNode{nodes20[5 * k], nodes20[5 * k + 1]};
+        memcpy(&b->axes[3 * k], &nodes20[5 * k + 2], 12);
+    }
+}
 template <typename Handle>
 int TwoLevelSetTree(const char *fn, Handle *t, int object, size_t nNodes, const uint32_t *nodes8, size_t nIdx, const uint32_t *idx, const float *bounds6) {
     if (!t || !nodes8 || !bounds6 || (nIdx && !idx) || object >= (int)t->objects.size()) return SetError(HPRT_E_INVALID, std::string(fn) + ": bad argument");
     auto &dst = object < 0 ? t->top : t->objects[object];
     if (object >= 0 && dst.nPrims < 2) return SetError(HPRT_E_INVALID, std::string(fn) + ": an object of one primitive has no tree");
     typename std::remove_reference<decltype(dst)>::type tree;
-    tree.nodes.resize(nNodes);
-    memcpy(tree.nodes.data(), nodes8, nNodes * sizeof(BspNode));
+    SetTreeNodes(&tree, nNodes, nodes8);
     tree.primIndices.assign(idx, idx + nIdx);
     memcpy(tree.bounds, bounds6, sizeof(tree.bounds));
     const char *bad = FinishHandMadeTree(dst, &tree);
@@ -898,6 +962,45 @@ int hprt_bsppaperkd_copy(const HprtBspPaperKd *t, void *nodes20, uint32_t *primI
     return BspPaperCopy(t->tree, nodes20, primIndices);
 } catch (...) { return hprt::HandleException(); }
 void hprt_bsppaperkd_destroy(HprtBspPaperKd *t) { delete t; }
+// ---- two-level general BSP trees (Accelerator "bsppaper" / "bsppaperkd" over object instances, pbrtObjectInstance,
+// core/api.cpp:1794-1819: MakeAccelerator for every object of more than one primitive and again in pbrtWorldEnd; helpers above) ----
+int hprt_bsppaperinst_build(const HprtModel *m, const HprtBspPaperParams *params, HprtBspPaperInst **out) try {
+    return BuildBspPaperInst("hprt_bsppaperinst_build", m, params, m ? m->sc.opt.bsppaper : BspPaperParams(), out);
+} catch (...) { return hprt::HandleException(); }
+int hprt_bsppaperkdinst_build(const HprtModel *m, const HprtBspPaperKdParams *params, HprtBspPaperInst **out) try {
+    return BuildBspPaperInst("hprt_bsppaperkdinst_build", m, params, m ? m->sc.opt.bsppaperkd : BspPaperParams(), out);
+} catch (...) { return hprt::HandleException(); }
+int hprt_bsppaperinst_info(const HprtBspPaperInst *t, uint32_t info[12]) try {
+    if (int rc = TwoLevelInfo("hprt_bsppaperinst_info", t, info)) return rc;
+    info[8] = t->kdAware ? 1u : 0u; info[9] = t->top.axisNodes; info[10] = t->top.planeNodes; info[11] = 0;
+    for (const BspPaperTree &o : t->objects) if (!o.nodes.empty()) { info[9] += o.axisNodes; info[10] += o.planeNodes; }
+    return HPRT_OK;
+} catch (...) { return hprt::HandleException(); }
+int hprt_bsppaperinst_object_info(const HprtBspPaperInst *t, uint32_t object, uint32_t info[4]) try {
+    return TwoLevelObjectInfo("hprt_bsppaperinst_object_info", t, object, info);
+} catch (...) { return hprt::HandleException(); }
+int hprt_bsppaperinst_copy(const HprtBspPaperInst *t, void *nodes20, uint32_t *primIndices) try {
+    if (!t) return SetError(HPRT_E_INVALID, "hprt_bsppaperinst_copy: null argument");
+    return BspPaperCopy(t->top, nodes20, primIndices);
+} catch (...) { return hprt::HandleException(); }
+int hprt_bsppaperinst_object_copy(const HprtBspPaperInst *t, uint32_t object, void *nodes20, uint32_t *primIndices) try {
+    const BspPaperTree *o = TwoLevelObject("hprt_bsppaperinst_object_copy", t, object);
+    if (!o) return HPRT_E_INVALID;
+    return BspPaperCopy(*o, nodes20, primIndices);
+} catch (...) { return hprt::HandleException(); }
+void hprt_bsppaperinst_destroy(HprtBspPaperInst *t) { delete t; }
+// Diagnostics hooks (not part of include/hprt.h; tests): the bounds of the top-level tree (object < 0) or of one object's tree, and
+// a tree made by hand in place of the built one — nodes20 / idx as hprt_bsppaperinst_copy writes them (5 words per node: the 8-byte
+// form cannot carry the axes), bounds6 pMin then pMax — so that trees with a known todo depth reach the walk.  The tree keeps its
+// primitive count and node layout and passes the structural check (CheckBspPaperTree / CheckBspPaperKdTree) and the two-level depth
+// rule a built handle passes (HPRT_E_INVALID, HPRT_E_UNSUPPORTED; the handle is unchanged when refused).
+__attribute__((visibility("default"))) int hprt_debug_bsppaperinst_bounds(const HprtBspPaperInst *t, int object, float bounds6[6]) try {
+    return TwoLevelBounds("hprt_debug_bsppaperinst_bounds", t, object, bounds6);
+} catch (...) { return hprt::HandleException(); }
+__attribute__((visibility("default"))) int hprt_debug_bsppaperinst_set_tree(HprtBspPaperInst *t, int object, size_t n_nodes, const uint32_t *nodes20, size_t n_idx,
+                                                                             const uint32_t *idx, const float *bounds6) try {
+    return TwoLevelSetTree("hprt_debug_bsppaperinst_set_tree", t, object, n_nodes, nodes20, n_idx, idx, bounds6);
+} catch (...) { return hprt::HandleException(); }
 // ---- node-based BSP trees (Accelerator "bsparbitrary", "bspcluster", "bsprandom" and their withkd / fastkd forms; helpers above):
 // no handles of their own — a tree over BSPNode is an HprtBspPaper, a tree over BSPKdNode an HprtBspPaperKd ----
 int hprt_bspnode_build(const HprtModel *m, const HprtBspNodeParams *params, HprtBspPaper **out) try {

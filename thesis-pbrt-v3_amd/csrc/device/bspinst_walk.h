@@ -2,12 +2,17 @@
 // TransformedPrimitive::Intersect / IntersectP (core/primitive.cpp:77-102) at every leaf primitive that is an object instance, and
 // the same walk over the instance's own tree with the transformed ray — what an instanced scene of one of the fork's BSP
 // accelerators is in the reference (pbrtObjectInstance, core/api.cpp:1794-1819).  All trees share one node array and one
-// primitiveIndices array.  The two-level RBSP walks (rbspinst_walk.hip) instantiate it; a walk passes its interior step in as
-// `Step`, with bsp_walk's contract:
+// primitiveIndices array.  The two-level RBSP walks (rbspinst_walk.hip) and the two-level general BSP walks
+// (bsppaperinst_walk.hip) instantiate it; a walk passes its interior step in as `Step`, with bsp_walk's contract:
 //   bool leaf(uint32_t flags), uint32_t high(uint32_t flags)   (aboveChild / nPrimitives),
 //   void plane(uint32_t flags, float split, vec3 ro, vec3 rd, vec3 invDir, float *tPlane, bool *belowFirst),
 // and with KD_SHARE `bool kd(uint32_t flags)` and `void kd_count_add(bool anyHit, uint32_t n)`.  The step keeps no per-ray state
 // and is given the ray of the level being walked, so both levels run the same instructions.
+// NODE_AXIS (the two-level general BSP walks) gives the step per-node data as bsp_walk's NODE_AXIS does: the step's
+// `float4 axis(uint32_t node)` — one entry per node of the SHARED node array, so an object's node finds its object-space axis at
+// its own index — is passed to `void plane(float4 axis, uint32_t flags, ...)` in front of the other arguments; requested together
+// with the node's 8-byte word (1), or only for the interior nodes for which the step's `bool has_axis(uint32_t flags)` holds (3;
+// `plane` gets zeros elsewhere).  0: the step has no per-node data (the RBSP walks), and nothing of this is compiled.
 //
 // Schedule and todo list are k_kdinstwalk's (kdinst_walk.hip).  One ray per lane; persistent waves draw 64 rays at a time from
 // the queue head.  ONE list for both levels: below, the top-level walk's entries {node, tPlane} as in bsp_walk.  Entering an
@@ -33,7 +38,7 @@ namespace hprt {
 // scene has spheres.  nodes / primIdx: the attached trees (one-primitive leaves and primIdx hold ORDERED indices over all
 // aggregates); entries: two float4 per instance, {lo, root} {hi, prim} (DevInstEntry, two_level.h); lo / hi: the top-level tree's bounds.
 // stackMem: the kernel's [LDS][BLOCK] LDS todo entries.
-template <bool ANY_HIT, bool COUNT, bool QUAD, int LDS, int BLOCK, class Step, bool KD_SHARE = false>
+template <bool ANY_HIT, bool COUNT, bool QUAD, int LDS, int BLOCK, class Step, bool KD_SHARE = false, int NODE_AXIS = 0>
 __device__ __forceinline__ void bspinst_walk(const DevScene &sc, const uint2 *nodes, const uint32_t *primIdx, const float4 *entries, const float *lo,
                                              const float *hi, Step &step, const uint32_t *queue, const uint32_t *countPtr, uint32_t countImm,
                                              const RayStream &rays, const HitStream &hits, uint8_t *occ, DevCounters *counters, uint4 *rayStats,
@@ -108,12 +113,21 @@ __device__ __forceinline__ void bspinst_walk(const DevScene &sc, const uint2 *no
                     }
                     if (COUNT) ++cnt.fetched;
                 }
-                const uint2 nd = nodes[node];
+                uint2 nd = nodes[node];
+                [[maybe_unused]] float4 axis;
+                if constexpr (NODE_AXIS == 1) {
+                    axis = step.axis(node);
+                    // an empty asm that takes the node word and the whole entry: both requests are issued before one wait, the
+                    // entry as one 16-byte load (bsp_walk.h)
+                    asm volatile("" : "+v"(nd.x), "+v"(nd.y), "+v"(axis.x), "+v"(axis.y), "+v"(axis.z), "+v"(axis.w));
+                }
                 if (!step.leaf(nd.y)) {
                     if (COUNT) ++cnt.entered;
                     if constexpr (COUNT && KD_SHARE) kdCnt += step.kd(nd.y) ? 1u : 0u;
                     float tPlane; bool belowFirst;
-                    step.plane(nd.y, __uint_as_float(nd.x), ro, rd, invDir, &tPlane, &belowFirst);
+                    if constexpr (NODE_AXIS == 3) { axis = make_float4(0.f, 0.f, 0.f, 0.f); if (step.has_axis(nd.y)) axis = step.axis(node); }
+                    if constexpr (NODE_AXIS != 0) step.plane(axis, nd.y, __uint_as_float(nd.x), ro, rd, invDir, &tPlane, &belowFirst);
+                    else step.plane(nd.y, __uint_as_float(nd.x), ro, rd, invDir, &tPlane, &belowFirst);
                     const uint32_t above = step.high(nd.y);
                     const uint32_t first = belowFirst ? node + 1u : above, second = belowFirst ? above : node + 1u;
                     if (tPlane > tMax || tPlane <= 0) node = first;

@@ -15,6 +15,7 @@
 #include "device/bsppaperkd_walk.h"
 #include "device/kdinst_walk.h"
 #include "device/rbspinst_walk.h"
+#include "device/bsppaperinst_walk.h"
 #include "hprt_internal.h"
 
 #define HIP_TRY(expr)                                                                                   \
@@ -104,7 +105,7 @@ struct HprtScene {
     // counter pair (DevRbspKd / DevBspPaperKd::kdCounters); pixelKdLocal / pixelKdFilm: their per-pixel kd share of HPRT_RENDER_PIXEL_STATS.
     // topOrder keeps the top-level prim_order (ordered -> creation number) to map a tree's creation-order primitives; instanced:
     // no tree walk
-    enum class Walk { Bvh, Kd, Rbsp, RbspKd, BspPaper, BspPaperKd, KdInst, RbspInst, RbspKdInst } walk = Walk::Bvh;
+    enum class Walk { Bvh, Kd, Rbsp, RbspKd, BspPaper, BspPaperKd, KdInst, RbspInst, RbspKdInst, BspPaperInst, BspPaperKdInst } walk = Walk::Bvh;
     hprt::DevBuf treeNodes, treePrims, treeAxes; hprt::DevKd kd{}; hprt::DevRbsp rbsp{}; hprt::DevBspPaper bsppaper{};
     hprt::DevBuf kdShare, pixelKdLocal, pixelKdFilm; bool pixelKdValid = false;
     std::vector<uint32_t> topOrder; bool instanced = false;
@@ -113,9 +114,11 @@ struct HprtScene {
     // primitiveIndices of the top-level tree followed by every object tree's, instEntries one DevInstEntry per instance
     // (device/two_level.h).  kdinst: two-level kd-trees (hprt_scene_attach_kdinst, Walk::KdInst); rbspinst: two-level RBSP trees
     // (hprt_scene_attach_rbspinst; Walk::RbspInst, or Walk::RbspKdInst for kd-aware trees, which count their kd share in kdShare as
-    // the rbspkd walk does).  objectOrder / objectPrimBase map an object tree's creation-order primitives as topOrder maps the top
+    // the rbspkd walk does); bsppaperinst: two-level general BSP trees (hprt_scene_attach_bsppaperinst; Walk::BspPaperInst, or
+    // Walk::BspPaperKdInst for kd-aware trees with their kd share in kdShare), whose per-node axes — one per node of treeNodes — sit
+    // in treeAxes.  objectOrder / objectPrimBase map an object tree's creation-order primitives as topOrder maps the top
     // level's; instanceObject: each instance's object definition
-    hprt::DevBuf instEntries; hprt::DevKdInst kdinst{}; hprt::DevRbspInst rbspinst{};
+    hprt::DevBuf instEntries; hprt::DevKdInst kdinst{}; hprt::DevRbspInst rbspinst{}; hprt::DevBspPaperInst bsppaperinst{};
     std::vector<std::vector<uint32_t>> objectOrder; std::vector<uint32_t> objectPrimBase; std::vector<int32_t> instanceObject;
     ~HprtScene() { if (hostCounts) (void)hipHostFree(hostCounts); if (lastUse) (void)hipEventDestroy(lastUse); }
 };

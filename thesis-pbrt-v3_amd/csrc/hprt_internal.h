@@ -18,7 +18,7 @@ struct HprtBvh {
 struct HprtKdTree { hprt::KdTree tree; };
 // Two-level trees (pbrtObjectInstance, core/api.cpp:1794-1819): the top-level tree over the top-level items, and per object
 // definition its own tree — none (no nodes) for an object of one primitive, which is wrapped as it is (:1798).  Tree: KdTree
-// (HprtKdInst), RbspTree (HprtRbspInst); what a further tree type has to supply: DESIGN.md §8k
+// (HprtKdInst), RbspTree (HprtRbspInst), BspPaperTree (HprtBspPaperInst); what a further tree type has to supply: DESIGN.md §8k
 template <typename Tree> struct HprtTwoLevel {
     Tree top;
     std::vector<Tree> objects;                // objects[o].nPrims: the object's primitives, tree (nodes) or not
@@ -34,6 +34,11 @@ struct HprtRbspInst : HprtTwoLevel<hprt::RbspTree> {
 };
 struct HprtBspPaper { hprt::BspPaperTree tree; };
 struct HprtBspPaperKd { hprt::BspPaperTree tree; };     // built with BspPaperParams::kdAware
+// Two-level general BSP trees (Accelerator "bsppaper" / "bsppaperkd"): one handle type for both cost models and node layouts; every
+// tree is built with the same parameters, so all carry BSPNode's flags or all BSPKdNode's.
+struct HprtBspPaperInst : HprtTwoLevel<hprt::BspPaperTree> {
+    bool kdAware = false;                     // built by hprt_bsppaperkdinst_build: BSPKdNode's flags, walked with the kd form at kd nodes
+};
 
 namespace hprt {
 extern thread_local std::string g_lastError;
