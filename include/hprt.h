@@ -382,6 +382,43 @@ int hprt_bsppaperkd_copy(const HprtBspPaperKd *t, void *nodes20, uint32_t *prim_
 void hprt_bsppaperkd_destroy(HprtBspPaperKd *t);
 
 /* ------------------------------------------------------------------------ */
+/* Device-assisted builds of the two general BSP trees (opt-in).  They      */
+/* stand in for the same BSPPaper::buildTree / BSPPaperKd::buildTree and    */
+/* return the same bytes as hprt_bsppaper_build / hprt_bsppaperkd_build:    */
+/* the axis sweep and its sorts, the BVH over a node's primitives, the      */
+/* first-minimum scan, the leaf tests, the winner's cut and the             */
+/* classification stay on the host; what moves to the GPU is the costing of */
+/* a node's split candidates (the extent test of a triangle's plane,        */
+/* KDOPMeshWithDirections::cut + KDOPSurfaceArea of                         */
+/* accelerators/kDOPMesh.h, BVHAccel::getAmountToLeftAndRight of            */
+/* accelerators/bvh.cpp:439-470 and the cost formulas of                    */
+/* bspPaper.cpp / bspPaperKd.cpp), one candidate per lane, for nodes with   */
+/* at least min_candidates candidates.  A candidate that outgrows one of    */
+/* the kernel's fixed capacities is costed again on the host; a node whose  */
+/* own mesh or direction list does is costed on the host whole.  Same       */
+/* handles: info, copy, attach and the walks are unchanged.  Refusals are   */
+/* those of the host entries; without a HIP device: HPRT_E_NO_DEVICE and    */
+/* *out stays NULL.  Two-level trees are not offered.                       */
+/* ------------------------------------------------------------------------ */
+typedef struct HprtBspBuildDeviceOpts {
+    int device;               /* HIP device ordinal */
+    uint32_t min_candidates;  /* nodes with fewer candidates are costed on the host; 0 = default */
+    uint32_t max_edges;       /* edges per half-mesh on the device; 0 = default (the compiled capacity); may only lower it */
+    uint32_t max_faces;       /* faces of a child's k-DOP that own an edge, plus the cut's two; 0 = default; may only lower it */
+    uint32_t max_face_edges;  /* entries of one face's edge list; 0 = default; may only lower it */
+    uint32_t max_stack;       /* entries of the stack that walks the node's BVH; 0 = default; may only lower it */
+} HprtBspBuildDeviceOpts;
+/* opts NULL: device 0 and the defaults; stats may be NULL */
+int hprt_bsppaper_build_device(const HprtModel *m, const HprtBspPaperParams *params, const HprtBspBuildDeviceOpts *opts, HprtBuildDeviceStats *stats,
+                               HprtBspPaper **out);
+int hprt_bsppaper_build_from_triangles_device(size_t n_tris, const float *p9, const HprtBspPaperParams *params, const HprtBspBuildDeviceOpts *opts,
+                                              HprtBuildDeviceStats *stats, HprtBspPaper **out);
+int hprt_bsppaperkd_build_device(const HprtModel *m, const HprtBspPaperKdParams *params, const HprtBspBuildDeviceOpts *opts, HprtBuildDeviceStats *stats,
+                                 HprtBspPaperKd **out);
+int hprt_bsppaperkd_build_from_triangles_device(size_t n_tris, const float *p9, const HprtBspPaperKdParams *params, const HprtBspBuildDeviceOpts *opts,
+                                                HprtBuildDeviceStats *stats, HprtBspPaperKd **out);
+
+/* ------------------------------------------------------------------------ */
 /* Two-level general BSP trees (Accelerator "bsppaper" / "bsppaperkd" on a  */
 /* model with object instances).  Stands in for pbrtObjectInstance          */
 /* (core/api.cpp:1794-1819): MakeAccelerator(renderOptions->AcceleratorName,*/

@@ -143,6 +143,24 @@ class BuildDeviceStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class BspBuildDeviceOpts(C.Structure):
+    """HprtBspBuildDeviceOpts: the device-assisted BspPaper / BspPaperKd build (0 = default)."""
+    _fields_ = [("device", C.c_int), ("min_candidates", C.c_uint32), ("max_edges", C.c_uint32), ("max_faces", C.c_uint32),
+                ("max_face_edges", C.c_uint32), ("max_stack", C.c_uint32)]
+
+
+def _build_bsp_tree(prefix, how, head, prm, device, min_candidates, caps):
+    """hprt_<prefix>_<how> or, with device not None, hprt_<prefix>_<how>_device: (handle, build stats dict or None); caps:
+    max_edges, max_faces, max_face_edges, max_stack"""
+    h = C.c_void_p()
+    if device is None:
+        _check(getattr(lib, "hprt_%s_%s" % (prefix, how))(*head, prm, C.byref(h)))
+        return h, None
+    opts, st = BspBuildDeviceOpts(int(device), min_candidates, *caps), BuildDeviceStats()
+    _check(getattr(lib, "hprt_%s_%s_device" % (prefix, how))(*head, prm, C.byref(opts), C.byref(st), C.byref(h)))
+    return h, st.as_dict()
+
+
 def _build_tree(prefix, how, head, prm, device, min_candidates, max_edges):
     """hprt_<prefix>_<how> or, with device not None, hprt_<prefix>_<how>_device: (handle, build stats dict or None)"""
     h = C.c_void_p()
@@ -340,6 +358,10 @@ def _load():
         "hprt_rbsp_build_from_triangles_device": (C.c_int, [sz, vp, vp, vp, vp, P(vp)]),
         "hprt_rbspkd_build_device": (C.c_int, [vp, vp, vp, vp, P(vp)]),
         "hprt_rbspkd_build_from_triangles_device": (C.c_int, [sz, vp, vp, vp, vp, P(vp)]),
+        "hprt_bsppaper_build_device": (C.c_int, [vp, vp, vp, vp, P(vp)]),
+        "hprt_bsppaper_build_from_triangles_device": (C.c_int, [sz, vp, vp, vp, vp, P(vp)]),
+        "hprt_bsppaperkd_build_device": (C.c_int, [vp, vp, vp, vp, P(vp)]),
+        "hprt_bsppaperkd_build_from_triangles_device": (C.c_int, [sz, vp, vp, vp, vp, P(vp)]),
         "hprt_bsppaper_build": (C.c_int, [vp, vp, P(vp)]),
         "hprt_bsppaper_build_from_triangles": (C.c_int, [sz, vp, vp, P(vp)]),
         "hprt_bsppaper_info": (C.c_int, [vp, P(u32)]),
@@ -696,21 +718,27 @@ class BspPaper(_Tree):
     _prefix = "bsppaper"
     _info_keys = ("nodes", "leaves", "depth", "prim_refs", "axis_interior", "plane_interior")
 
-    def __init__(self, model=None, handle=None, isect_cost=None, trav_cost=5, empty_bonus=0.0, max_prims=1, max_depth=-1, threads=0):
+    def __init__(self, model=None, handle=None, isect_cost=None, trav_cost=5, empty_bonus=0.0, max_prims=1, max_depth=-1, threads=0, device=None, min_candidates=0, max_edges=0, max_faces=0,
+                 max_face_edges=0, max_stack=0, build_stats=None):
+        """device: None builds on the host; a HIP device ordinal costs the split candidates of nodes with at least min_candidates
+        candidates on that GPU (the same tree, byte for byte) and leaves HprtBuildDeviceStats as a dict in self.build_stats.
+        max_edges / max_faces / max_face_edges / max_stack: 0, or a value that lowers the kernel's compiled capacity."""
+        self.build_stats = build_stats
         if handle is None:
-            handle = C.c_void_p()
             prm = None if isect_cost is None else C.byref(BspPaperParams(isect_cost, trav_cost, empty_bonus, max_prims, max_depth, threads))
-            _check(lib.hprt_bsppaper_build(model._h, prm, C.byref(handle)))
+            handle, self.build_stats = _build_bsp_tree("bsppaper", "build", (model._h,), prm, device, min_candidates,
+                                                       (max_edges, max_faces, max_face_edges, max_stack))
         self._h = handle
 
     @staticmethod
-    def from_triangles(p9, isect_cost=80, trav_cost=5, empty_bonus=0.0, max_prims=1, max_depth=-1, threads=0):
-        """p9: [n, 9] (or [n, 3, 3]) float32 world-space triangle vertices in creation order."""
+    def from_triangles(p9, isect_cost=80, trav_cost=5, empty_bonus=0.0, max_prims=1, max_depth=-1, threads=0, device=None, min_candidates=0,
+                       max_edges=0, max_faces=0, max_face_edges=0, max_stack=0):
+        """p9: [n, 9] (or [n, 3, 3]) float32 world-space triangle vertices in creation order.  device ...: as in the constructor."""
         p9 = np.ascontiguousarray(p9, np.float32).reshape(-1, 9)
-        h = C.c_void_p()
         prm = BspPaperParams(isect_cost, trav_cost, empty_bonus, max_prims, max_depth, threads)
-        _check(lib.hprt_bsppaper_build_from_triangles(p9.shape[0], _ptr(p9), C.byref(prm), C.byref(h)))
-        return BspPaper(handle=h)
+        h, st = _build_bsp_tree("bsppaper", "build_from_triangles", (p9.shape[0], _ptr(p9)), C.byref(prm), device, min_candidates,
+                                (max_edges, max_faces, max_face_edges, max_stack))
+        return BspPaper(handle=h, build_stats=st)
 
     @staticmethod
     def from_arrays(nodes, prim_indices, n_prims, bounds):
@@ -740,21 +768,27 @@ class BspPaperKd(_Tree):
     _prefix = "bsppaperkd"
     _info_keys = ("nodes", "leaves", "depth", "prim_refs", "kd_interior", "plane_interior")
 
-    def __init__(self, model=None, handle=None, isect_cost=None, trav_cost=5, kd_trav_cost=1, empty_bonus=0.0, max_prims=1, max_depth=-1, threads=0):
+    def __init__(self, model=None, handle=None, isect_cost=None, trav_cost=5, kd_trav_cost=1, empty_bonus=0.0, max_prims=1, max_depth=-1, threads=0, device=None, min_candidates=0, max_edges=0, max_faces=0,
+                 max_face_edges=0, max_stack=0, build_stats=None):
+        """device: None builds on the host; a HIP device ordinal costs the split candidates of nodes with at least min_candidates
+        candidates on that GPU (the same tree, byte for byte) and leaves HprtBuildDeviceStats as a dict in self.build_stats.
+        max_edges / max_faces / max_face_edges / max_stack: 0, or a value that lowers the kernel's compiled capacity."""
+        self.build_stats = build_stats
         if handle is None:
-            handle = C.c_void_p()
             prm = None if isect_cost is None else C.byref(BspPaperKdParams(isect_cost, trav_cost, kd_trav_cost, empty_bonus, max_prims, max_depth, threads))
-            _check(lib.hprt_bsppaperkd_build(model._h, prm, C.byref(handle)))
+            handle, self.build_stats = _build_bsp_tree("bsppaperkd", "build", (model._h,), prm, device, min_candidates,
+                                                       (max_edges, max_faces, max_face_edges, max_stack))
         self._h = handle
 
     @staticmethod
-    def from_triangles(p9, isect_cost=80, trav_cost=5, kd_trav_cost=1, empty_bonus=0.0, max_prims=1, max_depth=-1, threads=0):
-        """p9: [n, 9] (or [n, 3, 3]) float32 world-space triangle vertices in creation order."""
+    def from_triangles(p9, isect_cost=80, trav_cost=5, kd_trav_cost=1, empty_bonus=0.0, max_prims=1, max_depth=-1, threads=0, device=None,
+                       min_candidates=0, max_edges=0, max_faces=0, max_face_edges=0, max_stack=0):
+        """p9: [n, 9] (or [n, 3, 3]) float32 world-space triangle vertices in creation order.  device ...: as in the constructor."""
         p9 = np.ascontiguousarray(p9, np.float32).reshape(-1, 9)
-        h = C.c_void_p()
         prm = BspPaperKdParams(isect_cost, trav_cost, kd_trav_cost, empty_bonus, max_prims, max_depth, threads)
-        _check(lib.hprt_bsppaperkd_build_from_triangles(p9.shape[0], _ptr(p9), C.byref(prm), C.byref(h)))
-        return BspPaperKd(handle=h)
+        h, st = _build_bsp_tree("bsppaperkd", "build_from_triangles", (p9.shape[0], _ptr(p9)), C.byref(prm), device, min_candidates,
+                                (max_edges, max_faces, max_face_edges, max_stack))
+        return BspPaperKd(handle=h, build_stats=st)
 
     @staticmethod
     def from_arrays(nodes, prim_indices, n_prims, bounds):

@@ -6,12 +6,15 @@
 // The one liberty, as in the RBSP builder: the candidates of a node may be costed on several threads.  Each candidate's cost is a
 // pure function of the node's k-DOP, its BVH and the candidate, and the reduction keeps the first minimum in the reference's scan
 // order (axis candidates by axis and edge, then plane candidates by primitive and plane), so the tree does not depend on the
-// thread count.  The winner's two halves are then cut and measured once more, exactly as the scan left them.
+// thread count.  The winner's two halves are then cut and measured once more, exactly as the scan left them.  For the same reason
+// a node's candidates may be costed elsewhere altogether (BspPaperParams::costFn: the device-assisted build, bsp_cost.h), as long
+// as every cost, fixed cost and count carries the bits CostOne below would give; what the hook flags is costed here again.
 //
 // BspPaperParams::kdAware selects BSPPaperKd::buildTree (accelerators/bspPaperKd.cpp:34-339) over BSPKdNode (BSPKd.h:11-174): the
 // same scan with the kd-aware costs, a second minimum over the plane candidates alone, and the 3-bit node flags.
 #include "bsppaper_builder.h"
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstring>
 #include <functional>
@@ -114,8 +117,73 @@ struct NodeBvh {
 
 // k < 3: axis k's edge i (nBelow / nAbove from the sweep); k == 33: plane `plane` of the node's primitives
 struct Cand { uint32_t k, i, nBelow, nAbove; BspPlane plane; };
+static_assert(sizeof(Cand) == sizeof(bspcost::Cand) && sizeof(Cand) == 32, "bsp_cost.h restates Cand");
+static_assert(sizeof(KEdge) == sizeof(kdopcost::Edge) && sizeof(KEdge) == 32, "kdop_cost.h restates KEdge");
+
+// What one candidate's cost reads besides the node, its BVH and the candidate
+struct CostConsts {
+    bool kdAware; float invTotalSA, emptyBonus; uint32_t isectCost, traversalCost, kdTraversalCost;
+};
+// One candidate of the scan: costs[k] (and, kd-aware, costsFixed[k]) as the reference's loop body leaves them; a plane
+// candidate outside the k-DOP's extent costs +inf and keeps its counts
+void CostOne(const BuildNode &cur, const NodeBvh &nb, const CostConsts &cc, Cand &c, Scratch &s, std::vector<float> *candDirs,
+             std::vector<uint32_t> &bvhStack, float *cost, float *costFixed) {
+    const float BSP_ALPHA = 0.1f;                                    // bspPaperKd.cpp:35
+    if (c.k == 33u) {
+        Range db{std::numeric_limits<float>::max(), std::numeric_limits<float>::lowest()};
+        for (const KEdge &ke : cur.mesh) {
+            const float t1 = Dot(c.plane.axis, ke.v1), t2 = Dot(c.plane.axis, ke.v2);
+            db = Range{fmin_std(db.min, fmin_std(t1, t2)), fmax_std(db.max, fmax_std(t1, t2))};
+        }
+        if (!(c.plane.t > db.min && c.plane.t < db.max)) { *cost = std::numeric_limits<float>::infinity(); return; }
+    }
+    float areaBelow, areaAbove;
+    CutMeasure(cur, c.plane.t, c.plane.axis, s, candDirs, &areaBelow, &areaAbove);
+    const float pBelow = areaBelow * cc.invTotalSA;
+    const float pAbove = areaAbove * cc.invTotalSA;
+    if (c.k == 33u) nb.count(c.plane, &c.nBelow, &c.nAbove, bvhStack);
+    const float eb = (c.nAbove == 0 || c.nBelow == 0) ? cc.emptyBonus : 0;
+    if (!cc.kdAware) *cost = (float)cc.traversalCost + (float)cc.isectCost * (1 - eb) * (pBelow * (float)c.nBelow + pAbove * (float)c.nAbove);
+    else if (c.k != 33u) *cost = (float)cc.kdTraversalCost + (float)cc.isectCost * (1 - eb) * (pBelow * (float)c.nBelow + pAbove * (float)c.nAbove);
+    else {                                               // bspPaperKd.cpp:215-218
+        const float costIntersection = (float)cc.isectCost * (1 - eb) * (pBelow * (float)c.nBelow + pAbove * (float)c.nAbove);
+        *costFixed = (float)cc.traversalCost + costIntersection;
+        *cost = BSP_ALPHA * (float)cc.isectCost * (float)(cur.nPrimitives - 1) + (float)cc.kdTraversalCost + costIntersection;
+    }
+}
 
 }  // namespace
+
+void BspBvhRecords(const BvhNode *nodes, size_t n, bspcost::BvhRec *out) {
+    for (size_t k = 0; k < n; ++k) {
+        const BvhNode &nd = nodes[k];
+        // (NodeBvh::side, operation for operation)
+        const float dx = nd.bmax[0] - nd.bmin[0], dy = nd.bmax[1] - nd.bmin[1], dz = nd.bmax[2] - nd.bmin[2];
+        const float maxDiff = std::sqrt(dx * dx + dy * dy + dz * dz) / 2;
+        const float half = (float)1 / 2;
+        out[k] = bspcost::BvhRec{{nd.bmin[0] + dx * half, nd.bmin[1] + dy * half, nd.bmin[2] + dz * half}, maxDiff, nd.offset, nd.countAxis, 0u, 0u};
+    }
+}
+
+void BspCostVector(const BspCostRequest &rq) {
+    BuildNode cur{0u, rq.sc.nPrimitives, 0u, Mesh(), std::vector<float>(rq.dirs, rq.dirs + 3 * (size_t)rq.M), 0.f, 0, 0u};
+    cur.mesh.resize(rq.nEdges);
+    if (rq.nEdges) std::memcpy(static_cast<void *>(cur.mesh.data()), rq.mesh, (size_t)rq.nEdges * sizeof(KEdge));
+    NodeBvh nb{rq.bmin, rq.bmax, rq.tri9, rq.isTri, rq.primNums, {}, {}, {}};
+    nb.bvh.nodes.assign(rq.bvhNodes, rq.bvhNodes + rq.nBvh);
+    nb.bvh.primOrder.assign(rq.primOrder, rq.primOrder + (rq.nBvh ? rq.nPrims : 0u));
+    const CostConsts cc{rq.kdAware, rq.sc.invTotalSA, rq.sc.emptyBonus, rq.sc.isectCost, rq.sc.traversalCost, rq.sc.kdTraversalCost};
+    Scratch s;
+    std::vector<float> candDirs;
+    std::vector<uint32_t> bvhStack;
+    Cand *cands = reinterpret_cast<Cand *>(rq.cands);
+    for (size_t k = 0; k < rq.n; ++k) {
+        float fixed = std::numeric_limits<float>::infinity();
+        CostOne(cur, nb, cc, cands[k], s, &candDirs, bvhStack, &rq.costs[k], &fixed);
+        if (rq.costsFixed) rq.costsFixed[k] = fixed;
+        rq.overflow[k] = 0;
+    }
+}
 
 std::vector<BspPlane> BspPaperTrianglePlanes(const float *p9) {
     std::vector<BspPlane> planes;
@@ -156,7 +224,6 @@ std::string BuildBspPaperTree(size_t n, const float *bmin, const float *bmax, co
     const uint32_t isectCost = (uint32_t)p.isectCost, traversalCost = (uint32_t)p.travCost, maxPrims = (uint32_t)p.maxPrims;
     const bool kdAware = p.kdAware;
     const uint32_t kdTraversalCost = (uint32_t)p.kdTravCost;
-    const float BSP_ALPHA = 0.1f;                                    // bspPaperKd.cpp:35
     t.kdAware = kdAware;
     const uint32_t off = kdAware ? (uint32_t)BSPPAPERKD_OFF : (uint32_t)BSPPAPER_OFF;
     const float emptyBonus = p.emptyBonus;
@@ -215,6 +282,8 @@ std::string BuildBspPaperTree(size_t n, const float *bmin, const float *bmax, co
 
     std::vector<Cand> cands;
     std::vector<float> costs, costsFixed;                            // costsFixed: kdAware only, traversalCost + C_isect of a plane candidate
+    std::vector<uint8_t> overflow;                                   // per candidate: the costing hook could not cost it (BspPaperParams::costFn)
+    std::vector<bspcost::BvhRec> bvhRecs;                            // the node's BVH as the hook reads it
     std::vector<std::vector<uint32_t>> bvhStacks((size_t)nThreads);
     std::vector<std::vector<float>> candDirs((size_t)nThreads);
     std::vector<std::thread> pool;
@@ -267,34 +336,53 @@ std::string BuildBspPaperTree(size_t n, const float *bmin, const float *bmax, co
         if (planeBegin.back() != 0) nb.build(cur.nPrimitives);
         costs.resize(cands.size());
         if (kdAware) costsFixed.assign(cands.size(), std::numeric_limits<float>::infinity());
+        const CostConsts cc{kdAware, invTotalSA, emptyBonus, isectCost, traversalCost, kdTraversalCost};
         auto costRange = [&](size_t k0, size_t k1, int w) {
-            Scratch &s = scratch[(size_t)w];
-            for (size_t k = k0; k < k1; ++k) {
-                Cand &c = cands[k];
-                if (c.k == 33u) {
-                    Range db{std::numeric_limits<float>::max(), std::numeric_limits<float>::lowest()};
-                    for (const KEdge &ke : cur.mesh) {
-                        const float t1 = Dot(c.plane.axis, ke.v1), t2 = Dot(c.plane.axis, ke.v2);
-                        db = Range{fmin_std(db.min, fmin_std(t1, t2)), fmax_std(db.max, fmax_std(t1, t2))};
-                    }
-                    if (!(c.plane.t > db.min && c.plane.t < db.max)) { costs[k] = std::numeric_limits<float>::infinity(); continue; }
-                }
-                float areaBelow, areaAbove;
-                CutMeasure(cur, c.plane.t, c.plane.axis, s, &candDirs[(size_t)w], &areaBelow, &areaAbove);
-                const float pBelow = areaBelow * invTotalSA;
-                const float pAbove = areaAbove * invTotalSA;
-                if (c.k == 33u) nb.count(c.plane, &c.nBelow, &c.nAbove, bvhStacks[(size_t)w]);
-                const float eb = (c.nAbove == 0 || c.nBelow == 0) ? emptyBonus : 0;
-                if (!kdAware) costs[k] = (float)traversalCost + (float)isectCost * (1 - eb) * (pBelow * (float)c.nBelow + pAbove * (float)c.nAbove);
-                else if (c.k != 33u) costs[k] = (float)kdTraversalCost + (float)isectCost * (1 - eb) * (pBelow * (float)c.nBelow + pAbove * (float)c.nAbove);
-                else {                                               // bspPaperKd.cpp:215-218
-                    const float costIntersection = (float)isectCost * (1 - eb) * (pBelow * (float)c.nBelow + pAbove * (float)c.nAbove);
-                    costsFixed[k] = (float)traversalCost + costIntersection;
-                    costs[k] = BSP_ALPHA * (float)isectCost * (float)(cur.nPrimitives - 1) + (float)kdTraversalCost + costIntersection;
-                }
-            }
+            for (size_t k = k0; k < k1; ++k)
+                CostOne(cur, nb, cc, cands[k], scratch[(size_t)w], &candDirs[(size_t)w], bvhStacks[(size_t)w], &costs[k], kdAware ? &costsFixed[k] : nullptr);
         };
-        if (nThreads > 1 && cands.size() >= kParallelCandidates) {
+        // the costing hook (BspPaperParams::costFn): the node's candidates costed elsewhere, the flagged ones repaired here
+        bool costed = false;
+        if (p.costFn && !cands.empty() && cands.size() >= p.costMinCandidates) {
+            overflow.assign(cands.size(), 0);
+            const bool hasBvh = planeBegin.back() != 0;
+            bvhRecs.resize(hasBvh ? nb.bvh.nodes.size() : 0);
+            BspBvhRecords(nb.bvh.nodes.data(), bvhRecs.size(), bvhRecs.data());
+            size_t nAxis = 0;
+            while (nAxis < cands.size() && cands[nAxis].k != 33u) ++nAxis;
+            BspCostRequest rq;
+            rq.mesh = reinterpret_cast<const kdopcost::Edge *>(cur.mesh.data()); rq.nEdges = (uint32_t)cur.mesh.size();
+            rq.dirs = cur.dirs.data(); rq.M = (uint32_t)(cur.dirs.size() / 3); rq.kdAware = kdAware;
+            rq.sc = bspcost::Scalars{invTotalSA, emptyBonus, isectCost, traversalCost, kdTraversalCost, cur.nPrimitives, 0u, 0u, 0u, 0u};
+            rq.cands = reinterpret_cast<bspcost::Cand *>(cands.data()); rq.n = cands.size(); rq.nAxis = nAxis;
+            rq.bvhNodes = nb.bvh.nodes.data(); rq.bvh = bvhRecs.data(); rq.nBvh = (uint32_t)bvhRecs.size();
+            rq.primOrder = nb.bvh.primOrder.data(); rq.primNums = primNums; rq.nPrims = cur.nPrimitives;
+            rq.bmin = bmin; rq.bmax = bmax; rq.tri9 = tri9; rq.isTri = isTri; rq.nTotal = n;
+            rq.costs = costs.data(); rq.costsFixed = kdAware ? costsFixed.data() : nullptr; rq.overflow = overflow.data();
+            rq.level = maxDepth - cur.depth;
+            std::string err;
+            const auto t0 = std::chrono::steady_clock::now();
+            const int rc = p.costFn(rq, &err);
+            if (rc < 0) return err.empty() ? std::string("the costing hook failed") : err;
+            if (rc == 0) {
+                costed = true;
+                uint64_t redo = 0;
+                for (size_t k = 0; k < cands.size(); ++k)
+                    if (overflow[k]) {
+                        if (kdAware) costsFixed[k] = std::numeric_limits<float>::infinity();
+                        costRange(k, k + 1, 0); ++redo;
+                    }
+                if (p.stats) {
+                    p.stats->secondsDevice += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+                    ++p.stats->nodesDevice; p.stats->candidatesDevice += cands.size() - redo; p.stats->candidatesRecosted += redo;
+                }
+                if (p.costDone) p.costDone(rq);
+            }
+        }
+        if (!costed && p.stats) ++p.stats->nodesHost;
+        if (costed) {
+            // (costs[], costsFixed[] and the plane candidates' counts are complete)
+        } else if (nThreads > 1 && cands.size() >= kParallelCandidates) {
             const size_t chunk = (cands.size() + nThreads - 1) / nThreads;
             pool.clear();
             for (int w = 1; w < nThreads; ++w) {

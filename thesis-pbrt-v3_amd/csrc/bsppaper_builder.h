@@ -9,11 +9,15 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <functional>
 #include <string>
 #include <vector>
+#include "bsp_cost.h"
 #include "bsp_tree.h"
 
 namespace hprt {
+
+struct BvhNode;       // bvh_builder.h
 
 // BSPNode's first 8 bytes: a = split (float bits) | onePrimitive | primitiveIndicesOffset; b = flags: leaf 1 | nPrims << 1, interior
 // 0 | aboveChild << 1 (treeInitLeaf / treeInitInterior, BSP.h:11-35) — bsp_tree.h's node with M = 1 (off 1, mask 1).
@@ -21,6 +25,25 @@ enum : uint32_t { BSPPAPER_TODO_MAX = 64u, BSPPAPER_M = 1u, BSPPAPER_OFF = 1u, B
 // BSPKdNode's flags (BSPKd.h:11-57), the kd-aware tree's: the low 3 bits are 0-2 a kd interior node with that axis, 3 a leaf, 4 a
 // plane interior node; aboveChild / nPrims << 3
 enum : uint32_t { BSPPAPERKD_TODO_MAX = 64u, BSPPAPERKD_LEAF = 3u, BSPPAPERKD_PLANE = 4u, BSPPAPERKD_OFF = 3u, BSPPAPERKD_MASK = 7u };
+
+// One node's candidates, as costFn sees them (bsp_cost.h: Edge is kdop::KEdge field for field, Cand the builder's candidate).  The
+// axis candidates come first (nAxis of them), then the plane candidates.  bvhNodes / bvh: the BVH over the node's primitives as
+// BuildBvh left it and as NodeBvh::side reads it (BspBvhRecords); both empty when no primitive has a plane.  primNums: the node's
+// primitives; bmin .. isTri: the build's primitives (nTotal of them).
+struct BspCostRequest {
+    const kdopcost::Edge *mesh; uint32_t nEdges;          // face ids below 2 M
+    const float *dirs; uint32_t M;                        // the node's own direction list
+    bool kdAware;
+    bspcost::Scalars sc;
+    bspcost::Cand *cands; size_t n, nAxis;                // nBelow / nAbove of a costed plane candidate are written here
+    const BvhNode *bvhNodes; const bspcost::BvhRec *bvh; uint32_t nBvh;
+    const uint32_t *primOrder, *primNums; uint32_t nPrims;
+    const float *bmin, *bmax, *tri9; const uint8_t *isTri; size_t nTotal;
+    float *costs, *costsFixed;                            // costsFixed: NULL unless kdAware
+    uint8_t *overflow;                                    // 1: not costed (a capacity of the costing was exceeded)
+    uint32_t level;                                       // the node's depth below the root (diagnostics)
+};
+struct BspBuildStats { uint64_t nodesDevice = 0, candidatesDevice = 0, candidatesRecosted = 0, nodesHost = 0; double secondsDevice = 0; };
 
 struct BspPaperParams {
     int isectCost = 80, travCost = 5;     // "intersectcost", "traversalcost"
@@ -33,6 +56,16 @@ struct BspPaperParams {
     // the leaf tests and supplies the split only where the first is unset; nodes carry BSPKdNode's flags (BSPPAPERKD_*)
     bool kdAware = false;
     int kdTravCost = 1;                   // "kdtraversalcost"
+    // Optional costing hook (the device-assisted build, hprt_bsppaper_build_device): a node with at least costMinCandidates
+    // candidates is handed to costFn instead of the thread pool.  It fills costs / costsFixed / overflow for every candidate and
+    // nBelow / nAbove of every plane candidate it has costed, and returns 0; returns 1 to decline the node (it takes the host
+    // path), < 0 to fail the build with *err.  Flagged candidates are costed again by costRange itself.  Smaller nodes, and all
+    // nodes when costFn is empty, take the host path.  The scan over costs[] is the same either way.
+    std::function<int(const BspCostRequest &, std::string *err)> costFn;
+    uint32_t costMinCandidates = 1024;    // (kdop::kParallelCandidates)
+    BspBuildStats *stats = nullptr;       // filled when costFn is set
+    // Diagnostics: called for a node costFn has handled, after the repair, with the costs and counts the scan is about to read
+    std::function<void(const BspCostRequest &)> costDone;
 };
 
 struct BspPaperTree {
@@ -62,6 +95,11 @@ void BspPaperClassify(size_t n, const float *bmin, const float *bmax, const floa
 // reference's (maxDepth + 1) * N primitive buffer).
 std::string BuildBspPaperTree(size_t n, const float *bmin, const float *bmax, const float *tri9, const uint8_t *isTri, const BspPaperParams &p,
                               BspPaperTree *out);
+// What NodeBvh::side computes from a BVH node's box, with its operations: the centre and half the diagonal's length (out: n records)
+void BspBvhRecords(const BvhNode *nodes, size_t n, bspcost::BvhRec *out);
+// The candidates of rq costed with the builder's own code (CutMeasure over the vector meshes, NodeBvh::count over bvhNodes) and
+// costRange's formulas, on the calling thread: what the diagnostics hook hprt_debug_bsp_cost calls impl 0.  overflow is cleared.
+void BspCostVector(const BspCostRequest &rq);
 // Structural check of a tree handed to the device: CheckBspNodes with M = 1, one axis per node, every interior axis finite and
 // non-zero.  Returns an empty string when the tree is well-formed, else what is wrong.
 const char *CheckBspPaperTree(const BspPaperTree &t, uint32_t *depthOut);

@@ -14,6 +14,7 @@
 #include <string>
 #include <type_traits>
 #include "../../include/hprt.h"
+#include "bsp_cost_device.h"
 #include "bspnode_builder.h"
 #include "bvh_builder.h"
 #include "halton_tables.h"
@@ -206,11 +207,88 @@ void RbspPrimTriangles(const SceneModel &sc, int object, size_t n, std::vector<f
 // ---- the general BSP handles' builds and copies (hprt_bsppaper_* and hprt_bsppaperkd_* below) ----
 // Handle HprtBspPaper with Params HprtBspPaperParams, or HprtBspPaperKd (the kd-aware cost model and node flags) with
 // HprtBspPaperKdParams; params NULL keeps p
+// What a build does besides the host build (NULL: nothing), as RbspHook.  device: the device-assisted build
+// (hprt_bsppaper*_build*_device) — nodes of at least min_candidates candidates are costed by k_bspcost.  sink: the diagnostics hook
+// hprt_debug_bsp_root_nodes — the first maxNodes costed nodes are handed out with the costs and counts the builder's own code gave.
+struct HprtDebugBspNode {
+    const void *edges; uint32_t n_edges;              // 32-byte records (v1, v2, f1, f2), face ids below 2 M
+    const float *dirs; uint32_t M;                    // the node's direction list
+    const void *scalars;                              // bspcost::Scalars (10 words)
+    const void *cands; size_t n, n_axis;              // 32-byte records (k, i, nBelow, nAbove, t, axis); axis candidates first
+    const void *bvh_nodes; uint32_t n_bvh;            // 32-byte LinearBVHNode records of the BVH over the node's primitives
+    const uint32_t *prim_order, *prim_nums; uint32_t n_prims;
+    const float *bmin, *bmax, *tri9; const uint8_t *is_tri; size_t n_total;      // the build's primitives
+    const float *costs, *costs_fixed;                 // the builder's own (costs_fixed NULL unless kd-aware); NULL as an input
+    uint32_t level;                                   // the node's depth below the root
+};
+typedef void (*BspNodeSink)(void *user, uint32_t node, const HprtDebugBspNode *nd);
+struct BspHook {
+    bool device = false;
+    const HprtBspBuildDeviceOpts *opts = nullptr;
+    HprtBuildDeviceStats *stats = nullptr;
+    BspNodeSink sink = nullptr; void *user = nullptr; uint32_t maxNodes = 0;
+};
+// The node of a request as bsp_cost.h reads it: compact face ids and the directions that own a face.  False: the node's own
+// mesh, direction list or faces exceed the capacities (it is declined whole), or a face id is not below 2 M.
+struct BspCompact { std::vector<bspcost::Edge> mesh; std::vector<uint32_t> cdir; uint32_t nD = 0; };
+bool BspCompactRequest(const BspCostRequest &rq, const uint32_t cap[4], BspCompact *c) {
+    if (rq.nEdges > cap[0] || rq.M == 0 || rq.M > BSP_MAX_DIRS) return false;
+    for (uint32_t k = 0; k < rq.nEdges; ++k)
+        if (rq.mesh[k].f1 >= 2 * rq.M || rq.mesh[k].f2 >= 2 * rq.M) return false;
+    c->mesh.resize(rq.nEdges); c->cdir.resize(rq.M);
+    bspcost::CompactNode(rq.mesh, rq.nEdges, rq.M, c->mesh.data(), c->cdir.data(), &c->nD);
+    return 2 * c->nD <= cap[1];
+}
+// Takes over what a costing wrote beside rq's own arrays: the fixed costs and the counts of the candidates it has costed
+void BspTakeResults(const BspCostRequest &rq, const float *fixed, const uint32_t *counts) {
+    for (size_t k = 0; k < rq.n; ++k) {
+        if (rq.overflow[k]) continue;
+        if (rq.costsFixed) rq.costsFixed[k] = fixed[k];
+        rq.cands[k].nBelow = counts[2 * k]; rq.cands[k].nAbove = counts[2 * k + 1];
+    }
+}
+// bsp_cost.h on the host, one candidate after the other (the diagnostics hook's impl 1).  1: the node is declined.
+int BspCostRestated(const BspCostRequest &rq) {
+    uint32_t cap[4];
+    if (!bspcost::Capacities(rq.sc, cap)) return -1;
+    BspCompact cn;
+    if (!BspCompactRequest(rq, cap, &cn)) return 1;
+    using namespace bspcost;
+    std::vector<Q> words(kStoreWords);
+    uint8_t list[BSP_MAX_FACE_EDGES];
+    uint32_t stack[BSP_MAX_STACK];
+    Store st;
+    st.left = words.data(); st.right = words.data() + 2 * BSP_MAX_EDGES; st.fv = words.data() + 4 * BSP_MAX_EDGES; st.stride = 1;
+    st.flist = list; st.fstride = 1; st.stack = stack; st.sstride = 1;
+    st.capEdges = cap[0]; st.capFaces = cap[1]; st.capFaceEdges = cap[2]; st.capStack = cap[3];
+    const Node nd{cn.mesh.data(), rq.nEdges, rq.dirs, rq.M, cn.cdir.data(), cn.nD, rq.bvh, rq.nBvh, rq.primOrder, rq.primNums, rq.nPrims,
+                  rq.bmin, rq.bmax, rq.tri9, rq.isTri, (uint32_t)rq.nTotal};
+    std::vector<float> fixed(rq.n);
+    std::vector<uint32_t> counts(2 * rq.n);
+    for (size_t k = 0; k < rq.n; ++k)
+        CostCandidate(nd, rq.kdAware, rq.sc, rq.cands[k], st, &rq.costs[k], &fixed[k], &counts[2 * k], &counts[2 * k + 1], &rq.overflow[k]);
+    BspTakeResults(rq, fixed.data(), counts.data());
+    return 0;
+}
+// k_bspcost over a request (the device-assisted build, and the diagnostics hook's impl 2).  0, 1 (declined) or -1 with *rc / *err.
+int BspCostOnDevice(BspCostDevice *dev, const uint32_t cap[4], const BspCostRequest &rq, int *rc, std::string *err) {
+    BspCompact cn;
+    if (!BspCompactRequest(rq, cap, &cn)) return 1;
+    std::vector<float> fixed(rq.n);
+    std::vector<uint32_t> counts(2 * rq.n);
+    *rc = BspCostDeviceRun(dev, cn.mesh.data(), rq.nEdges, rq.dirs, rq.M, cn.cdir.data(), cn.nD, rq.kdAware, rq.sc, rq.cands, rq.n, rq.nAxis, rq.bvh, rq.nBvh,
+                           rq.primOrder, rq.primNums, rq.nPrims, rq.costs, fixed.data(), counts.data(), rq.overflow, err);
+    if (*rc != HPRT_OK) return -1;
+    BspTakeResults(rq, fixed.data(), counts.data());
+    return 0;
+}
+
 template <typename Handle, typename Params>
 int BuildBspPaper(size_t n, const float *lo, const float *hi, const float *tri9, const uint8_t *isTri, const Params *params,
-                  BspPaperParams p, Handle **out) {
+                  BspPaperParams p, Handle **out, const BspHook *hook = nullptr) {
     constexpr bool kdAware = std::is_same<Handle, HprtBspPaperKd>::value;
     p.kdAware = kdAware;
+    if (hook) *out = nullptr;
     if (params) {
         p.isectCost = params->isect_cost; p.travCost = params->trav_cost; p.emptyBonus = params->empty_bonus;
         p.maxPrims = params->max_prims; p.maxDepth = params->max_depth; p.threads = params->threads;
@@ -219,7 +297,40 @@ int BuildBspPaper(size_t n, const float *lo, const float *hi, const float *tri9,
     const std::string what = kdAware ? "bsppaperkd" : "bsppaper";
     constexpr uint32_t todoMax = kdAware ? BSPPAPERKD_TODO_MAX : BSPPAPER_TODO_MAX;
     std::unique_ptr<Handle> t(new Handle());
+    struct DeviceGuard { BspCostDevice *d = nullptr; ~DeviceGuard() { BspCostDeviceDestroy(d); } } dev;      // freed when the build ends or fails
+    BspBuildStats bs;
+    int hookRc = HPRT_OK;
+    uint32_t seen = 0, cap[4] = {0, 0, 0, 0};
+    if (hook && hook->device) {
+        if (hook->stats) *hook->stats = HprtBuildDeviceStats{0, 0, 0, 0, 0.0};
+        const HprtBspBuildDeviceOpts *o = hook->opts;
+        const uint32_t asked[4] = {o ? o->max_edges : 0u, o ? o->max_faces : 0u, o ? o->max_face_edges : 0u, o ? o->max_stack : 0u};
+        std::string derr;
+        const int rc = BspCostDeviceCreate(o ? o->device : 0, asked, n, lo, hi, tri9, isTri, &dev.d, &derr);
+        if (rc != HPRT_OK) return SetError(rc, derr);
+        bspcost::Scalars sc{};
+        sc.maxEdges = asked[0]; sc.maxFaces = asked[1]; sc.maxFaceEdges = asked[2]; sc.maxStack = asked[3];
+        bspcost::Capacities(sc, cap);
+        p.costMinCandidates = o && o->min_candidates ? o->min_candidates : kDeviceMinCandidates;
+        p.stats = &bs;
+        p.costFn = [&](const BspCostRequest &rq, std::string *e) -> int { return BspCostOnDevice(dev.d, cap, rq, &hookRc, e); };
+    } else if (hook && hook->sink) {
+        p.costMinCandidates = 1;
+        p.costFn = [&](const BspCostRequest &rq, std::string *) -> int {
+            if (seen >= hook->maxNodes) return 1;
+            memset(rq.overflow, 1, rq.n);          // every candidate "flagged": the builder costs them all with its own code
+            return 0;
+        };
+        p.costDone = [&](const BspCostRequest &rq) {
+            const HprtDebugBspNode nd{rq.mesh, rq.nEdges, rq.dirs, rq.M, &rq.sc, rq.cands, rq.n, rq.nAxis, rq.bvhNodes, rq.nBvh, rq.primOrder, rq.primNums,
+                                      rq.nPrims, rq.bmin, rq.bmax, rq.tri9, rq.isTri, rq.nTotal, rq.costs, rq.costsFixed, rq.level};
+            hook->sink(hook->user, seen++, &nd);
+        };
+    }
     const std::string err = BuildBspPaperTree(n, lo, hi, tri9, isTri, p, &t->tree);
+    if (hook && hook->stats)
+        *hook->stats = HprtBuildDeviceStats{bs.nodesDevice, bs.candidatesDevice, bs.candidatesRecosted, bs.nodesHost, bs.secondsDevice};
+    if (hookRc != HPRT_OK) return SetError(hookRc, err);
     if (!err.empty()) return SetError(HPRT_E_UNSUPPORTED, err);
     if (t->tree.depth > todoMax)
         return SetError(HPRT_E_UNSUPPORTED, what + " tree of depth " + std::to_string(t->tree.depth) + " is deeper than the device walk's todo list (" +
@@ -581,6 +692,30 @@ int WriteStatMatrices(const char *prefix, int width, int height, Value value) {
         if (!ok) return SetError(HPRT_E_IO, "write error on " + path);
     }
     return HPRT_OK;
+}
+// hprt_bsppaper*_build*_device and the diagnostics hooks: a model's primitives, or n triangles, through BuildBspPaper with a hook
+template <typename Handle, typename Params>
+int BuildBspPaperFromModel(const char *fn, const char *what, const HprtModel *m, const Params *params, Handle **out, const BspHook *hook) {
+    if (!m || !out) return SetError(HPRT_E_INVALID, std::string(fn) + ": null argument");
+    *out = nullptr;
+    if (m->sc.nObjects != 0 || !m->sc.instances.empty())
+        return SetError(HPRT_E_UNSUPPORTED, std::string(what) + " trees over object instances are not supported (the scene keeps its BVH)");
+    std::vector<float> lo, hi, tri9;
+    std::vector<uint8_t> isTri;
+    RbspModelPrims(m, &lo, &hi, &tri9, &isTri);
+    const BspPaperParams dflt = std::is_same<Handle, HprtBspPaperKd>::value ? m->sc.opt.bsppaperkd : m->sc.opt.bsppaper;
+    return BuildBspPaper(lo.size() / 3, lo.data(), hi.data(), tri9.data(), isTri.data(), params, dflt, out, hook);
+}
+template <typename Handle, typename Params>
+int BuildBspPaperFromTriangles(const char *fn, size_t n, const float *p9, const Params *params, Handle **out, const BspHook *hook) {
+    if (!out || (n && !p9)) return SetError(HPRT_E_INVALID, std::string(fn) + ": null argument");
+    *out = nullptr;
+    constexpr bool kdAware = std::is_same<Handle, HprtBspPaperKd>::value;
+    if (n > (kdAware ? 0x0fffffffull : 0x3fffffffull)) return SetError(HPRT_E_UNSUPPORTED, kdAware ? "more than 2^28 primitives" : "more than 2^30 primitives");
+    std::vector<float> lo, hi;
+    RbspTriangleBounds(n, p9, &lo, &hi);
+    std::vector<uint8_t> isTri(n, 1);
+    return BuildBspPaper(n, lo.data(), hi.data(), p9, isTri.data(), params, BspPaperParams(), out, hook);
 }
 }  // namespace
 
@@ -962,6 +1097,117 @@ int hprt_bsppaperkd_copy(const HprtBspPaperKd *t, void *nodes20, uint32_t *primI
     return BspPaperCopy(t->tree, nodes20, primIndices);
 } catch (...) { return hprt::HandleException(); }
 void hprt_bsppaperkd_destroy(HprtBspPaperKd *t) { delete t; }
+// ---- the device-assisted builds: the same builder with its candidates costed by k_bspcost (device/bsp_cost.hip) ----
+int hprt_bsppaper_build_device(const HprtModel *m, const HprtBspPaperParams *params, const HprtBspBuildDeviceOpts *opts, HprtBuildDeviceStats *stats,
+                               HprtBspPaper **out) try {
+    BspHook h; h.device = true; h.opts = opts; h.stats = stats;
+    return BuildBspPaperFromModel("hprt_bsppaper_build_device", "bsppaper", m, params, out, &h);
+} catch (...) { return hprt::HandleException(); }
+int hprt_bsppaper_build_from_triangles_device(size_t n, const float *p9, const HprtBspPaperParams *params, const HprtBspBuildDeviceOpts *opts,
+                                              HprtBuildDeviceStats *stats, HprtBspPaper **out) try {
+    BspHook h; h.device = true; h.opts = opts; h.stats = stats;
+    return BuildBspPaperFromTriangles("hprt_bsppaper_build_from_triangles_device", n, p9, params, out, &h);
+} catch (...) { return hprt::HandleException(); }
+int hprt_bsppaperkd_build_device(const HprtModel *m, const HprtBspPaperKdParams *params, const HprtBspBuildDeviceOpts *opts, HprtBuildDeviceStats *stats,
+                                 HprtBspPaperKd **out) try {
+    BspHook h; h.device = true; h.opts = opts; h.stats = stats;
+    return BuildBspPaperFromModel("hprt_bsppaperkd_build_device", "bsppaperkd", m, params, out, &h);
+} catch (...) { return hprt::HandleException(); }
+int hprt_bsppaperkd_build_from_triangles_device(size_t n, const float *p9, const HprtBspPaperKdParams *params, const HprtBspBuildDeviceOpts *opts,
+                                                HprtBuildDeviceStats *stats, HprtBspPaperKd **out) try {
+    BspHook h; h.device = true; h.opts = opts; h.stats = stats;
+    return BuildBspPaperFromTriangles("hprt_bsppaperkd_build_from_triangles_device", n, p9, params, out, &h);
+} catch (...) { return hprt::HandleException(); }
+// Diagnostics hooks of the general BSP candidate costing (not part of include/hprt.h; tests/bsp_cost_nodes.py).
+// hprt_debug_bsp_root_nodes hands out the first max_nodes nodes a build costs, in build order: mesh, directions, candidates, the
+// BVH over the node's primitives and the build's primitive arrays, with the costs and (in the candidates) the counts the builder's
+// own code gave them.  m != NULL: the model's primitives; else n triangles.  params: HprtBspPaperKdParams for both trees
+// (kd_trav_cost is not read when kd_aware is 0).  The pointers are valid during the call only.
+__attribute__((visibility("default"))) int hprt_debug_bsp_root_nodes(const HprtModel *m, size_t n, const float *p9, int kd_aware, const HprtBspPaperKdParams *params,
+                                                                      uint32_t max_nodes, BspNodeSink sink, void *user) try {
+    if (!params || !sink) return SetError(HPRT_E_INVALID, "hprt_debug_bsp_root_nodes: null argument");
+    BspHook h; h.sink = sink; h.user = user; h.maxNodes = max_nodes;
+    int rc;
+    if (kd_aware) {
+        HprtBspPaperKd *t = nullptr;
+        rc = m ? BuildBspPaperFromModel("hprt_debug_bsp_root_nodes", "bsppaperkd", m, params, &t, &h)
+               : BuildBspPaperFromTriangles("hprt_debug_bsp_root_nodes", n, p9, params, &t, &h);
+        delete t;
+    } else {
+        const HprtBspPaperParams q{params->isect_cost, params->trav_cost, params->empty_bonus, params->max_prims, params->max_depth, params->threads};
+        HprtBspPaper *t = nullptr;
+        rc = m ? BuildBspPaperFromModel("hprt_debug_bsp_root_nodes", "bsppaper", m, &q, &t, &h)
+               : BuildBspPaperFromTriangles("hprt_debug_bsp_root_nodes", n, p9, &q, &t, &h);
+        delete t;
+    }
+    return rc;
+} catch (...) { return hprt::HandleException(); }
+// hprt_debug_bsp_cost costs a node again with impl 0 (the vector code of bsp_build.h plus NodeBvh::count, BspCostVector), 1
+// (bsp_cost.h on the host) or 2 (k_bspcost).  nd: a node as the sink above receives it (costs / costs_fixed are not read; the
+// scalars' four capacity fields may lower the compiled capacities).  counts: nBelow, nAbove per candidate (an axis candidate's and
+// an out-of-extent plane's are the input's).  Everything the costing indexes by is checked first (HPRT_E_INVALID): M, every face
+// id, the order and kind of the candidates, the BVH's structure, primOrder, primNums and the capacities.  A node that impl 1 / 2
+// decline whole (its own mesh, faces or direction list beyond a capacity) comes back with every candidate flagged.
+__attribute__((visibility("default"))) int hprt_debug_bsp_cost(const HprtDebugBspNode *nd, int kd_aware, int impl, float *costs, float *costs_fixed,
+                                                                uint32_t *counts, uint8_t *overflow) try {
+    using namespace bspcost;
+    const char *fn = "hprt_debug_bsp_cost: ";
+    if (!nd || !costs || !costs_fixed || !counts || !overflow || !nd->scalars || !nd->dirs || (nd->n && !nd->cands) || (nd->n_edges && !nd->edges))
+        return SetError(HPRT_E_INVALID, std::string(fn) + "null argument");
+    if (impl < 0 || impl > 2) return SetError(HPRT_E_INVALID, std::string(fn) + "impl is not 0, 1 or 2");
+    if (nd->M == 0 || nd->M > 65536u || nd->n_edges > 65536u || nd->n > 0x7fffffffull || nd->n_total > 0x7fffffffull || nd->n_axis > nd->n)
+        return SetError(HPRT_E_INVALID, std::string(fn) + "a size that cannot be real");
+    Scalars sc;
+    memcpy(&sc, nd->scalars, sizeof(sc));
+    uint32_t cap[4];
+    if (!Capacities(sc, cap)) return SetError(HPRT_E_INVALID, std::string(fn) + "a capacity field may only lower the compiled capacity");
+    std::vector<Edge> mesh(nd->n_edges);
+    if (nd->n_edges) memcpy(static_cast<void *>(mesh.data()), nd->edges, (size_t)nd->n_edges * sizeof(Edge));
+    for (const Edge &e : mesh)
+        if (e.f1 >= 2 * nd->M || e.f2 >= 2 * nd->M) return SetError(HPRT_E_INVALID, std::string(fn) + "a face id is not below 2 M");
+    std::vector<Cand> cs(nd->n);
+    if (nd->n) memcpy(static_cast<void *>(cs.data()), nd->cands, nd->n * sizeof(Cand));
+    for (size_t k = 0; k < nd->n; ++k)
+        if (k < nd->n_axis ? cs[k].k >= 3u : cs[k].k != 33u)
+            return SetError(HPRT_E_INVALID, std::string(fn) + "the candidates are not n_axis axis candidates followed by plane candidates");
+    std::vector<BvhNode> bvhNodes;
+    std::vector<BvhRec> recs;
+    if (nd->n_axis < nd->n) {
+        if (!nd->bvh_nodes || !nd->prim_order || !nd->prim_nums || !nd->bmin || !nd->bmax || !nd->tri9 || !nd->is_tri || nd->n_bvh == 0 || nd->n_prims == 0 ||
+            nd->n_bvh > 0x7fffffffu)
+            return SetError(HPRT_E_INVALID, std::string(fn) + "plane candidates without a BVH or without primitives");
+        bvhNodes.resize(nd->n_bvh);
+        memcpy(static_cast<void *>(bvhNodes.data()), nd->bvh_nodes, (size_t)nd->n_bvh * sizeof(BvhNode));
+        const char *bad = CheckBvhNodes(bvhNodes.data(), nd->n_bvh, nd->n_prims, nullptr);
+        if (*bad) return SetError(HPRT_E_INVALID, std::string(fn) + "malformed BVH: " + bad);
+        for (uint32_t i = 0; i < nd->n_prims; ++i)
+            if (nd->prim_order[i] >= nd->n_prims || nd->prim_nums[i] >= nd->n_total)
+                return SetError(HPRT_E_INVALID, std::string(fn) + "primOrder or primNums points outside the primitives");
+        recs.resize(nd->n_bvh);
+        BspBvhRecords(bvhNodes.data(), bvhNodes.size(), recs.data());
+    }
+    for (size_t k = 0; k < nd->n; ++k) { costs[k] = 0; costs_fixed[k] = std::numeric_limits<float>::infinity(); overflow[k] = 1; counts[2 * k] = cs[k].nBelow; counts[2 * k + 1] = cs[k].nAbove; }
+    const BspCostRequest rq{mesh.data(), nd->n_edges, nd->dirs, nd->M, kd_aware != 0, sc, cs.data(), nd->n, nd->n_axis, bvhNodes.data(), recs.data(),
+                            (uint32_t)recs.size(), nd->prim_order, nd->prim_nums, recs.empty() ? 0u : nd->n_prims, nd->bmin, nd->bmax, nd->tri9, nd->is_tri,
+                            nd->n_total, costs, costs_fixed, overflow};
+    int rc = 0;
+    if (impl == 0) BspCostVector(rq);
+    else if (impl == 1) rc = BspCostRestated(rq);
+    else {
+        struct DeviceGuard { BspCostDevice *d = nullptr; ~DeviceGuard() { BspCostDeviceDestroy(d); } } dev;
+        std::string err;
+        const uint32_t asked[4] = {sc.maxEdges, sc.maxFaces, sc.maxFaceEdges, sc.maxStack};
+        int drc = BspCostDeviceCreate(0, asked, nd->n_total, nd->bmin, nd->bmax, nd->tri9, nd->is_tri, &dev.d, &err);
+        if (drc != HPRT_OK) return SetError(drc, err);
+        rc = BspCostOnDevice(dev.d, cap, rq, &drc, &err);
+        if (rc < 0) return SetError(drc, err);
+    }
+    if (rc == 1) return HPRT_OK;            // declined whole: every candidate flagged
+    for (size_t k = 0; k < nd->n; ++k)
+        if (!overflow[k]) { counts[2 * k] = cs[k].nBelow; counts[2 * k + 1] = cs[k].nAbove; }
+        else { costs[k] = 0; costs_fixed[k] = std::numeric_limits<float>::infinity(); }
+    return HPRT_OK;
+} catch (...) { return hprt::HandleException(); }
 // ---- two-level general BSP trees (Accelerator "bsppaper" / "bsppaperkd" over object instances, pbrtObjectInstance,
 // core/api.cpp:1794-1819: MakeAccelerator for every object of more than one primitive and again in pbrtWorldEnd; helpers above) ----
 int hprt_bsppaperinst_build(const HprtModel *m, const HprtBspPaperParams *params, HprtBspPaperInst **out) try {
