@@ -512,6 +512,24 @@ int hprt_bspnode_build_from_triangles(size_t n_tris, const float *p9, const Hprt
  * deeper than HPRT_BSPPAPERKD_MAX_DEPTH. */
 int hprt_bspnodekd_build(const HprtModel *m, const HprtBspNodeParams *params, HprtBspPaperKd **out);
 int hprt_bspnodekd_build_from_triangles(size_t n_tris, const float *p9, const HprtBspNodeParams *params, HprtBspPaperKd **out);
+/* Device-assisted builds of the node-based trees (opt-in).  They return the same bytes, the same refusals and the same messages as
+ * the four entries above: the direction chooser (k-means included) and its draws, the projections, sorts and sweeps, the
+ * first-minimum scans, the leaf tests, the winner's cut and the classification stay on the host; what moves to the GPU is the
+ * costing of a node's split candidates (KDOPMeshWithDirections::cut + KDOPSurfaceArea of accelerators/kDOPMesh.h and the cost
+ * formulas of bspNodeBased.cpp / bspNodeBasedFastKd.cpp), one candidate per lane, for nodes with at least min_candidates
+ * candidates.  A candidate that outgrows one of the kernel's fixed capacities is costed again on the host; a node whose own mesh or
+ * direction list does, or which sweeps more than 16 directions, is costed on the host whole.  opts NULL: device 0 and the defaults;
+ * max_stack is not read (these trees have no node BVH); stats may be NULL.  Without a HIP device: HPRT_E_NO_DEVICE and *out stays
+ * NULL; what the host entry refuses before it looks at a primitive (bad arguments, an instanced model, the wrong form, a K the
+ * reference's build is undefined for) is refused first, with the same code and message, on every machine. */
+int hprt_bspnode_build_device(const HprtModel *m, const HprtBspNodeParams *params, const HprtBspBuildDeviceOpts *opts, HprtBuildDeviceStats *stats,
+                              HprtBspPaper **out);
+int hprt_bspnode_build_from_triangles_device(size_t n_tris, const float *p9, const HprtBspNodeParams *params, const HprtBspBuildDeviceOpts *opts,
+                                             HprtBuildDeviceStats *stats, HprtBspPaper **out);
+int hprt_bspnodekd_build_device(const HprtModel *m, const HprtBspNodeParams *params, const HprtBspBuildDeviceOpts *opts, HprtBuildDeviceStats *stats,
+                                HprtBspPaperKd **out);
+int hprt_bspnodekd_build_from_triangles_device(size_t n_tris, const float *p9, const HprtBspNodeParams *params, const HprtBspBuildDeviceOpts *opts,
+                                               HprtBuildDeviceStats *stats, HprtBspPaperKd **out);
 
 /* ------------------------------------------------------------------------ */
 /* Device scene.  Upload step that follows the BVH build: stands in for the  */

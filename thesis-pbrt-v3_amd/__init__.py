@@ -386,6 +386,10 @@ def _load():
         "hprt_bspnode_build_from_triangles": (C.c_int, [sz, vp, vp, P(vp)]),
         "hprt_bspnodekd_build": (C.c_int, [vp, vp, P(vp)]),
         "hprt_bspnodekd_build_from_triangles": (C.c_int, [sz, vp, vp, P(vp)]),
+        "hprt_bspnode_build_device": (C.c_int, [vp, vp, vp, vp, P(vp)]),
+        "hprt_bspnode_build_from_triangles_device": (C.c_int, [sz, vp, vp, vp, vp, P(vp)]),
+        "hprt_bspnodekd_build_device": (C.c_int, [vp, vp, vp, vp, P(vp)]),
+        "hprt_bspnodekd_build_from_triangles_device": (C.c_int, [sz, vp, vp, vp, vp, P(vp)]),
         "hprt_scene_kd_counters": (C.c_int, [vp, vp]),
         "hprt_pixel_kd_stats_read": (C.c_int, [vp, vp, sz]),
         "hprt_write_pixel_stats_rbspkd": (C.c_int, [cp, vp, vp, C.c_int, C.c_int]),
@@ -855,56 +859,62 @@ class BspNode(BspPaper):
     params) — the reference's BSP over BSPNode, so a BspPaper in all but its builder: info(), arrays() and Scene.attach_bsppaper
     take it unchanged.  BspNode(model) takes accelerator and parameters from the scene's Accelerator line; given `accelerator`
     ("bspcluster", "bsprandomwithkd", ...), the keyword parameters replace it.  `seed` seeds the direction chooser's std::mt19937
-    (the reference seeds from std::random_device): the same seed gives the same tree."""
+    (the reference seeds from std::random_device): the same seed gives the same tree.  device: None builds on the host; a HIP
+    device ordinal costs the split candidates of nodes with at least min_candidates candidates on that GPU (k_sweepcost; the same
+    tree, byte for byte) and leaves HprtBuildDeviceStats as a dict in self.build_stats.  max_edges / max_faces / max_face_edges: 0,
+    or a value that lowers the kernel's compiled capacity."""
 
     def __init__(self, model=None, accelerator=None, handle=None, n_directions=3, seed=BSPNODE_DEFAULT_SEED, isect_cost=80, trav_cost=5,
-                 empty_bonus=0.0, max_prims=1, max_depth=-1, threads=0):
+                 empty_bonus=0.0, max_prims=1, max_depth=-1, threads=0, device=None, min_candidates=0, max_edges=0, max_faces=0, max_face_edges=0, build_stats=None):
+        self.build_stats = build_stats
         if handle is None:
-            handle = C.c_void_p()
             prm = None if accelerator is None else C.byref(_bspnode_params(accelerator, False, n_directions, seed, isect_cost, trav_cost, 1, empty_bonus,
                                                                           max_prims, max_depth, threads))
-            _check(lib.hprt_bspnode_build(model._h, prm, C.byref(handle)))
+            handle, self.build_stats = _build_bsp_tree("bspnode", "build", (model._h,), prm, device, min_candidates,
+                                                       (max_edges, max_faces, max_face_edges, 0))
         self._h = handle
 
     @staticmethod
     def from_triangles(p9, accelerator, n_directions=3, seed=BSPNODE_DEFAULT_SEED, isect_cost=80, trav_cost=5, empty_bonus=0.0, max_prims=1,
-                       max_depth=-1, threads=0):
-        """p9: [n, 9] (or [n, 3, 3]) float32 world-space triangle vertices in creation order."""
+                       max_depth=-1, threads=0, device=None, min_candidates=0, max_edges=0, max_faces=0, max_face_edges=0):
+        """p9: [n, 9] (or [n, 3, 3]) float32 world-space triangle vertices in creation order.  device ...: as in the constructor."""
         p9 = np.ascontiguousarray(p9, np.float32).reshape(-1, 9)
-        h = C.c_void_p()
         prm = _bspnode_params(accelerator, False, n_directions, seed, isect_cost, trav_cost, 1, empty_bonus, max_prims, max_depth, threads)
-        _check(lib.hprt_bspnode_build_from_triangles(p9.shape[0], _ptr(p9), C.byref(prm), C.byref(h)))
-        return BspNode(handle=h)
+        h, st = _build_bsp_tree("bspnode", "build_from_triangles", (p9.shape[0], _ptr(p9)), C.byref(prm), device, min_candidates,
+                                (max_edges, max_faces, max_face_edges, 0))
+        return BspNode(handle=h, build_stats=st)
 
 
 class BspNodeKd(BspPaperKd):
     """Node-based BSP tree, fastkd form (host): Create{BSPArbitrary,BSPCluster,BSPRandom}FastKdTreeAccelerator(prims, params) — the
     reference's BSPKd over BSPKdNode, so a BspPaperKd in all but its builder: Scene.attach_bsppaperkd takes it unchanged.
-    Arguments as BspNode's, plus kd_trav_cost."""
+    Arguments as BspNode's (device, min_candidates and the capacities included), plus kd_trav_cost."""
 
     def __init__(self, model=None, accelerator=None, handle=None, n_directions=3, seed=BSPNODE_DEFAULT_SEED, isect_cost=80, trav_cost=5,
-                 kd_trav_cost=1, empty_bonus=0.0, max_prims=1, max_depth=-1, threads=0):
+                 kd_trav_cost=1, empty_bonus=0.0, max_prims=1, max_depth=-1, threads=0, device=None, min_candidates=0, max_edges=0, max_faces=0, max_face_edges=0, build_stats=None):
+        self.build_stats = build_stats
         if handle is None:
-            handle = C.c_void_p()
             prm = None if accelerator is None else C.byref(_bspnode_params(accelerator, True, n_directions, seed, isect_cost, trav_cost, kd_trav_cost,
                                                                           empty_bonus, max_prims, max_depth, threads))
-            _check(lib.hprt_bspnodekd_build(model._h, prm, C.byref(handle)))
+            handle, self.build_stats = _build_bsp_tree("bspnodekd", "build", (model._h,), prm, device, min_candidates,
+                                                       (max_edges, max_faces, max_face_edges, 0))
         self._h = handle
 
     @staticmethod
     def from_triangles(p9, accelerator, n_directions=3, seed=BSPNODE_DEFAULT_SEED, isect_cost=80, trav_cost=5, kd_trav_cost=1, empty_bonus=0.0,
-                       max_prims=1, max_depth=-1, threads=0):
-        """p9: [n, 9] (or [n, 3, 3]) float32 world-space triangle vertices in creation order."""
+                       max_prims=1, max_depth=-1, threads=0, device=None, min_candidates=0, max_edges=0, max_faces=0, max_face_edges=0):
+        """p9: [n, 9] (or [n, 3, 3]) float32 world-space triangle vertices in creation order.  device ...: as in the constructor."""
         p9 = np.ascontiguousarray(p9, np.float32).reshape(-1, 9)
-        h = C.c_void_p()
         prm = _bspnode_params(accelerator, True, n_directions, seed, isect_cost, trav_cost, kd_trav_cost, empty_bonus, max_prims, max_depth, threads)
-        _check(lib.hprt_bspnodekd_build_from_triangles(p9.shape[0], _ptr(p9), C.byref(prm), C.byref(h)))
-        return BspNodeKd(handle=h)
+        h, st = _build_bsp_tree("bspnodekd", "build_from_triangles", (p9.shape[0], _ptr(p9)), C.byref(prm), device, min_candidates,
+                                (max_edges, max_faces, max_face_edges, 0))
+        return BspNodeKd(handle=h, build_stats=st)
 
 
 def bspnode_tree(model, accelerator=None, **kw):
     """The node-based BSP tree of `accelerator` (default: the scene's Accelerator line) and the Scene method that attaches it:
-    (BspNodeKd, "attach_bsppaperkd") for the fastkd forms, (BspNode, "attach_bsppaper") for the others."""
+    (BspNodeKd, "attach_bsppaperkd") for the fastkd forms, (BspNode, "attach_bsppaper") for the others.  kw: the builders' keywords,
+    device=, min_candidates=, max_edges=, max_faces= and max_face_edges= of the device-assisted build among them."""
     name = accelerator if accelerator is not None else model.accelerator
     fastkd = name.endswith("fastkd")
     if not fastkd:

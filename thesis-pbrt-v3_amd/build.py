@@ -17,17 +17,18 @@ HOST_SRCS = ["pbrt_frontend.cpp", "loop_subdiv.cpp", "scene_io.cpp", "texture_io
 # host code built by hipcc without an offload target (no code object): the float operations of the scene layout keep the code
 # generator they had when they sat in capi_device.hip
 HIPCC_HOST_SRCS = ["scene_layout.cpp"]
-HIP_SRCS = ["device/kernels.hip", "device/kd_walk.hip", "device/rbsp_walk.hip", "device/rbspkd_walk.hip", "device/bsppaper_walk.hip", "device/bsppaperkd_walk.hip", "device/kdinst_walk.hip", "device/kdop_cost.hip", "device/rbspinst_walk.hip", "device/bsppaperinst_walk.hip", "device/bsp_cost.hip", "capi_device.hip", "capi_gather.hip"]
+HIP_SRCS = ["device/kernels.hip", "device/kd_walk.hip", "device/rbsp_walk.hip", "device/rbspkd_walk.hip", "device/bsppaper_walk.hip", "device/bsppaperkd_walk.hip", "device/kdinst_walk.hip", "device/kdop_cost.hip", "device/rbspinst_walk.hip", "device/bsppaperinst_walk.hip", "device/bsp_cost.hip", "device/bspnode_cost.hip", "capi_device.hip", "capi_gather.hip"]
 # hipcc names every HIP translation unit by a CUID (the __hip_cuid_* symbol in its code object) that it otherwise hashes from
 # the source's and the object's ABSOLUTE paths, so the code objects — and the sha256 profiles/rNN_counters.json is stamped
 # with — would depend on where the tree is checked out.  Pinned to the values the stamped build derived: the same code
 # objects, byte for byte, from any directory.
-# (device/kd_walk.hip, device/rbsp_walk.hip, device/rbspkd_walk.hip, device/bsppaper_walk.hip, device/bsppaperkd_walk.hip, device/kdinst_walk.hip, device/kdop_cost.hip, device/rbspinst_walk.hip, device/bsppaperinst_walk.hip, device/bsp_cost.hip: values of their own, so that adding them left the other code
+# (device/kd_walk.hip, device/rbsp_walk.hip, device/rbspkd_walk.hip, device/bsppaper_walk.hip, device/bsppaperkd_walk.hip, device/kdinst_walk.hip, device/kdop_cost.hip, device/rbspinst_walk.hip, device/bsppaperinst_walk.hip, device/bsp_cost.hip, device/bspnode_cost.hip: values of their own, so that adding them left the other code
 # objects as they were)
 CUIDS = {"device/kernels.hip": "a6cd736c50efffab", "device/kd_walk.hip": "5c0d2e7f41b3a916", "device/rbsp_walk.hip": "3e91a5c07d2b84f6",
          "device/rbspkd_walk.hip": "7a4f0c2e9b61d385", "device/bsppaper_walk.hip": "c52e8b1d06f3a794",
          "device/bsppaperkd_walk.hip": "e8136d4a9f07c2b5", "device/kdinst_walk.hip": "4d9b27f1a60c8e53", "device/kdop_cost.hip": "b7e20a5c93d1f468",
          "device/rbspinst_walk.hip": "9f3c61d8b2047ae5", "device/bsppaperinst_walk.hip": "2c7e5a90d4b18f63", "device/bsp_cost.hip": "6b1f94c3e7a0d258",
+         "device/bspnode_cost.hip": "d3a7150c8e4f92b6",
          "capi_device.hip": "1b24418c11488d5c", "capi_gather.hip": "89501e8167866ce2"}
 COMMON = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-Wall", "-Wno-unused-function"]
 

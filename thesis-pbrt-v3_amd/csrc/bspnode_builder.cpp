@@ -8,9 +8,12 @@
 // on several threads: each candidate's cost is a pure function of the node's k-DOP, the direction and the candidate, and the
 // reduction keeps the first minimum in the reference's scan order (direction, then edge) — for the fastkd form each of its two
 // minima — so the tree does not depend on the thread count.  The winner's two halves are then cut and measured once more, exactly
-// as the scan left them.
+// as the scan left them.  For the same reason a node's candidates may be costed elsewhere altogether (BspNodeParams::costFn: the
+// device-assisted build, bspnode_cost.h), as long as every cost and fixed cost carries the bits CostOne below would give; what the
+// hook flags is costed here again.
 #include "bspnode_builder.h"
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstring>
 #include <functional>
@@ -26,6 +29,30 @@ namespace {
 using namespace bspbuild;
 
 struct Cand { uint32_t k, i, nBelow, nAbove; float t; };     // direction k's edge i
+static_assert(sizeof(KEdge) == sizeof(kdopcost::Edge) && sizeof(KEdge) == 32, "kdop_cost.h restates KEdge");
+
+// What one candidate's cost reads besides the node, the direction and the candidate
+struct CostConsts {
+    bool fastKd; float invTotalSA, emptyBonus; uint32_t isectCost, traversalCost, kdTraversalCost;
+};
+// One candidate of the scan: costs[k] (and, for a fastkd chosen direction, costsFixed[k]) as the reference's loop body leaves
+// them.  d: the candidate's direction; kdAxis: one of fastkd's three axes.
+void CostOne(const BuildNode &cur, const CostConsts &cc, const float *d, bool kdAxis, uint32_t nBelow, uint32_t nAbove, float t, Scratch &s,
+             std::vector<float> *candDirs, float *cost, float *costFixed) {
+    const float BSP_ALPHA = 0.1;                                     // bspNodeBasedFastKd.cpp:29
+    float areaBelow, areaAbove;
+    CutMeasure(cur, t, d, s, candDirs, &areaBelow, &areaAbove);
+    const float pBelow = areaBelow * cc.invTotalSA;
+    const float pAbove = areaAbove * cc.invTotalSA;
+    const float eb = (nAbove == 0 || nBelow == 0) ? cc.emptyBonus : 0;
+    if (!cc.fastKd) *cost = (float)cc.traversalCost + (float)cc.isectCost * (1 - eb) * (pBelow * (float)nBelow + pAbove * (float)nAbove);
+    else if (kdAxis) *cost = (float)cc.kdTraversalCost + (float)cc.isectCost * (1 - eb) * (pBelow * (float)nBelow + pAbove * (float)nAbove);
+    else {                                               // bspNodeBasedFastKd.cpp:237-239
+        const float costIntersection = (float)cc.isectCost * (1 - eb) * (pBelow * (float)nBelow + pAbove * (float)nAbove);
+        *costFixed = (float)cc.traversalCost + costIntersection;
+        *cost = BSP_ALPHA * (float)cc.isectCost * (float)(cur.nPrimitives - 1) + (float)cc.kdTraversalCost + costIntersection;
+    }
+}
 
 // Primitive::Normal: Triangle::Normal (shapes/triangle.cpp:584-594); every other shape's is (0, 0, 0) (core/shape.h:94-96)
 V PrimNormal(const float *tri9, const uint8_t *isTri, uint32_t pn) {
@@ -159,6 +186,23 @@ bool BspNodeAccelerator(const std::string &name, int *chooser, int *form) {
     return false;
 }
 
+void BspNodeCostVector(const BspNodeCostRequest &rq) {
+    BuildNode cur{0u, rq.sc.nPrimitives, 0u, Mesh(), std::vector<float>(rq.dirs, rq.dirs + 3 * (size_t)rq.M), 0.f, 0, 0u};
+    cur.mesh.resize(rq.nEdges);
+    if (rq.nEdges) std::memcpy(static_cast<void *>(cur.mesh.data()), rq.mesh, (size_t)rq.nEdges * sizeof(KEdge));
+    const CostConsts cc{rq.fastKd, rq.sc.invTotalSA, rq.sc.emptyBonus, rq.sc.isectCost, rq.sc.traversalCost, rq.sc.kdTraversalCost};
+    Scratch s;
+    std::vector<float> candDirs;
+    for (size_t k = 0; k < rq.n; ++k) {
+        const bspnodecost::Cand &c = rq.cands[k];
+        const bspnodecost::SweepDir &sd = rq.sweep[c.k];
+        float fixed = std::numeric_limits<float>::infinity();
+        CostOne(cur, cc, sd.axis, sd.kind != bspnodecost::KIND_CHOSEN, c.nBelow, c.nAbove, c.t, s, &candDirs, &rq.costs[k], &fixed);
+        if (rq.costsFixed) rq.costsFixed[k] = fixed;
+        rq.overflow[k] = 0;
+    }
+}
+
 std::string BspNodeChoose(int chooser, uint32_t K, uint32_t seed, size_t n, const float *tri9, uint32_t draws, std::vector<uint32_t> *counts,
                           std::vector<float> *dirs) {
     const std::vector<uint8_t> isTri(n, 1);
@@ -174,10 +218,7 @@ std::string BspNodeChoose(int chooser, uint32_t K, uint32_t seed, size_t n, cons
     return "";
 }
 
-std::string BuildBspNodeTree(size_t n, const float *bmin, const float *bmax, const float *tri9, const uint8_t *isTri, const BspNodeParams &p,
-                             BspPaperTree *out) {
-    BspPaperTree &t = *out;
-    t = BspPaperTree();
+std::string BspNodeRefuseParams(const BspNodeParams &p) {
     if (p.chooser < BSPNODE_ARBITRARY || p.chooser > BSPNODE_RANDOM || p.form < BSPNODE_PLAIN || p.form > BSPNODE_FASTKD)
         return "unknown direction chooser or tree form";
     const bool withKd = p.form == BSPNODE_WITHKD, fastKd = p.form == BSPNODE_FASTKD;
@@ -188,12 +229,21 @@ std::string BuildBspNodeTree(size_t n, const float *bmin, const float *bmax, con
     if (p.chooser == BSPNODE_CLUSTER && !withKd && !fastKd && p.nDirections < 1)
         return "nbDirections " + std::to_string(p.nDirections) + " is not supported: bspcluster needs at least one direction";
     if (p.nDirections < 0 || p.nDirections > 4096) return "nbDirections " + std::to_string(p.nDirections) + " is not supported";
+    return "";
+}
+
+std::string BuildBspNodeTree(size_t n, const float *bmin, const float *bmax, const float *tri9, const uint8_t *isTri, const BspNodeParams &p,
+                             BspPaperTree *out) {
+    BspPaperTree &t = *out;
+    t = BspPaperTree();
+    const std::string refused = BspNodeRefuseParams(p);
+    if (!refused.empty()) return refused;
+    const bool withKd = p.form == BSPNODE_WITHKD, fastKd = p.form == BSPNODE_FASTKD;
     const uint32_t K = (uint32_t)p.nDirections;
     const uint32_t nFixed = (withKd || fastKd) ? 3u : 0u, Kchosen = K - nFixed;
     // Create...TreeAccelerator / GenericBSP: the parameters as the reference holds them (uint32_t, Float)
     const uint32_t isectCost = (uint32_t)p.isectCost, traversalCost = (uint32_t)p.travCost, maxPrims = (uint32_t)p.maxPrims;
     const uint32_t kdTraversalCost = (uint32_t)p.kdTravCost;
-    const float BSP_ALPHA = 0.1;                                     // bspNodeBasedFastKd.cpp:29
     const float emptyBonus = p.emptyBonus;
     t.kdAware = fastKd;
     const uint32_t off = fastKd ? (uint32_t)BSPPAPERKD_OFF : (uint32_t)BSPPAPER_OFF;
@@ -246,6 +296,9 @@ std::string BuildBspNodeTree(size_t n, const float *bmin, const float *bmax, con
 
     std::vector<Cand> cands;
     std::vector<float> costs, costsFixed;       // costsFixed: fastkd's traversalCost + C_isect of a chosen direction's candidate
+    std::vector<uint8_t> overflow;              // per candidate: the costing hook could not cost it (BspNodeParams::costFn)
+    std::vector<bspnodecost::Cand> hookCands;   // the candidates and the sweep's directions as the hook reads them
+    std::vector<bspnodecost::SweepDir> hookDirs;
     std::vector<V> chosen;
     std::vector<float> nodeDirs;                // the node's directions, 3 floats each: the fixed axes, then the chosen ones
     std::vector<std::vector<float>> candDirs((size_t)nThreads);
@@ -302,26 +355,57 @@ std::string BuildBspNodeTree(size_t n, const float *bmin, const float *bmax, con
             }
         }
         costs.resize(cands.size());
-        if (fastKd) costsFixed.resize(cands.size());
+        if (fastKd) costsFixed.assign(cands.size(), std::numeric_limits<float>::infinity());
+        const CostConsts cc{fastKd, invTotalSA, emptyBonus, isectCost, traversalCost, kdTraversalCost};
         auto costRange = [&](size_t k0, size_t k1, int w) {
-            Scratch &s = scratch[(size_t)w];
             for (size_t k = k0; k < k1; ++k) {
                 const Cand &c = cands[k];
-                float areaBelow, areaAbove;
-                CutMeasure(cur, c.t, &nodeDirs[3 * c.k], s, &candDirs[(size_t)w], &areaBelow, &areaAbove);
-                const float pBelow = areaBelow * invTotalSA;
-                const float pAbove = areaAbove * invTotalSA;
-                const float eb = (c.nAbove == 0 || c.nBelow == 0) ? emptyBonus : 0;
-                if (!fastKd) costs[k] = (float)traversalCost + (float)isectCost * (1 - eb) * (pBelow * (float)c.nBelow + pAbove * (float)c.nAbove);
-                else if (c.k < 3) costs[k] = (float)kdTraversalCost + (float)isectCost * (1 - eb) * (pBelow * (float)c.nBelow + pAbove * (float)c.nAbove);
-                else {                                               // bspNodeBasedFastKd.cpp:237-239
-                    const float costIntersection = (float)isectCost * (1 - eb) * (pBelow * (float)c.nBelow + pAbove * (float)c.nAbove);
-                    costsFixed[k] = (float)traversalCost + costIntersection;
-                    costs[k] = BSP_ALPHA * (float)isectCost * (float)(cur.nPrimitives - 1) + (float)kdTraversalCost + costIntersection;
-                }
+                CostOne(cur, cc, &nodeDirs[3 * c.k], c.k < 3, c.nBelow, c.nAbove, c.t, scratch[(size_t)w], &candDirs[(size_t)w], &costs[k],
+                        fastKd ? &costsFixed[k] : nullptr);
             }
         };
-        if (nThreads > 1 && cands.size() >= kParallelCandidates) {
+        // the costing hook (BspNodeParams::costFn): the node's candidates costed elsewhere, the flagged ones repaired here
+        bool costed = false;
+        if (p.costFn && !cands.empty() && cands.size() >= p.costMinCandidates) {
+            overflow.assign(cands.size(), 0);
+            hookCands.resize(cands.size());
+            for (size_t k = 0; k < cands.size(); ++k) hookCands[k] = bspnodecost::Cand{cands[k].k, cands[k].nBelow, cands[k].nAbove, cands[k].t};
+            hookDirs.resize(nDirs);
+            for (uint32_t k = 0; k < nDirs; ++k)
+                hookDirs[k] = bspnodecost::SweepDir{{nodeDirs[3 * k], nodeDirs[3 * k + 1], nodeDirs[3 * k + 2]},
+                                                    !fastKd ? bspnodecost::KIND_PLAIN : (k < 3 ? bspnodecost::KIND_KD_AXIS : bspnodecost::KIND_CHOSEN)};
+            BspNodeCostRequest rq;
+            rq.mesh = reinterpret_cast<const kdopcost::Edge *>(cur.mesh.data()); rq.nEdges = (uint32_t)cur.mesh.size();
+            rq.dirs = cur.dirs.data(); rq.M = (uint32_t)(cur.dirs.size() / 3);
+            rq.sweep = hookDirs.data(); rq.nDirs = nDirs; rq.fastKd = fastKd;
+            rq.sc = bspcost::Scalars{invTotalSA, emptyBonus, isectCost, traversalCost, kdTraversalCost, cur.nPrimitives, 0u, 0u, 0u, 0u};
+            rq.cands = hookCands.data(); rq.n = cands.size();
+            rq.costs = costs.data(); rq.costsFixed = fastKd ? costsFixed.data() : nullptr; rq.overflow = overflow.data();
+            rq.level = maxDepth - cur.depth;
+            std::string err;
+            const auto t0 = std::chrono::steady_clock::now();
+            const int rc = p.costFn(rq, &err);
+            const double hookSeconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();      // costFn alone, not the repair
+            if (rc < 0) return err.empty() ? std::string("the costing hook failed") : err;
+            if (rc == 0) {
+                costed = true;
+                uint64_t redo = 0;
+                for (size_t k = 0; k < cands.size(); ++k)
+                    if (overflow[k]) {
+                        if (fastKd) costsFixed[k] = std::numeric_limits<float>::infinity();
+                        costRange(k, k + 1, 0); ++redo;
+                    }
+                if (p.stats) {
+                    p.stats->secondsDevice += hookSeconds;
+                    ++p.stats->nodesDevice; p.stats->candidatesDevice += cands.size() - redo; p.stats->candidatesRecosted += redo;
+                }
+                if (p.costDone) p.costDone(rq);
+            }
+        }
+        if (!costed && p.stats) ++p.stats->nodesHost;
+        if (costed) {
+            // (costs[] and costsFixed[] are complete)
+        } else if (nThreads > 1 && cands.size() >= kParallelCandidates) {
             const size_t chunk = (cands.size() + nThreads - 1) / nThreads;
             pool.clear();
             for (int w = 1; w < nThreads; ++w) {

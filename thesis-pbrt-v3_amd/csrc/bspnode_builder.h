@@ -12,8 +12,10 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <functional>
 #include <string>
 #include <vector>
+#include "bspnode_cost.h"
 #include "bsppaper_builder.h"
 
 namespace hprt {
@@ -21,6 +23,22 @@ namespace hprt {
 enum : int { BSPNODE_ARBITRARY = 0, BSPNODE_CLUSTER = 1, BSPNODE_RANDOM = 2 };      // chooseArbitraryNormals, calculateClusterMeans, chooseRandomDirections
 enum : int { BSPNODE_PLAIN = 0, BSPNODE_WITHKD = 1, BSPNODE_FASTKD = 2 };
 enum : uint32_t { BSPNODE_DEFAULT_SEED = 5489u };                                    // std::mt19937::default_seed
+
+// One node's candidates, as costFn sees them (bspnode_cost.h).  mesh / dirs: the node's k-DOP and its own direction list
+// (cur.dirs); sweep: the directions the node sweeps (nodeDirs), each with the kind of its cost formula; cands: every candidate in
+// the scan's (direction, edge) order, k indexing sweep.  nDirs is not always K: arbitrary yields min(np, K) directions, cluster np
+// of them when np <= K, fastkd with K = 3 none besides the axes; two may be equal, and one may be (0, 0, 0) (it has no candidate).
+struct BspNodeCostRequest {
+    const kdopcost::Edge *mesh; uint32_t nEdges;          // face ids below 2 M
+    const float *dirs; uint32_t M;
+    const bspnodecost::SweepDir *sweep; uint32_t nDirs;
+    bool fastKd;
+    bspcost::Scalars sc;
+    const bspnodecost::Cand *cands; size_t n;
+    float *costs, *costsFixed;                            // costsFixed: NULL unless fastKd; +inf except for KIND_CHOSEN
+    uint8_t *overflow;                                    // 1: not costed (a capacity of the costing was exceeded)
+    uint32_t level;                                       // the node's depth below the root (diagnostics)
+};
 
 struct BspNodeParams {
     int chooser = BSPNODE_CLUSTER, form = BSPNODE_PLAIN;
@@ -31,16 +49,35 @@ struct BspNodeParams {
     float emptyBonus = 0.f;               // "emptybonus"
     int maxPrims = 1, maxDepth = -1;      // "maxprims", "maxdepth" (-1: round(2 + 1.6 Log2Int(N)))
     int threads = 0;                      // candidate evaluation threads: 0 = OMP_NUM_THREADS (else 16), at most 16
+    // Optional costing hook (the device-assisted build, hprt_bspnode_build_device), as BspPaperParams has it: a node with at least
+    // costMinCandidates candidates is handed to costFn instead of the thread pool.  It fills costs / costsFixed / overflow for
+    // every candidate and returns 0; returns 1 to decline the node (it takes the host path), < 0 to fail the build with *err.
+    // Flagged candidates are costed again by costRange itself.  The chooser has drawn before costFn is called and costFn draws
+    // nothing, so the tree of a seed is the same either way.
+    std::function<int(const BspNodeCostRequest &, std::string *err)> costFn;
+    uint32_t costMinCandidates = 1024;    // (kdop::kParallelCandidates)
+    BspBuildStats *stats = nullptr;       // filled when costFn is set
+    // Diagnostics: called for a node costFn has handled, after the repair, with the costs the scan is about to read
+    std::function<void(const BspNodeCostRequest &)> costDone;
 };
 
 // "bsparbitrary" ... "bsprandomfastkd" -> chooser and form; false for any other name
 bool BspNodeAccelerator(const std::string &name, int *chooser, int *form);
+
+// Why BuildBspNodeTree refuses these parameters whatever the primitives are (an unknown chooser or form, a K the reference's build
+// is undefined for), or an empty string.  The device-assisted entries ask before they open a device, so that such a build is
+// refused with the host entry's message on every machine.
+std::string BspNodeRefuseParams(const BspNodeParams &p);
 
 // n primitives in creation order, as BuildBspPaperTree takes them.  Returns an empty string, or why the tree cannot be built: where
 // the reference's build is undefined (K < 3 for withkd / fastkd, a drawn index equal to the primitive count, the fastkd case in
 // which only the second minimum is set) and where it would write past its primitive buffer.
 std::string BuildBspNodeTree(size_t n, const float *bmin, const float *bmax, const float *tri9, const uint8_t *isTri, const BspNodeParams &p,
                              BspPaperTree *out);
+
+// The candidates of rq costed with the builder's own code (CutMeasure over the vector meshes and costRange's formulas) on the
+// calling thread: what the diagnostics hook hprt_debug_bspnode_cost calls impl 0.  overflow is cleared.
+void BspNodeCostVector(const BspNodeCostRequest &rq);
 
 // The direction choosers on their own (diagnostics; tests/test_bspnode_host.py): `draws` calls of the chooser over the triangles p9
 // (all n of them are the node's primitives, in order) from one engine seeded with `seed`.  Per call, counts gets the number of

@@ -15,6 +15,7 @@
 #include <type_traits>
 #include "../../include/hprt.h"
 #include "bsp_cost_device.h"
+#include "bspnode_cost_device.h"
 #include "bspnode_builder.h"
 #include "bvh_builder.h"
 #include "halton_tables.h"
@@ -352,10 +353,63 @@ int BspPaperCopy(const BspPaperTree &b, void *nodes20, uint32_t *primIndices) {
 
 // ---- the node-based BSP trees' builds (hprt_bspnode_* and hprt_bspnodekd_* below): Handle HprtBspPaper for the plain and withkd
 // forms, HprtBspPaperKd for the fastkd form; params NULL keeps p (the scene's Accelerator line)
+// What a build does besides the host build (NULL: nothing), as BspHook.  device: the device-assisted build
+// (hprt_bspnode*_build*_device) — nodes of at least min_candidates candidates are costed by k_sweepcost.  sink: the diagnostics hook
+// hprt_debug_bspnode_root_nodes — the first maxNodes costed nodes are handed out with the costs the builder's own code gave.
+struct HprtDebugBspSweepNode {
+    const void *edges; uint32_t n_edges;              // 32-byte records (v1, v2, f1, f2), face ids below 2 M
+    const float *dirs; uint32_t M;                    // the node's own direction list
+    const void *sweep; uint32_t n_dirs;               // 16-byte records (axis, kind): the directions the node sweeps
+    const void *scalars;                              // bspcost::Scalars (10 words)
+    const void *cands; size_t n;                      // 16-byte records (k, nBelow, nAbove, t) in (direction, edge) order
+    const float *costs, *costs_fixed;                 // the builder's own (costs_fixed NULL unless fastkd); NULL as an input
+    uint32_t level;                                   // the node's depth below the root
+};
+typedef void (*BspSweepNodeSink)(void *user, uint32_t node, const HprtDebugBspSweepNode *nd);
+struct BspNodeHook {
+    bool device = false;
+    const HprtBspBuildDeviceOpts *opts = nullptr;
+    HprtBuildDeviceStats *stats = nullptr;
+    BspSweepNodeSink sink = nullptr; void *user = nullptr; uint32_t maxNodes = 0;
+};
+// The node of a request as bspnode_cost.h reads it.  False: the node's own mesh, direction list, faces or sweep exceed the
+// capacities (it is declined whole), or a face id or a candidate's direction is out of range.
+bool BspNodeCompactRequest(const BspNodeCostRequest &rq, const uint32_t cap[4], BspCompact *c) {
+    if (rq.nEdges > cap[0] || rq.M == 0 || rq.M > BSP_MAX_DIRS || rq.nDirs == 0 || rq.nDirs > BSPNODE_MAX_SWEEP_DIRS) return false;
+    for (uint32_t k = 0; k < rq.nEdges; ++k)
+        if (rq.mesh[k].f1 >= 2 * rq.M || rq.mesh[k].f2 >= 2 * rq.M) return false;
+    for (size_t k = 0; k < rq.n; ++k)
+        if (rq.cands[k].k >= rq.nDirs) return false;
+    c->mesh.resize(rq.nEdges); c->cdir.resize(rq.M);
+    bspcost::CompactNode(rq.mesh, rq.nEdges, rq.M, c->mesh.data(), c->cdir.data(), &c->nD);
+    return 2 * c->nD <= cap[1];
+}
+// bspnode_cost.h on the host (the diagnostics hook's impl 1), over storage sized exactly to the capacities in force.  1: declined.
+int BspNodeCostRestated(const BspNodeCostRequest &rq) {
+    uint32_t cap[4];
+    if (!bspcost::Capacities(rq.sc, cap)) return -1;
+    BspCompact cn;
+    if (!BspNodeCompactRequest(rq, cap, &cn)) return 1;
+    std::vector<bspcost::Q> words(4 * (size_t)cap[0] + 2 * (size_t)cap[1]);
+    std::vector<uint8_t> list(cap[2]);
+    bspnodecost::CostNode(cn.mesh.data(), rq.nEdges, rq.dirs, rq.M, cn.cdir.data(), cn.nD, rq.fastKd, rq.sc, rq.sweep, rq.nDirs, rq.cands, rq.n, cap,
+                          words.data(), list.data(), rq.costs, rq.costsFixed, rq.overflow);
+    return 0;
+}
+// k_sweepcost over a request (the device-assisted build, and the diagnostics hook's impl 2).  0, 1 (declined) or -1 with *rc / *err.
+int BspNodeCostOnDevice(BspNodeCostDevice *dev, const uint32_t cap[4], const BspNodeCostRequest &rq, int *rc, std::string *err) {
+    BspCompact cn;
+    if (!BspNodeCompactRequest(rq, cap, &cn)) return 1;
+    *rc = BspNodeCostDeviceRun(dev, cn.mesh.data(), rq.nEdges, rq.dirs, rq.M, cn.cdir.data(), cn.nD, rq.fastKd, rq.sc, rq.sweep, rq.nDirs, rq.cands, rq.n,
+                               rq.costs, rq.costsFixed, rq.overflow, err);
+    return *rc != HPRT_OK ? -1 : 0;
+}
+
 template <typename Handle>
 int BuildBspNode(const char *fn, size_t n, const float *lo, const float *hi, const float *tri9, const uint8_t *isTri, const HprtBspNodeParams *params,
-                 BspNodeParams p, Handle **out) {
+                 BspNodeParams p, Handle **out, const BspNodeHook *hook = nullptr) {
     constexpr bool fastKd = std::is_same<Handle, HprtBspPaperKd>::value;
+    if (hook) *out = nullptr;
     if (params) {
         p.chooser = params->chooser; p.form = params->form; p.nDirections = params->n_directions; p.seed = params->seed;
         p.isectCost = params->isect_cost; p.travCost = params->trav_cost; p.kdTravCost = params->kd_trav_cost; p.emptyBonus = params->empty_bonus;
@@ -366,7 +420,42 @@ int BuildBspNode(const char *fn, size_t n, const float *lo, const float *hi, con
                                                                   : ": takes the plain and withkd forms only (the fastkd form is hprt_bspnodekd_build's)"));
     constexpr uint32_t todoMax = fastKd ? (uint32_t)BSPPAPERKD_TODO_MAX : (uint32_t)BSPPAPER_TODO_MAX;
     std::unique_ptr<Handle> t(new Handle());
+    struct DeviceGuard { BspNodeCostDevice *d = nullptr; ~DeviceGuard() { BspNodeCostDeviceDestroy(d); } } dev;      // freed when the build ends or fails
+    BspBuildStats bs;
+    int hookRc = HPRT_OK;
+    uint32_t seen = 0, cap[4] = {0, 0, 0, 0};
+    if (hook && hook->device) {
+        if (hook->stats) *hook->stats = HprtBuildDeviceStats{0, 0, 0, 0, 0.0};
+        // the refusals that do not depend on the primitives come first, as the host entry gives them, with or without a device
+        const std::string refused = BspNodeRefuseParams(p);
+        if (!refused.empty()) return SetError(HPRT_E_UNSUPPORTED, refused);
+        const HprtBspBuildDeviceOpts *o = hook->opts;
+        const uint32_t asked[3] = {o ? o->max_edges : 0u, o ? o->max_faces : 0u, o ? o->max_face_edges : 0u};      // (max_stack: no BVH here)
+        std::string derr;
+        const int rc = BspNodeCostDeviceCreate(o ? o->device : 0, asked, &dev.d, &derr);
+        if (rc != HPRT_OK) return SetError(rc, derr);
+        bspcost::Scalars sc{};
+        sc.maxEdges = asked[0]; sc.maxFaces = asked[1]; sc.maxFaceEdges = asked[2];
+        bspcost::Capacities(sc, cap);
+        p.costMinCandidates = o && o->min_candidates ? o->min_candidates : kDeviceMinCandidates;
+        p.stats = &bs;
+        p.costFn = [&](const BspNodeCostRequest &rq, std::string *e) -> int { return BspNodeCostOnDevice(dev.d, cap, rq, &hookRc, e); };
+    } else if (hook && hook->sink) {
+        p.costMinCandidates = 1;
+        p.costFn = [&](const BspNodeCostRequest &rq, std::string *) -> int {
+            if (seen >= hook->maxNodes) return 1;
+            memset(rq.overflow, 1, rq.n);          // every candidate "flagged": the builder costs them all with its own code
+            return 0;
+        };
+        p.costDone = [&](const BspNodeCostRequest &rq) {
+            const HprtDebugBspSweepNode nd{rq.mesh, rq.nEdges, rq.dirs, rq.M, rq.sweep, rq.nDirs, &rq.sc, rq.cands, rq.n, rq.costs, rq.costsFixed, rq.level};
+            hook->sink(hook->user, seen++, &nd);
+        };
+    }
     const std::string err = BuildBspNodeTree(n, lo, hi, tri9, isTri, p, &t->tree);
+    if (hook && hook->stats)
+        *hook->stats = HprtBuildDeviceStats{bs.nodesDevice, bs.candidatesDevice, bs.candidatesRecosted, bs.nodesHost, bs.secondsDevice};
+    if (hookRc != HPRT_OK) return SetError(hookRc, err);
     if (!err.empty()) return SetError(HPRT_E_UNSUPPORTED, err);
     if (t->tree.depth > todoMax)
         return SetError(HPRT_E_UNSUPPORTED, "node-based BSP tree of depth " + std::to_string(t->tree.depth) + " is deeper than the device walk's todo list (" +
@@ -375,8 +464,9 @@ int BuildBspNode(const char *fn, size_t n, const float *lo, const float *hi, con
     return HPRT_OK;
 }
 template <typename Handle>
-int BuildBspNodeFromModel(const char *fn, const HprtModel *m, const HprtBspNodeParams *params, Handle **out) {
+int BuildBspNodeFromModel(const char *fn, const HprtModel *m, const HprtBspNodeParams *params, Handle **out, const BspNodeHook *hook = nullptr) {
     if (!m || !out) return SetError(HPRT_E_INVALID, std::string(fn) + ": null argument");
+    if (hook) *out = nullptr;
     if (m->sc.nObjects != 0 || !m->sc.instances.empty())
         return SetError(HPRT_E_UNSUPPORTED, "node-based BSP trees over object instances are not supported (the scene keeps its BVH)");
     BspNodeParams p = m->sc.opt.bspnode;
@@ -385,16 +475,17 @@ int BuildBspNodeFromModel(const char *fn, const HprtModel *m, const HprtBspNodeP
     std::vector<float> lo, hi, tri9;
     std::vector<uint8_t> isTri;
     RbspModelPrims(m, &lo, &hi, &tri9, &isTri);
-    return BuildBspNode(fn, lo.size() / 3, lo.data(), hi.data(), tri9.data(), isTri.data(), params, p, out);
+    return BuildBspNode(fn, lo.size() / 3, lo.data(), hi.data(), tri9.data(), isTri.data(), params, p, out, hook);
 }
 template <typename Handle>
-int BuildBspNodeFromTriangles(const char *fn, size_t n, const float *p9, const HprtBspNodeParams *params, Handle **out) {
+int BuildBspNodeFromTriangles(const char *fn, size_t n, const float *p9, const HprtBspNodeParams *params, Handle **out, const BspNodeHook *hook = nullptr) {
     if (!out || !params || (n && !p9)) return SetError(HPRT_E_INVALID, std::string(fn) + ": null argument");
+    if (hook) *out = nullptr;
     if (n > 0x0fffffffull) return SetError(HPRT_E_UNSUPPORTED, "more than 2^28 primitives");
     std::vector<float> lo, hi;
     RbspTriangleBounds(n, p9, &lo, &hi);
     std::vector<uint8_t> isTri(n, 1);
-    return BuildBspNode(fn, n, lo.data(), hi.data(), p9, isTri.data(), params, BspNodeParams(), out);
+    return BuildBspNode(fn, n, lo.data(), hi.data(), p9, isTri.data(), params, BspNodeParams(), out, hook);
 }
 
 // ---- trees given as arrays (the hprt_debug_*_from_arrays hooks below): what a builder would have filled in, then the builder's own
@@ -1260,6 +1351,100 @@ int hprt_bspnodekd_build(const HprtModel *m, const HprtBspNodeParams *params, Hp
 } catch (...) { return hprt::HandleException(); }
 int hprt_bspnodekd_build_from_triangles(size_t n, const float *p9, const HprtBspNodeParams *params, HprtBspPaperKd **out) try {
     return BuildBspNodeFromTriangles("hprt_bspnodekd_build_from_triangles", n, p9, params, out);
+} catch (...) { return hprt::HandleException(); }
+// ---- the device-assisted builds: the same builder with its candidates costed by k_sweepcost (device/bspnode_cost.hip) ----
+int hprt_bspnode_build_device(const HprtModel *m, const HprtBspNodeParams *params, const HprtBspBuildDeviceOpts *opts, HprtBuildDeviceStats *stats,
+                              HprtBspPaper **out) try {
+    BspNodeHook h; h.device = true; h.opts = opts; h.stats = stats;
+    return BuildBspNodeFromModel("hprt_bspnode_build_device", m, params, out, &h);
+} catch (...) { return hprt::HandleException(); }
+int hprt_bspnode_build_from_triangles_device(size_t n, const float *p9, const HprtBspNodeParams *params, const HprtBspBuildDeviceOpts *opts,
+                                             HprtBuildDeviceStats *stats, HprtBspPaper **out) try {
+    BspNodeHook h; h.device = true; h.opts = opts; h.stats = stats;
+    return BuildBspNodeFromTriangles("hprt_bspnode_build_from_triangles_device", n, p9, params, out, &h);
+} catch (...) { return hprt::HandleException(); }
+int hprt_bspnodekd_build_device(const HprtModel *m, const HprtBspNodeParams *params, const HprtBspBuildDeviceOpts *opts, HprtBuildDeviceStats *stats,
+                                HprtBspPaperKd **out) try {
+    BspNodeHook h; h.device = true; h.opts = opts; h.stats = stats;
+    return BuildBspNodeFromModel("hprt_bspnodekd_build_device", m, params, out, &h);
+} catch (...) { return hprt::HandleException(); }
+int hprt_bspnodekd_build_from_triangles_device(size_t n, const float *p9, const HprtBspNodeParams *params, const HprtBspBuildDeviceOpts *opts,
+                                               HprtBuildDeviceStats *stats, HprtBspPaperKd **out) try {
+    BspNodeHook h; h.device = true; h.opts = opts; h.stats = stats;
+    return BuildBspNodeFromTriangles("hprt_bspnodekd_build_from_triangles_device", n, p9, params, out, &h);
+} catch (...) { return hprt::HandleException(); }
+// Diagnostics hooks of the node-based candidate costing (not part of include/hprt.h; tests/bspnode_cost_nodes.py).
+// hprt_debug_bspnode_root_nodes hands out the first max_nodes nodes a build costs, in build order: mesh, the node's directions, the
+// sweep's directions and the candidates, with the costs the builder's own code gave them.  m != NULL: the model's primitives; else n
+// triangles.  The form in params selects the handle.  The pointers are valid during the call only.
+__attribute__((visibility("default"))) int hprt_debug_bspnode_root_nodes(const HprtModel *m, size_t n, const float *p9, const HprtBspNodeParams *params,
+                                                                          uint32_t max_nodes, BspSweepNodeSink sink, void *user) try {
+    if (!params || !sink) return SetError(HPRT_E_INVALID, "hprt_debug_bspnode_root_nodes: null argument");
+    BspNodeHook h; h.sink = sink; h.user = user; h.maxNodes = max_nodes;
+    const char *fn = "hprt_debug_bspnode_root_nodes";
+    int rc;
+    if (params->form == BSPNODE_FASTKD) {
+        HprtBspPaperKd *t = nullptr;
+        rc = m ? BuildBspNodeFromModel(fn, m, params, &t, &h) : BuildBspNodeFromTriangles(fn, n, p9, params, &t, &h);
+        delete t;
+    } else {
+        HprtBspPaper *t = nullptr;
+        rc = m ? BuildBspNodeFromModel(fn, m, params, &t, &h) : BuildBspNodeFromTriangles(fn, n, p9, params, &t, &h);
+        delete t;
+    }
+    return rc;
+} catch (...) { return hprt::HandleException(); }
+// hprt_debug_bspnode_cost costs a node again with impl 0 (the vector code of bsp_build.h, BspNodeCostVector), 1 (bspnode_cost.h on
+// the host) or 2 (k_sweepcost).  nd: a node as the sink above receives it (costs / costs_fixed are not read; the scalars' capacity
+// fields may lower the compiled capacities).  Everything the costing indexes by is checked first (HPRT_E_INVALID): M, every face id,
+// every direction's kind against fastkd, every candidate's direction, the capacities.  *declined is 1 when impl 1 / 2 decline
+// the node whole (its own mesh, faces, direction list or sweep beyond a capacity); every candidate then comes back flagged.
+__attribute__((visibility("default"))) int hprt_debug_bspnode_cost(const HprtDebugBspSweepNode *nd, int fastkd, int impl, float *costs, float *costs_fixed,
+                                                                    uint8_t *overflow, int *declined) try {
+    using namespace bspnodecost;
+    const char *fn = "hprt_debug_bspnode_cost: ";
+    if (!nd || !costs || !costs_fixed || !overflow || !declined || !nd->scalars || !nd->dirs || !nd->sweep || (nd->n && !nd->cands) || (nd->n_edges && !nd->edges))
+        return SetError(HPRT_E_INVALID, std::string(fn) + "null argument");
+    if (impl < 0 || impl > 2) return SetError(HPRT_E_INVALID, std::string(fn) + "impl is not 0, 1 or 2");
+    if (nd->M == 0 || nd->M > 65536u || nd->n_edges > 65536u || nd->n > 0x7fffffffull || nd->n_dirs == 0 || nd->n_dirs > 4096u)
+        return SetError(HPRT_E_INVALID, std::string(fn) + "a size that cannot be real");
+    Scalars sc;
+    memcpy(&sc, nd->scalars, sizeof(sc));
+    uint32_t cap[4];
+    if (!bspcost::Capacities(sc, cap)) return SetError(HPRT_E_INVALID, std::string(fn) + "a capacity field may only lower the compiled capacity");
+    std::vector<Edge> mesh(nd->n_edges);
+    if (nd->n_edges) memcpy(static_cast<void *>(mesh.data()), nd->edges, (size_t)nd->n_edges * sizeof(Edge));
+    for (const Edge &e : mesh)
+        if (e.f1 >= 2 * nd->M || e.f2 >= 2 * nd->M) return SetError(HPRT_E_INVALID, std::string(fn) + "a face id is not below 2 M");
+    std::vector<SweepDir> sweep(nd->n_dirs);
+    memcpy(static_cast<void *>(sweep.data()), nd->sweep, (size_t)nd->n_dirs * sizeof(SweepDir));
+    for (const SweepDir &sd : sweep)
+        if (fastkd ? (sd.kind != KIND_KD_AXIS && sd.kind != KIND_CHOSEN) : sd.kind != KIND_PLAIN)
+            return SetError(HPRT_E_INVALID, std::string(fn) + "a direction's kind is not one of the tree form's");
+    std::vector<Cand> cs(nd->n);
+    if (nd->n) memcpy(static_cast<void *>(cs.data()), nd->cands, nd->n * sizeof(Cand));
+    for (const Cand &c : cs)
+        if (c.k >= nd->n_dirs) return SetError(HPRT_E_INVALID, std::string(fn) + "a candidate's direction is not one of the sweep's");
+    for (size_t k = 0; k < nd->n; ++k) { costs[k] = 0; costs_fixed[k] = std::numeric_limits<float>::infinity(); overflow[k] = 1; }
+    *declined = 0;
+    const BspNodeCostRequest rq{mesh.data(), nd->n_edges, nd->dirs, nd->M, sweep.data(), nd->n_dirs, fastkd != 0, sc, cs.data(), nd->n, costs,
+                                fastkd ? costs_fixed : nullptr, overflow, 0u};
+    int rc = 0;
+    if (impl == 0) BspNodeCostVector(rq);
+    else if (impl == 1) rc = BspNodeCostRestated(rq);
+    else {
+        struct DeviceGuard { BspNodeCostDevice *d = nullptr; ~DeviceGuard() { BspNodeCostDeviceDestroy(d); } } dev;
+        std::string err;
+        const uint32_t asked[3] = {sc.maxEdges, sc.maxFaces, sc.maxFaceEdges};
+        int drc = BspNodeCostDeviceCreate(0, asked, &dev.d, &err);
+        if (drc != HPRT_OK) return SetError(drc, err);
+        rc = BspNodeCostOnDevice(dev.d, cap, rq, &drc, &err);
+        if (rc < 0) return SetError(drc, err);
+    }
+    if (rc == 1) { *declined = 1; return HPRT_OK; }
+    for (size_t k = 0; k < nd->n; ++k)
+        if (overflow[k]) { costs[k] = 0; costs_fixed[k] = std::numeric_limits<float>::infinity(); }
+    return HPRT_OK;
 } catch (...) { return hprt::HandleException(); }
 // Diagnostics hooks (not part of include/hprt.h; tests/test_bspnode_host.py).  hprt_debug_bspnode_choose: `draws` calls of a
 // direction chooser over the triangles p9 from one engine seeded with `seed`; counts[k] = directions of call k, dirs their
