@@ -788,7 +788,7 @@ typedef struct HprtRenderStats {
  * buffers over GPUs (RCCL reduce) reproduces the single-GPU film exactly. */
 int hprt_render(HprtScene *s, const HprtRenderDesc *desc, float *d_film_xyzw, void *stream, HprtRenderStats *stats);
 /* Optional: allocate everything the coming hprt_render(s, desc, ...) needs in HBM now (the wavefront workspace is
- * ~413 B per path of a batch: 111 GB for the 256 M-path batches of a 700x700, 1,024 spp frame), so that a host that
+ * ~365 B per path of a batch: 98 GB for the 256 M-path batches of a 700x700, 1,024 spp frame), so that a host that
  * renders once (pbrt does: Integrator::Render, core/api.cpp:1851) pays the allocation at scene load — next to
  * BVHAccel's own node allocation (accelerators/bvh.cpp:181) — not inside Render().  A later render with a
  * description that needs more simply grows the buffers. */

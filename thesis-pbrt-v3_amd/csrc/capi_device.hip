@@ -53,17 +53,19 @@ struct Workspace {
     float4 *Lfinal;
 };
 // 16-byte words per stream index: 2 x (ray a,b + beta + L) + hit a + shadow a,b + mis a,b + misHit a
-// + pendLight/Mis/Beta + Lfinal; plus b2 + instance of the path hit and of the MIS hit (8 B each), occluded (1 B) and alignment slack
-const size_t kPlaneBytesPerSlot = 16 * (2 * 4 + 1 + 2 + 2 + 1 + 3 + 1) + 8 + 8 + 1;
-size_t PlaneBytes(size_t n) { return n * kPlaneBytesPerSlot + 32 * 256; }
+// + pendLight/Mis/Beta + Lfinal; plus occluded (1 B) and alignment slack.  A render reads the second word of a hit record
+// ({t, instance}, HitStream::b) for the instance alone, so only scenes with object instances get those planes (8 B each, path hit and MIS hit).
+const size_t kPlaneBytesPerSlot = 16 * (2 * 4 + 1 + 2 + 2 + 1 + 3 + 1) + 1, kInstancePlaneBytesPerSlot = 8 + 8;
+size_t PlaneBytesPerSlot(bool instances) { return kPlaneBytesPerSlot + (instances ? kInstancePlaneBytesPerSlot : 0); }
+size_t PlaneBytes(size_t n, bool instances) { return n * PlaneBytesPerSlot(instances) + 32 * 256; }
 
-void CarvePlanes(char *base, size_t n, Workspace *w) {
+void CarvePlanes(char *base, size_t n, bool instances, Workspace *w) {
     PlaneAllocator a{base, 0, 0};
     auto rays = [&](RayStream &r) { r.a = a.take<float4>(n); r.b = a.take<float4>(n); };
     for (int k = 0; k < 2; ++k) { rays(w->path[k].ray); w->path[k].beta = a.take<float4>(n); w->path[k].L = a.take<float4>(n); }
-    w->hit.a = a.take<float4>(n); w->hit.b = a.take<float2>(n);
+    w->hit.a = a.take<float4>(n); w->hit.b = instances ? a.take<float2>(n) : nullptr;
     rays(w->vs.shadow); w->vs.occluded = a.take<uint8_t>(n);
-    rays(w->vs.mis); w->vs.misHit.a = a.take<float4>(n); w->vs.misHit.b = a.take<float2>(n);      // (b2: the emitter's shading normal at a triangle light)
+    rays(w->vs.mis); w->vs.misHit.a = a.take<float4>(n); w->vs.misHit.b = instances ? a.take<float2>(n) : nullptr;
     w->vs.pendLight = a.take<float4>(n); w->vs.pendMis = a.take<float4>(n); w->vs.pendBeta = a.take<float4>(n);
     w->Lfinal = a.take<float4>(n);
 }
@@ -851,10 +853,10 @@ static int TraceHost(HprtScene *s, bool anyHit, size_t n, const float *o, const 
         HIP_TRY(hipMemcpy(ha.data(), hits.a, 16 * n, hipMemcpyDeviceToHost));
         HIP_TRY(hipMemcpy(hb.data(), hits.b, 8 * n, hipMemcpyDeviceToHost));
         for (size_t i = 0; i < n; ++i) {
-            if (t_out) t_out[i] = ha[i].x;
-            if (prim_out) { int32_t w; memcpy(&w, &ha[i].y, 4); prim_out[i] = hit_prim(w); }
-            if (inst_out) memcpy(&inst_out[i], &hb[i].y, 4);
-            if (bary_out) { bary_out[3 * i] = ha[i].z; bary_out[3 * i + 1] = ha[i].w; bary_out[3 * i + 2] = hb[i].x; }
+            if (t_out) t_out[i] = hit_t(hb[i]);
+            if (prim_out) prim_out[i] = hit_prim(hit_word(ha[i]));
+            if (inst_out) inst_out[i] = hit_inst(hb[i]);
+            if (bary_out) { bary_out[3 * i] = hit_b0(ha[i]); bary_out[3 * i + 1] = hit_b1(ha[i]); bary_out[3 * i + 2] = hit_b2(ha[i]); }
         }
     } else {
         DevBuf outOcc;
@@ -1021,8 +1023,9 @@ int RunBatch(HprtScene *s, hipStream_t st, const RenderParams &rpIn, const Works
 // words of s->queues per path: two QueueSets of four index queues, the deferral indices (BinSet::aux) and five bins of 8-byte entries
 constexpr size_t kQueueWordsPerSlot = 8 + 1 + 2 * N_BINS;
 int EnsureWorkspace(HprtScene *s, size_t nSlots, Workspace *ps, QueueSet *qa, QueueSet *qb, BinSet *bins) {
-    HIP_TRY(s->planes.alloc(PlaneBytes(nSlots)));
-    CarvePlanes(s->planes.as<char>(), nSlots, ps);
+    const bool instances = s->dev.nInstances != 0u;
+    HIP_TRY(s->planes.alloc(PlaneBytes(nSlots, instances)));
+    CarvePlanes(s->planes.as<char>(), nSlots, instances, ps);
     HIP_TRY(s->queues.alloc(kQueueWordsPerSlot * nSlots * sizeof(uint32_t) + 4096));
     HIP_TRY(s->queueCounts.alloc(2048 * sizeof(uint32_t)));
     uint32_t *qbase = s->queues.as<uint32_t>(), *cbase = s->queueCounts.as<uint32_t>();
@@ -1062,7 +1065,7 @@ int ChooseBatch(HprtScene *s, int32_t sppChunk, uint32_t nPix, uint32_t spp, uin
         size_t freeB = 0, totalB = 0;
         HIP_TRY(hipMemGetInfo(&freeB, &totalB));
         freeB += s->planes.bytes + s->queues.bytes;                 // this scene's previous workspace is reused or released
-        const size_t perPath = kPlaneBytesPerSlot + kQueueWordsPerSlot * sizeof(uint32_t);
+        const size_t perPath = PlaneBytesPerSlot(s->dev.nInstances != 0u) + kQueueWordsPerSlot * sizeof(uint32_t);
         static const size_t capM = [] { const char *e = getenv("HPRT_BATCH_MPATHS"); return e ? (size_t)atoi(e) : (size_t)256; }();
         const size_t budget = std::min<size_t>(capM << 20, std::max<size_t>(freeB / 2 / perPath, 1ull << 20));
         chunk = std::max<uint32_t>(1u, (uint32_t)(budget / std::max<uint32_t>(nPix, 1u)));
@@ -1118,8 +1121,8 @@ int hprt_render(HprtScene *s, const HprtRenderDesc *desc, float *d_film_xyzw, vo
     const size_t lallBytes = 3ull * spp * nPix * sizeof(float);
     if (lallBytes > (96ull << 30)) return SetError(HPRT_E_UNSUPPORTED, "per-sample radiance store would exceed 96 GiB; render in several tile ranges");
     // Paths per wavefront batch.  Every launch ends with a tail of half-empty waves and every bounce with a host
-    // read-back, so batches are as large as memory allows: up to 256 M paths (413 B per path of streams and queues = 111 GB
-    // of the 288 GB), less if the device has less free (half of what is free now), and of EQUAL size (1,024 spp of the atrium:
+    // read-back, so batches are as large as memory allows: up to 256 M paths (365 B per path of streams and queues = 98 GB of the 288 GB;
+    // 381 B with object instances), less if the device has less free (half of what is free now), and of EQUAL size (1,024 spp of the atrium:
     // two batches of 512 instead of 522 + 502 or, at the old 128 M cap, four of 256: -1 % per frame).  killeroo-simple
     // at 256 spp is one batch of 125 M paths: 6.5 % faster than two batches of 64 M.  (HPRT_BATCH_MPATHS changes the cap.)
     uint32_t chunk = 0;
@@ -1288,8 +1291,8 @@ int hprt_render(HprtScene *s, const HprtRenderDesc *desc, float *d_film_xyzw, vo
     return HPRT_OK;
 } catch (...) { return hprt::HandleException(); }
 
-// Pays for the coming hprt_render(s, desc, ...) at load time: the wavefront workspace (path streams and queues: ~413 B per path of
-// a batch, 111 GB for a 256 M-path batch) and the per-sample radiance store are allocated now, so that the render itself starts
+// Pays for the coming hprt_render(s, desc, ...) at load time: the wavefront workspace (path streams and queues: ~365 B per path of
+// a batch, 98 GB for a 256 M-path batch) and the per-sample radiance store are allocated now, so that the render itself starts
 // with its first kernel.  (A fresh process gets 100 GB in under a millisecond, but right after another process released as much the
 // driver may spend seconds reclaiming it inside hipMalloc — DESIGN.md §7; a pbrt host renders once and would pay that inside Render().)
 int hprt_scene_reserve(HprtScene *s, const HprtRenderDesc *desc) try {

@@ -229,8 +229,7 @@ __device__ __forceinline__ void bspinst_walk(const DevScene &sc, const uint2 *no
                                                     KD_SHARE ? kdCnt - kdSnap : 0u);
         if (ANY_HIT) occ[slot] = hit ? 1 : 0;
         else {
-            hits.a[slot] = make_float4(rayTMax, __int_as_float(hit ? prim : -1), hb0, hb1);
-            if (hits.b) hits.b[slot] = make_float2(hb2, __int_as_float(hit ? hitInst : -1));
+            hit_store(hits, slot, hit ? prim : -1, hb0, hb1, hb2, rayTMax, hit ? hitInst : -1);
         }
     }
     if (COUNT) wave_count_add(counters, ANY_HIT, cnt);

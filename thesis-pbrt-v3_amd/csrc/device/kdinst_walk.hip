@@ -233,8 +233,7 @@ __global__ __launch_bounds__(HPRT_KDINST_BLOCK, QUAD ? HPRT_KDINST_QUAD_WAVES : 
         if (COUNT && rayStats) rayStats[slot] = make_uint4(cnt.entered - snap.entered, cnt.leaf - snap.leaf, (cnt.tri + cnt.sphere) - (snap.tri + snap.sphere), 0u);
         if (ANY_HIT) occ[slot] = hit ? 1 : 0;
         else {
-            hits.a[slot] = make_float4(rayTMax, __int_as_float(hit ? prim : -1), hb0, hb1);
-            if (hits.b) hits.b[slot] = make_float2(hb2, __int_as_float(hit ? hitInst : -1));
+            hit_store(hits, slot, hit ? prim : -1, hb0, hb1, hb2, rayTMax, hit ? hitInst : -1);
         }
     }
     if (COUNT) wave_count_add(counters, ANY_HIT, cnt);

@@ -16,7 +16,29 @@ namespace hprt {
 // (in ascending runs, one per workgroup), so gathers stay almost sequential however thin the
 // paths become.
 struct RayStream { float4 *a, *b; };                 // a = {o.xyz, tMax}   b = {d.xyz, aux}
-struct HitStream { float4 *a; float2 *b; };           // a = {t, prim, b0, b1}   b = {b2, instance or -1}; b may be null
+// A closest hit is ONE 16-byte word: everything shading needs of a hit in a scene without object instances.  `word` is the hit's
+// primitive word (dev_scene.h: primitive index, shading bin in the high bits; negative: the ray escaped).  b carries what only some
+// callers read — the ray-call entry points return t, scenes with object instances need the instance — and is null for everybody else
+// (kernel-uniform): an accepted hit is then one store in the walk and one gather in k_shade.
+struct HitStream { float4 *a; float2 *b; };           // a = {b0, b1, b2, word}   b = {t, instance or -1}; b may be null
+// The layout lives in these helpers alone: every writer stores through hit_store / hit_store_miss, every reader loads a record
+// (hit_load, hit_load_aux) and names its fields through the accessors.
+__device__ __forceinline__ void hit_store(const HitStream &h, uint32_t slot, int32_t word, float b0, float b1, float b2, float t, int32_t inst) {
+    h.a[slot] = make_float4(b0, b1, b2, __int_as_float(word));
+    if (h.b) h.b[slot] = make_float2(t, __int_as_float(inst));
+}
+// (t of a miss: the ray's tMax, as Aggregate::Intersect leaves it)
+__device__ __forceinline__ void hit_store_miss(const HitStream &h, uint32_t slot, float tMax) { hit_store(h, slot, -1, 0.f, 0.f, 0.f, tMax, -1); }
+__device__ __forceinline__ float4 hit_load(const HitStream &h, uint32_t slot) { return h.a[slot]; }
+__device__ __forceinline__ float2 hit_load_aux(const HitStream &h, uint32_t slot) { return h.b[slot]; }      // (h.b non-null)
+__device__ __forceinline__ float2 hit_no_aux() { return make_float2(0.f, __int_as_float(-1)); }               // what a scene without instances would hold
+// (the accessors also serve records copied to the host: TraceHost)
+__host__ __device__ __forceinline__ int32_t hit_word(const float4 &rec) { return __builtin_bit_cast(int32_t, rec.w); }
+__host__ __device__ __forceinline__ float hit_b0(const float4 &rec) { return rec.x; }
+__host__ __device__ __forceinline__ float hit_b1(const float4 &rec) { return rec.y; }
+__host__ __device__ __forceinline__ float hit_b2(const float4 &rec) { return rec.z; }
+__host__ __device__ __forceinline__ float hit_t(const float2 &aux) { return aux.x; }
+__host__ __device__ __forceinline__ int32_t hit_inst(const float2 &aux) { return __builtin_bit_cast(int32_t, aux.y); }
 struct PathStream {
     RayStream ray;          // current path segment; ray.b.w = sampler dimension (bits 0-15) | bounces (bits 16-30) | the segment left a specular lobe (bit 31)
     float4 *beta;           // {beta.rgb, path id}   path id = sampleInBatch * nPix + pixel
@@ -25,7 +47,7 @@ struct PathStream {
 // What a shading pass leaves for the rest of its bounce, indexed like its output PathStream
 struct VertexStreams {
     RayStream shadow; uint8_t *occluded;             // shadow ray of the light sample, its any-hit result
-    RayStream mis; HitStream misHit;                 // BSDF-sampled MIS ray, its closest hit (b2 unused)
+    RayStream mis; HitStream misHit;                 // BSDF-sampled MIS ray, its closest hit (k_resolve: word, barycentrics)
     // A vertex with an MIS ray — every vertex with a pending term where RenderParams::speculate is off — is a FULL vertex: it leaves the
     // three pending streams and a resolve entry, and k_resolve adds its direct lighting once the rays are traced.
     float4 *pendLight;      // {light-sampling term rgb, info}   info: light number | bit30 shadow ray issued | bit31 MIS ray issued

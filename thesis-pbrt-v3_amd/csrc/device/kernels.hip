@@ -122,8 +122,8 @@ __device__ __forceinline__ void block_append(BlockAppendLds *lds, uint32_t *cons
 // parked leaf has been processed, so every later test sees the shrunken tMax exactly as in
 // the reference.
 //
-// queue == nullptr means "slot = ray index".  Closest hit writes {t, prim (ordered index or
-// -1), b0, b1} and b2; any hit writes one byte.
+// queue == nullptr means "slot = ray index".  Closest hit writes one hit record through hit_store
+// (kernels.h: {b0, b1, b2, prim word or -1}, and {t, instance} where hits.b exists); any hit writes one byte.
 // ---------------------------------------------------------------------------
 // Scheduling knobs of the persistent walk (defaults from a per-ray trace simulation of
 // killeroo-simple bounce rays; overridable through HPRT_TRACE_TUNE / HPRT_TRACE_TUNE_ANY =
@@ -317,7 +317,7 @@ __global__ __launch_bounds__(HPRT_TRACE_BLOCK, MODE == 0 ? (QUAD ? (ANY_HIT ? HP
         for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
             const uint32_t s = queue ? queue[i] : i;
             if (ANY_HIT) occ[s] = 0;
-            else { hits.a[s] = make_float4(rays.a[s].w, __int_as_float(-1), 0.f, 0.f); if (hits.b) hits.b[s] = make_float2(0.f, __int_as_float(-1)); }
+            else hit_store_miss(hits, s, hits.b ? rays.a[s].w : 0.f);
         }
     }
     while (true) {
@@ -599,8 +599,7 @@ __global__ __launch_bounds__(HPRT_TRACE_BLOCK, MODE == 0 ? (QUAD ? (ANY_HIT ? HP
                 if (COUNT && rayStats) rayStats[slot] = make_uint4(cnt.entered - snapEntered - (cnt.leaf - snapLeaf), cnt.leaf - snapLeaf, cnt.tri + cnt.sphere - snapPrim, 0u);
                 if (ANY_HIT) occ[slot] = hit ? 1 : 0;
                 else {
-                    hits.a[slot] = make_float4(rayTMax, __int_as_float(hit ? prim : -1), hb0, hb1);
-                    if (hits.b) hits.b[slot] = make_float2(hb2, __int_as_float(INST && hit ? hitInst : -1));
+                    hit_store(hits, slot, hit ? prim : -1, hb0, hb1, hb2, rayTMax, INST && hit ? hitInst : -1);
                 }
                 active = false;
             }
@@ -929,8 +928,7 @@ void k_walk4(DevScene sc, const uint32_t *queue, const uint32_t *countPtr, uint3
                                         // the record goes out now (a closer hit overwrites it): four registers fewer to carry through the walk, which is
                                         // what lets this kernel run six waves per SIMD; a ray that ends without a hit writes its miss record when it retires
                                         hit = true; rayTMax = t;
-                                        hits.a[slot] = make_float4(t, __int_as_float((int32_t)(pi | ((tag & TAG_BIN_MASK) << 24))), b0, b1);
-                                        if (hits.b) hits.b[slot] = make_float2(b2, __int_as_float(INST ? inst : -1));
+                                        hit_store(hits, slot, (int32_t)(pi | ((tag & TAG_BIN_MASK) << 24)), b0, b1, b2, t, INST ? inst : -1);
                                         if (INST) instHit = inst >= 0;
                                     }
                                     if (tag & TAG_LAST) leave = true; else cur = (int)((~(pi + 1u)) & ~WIDE_LEAF_FIRST);
@@ -1020,8 +1018,7 @@ void k_walk4(DevScene sc, const uint32_t *queue, const uint32_t *countPtr, uint3
                         else if (ANY_HIT) { hit = true; done = true; }
                         else {
                             hit = true; rayTMax = t;
-                            hits.a[slot] = make_float4(t, __int_as_float((int32_t)(pi | (((waitInfo & 0x40000000u) ? BIN_TEXTURED : BIN_GENERIC) << HIT_BIN_SHIFT))), 0.f, 0.f);
-                            if (hits.b) hits.b[slot] = make_float2(0.f, __int_as_float(INST ? inst : -1));
+                            hit_store(hits, slot, (int32_t)(pi | (((waitInfo & 0x40000000u) ? BIN_TEXTURED : BIN_GENERIC) << HIT_BIN_SHIFT)), 0.f, 0.f, 0.f, t, INST ? inst : -1);
                             if (INST) instHit = inst >= 0;
                         }
                     }
@@ -1035,10 +1032,7 @@ void k_walk4(DevScene sc, const uint32_t *queue, const uint32_t *countPtr, uint3
             // retire finished rays
             if (active && cur == REF_NONE) {
                 if (ANY_HIT) occ[slot] = hit ? 1 : 0;
-                else if (!hit) {
-                    hits.a[slot] = make_float4(rayTMax, __int_as_float(-1), 0.f, 0.f);
-                    if (hits.b) hits.b[slot] = make_float2(0.f, __int_as_float(-1));
-                }
+                else if (!hit) hit_store_miss(hits, slot, rayTMax);
                 active = false;
             }
             const int busy = __popcll(__ballot(active));
@@ -1139,7 +1133,7 @@ __global__ __launch_bounds__(1024) void k_bin(DevScene sc, PathStream in, HitStr
 #pragma unroll
     for (int k = 0; k < HPRT_BIN_ITEMS; ++k) {
         const uint32_t i = first + k * 1024u + threadIdx.x;
-        if (i < n) hitA[k] = hit.a[slot[k]];
+        if (i < n) hitA[k] = hit_load(hit, slot[k]);
     }
     unsigned long long mask[HPRT_BIN_ITEMS][N_BINS];
 #pragma unroll
@@ -1148,7 +1142,7 @@ __global__ __launch_bounds__(1024) void k_bin(DevScene sc, PathStream in, HitStr
         bin[k] = -1;
         if (i < n) {
             // the hit's primitive word carries the bin (dev_scene.h); every path of this pass is at the same bounce
-            const int32_t word = __float_as_int(hitA[k].y);
+            const int32_t word = hit_word(hitA[k]);
             if (word >= 0) {
                 // triangles reached directly go to the material-specialised variants; quadrics and hits inside
                 // object instances (surface interaction transformed back to world space) to the generic one
@@ -1195,7 +1189,7 @@ __global__ __launch_bounds__(1024) void k_bin(DevScene sc, PathStream in, HitStr
         const int b = bin[k];
         const unsigned long long m = b == 0 ? mask[k][0] : b == 1 ? mask[k][1] : b == 2 ? mask[k][2] : b == 3 ? mask[k][3] : mask[k][4];
         const uint32_t pos = binBase[b] + waveCount[b][k * 16 + wave] + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-        bins.q[b][pos] = make_uint2(slot[k], __float_as_uint(hitA[k].y));      // the primitive word travels with the entry (kernels.h, BinSet)
+        bins.q[b][pos] = make_uint2(slot[k], (uint32_t)hit_word(hitA[k]));      // the primitive word travels with the entry (kernels.h, BinSet)
     }
 }
 
@@ -1248,9 +1242,9 @@ __global__ __launch_bounds__(BS, MODE == 0 ? HPRT_SHADE_WAVES_MATTE : MODE == 1 
     // The vertex's queue entry and path words are requested BEFORE the Halton tables are staged: the staging (20 KB per workgroup and a
     // barrier, in front of everything) and the first two round trips of the vertex's own dependent chain then overlap.
     // The entry carries the hit's primitive word, so the primitive record (and the rest of the hit) is requested in the same round as the
-    // path streams, not one round trip after hit.a.
+    // path streams, not one round trip after the hit record.
     float4 rayA = make_float4(0.f, 0.f, 0.f, 0.f), rayB = rayA, hitA = rayA, beta4 = rayA, L4 = rayA, tv0 = rayA, tv1 = rayA, tv2 = rayA;
-    float2 hitB = make_float2(0.f, __int_as_float(-1));
+    float2 hitB = hit_no_aux();
     int32_t word = -1;          // the hit's primitive word (dev_scene.h)
     // One light and no spatial distribution (kernel-uniform): Distribution1D::SampleDiscrete returns light 0 for every u (its offset is
     // clamped to [0, size - 2] = [0, 0]), so the light is fetched here through the scalar path, ahead of the vertex's own chain.
@@ -1261,7 +1255,7 @@ __global__ __launch_bounds__(BS, MODE == 0 ? HPRT_SHADE_WAVES_MATTE : MODE == 1 
         // (one 8-byte request from either list; the retry lists keep {stream index, output index}: there the word comes from the hit — rare)
         const uint2 e = (retryPass ? bins.retry[RETRY] : bins.q[BIN])[i];
         slot = e.x;
-        word = retryPass ? __float_as_int(hit.a[slot].y) : (int32_t)e.y;
+        word = retryPass ? hit_word(hit_load(hit, slot)) : (int32_t)e.y;
         if (retryPass) j = e.y;
         else {
             // output index: bins in the order matte, plastic, substrate, generic (as binned), textured
@@ -1271,11 +1265,12 @@ __global__ __launch_bounds__(BS, MODE == 0 ? HPRT_SHADE_WAVES_MATTE : MODE == 1 
             if (BIN == (int)BIN_GENERIC && i >= bins.count[5 * BIN_STRIDE]) j = bins.aux[i];       // deferred by a specialised variant: keeps that variant's index
         }
         // One round of requests, all addressed by the entry alone (the record first: the wait for the entry then covers nothing younger).
-        // The generic bin also holds escaped rays (word < 0): no record to fetch.  Every slot of hit.b has an entry; a miss does not use it.
+        // The generic bin also holds escaped rays (word < 0): no record to fetch.  The one hit record carries all three barycentrics; hit.b is
+        // asked only for the instance, by the variants that know instances (every slot of it has an entry; a miss does not use it).
         const int32_t p = hit_prim(word);
         if (MODE != 2 || p >= 0) { tv0 = sc.tris[3 * p]; tv1 = sc.tris[3 * p + 1]; tv2 = sc.tris[3 * p + 2]; }
-        hitA = hit.a[slot]; rayA = in.ray.a[slot]; rayB = in.ray.b[slot];
-        if (hit.b) hitB = hit.b[slot];
+        hitA = hit_load(hit, slot); rayA = in.ray.a[slot]; rayB = in.ray.b[slot];
+        if ((MODE == 2 || INSTS) && hit.b) hitB = hit_load_aux(hit, slot);
         // a fresh path's throughput and radiance are constants (k_generate does not store them)
         beta4 = firstBounce ? make_float4(1.f, 1.f, 1.f, __uint_as_float(slot)) : in.beta[slot];
         L4 = firstBounce ? make_float4(0.f, 0.f, 0.f, 1.f) : in.L[slot];
@@ -1304,7 +1299,7 @@ __global__ __launch_bounds__(BS, MODE == 0 ? HPRT_SHADE_WAVES_MATTE : MODE == 1 
             const float4 v0 = tv0;
             // A hit inside an object instance was found by the instance-space ray: the surface interaction is
             // filled there and transformed back (TransformedPrimitive::Intersect, core/primitive.cpp:77-93)
-            const int inst = (MODE == 2 || INSTS) ? __float_as_int(hitB.y) : -1;
+            const int inst = (MODE == 2 || INSTS) ? hit_inst(hitB) : -1;
             DRay r0; r0.o = rayO; r0.d = rayD; r0.tMax = rayA.w;
             if ((MODE == 2 || INSTS) && inst >= 0) {      // Transform::operator()(const Ray &), core/transform.h:251-264
                 const DevInstance &in = sc.instances[inst];
@@ -1319,7 +1314,7 @@ __global__ __launch_bounds__(BS, MODE == 0 ? HPRT_SHADE_WAVES_MATTE : MODE == 1 
                 }
             }
             if (MODE != 2 || (__float_as_uint(v0.w) & TAG_KIND_MASK) == 0u)
-                fill_triangle(sc, (uint32_t)prim, tv0, tv1, tv2, hitA.z, hitA.w, hitB.x, r0.d, &si, texScene ? &tg : nullptr);
+                fill_triangle(sc, (uint32_t)prim, tv0, tv1, tv2, hit_b0(hitA), hit_b1(hitA), hit_b2(hitA), r0.d, &si, texScene ? &tg : nullptr);
             else {
                 float tt;
                 fill_sphere(sc, (int)__float_as_uint(tv1.w), r0, &si, &tt, texScene ? &tg : nullptr);
@@ -1608,8 +1603,8 @@ __global__ __launch_bounds__(256) void k_resolve(DevScene sc, VertexStreams vs, 
     rgb Ld(0.f);
     if ((info & 0x40000000u) && !vs.occluded[j]) Ld = Ld + rgb(pl.x, pl.y, pl.z);
     if (info & 0x80000000u) {
-        const float4 mh = vs.misHit.a[j];
-        const int32_t prim = hit_prim(__float_as_int(mh.y));
+        const float4 mh = hit_load(vs.misHit, j);
+        const int32_t prim = hit_prim(hit_word(mh));
         if (prim < 0) {      // the ray escaped: an infinite light's radiance along it was priced in by k_shade, any other light has none (core/light.cpp:66)
             if (sc.lights[lightNum].type == 4) Ld = Ld + rgb(pm.x, pm.y, pm.z);
         } else if (prim_area_light(sc, prim) == lightNum) {
@@ -1619,7 +1614,7 @@ __global__ __launch_bounds__(256) void k_resolve(DevScene sc, VertexStreams vs, 
             const DevLight light = sc.lights[lightNum];
             DevSI li;
             bool filled;
-            if (light.type == 3) { fill_triangle(sc, (uint32_t)prim, mh.z, mh.w, vs.misHit.b[j].x, r.d, &li); filled = true; }
+            if (light.type == 3) { fill_triangle(sc, (uint32_t)prim, hit_b0(mh), hit_b1(mh), hit_b2(mh), r.d, &li); filled = true; }
             else { float tt; filled = fill_sphere(sc, (int)__float_as_uint(sc.tris[3 * prim + 1].w), r, &li, &tt); }
             if (filled && (light.twoSided || dot(li.n, -r.d) > 0)) Ld = Ld + rgb(pm.x, pm.y, pm.z);
         }
@@ -2022,9 +2017,9 @@ __global__ __launch_bounds__(256) void k_pack_rays(const float *r7, uint32_t n, 
 __global__ __launch_bounds__(256) void k_unpack_hits(HitStream h, uint32_t n, float *t, int32_t *prim, float *bary3) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const float4 a = h.a[i];
-    t[i] = a.x; prim[i] = hit_prim(__float_as_int(a.y));
-    if (bary3) { const size_t N = n; bary3[i] = a.z; bary3[N + i] = a.w; bary3[2 * N + i] = h.b[i].x; }
+    const float4 a = hit_load(h, i);
+    t[i] = hit_t(hit_load_aux(h, i)); prim[i] = hit_prim(hit_word(a));
+    if (bary3) { const size_t N = n; bary3[i] = hit_b0(a); bary3[N + i] = hit_b1(a); bary3[2 * N + i] = hit_b2(a); }
 }
 // Per-pixel GeneralStats (the fork's heat-map data, core/film.h:91 + core/integrator.cpp:327-328): every traced ray adds
 // its counters to the pixel of the camera sample it belongs to.  ids[slot].w is the path id; pix: [6][nPix] =
