@@ -149,25 +149,18 @@ class BspBuildDeviceOpts(C.Structure):
                 ("max_face_edges", C.c_uint32), ("max_stack", C.c_uint32)]
 
 
-def _build_bsp_tree(prefix, how, head, prm, device, min_candidates, caps):
-    """hprt_<prefix>_<how> or, with device not None, hprt_<prefix>_<how>_device: (handle, build stats dict or None); caps:
-    max_edges, max_faces, max_face_edges, max_stack"""
-    h = C.c_void_p()
-    if device is None:
-        _check(getattr(lib, "hprt_%s_%s" % (prefix, how))(*head, prm, C.byref(h)))
-        return h, None
-    opts, st = BspBuildDeviceOpts(int(device), min_candidates, *caps), BuildDeviceStats()
-    _check(getattr(lib, "hprt_%s_%s_device" % (prefix, how))(*head, prm, C.byref(opts), C.byref(st), C.byref(h)))
-    return h, st.as_dict()
+def _device_opts(Opts, device, *fields):
+    """The options of a device-assisted build (BuildDeviceOpts or BspBuildDeviceOpts), or None for a host build (device None)"""
+    return None if device is None else Opts(int(device), *fields)
 
 
-def _build_tree(prefix, how, head, prm, device, min_candidates, max_edges):
-    """hprt_<prefix>_<how> or, with device not None, hprt_<prefix>_<how>_device: (handle, build stats dict or None)"""
+def _build_tree(prefix, how, head, prm, opts):
+    """hprt_<prefix>_<how> or, with opts (_device_opts) not None, hprt_<prefix>_<how>_device: (handle, build stats dict or None)"""
     h = C.c_void_p()
-    if device is None:
+    if opts is None:
         _check(getattr(lib, "hprt_%s_%s" % (prefix, how))(*head, prm, C.byref(h)))
         return h, None
-    opts, st = BuildDeviceOpts(int(device), min_candidates, max_edges), BuildDeviceStats()
+    st = BuildDeviceStats()
     _check(getattr(lib, "hprt_%s_%s_device" % (prefix, how))(*head, prm, C.byref(opts), C.byref(st), C.byref(h)))
     return h, st.as_dict()
 
@@ -235,7 +228,7 @@ class RbspKd(_Tree):
         if handle is None:
             prm = None if n_directions is None else C.byref(RbspKdParams(isect_cost, trav_cost, kd_trav_cost, empty_bonus, max_prims, max_depth,
                                                                            n_directions, threads))
-            handle, self.build_stats = _build_tree("rbspkd", "build", (model._h,), prm, device, min_candidates, max_edges)
+            handle, self.build_stats = _build_tree("rbspkd", "build", (model._h,), prm, _device_opts(BuildDeviceOpts, device, min_candidates, max_edges))
         self._h = handle
 
     @staticmethod
@@ -244,7 +237,8 @@ class RbspKd(_Tree):
         """p9: [n, 9] (or [n, 3, 3]) float32 world-space triangle vertices in creation order.  device: as in the constructor."""
         p9 = np.ascontiguousarray(p9, np.float32).reshape(-1, 9)
         prm = RbspKdParams(isect_cost, trav_cost, kd_trav_cost, empty_bonus, max_prims, max_depth, n_directions, threads)
-        h, st = _build_tree("rbspkd", "build_from_triangles", (p9.shape[0], _ptr(p9)), C.byref(prm), device, min_candidates, max_edges)
+        h, st = _build_tree("rbspkd", "build_from_triangles", (p9.shape[0], _ptr(p9)), C.byref(prm),
+                            _device_opts(BuildDeviceOpts, device, min_candidates, max_edges))
         return RbspKd(handle=h, build_stats=st)
 
     @staticmethod
@@ -662,7 +656,7 @@ class Rbsp(_Tree):
         self.build_stats = build_stats
         if handle is None:
             prm = None if n_directions is None else C.byref(_rbsp_params(n_directions, isect_cost, trav_cost, empty_bonus, max_prims, max_depth, threads))
-            handle, self.build_stats = _build_tree("rbsp", "build", (model._h,), prm, device, min_candidates, max_edges)
+            handle, self.build_stats = _build_tree("rbsp", "build", (model._h,), prm, _device_opts(BuildDeviceOpts, device, min_candidates, max_edges))
         self._h = handle
 
     @staticmethod
@@ -671,7 +665,8 @@ class Rbsp(_Tree):
         """p9: [n, 9] (or [n, 3, 3]) float32 world-space triangle vertices in creation order.  device: as in the constructor."""
         p9 = np.ascontiguousarray(p9, np.float32).reshape(-1, 9)
         prm = _rbsp_params(n_directions, isect_cost, trav_cost, empty_bonus, max_prims, max_depth, threads)
-        h, st = _build_tree("rbsp", "build_from_triangles", (p9.shape[0], _ptr(p9)), C.byref(prm), device, min_candidates, max_edges)
+        h, st = _build_tree("rbsp", "build_from_triangles", (p9.shape[0], _ptr(p9)), C.byref(prm),
+                            _device_opts(BuildDeviceOpts, device, min_candidates, max_edges))
         return Rbsp(handle=h, build_stats=st)
 
     @staticmethod
@@ -730,8 +725,8 @@ class BspPaper(_Tree):
         self.build_stats = build_stats
         if handle is None:
             prm = None if isect_cost is None else C.byref(BspPaperParams(isect_cost, trav_cost, empty_bonus, max_prims, max_depth, threads))
-            handle, self.build_stats = _build_bsp_tree("bsppaper", "build", (model._h,), prm, device, min_candidates,
-                                                       (max_edges, max_faces, max_face_edges, max_stack))
+            handle, self.build_stats = _build_tree("bsppaper", "build", (model._h,), prm,
+                                                   _device_opts(BspBuildDeviceOpts, device, min_candidates, max_edges, max_faces, max_face_edges, max_stack))
         self._h = handle
 
     @staticmethod
@@ -740,8 +735,8 @@ class BspPaper(_Tree):
         """p9: [n, 9] (or [n, 3, 3]) float32 world-space triangle vertices in creation order.  device ...: as in the constructor."""
         p9 = np.ascontiguousarray(p9, np.float32).reshape(-1, 9)
         prm = BspPaperParams(isect_cost, trav_cost, empty_bonus, max_prims, max_depth, threads)
-        h, st = _build_bsp_tree("bsppaper", "build_from_triangles", (p9.shape[0], _ptr(p9)), C.byref(prm), device, min_candidates,
-                                (max_edges, max_faces, max_face_edges, max_stack))
+        h, st = _build_tree("bsppaper", "build_from_triangles", (p9.shape[0], _ptr(p9)), C.byref(prm),
+                            _device_opts(BspBuildDeviceOpts, device, min_candidates, max_edges, max_faces, max_face_edges, max_stack))
         return BspPaper(handle=h, build_stats=st)
 
     @staticmethod
@@ -780,8 +775,8 @@ class BspPaperKd(_Tree):
         self.build_stats = build_stats
         if handle is None:
             prm = None if isect_cost is None else C.byref(BspPaperKdParams(isect_cost, trav_cost, kd_trav_cost, empty_bonus, max_prims, max_depth, threads))
-            handle, self.build_stats = _build_bsp_tree("bsppaperkd", "build", (model._h,), prm, device, min_candidates,
-                                                       (max_edges, max_faces, max_face_edges, max_stack))
+            handle, self.build_stats = _build_tree("bsppaperkd", "build", (model._h,), prm,
+                                                   _device_opts(BspBuildDeviceOpts, device, min_candidates, max_edges, max_faces, max_face_edges, max_stack))
         self._h = handle
 
     @staticmethod
@@ -790,8 +785,8 @@ class BspPaperKd(_Tree):
         """p9: [n, 9] (or [n, 3, 3]) float32 world-space triangle vertices in creation order.  device ...: as in the constructor."""
         p9 = np.ascontiguousarray(p9, np.float32).reshape(-1, 9)
         prm = BspPaperKdParams(isect_cost, trav_cost, kd_trav_cost, empty_bonus, max_prims, max_depth, threads)
-        h, st = _build_bsp_tree("bsppaperkd", "build_from_triangles", (p9.shape[0], _ptr(p9)), C.byref(prm), device, min_candidates,
-                                (max_edges, max_faces, max_face_edges, max_stack))
+        h, st = _build_tree("bsppaperkd", "build_from_triangles", (p9.shape[0], _ptr(p9)), C.byref(prm),
+                            _device_opts(BspBuildDeviceOpts, device, min_candidates, max_edges, max_faces, max_face_edges, max_stack))
         return BspPaperKd(handle=h, build_stats=st)
 
     @staticmethod
@@ -870,8 +865,8 @@ class BspNode(BspPaper):
         if handle is None:
             prm = None if accelerator is None else C.byref(_bspnode_params(accelerator, False, n_directions, seed, isect_cost, trav_cost, 1, empty_bonus,
                                                                           max_prims, max_depth, threads))
-            handle, self.build_stats = _build_bsp_tree("bspnode", "build", (model._h,), prm, device, min_candidates,
-                                                       (max_edges, max_faces, max_face_edges, 0))
+            handle, self.build_stats = _build_tree("bspnode", "build", (model._h,), prm,
+                                                   _device_opts(BspBuildDeviceOpts, device, min_candidates, max_edges, max_faces, max_face_edges, 0))
         self._h = handle
 
     @staticmethod
@@ -880,8 +875,8 @@ class BspNode(BspPaper):
         """p9: [n, 9] (or [n, 3, 3]) float32 world-space triangle vertices in creation order.  device ...: as in the constructor."""
         p9 = np.ascontiguousarray(p9, np.float32).reshape(-1, 9)
         prm = _bspnode_params(accelerator, False, n_directions, seed, isect_cost, trav_cost, 1, empty_bonus, max_prims, max_depth, threads)
-        h, st = _build_bsp_tree("bspnode", "build_from_triangles", (p9.shape[0], _ptr(p9)), C.byref(prm), device, min_candidates,
-                                (max_edges, max_faces, max_face_edges, 0))
+        h, st = _build_tree("bspnode", "build_from_triangles", (p9.shape[0], _ptr(p9)), C.byref(prm),
+                            _device_opts(BspBuildDeviceOpts, device, min_candidates, max_edges, max_faces, max_face_edges, 0))
         return BspNode(handle=h, build_stats=st)
 
 
@@ -896,8 +891,8 @@ class BspNodeKd(BspPaperKd):
         if handle is None:
             prm = None if accelerator is None else C.byref(_bspnode_params(accelerator, True, n_directions, seed, isect_cost, trav_cost, kd_trav_cost,
                                                                           empty_bonus, max_prims, max_depth, threads))
-            handle, self.build_stats = _build_bsp_tree("bspnodekd", "build", (model._h,), prm, device, min_candidates,
-                                                       (max_edges, max_faces, max_face_edges, 0))
+            handle, self.build_stats = _build_tree("bspnodekd", "build", (model._h,), prm,
+                                                   _device_opts(BspBuildDeviceOpts, device, min_candidates, max_edges, max_faces, max_face_edges, 0))
         self._h = handle
 
     @staticmethod
@@ -906,8 +901,8 @@ class BspNodeKd(BspPaperKd):
         """p9: [n, 9] (or [n, 3, 3]) float32 world-space triangle vertices in creation order.  device ...: as in the constructor."""
         p9 = np.ascontiguousarray(p9, np.float32).reshape(-1, 9)
         prm = _bspnode_params(accelerator, True, n_directions, seed, isect_cost, trav_cost, kd_trav_cost, empty_bonus, max_prims, max_depth, threads)
-        h, st = _build_bsp_tree("bspnodekd", "build_from_triangles", (p9.shape[0], _ptr(p9)), C.byref(prm), device, min_candidates,
-                                (max_edges, max_faces, max_face_edges, 0))
+        h, st = _build_tree("bspnodekd", "build_from_triangles", (p9.shape[0], _ptr(p9)), C.byref(prm),
+                            _device_opts(BspBuildDeviceOpts, device, min_candidates, max_edges, max_faces, max_face_edges, 0))
         return BspNodeKd(handle=h, build_stats=st)
 
 

@@ -13,7 +13,6 @@
 // hook flags is costed here again.
 #include "bspnode_builder.h"
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstring>
 #include <functional>
@@ -365,16 +364,14 @@ std::string BuildBspNodeTree(size_t n, const float *bmin, const float *bmax, con
             }
         };
         // the costing hook (BspNodeParams::costFn): the node's candidates costed elsewhere, the flagged ones repaired here
-        bool costed = false;
-        if (p.costFn && !cands.empty() && cands.size() >= p.costMinCandidates) {
-            overflow.assign(cands.size(), 0);
+        std::string hookErr;
+        const HookResult hooked = RunCostHook(p, cands.size(), overflow, false, [&](BspNodeCostRequest &rq) {      // (secondsDevice: costFn alone)
             hookCands.resize(cands.size());
             for (size_t k = 0; k < cands.size(); ++k) hookCands[k] = bspnodecost::Cand{cands[k].k, cands[k].nBelow, cands[k].nAbove, cands[k].t};
             hookDirs.resize(nDirs);
             for (uint32_t k = 0; k < nDirs; ++k)
                 hookDirs[k] = bspnodecost::SweepDir{{nodeDirs[3 * k], nodeDirs[3 * k + 1], nodeDirs[3 * k + 2]},
                                                     !fastKd ? bspnodecost::KIND_PLAIN : (k < 3 ? bspnodecost::KIND_KD_AXIS : bspnodecost::KIND_CHOSEN)};
-            BspNodeCostRequest rq;
             rq.mesh = reinterpret_cast<const kdopcost::Edge *>(cur.mesh.data()); rq.nEdges = (uint32_t)cur.mesh.size();
             rq.dirs = cur.dirs.data(); rq.M = (uint32_t)(cur.dirs.size() / 3);
             rq.sweep = hookDirs.data(); rq.nDirs = nDirs; rq.fastKd = fastKd;
@@ -382,28 +379,12 @@ std::string BuildBspNodeTree(size_t n, const float *bmin, const float *bmax, con
             rq.cands = hookCands.data(); rq.n = cands.size();
             rq.costs = costs.data(); rq.costsFixed = fastKd ? costsFixed.data() : nullptr; rq.overflow = overflow.data();
             rq.level = maxDepth - cur.depth;
-            std::string err;
-            const auto t0 = std::chrono::steady_clock::now();
-            const int rc = p.costFn(rq, &err);
-            const double hookSeconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();      // costFn alone, not the repair
-            if (rc < 0) return err.empty() ? std::string("the costing hook failed") : err;
-            if (rc == 0) {
-                costed = true;
-                uint64_t redo = 0;
-                for (size_t k = 0; k < cands.size(); ++k)
-                    if (overflow[k]) {
-                        if (fastKd) costsFixed[k] = std::numeric_limits<float>::infinity();
-                        costRange(k, k + 1, 0); ++redo;
-                    }
-                if (p.stats) {
-                    p.stats->secondsDevice += hookSeconds;
-                    ++p.stats->nodesDevice; p.stats->candidatesDevice += cands.size() - redo; p.stats->candidatesRecosted += redo;
-                }
-                if (p.costDone) p.costDone(rq);
-            }
-        }
-        if (!costed && p.stats) ++p.stats->nodesHost;
-        if (costed) {
+        }, [&](size_t k) {
+            if (fastKd) costsFixed[k] = std::numeric_limits<float>::infinity();
+            costRange(k, k + 1, 0);
+        }, &hookErr);
+        if (hooked == HookResult::Failed) return hookErr;
+        if (hooked == HookResult::Costed) {
             // (costs[] and costsFixed[] are complete)
         } else if (nThreads > 1 && cands.size() >= kParallelCandidates) {
             const size_t chunk = (cands.size() + nThreads - 1) / nThreads;

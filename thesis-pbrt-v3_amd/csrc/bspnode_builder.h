@@ -40,7 +40,9 @@ struct BspNodeCostRequest {
     uint32_t level;                                       // the node's depth below the root (diagnostics)
 };
 
-struct BspNodeParams {
+// costFn, costMinCandidates, stats, costDone: the costing hook (cost_hook.h; the device-assisted build, hprt_bspnode_build_device).
+// The chooser has drawn before costFn is called and costFn draws nothing, so the tree of a seed is the same either way.
+struct BspNodeParams : CostHook<BspNodeCostRequest> {
     int chooser = BSPNODE_CLUSTER, form = BSPNODE_PLAIN;
     int nDirections = 3;                  // "nbDirections": K; the withkd / fastkd forms choose K - 3 and need K >= 3
     uint32_t seed = BSPNODE_DEFAULT_SEED; // "seed"
@@ -49,16 +51,6 @@ struct BspNodeParams {
     float emptyBonus = 0.f;               // "emptybonus"
     int maxPrims = 1, maxDepth = -1;      // "maxprims", "maxdepth" (-1: round(2 + 1.6 Log2Int(N)))
     int threads = 0;                      // candidate evaluation threads: 0 = OMP_NUM_THREADS (else 16), at most 16
-    // Optional costing hook (the device-assisted build, hprt_bspnode_build_device), as BspPaperParams has it: a node with at least
-    // costMinCandidates candidates is handed to costFn instead of the thread pool.  It fills costs / costsFixed / overflow for
-    // every candidate and returns 0; returns 1 to decline the node (it takes the host path), < 0 to fail the build with *err.
-    // Flagged candidates are costed again by costRange itself.  The chooser has drawn before costFn is called and costFn draws
-    // nothing, so the tree of a seed is the same either way.
-    std::function<int(const BspNodeCostRequest &, std::string *err)> costFn;
-    uint32_t costMinCandidates = 1024;    // (kdop::kParallelCandidates)
-    BspBuildStats *stats = nullptr;       // filled when costFn is set
-    // Diagnostics: called for a node costFn has handled, after the repair, with the costs the scan is about to read
-    std::function<void(const BspNodeCostRequest &)> costDone;
 };
 
 // "bsparbitrary" ... "bsprandomfastkd" -> chooser and form; false for any other name

@@ -14,7 +14,6 @@
 // same scan with the kd-aware costs, a second minimum over the plane candidates alone, and the 3-bit node flags.
 #include "bsppaper_builder.h"
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstring>
 #include <functional>
@@ -342,15 +341,13 @@ std::string BuildBspPaperTree(size_t n, const float *bmin, const float *bmax, co
                 CostOne(cur, nb, cc, cands[k], scratch[(size_t)w], &candDirs[(size_t)w], bvhStacks[(size_t)w], &costs[k], kdAware ? &costsFixed[k] : nullptr);
         };
         // the costing hook (BspPaperParams::costFn): the node's candidates costed elsewhere, the flagged ones repaired here
-        bool costed = false;
-        if (p.costFn && !cands.empty() && cands.size() >= p.costMinCandidates) {
-            overflow.assign(cands.size(), 0);
+        std::string hookErr;
+        const HookResult hooked = RunCostHook(p, cands.size(), overflow, true, [&](BspCostRequest &rq) {
             const bool hasBvh = planeBegin.back() != 0;
             bvhRecs.resize(hasBvh ? nb.bvh.nodes.size() : 0);
             BspBvhRecords(nb.bvh.nodes.data(), bvhRecs.size(), bvhRecs.data());
             size_t nAxis = 0;
             while (nAxis < cands.size() && cands[nAxis].k != 33u) ++nAxis;
-            BspCostRequest rq;
             rq.mesh = reinterpret_cast<const kdopcost::Edge *>(cur.mesh.data()); rq.nEdges = (uint32_t)cur.mesh.size();
             rq.dirs = cur.dirs.data(); rq.M = (uint32_t)(cur.dirs.size() / 3); rq.kdAware = kdAware;
             rq.sc = bspcost::Scalars{invTotalSA, emptyBonus, isectCost, traversalCost, kdTraversalCost, cur.nPrimitives, 0u, 0u, 0u, 0u};
@@ -360,27 +357,12 @@ std::string BuildBspPaperTree(size_t n, const float *bmin, const float *bmax, co
             rq.bmin = bmin; rq.bmax = bmax; rq.tri9 = tri9; rq.isTri = isTri; rq.nTotal = n;
             rq.costs = costs.data(); rq.costsFixed = kdAware ? costsFixed.data() : nullptr; rq.overflow = overflow.data();
             rq.level = maxDepth - cur.depth;
-            std::string err;
-            const auto t0 = std::chrono::steady_clock::now();
-            const int rc = p.costFn(rq, &err);
-            if (rc < 0) return err.empty() ? std::string("the costing hook failed") : err;
-            if (rc == 0) {
-                costed = true;
-                uint64_t redo = 0;
-                for (size_t k = 0; k < cands.size(); ++k)
-                    if (overflow[k]) {
-                        if (kdAware) costsFixed[k] = std::numeric_limits<float>::infinity();
-                        costRange(k, k + 1, 0); ++redo;
-                    }
-                if (p.stats) {
-                    p.stats->secondsDevice += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-                    ++p.stats->nodesDevice; p.stats->candidatesDevice += cands.size() - redo; p.stats->candidatesRecosted += redo;
-                }
-                if (p.costDone) p.costDone(rq);
-            }
-        }
-        if (!costed && p.stats) ++p.stats->nodesHost;
-        if (costed) {
+        }, [&](size_t k) {
+            if (kdAware) costsFixed[k] = std::numeric_limits<float>::infinity();
+            costRange(k, k + 1, 0);
+        }, &hookErr);
+        if (hooked == HookResult::Failed) return hookErr;
+        if (hooked == HookResult::Costed) {
             // (costs[], costsFixed[] and the plane candidates' counts are complete)
         } else if (nThreads > 1 && cands.size() >= kParallelCandidates) {
             const size_t chunk = (cands.size() + nThreads - 1) / nThreads;

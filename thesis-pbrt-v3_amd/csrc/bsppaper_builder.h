@@ -14,6 +14,7 @@
 #include <vector>
 #include "bsp_cost.h"
 #include "bsp_tree.h"
+#include "cost_hook.h"
 
 namespace hprt {
 
@@ -43,9 +44,10 @@ struct BspCostRequest {
     uint8_t *overflow;                                    // 1: not costed (a capacity of the costing was exceeded)
     uint32_t level;                                       // the node's depth below the root (diagnostics)
 };
-struct BspBuildStats { uint64_t nodesDevice = 0, candidatesDevice = 0, candidatesRecosted = 0, nodesHost = 0; double secondsDevice = 0; };
 
-struct BspPaperParams {
+// costFn, costMinCandidates, stats, costDone: the costing hook (cost_hook.h; the device-assisted build, hprt_bsppaper_build_device).
+// Besides the costs, costFn fills nBelow / nAbove of every plane candidate it has costed.
+struct BspPaperParams : CostHook<BspCostRequest> {
     int isectCost = 80, travCost = 5;     // "intersectcost", "traversalcost"
     float emptyBonus = 0.f;               // "emptybonus"
     int maxPrims = 1, maxDepth = -1;      // "maxprims", "maxdepth" (-1: round(2 + 1.6 Log2Int(N)), core/geometry.h:1845)
@@ -56,16 +58,6 @@ struct BspPaperParams {
     // the leaf tests and supplies the split only where the first is unset; nodes carry BSPKdNode's flags (BSPPAPERKD_*)
     bool kdAware = false;
     int kdTravCost = 1;                   // "kdtraversalcost"
-    // Optional costing hook (the device-assisted build, hprt_bsppaper_build_device): a node with at least costMinCandidates
-    // candidates is handed to costFn instead of the thread pool.  It fills costs / costsFixed / overflow for every candidate and
-    // nBelow / nAbove of every plane candidate it has costed, and returns 0; returns 1 to decline the node (it takes the host
-    // path), < 0 to fail the build with *err.  Flagged candidates are costed again by costRange itself.  Smaller nodes, and all
-    // nodes when costFn is empty, take the host path.  The scan over costs[] is the same either way.
-    std::function<int(const BspCostRequest &, std::string *err)> costFn;
-    uint32_t costMinCandidates = 1024;    // (kdop::kParallelCandidates)
-    BspBuildStats *stats = nullptr;       // filled when costFn is set
-    // Diagnostics: called for a node costFn has handled, after the repair, with the costs and counts the scan is about to read
-    std::function<void(const BspCostRequest &)> costDone;
 };
 
 struct BspPaperTree {

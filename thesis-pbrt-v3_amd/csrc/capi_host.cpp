@@ -71,21 +71,73 @@ void RbspTriangleBounds(size_t n, const float *p9, std::vector<float> *lo, std::
             (*lo)[3 * i + d] = std::min(l, c); (*hi)[3 * i + d] = std::max(h, c);
         }
 }
-// Handle HprtRbsp with Params HprtRbspParams, or HprtRbspKd (the kd-aware cost model) with HprtRbspKdParams; params NULL keeps p
+// ---- what the RBSP, general BSP and node-based BSP builds share: the costing hook's two users and the end of a build ----
 // What a build does besides the host build (NULL: nothing).  device: the device-assisted build (hprt_*_build*_device) — nodes of
-// at least min_candidates candidates are costed by k_kdopcost.  sink: the diagnostics hook hprt_debug_rbsp_root_mesh — the first
-// maxNodes costed nodes are handed to the sink with the costs the builder's own code gave them.
-typedef void (*RbspNodeSink)(void *user, uint32_t node, const void *edges, uint32_t n_edges, const void *scalars, const void *cands, size_t n,
-                             const float *costs, const float *costs_fixed);
-struct RbspHook {
+// at least min_candidates candidates are costed by the family's kernel (k_kdopcost, k_bspcost, k_sweepcost).  sink: the diagnostics
+// hooks hprt_debug_*_root_* — the first maxNodes costed nodes are handed to the sink with the costs (and counts) the builder's own
+// code gave them.
+template <typename Opts, typename Sink>
+struct BuildHook {
     bool device = false;
-    const HprtBuildDeviceOpts *opts = nullptr;
+    const Opts *opts = nullptr;
     HprtBuildDeviceStats *stats = nullptr;
-    RbspNodeSink sink = nullptr; void *user = nullptr; uint32_t maxNodes = 0;
+    Sink sink = nullptr; void *user = nullptr; uint32_t maxNodes = 0;
 };
 // Below this many candidates a node of a device-assisted build stays on the host: a launch and two copies cost more than the
 // candidates do
 constexpr uint32_t kDeviceMinCandidates = 1024;
+// What the hook's callbacks keep for the end of the build
+struct HookState { BuildDeviceStats bs; int rc = HPRT_OK; uint32_t seen = 0; };
+// Installs hook into a builder's params (cost_hook.h).  open(): opens the family's device, HPRT_OK or a code with the error set.
+// cost(rq, err): costs a node on it — 0, 1 (declined) or -1 with st->rc and *err.  emit(node, rq): hands a costed node to the sink.
+template <typename Request, typename Hook, typename Open, typename Cost, typename Emit>
+int InstallHook(const Hook *hook, CostHook<Request> *p, HookState *st, Open open, Cost cost, Emit emit) {
+    if (hook && hook->device) {
+        if (hook->stats) *hook->stats = HprtBuildDeviceStats{0, 0, 0, 0, 0.0};
+        if (const int rc = open()) return rc;
+        p->costMinCandidates = hook->opts && hook->opts->min_candidates ? hook->opts->min_candidates : kDeviceMinCandidates;
+        p->stats = &st->bs;
+        p->costFn = cost;
+    } else if (hook && hook->sink) {
+        p->costMinCandidates = 1;
+        p->costFn = [=](const Request &rq, std::string *) -> int {
+            if (st->seen >= hook->maxNodes) return 1;
+            memset(rq.overflow, 1, rq.n);          // every candidate "flagged": the builder costs them all with its own code
+            return 0;
+        };
+        p->costDone = [=](const Request &rq) { emit(st->seen++, rq); };
+    }
+    return HPRT_OK;
+}
+// "<what> of depth <depth> is deeper than the device walk's todo list", with the limit and the remedy when todoMax is given
+std::string TooDeepMessage(const std::string &what, uint32_t depth, uint32_t todoMax = 0) {
+    std::string msg = what + " of depth " + std::to_string(depth) + " is deeper than the device walk's todo list";
+    if (todoMax) msg += " (" + std::to_string(todoMax) + " entries); lower \"maxdepth\"";
+    return msg;
+}
+// The end of a build: the statistics out, the hook's failure or the builder's, and no tree deeper than the walk's todo list
+template <typename Hook, typename Handle>
+int FinishBuild(const Hook *hook, const HookState &st, const std::string &err, const char *what, uint32_t todoMax, std::unique_ptr<Handle> &t, Handle **out) {
+    if (hook && hook->stats)
+        *hook->stats = HprtBuildDeviceStats{st.bs.nodesDevice, st.bs.candidatesDevice, st.bs.candidatesRecosted, st.bs.nodesHost, st.bs.secondsDevice};
+    if (st.rc != HPRT_OK) return SetError(st.rc, err);
+    if (!err.empty()) return SetError(HPRT_E_UNSUPPORTED, err);
+    if (t->tree.depth > todoMax) return SetError(HPRT_E_UNSUPPORTED, TooDeepMessage(what, t->tree.depth, todoMax));
+    *out = t.release();
+    return HPRT_OK;
+}
+// A family's device for the length of a build or a call
+template <typename Device, void (*Destroy)(Device *)>
+using DevicePtr = std::unique_ptr<Device, std::integral_constant<void (*)(Device *), Destroy>>;
+using KdopDevicePtr = DevicePtr<KdopCostDevice, KdopCostDeviceDestroy>;
+using BspDevicePtr = DevicePtr<BspCostDevice, BspCostDeviceDestroy>;
+using BspNodeDevicePtr = DevicePtr<BspNodeCostDevice, BspNodeCostDeviceDestroy>;
+
+// ---- the RBSP handles' builds (Handle HprtRbsp with Params HprtRbspParams, or HprtRbspKd, the kd-aware cost model, with
+// HprtRbspKdParams; params NULL keeps p) ----
+typedef void (*RbspNodeSink)(void *user, uint32_t node, const void *edges, uint32_t n_edges, const void *scalars, const void *cands, size_t n,
+                             const float *costs, const float *costs_fixed);
+using RbspHook = BuildHook<HprtBuildDeviceOpts, RbspNodeSink>;
 
 // HprtRbspParams / HprtRbspKdParams over the Accelerator line's (or the defaults'); params NULL keeps *p
 template <typename Params>
@@ -105,43 +157,24 @@ int BuildRbsp(size_t n, const float *lo, const float *hi, const float *tri9, con
     if (p.nDirections != 3 && p.nDirections != 7 && p.nDirections != 9 && p.nDirections != 13)
         return SetError(HPRT_E_UNSUPPORTED, "nbDirections " + std::to_string(p.nDirections) + " is not supported (3, 7, 9 or 13)");
     std::unique_ptr<Handle> t(new Handle());
-    struct DeviceGuard { KdopCostDevice *d = nullptr; ~DeviceGuard() { KdopCostDeviceDestroy(d); } } dev;      // freed when the build ends or fails
-    RbspBuildStats bs;
-    int hookRc = HPRT_OK;
-    uint32_t seen = 0;
-    if (hook && hook->device) {
-        if (hook->stats) *hook->stats = HprtBuildDeviceStats{0, 0, 0, 0, 0.0};
+    KdopDevicePtr dev;                                   // freed when the build ends or fails
+    HookState st;
+    const int rc = InstallHook<RbspCostRequest>(hook, &p, &st, [&]() -> int {
         std::string derr;
-        const int rc = KdopCostDeviceCreate(hook->opts ? hook->opts->device : 0, hook->opts ? hook->opts->max_edges : 0u, &dev.d, &derr);
-        if (rc != HPRT_OK) return SetError(rc, derr);
-        p.costMinCandidates = hook->opts && hook->opts->min_candidates ? hook->opts->min_candidates : kDeviceMinCandidates;
-        p.stats = &bs;
-        p.costFn = [&](const RbspCostRequest &rq, std::string *e) -> int {
-            if (rq.nEdges > KdopCostDeviceCapacity(dev.d)) return 1;      // the whole node on the host
-            hookRc = KdopCostDeviceRun(dev.d, rq.mesh, rq.nEdges, rq.dirs, rq.M, rq.kdAware, rq.sc, rq.cands, rq.n, rq.costs, rq.costsFixed, rq.overflow, e);
-            return hookRc == HPRT_OK ? 0 : -1;
-        };
-    } else if (hook && hook->sink) {
-        p.costMinCandidates = 1;
-        p.costFn = [&](const RbspCostRequest &rq, std::string *) -> int {
-            if (seen >= hook->maxNodes) return 1;
-            memset(rq.overflow, 1, rq.n);          // every candidate "flagged": the builder costs them all with its own code
-            return 0;
-        };
-        p.costDone = [&](const RbspCostRequest &rq) {
-            hook->sink(hook->user, seen++, rq.mesh, rq.nEdges, &rq.sc, rq.cands, rq.n, rq.costs, rq.costsFixed);
-        };
-    }
+        KdopCostDevice *d = nullptr;
+        const int rc = KdopCostDeviceCreate(hook->opts ? hook->opts->device : 0, hook->opts ? hook->opts->max_edges : 0u, &d, &derr);
+        dev.reset(d);
+        return rc != HPRT_OK ? SetError(rc, derr) : HPRT_OK;
+    }, [&](const RbspCostRequest &rq, std::string *e) -> int {
+        if (rq.nEdges > KdopCostDeviceCapacity(dev.get())) return 1;      // the whole node on the host
+        st.rc = KdopCostDeviceRun(dev.get(), rq.mesh, rq.nEdges, rq.dirs, rq.M, rq.kdAware, rq.sc, rq.cands, rq.n, rq.costs, rq.costsFixed, rq.overflow, e);
+        return st.rc == HPRT_OK ? 0 : -1;
+    }, [=](uint32_t node, const RbspCostRequest &rq) {
+        hook->sink(hook->user, node, rq.mesh, rq.nEdges, &rq.sc, rq.cands, rq.n, rq.costs, rq.costsFixed);
+    });
+    if (rc != HPRT_OK) return rc;
     const std::string err = BuildRbspTree(n, lo, hi, tri9, isTri, p, &t->tree);
-    if (hook && hook->stats)
-        *hook->stats = HprtBuildDeviceStats{bs.nodesDevice, bs.candidatesDevice, bs.candidatesRecosted, bs.nodesHost, bs.secondsDevice};
-    if (hookRc != HPRT_OK) return SetError(hookRc, err);
-    if (!err.empty()) return SetError(HPRT_E_UNSUPPORTED, err);
-    if (t->tree.depth > RBSP_TODO_MAX)
-        return SetError(HPRT_E_UNSUPPORTED, "RBSP tree of depth " + std::to_string(t->tree.depth) + " is deeper than the device walk's todo list (" +
-                                                std::to_string((unsigned)RBSP_TODO_MAX) + " entries); lower \"maxdepth\"");
-    *out = t.release();
-    return HPRT_OK;
+    return FinishBuild(hook, st, err, "RBSP tree", RBSP_TODO_MAX, t, out);
 }
 // hprt_rbsp_build / hprt_rbspkd_build: the model's primitives and its Accelerator line (dflt); `what` names the tree in messages
 template <typename Handle, typename Params>
@@ -208,9 +241,7 @@ void RbspPrimTriangles(const SceneModel &sc, int object, size_t n, std::vector<f
 // ---- the general BSP handles' builds and copies (hprt_bsppaper_* and hprt_bsppaperkd_* below) ----
 // Handle HprtBspPaper with Params HprtBspPaperParams, or HprtBspPaperKd (the kd-aware cost model and node flags) with
 // HprtBspPaperKdParams; params NULL keeps p
-// What a build does besides the host build (NULL: nothing), as RbspHook.  device: the device-assisted build
-// (hprt_bsppaper*_build*_device) — nodes of at least min_candidates candidates are costed by k_bspcost.  sink: the diagnostics hook
-// hprt_debug_bsp_root_nodes — the first maxNodes costed nodes are handed out with the costs and counts the builder's own code gave.
+// What the diagnostics hook hprt_debug_bsp_root_nodes hands out (BuildHook's sink)
 struct HprtDebugBspNode {
     const void *edges; uint32_t n_edges;              // 32-byte records (v1, v2, f1, f2), face ids below 2 M
     const float *dirs; uint32_t M;                    // the node's direction list
@@ -223,12 +254,8 @@ struct HprtDebugBspNode {
     uint32_t level;                                   // the node's depth below the root
 };
 typedef void (*BspNodeSink)(void *user, uint32_t node, const HprtDebugBspNode *nd);
-struct BspHook {
-    bool device = false;
-    const HprtBspBuildDeviceOpts *opts = nullptr;
-    HprtBuildDeviceStats *stats = nullptr;
-    BspNodeSink sink = nullptr; void *user = nullptr; uint32_t maxNodes = 0;
-};
+using BspHook = BuildHook<HprtBspBuildDeviceOpts, BspNodeSink>;
+constexpr uint32_t BspPaperTodoMax(bool kdAware) { return kdAware ? (uint32_t)BSPPAPERKD_TODO_MAX : (uint32_t)BSPPAPER_TODO_MAX; }
 // The node of a request as bsp_cost.h reads it: compact face ids and the directions that own a face.  False: the node's own
 // mesh, direction list or faces exceed the capacities (it is declined whole), or a face id is not below 2 M.
 struct BspCompact { std::vector<bspcost::Edge> mesh; std::vector<uint32_t> cdir; uint32_t nD = 0; };
@@ -295,49 +322,31 @@ int BuildBspPaper(size_t n, const float *lo, const float *hi, const float *tri9,
         p.maxPrims = params->max_prims; p.maxDepth = params->max_depth; p.threads = params->threads;
         if constexpr (kdAware) p.kdTravCost = params->kd_trav_cost;
     }
-    const std::string what = kdAware ? "bsppaperkd" : "bsppaper";
-    constexpr uint32_t todoMax = kdAware ? BSPPAPERKD_TODO_MAX : BSPPAPER_TODO_MAX;
     std::unique_ptr<Handle> t(new Handle());
-    struct DeviceGuard { BspCostDevice *d = nullptr; ~DeviceGuard() { BspCostDeviceDestroy(d); } } dev;      // freed when the build ends or fails
-    BspBuildStats bs;
-    int hookRc = HPRT_OK;
-    uint32_t seen = 0, cap[4] = {0, 0, 0, 0};
-    if (hook && hook->device) {
-        if (hook->stats) *hook->stats = HprtBuildDeviceStats{0, 0, 0, 0, 0.0};
+    BspDevicePtr dev;                                    // freed when the build ends or fails
+    HookState st;
+    uint32_t cap[4] = {0, 0, 0, 0};
+    const int rc = InstallHook<BspCostRequest>(hook, &p, &st, [&]() -> int {
         const HprtBspBuildDeviceOpts *o = hook->opts;
         const uint32_t asked[4] = {o ? o->max_edges : 0u, o ? o->max_faces : 0u, o ? o->max_face_edges : 0u, o ? o->max_stack : 0u};
         std::string derr;
-        const int rc = BspCostDeviceCreate(o ? o->device : 0, asked, n, lo, hi, tri9, isTri, &dev.d, &derr);
+        BspCostDevice *d = nullptr;
+        const int rc = BspCostDeviceCreate(o ? o->device : 0, asked, n, lo, hi, tri9, isTri, &d, &derr);
+        dev.reset(d);
         if (rc != HPRT_OK) return SetError(rc, derr);
         bspcost::Scalars sc{};
         sc.maxEdges = asked[0]; sc.maxFaces = asked[1]; sc.maxFaceEdges = asked[2]; sc.maxStack = asked[3];
         bspcost::Capacities(sc, cap);
-        p.costMinCandidates = o && o->min_candidates ? o->min_candidates : kDeviceMinCandidates;
-        p.stats = &bs;
-        p.costFn = [&](const BspCostRequest &rq, std::string *e) -> int { return BspCostOnDevice(dev.d, cap, rq, &hookRc, e); };
-    } else if (hook && hook->sink) {
-        p.costMinCandidates = 1;
-        p.costFn = [&](const BspCostRequest &rq, std::string *) -> int {
-            if (seen >= hook->maxNodes) return 1;
-            memset(rq.overflow, 1, rq.n);          // every candidate "flagged": the builder costs them all with its own code
-            return 0;
-        };
-        p.costDone = [&](const BspCostRequest &rq) {
-            const HprtDebugBspNode nd{rq.mesh, rq.nEdges, rq.dirs, rq.M, &rq.sc, rq.cands, rq.n, rq.nAxis, rq.bvhNodes, rq.nBvh, rq.primOrder, rq.primNums,
-                                      rq.nPrims, rq.bmin, rq.bmax, rq.tri9, rq.isTri, rq.nTotal, rq.costs, rq.costsFixed, rq.level};
-            hook->sink(hook->user, seen++, &nd);
-        };
-    }
+        return HPRT_OK;
+    }, [&](const BspCostRequest &rq, std::string *e) -> int { return BspCostOnDevice(dev.get(), cap, rq, &st.rc, e); },
+    [=](uint32_t node, const BspCostRequest &rq) {
+        const HprtDebugBspNode nd{rq.mesh, rq.nEdges, rq.dirs, rq.M, &rq.sc, rq.cands, rq.n, rq.nAxis, rq.bvhNodes, rq.nBvh, rq.primOrder, rq.primNums,
+                                  rq.nPrims, rq.bmin, rq.bmax, rq.tri9, rq.isTri, rq.nTotal, rq.costs, rq.costsFixed, rq.level};
+        hook->sink(hook->user, node, &nd);
+    });
+    if (rc != HPRT_OK) return rc;
     const std::string err = BuildBspPaperTree(n, lo, hi, tri9, isTri, p, &t->tree);
-    if (hook && hook->stats)
-        *hook->stats = HprtBuildDeviceStats{bs.nodesDevice, bs.candidatesDevice, bs.candidatesRecosted, bs.nodesHost, bs.secondsDevice};
-    if (hookRc != HPRT_OK) return SetError(hookRc, err);
-    if (!err.empty()) return SetError(HPRT_E_UNSUPPORTED, err);
-    if (t->tree.depth > todoMax)
-        return SetError(HPRT_E_UNSUPPORTED, what + " tree of depth " + std::to_string(t->tree.depth) + " is deeper than the device walk's todo list (" +
-                                                std::to_string((unsigned)todoMax) + " entries); lower \"maxdepth\"");
-    *out = t.release();
-    return HPRT_OK;
+    return FinishBuild(hook, st, err, kdAware ? "bsppaperkd tree" : "bsppaper tree", BspPaperTodoMax(kdAware), t, out);
 }
 // nodes20: the reference's 5 words per node (BSPNode / BSPKdNode)
 int BspPaperCopy(const BspPaperTree &b, void *nodes20, uint32_t *primIndices) {
@@ -353,9 +362,7 @@ int BspPaperCopy(const BspPaperTree &b, void *nodes20, uint32_t *primIndices) {
 
 // ---- the node-based BSP trees' builds (hprt_bspnode_* and hprt_bspnodekd_* below): Handle HprtBspPaper for the plain and withkd
 // forms, HprtBspPaperKd for the fastkd form; params NULL keeps p (the scene's Accelerator line)
-// What a build does besides the host build (NULL: nothing), as BspHook.  device: the device-assisted build
-// (hprt_bspnode*_build*_device) — nodes of at least min_candidates candidates are costed by k_sweepcost.  sink: the diagnostics hook
-// hprt_debug_bspnode_root_nodes — the first maxNodes costed nodes are handed out with the costs the builder's own code gave.
+// What the diagnostics hook hprt_debug_bspnode_root_nodes hands out (BuildHook's sink)
 struct HprtDebugBspSweepNode {
     const void *edges; uint32_t n_edges;              // 32-byte records (v1, v2, f1, f2), face ids below 2 M
     const float *dirs; uint32_t M;                    // the node's own direction list
@@ -366,12 +373,7 @@ struct HprtDebugBspSweepNode {
     uint32_t level;                                   // the node's depth below the root
 };
 typedef void (*BspSweepNodeSink)(void *user, uint32_t node, const HprtDebugBspSweepNode *nd);
-struct BspNodeHook {
-    bool device = false;
-    const HprtBspBuildDeviceOpts *opts = nullptr;
-    HprtBuildDeviceStats *stats = nullptr;
-    BspSweepNodeSink sink = nullptr; void *user = nullptr; uint32_t maxNodes = 0;
-};
+using BspNodeHook = BuildHook<HprtBspBuildDeviceOpts, BspSweepNodeSink>;
 // The node of a request as bspnode_cost.h reads it.  False: the node's own mesh, direction list, faces or sweep exceed the
 // capacities (it is declined whole), or a face id or a candidate's direction is out of range.
 bool BspNodeCompactRequest(const BspNodeCostRequest &rq, const uint32_t cap[4], BspCompact *c) {
@@ -418,50 +420,33 @@ int BuildBspNode(const char *fn, size_t n, const float *lo, const float *hi, con
     if ((p.form == BSPNODE_FASTKD) != fastKd)
         return SetError(HPRT_E_INVALID, std::string(fn) + (fastKd ? ": takes the fastkd form only (the plain and withkd forms are hprt_bspnode_build's)"
                                                                   : ": takes the plain and withkd forms only (the fastkd form is hprt_bspnodekd_build's)"));
-    constexpr uint32_t todoMax = fastKd ? (uint32_t)BSPPAPERKD_TODO_MAX : (uint32_t)BSPPAPER_TODO_MAX;
     std::unique_ptr<Handle> t(new Handle());
-    struct DeviceGuard { BspNodeCostDevice *d = nullptr; ~DeviceGuard() { BspNodeCostDeviceDestroy(d); } } dev;      // freed when the build ends or fails
-    BspBuildStats bs;
-    int hookRc = HPRT_OK;
-    uint32_t seen = 0, cap[4] = {0, 0, 0, 0};
-    if (hook && hook->device) {
-        if (hook->stats) *hook->stats = HprtBuildDeviceStats{0, 0, 0, 0, 0.0};
+    BspNodeDevicePtr dev;                                // freed when the build ends or fails
+    HookState st;
+    uint32_t cap[4] = {0, 0, 0, 0};
+    const int rc = InstallHook<BspNodeCostRequest>(hook, &p, &st, [&]() -> int {
         // the refusals that do not depend on the primitives come first, as the host entry gives them, with or without a device
         const std::string refused = BspNodeRefuseParams(p);
         if (!refused.empty()) return SetError(HPRT_E_UNSUPPORTED, refused);
         const HprtBspBuildDeviceOpts *o = hook->opts;
         const uint32_t asked[3] = {o ? o->max_edges : 0u, o ? o->max_faces : 0u, o ? o->max_face_edges : 0u};      // (max_stack: no BVH here)
         std::string derr;
-        const int rc = BspNodeCostDeviceCreate(o ? o->device : 0, asked, &dev.d, &derr);
+        BspNodeCostDevice *d = nullptr;
+        const int rc = BspNodeCostDeviceCreate(o ? o->device : 0, asked, &d, &derr);
+        dev.reset(d);
         if (rc != HPRT_OK) return SetError(rc, derr);
         bspcost::Scalars sc{};
         sc.maxEdges = asked[0]; sc.maxFaces = asked[1]; sc.maxFaceEdges = asked[2];
         bspcost::Capacities(sc, cap);
-        p.costMinCandidates = o && o->min_candidates ? o->min_candidates : kDeviceMinCandidates;
-        p.stats = &bs;
-        p.costFn = [&](const BspNodeCostRequest &rq, std::string *e) -> int { return BspNodeCostOnDevice(dev.d, cap, rq, &hookRc, e); };
-    } else if (hook && hook->sink) {
-        p.costMinCandidates = 1;
-        p.costFn = [&](const BspNodeCostRequest &rq, std::string *) -> int {
-            if (seen >= hook->maxNodes) return 1;
-            memset(rq.overflow, 1, rq.n);          // every candidate "flagged": the builder costs them all with its own code
-            return 0;
-        };
-        p.costDone = [&](const BspNodeCostRequest &rq) {
-            const HprtDebugBspSweepNode nd{rq.mesh, rq.nEdges, rq.dirs, rq.M, rq.sweep, rq.nDirs, &rq.sc, rq.cands, rq.n, rq.costs, rq.costsFixed, rq.level};
-            hook->sink(hook->user, seen++, &nd);
-        };
-    }
+        return HPRT_OK;
+    }, [&](const BspNodeCostRequest &rq, std::string *e) -> int { return BspNodeCostOnDevice(dev.get(), cap, rq, &st.rc, e); },
+    [=](uint32_t node, const BspNodeCostRequest &rq) {
+        const HprtDebugBspSweepNode nd{rq.mesh, rq.nEdges, rq.dirs, rq.M, rq.sweep, rq.nDirs, &rq.sc, rq.cands, rq.n, rq.costs, rq.costsFixed, rq.level};
+        hook->sink(hook->user, node, &nd);
+    });
+    if (rc != HPRT_OK) return rc;
     const std::string err = BuildBspNodeTree(n, lo, hi, tri9, isTri, p, &t->tree);
-    if (hook && hook->stats)
-        *hook->stats = HprtBuildDeviceStats{bs.nodesDevice, bs.candidatesDevice, bs.candidatesRecosted, bs.nodesHost, bs.secondsDevice};
-    if (hookRc != HPRT_OK) return SetError(hookRc, err);
-    if (!err.empty()) return SetError(HPRT_E_UNSUPPORTED, err);
-    if (t->tree.depth > todoMax)
-        return SetError(HPRT_E_UNSUPPORTED, "node-based BSP tree of depth " + std::to_string(t->tree.depth) + " is deeper than the device walk's todo list (" +
-                                                std::to_string((unsigned)todoMax) + " entries); lower \"maxdepth\"");
-    *out = t.release();
-    return HPRT_OK;
+    return FinishBuild(hook, st, err, "node-based BSP tree", BspPaperTodoMax(fastKd), t, out);
 }
 template <typename Handle>
 int BuildBspNodeFromModel(const char *fn, const HprtModel *m, const HprtBspNodeParams *params, Handle **out, const BspNodeHook *hook = nullptr) {
@@ -508,9 +493,7 @@ int RbspFromArrays(const char *fn, uint32_t M, size_t nNodes, const uint32_t *no
     const char *bad = CheckRbspTree(r, &r.depth);
     if (*bad) return SetError(HPRT_E_INVALID, std::string("malformed tree: ") + bad);
     r.maxDepth = r.depth; r.leaves = CountLeaves(r.nodes, RbspBitMask(M), M);
-    if (r.depth > RBSP_TODO_MAX)
-        return SetError(HPRT_E_UNSUPPORTED, "RBSP tree of depth " + std::to_string(r.depth) + " is deeper than the device walk's todo list (" +
-                                                std::to_string((unsigned)RBSP_TODO_MAX) + " entries); lower \"maxdepth\"");
+    if (r.depth > RBSP_TODO_MAX) return SetError(HPRT_E_UNSUPPORTED, TooDeepMessage("RBSP tree", r.depth, RBSP_TODO_MAX));
     *out = t.release();
     return HPRT_OK;
 }
@@ -548,10 +531,8 @@ int BspPaperFromArrays(const char *fn, size_t nNodes, const uint32_t *nodes20, s
     b.maxDepth = b.depth;
     b.leaves = kdAware ? CountLeaves(b.nodes, BSPPAPERKD_MASK, BSPPAPERKD_LEAF) : CountLeaves(b.nodes, BSPPAPER_MASK, 1u);
     CountHandMadeInterior(&b);
-    constexpr uint32_t todoMax = kdAware ? BSPPAPERKD_TODO_MAX : BSPPAPER_TODO_MAX;
-    if (b.depth > todoMax)
-        return SetError(HPRT_E_UNSUPPORTED, std::string(kdAware ? "bsppaperkd" : "bsppaper") + " tree of depth " + std::to_string(b.depth) +
-                                                " is deeper than the device walk's todo list (" + std::to_string((unsigned)todoMax) + " entries); lower \"maxdepth\"");
+    if (b.depth > BspPaperTodoMax(kdAware))
+        return SetError(HPRT_E_UNSUPPORTED, TooDeepMessage(kdAware ? "bsppaperkd tree" : "bsppaper tree", b.depth, BspPaperTodoMax(kdAware)));
     *out = t.release();
     return HPRT_OK;
 }
@@ -952,8 +933,7 @@ void hprt_bvh_destroy(HprtBvh *b) { delete b; }
 // ---- kd-tree (Accelerator "kdtree") ----
 static int FinishKdTree(HprtKdTree *t, HprtKdTree **out) {
     if (t->tree.depth > KD_TODO_MAX) {
-        const std::string msg = "kd-tree of depth " + std::to_string(t->tree.depth) + " is deeper than the device walk's todo list (" +
-                                std::to_string((unsigned)KD_TODO_MAX) + " entries); lower \"maxdepth\"";
+        const std::string msg = TooDeepMessage("kd-tree", t->tree.depth, KD_TODO_MAX);
         delete t;
         return SetError(HPRT_E_UNSUPPORTED, msg);
     }
@@ -1285,12 +1265,13 @@ __attribute__((visibility("default"))) int hprt_debug_bsp_cost(const HprtDebugBs
     if (impl == 0) BspCostVector(rq);
     else if (impl == 1) rc = BspCostRestated(rq);
     else {
-        struct DeviceGuard { BspCostDevice *d = nullptr; ~DeviceGuard() { BspCostDeviceDestroy(d); } } dev;
         std::string err;
         const uint32_t asked[4] = {sc.maxEdges, sc.maxFaces, sc.maxFaceEdges, sc.maxStack};
-        int drc = BspCostDeviceCreate(0, asked, nd->n_total, nd->bmin, nd->bmax, nd->tri9, nd->is_tri, &dev.d, &err);
+        BspCostDevice *d = nullptr;
+        int drc = BspCostDeviceCreate(0, asked, nd->n_total, nd->bmin, nd->bmax, nd->tri9, nd->is_tri, &d, &err);
+        const BspDevicePtr dev(d);
         if (drc != HPRT_OK) return SetError(drc, err);
-        rc = BspCostOnDevice(dev.d, cap, rq, &drc, &err);
+        rc = BspCostOnDevice(d, cap, rq, &drc, &err);
         if (rc < 0) return SetError(drc, err);
     }
     if (rc == 1) return HPRT_OK;            // declined whole: every candidate flagged
@@ -1433,12 +1414,13 @@ __attribute__((visibility("default"))) int hprt_debug_bspnode_cost(const HprtDeb
     if (impl == 0) BspNodeCostVector(rq);
     else if (impl == 1) rc = BspNodeCostRestated(rq);
     else {
-        struct DeviceGuard { BspNodeCostDevice *d = nullptr; ~DeviceGuard() { BspNodeCostDeviceDestroy(d); } } dev;
         std::string err;
         const uint32_t asked[3] = {sc.maxEdges, sc.maxFaces, sc.maxFaceEdges};
-        int drc = BspNodeCostDeviceCreate(0, asked, &dev.d, &err);
+        BspNodeCostDevice *d = nullptr;
+        int drc = BspNodeCostDeviceCreate(0, asked, &d, &err);
+        const BspNodeDevicePtr dev(d);
         if (drc != HPRT_OK) return SetError(drc, err);
-        rc = BspNodeCostOnDevice(dev.d, cap, rq, &drc, &err);
+        rc = BspNodeCostOnDevice(d, cap, rq, &drc, &err);
         if (rc < 0) return SetError(drc, err);
     }
     if (rc == 1) { *declined = 1; return HPRT_OK; }
@@ -1471,8 +1453,7 @@ __attribute__((visibility("default"))) int hprt_debug_bspnode_check(size_t n_nod
     t.primIndices.assign(idx, idx + n_idx);
     const char *bad = t.kdAware ? CheckBspPaperKdTree(t, depth) : CheckBspPaperTree(t, depth);
     if (*bad) return SetError(HPRT_E_INVALID, std::string("malformed tree: ") + bad);
-    if (*depth > (t.kdAware ? (uint32_t)BSPPAPERKD_TODO_MAX : (uint32_t)BSPPAPER_TODO_MAX))
-        return SetError(HPRT_E_UNSUPPORTED, "node-based BSP tree of depth " + std::to_string(*depth) + " is deeper than the device walk's todo list");
+    if (*depth > BspPaperTodoMax(t.kdAware)) return SetError(HPRT_E_UNSUPPORTED, TooDeepMessage("node-based BSP tree", *depth));
     return HPRT_OK;
 } catch (...) { return hprt::HandleException(); }
 // Diagnostics hooks (not part of include/hprt.h; tests/deep_todo.py): a tree made by hand as an ordinary handle, so that a tree with a
@@ -1540,11 +1521,12 @@ __attribute__((visibility("default"))) int hprt_debug_kdop_cost(const void *edge
         for (size_t k = 0; k < n; ++k) CostCandidate(mesh.data(), n_edges, dirs.data(), M, kd_aware != 0, sc, cs[k], st, &costs[k], &costs_fixed[k], &overflow[k]);
         return HPRT_OK;
     }
-    struct DeviceGuard { KdopCostDevice *d = nullptr; ~DeviceGuard() { KdopCostDeviceDestroy(d); } } dev;
     std::string err;
-    int rc = KdopCostDeviceCreate(0, sc.maxEdges, &dev.d, &err);
+    KdopCostDevice *d = nullptr;
+    int rc = KdopCostDeviceCreate(0, sc.maxEdges, &d, &err);
+    const KdopDevicePtr dev(d);
     if (rc != HPRT_OK) return SetError(rc, err);
-    rc = KdopCostDeviceRun(dev.d, mesh.data(), n_edges, dirs.data(), M, kd_aware != 0, sc, cs.data(), n, costs, costs_fixed, overflow, &err);
+    rc = KdopCostDeviceRun(d, mesh.data(), n_edges, dirs.data(), M, kd_aware != 0, sc, cs.data(), n, costs, costs_fixed, overflow, &err);
     if (rc != HPRT_OK) return SetError(rc, err);
     if (!kd_aware) for (size_t k = 0; k < n; ++k) costs_fixed[k] = 0;
     return HPRT_OK;

@@ -16,14 +16,12 @@
 #include <string>
 #include "../../../include/hprt.h"
 #include "../bsp_cost_device.h"
+#include "cost_session.h"
 
 namespace hprt {
 namespace {
 
 using namespace bspcost;
-
-constexpr uint32_t kWave = 64;
-constexpr uint32_t kWavesPerCU = 8;      // lanes in flight = CUs * kWavesPerCU * 64 at most
 
 template <bool KD_AWARE, bool PLANES>
 __global__ __launch_bounds__(64) void k_bspcost(Node nd, Scalars sc, const Cand *__restrict__ cands, uint32_t first, uint32_t n, uint32_t capEdges,
@@ -81,52 +79,21 @@ __global__ __launch_bounds__(64) void k_bspcost(Node nd, Scalars sc, const Cand 
     }
 }
 
-struct Pinned {
-    void *p = nullptr; size_t bytes = 0;
-    hipError_t reserve(size_t b) {
-        if (b <= bytes) return hipSuccess;
-        if (p) (void)hipHostFree(p);
-        p = nullptr; bytes = 0;
-        b = std::max<size_t>(b + b / 2, 4096);
-        hipError_t e = hipHostMalloc(&p, b, hipHostMallocDefault);
-        if (e == hipSuccess) bytes = b; else p = nullptr;
-        return e;
-    }
-    ~Pinned() { if (p) (void)hipHostFree(p); }
-};
-struct Dev {
-    void *p = nullptr; size_t bytes = 0;
-    hipError_t reserve(size_t b, bool grow = true) {
-        if (b <= bytes) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr; bytes = 0;
-        b = std::max<size_t>(grow ? b + b / 2 : b, 4096);
-        hipError_t e = hipMalloc(&p, b);
-        if (e == hipSuccess) bytes = b; else p = nullptr;
-        return e;
-    }
-    ~Dev() { if (p) (void)hipFree(p); }
-};
-constexpr size_t Pad16(size_t b) { return (b + 15) & ~(size_t)15; }
-
 }  // namespace
 
-struct BspCostDevice {
-    int device = 0;
+// hIn: mesh, directions, compact table, candidates, BVH, primOrder, primNums; hOut: costs, costsFixed, counts, overflow
+struct BspCostDevice : CostSession {
     uint32_t cap[4] = {BSP_MAX_EDGES, BSP_MAX_FACES, BSP_MAX_FACE_EDGES, BSP_MAX_STACK};
-    uint32_t maxLanes = 0, wsLanes = 0, nTotal = 0;
-    hipStream_t stream = nullptr;
-    Pinned hIn, hOut;           // in: mesh, directions, compact table, candidates, BVH, primOrder, primNums; out: costs, costsFixed, counts, overflow
-    Dev dIn, dOut, ws, prims;   // prims: bmin | bmax | tri9 | isTri of the whole build
+    uint32_t nTotal = 0;
+    Dev prims;                  // bmin | bmax | tri9 | isTri of the whole build
     size_t offBmax = 0, offTri9 = 0, offIsTri = 0;
-    ~BspCostDevice() { if (stream) (void)hipStreamDestroy(stream); }
 };
 
 int BspCostDeviceCreate(int device, const uint32_t caps[4], size_t nTotal, const float *bmin, const float *bmax, const float *tri9,
                         const uint8_t *isTri, BspCostDevice **out, std::string *err) {
     *out = nullptr;
     int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) { *err = "no HIP device available (the device-assisted build has no CPU fallback)"; return HPRT_E_NO_DEVICE; }
+    if (const int rc = CostDeviceCount(&n, err)) return rc;
     Scalars sc{};
     sc.maxEdges = caps[0]; sc.maxFaces = caps[1]; sc.maxFaceEdges = caps[2]; sc.maxStack = caps[3];
     uint32_t cap[4];
@@ -136,17 +103,10 @@ int BspCostDeviceCreate(int device, const uint32_t caps[4], size_t nTotal, const
         return HPRT_E_INVALID;
     }
     if (nTotal > 0x7fffffffull) { *err = "more primitives than the device costing indexes"; return HPRT_E_INVALID; }
-    if (device < 0) { if (hipGetDevice(&device) != hipSuccess) device = 0; }
-    if (device >= n) { *err = "device ordinal out of range"; return HPRT_E_INVALID; }
-    if (hipSetDevice(device) != hipSuccess) { *err = "hipSetDevice failed"; return HPRT_E_DEVICE; }
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) != hipSuccess) { *err = "hipGetDeviceProperties failed"; return HPRT_E_DEVICE; }
     BspCostDevice *d = new BspCostDevice();
-    d->device = device;
     for (int k = 0; k < 4; ++k) d->cap[k] = cap[k];
-    d->maxLanes = (uint32_t)std::max(1, prop.multiProcessorCount) * kWavesPerCU * kWave;
     d->nTotal = (uint32_t)nTotal;
-    if (hipStreamCreate(&d->stream) != hipSuccess) { d->stream = nullptr; delete d; *err = "hipStreamCreate failed"; return HPRT_E_DEVICE; }
+    if (const int rc = d->Open(device, n, err)) { delete d; return rc; }
     // the primitives, once per build: bmin | bmax | tri9 | isTri
     const size_t b3 = Pad16(nTotal * 12), b9 = Pad16(nTotal * 36);
     d->offBmax = b3; d->offTri9 = 2 * b3; d->offIsTri = 2 * b3 + b9;
@@ -165,11 +125,7 @@ int BspCostDeviceCreate(int device, const uint32_t caps[4], size_t nTotal, const
     return HPRT_OK;
 }
 
-void BspCostDeviceDestroy(BspCostDevice *d) {
-    if (!d) return;
-    (void)hipSetDevice(d->device);
-    delete d;
-}
+void BspCostDeviceDestroy(BspCostDevice *d) { CostSessionDestroy(d); }
 
 int BspCostDeviceRun(BspCostDevice *d, const Edge *mesh, uint32_t nE, const float *dirs, uint32_t M, const uint32_t *cdir, uint32_t nD, bool kdAware,
                      const Scalars &sc, const Cand *cands, size_t n, size_t nAxis, const BvhRec *bvh, uint32_t nBvh, const uint32_t *primOrder,
@@ -181,7 +137,7 @@ int BspCostDeviceRun(BspCostDevice *d, const Edge *mesh, uint32_t nE, const floa
         *err = "k_bspcost: a mesh, a direction list, a BVH or a candidate list beyond the kernel's bounds"; return HPRT_E_INVALID;
     }
     if (!planes) { nBvh = 0; nPrims = 0; }
-#define BSP_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { *err = std::string("k_bspcost launcher: ") + hipGetErrorString(e_); return HPRT_E_DEVICE; } } while (0)
+#define BSP_TRY(x) COST_TRY("k_bspcost", x)
     BSP_TRY(hipSetDevice(d->device));
     // staging layout (16-byte aligned parts): in = mesh | directions | compact table | candidates | BVH | primOrder | primNums;
     // out = costs | costsFixed | counts | overflow
@@ -191,14 +147,8 @@ int BspCostDeviceRun(BspCostDevice *d, const Edge *mesh, uint32_t nE, const floa
                  offNums = offOrder + idxBytes, inBytes = offNums + idxBytes;
     const size_t costBytes = Pad16(n * 4), countBytes = Pad16(n * 8);
     const size_t outBytes = 2 * costBytes + countBytes + n;
-    BSP_TRY(d->hIn.reserve(inBytes)); BSP_TRY(d->hOut.reserve(outBytes));
-    BSP_TRY(d->dIn.reserve(inBytes)); BSP_TRY(d->dOut.reserve(outBytes));
-    const size_t widest = std::max(nAxis, n - nAxis);
-    const uint32_t lanes = (uint32_t)std::min<size_t>(d->maxLanes, (widest + kWave - 1) / kWave * kWave);
-    if (lanes > d->wsLanes) {
-        BSP_TRY(d->ws.reserve((size_t)lanes * kStoreWords * sizeof(Q), false));
-        d->wsLanes = lanes;
-    }
+    const uint32_t lanes = d->Lanes(std::max(nAxis, n - nAxis));      // (the wider of the two launches)
+    BSP_TRY(d->Reserve(inBytes, outBytes, lanes, kStoreWords * sizeof(Q), false));
     char *h = (char *)d->hIn.p;
     if (nE) std::memcpy(h, mesh, (size_t)nE * sizeof(Edge));
     std::memcpy(h + offDirs, dirs, (size_t)3 * M * 4);
@@ -209,7 +159,7 @@ int BspCostDeviceRun(BspCostDevice *d, const Edge *mesh, uint32_t nE, const floa
         std::memcpy(h + offOrder, primOrder, (size_t)nPrims * 4);
         std::memcpy(h + offNums, primNums, (size_t)nPrims * 4);
     }
-    BSP_TRY(hipMemcpyAsync(d->dIn.p, h, inBytes, hipMemcpyHostToDevice, d->stream));
+    BSP_TRY(d->Upload(inBytes));
     char *di = (char *)d->dIn.p, *dO = (char *)d->dOut.p;
     const char *pr = (const char *)d->prims.p;
     Node nd;
@@ -224,7 +174,7 @@ int BspCostDeviceRun(BspCostDevice *d, const Edge *mesh, uint32_t nE, const floa
     // the layout of the workspace uses the lanes of a launch as its stride: every launch owns the whole workspace, and the two
     // launches of a node follow each other on one stream
     auto launch = [&](auto kernel, uint32_t first, uint32_t count) {
-        const uint32_t l = (uint32_t)std::min<size_t>(lanes, ((size_t)count + kWave - 1) / kWave * kWave);
+        const uint32_t l = d->Lanes(count);      // (at most `lanes`)
         hipLaunchKernelGGL(kernel, dim3(l / kWave), dim3(kWave), 0, d->stream, nd, sc, (const Cand *)(di + offCands), first, count, d->cap[0], d->cap[1],
                            d->cap[2], d->cap[3], (Q *)d->ws.p, l, dCosts, dFixed, dCounts, dOvf);
     };
@@ -232,8 +182,7 @@ int BspCostDeviceRun(BspCostDevice *d, const Edge *mesh, uint32_t nE, const floa
     BSP_TRY(hipGetLastError());
     if (planes) { if (kdAware) launch(k_bspcost<true, true>, (uint32_t)nAxis, (uint32_t)(n - nAxis)); else launch(k_bspcost<false, true>, (uint32_t)nAxis, (uint32_t)(n - nAxis)); }
     BSP_TRY(hipGetLastError());
-    BSP_TRY(hipMemcpyAsync(d->hOut.p, d->dOut.p, outBytes, hipMemcpyDeviceToHost, d->stream));
-    BSP_TRY(hipStreamSynchronize(d->stream));
+    BSP_TRY(d->Download(outBytes));
 #undef BSP_TRY
     const char *o = (const char *)d->hOut.p;
     std::memcpy(costs, o, n * 4);

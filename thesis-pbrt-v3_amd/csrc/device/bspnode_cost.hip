@@ -17,15 +17,13 @@
 #include <string>
 #include "../../../include/hprt.h"
 #include "../bspnode_cost_device.h"
+#include "cost_session.h"
 
 namespace hprt {
 namespace {
 
 using namespace bspnodecost;
 using bspcost::BitsF;
-
-constexpr uint32_t kWave = 64;
-constexpr uint32_t kWavesPerCU = 8;      // lanes in flight = CUs * kWavesPerCU * 64 at most
 
 template <bool FASTKD>
 __global__ __launch_bounds__(64) void k_sweepcost(Node nd, Scalars sc, const SweepDir *__restrict__ sweep, uint32_t nDirs, const Cand *__restrict__ cands,
@@ -83,51 +81,17 @@ __global__ __launch_bounds__(64) void k_sweepcost(Node nd, Scalars sc, const Swe
     }
 }
 
-// (Pinned, Dev and Pad16 are bsp_cost.hip's, repeated: that unit is left untouched so that its code object cannot move)
-struct Pinned {
-    void *p = nullptr; size_t bytes = 0;
-    hipError_t reserve(size_t b) {
-        if (b <= bytes) return hipSuccess;
-        if (p) (void)hipHostFree(p);
-        p = nullptr; bytes = 0;
-        b = std::max<size_t>(b + b / 2, 4096);
-        hipError_t e = hipHostMalloc(&p, b, hipHostMallocDefault);
-        if (e == hipSuccess) bytes = b; else p = nullptr;
-        return e;
-    }
-    ~Pinned() { if (p) (void)hipHostFree(p); }
-};
-struct Dev {
-    void *p = nullptr; size_t bytes = 0;
-    hipError_t reserve(size_t b, bool grow = true) {
-        if (b <= bytes) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr; bytes = 0;
-        b = std::max<size_t>(grow ? b + b / 2 : b, 4096);
-        hipError_t e = hipMalloc(&p, b);
-        if (e == hipSuccess) bytes = b; else p = nullptr;
-        return e;
-    }
-    ~Dev() { if (p) (void)hipFree(p); }
-};
-constexpr size_t Pad16(size_t b) { return (b + 15) & ~(size_t)15; }
-
 }  // namespace
 
-struct BspNodeCostDevice {
-    int device = 0;
+// hIn: mesh, directions, compact table, sweep directions, candidates; hOut: costs, costsFixed, overflow
+struct BspNodeCostDevice : CostSession {
     uint32_t cap[3] = {BSP_MAX_EDGES, BSP_MAX_FACES, BSP_MAX_FACE_EDGES};
-    uint32_t maxLanes = 0, wsLanes = 0;
-    hipStream_t stream = nullptr;
-    Pinned hIn, hOut;           // in: mesh, directions, compact table, sweep directions, candidates; out: costs, costsFixed, overflow
-    Dev dIn, dOut, ws;
-    ~BspNodeCostDevice() { if (stream) (void)hipStreamDestroy(stream); }
 };
 
 int BspNodeCostDeviceCreate(int device, const uint32_t caps[3], BspNodeCostDevice **out, std::string *err) {
     *out = nullptr;
     int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) { *err = "no HIP device available (the device-assisted build has no CPU fallback)"; return HPRT_E_NO_DEVICE; }
+    if (const int rc = CostDeviceCount(&n, err)) return rc;
     Scalars sc{};
     sc.maxEdges = caps[0]; sc.maxFaces = caps[1]; sc.maxFaceEdges = caps[2];
     uint32_t cap[4];
@@ -136,25 +100,14 @@ int BspNodeCostDeviceCreate(int device, const uint32_t caps[3], BspNodeCostDevic
                std::to_string(BSP_MAX_FACES) + ", " + std::to_string(BSP_MAX_FACE_EDGES) + ")";
         return HPRT_E_INVALID;
     }
-    if (device < 0) { if (hipGetDevice(&device) != hipSuccess) device = 0; }
-    if (device >= n) { *err = "device ordinal out of range"; return HPRT_E_INVALID; }
-    if (hipSetDevice(device) != hipSuccess) { *err = "hipSetDevice failed"; return HPRT_E_DEVICE; }
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) != hipSuccess) { *err = "hipGetDeviceProperties failed"; return HPRT_E_DEVICE; }
     BspNodeCostDevice *d = new BspNodeCostDevice();
-    d->device = device;
     for (int k = 0; k < 3; ++k) d->cap[k] = cap[k];
-    d->maxLanes = (uint32_t)std::max(1, prop.multiProcessorCount) * kWavesPerCU * kWave;
-    if (hipStreamCreate(&d->stream) != hipSuccess) { d->stream = nullptr; delete d; *err = "hipStreamCreate failed"; return HPRT_E_DEVICE; }
+    if (const int rc = d->Open(device, n, err)) { delete d; return rc; }
     *out = d;
     return HPRT_OK;
 }
 
-void BspNodeCostDeviceDestroy(BspNodeCostDevice *d) {
-    if (!d) return;
-    (void)hipSetDevice(d->device);
-    delete d;
-}
+void BspNodeCostDeviceDestroy(BspNodeCostDevice *d) { CostSessionDestroy(d); }
 
 int BspNodeCostDeviceRun(BspNodeCostDevice *d, const Edge *mesh, uint32_t nE, const float *dirs, uint32_t M, const uint32_t *cdir, uint32_t nD, bool fastKd,
                          const Scalars &sc, const SweepDir *sweep, uint32_t nDirs, const Cand *cands, size_t n, float *costs, float *costsFixed,
@@ -164,7 +117,7 @@ int BspNodeCostDeviceRun(BspNodeCostDevice *d, const Edge *mesh, uint32_t nE, co
         (fastKd && !costsFixed)) {
         *err = "k_sweepcost: a mesh, a direction list, a sweep or a candidate list beyond the kernel's bounds"; return HPRT_E_INVALID;
     }
-#define BSPNODE_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { *err = std::string("k_sweepcost launcher: ") + hipGetErrorString(e_); return HPRT_E_DEVICE; } } while (0)
+#define BSPNODE_TRY(x) COST_TRY("k_sweepcost", x)
     BSPNODE_TRY(hipSetDevice(d->device));
     // staging layout (16-byte aligned parts): in = mesh | directions | compact table | sweep directions | candidates;
     // out = costs | costsFixed (fastKd) | overflow
@@ -172,21 +125,16 @@ int BspNodeCostDeviceRun(BspNodeCostDevice *d, const Edge *mesh, uint32_t nE, co
     const size_t sweepBytes = (size_t)BSPNODE_MAX_SWEEP_DIRS * sizeof(SweepDir), candBytes = n * sizeof(Cand);
     const size_t offDirs = meshBytes, offCdir = offDirs + dirBytes, offSweep = offCdir + cdirBytes, offCands = offSweep + sweepBytes, inBytes = offCands + candBytes;
     const size_t costBytes = Pad16(n * 4), offOvf = (fastKd ? 2 : 1) * costBytes, outBytes = offOvf + n;
-    BSPNODE_TRY(d->hIn.reserve(inBytes)); BSPNODE_TRY(d->hOut.reserve(outBytes));
-    BSPNODE_TRY(d->dIn.reserve(inBytes)); BSPNODE_TRY(d->dOut.reserve(outBytes));
-    const uint32_t lanes = (uint32_t)std::min<size_t>(d->maxLanes, (n + kWave - 1) / kWave * kWave);
-    if (lanes > d->wsLanes) {
-        // the first node that fills the device sizes the workspace for the build: (4 BSP_MAX_EDGES + 2 BSP_MAX_FACES) words a lane
-        BSPNODE_TRY(d->ws.reserve((size_t)lanes * bspcost::kStoreWords * sizeof(Q), false));
-        d->wsLanes = lanes;
-    }
+    const uint32_t lanes = d->Lanes(n);
+    // the first node that fills the device sizes the workspace for the build: (4 BSP_MAX_EDGES + 2 BSP_MAX_FACES) words a lane
+    BSPNODE_TRY(d->Reserve(inBytes, outBytes, lanes, bspcost::kStoreWords * sizeof(Q), false));
     char *h = (char *)d->hIn.p;
     if (nE) std::memcpy(h, mesh, (size_t)nE * sizeof(Edge));
     std::memcpy(h + offDirs, dirs, (size_t)3 * M * 4);
     if (nD) std::memcpy(h + offCdir, cdir, (size_t)nD * 4);
     std::memcpy(h + offSweep, sweep, (size_t)nDirs * sizeof(SweepDir));
     std::memcpy(h + offCands, cands, candBytes);
-    BSPNODE_TRY(hipMemcpyAsync(d->dIn.p, h, inBytes, hipMemcpyHostToDevice, d->stream));
+    BSPNODE_TRY(d->Upload(inBytes));
     char *di = (char *)d->dIn.p, *dO = (char *)d->dOut.p;
     Node nd{};
     nd.mesh = (const Edge *)di; nd.nE = nE; nd.dirs = (const float *)(di + offDirs); nd.M = M; nd.cdir = (const uint32_t *)(di + offCdir); nd.nD = nD;
@@ -200,8 +148,7 @@ int BspNodeCostDeviceRun(BspNodeCostDevice *d, const Edge *mesh, uint32_t nE, co
         hipLaunchKernelGGL(k_sweepcost<false>, dim3(lanes / kWave), dim3(kWave), 0, d->stream, nd, sc, (const SweepDir *)(di + offSweep), nDirs,
                            (const Cand *)(di + offCands), (uint32_t)n, d->cap[0], d->cap[1], d->cap[2], (Q *)d->ws.p, lanes, dCosts, dFixed, dOvf);
     BSPNODE_TRY(hipGetLastError());
-    BSPNODE_TRY(hipMemcpyAsync(d->hOut.p, d->dOut.p, outBytes, hipMemcpyDeviceToHost, d->stream));
-    BSPNODE_TRY(hipStreamSynchronize(d->stream));
+    BSPNODE_TRY(d->Download(outBytes));
 #undef BSPNODE_TRY
     const char *o = (const char *)d->hOut.p;
     std::memcpy(costs, o, n * 4);

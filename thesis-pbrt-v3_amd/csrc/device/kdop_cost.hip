@@ -14,14 +14,12 @@
 #include <string>
 #include "../../../include/hprt.h"
 #include "../kdop_cost_device.h"
+#include "cost_session.h"
 
 namespace hprt {
 namespace {
 
 using namespace kdopcost;
-
-constexpr uint32_t kWave = 64;
-constexpr uint32_t kWavesPerCU = 8;      // lanes in flight = CUs * kWavesPerCU * 64 at most
 
 template <bool KD_AWARE>
 __global__ __launch_bounds__(64) void k_kdopcost(const Edge *__restrict__ mesh, uint32_t nE, const float *__restrict__ dirs, uint32_t M, Scalars sc,
@@ -55,68 +53,25 @@ __global__ __launch_bounds__(64) void k_kdopcost(const Edge *__restrict__ mesh, 
     }
 }
 
-struct Pinned {
-    void *p = nullptr; size_t bytes = 0;
-    hipError_t reserve(size_t b) {
-        if (b <= bytes) return hipSuccess;
-        if (p) (void)hipHostFree(p);
-        p = nullptr; bytes = 0;
-        b = std::max<size_t>(b + b / 2, 4096);
-        hipError_t e = hipHostMalloc(&p, b, hipHostMallocDefault);
-        if (e == hipSuccess) bytes = b; else p = nullptr;
-        return e;
-    }
-    ~Pinned() { if (p) (void)hipHostFree(p); }
-};
-struct Dev {
-    void *p = nullptr; size_t bytes = 0;
-    hipError_t reserve(size_t b) {
-        if (b <= bytes) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr; bytes = 0;
-        b = std::max<size_t>(b + b / 2, 4096);
-        hipError_t e = hipMalloc(&p, b);
-        if (e == hipSuccess) bytes = b; else p = nullptr;
-        return e;
-    }
-    ~Dev() { if (p) (void)hipFree(p); }
-};
-
 }  // namespace
 
-struct KdopCostDevice {
-    int device = 0;
-    uint32_t cap = KDOP_MAX_EDGES, maxLanes = 0, wsLanes = 0;
-    hipStream_t stream = nullptr;
-    Pinned hIn, hOut;           // in: mesh, directions, candidates; out: costs, costsFixed, overflow
-    Dev dIn, dOut, ws;
-    ~KdopCostDevice() { if (stream) (void)hipStreamDestroy(stream); }
+struct KdopCostDevice : CostSession {      // hIn: mesh, directions, candidates; hOut: costs, costsFixed, overflow
+    uint32_t cap = KDOP_MAX_EDGES;
 };
 
 int KdopCostDeviceCreate(int device, uint32_t maxEdges, KdopCostDevice **out, std::string *err) {
     *out = nullptr;
     int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) { *err = "no HIP device available (the device-assisted build has no CPU fallback)"; return HPRT_E_NO_DEVICE; }
+    if (const int rc = CostDeviceCount(&n, err)) return rc;
     if (maxEdges > KDOP_MAX_EDGES) { *err = "max_edges may only lower the compiled capacity (" + std::to_string(KDOP_MAX_EDGES) + ")"; return HPRT_E_INVALID; }
-    if (device < 0) { if (hipGetDevice(&device) != hipSuccess) device = 0; }
-    if (device >= n) { *err = "device ordinal out of range"; return HPRT_E_INVALID; }
-    if (hipSetDevice(device) != hipSuccess) { *err = "hipSetDevice failed"; return HPRT_E_DEVICE; }
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) != hipSuccess) { *err = "hipGetDeviceProperties failed"; return HPRT_E_DEVICE; }
     KdopCostDevice *d = new KdopCostDevice();
-    d->device = device;
     d->cap = maxEdges ? maxEdges : KDOP_MAX_EDGES;
-    d->maxLanes = (uint32_t)std::max(1, prop.multiProcessorCount) * kWavesPerCU * kWave;
-    if (hipStreamCreate(&d->stream) != hipSuccess) { d->stream = nullptr; delete d; *err = "hipStreamCreate failed"; return HPRT_E_DEVICE; }
+    if (const int rc = d->Open(device, n, err)) { delete d; return rc; }
     *out = d;
     return HPRT_OK;
 }
 
-void KdopCostDeviceDestroy(KdopCostDevice *d) {
-    if (!d) return;
-    (void)hipSetDevice(d->device);
-    delete d;
-}
+void KdopCostDeviceDestroy(KdopCostDevice *d) { CostSessionDestroy(d); }
 
 uint32_t KdopCostDeviceCapacity(const KdopCostDevice *d) { return d->cap; }
 
@@ -124,24 +79,19 @@ int KdopCostDeviceRun(KdopCostDevice *d, const Edge *mesh, uint32_t nE, const fl
                       const Cand *cands, size_t n, float *costs, float *costsFixed, uint8_t *overflow, std::string *err) {
     if (n == 0) return HPRT_OK;
     if (nE > d->cap || M > 13u || n > 0xffffffffull) { *err = "k_kdopcost: a mesh or a candidate list beyond the kernel's bounds"; return HPRT_E_INVALID; }
-#define KD_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { *err = std::string("k_kdopcost launcher: ") + hipGetErrorString(e_); return HPRT_E_DEVICE; } } while (0)
+#define KD_TRY(x) COST_TRY("k_kdopcost", x)
     KD_TRY(hipSetDevice(d->device));
     // staging layout (16-byte aligned parts): in = mesh | directions | candidates; out = costs | costsFixed | overflow
     const size_t meshBytes = (size_t)KDOP_MAX_EDGES * sizeof(Edge), dirBytes = 160, candBytes = n * sizeof(Cand);
-    const size_t costBytes = (n * 4 + 15) & ~(size_t)15;
+    const size_t costBytes = Pad16(n * 4);
     const size_t inBytes = meshBytes + dirBytes + candBytes, outBytes = 2 * costBytes + n;
-    KD_TRY(d->hIn.reserve(inBytes)); KD_TRY(d->hOut.reserve(outBytes));
-    KD_TRY(d->dIn.reserve(inBytes)); KD_TRY(d->dOut.reserve(outBytes));
-    const uint32_t lanes = (uint32_t)std::min<size_t>(d->maxLanes, (n + kWave - 1) / kWave * kWave);
-    if (lanes > d->wsLanes) {
-        KD_TRY(d->ws.reserve((size_t)lanes * kStoreWords * sizeof(Q)));
-        d->wsLanes = lanes;
-    }
+    const uint32_t lanes = d->Lanes(n);
+    KD_TRY(d->Reserve(inBytes, outBytes, lanes, kStoreWords * sizeof(Q), true));
     char *h = (char *)d->hIn.p;
     if (nE) std::memcpy(h, mesh, (size_t)nE * sizeof(Edge));
     std::memcpy(h + meshBytes, dirs, (size_t)3 * M * 4);
     std::memcpy(h + meshBytes + dirBytes, cands, candBytes);
-    KD_TRY(hipMemcpyAsync(d->dIn.p, h, inBytes, hipMemcpyHostToDevice, d->stream));
+    KD_TRY(d->Upload(inBytes));
     char *di = (char *)d->dIn.p, *dO = (char *)d->dOut.p;
     const dim3 grid(lanes / kWave), block(kWave);
     // the layout of the workspace uses the lanes of THIS launch as its stride: every launch owns the whole workspace
@@ -154,8 +104,7 @@ int KdopCostDeviceRun(KdopCostDevice *d, const Edge *mesh, uint32_t nE, const fl
                            (const Cand *)(di + meshBytes + dirBytes), (uint32_t)n, d->cap, (Q *)d->ws.p, lanes, (float *)dO, (float *)(dO + costBytes),
                            (uint8_t *)(dO + 2 * costBytes));
     KD_TRY(hipGetLastError());
-    KD_TRY(hipMemcpyAsync(d->hOut.p, d->dOut.p, outBytes, hipMemcpyDeviceToHost, d->stream));
-    KD_TRY(hipStreamSynchronize(d->stream));
+    KD_TRY(d->Download(outBytes));
 #undef KD_TRY
     const char *o = (const char *)d->hOut.p;
     std::memcpy(costs, o, n * 4);

@@ -8,7 +8,6 @@
 // The winner's two halves are then cut and measured once more, exactly as the scan left them.
 #include "rbsp_builder.h"
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -211,33 +210,16 @@ std::string BuildRbspTree(size_t n, const float *bmin, const float *bmax, const 
             }
         };
         // the costing hook (RbspParams::costFn): the node's candidates costed elsewhere, the flagged ones repaired here
-        bool costed = false;
-        if (p.costFn && !cands.empty() && cands.size() >= p.costMinCandidates) {
-            overflow.assign(cands.size(), 0);
-            RbspCostRequest rq;
+        std::string hookErr;
+        const HookResult hooked = RunCostHook(p, cands.size(), overflow, true, [&](RbspCostRequest &rq) {
             rq.mesh = reinterpret_cast<const kdopcost::Edge *>(cur.mesh.data()); rq.nEdges = (uint32_t)cur.mesh.size();
             rq.dirs = dirs; rq.M = M; rq.kdAware = p.kdAware;
             rq.sc = kdopcost::Scalars{invTotalSA, emptyBonus, isectCost, traversalCost, kdTraversalCost, cur.nPrimitives, 0u};
             rq.cands = cands.data(); rq.n = cands.size();
             rq.costs = costs.data(); rq.costsFixed = p.kdAware ? costsFixed.data() : nullptr; rq.overflow = overflow.data();
-            std::string err;
-            const auto t0 = std::chrono::steady_clock::now();
-            const int rc = p.costFn(rq, &err);
-            if (rc < 0) return err.empty() ? std::string("the costing hook failed") : err;
-            if (rc == 0) {
-                costed = true;
-                uint64_t redo = 0;
-                for (size_t k = 0; k < cands.size(); ++k)
-                    if (overflow[k]) { costRange(k, k + 1, scratch[0]); ++redo; }
-                if (p.stats) {
-                    p.stats->secondsDevice += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-                    ++p.stats->nodesDevice; p.stats->candidatesDevice += cands.size() - redo; p.stats->candidatesRecosted += redo;
-                }
-                if (p.costDone) p.costDone(rq);
-            }
-        }
-        if (!costed && p.stats) ++p.stats->nodesHost;
-        if (costed) {
+        }, [&](size_t k) { costRange(k, k + 1, scratch[0]); }, &hookErr);
+        if (hooked == HookResult::Failed) return hookErr;
+        if (hooked == HookResult::Costed) {
             // (costs[] is complete)
         } else if (nThreads > 1 && cands.size() >= kParallelCandidates) {
             const size_t chunk = (cands.size() + nThreads - 1) / nThreads;

@@ -10,6 +10,7 @@
 #include <string>
 #include <vector>
 #include "bsp_tree.h"
+#include "cost_hook.h"
 #include "kdop_cost.h"
 
 namespace hprt {
@@ -35,9 +36,9 @@ struct RbspCostRequest {
     float *costs, *costsFixed;            // costsFixed: NULL unless kdAware
     uint8_t *overflow;
 };
-struct RbspBuildStats { uint64_t nodesDevice = 0, candidatesDevice = 0, candidatesRecosted = 0, nodesHost = 0; double secondsDevice = 0; };
 
-struct RbspParams {
+// costFn, costMinCandidates, stats, costDone: the costing hook (cost_hook.h; the device-assisted build, hprt_rbsp_build_device)
+struct RbspParams : CostHook<RbspCostRequest> {
     int isectCost = 80, travCost = 5;     // "intersectcost", "traversalcost"
     float emptyBonus = 0.f;               // "emptybonus"
     int maxPrims = 1, maxDepth = -1;      // "maxprims", "maxdepth" (-1: round(2 + 1.6 Log2Int(N)), core/geometry.h:1845)
@@ -48,16 +49,6 @@ struct RbspParams {
     // chosen, and travCost + C_isect for a second minimum that only the leaf tests read.
     bool kdAware = false;
     int kdTravCost = 1;                   // "kdtraversalcost"
-    // Optional costing hook (the device-assisted build, hprt_rbsp_build_device): a node with at least costMinCandidates
-    // candidates is handed to costFn instead of the thread pool.  It fills costs / costsFixed / overflow for every candidate
-    // and returns 0; the builder then re-costs the candidates flagged in overflow with costRange's own code.  1: the hook
-    // declines the node (a mesh beyond its capacity) and the node takes the host path; < 0: the build fails with *err.
-    // Smaller nodes, and all nodes when costFn is empty, take the host path.  The scan over costs[] is the same either way.
-    std::function<int(const RbspCostRequest &, std::string *err)> costFn;
-    uint32_t costMinCandidates = 1024;    // (kdop::kParallelCandidates)
-    RbspBuildStats *stats = nullptr;      // filled when costFn is set
-    // Diagnostics: called for a node costFn has handled, after the repair, with the costs the scan is about to read
-    std::function<void(const RbspCostRequest &)> costDone;
 };
 
 struct RbspTree {
