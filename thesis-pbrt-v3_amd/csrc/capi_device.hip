@@ -50,12 +50,13 @@ struct Workspace {
     PathStream path[2];
     HitStream hit;
     VertexStreams vs;
+    float4 *pend[2];        // the two planes of vs.pendBeta / vs.pendPrev: bounce b writes pend[b & 1] (RunBatch)
     float4 *Lfinal;
 };
 // 16-byte words per stream index: 2 x (ray a,b + beta + L) + hit a + shadow a,b + mis a,b + misHit a
-// + pendLight/Mis/Beta + Lfinal; plus occluded (1 B) and alignment slack.  A render reads the second word of a hit record
+// + pendLight/Mis + 2 x pendBeta + Lfinal; plus occluded (1 B) and alignment slack.  A render reads the second word of a hit record
 // ({t, instance}, HitStream::b) for the instance alone, so only scenes with object instances get those planes (8 B each, path hit and MIS hit).
-const size_t kPlaneBytesPerSlot = 16 * (2 * 4 + 1 + 2 + 2 + 1 + 3 + 1) + 1, kInstancePlaneBytesPerSlot = 8 + 8;
+const size_t kPlaneBytesPerSlot = 16 * (2 * 4 + 1 + 2 + 2 + 1 + 4 + 1) + 1, kInstancePlaneBytesPerSlot = 8 + 8;
 size_t PlaneBytesPerSlot(bool instances) { return kPlaneBytesPerSlot + (instances ? kInstancePlaneBytesPerSlot : 0); }
 size_t PlaneBytes(size_t n, bool instances) { return n * PlaneBytesPerSlot(instances) + 32 * 256; }
 
@@ -66,7 +67,9 @@ void CarvePlanes(char *base, size_t n, bool instances, Workspace *w) {
     w->hit.a = a.take<float4>(n); w->hit.b = instances ? a.take<float2>(n) : nullptr;
     rays(w->vs.shadow); w->vs.occluded = a.take<uint8_t>(n);
     rays(w->vs.mis); w->vs.misHit.a = a.take<float4>(n); w->vs.misHit.b = instances ? a.take<float2>(n) : nullptr;
-    w->vs.pendLight = a.take<float4>(n); w->vs.pendMis = a.take<float4>(n); w->vs.pendBeta = a.take<float4>(n);
+    w->vs.pendLight = a.take<float4>(n); w->vs.pendMis = a.take<float4>(n);
+    for (int k = 0; k < 2; ++k) w->pend[k] = a.take<float4>(n);
+    w->vs.pendBeta = w->pend[0]; w->vs.pendPrev = w->pend[1];
     w->Lfinal = a.take<float4>(n);
 }
 
@@ -281,6 +284,15 @@ static bool SpeculateLightEnabled() {
     return g_speculateLight < 0 ? fromEnv : g_speculateLight != 0;
 }
 __attribute__((visibility("default"))) int hprt_debug_speculate_light(int on) { const int was = SpeculateLightEnabled() ? 1 : 0; g_speculateLight = on; return was; }
+// HPRT_FOLD_REPAIR=0 in the environment, or hprt_debug_fold_repair(0) at run time (diagnostics hook, not part of include/hprt.h): every
+// speculated vertex's shadow ray goes through k_repair and no path segment is marked, as before the repair was folded into the next
+// bounce's readers (A/B runs, tests).  Returns the setting before.
+static int g_foldRepair = -1;
+static bool FoldRepairEnabled() {
+    static const bool fromEnv = [] { const char *e = getenv("HPRT_FOLD_REPAIR"); return !(e && atoi(e) == 0); }();
+    return g_foldRepair < 0 ? fromEnv : g_foldRepair != 0;
+}
+__attribute__((visibility("default"))) int hprt_debug_fold_repair(int on) { const int was = FoldRepairEnabled() ? 1 : 0; g_foldRepair = on; return was; }
 __attribute__((visibility("default"))) int hprt_debug_poison_workspace(HprtScene *s, int byte) { if (!s) return HPRT_E_INVALID; s->poisonByte = byte < 0 ? -1 : (byte & 255); return HPRT_OK; }
 // Diagnostics hook (not part of include/hprt.h): the first batch of the next hprt_render copies the rays that bounce `bounce` queues
 // (kind 0: the path segments entering bounce + 1, 1: its shadow rays, 2: its BSDF-sampled light rays) into d_out7 ([7][cap] planes:
@@ -894,7 +906,12 @@ struct BatchTimers { double extendMs = 0, occludedMs = 0; uint64_t extendLaunche
 // pixelStats (or null): [6][nPix] per-pixel counters of the local pixels, fed from the per-ray counts of every trace
 //
 // Per bounce b:   trace(path b) -> bin -> shade x3 -> [counts to the host] -> trace(shadow b) | trace(MIS b) | trace(path b+1)
-//                 -> resolve(b) (vertices with an MIS ray, if any) -> repair(b) (occluded speculated vertices) -> bin(b+1) ...
+//                 -> resolve(b) (vertices with an MIS ray, if any) -> repair(b) -> bin(b+1) ...
+// repair(b) sets right the speculated vertices of b whose shadow ray was blocked AND whose path ends there (QueueSet::end; no launch when
+// there are none).  A blocked speculated vertex whose path goes on is set right where its radiance is read next: bin(b+1) for a path that
+// ends at the bin, else shade(b+1) — they take the record of plane b & 1 instead of out.L when the segment carries RAY_FOLD_MARK and
+// occluded[] is set, while shade(b+1) writes its own records to the other plane.  HPRT_FOLD_REPAIR=0, or a render that counts the
+// speculated vertices, sends every shadow ray of b through repair(b) as before and marks nothing.
 // The three traces that follow a shading pass depend on nothing but that pass.  Running them on three HIP streams (so that
 // each fills the tails of the others' persistent kernels) was built and measured in round 2: SLOWER — atrium 1024 spp
 // 1064 -> 1119 ms, living room 455 -> 478 ms, killeroo-simple 90.6 -> 91.8 ms (every persistent kernel is sized to fill the
@@ -909,6 +926,10 @@ int RunBatch(HprtScene *s, hipStream_t st, const RenderParams &rpIn, const Works
     RenderParams rp = rpIn;
     rp.speculate = SpeculateLightEnabled() && !pixelStats && !rayStats && nSlots <= SPEC_MAX_PATHS ? 1 : 0;
     assert(!rp.speculate || nSlots <= SPEC_MAX_PATHS);
+    // Folded repair: a blocked speculated vertex whose path goes on is set right by the next bounce's reader of its radiance (k_shade, k_bin:
+    // RAY_FOLD_MARK), and k_repair runs over the vertices at which a path ends (QueueSet::end) alone.  A counting render of the tests
+    // (shadeCountsOn) keeps every shadow ray in k_repair: that is where the speculated and the repaired vertices are counted.
+    rp.foldRepair = rp.speculate && FoldRepairEnabled() && !s->shadeCountsOn ? 1 : 0;
     uint32_t *specCounts = rp.speculate && s->shadeCountsOn ? s->queueCounts.as<uint32_t>() + kSpecCountsAt : nullptr;
     if (specCounts) HIP_TRY(hipMemsetAsync(specCounts, 0, 2 * sizeof(uint32_t), st));
     uint32_t *pixelKd = pixelStats && CountsKdShare(s) ? s->pixelKdLocal.as<uint32_t>() : nullptr;     // the rbspkd / bsppaperkd walk's kd share
@@ -934,9 +955,12 @@ int RunBatch(HprtScene *s, hipStream_t st, const RenderParams &rpIn, const Works
     for (int bounce = 0; active > 0; ++bounce) {
         const QueueSet &cur = q[bounce & 1];
         const PathStream &in = w.path[bounce & 1], &out = w.path[(bounce + 1) & 1];
-        HIP_TRY(hipMemsetAsync(cur.nextCount, 0, 256 * sizeof(uint32_t), st));   // the four counters, 64 words apart
+        // this bounce's records go to one plane while its readers (k_bin, k_shade) still find the bounce before's in the other
+        VertexStreams vs = w.vs;
+        vs.pendBeta = w.pend[bounce & 1]; vs.pendPrev = w.pend[(bounce + 1) & 1];
+        HIP_TRY(hipMemsetAsync(cur.nextCount, 0, 256 * sizeof(uint32_t), st));   // the five counters (EnsureWorkspace)
         HIP_TRY(hipMemsetAsync(bins.count, 0, 8 * BIN_STRIDE * sizeof(uint32_t), st));
-        LaunchBin(st, s->dev, in, w.hit, activeQ, nullptr, active, active, rp.maxDepth, bounce, bins, w.Lfinal);
+        LaunchBin(st, s->dev, in, w.hit, activeQ, nullptr, active, active, rp.maxDepth, bounce, bins, w.Lfinal, vs, rp.foldRepair != 0);
         HIP_TRY(hipMemcpyAsync(bins.count + 5 * BIN_STRIDE, bins.count + 2 * BIN_STRIDE, sizeof(uint32_t), hipMemcpyDeviceToDevice, st));   // bin 2 before deferrals
         // one launch per material bin; grids are sized for the upper bound, surplus blocks exit on the bin's count
         // (the specialised variants first: they may hand vertices over to the generic one; bin 3: vertices on image-textured materials)
@@ -944,7 +968,7 @@ int RunBatch(HprtScene *s, hipStream_t st, const RenderParams &rpIn, const Works
         for (int k = 0; k < (s->dev.textures ? 5 : 4); ++k) {
             const int mode = order[k];
             if (mode == (int)BIN_SUBSTRATE && !s->hasSubstrateBin) continue;
-            LaunchShade(st, mode, s->dev, rp, in, w.hit, active, s0, out, w.vs, cur, bins, w.Lfinal, bounce == 0);
+            LaunchShade(st, mode, s->dev, rp, in, w.hit, active, s0, out, vs, cur, bins, w.Lfinal, bounce == 0);
         }
         HIP_TRY(hipMemcpyAsync(s->hostCounts + 4096, cur.nextCount, 256 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         if (s->shadeCountsOn) {      // (tests only) bin 2 after the deferrals and as binned
@@ -966,17 +990,18 @@ int RunBatch(HprtScene *s, hipStream_t st, const RenderParams &rpIn, const Works
                 s->voxRowsUsed += nReq;
                 HIP_TRY(hipMemsetAsync(s->dev.voxRequestCount, 0, sizeof(uint32_t), st));
                 for (int r = 0; r < 2; ++r)
-                    if (nRetry[r]) LaunchShade(st, 2 + r, s->dev, rp, in, w.hit, nRetry[r], s0, out, w.vs, cur, bins, w.Lfinal, bounce == 0, true);
+                    if (nRetry[r]) LaunchShade(st, 2 + r, s->dev, rp, in, w.hit, nRetry[r], s0, out, vs, cur, bins, w.Lfinal, bounce == 0, true);
                 HIP_TRY(hipMemcpyAsync(s->hostCounts + 4096, cur.nextCount, 256 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
             }
         }
         HIP_TRY(hipStreamSynchronize(st));
         if (s->shadeCountsOn) s->shadeDeferred += s->hostCounts[12] - s->hostCounts[13];
         const uint32_t nNext = s->hostCounts[4096], nShadow = s->hostCounts[4096 + 64], nMis = s->hostCounts[4096 + 128], nResolve = s->hostCounts[4096 + 192];
+        const uint32_t nEnd = s->hostCounts[4096 + 32];
         if (s->capture.out7 && s->capture.bounce == bounce && s0 == 0) {      // diagnostics (hprt_debug_capture_rays)
             const uint32_t *cq = s->capture.kind == 0 ? cur.next : s->capture.kind == 1 ? cur.shadow : cur.mis;
             const uint32_t cn = s->capture.kind == 0 ? nNext : s->capture.kind == 1 ? nShadow : nMis;
-            const RayStream &cs = s->capture.kind == 0 ? out.ray : s->capture.kind == 1 ? w.vs.shadow : w.vs.mis;
+            const RayStream &cs = s->capture.kind == 0 ? out.ray : s->capture.kind == 1 ? vs.shadow : vs.mis;
             LaunchCaptureRays(st, cq, cn, cs, s->capture.out7, (uint32_t)s->capture.cap);
             s->capture.n = std::min<size_t>(cn, s->capture.cap);
         }
@@ -984,9 +1009,9 @@ int RunBatch(HprtScene *s, hipStream_t st, const RenderParams &rpIn, const Works
             hipEvent_t a = ev.get(), b = ev.get();
             HIP_TRY(hipEventRecord(a, st));
             HitStream none; none.a = nullptr; none.b = nullptr;
-            Trace(s, st, true, count, cur.shadow, nullptr, nShadow, nShadow, w.vs.shadow, none, w.vs.occluded, ctr, wcPath, rayStats);
-            if (pixelStats) LaunchPixelStats(st, rayStats, w.vs.pendBeta, cur.shadow, nullptr, nShadow, nShadow, rp.nPix, true, pixelStats);
-            if (pixelKd) LaunchPixelKdStats(st, rayStats, w.vs.pendBeta, cur.shadow, nullptr, nShadow, nShadow, rp.nPix, true, pixelKd);
+            Trace(s, st, true, count, cur.shadow, nullptr, nShadow, nShadow, vs.shadow, none, vs.occluded, ctr, wcPath, rayStats);
+            if (pixelStats) LaunchPixelStats(st, rayStats, vs.pendBeta, cur.shadow, nullptr, nShadow, nShadow, rp.nPix, true, pixelStats);
+            if (pixelKd) LaunchPixelKdStats(st, rayStats, vs.pendBeta, cur.shadow, nullptr, nShadow, nShadow, rp.nPix, true, pixelKd);
             HIP_TRY(hipEventRecord(b, st));
             evOcc.push_back({a, b}); bt->occludedRays += nShadow; ++bt->occludedLaunches;
             stats->shadow_rays += nShadow;
@@ -994,9 +1019,9 @@ int RunBatch(HprtScene *s, hipStream_t st, const RenderParams &rpIn, const Works
         if (nMis) {
             hipEvent_t a = ev.get(), b = ev.get();
             HIP_TRY(hipEventRecord(a, st));
-            Trace(s, st, false, count, cur.mis, nullptr, nMis, nMis, w.vs.mis, w.vs.misHit, nullptr, ctr, wcPath, rayStats);
-            if (pixelStats) LaunchPixelStats(st, rayStats, w.vs.pendBeta, cur.mis, nullptr, nMis, nMis, rp.nPix, false, pixelStats);
-            if (pixelKd) LaunchPixelKdStats(st, rayStats, w.vs.pendBeta, cur.mis, nullptr, nMis, nMis, rp.nPix, false, pixelKd);
+            Trace(s, st, false, count, cur.mis, nullptr, nMis, nMis, vs.mis, vs.misHit, nullptr, ctr, wcPath, rayStats);
+            if (pixelStats) LaunchPixelStats(st, rayStats, vs.pendBeta, cur.mis, nullptr, nMis, nMis, rp.nPix, false, pixelStats);
+            if (pixelKd) LaunchPixelKdStats(st, rayStats, vs.pendBeta, cur.mis, nullptr, nMis, nMis, rp.nPix, false, pixelKd);
             HIP_TRY(hipEventRecord(b, st));
             evExt.push_back({a, b}); bt->extendRays += nMis; ++bt->extendLaunches;
             stats->rays += nMis;
@@ -1005,8 +1030,9 @@ int RunBatch(HprtScene *s, hipStream_t st, const RenderParams &rpIn, const Works
         // (maxDepth is bounded by CheckDepth, and no path outlives bounce maxDepth)
         if (active > 0 && bounce > rp.maxDepth) return SetError(HPRT_E_DEVICE, "internal error: paths are still active beyond maxdepth");
         // the full vertices' direct lighting, then the speculated vertices whose shadow ray was blocked (disjoint sets of vertices)
-        if (nResolve) LaunchResolve(st, s->dev, w.vs, out.L, w.Lfinal, cur.resolve, cur.resolveCount, nResolve);
-        if (rp.speculate && nShadow) LaunchRepair(st, w.vs, out.L, w.Lfinal, cur.shadow, nShadow, specCounts);
+        if (nResolve) LaunchResolve(st, s->dev, vs, out.L, w.Lfinal, cur.resolve, cur.resolveCount, nResolve);
+        if (rp.foldRepair) { if (nEnd) LaunchRepair(st, vs, out.L, w.Lfinal, cur.end, nEnd, nullptr); }
+        else if (rp.speculate && nShadow) LaunchRepair(st, vs, out.L, w.Lfinal, cur.shadow, nShadow, specCounts);
         if (s->shadeCountsOn) s->shadeFull += nResolve;
         if (active > 0) { int rc = tracePath(bounce + 1); if (rc != HPRT_OK) return rc; }
     }
@@ -1020,8 +1046,8 @@ int RunBatch(HprtScene *s, hipStream_t st, const RenderParams &rpIn, const Works
     return HPRT_OK;
 }
 
-// words of s->queues per path: two QueueSets of four index queues, the deferral indices (BinSet::aux) and five bins of 8-byte entries
-constexpr size_t kQueueWordsPerSlot = 8 + 1 + 2 * N_BINS;
+// words of s->queues per path: two QueueSets of five index queues, the deferral indices (BinSet::aux) and five bins of 8-byte entries
+constexpr size_t kQueueWordsPerSlot = 10 + 1 + 2 * N_BINS;
 int EnsureWorkspace(HprtScene *s, size_t nSlots, Workspace *ps, QueueSet *qa, QueueSet *qb, BinSet *bins) {
     const bool instances = s->dev.nInstances != 0u;
     HIP_TRY(s->planes.alloc(PlaneBytes(nSlots, instances)));
@@ -1031,13 +1057,15 @@ int EnsureWorkspace(HprtScene *s, size_t nSlots, Workspace *ps, QueueSet *qa, Qu
     uint32_t *qbase = s->queues.as<uint32_t>(), *cbase = s->queueCounts.as<uint32_t>();
     QueueSet *qs[2] = {qa, qb};
     for (int k = 0; k < 2; ++k) {
-        qs[k]->next = qbase + (4 * k + 0) * nSlots; qs[k]->shadow = qbase + (4 * k + 1) * nSlots;
-        qs[k]->mis = qbase + (4 * k + 2) * nSlots; qs[k]->resolve = qbase + (4 * k + 3) * nSlots;
-        // one counter per 256-byte line: atomics of different queues do not serialise on a shared line
+        qs[k]->next = qbase + (5 * k + 0) * nSlots; qs[k]->shadow = qbase + (5 * k + 1) * nSlots;
+        qs[k]->mis = qbase + (5 * k + 2) * nSlots; qs[k]->resolve = qbase + (5 * k + 3) * nSlots; qs[k]->end = qbase + (5 * k + 4) * nSlots;
+        // one counter per 256-byte line: atomics of different queues do not serialise on a shared line (the end queue's, rarely
+        // touched, sits half a line behind nextCount: the set's 256 words are still cleared and copied to the host as one block)
         qs[k]->nextCount = cbase + 256 * k; qs[k]->shadowCount = cbase + 256 * k + 64; qs[k]->misCount = cbase + 256 * k + 128; qs[k]->resolveCount = cbase + 256 * k + 192;
+        qs[k]->endCount = cbase + 256 * k + 32;
     }
-    bins->aux = qbase + 8 * nSlots;
-    for (int k = 0; k < (int)N_BINS; ++k) bins->q[k] = reinterpret_cast<uint2 *>(qbase + (9 + 2 * k) * nSlots + (nSlots & 1u));      // (8-byte entries, 8-byte aligned)
+    bins->aux = qbase + 10 * nSlots;
+    for (int k = 0; k < (int)N_BINS; ++k) bins->q[k] = reinterpret_cast<uint2 *>(qbase + (11 + 2 * k) * nSlots + (nSlots & 1u));      // (8-byte entries, 8-byte aligned)
     bins->count = cbase + 512;
     bins->retry[0] = bins->retry[1] = nullptr;
     if (s->dev.voxSlot) {      // (on-demand voxel tables only)
@@ -1145,7 +1173,7 @@ int hprt_render(HprtScene *s, const HprtRenderDesc *desc, float *d_film_xyzw, vo
     const bool wantPixelStats = (desc->flags & HPRT_RENDER_PIXEL_STATS) != 0;
     const bool count = (desc->flags & HPRT_RENDER_COUNT_WORK) != 0 || wantPixelStats;
     // a counting render traces exactly the reference's rays (its counters are the reference's) unless asked to count what a plain render traces
-    rp.speculate = 0;      // (RunBatch decides, batch by batch)
+    rp.speculate = rp.foldRepair = 0;      // (RunBatch decides, batch by batch)
     rp.cullMis = (!count || (desc->flags & HPRT_RENDER_COUNT_TRACED) != 0) && !(desc->flags & HPRT_RENDER_TRACE_ALL) ? 1 : 0;
     uint32_t *pixelStats = nullptr;
     if (wantPixelStats) {
@@ -1392,7 +1420,7 @@ int hprt_sample_radiance(HprtScene *s, const HprtRenderOptions *opt, size_t n, c
     rp.hal.samplePixelCenter = opt->sample_pixel_center;
     rp.pixelXY = s->pixelXY.as<uint32_t>(); rp.pixelOffset = s->pixelOffset.as<uint64_t>(); rp.nPix = (uint32_t)n;
     rp.maxDepth = opt->max_depth; rp.rrThreshold = opt->rr_threshold;
-    rp.invSqrtSpp = 1 / std::sqrt((float)std::max(1, opt->spp)); rp.cullMis = 1; rp.speculate = 0;      // (RunBatch decides)
+    rp.invSqrtSpp = 1 / std::sqrt((float)std::max(1, opt->spp)); rp.cullMis = 1; rp.speculate = rp.foldRepair = 0;      // (RunBatch decides)
     EventTimer ev; BatchTimers bt; HprtRenderStats stats; memset(&stats, 0, sizeof(stats));
     rc = RunBatch(s, nullptr, rp, ps, qa, qb, bins, 0, (uint32_t)n, false, ev, &bt, &stats);
     if (rc != HPRT_OK) return rc;

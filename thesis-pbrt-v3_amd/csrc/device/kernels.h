@@ -40,10 +40,14 @@ __host__ __device__ __forceinline__ float hit_b2(const float4 &rec) { return rec
 __host__ __device__ __forceinline__ float hit_t(const float2 &aux) { return aux.x; }
 __host__ __device__ __forceinline__ int32_t hit_inst(const float2 &aux) { return __builtin_bit_cast(int32_t, aux.y); }
 struct PathStream {
-    RayStream ray;          // current path segment; ray.b.w = sampler dimension (bits 0-15) | bounces (bits 16-30) | the segment left a specular lobe (bit 31)
+    RayStream ray;          // current path segment; ray.b.w = sampler dimension (bits 0-15) | bounces (bits 16-29) | RAY_FOLD_MARK (bit 30) | the segment left a specular lobe (bit 31)
     float4 *beta;           // {beta.rgb, path id}   path id = sampleInBatch * nPix + pixel
     float4 *L;              // {L.rgb, w}: w = 0 if the path ends at this vertex, else its etaScale (1 until it crosses a dielectric boundary)
 };
+// Fields of ray.b.w.  The bounce count keeps 14 bits (CheckDepth bounds maxdepth at 123).  RAY_FOLD_MARK: the vertex this segment leaves
+// is a speculated one whose repair is left to the segment's reader (RenderParams::foldRepair) — only then does vs.occluded[that vertex]
+// mean anything to the reader: a vertex without a shadow ray leaves the byte of an earlier bounce or batch there.
+enum : uint32_t { RAY_DIM_MASK = 0xffffu, RAY_BOUNCE_SHIFT = 16u, RAY_BOUNCE_MASK = 0x3fffu, RAY_FOLD_MARK = 0x40000000u, RAY_SPECULAR = 0x80000000u };
 // What a shading pass leaves for the rest of its bounce, indexed like its output PathStream
 struct VertexStreams {
     RayStream shadow; uint8_t *occluded;             // shadow ray of the light sample, its any-hit result
@@ -55,15 +59,21 @@ struct VertexStreams {
     float4 *pendBeta;       // {beta before this vertex rgb, path id}
     // A SPECULATED vertex (a shadow ray and no MIS ray, RenderParams::speculate on) leaves one record in pendBeta instead and nothing in the
     // other two streams or the resolve queue: {radiance if the shadow ray is blocked rgb, path id | SPEC_RECORD | SPEC_END if the path ends
-    // here}.  Its radiance if the ray is not blocked is already in out.L[j] (in Lfinal[path id] if the path ends here); k_repair puts the
-    // record's value there once the ray has turned out blocked.
+    // here}.  Its radiance if the ray is not blocked is already in out.L[j] (in Lfinal[path id] if the path ends here).  Where the ray has
+    // turned out blocked the record's value stands for it: k_repair puts it there, or — RenderParams::foldRepair, for a vertex whose path
+    // goes on — the next bounce's reader of out.L[j] (k_shade, k_bin) takes the record instead (RAY_FOLD_MARK).
+    // pendBeta is one of two planes, alternated by bounce parity like the path streams: the readers of bounce b + 1 find bounce b's records
+    // in pendPrev while k_shade(b + 1) writes its own at unrelated indices.  occluded needs no second plane: the any-hit walk of b + 1
+    // writes it after those readers have run.
+    const float4 *pendPrev;
 };
 // Flag bits of a speculated vertex's record word.  Path ids stay below 2^28: a batch holds at most 256 M paths (ChooseBatch), and RunBatch
 // keeps a larger one (a caller's spp_chunk) on the full path.
 enum : uint32_t { SPEC_RECORD = 0x80000000u, SPEC_END = 0x40000000u, SPEC_ID_MASK = 0x0fffffffu, SPEC_MAX_PATHS = 1u << 28 };
+// end (RenderParams::foldRepair): the speculated vertices at which a path ends — no later reader, so k_repair runs over these alone
 struct QueueSet {
-    uint32_t *next, *shadow, *mis, *resolve;
-    uint32_t *nextCount, *shadowCount, *misCount, *resolveCount;
+    uint32_t *next, *shadow, *mis, *resolve, *end;
+    uint32_t *nextCount, *shadowCount, *misCount, *resolveCount, *endCount;
 };
 // material bins (BIN_*, dev_scene.h): 0 matte, 1 plastic, 2 generic, 3 generic on an image-textured material (the variant compiled
 // with the MIPMap lookups: scenes with textures only), 4 substrate.  count[k * BIN_STRIDE], k = 0..4: sizes; k = 5: size of bin 2
@@ -88,6 +98,8 @@ struct RenderParams {
                                     // cannot reach its emitter, the segment behind the last vertex of a path
     int32_t speculate;              // k_shade adds the light sample of a vertex with a shadow ray and no MIS ray at once (k_repair undoes the
                                     // blocked ones); 0: every such vertex goes through the pending streams and k_resolve
+    int32_t foldRepair;             // (with speculate) a blocked speculated vertex whose path goes on is repaired by the next bounce's reader of its
+                                    // radiance (RAY_FOLD_MARK); k_repair handles QueueSet::end only.  0: every shadow ray through k_repair, no mark
 };
 struct FilmGeom {
     int32_t cx0, cy0, cx1, cy1;     // croppedPixelBounds
@@ -139,13 +151,13 @@ void LaunchGenerate(hipStream_t st, const DevScene &sc, const RenderParams &rp, 
                     const IrregularSink *irr = nullptr);
 void LaunchBin(hipStream_t st, const DevScene &sc, const PathStream &in, const HitStream &hit, const uint32_t *queue,
                const uint32_t *countPtr, uint32_t countImm, uint32_t gridItems, int32_t maxDepth, int32_t bounces, const BinSet &bins,
-               float4 *Lfinal);
+               float4 *Lfinal, const VertexStreams &vs, bool foldRepair);
 void LaunchShade(hipStream_t st, int mode, const DevScene &sc, const RenderParams &rp, const PathStream &in, const HitStream &hit,
                  uint32_t gridItems, uint32_t s0, const PathStream &out, const VertexStreams &vs, const QueueSet &q,
                  const BinSet &bins, float4 *Lfinal, bool firstBounce, bool retryPass = false);
 void LaunchResolve(hipStream_t st, const DevScene &sc, const VertexStreams &vs, float4 *L, float4 *Lfinal, const uint32_t *queue,
                    const uint32_t *countPtr, uint32_t gridItems);
-// counts (tests only, else null): {speculated, repaired} += this launch's
+// queue: the bounce's shadow rays, or (RenderParams::foldRepair) its QueueSet::end.  counts (tests only, else null): {speculated, repaired} += this launch's
 void LaunchRepair(hipStream_t st, const VertexStreams &vs, float4 *L, float4 *Lfinal, const uint32_t *queue, uint32_t n, uint32_t *counts);
 void LaunchStoreRadiance(hipStream_t st, const float4 *Lfinal, float *LallR, float *LallG, float *LallB, uint32_t nPix, uint32_t s0,
                          uint32_t nSlots);

@@ -10,7 +10,8 @@
 //     k_trace<any>      shadow rays          BVHAccel::IntersectP (VisibilityTester::Unoccluded)
 //     k_trace<closest>  MIS rays             scene.Intersect at core/integrator.cpp:195
 //     k_resolve         L += beta * Ld / lightPdf, in bounce order (vertices with an MIS ray; every vertex on the old path)
-//     k_repair          the dark value for the speculated vertices whose shadow ray was blocked
+//     k_repair          the dark value for the speculated vertices whose shadow ray was blocked and whose path ends there
+//                       (a path that goes on is repaired by the next bounce's k_shade / k_bin as it reads the radiance)
 // and once per batch k_generate (Render loop head, core/integrator.cpp:281-293) and
 // k_store_radiance (radiance guards, :300-321).  The film (FilmTile::AddSample /
 // MergeFilmTile, core/film.h:130-170, core/film.cpp:118-132) is folded per pixel in
@@ -65,12 +66,12 @@ __device__ __forceinline__ uint32_t wave_append(uint32_t *counter, bool pred) {
     return base + prefix;
 }
 
-// Block-level queue append for up to four queues at once.  Global atomics on ONE address
+// Block-level queue append for up to five queues at once.  Global atomics on ONE address
 // retire at only ~90 per microsecond on this chip, so appends are aggregated over the
 // whole workgroup: ballots per wave, a 16-entry scan in LDS, then one atomic per queue and
 // workgroup (1024 lanes) instead of one per wave.  Must be called by every thread of the
 // block in uniform control flow.  pos[k] is valid where pred[k] is set.
-struct BlockAppendLds { uint32_t waveCount[4][16]; uint32_t base[4]; };
+struct BlockAppendLds { uint32_t waveCount[5][16]; uint32_t base[5]; };
 template <int NQ>
 __device__ __forceinline__ void block_append(BlockAppendLds *lds, uint32_t *const counter[NQ], const bool pred[NQ], uint32_t pos[NQ]) {
     const uint32_t lane = __lane_id(), wave = threadIdx.x >> 6, nWaves = (blockDim.x + 63) >> 6;
@@ -1114,7 +1115,8 @@ __global__ __launch_bounds__(256) void k_generate(DevScene sc, RenderParams rp, 
 // 256-byte lines (BIN_STRIDE).
 #define HPRT_BIN_ITEMS 4
 __global__ __launch_bounds__(1024) void k_bin(DevScene sc, PathStream in, HitStream hit, const uint32_t *queue, const uint32_t *countPtr,
-                                              uint32_t countImm, int32_t maxDepth, int32_t bounces, BinSet bins, float4 *Lfinal) {
+                                              uint32_t countImm, int32_t maxDepth, int32_t bounces, BinSet bins, float4 *Lfinal,
+                                              const uint8_t *occluded, const float4 *pendPrev) {      // (both null unless RenderParams::foldRepair)
     __shared__ uint32_t waveCount[N_BINS][HPRT_BIN_ITEMS * 16];      // [bin][item round * 16 + wave]
     __shared__ uint32_t binBase[N_BINS];
     const uint32_t n = countPtr ? *countPtr : countImm;
@@ -1159,9 +1161,16 @@ __global__ __launch_bounds__(1024) void k_bin(DevScene sc, PathStream in, HitStr
                 else {
                     const float4 b4 = in.beta[slot[k]];
                     float4 L4 = in.L[slot[k]];
+                    const uint32_t st = (occluded || word >= 0) ? __float_as_uint(in.ray.b[slot[k]].w) : 0u;
+                    // the vertex behind this segment was speculated and left its repair to its reader (RAY_FOLD_MARK, kernels.h): blocked, its
+                    // radiance is the record's; the w word stays, as k_repair leaves it
+                    if (occluded && (st & RAY_FOLD_MARK) && occluded[slot[k]] != 0) {
+                        const float4 rec = pendPrev[slot[k]];
+                        L4.x = rec.x; L4.y = rec.y; L4.z = rec.z;
+                    }
                     // a specular segment that ends on a non-emitter at the depth limit still adds beta * isect.Le(-ray.d) = beta * 0 (path.cpp:97-100
                     // precedes the depth test, :110): +-0 unless the throughput is infinite or NaN — then NaN, and the reference zeroes the sample
-                    if (word >= 0 && (__float_as_uint(in.ray.b[slot[k]].w) >> 31)) { L4.x += b4.x * 0.f; L4.y += b4.y * 0.f; L4.z += b4.z * 0.f; }
+                    if (word >= 0 && (st >> 31)) { L4.x += b4.x * 0.f; L4.y += b4.y * 0.f; L4.z += b4.z * 0.f; }
                     Lfinal[__float_as_uint(b4.w)] = L4;
                 }
             }
@@ -1218,6 +1227,9 @@ __global__ __launch_bounds__(1024) void k_bin(DevScene sc, PathStream in, HitStr
 #ifndef HPRT_SHADE_WAVES_SUBSTRATE
 #define HPRT_SHADE_WAVES_SUBSTRATE 4
 #endif
+// {L, etaScale} of a path that k_generate has just made (it does not store them).  Not const: a constant lives in another address space, and a
+// pointer selected between it and a stream is a generic one (flat loads, which every wait for LDS or scalar data then has to cover).
+__device__ float4 kFreshPathL = {0.f, 0.f, 0.f, 1.f};
 // INSTS: the scene has object instances — the specialised variants then carry the instance transform as well (a hit inside an instance keeps
 // its material's bin); without instances that code is compiled out of them.
 template <int MODE, int BS, bool TEX = false, bool INSTS = false>
@@ -1243,9 +1255,10 @@ __global__ __launch_bounds__(BS, MODE == 0 ? HPRT_SHADE_WAVES_MATTE : MODE == 1 
     // barrier, in front of everything) and the first two round trips of the vertex's own dependent chain then overlap.
     // The entry carries the hit's primitive word, so the primitive record (and the rest of the hit) is requested in the same round as the
     // path streams, not one round trip after the hit record.
-    float4 rayA = make_float4(0.f, 0.f, 0.f, 0.f), rayB = rayA, hitA = rayA, beta4 = rayA, L4 = rayA, tv0 = rayA, tv1 = rayA, tv2 = rayA;
+    float4 rayA = make_float4(0.f, 0.f, 0.f, 0.f), rayB = rayA, hitA = rayA, beta4 = rayA, tv0 = rayA, tv1 = rayA, tv2 = rayA;
     float2 hitB = hit_no_aux();
     int32_t word = -1;          // the hit's primitive word (dev_scene.h)
+    uint32_t occ = 0u;          // (rp.foldRepair) the shadow ray of the vertex behind this segment was blocked — meaningful under RAY_FOLD_MARK only
     // One light and no spatial distribution (kernel-uniform): Distribution1D::SampleDiscrete returns light 0 for every u (its offset is
     // clamped to [0, size - 2] = [0, 0]), so the light is fetched here through the scalar path, ahead of the vertex's own chain.
     const bool oneLight = sc.nLights == 1u && !sc.spatial;
@@ -1271,16 +1284,26 @@ __global__ __launch_bounds__(BS, MODE == 0 ? HPRT_SHADE_WAVES_MATTE : MODE == 1 
         if (MODE != 2 || p >= 0) { tv0 = sc.tris[3 * p]; tv1 = sc.tris[3 * p + 1]; tv2 = sc.tris[3 * p + 2]; }
         hitA = hit_load(hit, slot); rayA = in.ray.a[slot]; rayB = in.ray.b[slot];
         if ((MODE == 2 || INSTS) && hit.b) hitB = hit_load_aux(hit, slot);
-        // a fresh path's throughput and radiance are constants (k_generate does not store them)
+        // a fresh path's throughput is a constant (k_generate does not store it)
         beta4 = firstBounce ? make_float4(1.f, 1.f, 1.f, __uint_as_float(slot)) : in.beta[slot];
-        L4 = firstBounce ? make_float4(0.f, 0.f, 0.f, 1.f) : in.L[slot];
+        // (the radiance is requested below, from the address that the segment's mark and this byte select)
+        if (!firstBounce && rp.foldRepair) occ = vs.occluded[slot];
     }
     halton_lds_load(sc, &hl);
     if (i < n) {
         SP_MARK(6);      // queue entry + path streams
         const uint32_t st = __float_as_uint(rayB.w);
-        int dim = (int)(st & 0xffffu);
-        const int bounces = (int)((st >> 16) & 0x7fffu);
+        // The radiance so far.  Under rp.foldRepair the vertex behind a marked segment (RAY_FOLD_MARK, kernels.h) left its repair to this
+        // reader: if its shadow ray was blocked its radiance is its record's, else what it stored; the w word (etaScale) is the stored one either
+        // way, as k_repair leaves it.  Hence one round after the other path words — and with no use before this vertex's own light term, so
+        // that the round trip is covered by the surface interaction's and the material's.  Two plain requests whose addresses are SELECTED
+        // (a fresh path reads its constants from kFreshPathL): a request inside a branch is waited for where the branch ends.
+        const bool dark = rp.foldRepair && (st & RAY_FOLD_MARK) && occ != 0u;
+        const float4 *const Lstored = firstBounce ? &kFreshPathL : in.L + slot;
+        const float *const Lrgb = reinterpret_cast<const float *>(dark ? vs.pendPrev + slot : Lstored);
+        const float4 L4 = make_float4(Lrgb[0], Lrgb[1], Lrgb[2], Lstored->w);
+        int dim = (int)(st & RAY_DIM_MASK);
+        const int bounces = (int)((st >> RAY_BOUNCE_SHIFT) & RAY_BOUNCE_MASK);
         const bool specularBounce = (st >> 31) != 0u;      // the segment left a specular lobe (integrators/path.cpp:160)
         const uint32_t pathId = __float_as_uint(beta4.w);
         const uint32_t pix = pathId % rp.nPix, sIdx = pathId / rp.nPix;
@@ -1291,6 +1314,11 @@ __global__ __launch_bounds__(BS, MODE == 0 ? HPRT_SHADE_WAVES_MATTE : MODE == 1 
         rgb beta(beta4.x, beta4.y, beta4.z);
         rgb L(L4.x, L4.y, L4.z), Ldark(0.f);
         float etaScale = L4.w;      // (a stored path continues, so its w word is its etaScale; fresh paths: 1)
+        // The specialised variants' "+ beta * 0" of a specular segment is the first operation on L, and nothing else touches L (or beta) before
+        // the vertex's light term.  It is added where L is next used, not where it arises: L's request (rp.foldRepair: issued one round after
+        // the others) then stays in flight across the surface interaction.  Same operands, same order of the operations on L.
+        bool zeroTerm = false;
+        auto added_zero_term = [&] { if (MODE != 2 && zeroTerm) { L = rgb(L.r + beta.r * 0.f, L.g + beta.g * 0.f, L.b + beta.b * 0.f); zeroTerm = false; } };
         const bool found = prim >= 0;
         DevSI si;
         DevTexGeom tg;
@@ -1344,7 +1372,7 @@ __global__ __launch_bounds__(BS, MODE == 0 ? HPRT_SHADE_WAVES_MATTE : MODE == 1 
                     // specular bounce left beta infinite or NaN, and the reference then zeroes the whole sample (core/integrator.cpp:300-321)
                     L = rgb(L.r + beta.r * 0.f, L.g + beta.g * 0.f, L.b + beta.b * 0.f);
                 }
-            } else if (MODE != 2 && specularBounce) L = rgb(L.r + beta.r * 0.f, L.g + beta.g * 0.f, L.b + beta.b * 0.f);      // (the same term on a non-emitter reached directly; beta == 1 at bounce 0)
+            } else if (MODE != 2 && specularBounce) zeroTerm = true;      // (the same term on a non-emitter reached directly; beta == 1 at bounce 0: added_zero_term below)
         }
         SP_MARK(0);      // loads + surface interaction
         if (MODE == 2 && !found && (bounces == 0 || specularBounce))
@@ -1474,6 +1502,7 @@ __global__ __launch_bounds__(BS, MODE == 0 ? HPRT_SHADE_WAVES_MATTE : MODE == 1 
                             }
                         }
                     }
+                    added_zero_term();
                     if (rp.speculate && wantShadow && !wantMis) {
                         // The light sample is this vertex's only pending term: its radiance is one of two values, told apart by the shadow ray alone.
                         // Both are formed here with k_resolve's operations in k_resolve's order (pickPdf is what it re-derives, word for word:
@@ -1501,6 +1530,7 @@ __global__ __launch_bounds__(BS, MODE == 0 ? HPRT_SHADE_WAVES_MATTE : MODE == 1 
             // is Spectrum(0) (no light, pick pdf 0, black f, zero light pdf): beta * 0 is +-0 for a finite throughput — which is why such a vertex
             // queues no resolve work — but NaN for an infinite or NaN one (a degenerate microfacet alpha, a vanishing pdf), and the
             // reference's NaN guard then zeroes the whole sample.  Found by the random scenes (rough glass with alpha 0 along one axis).
+            added_zero_term();
             if (!defer && !wantResolve && !speculated && bsdf_num(bsdf) > 0) L = rgb(L.r + beta.r * 0.f, L.g + beta.g * 0.f, L.b + beta.b * 0.f);
             SP_MARK(4);      // BSDF-sampled light term + pending stores
             // ---- sample the BSDF for the next path segment (path.cpp:141-164) ----
@@ -1535,7 +1565,7 @@ __global__ __launch_bounds__(BS, MODE == 0 ? HPRT_SHADE_WAVES_MATTE : MODE == 1 
                 if (rp.cullMis && bounces + 1 >= rp.maxDepth && !(flags & BX_SPECULAR)) alive = false;
                 if (alive) {
                     out.ray.a[j] = make_float4(o.x, o.y, o.z, HPRT_INF);
-                    out.ray.b[j] = make_float4(wi.x, wi.y, wi.z, __uint_as_float((uint32_t)dim | ((uint32_t)(bounces + 1) << 16) | ((flags & BX_SPECULAR) ? 0x80000000u : 0u)));
+                    out.ray.b[j] = make_float4(wi.x, wi.y, wi.z, __uint_as_float((uint32_t)dim | ((uint32_t)(bounces + 1) << RAY_BOUNCE_SHIFT) | (speculated && rp.foldRepair ? RAY_FOLD_MARK : 0u) | ((flags & BX_SPECULAR) ? RAY_SPECULAR : 0u)));
                     out.beta[j] = make_float4(beta.r, beta.g, beta.b, beta4.w);
                     wantNext = true;
                 }
@@ -1544,7 +1574,9 @@ __global__ __launch_bounds__(BS, MODE == 0 ? HPRT_SHADE_WAVES_MATTE : MODE == 1 
         }
         // Radiance so far: k_resolve adds this vertex's direct lighting to out.L[j] and, if the path
         // stops here (w == 0), passes the sum on to Lfinal; without a pending term this lane does it.
-        // (A speculated vertex has no pending term: L holds its lit value, and k_repair puts the dark one in its place if the shadow ray is blocked.)
+        // (A speculated vertex has no pending term: L holds its lit value; if the shadow ray is blocked the dark one takes its place — through k_repair,
+        // or, rp.foldRepair and the path goes on, through the next bounce's reader of out.L[j].)
+        added_zero_term();      // (a vertex at the depth limit: the block above did not run, beta is the incoming one)
         if (!defer) {
             if (speculated) vs.pendBeta[j] = make_float4(Ldark.r, Ldark.g, Ldark.b, __uint_as_float(pathId | SPEC_RECORD | (wantNext ? 0u : SPEC_END)));
             if (wantNext || wantResolve) out.L[j] = make_float4(L.r, L.g, L.b, wantNext ? etaScale : 0.f);      // w: 0 = the path ends at this vertex, else its etaScale
@@ -1571,14 +1603,17 @@ __global__ __launch_bounds__(BS, MODE == 0 ? HPRT_SHADE_WAVES_MATTE : MODE == 1 
         const uint32_t pr = wave_append(bins.count + (6 + RETRY) * BIN_STRIDE, voxelMiss && !retryPass);
         if (voxelMiss && !retryPass) bins.retry[RETRY][pr] = make_uint2(slot, j);
     }
-    uint32_t *const ctr[4] = {q.nextCount, q.shadowCount, q.misCount, q.resolveCount};
-    const bool pred[4] = {wantNext, wantShadow, wantMis, wantResolve};
-    uint32_t pos[4];
-    block_append<4>(&al, ctr, pred, pos);
+    // (rp.foldRepair) a speculated vertex at which the path ends has no later reader: k_repair's
+    const bool wantEnd = speculated && !wantNext && rp.foldRepair;
+    uint32_t *const ctr[5] = {q.nextCount, q.shadowCount, q.misCount, q.resolveCount, q.endCount};
+    const bool pred[5] = {wantNext, wantShadow, wantMis, wantResolve, wantEnd};
+    uint32_t pos[5];
+    block_append<5>(&al, ctr, pred, pos);
     if (wantNext) q.next[pos[0]] = j;
     if (wantShadow) q.shadow[pos[1]] = j;
     if (wantMis) q.mis[pos[2]] = j;
     if (wantResolve) q.resolve[pos[3]] = j;
+    if (wantEnd) q.end[pos[4]] = j;
 }
 
 // ---------------------------------------------------------------------------
@@ -1628,25 +1663,40 @@ __global__ __launch_bounds__(256) void k_resolve(DevScene sc, VertexStreams vs, 
 // ---------------------------------------------------------------------------
 // k_repair: one lane per shadow ray.  A speculated vertex (k_shade, rp.speculate) carries its lit radiance already; where the ray
 // turned out blocked, the dark value of its record replaces it.  Vertices that are not speculated are k_resolve's.
+// The queue is the bounce's shadow rays or, with RenderParams::foldRepair, only the speculated vertices at which a path ends (a path that
+// goes on is repaired by the reader of its radiance, k_shade or k_bin of the next bounce).
 // COUNT (tests only): counts[0] += speculated vertices, counts[1] += repaired ones.
+// A thread's work is a chain of three small dependent requests (entry, byte, record), so it takes HPRT_REPAIR_ITEMS entries, 256 apart,
+// and has each round's requests of all of them in flight together (k_bin, HPRT_BIN_ITEMS).
 // ---------------------------------------------------------------------------
+#define HPRT_REPAIR_ITEMS 4
 template <bool COUNT>
 __global__ __launch_bounds__(256) void k_repair(VertexStreams vs, float4 *Lio, float4 *Lfinal, const uint32_t *queue, uint32_t n, uint32_t *counts) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t j = queue[i];
-    const bool occluded = vs.occluded[j] != 0;
-    if (!COUNT && !occluded) return;
-    const float4 rec = vs.pendBeta[j];
-    const uint32_t w = __float_as_uint(rec.w);
-    if (!(w & SPEC_RECORD)) return;
-    if (COUNT) atomicAdd(counts, 1u);
-    if (!occluded) return;
-    if (COUNT) atomicAdd(counts + 1, 1u);
-    if (w & SPEC_END) Lfinal[w & SPEC_ID_MASK] = make_float4(rec.x, rec.y, rec.z, 0.f);      // last vertex of the path
-    else {      // the path goes on: the w word is its etaScale and stays
-        float *const Lj = reinterpret_cast<float *>(Lio + j);
-        Lj[0] = rec.x; Lj[1] = rec.y; Lj[2] = rec.z;
+    const uint32_t first = blockIdx.x * (HPRT_REPAIR_ITEMS * 256u) + threadIdx.x;
+    uint32_t j[HPRT_REPAIR_ITEMS];
+    bool occluded[HPRT_REPAIR_ITEMS], want[HPRT_REPAIR_ITEMS];
+    float4 rec[HPRT_REPAIR_ITEMS];
+#pragma unroll
+    for (int k = 0; k < HPRT_REPAIR_ITEMS; ++k) { const uint32_t i = first + k * 256u; want[k] = i < n; j[k] = want[k] ? queue[i] : 0u; }
+#pragma unroll
+    for (int k = 0; k < HPRT_REPAIR_ITEMS; ++k) {
+        occluded[k] = want[k] && vs.occluded[j[k]] != 0;
+        if (!COUNT) want[k] = occluded[k];
+    }
+#pragma unroll
+    for (int k = 0; k < HPRT_REPAIR_ITEMS; ++k) rec[k] = want[k] ? vs.pendBeta[j[k]] : make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+    for (int k = 0; k < HPRT_REPAIR_ITEMS; ++k) {
+        const uint32_t w = __float_as_uint(rec[k].w);
+        if (!want[k] || !(w & SPEC_RECORD)) continue;
+        if (COUNT) atomicAdd(counts, 1u);
+        if (!occluded[k]) continue;
+        if (COUNT) atomicAdd(counts + 1, 1u);
+        if (w & SPEC_END) Lfinal[w & SPEC_ID_MASK] = make_float4(rec[k].x, rec[k].y, rec[k].z, 0.f);      // last vertex of the path
+        else {      // the path goes on: the w word is its etaScale and stays
+            float *const Lj = reinterpret_cast<float *>(Lio + j[k]);
+            Lj[0] = rec[k].x; Lj[1] = rec[k].y; Lj[2] = rec[k].z;
+        }
     }
 }
 
@@ -1965,8 +2015,10 @@ void LaunchGenerate(hipStream_t st, const DevScene &sc, const RenderParams &rp, 
 }
 void LaunchBin(hipStream_t st, const DevScene &sc, const PathStream &in, const HitStream &hit, const uint32_t *queue,
                const uint32_t *countPtr, uint32_t countImm, uint32_t gridItems, int32_t maxDepth, int32_t bounces, const BinSet &bins,
-               float4 *Lfinal) {
-    if (gridItems) hipLaunchKernelGGL(k_bin, dim3(blocks_for(gridItems, HPRT_BIN_ITEMS * 1024)), dim3(1024), 0, st, sc, in, hit, queue, countPtr, countImm, maxDepth, bounces, bins, Lfinal);
+               float4 *Lfinal, const VertexStreams &vs, bool foldRepair) {
+    const uint8_t *occluded = foldRepair ? vs.occluded : nullptr;
+    const float4 *pendPrev = foldRepair ? vs.pendPrev : nullptr;
+    if (gridItems) hipLaunchKernelGGL(k_bin, dim3(blocks_for(gridItems, HPRT_BIN_ITEMS * 1024)), dim3(1024), 0, st, sc, in, hit, queue, countPtr, countImm, maxDepth, bounces, bins, Lfinal, occluded, pendPrev);
 }
 void LaunchShade(hipStream_t st, int mode, const DevScene &sc, const RenderParams &rp, const PathStream &in, const HitStream &hit,
                  uint32_t gridItems, uint32_t s0, const PathStream &out, const VertexStreams &vs, const QueueSet &q,
@@ -2000,8 +2052,8 @@ void LaunchResolve(hipStream_t st, const DevScene &sc, const VertexStreams &vs, 
 }
 void LaunchRepair(hipStream_t st, const VertexStreams &vs, float4 *L, float4 *Lfinal, const uint32_t *queue, uint32_t n, uint32_t *counts) {
     if (n == 0) return;
-    if (counts) hipLaunchKernelGGL(k_repair<true>, dim3(blocks_for(n, 256)), dim3(256), 0, st, vs, L, Lfinal, queue, n, counts);
-    else hipLaunchKernelGGL(k_repair<false>, dim3(blocks_for(n, 256)), dim3(256), 0, st, vs, L, Lfinal, queue, n, counts);
+    if (counts) hipLaunchKernelGGL(k_repair<true>, dim3(blocks_for(n, HPRT_REPAIR_ITEMS * 256)), dim3(256), 0, st, vs, L, Lfinal, queue, n, counts);
+    else hipLaunchKernelGGL(k_repair<false>, dim3(blocks_for(n, HPRT_REPAIR_ITEMS * 256)), dim3(256), 0, st, vs, L, Lfinal, queue, n, counts);
 }
 void LaunchStoreRadiance(hipStream_t st, const float4 *Lfinal, float *LallR, float *LallG, float *LallB, uint32_t nPix, uint32_t s0,
                          uint32_t nSlots) {
