@@ -183,6 +183,11 @@ int64_t orc_halton(int sx0, int sy0, int sx1, int sy1, int px, int py, int64_t s
     for (int i = 0; i < nd; ++i) out[i] = s.SampleDimension(s.intervalSampleIndex, dim0 + i);
     return s.intervalSampleIndex;
 }
+// SampleDimension(index[i], dim[i]) of a sampler over [sx0,sx1)x[sy0,sy1), for any Halton index (no pixel, no sample number)
+void orc_halton_dims(int sx0, int sy0, int sx1, int sy1, int center, size_t n, const uint64_t *index, const int32_t *dim, float *out) {
+    HaltonSampler s(1 << 30, sx0, sy0, sx1, sy1, center != 0);
+    for (size_t i = 0; i < n; ++i) out[i] = s.SampleDimension((int64_t)index[i], dim[i]);
+}
 
 // Camera rays for (px,py,sampleNum) triples
 void orc_camera_rays(void *h, size_t n, const int *px, const int *py, const int64_t *sn, float *o, float *d) {

@@ -51,6 +51,8 @@ def _load():
     lib.orc_scrambled_radical_inverse.argtypes = [C.c_int, C.c_uint64]
     lib.orc_halton.restype = C.c_int64
     lib.orc_halton.argtypes = [C.c_int] * 6 + [C.c_int64, C.c_int, C.c_int, vp]
+    lib.orc_halton_dims.restype = None
+    lib.orc_halton_dims.argtypes = [C.c_int] * 5 + [C.c_size_t, vp, vp, vp]
     lib.orc_camera_rays.argtypes = [vp, C.c_size_t, vp, vp, vp, vp, vp]
     lib.orc_sample_radiance.argtypes = [vp, C.c_size_t, vp, vp, vp, vp]
     lib.orc_render.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp]
@@ -179,3 +181,12 @@ def halton(sample_bounds, px, py, sample, dim0, nd):
     out = np.zeros(nd, np.float32)
     idx = lib.orc_halton(sample_bounds[0], sample_bounds[1], sample_bounds[2], sample_bounds[3], px, py, sample, dim0, nd, _p(out))
     return idx, out
+
+
+def halton_dims(sample_bounds, index, dim, center=False):
+    """HaltonSampler::SampleDimension(index[i], dim[i]) of a sampler over `sample_bounds`, for Halton indices below 2^63"""
+    index = np.ascontiguousarray(index, np.uint64); dim = np.ascontiguousarray(dim, np.int32)
+    assert index.shape == dim.shape and index.ndim == 1
+    out = np.zeros(index.shape[0], np.float32)
+    lib.orc_halton_dims(sample_bounds[0], sample_bounds[1], sample_bounds[2], sample_bounds[3], int(bool(center)), index.shape[0], _p(index), _p(dim), _p(out))
+    return out

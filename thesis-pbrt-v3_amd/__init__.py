@@ -393,6 +393,7 @@ def _load():
     for prefix in ("kdinst", "rbspinst", "bsppaperinst"):
         debug["hprt_debug_%s_bounds" % prefix] = (C.c_int, [vp, C.c_int, vp])
         debug["hprt_debug_%s_set_tree" % prefix] = (C.c_int, [vp, C.c_int, sz, vp, sz, vp, vp])
+    debug["hprt_debug_halton_index"] = (C.c_int, [P(RenderOptions), sz, vp, vp, vp, vp, vp, vp])
     for name, (res, args) in list(sig.items()) + list(debug.items()):
         fn = getattr(lib, name)   # raises AttributeError if an export is missing
         fn.restype = res
@@ -414,6 +415,33 @@ def _ptr(a):
 
 def version():
     return lib.hprt_version().decode()
+
+
+_probe_lib = None
+
+
+def _probe():
+    """lib/libhprt_probe.so (build.py): the device probes of the tests, in a library of their own beside libhprt.so."""
+    global _probe_lib
+    if _probe_lib is None:
+        path = os.path.join(os.path.dirname(LIB_PATH), "libhprt_probe.so")
+        if not os.path.exists(path):
+            raise ImportError("hprt: %s is missing — run `python thesis-pbrt-v3_amd/build.py`" % path)
+        p = C.CDLL(path)
+        p.hprt_debug_device_halton.restype = C.c_int
+        p.hprt_debug_device_halton.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
+        _probe_lib = p
+    return _probe_lib
+
+
+def debug_halton_index(opt, px, py, sample):
+    """Test hook (not part of include/hprt.h; host only): the Halton indices of samples `sample` at pixels (px, py) of the frame `opt`
+    describes, as a render forms them (SetupFrame's offset tables) and as sample_radiance does (HaltonPixelOffset), both uint64
+    arrays, and the frame's sample bounds (sx0, sy0, sx1, sy1)."""
+    px = np.ascontiguousarray(px, np.int32); py = np.ascontiguousarray(py, np.int32); sample = np.ascontiguousarray(sample, np.int64)
+    a = np.zeros(px.shape[0], np.uint64); b = np.zeros(px.shape[0], np.uint64); bounds = np.zeros(4, np.int32)
+    _check(lib.hprt_debug_halton_index(C.byref(opt), px.shape[0], _ptr(px), _ptr(py), _ptr(sample), _ptr(a), _ptr(b), _ptr(bounds)))
+    return a, b, tuple(int(v) for v in bounds)
 
 
 class Model:
@@ -1062,6 +1090,16 @@ class Scene:
         (None switches it off).  A film that changes under it means a render consumed a word it never wrote."""
         lib.hprt_debug_poison_workspace.argtypes = [C.c_void_p, C.c_int]
         _check(lib.hprt_debug_poison_workspace(self._h, -1 if byte is None else int(byte)))
+
+    def debug_device_halton(self, bounds_w, bounds_h, index, dim, sample_pixel_center=False, use_lds=False):
+        """Test hook (not part of include/hprt.h): the device's halton_dim(index[i], dim[i]) of a sampler over bounds_w x bounds_h sample
+        bounds, read from this scene's tables; use_lds: through the workgroup's LDS copy, as k_shade reads dimensions below 64."""
+        index = np.ascontiguousarray(index, np.uint64); dim = np.ascontiguousarray(dim, np.int32)
+        assert index.shape == dim.shape and index.ndim == 1
+        out = np.zeros(index.shape[0], np.float32)
+        _check(_probe().hprt_debug_device_halton(self._h, int(bounds_w), int(bounds_h), int(bool(sample_pixel_center)), int(bool(use_lds)),
+                                                 index.shape[0], _ptr(index), _ptr(dim), _ptr(out)))
+        return out
 
     def film_records(self):
         """Cross-tile film contributions of the last render(export_foreign=True): FILM_RECORD array (HprtFilmRecord)."""

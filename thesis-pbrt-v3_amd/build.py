@@ -30,6 +30,10 @@ CUIDS = {"device/kernels.hip": "a6cd736c50efffab", "device/kd_walk.hip": "5c0d2e
          "device/rbspinst_walk.hip": "9f3c61d8b2047ae5", "device/bsppaperinst_walk.hip": "2c7e5a90d4b18f63", "device/bsp_cost.hip": "6b1f94c3e7a0d258",
          "device/bspnode_cost.hip": "d3a7150c8e4f92b6",
          "capi_device.hip": "1b24418c11488d5c", "capi_gather.hip": "89501e8167866ce2"}
+# lib/libhprt_probe.so: device probes for the tests (device/halton_probe.hip: halton_dim over host arrays), linked against libhprt.so.
+# A library of its own, so that libhprt.so's .hip_fatbin — what profiles/rNN_counters.json is stamped with — gains no code object.
+PROBE_SRCS = ["device/halton_probe.hip"]
+CUIDS["device/halton_probe.hip"] = "f04b8d61c2a79e35"
 COMMON = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-Wall", "-Wno-unused-function"]
 
 
@@ -66,7 +70,7 @@ def build(verbose=False, force=False):
         obj = os.path.join(OBJ, s.replace("/", "_") + ".o")
         cmd = [hipcc if s in HIPCC_HOST_SRCS else "g++"] + COMMON + ["-c", src, "-o", obj]
         jobs.append((src, obj, cmd))
-    for s in HIP_SRCS:
+    for s in HIP_SRCS + PROBE_SRCS:
         src = os.path.join(CSRC, s)
         obj = os.path.join(OBJ, s.replace("/", "_") + ".o")
         cmd = [hipcc, "--offload-arch=gfx950"] + COMMON + ["-Wno-unused-result", "-cuid=" + CUIDS[s], "-c", src, "-o", obj]
@@ -86,9 +90,16 @@ def build(verbose=False, force=False):
             if verbose and out:
                 print(out)
     lib = os.path.join(LIB, "libhprt.so")
-    objs = [j[1] for j in jobs]
+    probe_objs = [j[1] for j in jobs[len(jobs) - len(PROBE_SRCS):]]
+    objs = [j[1] for j in jobs[:len(jobs) - len(PROBE_SRCS)]]
     if force or _newer(objs, lib):
         cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-o", lib] + objs + ["-lz", "-L/opt/rocm/lib", "-lrccl"]   # zlib: PNG textures (texture_io.cpp); RCCL: film gather (capi_gather.hip)
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        if r.returncode != 0:
+            raise RuntimeError("link failed: %s\n%s" % (" ".join(cmd), r.stderr))
+    probe = os.path.join(LIB, "libhprt_probe.so")
+    if force or _newer(probe_objs + [lib], probe):
+        cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-o", probe] + probe_objs + ["-L" + LIB, "-lhprt", "-Wl,-rpath,$ORIGIN"]
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError("link failed: %s\n%s" % (" ".join(cmd), r.stderr))

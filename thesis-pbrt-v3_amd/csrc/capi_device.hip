@@ -140,16 +140,20 @@ int SetupFrame(const HprtRenderOptions &o, FrameSetup *f) {
     }
     return HPRT_OK;
 }
+// a render's offset of pixel (x, y), from the two tables (hprt_debug_halton_index holds it against HaltonPixelOffset)
+uint64_t TilePixelOffset(const FrameSetup &f, int x, int y) {
+    const uint64_t stride = (uint64_t)std::max(1, f.hal.sampleStride);
+    return f.hal.sampleStride > 1 ? (f.offX[((x % 128) + 128) % 128] + f.offY[((y % 128) + 128) % 128]) % stride : 0ull;
+}
 void AddTilePixels(FrameSetup *f, int tile) {
     const FilmGeom &fg = f->fg;
     int tx = tile % f->ntx, ty = tile / f->ntx;
     int x0 = fg.sx0 + tx * 16, x1 = std::min(x0 + 16, fg.sx1), y0 = fg.sy0 + ty * 16, y1 = std::min(y0 + 16, fg.sy1);
-    const uint64_t stride = (uint64_t)std::max(1, f->hal.sampleStride);
     for (int y = y0; y < y1; ++y)
         for (int x = x0; x < x1; ++x) {
             f->localIndex[(size_t)(y - fg.cy0) * f->W + (x - fg.cx0)] = (int32_t)f->pixelXY.size();
             f->pixelXY.push_back((uint32_t)x | ((uint32_t)y << 16));
-            f->pixelOffset.push_back(f->hal.sampleStride > 1 ? (f->offX[((x % 128) + 128) % 128] + f->offY[((y % 128) + 128) % 128]) % stride : 0ull);
+            f->pixelOffset.push_back(TilePixelOffset(*f, x, y));
         }
 }
 
@@ -1430,6 +1434,24 @@ int hprt_sample_radiance(HprtScene *s, const HprtRenderOptions *opt, size_t n, c
     std::vector<float> planes(3 * n);
     HIP_TRY(hipMemcpy(planes.data(), LR, 12 * n, hipMemcpyDeviceToHost));
     for (size_t i = 0; i < n; ++i) { L_out[3 * i] = planes[i]; L_out[3 * i + 1] = planes[n + i]; L_out[3 * i + 2] = planes[2 * n + i]; }
+    return HPRT_OK;
+} catch (...) { return hprt::HandleException(); }
+
+// Diagnostics hook (not part of include/hprt.h; host code only, no device needed): the Halton index of sample `sample[i]` at pixel
+// (px[i], py[i]) of the frame `opt` describes, both ways the library forms it — via_tables: a render's, from SetupFrame's offX / offY
+// tables (AddTilePixels); direct: hprt_sample_radiance's, from HaltonPixelOffset — and the frame's sample bounds {sx0, sy0, sx1, sy1}.
+__attribute__((visibility("default"))) int hprt_debug_halton_index(const HprtRenderOptions *opt, size_t n, const int32_t *px, const int32_t *py, const int64_t *sample,
+                                                                    uint64_t *via_tables, uint64_t *direct, int32_t *sample_bounds4) try {
+    if (!opt || !sample_bounds4 || (n && (!px || !py || !sample || !via_tables || !direct))) return SetError(HPRT_E_INVALID, "hprt_debug_halton_index: null argument");
+    FrameSetup f;
+    if (int rc = SetupFrame(*opt, &f)) return rc;
+    sample_bounds4[0] = f.fg.sx0; sample_bounds4[1] = f.fg.sy0; sample_bounds4[2] = f.fg.sx1; sample_bounds4[3] = f.fg.sy1;
+    for (size_t i = 0; i < n; ++i) {
+        if (px[i] < f.fg.sx0 || px[i] >= f.fg.sx1 || py[i] < f.fg.sy0 || py[i] >= f.fg.sy1 || sample[i] < 0)
+            return SetError(HPRT_E_INVALID, "hprt_debug_halton_index: pixel outside the sample bounds");
+        via_tables[i] = TilePixelOffset(f, px[i], py[i]) + (uint64_t)sample[i] * (uint64_t)f.hal.sampleStride;
+        direct[i] = (uint64_t)HaltonPixelOffset(f.hal, px[i], py[i]) + (uint64_t)sample[i] * (uint64_t)f.hal.sampleStride;
+    }
     return HPRT_OK;
 } catch (...) { return hprt::HandleException(); }
 
