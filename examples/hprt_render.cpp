@@ -66,9 +66,15 @@ int main(int argc, char **argv) {
     if (spp > 0) opt.spp = spp;
     if (haveCrop) std::memcpy(opt.crop, crop, sizeof(crop));
 
-    // BVHAccel's constructor on the host (accelerators/bvh.cpp:181-250)
+    char accel[64] = "";
+    TRY(hprt_model_accelerator(model, accel, sizeof(accel)));
+    const std::string acc = accel;
+
+    // BVHAccel's constructor on the host (accelerators/bvh.cpp:181-250); for Accelerator "bvhold" BVHAccelOld's
+    // (accelerators/bvhOld.cpp:185-227) with the Accelerator line's split method: the same handle, the same walks
     HprtBvh *bvh = nullptr;
-    TRY(hprt_bvh_build(model, &bvh));
+    if (acc == "bvhold") TRY(hprt_bvhold_build(model, nullptr, &bvh));
+    else TRY(hprt_bvh_build(model, &bvh));
 
     // croppedPixelBounds (core/film.cpp:56-60)
     const int x0 = (int)std::ceil((float)opt.xres * opt.crop[0]), x1 = (int)std::ceil((float)opt.xres * opt.crop[1]);
@@ -82,9 +88,6 @@ int main(int argc, char **argv) {
     for (int g = 0; g < gpus; ++g) TRY(hprt_scene_create_from_model(model, bvh, g, &scenes[(size_t)g]));
     // Accelerator "kdtree", "rbsp", "rbspkd", "bsppaper", "bsppaperkd" or a node-based BSP tree (MakeAccelerator, core/api.cpp:790-831): the tree is built on the host from the
     // scene's Accelerator line and every scene walks it
-    char accel[64] = "";
-    TRY(hprt_model_accelerator(model, accel, sizeof(accel)));
-    const std::string acc = accel;
     int arc = 0;
     if (acc == "kdtree") arc = AttachTree<HprtKdTree>(acc, [&](HprtKdTree **t) { return hprt_kdtree_build(model, t); }, hprt_scene_attach_kdtree, hprt_kdtree_destroy, scenes, false);
     if (acc == "rbsp") arc = AttachTree<HprtRbsp>(acc, [&](HprtRbsp **t) { return hprt_rbsp_build(model, nullptr, t); }, hprt_scene_attach_rbsp, hprt_rbsp_destroy, scenes, true);

@@ -118,6 +118,58 @@ int hprt_bvh_object_info(const HprtBvh *b, uint32_t object, uint32_t info[4], fl
 int hprt_bvh_object_copy(const HprtBvh *b, uint32_t object, void *nodes32, uint32_t *prim_order);
 
 /* ------------------------------------------------------------------------ */
+/* Accelerator "bvhold": the stock pbrt-v3 BVH the fork keeps as            */
+/* BVHAccelOld.  Stands in for BVHAccelOld::BVHAccelOld                      */
+/* (accelerators/bvhOld.cpp:185-227), recursiveBuild (:238-404), HLBVHBuild / */
+/* emitLBVH / buildUpperSAH (:406-640), flattenBVHTree (:642-660) and        */
+/* CreateBVHAcceleratorOld (:742-762).  The result is an ordinary HprtBvh:   */
+/* hprt_bvh_info / _copy, their object variants, hprt_bvh_destroy and        */
+/* hprt_scene_create_from_model take it unchanged, and the walks walk it as  */
+/* they walk the fork's tree (BVHAccelOld::Intersect / IntersectP, :664-740, */
+/* are BVHAccel's).  An interior node's count is 0 (LinearBVHNodeOld).       */
+/* Models with object instances: every object of more than one primitive    */
+/* gets a tree with the same parameters (pbrtObjectInstance,                 */
+/* core/api.cpp:1798-1806), the top level is built over                      */
+/* TransformedPrimitive::WorldBound.  HPRT_E_UNSUPPORTED where the           */
+/* reference's build is undefined: the CHECK_NE of :566 (hlbvh: the treelet  */
+/* roots' centroids coincide on the widest axis), bounds that are not        */
+/* finite, a centroid outside the 12 SAH buckets (:331-332, :585-586: bounds */
+/* whose sum overflows), a leaf of 65,536 primitives or more (:648), more    */
+/* than 2^31 - 1 primitives (the device entries: more than 2^26 per tree,    */
+/* what their one-workgroup scan serves).  A leaf of more than 255 primitives (coincident      */
+/* codes, a degenerate centroid extent) is laid out and walked like any      */
+/* other: the layout marks a leaf's last primitive and keeps no count.       */
+/* ------------------------------------------------------------------------ */
+enum { HPRT_BVHOLD_SAH = 0, HPRT_BVHOLD_HLBVH = 1, HPRT_BVHOLD_MIDDLE = 2, HPRT_BVHOLD_EQUAL = 3 };
+typedef struct HprtBvhOldParams {
+    int32_t split_method;     /* HPRT_BVHOLD_*: "string splitmethod" sah | hlbvh | middle | equal (:744-758) */
+    int32_t max_node_prims;   /* "integer maxnodeprims" (:760); min(255, .) applies (:187) */
+} HprtBvhOldParams;
+/* params NULL: the parameters of the model's Accelerator line (defaults sah, 4) */
+int hprt_bvhold_build(const HprtModel *m, const HprtBvhOldParams *params, HprtBvh **out);
+/* The same from the primitives' world bounds (3 floats per primitive, creation order); params NULL: sah, 4 */
+int hprt_bvhold_build_from_bounds(size_t n_prims, const float *bmin, const float *bmax, const HprtBvhOldParams *params, HprtBvh **out);
+/* The HLBVH form built on the GPU (opt-in): HLBVHBuild's centroid bounds, Morton codes (:415-424), radix sort (:141-182),
+ * treelet intervals (:431-449) and emitLBVH (:476-538) run as gfx950 kernels; buildUpperSAH (:540-640) over the at most
+ * 4,096 treelet roots and the final depth-first array stay on the host.  Returns the same bytes as hprt_bvhold_build with
+ * split_method HPRT_BVHOLD_HLBVH.  A treelet of more than serial_treelet_max primitives is emitted on the host from the
+ * downloaded sorted array.  Another split method: HPRT_E_UNSUPPORTED (hprt_bvhold_build builds it).  Without a HIP device:
+ * HPRT_E_NO_DEVICE and *out stays NULL.  Models with object instances: every tree goes through the one device session. */
+typedef struct HprtBvhOldDeviceOpts {
+    int device;                    /* HIP device ordinal */
+    uint32_t serial_treelet_max;   /* largest treelet one lane emits; 0 = default (4096) */
+} HprtBvhOldDeviceOpts;
+typedef struct HprtBvhOldDeviceStats {
+    uint64_t prims_sorted, sort_passes, treelets, treelets_host, launches;   /* summed over the model's trees */
+    double seconds_device;         /* wall time of the device steps, staging and downloads included */
+} HprtBvhOldDeviceStats;
+/* opts NULL: device 0 and the defaults; stats may be NULL */
+int hprt_bvhold_build_device(const HprtModel *m, const HprtBvhOldParams *params, const HprtBvhOldDeviceOpts *opts, HprtBvhOldDeviceStats *stats,
+                             HprtBvh **out);
+int hprt_bvhold_build_device_from_bounds(size_t n_prims, const float *bmin, const float *bmax, const HprtBvhOldParams *params,
+                                         const HprtBvhOldDeviceOpts *opts, HprtBvhOldDeviceStats *stats, HprtBvh **out);
+
+/* ------------------------------------------------------------------------ */
 /* kd-tree (Accelerator "kdtree").  Stands in for KdTreeAccel::KdTreeAccel +  */
 /* buildTree (accelerators/kdtreeaccel.cpp:163-380) and                       */
 /* CreateKdTreeAccelerator (:523-545).  Host side; the node array is          */

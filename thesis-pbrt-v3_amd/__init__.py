@@ -287,6 +287,10 @@ def _load():
         "hprt_bvh_copy": (C.c_int, [vp, vp, vp]),
         "hprt_bvh_object_info": (C.c_int, [vp, C.c_uint32, P(u32), P(C.c_float)]),
         "hprt_bvh_object_copy": (C.c_int, [vp, C.c_uint32, vp, vp]),
+        "hprt_bvhold_build": (C.c_int, [vp, vp, P(vp)]),
+        "hprt_bvhold_build_from_bounds": (C.c_int, [sz, vp, vp, vp, P(vp)]),
+        "hprt_bvhold_build_device": (C.c_int, [vp, vp, vp, vp, P(vp)]),
+        "hprt_bvhold_build_device_from_bounds": (C.c_int, [sz, vp, vp, vp, vp, vp, P(vp)]),
         "hprt_scene_create": (C.c_int, [vp, C.c_int, P(vp)]),
         "hprt_scene_create_from_model": (C.c_int, [vp, vp, C.c_int, P(vp)]),
         "hprt_scene_destroy": (None, [vp]),
@@ -557,6 +561,64 @@ class Bvh:
         if getattr(self, "_h", None) and lib is not None:      # (module globals are cleared at interpreter exit)
             lib.hprt_bvh_destroy(self._h)
             self._h = None
+
+
+class BvhOldParams(C.Structure):
+    """HprtBvhOldParams: CreateBVHAcceleratorOld's parameters."""
+    _fields_ = [("split_method", C.c_int32), ("max_node_prims", C.c_int32)]
+
+
+class BvhOldDeviceOpts(C.Structure):
+    """HprtBvhOldDeviceOpts: the device build of the HLBVH form (0 = default)."""
+    _fields_ = [("device", C.c_int), ("serial_treelet_max", C.c_uint32)]
+
+
+class BvhOldDeviceStats(C.Structure):
+    """HprtBvhOldDeviceStats"""
+    _fields_ = [("prims_sorted", C.c_uint64), ("sort_passes", C.c_uint64), ("treelets", C.c_uint64), ("treelets_host", C.c_uint64),
+                ("launches", C.c_uint64), ("seconds_device", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+BVHOLD_SPLIT_METHODS = {"sah": 0, "hlbvh": 1, "middle": 2, "equal": 3}      # HPRT_BVHOLD_*
+
+
+class BvhOld(Bvh):
+    """The stock pbrt-v3 BVH (host), Accelerator "bvhold": CreateBVHAcceleratorOld(prims, params).  An ordinary Bvh: Scene(model, BvhOld(model))
+    walks it.  BvhOld(model) takes the scene's Accelerator line; split_method ("sah", "hlbvh", "middle", "equal") and max_node_prims
+    override it (the other one then takes its default, "sah" or 4)."""
+
+    def __init__(self, model=None, split_method=None, max_node_prims=None, device=None, serial_treelet_max=0, handle=None, build_stats=None):
+        """device: None builds on the host; a HIP device ordinal builds the "hlbvh" form on that GPU (the same tree, byte for byte) and
+        leaves HprtBvhOldDeviceStats as a dict in self.build_stats.  serial_treelet_max: treelets of more primitives are emitted on the host."""
+        self.build_stats = build_stats
+        if handle is None:
+            handle, self.build_stats = BvhOld._build("build", (model._h,), split_method, max_node_prims, device, serial_treelet_max)
+        self._h = handle
+
+    @staticmethod
+    def _build(how, head, split_method, max_node_prims, device, serial_treelet_max):
+        prm = None
+        if split_method is not None or max_node_prims is not None:
+            sm = BVHOLD_SPLIT_METHODS[split_method] if isinstance(split_method, str) else (0 if split_method is None else int(split_method))
+            prm = C.byref(BvhOldParams(sm, 4 if max_node_prims is None else int(max_node_prims)))
+        h = C.c_void_p()
+        if device is None:
+            _check(getattr(lib, "hprt_bvhold_" + how)(*head, prm, C.byref(h)))
+            return h, None
+        opts, st = BvhOldDeviceOpts(int(device), int(serial_treelet_max)), BvhOldDeviceStats()
+        dev_name = "hprt_bvhold_build_device" + how[len("build"):]
+        _check(getattr(lib, dev_name)(*head, prm, C.byref(opts), C.byref(st), C.byref(h)))
+        return h, st.as_dict()
+
+    @staticmethod
+    def from_bounds(bmin, bmax, split_method="sah", max_node_prims=4, device=None, serial_treelet_max=0):
+        """bmin, bmax: [n, 3] float32 world bounds in creation order.  device: as in the constructor."""
+        bmin = np.ascontiguousarray(bmin, np.float32).reshape(-1, 3); bmax = np.ascontiguousarray(bmax, np.float32).reshape(-1, 3)
+        h, st = BvhOld._build("build_from_bounds", (bmin.shape[0], _ptr(bmin), _ptr(bmax)), split_method, max_node_prims, device, serial_treelet_max)
+        return BvhOld(handle=h, build_stats=st)
 
 
 class KdTree(_Tree):

@@ -19,6 +19,7 @@
 #include "bspnode_builder.h"
 #include "bvh_builder.h"
 #include "halton_tables.h"
+#include "hlbvh_build_device.h"
 #include "hprt_internal.h"
 #include "kdop_cost_device.h"
 #include "scene_model.h"
@@ -816,6 +817,9 @@ int hprt_model_parse(const char *pbrt_path, const char *const *subst, int n_subs
     } else if (std::count(std::begin(kTreeAccelerators), std::end(kTreeAccelerators), acc) && plainScene)
         m->sc.warnings.push_back("Accelerator \"" + acc + "\": the host builds the tree (hprt_" + acc + "_build) and attaches it to the scene (hprt_scene_attach_" +
                                  acc + "); a scene without it walks a BVH");
+    else if (acc == "bvhold")      // (with or without object instances: hprt_bvhold_build builds every aggregate's tree)
+        m->sc.warnings.push_back("Accelerator \"bvhold\": the host builds the tree (hprt_bvhold_build) and passes it to hprt_scene_create_from_model; "
+                                 "hprt_bvh_build builds the fork's BVH");
     else if (acc != "bvh") m->sc.warnings.push_back("Accelerator \"" + acc + "\" is outside the hot-path scope; \"bvh\" used");
     if (m->sc.opt.integrator != "path") m->sc.warnings.push_back("Integrator \"" + m->sc.opt.integrator + "\" is outside the hot-path scope; \"path\" used");
     if (m->sc.opt.sampler != "halton") m->sc.warnings.push_back("Sampler \"" + m->sc.opt.sampler + "\" is outside the hot-path scope; \"halton\" used");
@@ -929,6 +933,110 @@ int hprt_bvh_build_from_bounds(size_t n, const float *bmin, const float *bmax, i
     return HPRT_OK;
 } catch (...) { return hprt::HandleException(); }
 void hprt_bvh_destroy(HprtBvh *b) { delete b; }
+
+// ---- the stock BVH (Accelerator "bvhold"): BVHAccelOld, accelerators/bvhOld.cpp ----
+namespace {
+using HlbvhDevicePtr = DevicePtr<HlbvhDevice, HlbvhDeviceDestroy>;
+
+// HprtBvhOldParams over the Accelerator line's (or the defaults'); HPRT_OK or HPRT_E_INVALID
+int BvhOldParamsOf(const char *fn, const HprtBvhOldParams *params, BvhOldParams *p) {
+    if (!params) return HPRT_OK;
+    if (params->split_method < HPRT_BVHOLD_SAH || params->split_method > HPRT_BVHOLD_EQUAL)
+        return SetError(HPRT_E_INVALID, std::string(fn) + ": split_method is not one of HPRT_BVHOLD_SAH, _HLBVH, _MIDDLE, _EQUAL");
+    p->splitMethod = params->split_method; p->maxNodePrims = params->max_node_prims;
+    return HPRT_OK;
+}
+// One aggregate's tree, on the host or (dev) through the device session; `what` names the aggregate in a refusal
+int BuildBvhOldTree(size_t n, const float *lo, const float *hi, const BvhOldParams &p, HlbvhDevice *dev, HprtBvhOldDeviceStats *stats, const std::string &what,
+                    BvhTree *out) {
+    if (n > 0x7fffffffull) return SetError(HPRT_E_UNSUPPORTED, what + "more than 2^31 - 1 primitives");
+    // bounds that are not finite: refused by both builds before a Morton code or a bucket is formed from them (the reference
+    // would run into one of its checks, or convert a NaN to an integer)
+    for (size_t i = 0; i < 3 * n; ++i)
+        if (!std::isfinite(lo[i]) || !std::isfinite(hi[i]))
+            return SetError(HPRT_E_UNSUPPORTED, what + "bvhold: the bounds of primitive " + std::to_string(i / 3) + " are not finite");
+    if (dev) {
+        if (n > kHlbvhMaxPrims) return SetError(HPRT_E_UNSUPPORTED, what + "more than 2^26 primitives: beyond what the device build's one-workgroup scan serves (hprt_bvhold_build builds such a tree)");
+        std::string err;
+        const int rc = HlbvhDeviceBuild(dev, n, lo, hi, p.maxNodePrims, out, stats, &err);
+        return rc == HPRT_OK ? HPRT_OK : SetError(rc, what + err);
+    }
+    const std::string refused = BuildBvhOld(n, lo, hi, p, out);
+    return refused.empty() ? HPRT_OK : SetError(HPRT_E_UNSUPPORTED, what + refused);
+}
+// BuildBvhOld where hprt_bvh_build calls BuildBvh: every object definition's aggregate (pbrtObjectInstance,
+// core/api.cpp:1798-1806, same parameters), then the top level over TransformedPrimitive::WorldBound
+int BuildBvhOldModel(const HprtModel *m, const BvhOldParams &p, HlbvhDevice *dev, HprtBvhOldDeviceStats *stats, HprtBvh **out) {
+    std::vector<float> lo, hi;
+    std::unique_ptr<HprtBvh> b(new HprtBvh());
+    b->objects.resize(m->sc.nObjects);
+    for (uint32_t o = 0; o < m->sc.nObjects; ++o) {
+        ComputeObjectPrimBounds(m->sc, (int)o, &lo, &hi);
+        if (const int rc = BuildBvhOldTree(lo.size() / 3, lo.data(), hi.data(), p, dev, stats, "object " + std::to_string(o) + ": ", &b->objects[o])) return rc;
+    }
+    ComputePrimBounds(m->sc, b->objects, &lo, &hi);
+    if (const int rc = BuildBvhOldTree(lo.size() / 3, lo.data(), hi.data(), p, dev, stats, "", &b->tree)) return rc;
+    *out = b.release();
+    return HPRT_OK;
+}
+// The device entries' session: no device, then the split method and the capacity, then the ordinal
+int OpenHlbvhDevice(const char *fn, const BvhOldParams &p, const HprtBvhOldDeviceOpts *opts, HlbvhDevicePtr *dev) {
+    std::string err;
+    int nDevices = 0;
+    if (const int rc = HlbvhDeviceCount(&nDevices, &err)) return SetError(rc, err);
+    if (p.splitMethod != BVHOLD_HLBVH)
+        return SetError(HPRT_E_UNSUPPORTED, std::string(fn) + ": only split method \"hlbvh\" has a device build; hprt_bvhold_build builds \"sah\", \"middle\" and \"equal\"");
+    HlbvhDevice *d = nullptr;
+    const int rc = HlbvhDeviceCreate(opts ? opts->device : 0, opts ? opts->serial_treelet_max : 0u, &d, &err);
+    dev->reset(d);
+    return rc == HPRT_OK ? HPRT_OK : SetError(rc, err);
+}
+}  // namespace
+
+int hprt_bvhold_build(const HprtModel *m, const HprtBvhOldParams *params, HprtBvh **out) try {
+    if (out) *out = nullptr;
+    if (!m || !out) return SetError(HPRT_E_INVALID, "hprt_bvhold_build: null argument");
+    BvhOldParams p;
+    p.splitMethod = m->sc.opt.bvhOldSplitMethod; p.maxNodePrims = m->sc.opt.bvhOldMaxNodePrims;
+    if (const int rc = BvhOldParamsOf("hprt_bvhold_build", params, &p)) return rc;
+    return BuildBvhOldModel(m, p, nullptr, nullptr, out);
+} catch (...) { return hprt::HandleException(); }
+int hprt_bvhold_build_from_bounds(size_t n, const float *bmin, const float *bmax, const HprtBvhOldParams *params, HprtBvh **out) try {
+    if (out) *out = nullptr;
+    if (!out || (n && (!bmin || !bmax))) return SetError(HPRT_E_INVALID, "hprt_bvhold_build_from_bounds: null argument");
+    BvhOldParams p;
+    if (const int rc = BvhOldParamsOf("hprt_bvhold_build_from_bounds", params, &p)) return rc;
+    std::unique_ptr<HprtBvh> b(new HprtBvh());
+    if (const int rc = BuildBvhOldTree(n, bmin, bmax, p, nullptr, nullptr, "", &b->tree)) return rc;
+    *out = b.release();
+    return HPRT_OK;
+} catch (...) { return hprt::HandleException(); }
+int hprt_bvhold_build_device(const HprtModel *m, const HprtBvhOldParams *params, const HprtBvhOldDeviceOpts *opts, HprtBvhOldDeviceStats *stats,
+                             HprtBvh **out) try {
+    if (out) *out = nullptr;
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (!m || !out) return SetError(HPRT_E_INVALID, "hprt_bvhold_build_device: null argument");
+    BvhOldParams p;
+    p.splitMethod = m->sc.opt.bvhOldSplitMethod; p.maxNodePrims = m->sc.opt.bvhOldMaxNodePrims;
+    if (const int rc = BvhOldParamsOf("hprt_bvhold_build_device", params, &p)) return rc;
+    HlbvhDevicePtr dev;                                  // freed when the build ends or fails
+    if (const int rc = OpenHlbvhDevice("hprt_bvhold_build_device", p, opts, &dev)) return rc;
+    return BuildBvhOldModel(m, p, dev.get(), stats, out);
+} catch (...) { return hprt::HandleException(); }
+int hprt_bvhold_build_device_from_bounds(size_t n, const float *bmin, const float *bmax, const HprtBvhOldParams *params, const HprtBvhOldDeviceOpts *opts,
+                                         HprtBvhOldDeviceStats *stats, HprtBvh **out) try {
+    if (out) *out = nullptr;
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (!out || (n && (!bmin || !bmax))) return SetError(HPRT_E_INVALID, "hprt_bvhold_build_device_from_bounds: null argument");
+    BvhOldParams p;
+    if (const int rc = BvhOldParamsOf("hprt_bvhold_build_device_from_bounds", params, &p)) return rc;
+    HlbvhDevicePtr dev;
+    if (const int rc = OpenHlbvhDevice("hprt_bvhold_build_device_from_bounds", p, opts, &dev)) return rc;
+    std::unique_ptr<HprtBvh> b(new HprtBvh());
+    if (const int rc = BuildBvhOldTree(n, bmin, bmax, p, dev.get(), stats, "", &b->tree)) return rc;
+    *out = b.release();
+    return HPRT_OK;
+} catch (...) { return hprt::HandleException(); }
 
 // ---- kd-tree (Accelerator "kdtree") ----
 static int FinishKdTree(HprtKdTree *t, HprtKdTree **out) {

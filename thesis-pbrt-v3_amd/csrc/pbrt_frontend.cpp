@@ -648,6 +648,16 @@ struct Frontend {
             o.bspnode.seed = (uint32_t)accelParams.oneInt("seed", (int)o.bspnode.seed);
             if (nodeForm == BSPNODE_FASTKD) o.bspnode.kdTravCost = accelParams.oneInt("kdtraversalcost", o.bspnode.kdTravCost);
         }
+        // CreateBVHAcceleratorOld, accelerators/bvhOld.cpp:742-762 (the clamp to 255 is the constructor's, :187)
+        if (sc->opt.accelerator == "bvhold") {
+            const std::string sm = accelParams.oneString("splitmethod", "sah");
+            if (sm == "sah") o.bvhOldSplitMethod = 0;
+            else if (sm == "hlbvh") o.bvhOldSplitMethod = 1;
+            else if (sm == "middle") o.bvhOldSplitMethod = 2;
+            else if (sm == "equal") o.bvhOldSplitMethod = 3;
+            else { warn("BVH split method \"" + sm + "\" unknown.  Using \"sah\"."); o.bvhOldSplitMethod = 0; }
+            o.bvhOldMaxNodePrims = std::min(255, accelParams.oneInt("maxnodeprims", 4));
+        }
         reportUnused(filmParams, "Film", {"diagonal"});
         reportUnused(filterParams, "PixelFilter");
         reportUnused(cameraParams, "Camera");

@@ -98,6 +98,9 @@ struct RenderOptions {
     // Create...TreeAccelerator functions (accelerators/bsp{Arbitrary,Cluster,Random}{,WithKd,FastKd}.cpp) plus "seed"; chooser and form
     // come from the accelerator's name (BspNodeAccelerator)
     BspNodeParams bspnode;
+    // Accelerator "bvhold": CreateBVHAcceleratorOld's "splitmethod" (0 sah, 1 hlbvh, 2 middle, 3 equal: BVHOLD_*) and "maxnodeprims"
+    // (accelerators/bvhOld.cpp:742-762); host side only (not baked)
+    int32_t bvhOldSplitMethod = 0, bvhOldMaxNodePrims = 4;
     std::string filename = "pbrt.exr", accelerator = "bvh", integrator = "path", sampler = "halton";
 };
 struct SceneModel {
