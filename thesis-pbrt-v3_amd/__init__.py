@@ -398,6 +398,11 @@ def _load():
         debug["hprt_debug_%s_bounds" % prefix] = (C.c_int, [vp, C.c_int, vp])
         debug["hprt_debug_%s_set_tree" % prefix] = (C.c_int, [vp, C.c_int, sz, vp, sz, vp, vp])
     debug["hprt_debug_halton_index"] = (C.c_int, [P(RenderOptions), sz, vp, vp, vp, vp, vp, vp])
+    # the light-centred shadow grid (csrc/shadow_grid.h)
+    debug["hprt_debug_shadow_grid"] = (C.c_int, [C.c_int])
+    debug["hprt_debug_shadow_grid_info"] = (C.c_int, [vp, vp])
+    debug["hprt_debug_shadow_grid_occluded"] = (C.c_int, [vp, sz, vp, vp, vp])
+    debug["hprt_debug_shadow_grid_build"] = (C.c_int, [sz, vp, vp, C.c_uint32, vp, vp, sz, vp, sz])
     for name, (res, args) in list(sig.items()) + list(debug.items()):
         fn = getattr(lib, name)   # raises AttributeError if an export is missing
         fn.restype = res
@@ -436,6 +441,33 @@ def _probe():
         p.hprt_debug_device_halton.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
         _probe_lib = p
     return _probe_lib
+
+
+SG_SINGLE, SG_PRIM_MASK = 0x80000000, 0x0fffffff
+
+
+def debug_shadow_grid(on):
+    """Test hook (not part of include/hprt.h): 0 sends the shadow rays of later plain renders through the walk, 1 through the light-centred
+    grid where a scene has one, -1 back to the default (HPRT_SHADOW_GRID at scene creation); returns the setting before."""
+    return lib.hprt_debug_shadow_grid(int(on))
+
+
+def shadow_grid_build(p9, light, res):
+    """Test hook (not part of include/hprt.h; host only): the shadow grid of the triangles p9 ([n, 9] float32, each a leaf of its own)
+    around the point `light` at res x res cells per cube face.  dict: R, eps, near (near-list length), longest, seconds, cell_start
+    (uint32 [6 R^2 + 1]), prim (entry -> triangle), single (entry -> SG_SINGLE mark), key (entry -> float32 depth key), rect (entry ->
+    [u0, u1, v0, v1], the sixteenths of its cell the triangle reaches, inclusive); the first `near` entries are the near list."""
+    p9 = np.ascontiguousarray(p9, np.float32).reshape(-1, 9)
+    light = np.ascontiguousarray(light, np.float32)
+    info = np.zeros(6, np.float64)
+    _check(lib.hprt_debug_shadow_grid_build(p9.shape[0], _ptr(p9), _ptr(light), int(res), _ptr(info), None, 0, None, 0))
+    R, n_entries = int(info[0]), int(info[1])
+    cell_start = np.zeros(6 * R * R + 1, np.uint32); entries = np.zeros((max(1, n_entries), 2), np.uint32)
+    _check(lib.hprt_debug_shadow_grid_build(p9.shape[0], _ptr(p9), _ptr(light), int(res), _ptr(info), _ptr(cell_start), cell_start.size, _ptr(entries), entries.shape[0]))
+    entries = entries[:n_entries]
+    return {"R": R, "eps": float(info[3]), "near": int(info[2]), "longest": int(info[4]), "seconds": float(info[5]), "cell_start": cell_start,
+            "prim": (entries[:, 0] & SG_PRIM_MASK).astype(np.int64), "single": (entries[:, 0] & SG_SINGLE) != 0, "key": (entries[:, 1] & np.uint32(0xffff0000)).view(np.float32),
+            "rect": np.stack([(entries[:, 1] >> s) & 15 for s in (0, 4, 8, 12)], axis=1).astype(np.int64)}
 
 
 def debug_halton_index(opt, px, py, sample):
@@ -1111,6 +1143,22 @@ class Scene:
         ctr = np.zeros(4, np.uint64) if count else None
         _check(lib.hprt_occluded(self._h, n, _ptr(o), _ptr(d), _ptr(tmax), _ptr(occ), _ptr(ctr)))
         return (occ, ctr) if count else occ
+
+    def shadow_grid_info(self):
+        """Test hook (not part of include/hprt.h): the scene's light-centred shadow grid — eligible (False: its shadow rays take the walk),
+        R, entries, near (near-list length), bytes, build_seconds, longest and mean list, light (the point every ray must end at), render_launches
+        (launches of k_shadow_grid by this scene's renders so far)."""
+        out = np.zeros(12, np.float64)
+        _check(lib.hprt_debug_shadow_grid_info(self._h, _ptr(out)))
+        return {"eligible": bool(out[0]), "R": int(out[1]), "entries": int(out[2]), "near": int(out[3]), "bytes": int(out[4]), "build_seconds": float(out[5]),
+                "longest": int(out[6]), "mean": float(out[7]), "light": out[8:11].astype(np.float32), "render_launches": int(out[11])}
+
+    def shadow_grid_occluded_device(self, n, rays7_ptr, occ_ptr):
+        """Test hook (not part of include/hprt.h): k_shadow_grid on n device rays ([7][n] planes) that all end at the scene's light,
+        d = float32(light - o); returns the kernel's milliseconds."""
+        ms = C.c_float()
+        _check(lib.hprt_debug_shadow_grid_occluded(self._h, n, rays7_ptr, occ_ptr, C.byref(ms)))
+        return float(ms.value)
 
     def intersect_device(self, n, rays7_ptr, t_ptr, prim_ptr, bary_ptr=None, stream=None):
         _check(lib.hprt_intersect_device(self._h, n, rays7_ptr, t_ptr, prim_ptr, bary_ptr, stream))

@@ -13,22 +13,22 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "lib")
-HOST_SRCS = ["pbrt_frontend.cpp", "loop_subdiv.cpp", "scene_io.cpp", "texture_io.cpp", "bvh_builder.cpp", "kdtree_builder.cpp", "rbsp_builder.cpp", "bsppaper_builder.cpp", "bspnode_builder.cpp", "bvhold_builder.cpp", "wide_bvh.cpp", "halton_tables.cpp", "capi_host.cpp"]
+HOST_SRCS = ["pbrt_frontend.cpp", "loop_subdiv.cpp", "scene_io.cpp", "texture_io.cpp", "bvh_builder.cpp", "kdtree_builder.cpp", "rbsp_builder.cpp", "bsppaper_builder.cpp", "bspnode_builder.cpp", "bvhold_builder.cpp", "wide_bvh.cpp", "shadow_grid.cpp", "halton_tables.cpp", "capi_host.cpp"]
 # host code built by hipcc without an offload target (no code object): the float operations of the scene layout keep the code
 # generator they had when they sat in capi_device.hip
 HIPCC_HOST_SRCS = ["scene_layout.cpp"]
-HIP_SRCS = ["device/kernels.hip", "device/kd_walk.hip", "device/rbsp_walk.hip", "device/rbspkd_walk.hip", "device/bsppaper_walk.hip", "device/bsppaperkd_walk.hip", "device/kdinst_walk.hip", "device/kdop_cost.hip", "device/rbspinst_walk.hip", "device/bsppaperinst_walk.hip", "device/bsp_cost.hip", "device/bspnode_cost.hip", "device/hlbvh_build.hip", "capi_device.hip", "capi_gather.hip"]
+HIP_SRCS = ["device/kernels.hip", "device/kd_walk.hip", "device/rbsp_walk.hip", "device/rbspkd_walk.hip", "device/bsppaper_walk.hip", "device/bsppaperkd_walk.hip", "device/kdinst_walk.hip", "device/kdop_cost.hip", "device/rbspinst_walk.hip", "device/bsppaperinst_walk.hip", "device/bsp_cost.hip", "device/bspnode_cost.hip", "device/hlbvh_build.hip", "device/shadow_grid.hip", "capi_device.hip", "capi_gather.hip"]
 # hipcc names every HIP translation unit by a CUID (the __hip_cuid_* symbol in its code object) that it otherwise hashes from
 # the source's and the object's ABSOLUTE paths, so the code objects — and the sha256 profiles/rNN_counters.json is stamped
 # with — would depend on where the tree is checked out.  Pinned to the values the stamped build derived: the same code
 # objects, byte for byte, from any directory.
-# (device/kd_walk.hip, device/rbsp_walk.hip, device/rbspkd_walk.hip, device/bsppaper_walk.hip, device/bsppaperkd_walk.hip, device/kdinst_walk.hip, device/kdop_cost.hip, device/rbspinst_walk.hip, device/bsppaperinst_walk.hip, device/bsp_cost.hip, device/bspnode_cost.hip, device/hlbvh_build.hip: values of their own, so that adding them left the other code
+# (device/kd_walk.hip, device/rbsp_walk.hip, device/rbspkd_walk.hip, device/bsppaper_walk.hip, device/bsppaperkd_walk.hip, device/kdinst_walk.hip, device/kdop_cost.hip, device/rbspinst_walk.hip, device/bsppaperinst_walk.hip, device/bsp_cost.hip, device/bspnode_cost.hip, device/hlbvh_build.hip, device/shadow_grid.hip: values of their own, so that adding them left the other code
 # objects as they were)
 CUIDS = {"device/kernels.hip": "a6cd736c50efffab", "device/kd_walk.hip": "5c0d2e7f41b3a916", "device/rbsp_walk.hip": "3e91a5c07d2b84f6",
          "device/rbspkd_walk.hip": "7a4f0c2e9b61d385", "device/bsppaper_walk.hip": "c52e8b1d06f3a794",
          "device/bsppaperkd_walk.hip": "e8136d4a9f07c2b5", "device/kdinst_walk.hip": "4d9b27f1a60c8e53", "device/kdop_cost.hip": "b7e20a5c93d1f468",
          "device/rbspinst_walk.hip": "9f3c61d8b2047ae5", "device/bsppaperinst_walk.hip": "2c7e5a90d4b18f63", "device/bsp_cost.hip": "6b1f94c3e7a0d258",
-         "device/bspnode_cost.hip": "d3a7150c8e4f92b6", "device/hlbvh_build.hip": "58e2c9a4f1b7063d",
+         "device/bspnode_cost.hip": "d3a7150c8e4f92b6", "device/hlbvh_build.hip": "58e2c9a4f1b7063d", "device/shadow_grid.hip": "a17c3e58d90b24f6",
          "capi_device.hip": "1b24418c11488d5c", "capi_gather.hip": "89501e8167866ce2"}
 # lib/libhprt_probe.so: device probes for the tests (device/halton_probe.hip: halton_dim over host arrays), linked against libhprt.so.
 # A library of its own, so that libhprt.so's .hip_fatbin — what profiles/rNN_counters.json is stamped with — gains no code object.

@@ -187,6 +187,16 @@ int hprt_scene_create(const HprtSceneDesc *d, int device, HprtScene **out) try {
     HIP_TRY(upload(sc->textures, L.textures)); HIP_TRY(upload(sc->mipLevels, L.mipLevels)); HIP_TRY(upload(sc->texels, L.texels)); HIP_TRY(upload(sc->weightLut, L.weightLut));
     HIP_TRY(upload(sc->wide, L.wide)); HIP_TRY(upload(sc->leafBox, L.leafBox));
     HIP_TRY(upload(sc->envLights, L.envLights)); HIP_TRY(upload(sc->envData, L.envData));
+    if (L.shadowGrid.eligible) {
+        const ShadowGrid &sg = L.shadowGrid;
+        static_assert(sizeof(SgEntry) == sizeof(uint2), "grid entries are read as 8-byte words");
+        std::vector<SgEntry> padded(sg.entries);      // (k_shadow_grid reads entries in pairs: one entry of padding behind the last)
+        padded.push_back(SgEntry{0u, 0u});
+        HIP_TRY(upload(sc->sgCells, sg.cellStart)); HIP_TRY(upload(sc->sgEntries, padded));
+        sc->sg = DevShadowGrid{sc->sgCells.as<uint32_t>(), sc->sgEntries.as<uint2>(), (uint32_t)sg.entries.size(), sg.nNear, sg.R};
+        sc->sgInfo.longest = sg.longest; sc->sgInfo.buildSeconds = sg.buildSeconds; sc->sgInfo.eps = sg.eps; sc->sgInfo.bytes = sg.bytes();
+        for (int a = 0; a < 3; ++a) sc->sgInfo.light[a] = sg.light[a];
+    }
     HIP_TRY(sc->counters.alloc(sizeof(DevCounters)));
     HIP_TRY(hipMemset(sc->counters.p, 0, sizeof(DevCounters)));
     HIP_TRY(sc->deepStack.alloc((size_t)HPRT_SPILL_STACK * HPRT_DEEP_THREADS * sizeof(uint2)));
@@ -346,6 +356,49 @@ static void Trace(HprtScene *s, hipStream_t st, bool anyHit, bool count, const u
     case HprtScene::Walk::Bvh: LaunchTrace(st, s->dev, anyHit, count, queue, countPtr, countImm, gridItems, rays, hits, occ, counters, workCounter, rayStats); break;
     }
 }
+// The shadow rays of a plain render go to k_shadow_grid: the scene has a grid (eligibility: scene_layout.cpp, LayoutShadowGrid), still
+// walks its BVH and takes the leaf-exact walk, whose leaf boxes the grid kernel tests with.  hprt_debug_shadow_grid(0) keeps the walk.
+static int g_shadowGrid = -1;
+static bool ShadowGridInUse(const HprtScene *s) {
+    // (a phase-profile render keeps the walk: its any-hit records per ray are k_walk4's, and the grid kernel has no profile variant)
+    return s->sg.entries != nullptr && g_shadowGrid != 0 && s->walk == HprtScene::Walk::Bvh && hprt::WideWalkInUse(s->dev) && !hprt::TraceProfileInUse();
+}
+// Diagnostics hooks (not part of include/hprt.h; tests/test_gpu_shadow_grid.py, tools/shadow_grid_replay.py).
+// hprt_debug_shadow_grid: on = 0 sends the shadow rays of later renders through the walk again, 1 through the grid where a scene has
+// one, -1 back to the default; returns the setting before.
+__attribute__((visibility("default"))) int hprt_debug_shadow_grid(int on) { const int was = g_shadowGrid; g_shadowGrid = on; return was; }
+// hprt_debug_shadow_grid_info: out = {eligible, R, entries, near-list length, bytes, build seconds, longest list, mean list, light x y z,
+// launches of k_shadow_grid by this scene's renders so far}
+__attribute__((visibility("default"))) int hprt_debug_shadow_grid_info(HprtScene *s, double out[12]) {
+    if (!s || !out) return HPRT_E_INVALID;
+    for (int a = 0; a < 3; ++a) out[8 + a] = s->sgInfo.light[a];
+    out[11] = (double)s->sgInfo.renderLaunches;
+    const bool has = s->sg.entries != nullptr;
+    const double nCells = has ? 6.0 * s->sg.R * s->sg.R : 1.0;
+    out[0] = has ? 1 : 0; out[1] = s->sg.R; out[2] = s->sg.nEntries; out[3] = s->sg.nNear; out[4] = (double)s->sgInfo.bytes;
+    out[5] = s->sgInfo.buildSeconds; out[6] = s->sgInfo.longest; out[7] = has ? (s->sg.nEntries - s->sg.nNear) / nCells : 0.0;
+    return HPRT_OK;
+}
+// hprt_debug_shadow_grid_occluded: k_shadow_grid on the n rays of d_rays7 ([7][n] planes, as hprt_occluded_device takes them), every one
+// of which must end at the scene's light (d = light - o in float); ms, if given, receives the kernel's time.
+__attribute__((visibility("default"))) int hprt_debug_shadow_grid_occluded(HprtScene *s, size_t n, const float *d_rays7, uint8_t *d_occ, float *ms) try {
+    if (!s || !d_rays7 || !d_occ || n == 0 || n > 0x7ffffff0ull) return SetError(HPRT_E_INVALID, "hprt_debug_shadow_grid_occluded: bad argument");
+    if (!s->sg.entries) return SetError(HPRT_E_UNSUPPORTED, "hprt_debug_shadow_grid_occluded: the scene has no shadow grid");
+    HIP_TRY(hipSetDevice(s->device));
+    SceneCall call(s, nullptr);
+    RayStream rays; HitStream hits;
+    if (int rc = ApiStreams(s, n, &rays, &hits)) return rc;
+    struct Events { hipEvent_t e[2] = {nullptr, nullptr}; ~Events() { for (auto x : e) if (x) (void)hipEventDestroy(x); } } ev;
+    for (auto &x : ev.e) HIP_TRY(hipEventCreate(&x));
+    LaunchPackRays(nullptr, d_rays7, (uint32_t)n, rays);
+    HIP_TRY(hipEventRecord(ev.e[0], nullptr));
+    LaunchShadowGrid(nullptr, s->dev, s->sg, nullptr, nullptr, (uint32_t)n, (uint32_t)n, rays, d_occ, s->workCounter.as<uint32_t>());
+    HIP_TRY(hipEventRecord(ev.e[1], nullptr));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    if (ms) HIP_TRY(hipEventElapsedTime(ms, ev.e[0], ev.e[1]));
+    return HPRT_OK;
+} catch (...) { return hprt::HandleException(); }
 // Diagnostics (tools/sort_experiment.py): what consuming rays through a PERMUTED index queue costs.  The n rays of d_rays7 stay where
 // they are; d_queue lists them in the order to be traced.  ms[0]: a streaming pass that gathers the rays through the queue into
 // [7][n] planes at d_scratch7 (the physical permutation a sort would have to do), ms[1]: the scene's walk reading the rays through the queue.
@@ -1013,7 +1066,13 @@ int RunBatch(HprtScene *s, hipStream_t st, const RenderParams &rpIn, const Works
             hipEvent_t a = ev.get(), b = ev.get();
             HIP_TRY(hipEventRecord(a, st));
             HitStream none; none.a = nullptr; none.b = nullptr;
-            Trace(s, st, true, count, cur.shadow, nullptr, nShadow, nShadow, vs.shadow, none, vs.occluded, ctr, wcPath, rayStats);
+            // a plain render of an eligible scene answers its shadow rays from the light-centred grid; counting, per-pixel-statistics and
+            // trace-all renders keep the walk (their counters are the reference's node counts)
+            if (ShadowGridInUse(s) && !count && !rayStats && rp.cullMis) {
+                LaunchShadowGrid(st, s->dev, s->sg, cur.shadow, nullptr, nShadow, nShadow, vs.shadow, vs.occluded, wcPath);
+                ++s->sgInfo.renderLaunches;
+            }
+            else Trace(s, st, true, count, cur.shadow, nullptr, nShadow, nShadow, vs.shadow, none, vs.occluded, ctr, wcPath, rayStats);
             if (pixelStats) LaunchPixelStats(st, rayStats, vs.pendBeta, cur.shadow, nullptr, nShadow, nShadow, rp.nPix, true, pixelStats);
             if (pixelKd) LaunchPixelKdStats(st, rayStats, vs.pendBeta, cur.shadow, nullptr, nShadow, nShadow, rp.nPix, true, pixelKd);
             HIP_TRY(hipEventRecord(b, st));

@@ -25,6 +25,7 @@
 #include "scene_model.h"
 #include "hprt_math.h"
 #include "wide_bvh.h"
+#include "shadow_grid.h"
 
 using namespace hprt;
 
@@ -1995,6 +1996,33 @@ __attribute__((visibility("default"))) int hprt_debug_shape_inline(const HprtSce
     *n_prims = t.size(); *n_shapes = sf.size();
     if (tags && prim_shape && prim_cap >= t.size()) { memcpy(tags, t.data(), 4 * t.size()); memcpy(prim_shape, ps.data(), 4 * ps.size()); }
     if (shape_flags && shape_material && shape_cap >= sf.size()) { memcpy(shape_flags, sf.data(), 4 * sf.size()); memcpy(shape_material, smat.data(), 4 * smat.size()); }
+    return HPRT_OK;
+} catch (...) { return hprt::HandleException(); }
+
+// Diagnostics hook (not part of include/hprt.h; tests/test_shadow_grid_host.py): BuildShadowGrid, no device, on n triangles given as
+// [n][9] floats — each a leaf of its own — around `light`, over the bound of the triangles.  info6 = {R, entries, near-list
+// length, eps, longest list, build seconds}; cell_start (6 R^2 + 1 words) and entries ({primitive word, key bits} pairs) are
+// written when they fit their capacities (counted in words and pairs).
+__attribute__((visibility("default"))) int hprt_debug_shadow_grid_build(size_t n, const float *p9, const float light[3], uint32_t R, double info6[6],
+                                                                         uint32_t *cell_start, size_t cell_cap, uint32_t *entries, size_t entry_cap) try {
+    if (!n || !p9 || !light || !info6 || R == 0 || n >= (1u << 28)) return SetError(HPRT_E_INVALID, "hprt_debug_shadow_grid_build: bad argument");
+    std::vector<float> tris(12 * n, 0.f);
+    std::vector<uint8_t> single(n, 1);
+    float lo[3] = {HPRT_INF, HPRT_INF, HPRT_INF}, hi[3] = {-HPRT_INF, -HPRT_INF, -HPRT_INF};
+    for (size_t i = 0; i < n; ++i)
+        for (int v = 0; v < 3; ++v)
+            for (int a = 0; a < 3; ++a) {
+                const float x = p9[9 * i + 3 * v + a];
+                tris[12 * i + 4 * v + a] = x;
+                if (x < lo[a]) lo[a] = x;
+                if (x > hi[a]) hi[a] = x;
+            }
+    ShadowGrid g;
+    BuildShadowGrid(tris.data(), single.data(), (uint32_t)n, light, lo, hi, R, (size_t)1 << 27, 0.0, &g);
+    if (!g.eligible) return SetError(HPRT_E_UNSUPPORTED, "hprt_debug_shadow_grid_build: the lists do not fit");
+    info6[0] = g.R; info6[1] = (double)g.entries.size(); info6[2] = g.nNear; info6[3] = g.eps; info6[4] = g.longest; info6[5] = g.buildSeconds;
+    if (cell_start && cell_cap >= g.cellStart.size()) memcpy(cell_start, g.cellStart.data(), 4 * g.cellStart.size());
+    if (entries && entry_cap >= g.entries.size()) memcpy(entries, g.entries.data(), 8 * g.entries.size());
     return HPRT_OK;
 } catch (...) { return hprt::HandleException(); }
 

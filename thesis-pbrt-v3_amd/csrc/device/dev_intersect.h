@@ -89,6 +89,31 @@ __device__ __forceinline__ bool tri_test(vec3 p0, vec3 p1, vec3 p2, vec3 rayO, f
     return true;
 }
 
+// ---- box ----------------------------------------------------------------
+// Bounds3::IntersectP(ray, invDir, dirIsNeg) (core/geometry.h:1754-1780) split into its tMax-independent part (returned)
+// and the entry distance for the `tMin < ray.tMax` part.  Branch-free: the reference's early returns only skip work,
+// they do not change the values that the later comparisons see.  (One child at a time: the form the kernels with the
+// quadric code use — the packed form below needs registers that their 128 do not have.)
+__device__ __forceinline__ bool slab_test(float lox, float hix, float loy, float hiy, float loz, float hiz, vec3 ro, vec3 invDir,
+                                          bool negX, bool negY, bool negZ, float robust, float *tEntry) {
+    float tMin = ((negX ? hix : lox) - ro.x) * invDir.x;
+    float tMax = ((negX ? lox : hix) - ro.x) * invDir.x;
+    const float tyMin = ((negY ? hiy : loy) - ro.y) * invDir.y;
+    float tyMax = ((negY ? loy : hiy) - ro.y) * invDir.y;
+    tMax *= robust; tyMax *= robust;
+    bool ok = !(tMin > tyMax || tyMin > tMax);
+    if (tyMin > tMin) tMin = tyMin;
+    if (tyMax < tMax) tMax = tyMax;
+    const float tzMin = ((negZ ? hiz : loz) - ro.z) * invDir.z;
+    float tzMax = ((negZ ? loz : hiz) - ro.z) * invDir.z;
+    tzMax *= robust;
+    ok = ok && !(tMin > tzMax || tzMin > tMax);
+    if (tzMin > tMin) tMin = tzMin;
+    if (tzMax < tMax) tMax = tzMax;
+    *tEntry = tMin;
+    return ok && (tMax > 0);
+}
+
 // ---- EFloat interval arithmetic (core/efloat.h, NDEBUG layout) --------------
 struct efloat { float v, lo, hi; };
 __device__ __forceinline__ efloat ef(float v) { efloat r; r.v = v; r.lo = v; r.hi = v; return r; }

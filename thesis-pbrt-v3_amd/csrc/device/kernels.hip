@@ -140,30 +140,7 @@ static TraceTune DefaultTraceTune(bool anyHit) {
     return t;
 }
 
-// Bounds3::IntersectP(ray, invDir, dirIsNeg) (core/geometry.h:1754-1780) split into its tMax-independent part (returned)
-// and the entry distance for the `tMin < ray.tMax` part.  Branch-free: the reference's early returns only skip work,
-// they do not change the values that the later comparisons see.  (One child at a time: the form the kernels with the
-// quadric code use — the packed form below needs registers that their 128 do not have.)
-__device__ __forceinline__ bool slab_test(float lox, float hix, float loy, float hiy, float loz, float hiz, vec3 ro, vec3 invDir,
-                                          bool negX, bool negY, bool negZ, float robust, float *tEntry) {
-    float tMin = ((negX ? hix : lox) - ro.x) * invDir.x;
-    float tMax = ((negX ? lox : hix) - ro.x) * invDir.x;
-    const float tyMin = ((negY ? hiy : loy) - ro.y) * invDir.y;
-    float tyMax = ((negY ? loy : hiy) - ro.y) * invDir.y;
-    tMax *= robust; tyMax *= robust;
-    bool ok = !(tMin > tyMax || tyMin > tMax);
-    if (tyMin > tMin) tMin = tyMin;
-    if (tyMax < tMax) tMax = tyMax;
-    const float tzMin = ((negZ ? hiz : loz) - ro.z) * invDir.z;
-    float tzMax = ((negZ ? loz : hiz) - ro.z) * invDir.z;
-    tzMax *= robust;
-    ok = ok && !(tMin > tzMax || tzMin > tMax);
-    if (tzMin > tMin) tMin = tzMin;
-    if (tzMax < tMax) tMax = tzMax;
-    *tEntry = tMin;
-    return ok && (tMax > 0);
-}
-
+// (slab_test, one box at a time: dev_intersect.h)
 // Bounds3::IntersectP(ray, invDir, dirIsNeg) (core/geometry.h:1754-1780) for BOTH children of a pair at once, split into
 // its tMax-independent part (returned per child) and the entry distances for the `tMin < ray.tMax` part.  n* hold the
 // bounds the reference selects with dirIsNeg for tMin (pMin, or pMax where the ray runs backwards), f* those for tMax,
@@ -1913,6 +1890,7 @@ static bool TraceProfileEnabled() {
 extern "C" __attribute__((visibility("default"))) int hprt_debug_trace_profile_mode(int on) { const int was = TraceProfileEnabled() ? 1 : 0; g_traceProfileMode = on; return was; }
 // which walk a plain render of this scene takes: 1 the leaf-exact wide walk (k_walk4), 0 the binary walk (k_trace)
 bool WideWalkInUse(const DevScene &sc) { return sc.wide != nullptr && WideWalkEnabled(); }
+bool TraceProfileInUse() { return TraceProfileEnabled(); }
 extern "C" __attribute__((visibility("default"))) int hprt_debug_wide_walk(int on) { const int was = WideWalkEnabled() ? 1 : 0; g_wideWalk = on; return was; }
 void LaunchTrace(hipStream_t st, const DevScene &sc, bool anyHit, bool count, const uint32_t *queue, const uint32_t *countPtr,
                  uint32_t countImm, uint32_t gridItems, const RayStream &rays, const HitStream &hits, uint8_t *occ,

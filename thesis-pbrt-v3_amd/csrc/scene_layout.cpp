@@ -533,7 +533,7 @@ int LayoutWide(Work &w) {
         if (g.nNodes == 0) continue;
         const BvhNode *nd = g.nodes;
         std::vector<int32_t> leafRefW(g.nNodes, WIDE_NONE);
-        if (L.leafBox.empty()) L.leafBox.assign(2 * (size_t)L.nPrims, make_float4(0.f, 0.f, 0.f, 0.f));
+        if (L.leafBox.empty()) { L.leafBox.assign(2 * (size_t)L.nPrims, make_float4(0.f, 0.f, 0.f, 0.f)); L.primSingle.assign(L.nPrims, 0); }
         for (uint32_t i = 0; i < g.nNodes; ++i) {
             if ((nd[i].countAxis & 3u) != 3u) continue;
             const uint32_t firstPrim = w.primBase[ai] + (uint32_t)nd[i].offset, count = nd[i].countAxis >> 2;
@@ -550,6 +550,7 @@ int LayoutWide(Work &w) {
             }
             uint32_t r = ~firstPrim;
             if (!single) r &= ~WIDE_LEAF_BOXED;
+            else L.primSingle[firstPrim] = 1;
             leafRefW[i] = (int32_t)r;
             for (uint32_t k = 0; k < count; ++k) {
                 L.leafBox[2 * (size_t)(firstPrim + k)] = make_float4(nd[i].bmin[0], nd[i].bmin[1], nd[i].bmin[2], nd[i].bmax[0]);
@@ -562,7 +563,25 @@ int LayoutWide(Work &w) {
         if (ai == 0) wideNeedTop = need; else wideNeedObject = std::max(wideNeedObject, need);
     }
     // (the wide walk's stack: LDS entries + the scene's deep-stack area; a scene that could need more keeps the binary walk)
-    if (!wideOk || wideNeedTop + (w.d.n_instances ? 1 + wideNeedObject : 0) > HPRT_WIDE_STACK_MAX || w.wideBase[0] != 0) { L.wide.clear(); L.leafBox.clear(); }
+    if (!wideOk || wideNeedTop + (w.d.n_instances ? 1 + wideNeedObject : 0) > HPRT_WIDE_STACK_MAX || w.wideBase[0] != 0) { L.wide.clear(); L.leafBox.clear(); L.primSingle.clear(); }
+    return HPRT_OK;
+}
+
+// The shadow grid (shadow_grid.h) of a scene whose every shadow ray ends at one point: exactly one light, a point light; triangles
+// only, no object instances; the leaf-exact walk in use (its leaf boxes and one-triangle marks are what the grid kernel tests with).
+// HPRT_SHADOW_GRID=0: no grid (A/B runs); unset: only a grid that is expected to be cheaper than the walk (SG_MAX_CANDIDATES); 1: any.
+// Everything else keeps the walk for its shadow rays.
+int LayoutShadowGrid(Work &w) {
+    SceneLayout &L = w.L;
+    const int mode = ShadowGridModeFromEnv();
+    if (mode == 0 || w.d.n_lights != 1 || L.lights.size() != 1 || L.lights[0].type != 0 || w.d.n_instances != 0 || w.d.n_objects != 0 ||
+        !L.spheres.empty() || L.wide.empty() || L.nPrims == 0 || L.nPrims >= (1u << 28))
+        return HPRT_OK;
+    for (uint32_t i = 0; i < L.nPrims; ++i) if ((f2u(L.tris[3 * (size_t)i].w) & TAG_KIND_MASK) != 0u) return HPRT_OK;
+    static_assert(sizeof(float4) == 16, "triangle records are read as 12 floats per primitive");
+    // at most 1 GiB of lists (HPRT_SHADOW_GRID_MAX_MB): a finer grid is halved until it fits
+    const size_t capMb = [] { const char *e = getenv("HPRT_SHADOW_GRID_MAX_MB"); return e ? (size_t)std::max(1l, atol(e)) : (size_t)1024; }();
+    BuildShadowGrid(&L.tris[0].x, L.primSingle.data(), L.nPrims, L.lights[0].pos, L.wbMin, L.wbMax, ShadowGridResFromEnv(), capMb * ((1u << 20) / sizeof(SgEntry)), mode < 0 ? SG_MAX_CANDIDATES : 0.0, &L.shadowGrid);
     return HPRT_OK;
 }
 
@@ -623,7 +642,7 @@ int BuildSceneLayout(const HprtSceneDesc &d, SceneLayout *out) {
     }
     for (uint32_t i = 0; i < d.n_instances; ++i) out->instanceObject.push_back(d.instances[i].object);
     for (int (*stage)(Work &) : {LayoutShapes, LayoutPrimitives, LayoutMaterials, LayoutTextures, LayoutLights, LayoutEnvLights,
-                                 LayoutLightDistribution, LayoutPairs, LayoutWide, LayoutInstances})
+                                 LayoutLightDistribution, LayoutPairs, LayoutWide, LayoutInstances, LayoutShadowGrid})
         if (int rc = stage(w)) return rc;
     return HPRT_OK;
 }

@@ -6,6 +6,7 @@
 #include <vector>
 #include "../../include/hprt.h"
 #include "device/dev_scene.h"
+#include "shadow_grid.h"
 
 namespace hprt {
 
@@ -41,6 +42,11 @@ struct SceneLayout {
     std::vector<uint32_t> objectPrimBase;
     std::vector<int32_t> instanceObject;           // per instance, its object definition
     bool instanced = false, hasSubstrateBin = false;
+    // per ordered primitive: its leaf holds that one triangle alone, marked WIDE_LEAF_BOXED | WIDE_LEAF_FIRST in the wide records
+    std::vector<uint8_t> primSingle;
+    // the light-centred candidate grid of the shadow rays (shadow_grid.h): eligible for a triangle-only scene without instances
+    // that is lit by one point light and takes the leaf-exact walk
+    ShadowGrid shadowGrid;
 };
 
 // Validates *d and fills *out; HPRT_OK or an HPRT_E_* code with hprt_last_error() set.
