@@ -189,6 +189,52 @@ void orc_halton_dims(int sx0, int sy0, int sx1, int sy1, int center, size_t n, c
     for (size_t i = 0; i < n; ++i) out[i] = s.SampleDimension((int64_t)index[i], dim[i]);
 }
 
+// The BSDF of shapes[shape[i]]'s material over arrays of queries, in the layout of the product's hprt_debug_device_bsdf
+// (tests/test_gpu_bsdf.py): frame9 = n, shading.n, shading.dpdu; out8 (unused words 0):
+//   mode 0: the material's type, NumComponents(BSDF_ALL & ~BSDF_SPECULAR), bsdf.eta
+//   mode 1: f(wo, wi, BSDF_ALL & ~BSDF_SPECULAR) (3)          mode 2: Pdf(wo, wi, BSDF_ALL & ~BSDF_SPECULAR)
+//   mode 3 / 4: Sample_f(wo, &wi, u, &pdf, BSDF_ALL & ~BSDF_SPECULAR / BSDF_ALL, &sampledType): f (3), wi (3), pdf, sampledType,
+//   with pdf, wi and sampledType preset to -7, (9, 9, 9) and -1 (the early returns leave them untouched)
+// — the two flag sets EstimateDirect and PathIntegrator::Li pass (core/integrator.cpp:114, integrators/path.cpp:147-148).
+// Returns 0, or -1 for a bad argument (nothing written).
+int orc_bsdf_eval(void *h, int mode, size_t n, const int32_t *shape, const float *frame9, const float *wo3, const float *wi3,
+                  const float *u2, float *out8) {
+    Renderer *r = (Renderer *)h;
+    if (!r || !shape || !frame9 || !wo3 || !wi3 || !u2 || !out8 || mode < 0 || mode > 4) return -1;
+    const Scene &sc = r->scene;
+    for (size_t i = 0; i < n; ++i) {
+        if (shape[i] < 0 || (size_t)shape[i] >= sc.shapes.size()) return -1;
+        const int mi = sc.shapes[shape[i]].material;
+        if (mi < 0 || (size_t)mi >= sc.materials.size()) return -1;
+    }
+    const int nonSpecular = BSDF_ALL & ~BSDF_SPECULAR;
+    for (size_t i = 0; i < n; ++i) {
+        const float *fr = frame9 + 9 * i;
+        SurfaceInteraction si;
+        si.n = V3(fr[0], fr[1], fr[2]); si.shading.n = V3(fr[3], fr[4], fr[5]); si.shading.dpdu = V3(fr[6], fr[7], fr[8]);
+        si.shape = shape[i];
+        const Material &m = sc.materials[sc.shapes[shape[i]].material];
+        BSDF bsdf;
+        ComputeScatteringFunctions(sc, m, si, &bsdf);
+        const V3 wo(wo3[3 * i], wo3[3 * i + 1], wo3[3 * i + 2]), wi(wi3[3 * i], wi3[3 * i + 1], wi3[3 * i + 2]);
+        float *o = out8 + 8 * i;
+        for (int k = 0; k < 8; ++k) o[k] = 0.f;
+        if (mode == 0) {
+            o[0] = (float)m.type; o[1] = (float)bsdf.NumComponents(nonSpecular); o[2] = bsdf.eta;
+        } else if (mode == 1) {
+            const Spec f = bsdf.f(wo, wi, nonSpecular);
+            o[0] = f.c[0]; o[1] = f.c[1]; o[2] = f.c[2];
+        } else if (mode == 2) {
+            o[0] = bsdf.Pdf(wo, wi, nonSpecular);
+        } else {
+            Float pdf = -7.0f; V3 w(9, 9, 9); int sampledType = -1;
+            const Spec f = bsdf.Sample_f(wo, &w, P2(u2[2 * i], u2[2 * i + 1]), &pdf, mode == 3 ? nonSpecular : (int)BSDF_ALL, &sampledType);
+            o[0] = f.c[0]; o[1] = f.c[1]; o[2] = f.c[2]; o[3] = w.x; o[4] = w.y; o[5] = w.z; o[6] = pdf; o[7] = (float)sampledType;
+        }
+    }
+    return 0;
+}
+
 // Camera rays for (px,py,sampleNum) triples
 void orc_camera_rays(void *h, size_t n, const int *px, const int *py, const int64_t *sn, float *o, float *d) {
     Renderer *r = (Renderer *)h;

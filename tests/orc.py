@@ -53,6 +53,8 @@ def _load():
     lib.orc_halton.argtypes = [C.c_int] * 6 + [C.c_int64, C.c_int, C.c_int, vp]
     lib.orc_halton_dims.restype = None
     lib.orc_halton_dims.argtypes = [C.c_int] * 5 + [C.c_size_t, vp, vp, vp]
+    lib.orc_bsdf_eval.restype = C.c_int
+    lib.orc_bsdf_eval.argtypes = [vp, C.c_int, C.c_size_t] + [vp] * 6
     lib.orc_camera_rays.argtypes = [vp, C.c_size_t, vp, vp, vp, vp, vp]
     lib.orc_sample_radiance.argtypes = [vp, C.c_size_t, vp, vp, vp, vp]
     lib.orc_render.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp]
@@ -153,6 +155,19 @@ class OracleScene:
         L = np.zeros((px.shape[0], 3), np.float32)
         lib.orc_sample_radiance(self._h, px.shape[0], _p(px), _p(py), _p(sample), _p(L))
         return L
+
+    def bsdf_eval(self, mode, shape, frame9, wo, wi, u):
+        """orc_bsdf_eval: float32 [n, 8] in the layout of hprt.Scene.debug_device_bsdf"""
+        shape = np.ascontiguousarray(shape, np.int32)
+        frame9 = np.ascontiguousarray(frame9, np.float32).reshape(-1, 9)
+        wo = np.ascontiguousarray(wo, np.float32).reshape(-1, 3); wi = np.ascontiguousarray(wi, np.float32).reshape(-1, 3)
+        u = np.ascontiguousarray(u, np.float32).reshape(-1, 2)
+        n = shape.shape[0]
+        assert shape.ndim == 1 and frame9.shape[0] == n and wo.shape[0] == n and wi.shape[0] == n and u.shape[0] == n
+        out = np.zeros((n, 8), np.float32)
+        if lib.orc_bsdf_eval(self._h, int(mode), n, _p(shape), _p(frame9), _p(wo), _p(wi), _p(u), _p(out)) != 0:
+            raise ValueError("orc_bsdf_eval: bad argument")
+        return out
 
     def render(self, spp=0, threads=0):
         x0, y0, x1, y1 = self.film_bounds()

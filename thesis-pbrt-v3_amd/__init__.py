@@ -439,6 +439,8 @@ def _probe():
         p = C.CDLL(path)
         p.hprt_debug_device_halton.restype = C.c_int
         p.hprt_debug_device_halton.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
+        p.hprt_debug_device_bsdf.restype = C.c_int
+        p.hprt_debug_device_bsdf.argtypes = [C.c_void_p, C.c_int, C.c_size_t] + [C.c_void_p] * 6
         _probe_lib = p
     return _probe_lib
 
@@ -1209,6 +1211,20 @@ class Scene:
         out = np.zeros(index.shape[0], np.float32)
         _check(_probe().hprt_debug_device_halton(self._h, int(bounds_w), int(bounds_h), int(bool(sample_pixel_center)), int(bool(use_lds)),
                                                  index.shape[0], _ptr(index), _ptr(dim), _ptr(out)))
+        return out
+
+    def debug_device_bsdf(self, mode, shape, frame9, wo, wi, u):
+        """Test hook (not part of include/hprt.h): the device BSDF of shapes[shape[i]]'s material at the frame frame9[i] (n, shading.n,
+        shading.dpdu), no texture overrides.  mode 0: (material type, bsdf_num, eta); 1: bsdf_f; 2: bsdf_pdf; 3 / 4: bsdf_sample with
+        all = false / true: f, wi, pdf, sampledType, the last three preset to (9, 9, 9), -7 and -1.  Returns float32 [n, 8]."""
+        shape = np.ascontiguousarray(shape, np.int32)
+        frame9 = np.ascontiguousarray(frame9, np.float32).reshape(-1, 9)
+        wo = np.ascontiguousarray(wo, np.float32).reshape(-1, 3); wi = np.ascontiguousarray(wi, np.float32).reshape(-1, 3)
+        u = np.ascontiguousarray(u, np.float32).reshape(-1, 2)
+        n = shape.shape[0]
+        assert shape.ndim == 1 and frame9.shape[0] == n and wo.shape[0] == n and wi.shape[0] == n and u.shape[0] == n
+        out = np.zeros((n, 8), np.float32)
+        _check(_probe().hprt_debug_device_bsdf(self._h, int(mode), n, _ptr(shape), _ptr(frame9), _ptr(wo), _ptr(wi), _ptr(u), _ptr(out)))
         return out
 
     def film_records(self):

@@ -30,10 +30,12 @@ CUIDS = {"device/kernels.hip": "a6cd736c50efffab", "device/kd_walk.hip": "5c0d2e
          "device/rbspinst_walk.hip": "9f3c61d8b2047ae5", "device/bsppaperinst_walk.hip": "2c7e5a90d4b18f63", "device/bsp_cost.hip": "6b1f94c3e7a0d258",
          "device/bspnode_cost.hip": "d3a7150c8e4f92b6", "device/hlbvh_build.hip": "58e2c9a4f1b7063d", "device/shadow_grid.hip": "a17c3e58d90b24f6",
          "capi_device.hip": "1b24418c11488d5c", "capi_gather.hip": "89501e8167866ce2"}
-# lib/libhprt_probe.so: device probes for the tests (device/halton_probe.hip: halton_dim over host arrays), linked against libhprt.so.
+# lib/libhprt_probe.so: device probes for the tests (device/halton_probe.hip: halton_dim over host arrays; device/bsdf_probe.hip: the
+# BSDF functions over host arrays of queries), linked against libhprt.so.
 # A library of its own, so that libhprt.so's .hip_fatbin — what profiles/rNN_counters.json is stamped with — gains no code object.
-PROBE_SRCS = ["device/halton_probe.hip"]
+PROBE_SRCS = ["device/halton_probe.hip", "device/bsdf_probe.hip"]
 CUIDS["device/halton_probe.hip"] = "f04b8d61c2a79e35"
+CUIDS["device/bsdf_probe.hip"] = "3d8a6f0b92e4c517"
 COMMON = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-Wall", "-Wno-unused-function"]
 
 

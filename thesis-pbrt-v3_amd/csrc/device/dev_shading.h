@@ -791,6 +791,8 @@ __device__ __forceinline__ rgb bsdf_sample(const DevBsdf &b, vec3 woW, vec3 *wiW
         }
     }
     if (b.hasR) {
+        // BSDF_ALL & ~BSDF_SPECULAR matches no lobe of a BSDF whose one lobe is specular (core/reflection.cpp:708-713)
+        if (!all) { *pdf = 0; *sampledType = 0; return rgb(0.f); }
         // the one lobe is SpecularReflection (core/reflection.cpp:136-143; FresnelNoOp::Evaluate == Spectrum(1.)): BSDF::Sample_f
         // returns its value as sampled, with its pdf of 1 (:744-760 skip specular lobes)
         const vec3 wo = to_local(b, woW);
