@@ -403,6 +403,8 @@ def _load():
     debug["hprt_debug_shadow_grid_info"] = (C.c_int, [vp, vp])
     debug["hprt_debug_shadow_grid_occluded"] = (C.c_int, [vp, sz, vp, vp, vp])
     debug["hprt_debug_shadow_grid_build"] = (C.c_int, [sz, vp, vp, C.c_uint32, vp, vp, sz, vp, sz])
+    debug["hprt_debug_shadow_grid_image"] = (C.c_int, [sz, vp, vp, C.c_uint32, vp, vp, sz, vp, sz])
+    debug["hprt_debug_shadow_grid_image_read"] = (C.c_int, [vp, vp, vp, sz, vp, sz])
     for name, (res, args) in list(sig.items()) + list(debug.items()):
         fn = getattr(lib, name)   # raises AttributeError if an export is missing
         fn.restype = res
@@ -470,6 +472,57 @@ def shadow_grid_build(p9, light, res):
     return {"R": R, "eps": float(info[3]), "near": int(info[2]), "longest": int(info[4]), "seconds": float(info[5]), "cell_start": cell_start,
             "prim": (entries[:, 0] & SG_PRIM_MASK).astype(np.int64), "single": (entries[:, 0] & SG_SINGLE) != 0, "key": (entries[:, 1] & np.uint32(0xffff0000)).view(np.float32),
             "rect": np.stack([(entries[:, 1] >> s) & 15 for s in (0, 4, 8, 12)], axis=1).astype(np.int64)}
+
+
+SG_BLOCK_WORDS, SG_RECORD_WORDS, SG_BLOCK_SLOTS = 32, 12, 2
+
+
+def shadow_grid_image_decode(blocks, records, R, near):
+    """The lists of a shadow grid's device image (csrc/shadow_grid.h, ShadowGridImage) as the kernel follows them: per cell the block's
+    slots, then the run of records its head points to; before them the near list, records 0 .. near - 1.  dict: blocks [6 R^2, 32] and
+    records [n, 12] uint32, count (per cell), overflow (per cell: the record of its third entry), cell_start (int64 [6 R^2 + 1], the
+    near list first, as ShadowGrid::cellStart), and per entry in list order prim_word, key_word (uint32), verts ([n, 9] uint32, the
+    vertex floats' bits), next_key (uint32: the fourth lane of a record's third word; 0 for block slots), key2 (per cell: the block's
+    copy of entry 2's key word)."""
+    blocks = np.asarray(blocks, np.uint32).reshape(6 * R * R, SG_BLOCK_WORDS)
+    records = np.asarray(records, np.uint32).reshape(-1, SG_RECORD_WORDS)
+    count = blocks[:, 0].astype(np.int64); overflow = blocks[:, 1].astype(np.int64)
+    cell_start = near + np.concatenate([[0], np.cumsum(count)])
+    n = int(cell_start[-1])
+    prim = np.zeros(n, np.uint32); key = np.zeros(n, np.uint32); nxt = np.zeros(n, np.uint32); verts = np.zeros((n, 9), np.uint32)
+    vcols = [0, 1, 2, 4, 5, 6, 8, 9, 10]
+
+    def from_records(dst, src):
+        prim[dst] = records[src, 3]; key[dst] = records[src, 7]; nxt[dst] = records[src, 11]; verts[dst] = records[src][:, vcols]
+
+    from_records(np.arange(near), np.arange(near))
+    for slot, (pw, kw, v0) in enumerate([((0, 2), (0, 3), 4), ((0, 7), (0, 11), 16)]):
+        cells = np.nonzero(count > slot)[0]
+        dst = cell_start[cells] + slot
+        prim[dst] = blocks[cells, pw[1]]; key[dst] = blocks[cells, kw[1]]
+        verts[dst] = blocks[cells][:, [v0 + c for c in vcols]]
+    over = np.maximum(count - SG_BLOCK_SLOTS, 0)
+    cells = np.repeat(np.arange(count.size), over)
+    k = np.arange(int(over.sum())) - np.repeat(np.cumsum(over) - over, over)      # 0, 1, .. within each run
+    from_records(cell_start[cells] + SG_BLOCK_SLOTS + k, overflow[cells] + k)
+    return {"blocks": blocks, "records": records, "count": count, "overflow": overflow, "cell_start": cell_start, "prim_word": prim, "key_word": key,
+            "verts": verts, "next_key": nxt, "key2": blocks[:, 15]}
+
+
+def shadow_grid_image(p9, light, res):
+    """Test hook (not part of include/hprt.h; host only): the device image of the grid shadow_grid_build gives for the same arguments,
+    decoded by shadow_grid_image_decode; "words": (block words, record words with the padding, the words ShadowGridImageBytes counts)."""
+    p9 = np.ascontiguousarray(p9, np.float32).reshape(-1, 9)
+    light = np.ascontiguousarray(light, np.float32)
+    words = np.zeros(3, np.uint64)
+    _check(lib.hprt_debug_shadow_grid_image(p9.shape[0], _ptr(p9), _ptr(light), int(res), _ptr(words), None, 0, None, 0))
+    blocks = np.zeros(int(words[0]), np.uint32); records = np.zeros(int(words[1]), np.uint32)
+    _check(lib.hprt_debug_shadow_grid_image(p9.shape[0], _ptr(p9), _ptr(light), int(res), _ptr(words), _ptr(blocks), blocks.size, _ptr(records), records.size))
+    info = np.zeros(6, np.float64)
+    _check(lib.hprt_debug_shadow_grid_build(p9.shape[0], _ptr(p9), _ptr(light), int(res), _ptr(info), None, 0, None, 0))
+    out = shadow_grid_image_decode(blocks, records, int(res), int(info[2]))
+    out["words"] = tuple(int(w) for w in words)
+    return out
 
 
 def debug_halton_index(opt, px, py, sample):
@@ -1154,6 +1207,16 @@ class Scene:
         _check(lib.hprt_debug_shadow_grid_info(self._h, _ptr(out)))
         return {"eligible": bool(out[0]), "R": int(out[1]), "entries": int(out[2]), "near": int(out[3]), "bytes": int(out[4]), "build_seconds": float(out[5]),
                 "longest": int(out[6]), "mean": float(out[7]), "light": out[8:11].astype(np.float32), "render_launches": int(out[11])}
+
+    def shadow_grid_image(self):
+        """Test hook (not part of include/hprt.h): the image k_shadow_grid reads of this scene, copied back from the device and decoded as
+        shadow_grid_image_decode does."""
+        words = np.zeros(2, np.uint64)
+        _check(lib.hprt_debug_shadow_grid_image_read(self._h, _ptr(words), None, 0, None, 0))
+        blocks = np.zeros(int(words[0]), np.uint32); records = np.zeros(max(1, int(words[1])), np.uint32)
+        _check(lib.hprt_debug_shadow_grid_image_read(self._h, _ptr(words), _ptr(blocks), blocks.size, _ptr(records), records.size))
+        info = self.shadow_grid_info()
+        return shadow_grid_image_decode(blocks, records[:int(words[1])], info["R"], info["near"])
 
     def shadow_grid_occluded_device(self, n, rays7_ptr, occ_ptr):
         """Test hook (not part of include/hprt.h): k_shadow_grid on n device rays ([7][n] planes) that all end at the scene's light,

@@ -189,12 +189,16 @@ int hprt_scene_create(const HprtSceneDesc *d, int device, HprtScene **out) try {
     HIP_TRY(upload(sc->envLights, L.envLights)); HIP_TRY(upload(sc->envData, L.envData));
     if (L.shadowGrid.eligible) {
         const ShadowGrid &sg = L.shadowGrid;
-        static_assert(sizeof(SgEntry) == sizeof(uint2), "grid entries are read as 8-byte words");
-        std::vector<SgEntry> padded(sg.entries);      // (k_shadow_grid reads entries in pairs: one entry of padding behind the last)
-        padded.push_back(SgEntry{0u, 0u});
-        HIP_TRY(upload(sc->sgCells, sg.cellStart)); HIP_TRY(upload(sc->sgEntries, padded));
-        sc->sg = DevShadowGrid{sc->sgCells.as<uint32_t>(), sc->sgEntries.as<uint2>(), (uint32_t)sg.entries.size(), sg.nNear, sg.R};
-        sc->sgInfo.longest = sg.longest; sc->sgInfo.buildSeconds = sg.buildSeconds; sc->sgInfo.eps = sg.eps; sc->sgInfo.bytes = sg.bytes();
+        const ShadowGridImage &im = L.shadowGridImage;      // (the lists with their triangles in list order: shadow_grid.h)
+        // blocks, then records, in one allocation (scene_layout.cpp keeps the image below 2^32 bytes)
+        const size_t blockBytes = im.blocks.size() * sizeof(uint32_t), recordBytes = im.records.size() * sizeof(uint32_t);
+        if (blockBytes + recordBytes > 0xffff0000ull) return SetError(HPRT_E_INVALID, "hprt_scene_create: the shadow grid's image is too large");
+        HIP_TRY(sc->sgImage.alloc(blockBytes + recordBytes));
+        HIP_TRY(hipMemcpy(sc->sgImage.p, im.blocks.data(), blockBytes, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy((char *)sc->sgImage.p + blockBytes, im.records.data(), recordBytes, hipMemcpyHostToDevice));
+        sc->sg = DevShadowGrid{sc->sgImage.as<uint32_t>(), (uint32_t)(blockBytes + recordBytes), (uint32_t)blockBytes, sg.nNear, sg.R};
+        sc->sgInfo.nEntries = sg.entries.size(); sc->sgInfo.longest = sg.longest; sc->sgInfo.buildSeconds = sg.buildSeconds + im.packSeconds; sc->sgInfo.eps = sg.eps;
+        sc->sgInfo.bytes = im.bytes();
         for (int a = 0; a < 3; ++a) sc->sgInfo.light[a] = sg.light[a];
     }
     HIP_TRY(sc->counters.alloc(sizeof(DevCounters)));
@@ -361,29 +365,40 @@ static void Trace(HprtScene *s, hipStream_t st, bool anyHit, bool count, const u
 static int g_shadowGrid = -1;
 static bool ShadowGridInUse(const HprtScene *s) {
     // (a phase-profile render keeps the walk: its any-hit records per ray are k_walk4's, and the grid kernel has no profile variant)
-    return s->sg.entries != nullptr && g_shadowGrid != 0 && s->walk == HprtScene::Walk::Bvh && hprt::WideWalkInUse(s->dev) && !hprt::TraceProfileInUse();
+    return s->sg.image != nullptr && g_shadowGrid != 0 && s->walk == HprtScene::Walk::Bvh && hprt::WideWalkInUse(s->dev) && !hprt::TraceProfileInUse();
 }
 // Diagnostics hooks (not part of include/hprt.h; tests/test_gpu_shadow_grid.py, tools/shadow_grid_replay.py).
 // hprt_debug_shadow_grid: on = 0 sends the shadow rays of later renders through the walk again, 1 through the grid where a scene has
 // one, -1 back to the default; returns the setting before.
 __attribute__((visibility("default"))) int hprt_debug_shadow_grid(int on) { const int was = g_shadowGrid; g_shadowGrid = on; return was; }
-// hprt_debug_shadow_grid_info: out = {eligible, R, entries, near-list length, bytes, build seconds, longest list, mean list, light x y z,
+// hprt_debug_shadow_grid_info: out = {eligible, R, entries, near-list length, bytes of the device image, build and pack seconds, longest list, mean list, light x y z,
 // launches of k_shadow_grid by this scene's renders so far}
 __attribute__((visibility("default"))) int hprt_debug_shadow_grid_info(HprtScene *s, double out[12]) {
     if (!s || !out) return HPRT_E_INVALID;
     for (int a = 0; a < 3; ++a) out[8 + a] = s->sgInfo.light[a];
     out[11] = (double)s->sgInfo.renderLaunches;
-    const bool has = s->sg.entries != nullptr;
+    const bool has = s->sg.image != nullptr;
     const double nCells = has ? 6.0 * s->sg.R * s->sg.R : 1.0;
-    out[0] = has ? 1 : 0; out[1] = s->sg.R; out[2] = s->sg.nEntries; out[3] = s->sg.nNear; out[4] = (double)s->sgInfo.bytes;
-    out[5] = s->sgInfo.buildSeconds; out[6] = s->sgInfo.longest; out[7] = has ? (s->sg.nEntries - s->sg.nNear) / nCells : 0.0;
+    out[0] = has ? 1 : 0; out[1] = s->sg.R; out[2] = (double)s->sgInfo.nEntries; out[3] = s->sg.nNear; out[4] = (double)s->sgInfo.bytes;
+    out[5] = s->sgInfo.buildSeconds; out[6] = s->sgInfo.longest; out[7] = has ? (double)(s->sgInfo.nEntries - s->sg.nNear) / nCells : 0.0;
     return HPRT_OK;
 }
+// hprt_debug_shadow_grid_image_read: the image k_shadow_grid reads of this scene (shadow_grid.h, ShadowGridImage), copied back from the
+// device: words2 = {block words, record words, the padding included}; each array is written when it fits its capacity in words.
+__attribute__((visibility("default"))) int hprt_debug_shadow_grid_image_read(HprtScene *s, size_t words2[2], uint32_t *blocks, size_t block_cap, uint32_t *records, size_t record_cap) try {
+    if (!s || !words2) return SetError(HPRT_E_INVALID, "hprt_debug_shadow_grid_image_read: bad argument");
+    if (!s->sg.image) return SetError(HPRT_E_UNSUPPORTED, "hprt_debug_shadow_grid_image_read: the scene has no shadow grid");
+    HIP_TRY(hipSetDevice(s->device));
+    words2[0] = s->sg.recordsAt / sizeof(uint32_t); words2[1] = (s->sg.imageBytes - s->sg.recordsAt) / sizeof(uint32_t);
+    if (blocks && block_cap >= words2[0]) HIP_TRY(hipMemcpy(blocks, s->sg.image, words2[0] * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (records && record_cap >= words2[1]) HIP_TRY(hipMemcpy(records, s->sg.image + words2[0], words2[1] * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return HPRT_OK;
+} catch (...) { return hprt::HandleException(); }
 // hprt_debug_shadow_grid_occluded: k_shadow_grid on the n rays of d_rays7 ([7][n] planes, as hprt_occluded_device takes them), every one
 // of which must end at the scene's light (d = light - o in float); ms, if given, receives the kernel's time.
 __attribute__((visibility("default"))) int hprt_debug_shadow_grid_occluded(HprtScene *s, size_t n, const float *d_rays7, uint8_t *d_occ, float *ms) try {
     if (!s || !d_rays7 || !d_occ || n == 0 || n > 0x7ffffff0ull) return SetError(HPRT_E_INVALID, "hprt_debug_shadow_grid_occluded: bad argument");
-    if (!s->sg.entries) return SetError(HPRT_E_UNSUPPORTED, "hprt_debug_shadow_grid_occluded: the scene has no shadow grid");
+    if (!s->sg.image) return SetError(HPRT_E_UNSUPPORTED, "hprt_debug_shadow_grid_occluded: the scene has no shadow grid");
     HIP_TRY(hipSetDevice(s->device));
     SceneCall call(s, nullptr);
     RayStream rays; HitStream hits;

@@ -2026,4 +2026,32 @@ __attribute__((visibility("default"))) int hprt_debug_shadow_grid_build(size_t n
     return HPRT_OK;
 } catch (...) { return hprt::HandleException(); }
 
+// Diagnostics hook (not part of include/hprt.h; tests/test_shadow_grid_blocks_host.py): the device image (shadow_grid.h, ShadowGridImage)
+// of the grid that hprt_debug_shadow_grid_build builds of the same arguments, no device.  words3 = {block words, record words with
+// the padding, what ShadowGridImageBytes says of the grid}; each array is written when it fits its capacity in words.
+__attribute__((visibility("default"))) int hprt_debug_shadow_grid_image(size_t n, const float *p9, const float light[3], uint32_t R, size_t words3[3],
+                                                                         uint32_t *blocks, size_t block_cap, uint32_t *records, size_t record_cap) try {
+    if (!n || !p9 || !light || !words3 || R == 0 || n >= (1u << 28)) return SetError(HPRT_E_INVALID, "hprt_debug_shadow_grid_image: bad argument");
+    std::vector<float> tris(12 * n, 0.f);
+    std::vector<uint8_t> single(n, 1);
+    float lo[3] = {HPRT_INF, HPRT_INF, HPRT_INF}, hi[3] = {-HPRT_INF, -HPRT_INF, -HPRT_INF};
+    for (size_t i = 0; i < n; ++i)
+        for (int v = 0; v < 3; ++v)
+            for (int a = 0; a < 3; ++a) {
+                const float x = p9[9 * i + 3 * v + a];
+                tris[12 * i + 4 * v + a] = x;
+                if (x < lo[a]) lo[a] = x;
+                if (x > hi[a]) hi[a] = x;
+            }
+    ShadowGrid g;
+    BuildShadowGrid(tris.data(), single.data(), (uint32_t)n, light, lo, hi, R, (size_t)1 << 27, 0.0, &g);
+    if (!g.eligible || g.R != R) return SetError(HPRT_E_UNSUPPORTED, "hprt_debug_shadow_grid_image: the lists do not fit");
+    ShadowGridImage im;
+    PackShadowGrid(g, tris.data(), &im);
+    words3[0] = im.blocks.size(); words3[1] = im.records.size(); words3[2] = ShadowGridImageBytes(g) / sizeof(uint32_t);
+    if (blocks && block_cap >= im.blocks.size()) memcpy(blocks, im.blocks.data(), 4 * im.blocks.size());
+    if (records && record_cap >= im.records.size()) memcpy(records, im.records.data(), 4 * im.records.size());
+    return HPRT_OK;
+} catch (...) { return hprt::HandleException(); }
+
 }  // extern "C"

@@ -5,8 +5,10 @@
 
 namespace hprt {
 
-// cellStart[6 R^2 + 1], entries[nEntries] of {ordered primitive | SG_SINGLE, depth key}; entries[0 .. nNear) is the near list
-struct DevShadowGrid { const uint32_t *cellStart; const uint2 *entries; uint32_t nEntries, nNear, R; };
+// The grid's device image (../shadow_grid.h, ShadowGridImage): blocks, 128 bytes per cell with the list's first two candidates in
+// place, then — from byte recordsAt = 6 R^2 * 128 on — records, 48 bytes per further entry, the padding included; the first nNear
+// records are the near list.  One allocation of imageBytes < 2^32, so that the kernel reads both through one buffer resource.
+struct DevShadowGrid { const uint32_t *image; uint32_t imageBytes, recordsAt, nNear, R; };
 
 // Any-hit results of rays that all end at the grid's light, d = fl(light - o): occ[slot] as LaunchTrace's any-hit form writes it.
 // Persistent waves over the index queue (null: rays 0 .. n - 1), as the walks.

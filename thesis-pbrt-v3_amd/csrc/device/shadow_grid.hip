@@ -8,9 +8,13 @@
 // falls into, nearest to the light first; the kernel runs the walk's own tri_test over that list and, on a reported hit, the
 // walk's own leaf-box test (slab_test on the min / max of the vertices for a one-triangle leaf, else on DevScene::leafBox).
 //
-// Persistent waves with the walks' chunked dequeue and entry window.  A lane is a small state machine — ray wanted, cell head
-// wanted, first entry wanted, candidate under test, leaf box wanted — and every iteration of the wave issues the loads of all
-// its lanes' states together and waits once: a lane that starts a new ray costs the others no round trip of their own.
+// The lists are read from the grid's device image (../shadow_grid.h, ShadowGridImage): a 128-byte block per cell that holds the
+// list's head and its first two candidates, vertices and all, and 48-byte records in list order for the rest, so that a ray's
+// typical two or three candidates cost two or three 128-byte lines and as many dependent rounds.  DevScene::tris is not read.
+//
+// Persistent waves with the walks' chunked dequeue and entry window.  A lane is a small state machine — ray wanted, block
+// wanted, the block's second triangle wanted, a record wanted, leaf box wanted — and every iteration of the wave issues the
+// loads of all its lanes' states together and waits once: a lane that starts a new ray costs the others no round trip of their own.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdlib>
@@ -55,24 +59,28 @@ __device__ __forceinline__ bool sg_reaches(uint32_t w, uint32_t sub) {
     return su >= (w & 15u) && su <= ((w >> 4) & 15u) && sv >= ((w >> 8) & 15u) && sv <= ((w >> 12) & 15u);
 }
 
-enum : int { SG_IDLE = 0, SG_RAY = 1, SG_HEAD = 2, SG_FIRST = 3, SG_TEST = 4, SG_BOX = 5 };
+__device__ __forceinline__ float sg_key(uint32_t w) { return __uint_as_float(w & SG_KEY_MASK); }
+
+// SG_BLOCK: the first four words of the cell's block wanted (its head, triangle 0, the key words of entries 1 and 2); SG_BLOCK2: the
+// block's triangle 1; SG_OVER: the 48-byte record of entry i (the near list, a cell's list from its third entry on)
+enum : int { SG_IDLE = 0, SG_RAY = 1, SG_BLOCK = 2, SG_BLOCK2 = 3, SG_OVER = 4, SG_BOX = 5 };
 
 __global__ __launch_bounds__(HPRT_TRACE_BLOCK, HPRT_SHADOW_GRID_WAVES)
 void k_shadow_grid(DevScene sc, DevShadowGrid g, const uint32_t *queue, const uint32_t *countPtr, uint32_t countImm, RayStream rays, uint8_t *occ,
                    uint32_t *workCounter, uint32_t chunk, uint32_t refillMin) {
     const uint32_t n = countPtr ? *countPtr : countImm;
     const uint32_t lane = __lane_id();
-    const auto triRsrc = __builtin_amdgcn_make_buffer_rsrc((void *)sc.tris, 0, (int)(sc.nPrims * 48u), 0x00020000);
     const auto boxRsrc = __builtin_amdgcn_make_buffer_rsrc((void *)sc.leafBox, 0, (int)(sc.nPrims * 32u), 0x00020000);
-    const auto entRsrc = __builtin_amdgcn_make_buffer_rsrc((void *)g.entries, 0, (int)((g.nEntries + 1u) * 8u), 0x00020000);      // (one entry of padding: entries are read in pairs)
-    const auto cellRsrc = __builtin_amdgcn_make_buffer_rsrc((void *)g.cellStart, 0, (int)((6u * g.R * g.R + 1u) * 4u), 0x00020000);
+    const auto imgRsrc = __builtin_amdgcn_make_buffer_rsrc((void *)g.image, 0, (int)g.imageBytes, 0x00020000);      // (blocks, then records: one resource, 32-bit byte offsets)
     const float robust = 1 + 2 * gamma_n(3);
     const float fineScale = 8.f * (float)g.R;
     int st = SG_IDLE;
     bool hit = false;
     uint32_t slot = 0u;
-    // the list being read, entries[i .. end), and the one after it (the near list comes first, then the cell's); SG_HEAD: i is the cell
-    uint32_t i = 0u, end = 0u, i2 = 0u, end2 = 0u;
+    // the list being read (the near list comes first, then the cell's): entry i of cnt is the one wanted or under test; recAt: the byte
+    // offset of entry i's record (a cell's list: of entry 2's while i < 2); kwN: SG_BLOCK2, the key word of entry 2
+    uint32_t i = 0u, cnt = 0u, recAt = 0u, kwN = 0u, cell = 0u;
+    bool nearList = false;
     uint32_t ePrim = 0u;      // the candidate under test (entry i)
     uint32_t sub = 0u;        // the sixteenth of its cell the ray falls into
     vec3 ro, invDir;
@@ -117,23 +125,20 @@ void k_shadow_grid(DevScene sc, DevShadowGrid g, const uint32_t *queue, const ui
         // ---- the loads of every lane's state, issued together ----
         u32x4 r0 = {0u, 0u, 0u, 0u}, r1 = {0u, 0u, 0u, 0u}, r2 = {0u, 0u, 0u, 0u};
         u32x4 r3 = {0u, 0u, 0u, 0u};
-        const uint32_t pi = ePrim & SG_PRIM_MASK;
-        if (st == SG_TEST) {
-            r0 = __builtin_amdgcn_raw_buffer_load_b128(triRsrc, pi * 48u, 0, 0);
-            r1 = __builtin_amdgcn_raw_buffer_load_b128(triRsrc, pi * 48u + 16u, 0, 0);
-            r2 = __builtin_amdgcn_raw_buffer_load_b128(triRsrc, pi * 48u + 32u, 0, 0);
-            if (i + 1u < end) r3 = __builtin_amdgcn_raw_buffer_load_b128(entRsrc, (i + 1u) * 8u, 0, 0);
-        } else if (st == SG_RAY) {
+        if (st == SG_RAY) {
             r0 = __builtin_bit_cast(u32x4, rays.a[slot]);
             r1 = __builtin_bit_cast(u32x4, rays.b[slot]);
-        } else if (st == SG_HEAD) {
-            const u32x2 h = __builtin_amdgcn_raw_buffer_load_b64(cellRsrc, i * 4u, 0, 0);
-            r3.x = h.x; r3.y = h.y;
-        } else if (st == SG_FIRST) {
-            r3 = __builtin_amdgcn_raw_buffer_load_b128(entRsrc, i * 8u, 0, 0);
         } else if (st == SG_BOX) {
+            const uint32_t pi = ePrim & SG_PRIM_MASK;
             r0 = __builtin_amdgcn_raw_buffer_load_b128(boxRsrc, pi * 32u, 0, 0);
             r1 = __builtin_amdgcn_raw_buffer_load_b128(boxRsrc, pi * 32u + 16u, 0, 0);
+        } else if (st != SG_IDLE) {
+            // a triangle with the words in its fourth lanes always arrives in r0 - r2: the block's first, its second, a record's
+            const uint32_t at = st == SG_BLOCK ? cell * 128u + 16u : st == SG_BLOCK2 ? cell * 128u + 64u : recAt;
+            r0 = __builtin_amdgcn_raw_buffer_load_b128(imgRsrc, at, 0, 0);
+            r1 = __builtin_amdgcn_raw_buffer_load_b128(imgRsrc, at + 16u, 0, 0);
+            r2 = __builtin_amdgcn_raw_buffer_load_b128(imgRsrc, at + 32u, 0, 0);
+            if (st == SG_BLOCK) r3 = __builtin_amdgcn_raw_buffer_load_b128(imgRsrc, cell * 128u, 0, 0);
         }
         asm volatile("" : "+v"(r0), "+v"(r1), "+v"(r2), "+v"(r3));
         // ---- one step of every lane ----
@@ -142,9 +147,11 @@ void k_shadow_grid(DevScene sc, DevShadowGrid g, const uint32_t *queue, const ui
             float tEn;
             return slab_test(lx, hx, ly, hy, lz, hz, ro, invDir, invDir.x < 0, invDir.y < 0, invDir.z < 0, robust, &tEn) && tEn < rayTMax;
         };
+        const int st0 = st;         // the state whose loads have arrived
         bool done = false;          // the ray's answer is known
-        bool haveNext = false;      // r3 holds entries i and i + 1 of the list being read
-        if (st == SG_RAY) {
+        bool listEnd = false;       // the list being read holds nothing more for this ray
+        bool doTest = false;        // r0 - r2 hold a candidate (ePrim) that the ray meets
+        if (st0 == SG_RAY) {
             ro = vec3(__uint_as_float(r0.x), __uint_as_float(r0.y), __uint_as_float(r0.z));
             rayTMax = __uint_as_float(r0.w);
             const vec3 d(__uint_as_float(r1.x), __uint_as_float(r1.y), __uint_as_float(r1.z));
@@ -154,21 +161,41 @@ void k_shadow_grid(DevScene sc, DevShadowGrid g, const uint32_t *queue, const ui
             // farther from the light than the origin.  (A caller's ray with tMax > 1 reads its lists to the end.)
             const float dist2 = d.x * d.x + d.y * d.y + d.z * d.z;
             lim = rayTMax <= 1.f ? dist2 * (1.f + 0x1p-20f) : HPRT_INF;
-            i = sg_cell(d, g.R, fineScale, &sub);
-            st = SG_HEAD;
-        } else if (st == SG_HEAD) {
-            if (g.nNear != 0u) { i = 0u; end = g.nNear; i2 = r3.x; end2 = r3.y; }
-            else { i = r3.x; end = r3.y; i2 = end2 = 0u; }
-            st = SG_FIRST;
-            if (i >= end) done = true;      // (an empty cell and no near list)
-        } else if (st == SG_FIRST) {
-            haveNext = true;
-        } else if (st == SG_TEST) {
+            cell = sg_cell(d, g.R, fineScale, &sub);
+            i = 0u;
+            if (g.nNear != 0u) { nearList = true; cnt = g.nNear; recAt = g.recordsAt; st = SG_OVER; }
+            else { nearList = false; st = SG_BLOCK; }
+        } else if (st0 == SG_BLOCK) {
+            // r3: the block's head {count, record of entry 2, prim[0], key[0]}.  (i == 1: back after a leaf box that failed entry 0's hit)
+            cnt = r3.x; recAt = g.recordsAt + r3.y * 48u;
+            if (i == 0u) {
+                if (cnt == 0u || sg_key(r3.w) > lim) listEnd = true;
+                else if (sg_reaches(r3.w, sub)) { doTest = true; ePrim = r3.z; }
+            }
+        } else if (st0 == SG_BLOCK2) {
+            doTest = true;
+        } else if (st0 == SG_OVER) {
+            // a key beyond the ray's origin ends a cell's list (near-list keys are 0); an entry whose triangle does not reach the
+            // ray's sixteenth of the cell is passed over
+            if (sg_key(r1.w) > lim) listEnd = true;
+            else if (sg_reaches(r1.w, sub)) { doTest = true; ePrim = r0.w; }
+        } else if (st0 == SG_BOX) {
+            if (leaf_reached(__uint_as_float(r0.x), __uint_as_float(r0.y), __uint_as_float(r0.z), __uint_as_float(r0.w), __uint_as_float(r1.x), __uint_as_float(r1.y))) { hit = true; done = true; }
+            else {
+                // on with the entry behind the one under test: the block again for its second, else a record
+                ++i;
+                if (nearList || i > 2u) recAt += 48u;
+                if (!nearList && i < 2u) st = SG_BLOCK;
+                else if (i >= cnt) listEnd = true;
+                else st = SG_OVER;
+            }
+        }
+        bool boxWanted = false;
+        if (doTest) {
             asm volatile("" : "+v"(r0), "+v"(r1), "+v"(r2));
             const vec3 p0(__uint_as_float(r0.x), __uint_as_float(r0.y), __uint_as_float(r0.z)), p1(__uint_as_float(r1.x), __uint_as_float(r1.y), __uint_as_float(r1.z)),
                        p2(__uint_as_float(r2.x), __uint_as_float(r2.y), __uint_as_float(r2.z));
             float b0, b1, b2, t;
-            bool boxWanted = false;
             if (tri_test(p0, p1, p2, ro, rayTMax, shear, &b0, &b1, &b2, &t)) {
                 // a hit counts if the reference's walk reaches this primitive's leaf
                 if (ePrim & SG_SINGLE) {
@@ -176,21 +203,26 @@ void k_shadow_grid(DevScene sc, DevShadowGrid g, const uint32_t *queue, const ui
                                      fmaxf(fmaxf(p0.x, p1.x), p2.x), fmaxf(fmaxf(p0.y, p1.y), p2.y), fmaxf(fmaxf(p0.z, p1.z), p2.z))) { hit = true; done = true; }
                 } else boxWanted = true;
             }
-            if (boxWanted) st = SG_BOX;
-            else if (!done) { ++i; haveNext = true; }
-        } else if (st == SG_BOX) {
-            if (leaf_reached(__uint_as_float(r0.x), __uint_as_float(r0.y), __uint_as_float(r0.z), __uint_as_float(r0.w), __uint_as_float(r1.x), __uint_as_float(r1.y))) { hit = true; done = true; }
-            else { ++i; st = SG_FIRST; if (i >= end) { i = i2; end = end2; i2 = end2 = 0u; if (i >= end) done = true; } }
         }
-        if (haveNext) {
-            // entries i and i + 1 have arrived (r3), or the list is at its end.  A key beyond the ray's origin ends a cell's list
-            // (near-list keys are 0); an entry whose triangle does not reach the ray's sixteenth of the cell is passed over.
-            const bool in0 = i < end && !(__uint_as_float(r3.y & SG_KEY_MASK) > lim);
-            const bool in1 = in0 && i + 1u < end && !(__uint_as_float(r3.w & SG_KEY_MASK) > lim);
-            if (in0 && sg_reaches(r3.y, sub)) { ePrim = r3.x; st = SG_TEST; }
-            else if (in1 && sg_reaches(r3.w, sub)) { ePrim = r3.z; ++i; st = SG_TEST; }
-            else if (in1) { i += 2u; st = SG_FIRST; if (i >= end) { i = i2; end = end2; i2 = end2 = 0u; if (i >= end) done = true; } }
-            else { i = i2; end = end2; i2 = end2 = 0u; st = SG_FIRST; if (i >= end) done = true; }
+        if (boxWanted) st = SG_BOX;
+        else if (!done && !listEnd) {
+            // entry i is done with: whether the next one concerns the ray is known from the words that came with this one
+            if (st0 == SG_BLOCK) {
+                i = 1u;
+                if (cnt <= 1u || sg_key(r1.w) > lim) listEnd = true;
+                else if (sg_reaches(r1.w, sub)) { st = SG_BLOCK2; ePrim = r0.w; kwN = r2.w; }
+                else { i = 2u; if (cnt <= 2u || sg_key(r2.w) > lim) listEnd = true; else st = SG_OVER; }
+            } else if (st0 == SG_BLOCK2) {
+                i = 2u;
+                if (cnt <= 2u || sg_key(kwN) > lim) listEnd = true; else st = SG_OVER;
+            } else if (st0 == SG_OVER) {
+                ++i; recAt += 48u;
+                if (i >= cnt || sg_key(r2.w) > lim) listEnd = true;
+            }
+        }
+        if (listEnd) {
+            if (nearList) { nearList = false; i = 0u; st = SG_BLOCK; }      // the near list is through: the cell's
+            else done = true;
         }
         if (done) { occ[slot] = hit ? 1 : 0; st = SG_IDLE; }
     }

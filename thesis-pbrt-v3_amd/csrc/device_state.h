@@ -72,10 +72,10 @@ struct HprtScene {
     hprt::DevBuf nodes, tris, primVtx, primN, vUV, vS, shapes, materials, lights, spheres, instances, topEntry, topEntryWide, lightFunc, lightCdf, perms, primes, primeSums, primeMagic;
     hprt::DevBuf envLights, envData;      // infinite lights: DevEnvLight table and their Distribution2D tables
     hprt::DevBuf wide, leafBox;           // the leaf-exact walk structure (wide_bvh.h)
-    // the light-centred shadow grid (shadow_grid.h; sg.entries == null: the scene is not eligible, its shadow rays take the walk) and
+    // the light-centred shadow grid (shadow_grid.h; sg.image == null: the scene is not eligible, its shadow rays take the walk) and
     // what hprt_debug_shadow_grid_info reports of it
-    hprt::DevBuf sgCells, sgEntries; hprt::DevShadowGrid sg{};
-    struct ShadowGridInfo { uint32_t longest = 0; double buildSeconds = 0, eps = 0; size_t bytes = 0; float light[3] = {0, 0, 0}; uint64_t renderLaunches = 0; } sgInfo;
+    hprt::DevBuf sgImage; hprt::DevShadowGrid sg{};
+    struct ShadowGridInfo { size_t nEntries = 0; uint32_t longest = 0; double buildSeconds = 0, eps = 0; size_t bytes = 0; float light[3] = {0, 0, 0}; uint64_t renderLaunches = 0; } sgInfo;
     hprt::DevBuf counters, workCounter, deepStack;
     // hprt_debug_capture_rays (tools/sort_experiment.py): the next render copies the rays one bounce queues into a caller buffer
     struct Capture { int bounce = -1, kind = 0; float *out7 = nullptr; size_t cap = 0, n = 0; } capture;

@@ -579,9 +579,20 @@ int LayoutShadowGrid(Work &w) {
         return HPRT_OK;
     for (uint32_t i = 0; i < L.nPrims; ++i) if ((f2u(L.tris[3 * (size_t)i].w) & TAG_KIND_MASK) != 0u) return HPRT_OK;
     static_assert(sizeof(float4) == 16, "triangle records are read as 12 floats per primitive");
-    // at most 1 GiB of lists (HPRT_SHADOW_GRID_MAX_MB): a finer grid is halved until it fits
+    // at most 1 GiB of device image (HPRT_SHADOW_GRID_MAX_MB; the kernel forms 32-bit byte offsets into it): a finer grid is halved
+    // until its image fits
     const size_t capMb = [] { const char *e = getenv("HPRT_SHADOW_GRID_MAX_MB"); return e ? (size_t)std::max(1l, atol(e)) : (size_t)1024; }();
-    BuildShadowGrid(&L.tris[0].x, L.primSingle.data(), L.nPrims, L.lights[0].pos, L.wbMin, L.wbMax, ShadowGridResFromEnv(), capMb * ((1u << 20) / sizeof(SgEntry)), mode < 0 ? SG_MAX_CANDIDATES : 0.0, &L.shadowGrid);
+    const size_t capBytes = std::min(capMb << 20, (size_t)0xffff0000u);
+    for (uint32_t R = ShadowGridResFromEnv();; R = std::max(1u, L.shadowGrid.R / 2)) {
+        while (R > 1 && (size_t)6 * R * R * SG_BLOCK_WORDS * sizeof(uint32_t) > capBytes) R /= 2;      // (the blocks alone)
+        // no image that fits holds more entries: the records, and two in every block
+        const size_t maxEntries = capBytes / (SG_RECORD_WORDS * sizeof(uint32_t)) + (size_t)SG_BLOCK_SLOTS * 6 * R * R;
+        BuildShadowGrid(&L.tris[0].x, L.primSingle.data(), L.nPrims, L.lights[0].pos, L.wbMin, L.wbMax, R, maxEntries, mode < 0 ? SG_MAX_CANDIDATES : 0.0, &L.shadowGrid);
+        if (!L.shadowGrid.eligible) return HPRT_OK;
+        if (ShadowGridImageBytes(L.shadowGrid) <= capBytes) break;
+        if (L.shadowGrid.R == 1) { L.shadowGrid = ShadowGrid(); return HPRT_OK; }      // (not even one cell per face fits: the scene keeps the walk)
+    }
+    PackShadowGrid(L.shadowGrid, &L.tris[0].x, &L.shadowGridImage);
     return HPRT_OK;
 }
 

@@ -47,6 +47,7 @@ struct SceneLayout {
     // the light-centred candidate grid of the shadow rays (shadow_grid.h): eligible for a triangle-only scene without instances
     // that is lit by one point light and takes the leaf-exact walk
     ShadowGrid shadowGrid;
+    ShadowGridImage shadowGridImage;               // what is uploaded of it (filled when shadowGrid.eligible)
 };
 
 // Validates *d and fills *out; HPRT_OK or an HPRT_E_* code with hprt_last_error() set.

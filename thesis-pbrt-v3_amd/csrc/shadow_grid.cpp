@@ -158,4 +158,53 @@ void BuildShadowGrid(const float *tris, const uint8_t *single, uint32_t nPrims, 
     g.buildSeconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 }
 
+size_t ShadowGridImageBytes(const ShadowGrid &g) {
+    const size_t nCells = g.cellStart.empty() ? 0 : g.cellStart.size() - 1;
+    size_t nRecords = g.nNear;
+    for (size_t c = 0; c < nCells; ++c) {
+        const uint32_t n = g.cellStart[c + 1] - g.cellStart[c];
+        if (n > SG_BLOCK_SLOTS) nRecords += n - SG_BLOCK_SLOTS;
+    }
+    return (nCells * SG_BLOCK_WORDS + (nRecords + SG_PAD_RECORDS) * SG_RECORD_WORDS) * sizeof(uint32_t);
+}
+
+void PackShadowGrid(const ShadowGrid &g, const float *tris, ShadowGridImage *out) {
+    const auto t0 = std::chrono::steady_clock::now();
+    ShadowGridImage &im = *out;
+    im = ShadowGridImage();
+    im.R = g.R; im.nNear = g.nNear;
+    const size_t nCells = (size_t)6 * g.R * g.R;
+    im.nRecords =(ShadowGridImageBytes(g) / sizeof(uint32_t) - nCells * SG_BLOCK_WORDS) / SG_RECORD_WORDS - SG_PAD_RECORDS;
+    im.blocks.assign(nCells * SG_BLOCK_WORDS, 0u);
+    im.records.assign((im.nRecords + SG_PAD_RECORDS) * SG_RECORD_WORDS, 0u);
+    // a vertex and the word that rides in its fourth lane
+    auto put = [&](uint32_t *w, const SgEntry &e, int vertex, uint32_t fourth) {
+        memcpy(w, tris + 12 * (size_t)(e.prim & SG_PRIM_MASK) + 4 * vertex, 12);
+        w[3] = fourth;
+    };
+    // entries[a .. b) as one run of records at record `at`
+    auto run = [&](size_t at, uint32_t a, uint32_t b) {
+        for (uint32_t k = a; k < b; ++k, ++at) {
+            uint32_t *w = im.records.data() + at * SG_RECORD_WORDS;
+            const SgEntry &e = g.entries[k];
+            put(w, e, 0, e.prim); put(w + 4, e, 1, e.key); put(w + 8, e, 2, k + 1 < b ? g.entries[k + 1].key : 0u);
+        }
+        return at;
+    };
+    size_t at = run(0, 0u, g.nNear);
+    for (size_t c = 0; c < nCells; ++c) {
+        const uint32_t a = g.cellStart[c], n = g.cellStart[c + 1] - a;
+        uint32_t *w = im.blocks.data() + c * SG_BLOCK_WORDS;
+        const SgEntry *e = g.entries.data() + a;
+        w[0] = n; w[1] = (uint32_t)at;
+        if (n > 0) {
+            w[2] = e[0].prim; w[3] = e[0].key;
+            put(w + 4, e[0], 0, n > 1 ? e[1].prim : 0u); put(w + 8, e[0], 1, n > 1 ? e[1].key : 0u); put(w + 12, e[0], 2, n > 2 ? e[2].key : 0u);
+        }
+        if (n > 1) { put(w + 16, e[1], 0, 0u); put(w + 20, e[1], 1, 0u); put(w + 24, e[1], 2, 0u); }
+        if (n > SG_BLOCK_SLOTS) at = run(at, a + SG_BLOCK_SLOTS, a + n);
+    }
+    im.packSeconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+}
+
 }  // namespace hprt

@@ -41,6 +41,34 @@ struct ShadowGrid {
 void BuildShadowGrid(const float *tris, const uint8_t *single, uint32_t nPrims, const float light[3], const float bmin[3],
                      const float bmax[3], uint32_t R, size_t maxEntries, double maxCandidates, ShadowGrid *out);
 
+// The image of a grid that k_shadow_grid reads: the lists with their triangles in list order, so that a ray's candidates arrive
+// with the words that name them instead of being gathered from all over the triangle array.
+//
+// blocks: one 128-byte block per cell, at cell * 128 — eight 16-byte words, of which the kernel reads the first seven:
+//   W0 {entry count, record index of the cell's third entry, prim[0], key[0]}
+//   W1 {p0 of triangle 0, prim[1]}    W2 {p1 of triangle 0, key[1]}    W3 {p2 of triangle 0, key[2]}
+//   W4 {p0 of triangle 1, 0}          W5 {p1 of triangle 1, 0}         W6 {p2 of triangle 1, 0}         W7 {0, 0, 0, 0}
+// (prim[k], key[k]: the two words of the list's entry k, as SgEntry holds them; words of entries the list does not have are 0.)
+// The first two candidates of a list are tested from the block alone, and key[2] tells a ray whether the third concerns it.
+//
+// records: 48 bytes per entry, {p0, prim} {p1, key} {p2, key of the next entry of the same run (0 behind the last)}: the near list
+// as one run at record 0, then per cell, in cell order, the run of its entries from the third on; SG_PAD_RECORDS records of zeros
+// behind the last, so that no read of a record the kernel can form leaves the buffer.
+// The vertex floats are those of the triangle records, bit for bit.
+enum : uint32_t { SG_BLOCK_WORDS = 32u, SG_BLOCK_SLOTS = 2u, SG_RECORD_WORDS = 12u, SG_PAD_RECORDS = 1u };
+struct ShadowGridImage {
+    uint32_t R = 0, nNear = 0;
+    size_t nRecords = 0;                 // near list + overflow runs, without the padding
+    std::vector<uint32_t> blocks;        // 6 R^2 * SG_BLOCK_WORDS
+    std::vector<uint32_t> records;       // (nRecords + SG_PAD_RECORDS) * SG_RECORD_WORDS
+    double packSeconds = 0;
+    size_t bytes() const { return (blocks.size() + records.size()) * sizeof(uint32_t); }
+};
+// the bytes PackShadowGrid's image of g takes, without forming it
+size_t ShadowGridImageBytes(const ShadowGrid &g);
+// tris: the triangle records BuildShadowGrid was given
+void PackShadowGrid(const ShadowGrid &g, const float *tris, ShadowGridImage *out);
+
 // HPRT_SHADOW_GRID: 0 no grid (A/B runs), 1 a grid for every scene that can have one, unset (-1) only where it is expected to
 // be cheaper than the walk (SG_MAX_CANDIDATES); HPRT_SHADOW_GRID_RES: cells per face side.  Read per scene.
 int ShadowGridModeFromEnv();
