@@ -69,6 +69,13 @@ int main(int argc, char **argv) {
     char accel[64] = "";
     TRY(hprt_model_accelerator(model, accel, sizeof(accel)));
     const std::string acc = accel;
+    // Integrator "ambientocclusion" (core/api.cpp:1922): hprt_render_ao with the directive's "nsamples" and "cossample"; every other name
+    // renders the path integrator.  (The cross-tile film records a multi-GPU gather merges stay with hprt_render.)
+    char integ[64] = "";
+    HprtAoParams ao;
+    TRY(hprt_model_integrator(model, integ, sizeof(integ), &ao));
+    const bool ambientOcclusion = std::string(integ) == "ambientocclusion";
+    if (ambientOcclusion && gpus > 1) { std::fprintf(stderr, "Integrator \"ambientocclusion\" renders on one GPU (--gpus 1)\n"); return 2; }
 
     // BVHAccel's constructor on the host (accelerators/bvh.cpp:181-250); for Accelerator "bvhold" BVHAccelOld's
     // (accelerators/bvhOld.cpp:185-227) with the Accelerator line's split method: the same handle, the same walks
@@ -111,14 +118,16 @@ int main(int argc, char **argv) {
             HprtRenderDesc desc; std::memset(&desc, 0, sizeof(desc));
             desc.opt = opt; desc.tile_begin = g; desc.tile_end = 0; desc.tile_stride = gpus;
             desc.flags = gpus > 1 ? HPRT_RENDER_EXPORT_FOREIGN : 0;
-            rcs[(size_t)g] = hprt_render(scenes[(size_t)g], &desc, nullptr, nullptr, &stats[(size_t)g]);      // the library-owned film of this scene
+            // (the library-owned film of this scene)
+            rcs[(size_t)g] = ambientOcclusion ? hprt_render_ao(scenes[(size_t)g], &desc, &ao, nullptr, nullptr, &stats[(size_t)g])
+                                              : hprt_render(scenes[(size_t)g], &desc, nullptr, nullptr, &stats[(size_t)g]);
             if (rcs[(size_t)g] != HPRT_OK) errs[(size_t)g] = hprt_last_error();
         });
     for (std::thread &t : workers) t.join();
     HprtRenderStats total; std::memset(&total, 0, sizeof(total));
     double seconds = 0;
     for (int g = 0; g < gpus; ++g) {
-        if (rcs[(size_t)g] != HPRT_OK) { std::fprintf(stderr, "hprt_render on GPU %d failed (%d): %s\n", g, rcs[(size_t)g], errs[(size_t)g].c_str()); return 1; }
+        if (rcs[(size_t)g] != HPRT_OK) { std::fprintf(stderr, "%s on GPU %d failed (%d): %s\n", ambientOcclusion ? "hprt_render_ao" : "hprt_render", g, rcs[(size_t)g], errs[(size_t)g].c_str()); return 1; }
         const HprtRenderStats &st = stats[(size_t)g];
         total.camera_rays += st.camera_rays; total.rays += st.rays; total.shadow_rays += st.shadow_rays;
         if (st.render_seconds > seconds) seconds = st.render_seconds;

@@ -183,6 +183,12 @@ typedef struct HprtKdTree HprtKdTree;
 /* The scene's Accelerator name as written ("bvh", "kdtree", ...): cap bytes including the terminating 0.  Baked models
  * report "bvh". */
 int hprt_model_accelerator(const HprtModel *m, char *name, size_t cap);
+/* CreateAOIntegrator's parameters (integrators/ao.cpp:105-126): "nsamples" 64, "cossample" true */
+typedef struct HprtAoParams { int32_t n_samples; int32_t cos_sample; } HprtAoParams;
+/* The scene's Integrator name as written ("path", "ambientocclusion", ...): cap bytes including the terminating 0; ao (may
+ * be NULL) receives the parameters of an Integrator "ambientocclusion" line, the defaults for every other name.  Like the
+ * accelerators' parameters these live on the host side of the model and are not baked: baked models report "path". */
+int hprt_model_integrator(const HprtModel *m, char *name, size_t cap, HprtAoParams *ao);
 /* Built with the parameters of the scene's Accelerator line (defaults intersectcost 80, traversalcost 1, emptybonus 0,
  * maxprims 1, maxdepth -1 = round(2 + 1.6 Log2Int(N))).  Models with object instances: HPRT_E_UNSUPPORTED. */
 int hprt_kdtree_build(const HprtModel *m, HprtKdTree **out);
@@ -930,6 +936,31 @@ int hprt_film_records_merge(float *xyzw, size_t n_pixels, HprtFilmRecord *record
  * Test hook for per-sample parity. */
 int hprt_sample_radiance(HprtScene *s, const HprtRenderOptions *opt, size_t n, const int32_t *px, const int32_t *py,
                          const int64_t *sample, float *L_out);
+
+/* ------------------------------------------------------------------------ */
+/* Integrator "ambientocclusion" (core/api.cpp:1922).  SamplerIntegrator::Render */
+/* (core/integrator.cpp:230-360) with AOIntegrator::Li (integrators/ao.cpp:57-103) */
+/* as the estimator: one closest hit per camera sample, then n_samples         */
+/* hemisphere rays from the hit, each answered by Scene::IntersectP            */
+/* (tMax = Infinity), drawn from the sampler's 2D array (Request2DArray,       */
+/* ao.cpp:54; GlobalSampler::StartPixel, core/sampler.cpp:136-166: dimensions  */
+/* 5 and 6 at index GetIndexForSample(pixel sample * n_samples + i)).  The     */
+/* hemisphere rays go through the scene's walk — the BVH or an attached tree — */
+/* never through the shadow grid.                                              */
+/* Same film, tiles, spp_chunk, d_film_xyzw, stream and stats contract as      */
+/* hprt_render (shadow_rays: the hemisphere rays, n_samples per camera ray     */
+/* that hit); opt.max_depth / rr_threshold / light_strategy are not read.      */
+/* Refused: n_samples outside 1..1024 (HPRT_E_INVALID), n_samples * spp above  */
+/* INT32_MAX (the reference's int nSamples = size * samplesPerPixel overflows, */
+/* core/sampler.cpp:157: HPRT_E_UNSUPPORTED), any flag but                     */
+/* HPRT_RENDER_COUNT_WORK (HPRT_E_UNSUPPORTED).                                */
+/* ------------------------------------------------------------------------ */
+int hprt_render_ao(HprtScene *s, const HprtRenderDesc *desc, const HprtAoParams *ao, float *d_film_xyzw, void *stream,
+                   HprtRenderStats *stats);
+/* L (ao.cpp:57-103) of individual camera samples after the guards of core/integrator.cpp:300-321; L3_out = 3*n floats.
+ * The AO twin of hprt_sample_radiance. */
+int hprt_sample_ao(HprtScene *s, const HprtRenderOptions *opt, const HprtAoParams *ao, size_t n, const int32_t *px,
+                   const int32_t *py, const int64_t *sample, float *L3_out);
 
 /* Halton sampler tables (host): ComputeRadicalInversePermutations
  * (core/lowdiscrepancy.cpp:2490-2504) with the default-seeded PCG32. */

@@ -81,6 +81,11 @@ class RenderDesc(C.Structure):
                 ("spp_chunk", C.c_int32), ("flags", C.c_int32)]
 
 
+class AoParams(C.Structure):
+    """HprtAoParams: CreateAOIntegrator's "nsamples" and "cossample" (integrators/ao.cpp:105-126)."""
+    _fields_ = [("n_samples", C.c_int32), ("cos_sample", C.c_int32)]
+
+
 class RenderStats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in (
         "camera_rays", "rays", "shadow_rays", "nodes_fetched", "nodes_fetched_p", "nodes_entered", "nodes_entered_p",
@@ -391,12 +396,17 @@ def _load():
         "hprt_scene_kd_counters": (C.c_int, [vp, vp]),
         "hprt_pixel_kd_stats_read": (C.c_int, [vp, vp, sz]),
         "hprt_write_pixel_stats_rbspkd": (C.c_int, [cp, vp, vp, C.c_int, C.c_int]),
+        "hprt_model_integrator": (C.c_int, [vp, vp, sz, P(AoParams)]),
+        "hprt_render_ao": (C.c_int, [vp, P(RenderDesc), P(AoParams), vp, vp, P(RenderStats)]),
+        "hprt_sample_ao": (C.c_int, [vp, P(RenderOptions), P(AoParams), sz, vp, vp, vp, vp]),
     }
     # the two-level handles' diagnostics hooks (not part of include/hprt.h, so not among EXPORTS)
     debug = {}
     for prefix in ("kdinst", "rbspinst", "bsppaperinst"):
         debug["hprt_debug_%s_bounds" % prefix] = (C.c_int, [vp, C.c_int, vp])
         debug["hprt_debug_%s_set_tree" % prefix] = (C.c_int, [vp, C.c_int, sz, vp, sz, vp, vp])
+    debug["hprt_debug_ao_ray_capacity"] = (sz, [sz])
+    debug["hprt_debug_ao_kernel_seconds"] = (C.c_int, [vp, vp])
     debug["hprt_debug_halton_index"] = (C.c_int, [P(RenderOptions), sz, vp, vp, vp, vp, vp, vp])
     # the light-centred shadow grid (csrc/shadow_grid.h)
     debug["hprt_debug_shadow_grid"] = (C.c_int, [C.c_int])
@@ -454,6 +464,12 @@ def debug_shadow_grid(on):
     """Test hook (not part of include/hprt.h): 0 sends the shadow rays of later plain renders through the walk, 1 through the light-centred
     grid where a scene has one, -1 back to the default (HPRT_SHADOW_GRID at scene creation); returns the setting before."""
     return lib.hprt_debug_shadow_grid(int(on))
+
+
+def debug_ao_ray_capacity(rays):
+    """Test hook (not part of include/hprt.h): the hemisphere rays one any-hit launch of later render_ao calls takes at most (never fewer
+    than one hit's n_samples); 0: back to the default.  Returns the setting before."""
+    return int(lib.hprt_debug_ao_ray_capacity(int(rays)))
 
 
 def shadow_grid_build(p9, light, res):
@@ -595,6 +611,14 @@ class Model:
         buf = C.create_string_buffer(256)
         _check(lib.hprt_model_accelerator(self._h, buf, 256))
         return buf.value.decode()
+
+    def integrator(self):
+        """(name, n_samples, cos_sample): the scene's Integrator name ("path", "ambientocclusion", ...) and the parameters of an
+        "ambientocclusion" line (the defaults 64, True for any other name); baked models report "path"."""
+        buf = C.create_string_buffer(256)
+        ao = AoParams()
+        _check(lib.hprt_model_integrator(self._h, buf, 256, C.byref(ao)))
+        return buf.value.decode(), int(ao.n_samples), bool(ao.cos_sample)
 
     def warnings(self):
         w = lib.hprt_model_warnings(self._h).decode()
@@ -1252,6 +1276,42 @@ class Scene:
             film = np.zeros((y1 - y0, x1 - x0, 4), np.float32)
             _check(lib.hprt_film_read(self._h, _ptr(film), film.shape[0] * film.shape[1]))
         return film, st.as_dict()
+
+    def render_ao(self, n_samples=64, cos_sample=True, opt=None, tile_begin=0, tile_end=0, tile_stride=1, spp_chunk=0, count_work=False,
+                  film_ptr=None, stream=None):
+        """hprt_render_ao: Render() with AOIntegrator::Li (integrators/ao.cpp) as the estimator; returns what render() returns."""
+        opt = opt or self._model.options
+        desc = RenderDesc()
+        desc.opt = opt
+        desc.tile_begin, desc.tile_end, desc.tile_stride = tile_begin, tile_end, tile_stride
+        desc.spp_chunk = spp_chunk
+        desc.flags = RENDER_COUNT_WORK if count_work else 0
+        ao = AoParams(int(n_samples), int(bool(cos_sample)))
+        st = RenderStats()
+        _check(lib.hprt_render_ao(self._h, C.byref(desc), C.byref(ao), film_ptr, stream, C.byref(st)))
+        self._film_shape = tuple(int(v) for v in (opt.film_bounds()[3] - opt.film_bounds()[1], opt.film_bounds()[2] - opt.film_bounds()[0]))
+        film = None
+        if film_ptr is None:
+            x0, y0, x1, y1 = opt.film_bounds()
+            film = np.zeros((y1 - y0, x1 - x0, 4), np.float32)
+            _check(lib.hprt_film_read(self._h, _ptr(film), film.shape[0] * film.shape[1]))
+        return film, st.as_dict()
+
+    def ao_kernel_seconds(self):
+        """Measurement hook (not part of include/hprt.h): HIP-event seconds of (k_ao_frame, k_ao_rays, k_ao_resolve) in the last render_ao."""
+        out = np.zeros(3, np.float64)
+        _check(lib.hprt_debug_ao_kernel_seconds(self._h, _ptr(out)))
+        return tuple(float(v) for v in out)
+
+    def sample_ao(self, px, py, sample, n_samples, cos_sample, opt=None):
+        """hprt_sample_ao: L of individual camera samples under the ambient-occlusion estimator, [n, 3] float32."""
+        opt = opt or self._model.options
+        px = np.ascontiguousarray(px, np.int32); py = np.ascontiguousarray(py, np.int32)
+        sample = np.ascontiguousarray(sample, np.int64)
+        L = np.zeros((px.shape[0], 3), np.float32)
+        ao = AoParams(int(n_samples), int(bool(cos_sample)))
+        _check(lib.hprt_sample_ao(self._h, C.byref(opt), C.byref(ao), px.shape[0], _ptr(px), _ptr(py), _ptr(sample), _ptr(L)))
+        return L
 
     def reserve(self, opt=None, tile_begin=0, tile_end=0, tile_stride=1, spp_chunk=0):
         """hprt_scene_reserve: allocate the workspace of the coming render now (a host that renders once pays it at load)."""

@@ -16,6 +16,7 @@
 #include <vector>
 #include "../../include/hprt.h"
 #include "device/kernels.h"
+#include "device/ao.h"
 #include "halton_tables.h"
 #include "host_transform.h"
 #include "hprt_internal.h"
@@ -1157,7 +1158,7 @@ int EnsureWorkspace(HprtScene *s, size_t nSlots, Workspace *ps, QueueSet *qa, Qu
 // it never wrote (a fresh allocation on a busy card holds other processes' data, not zeros).
 int PoisonWorkspace(HprtScene *s) {
     if (s->poisonByte < 0) return HPRT_OK;
-    hprt::DevBuf *bufs[] = {&s->planes, &s->queues, &s->Lall, &s->deepStack, &s->rayStats, &s->irregular};
+    hprt::DevBuf *bufs[] = {&s->planes, &s->queues, &s->Lall, &s->deepStack, &s->rayStats, &s->irregular, &s->aoSlots, &s->aoRays};
     for (hprt::DevBuf *b : bufs) if (b->p && b->bytes) HIP_TRY(hipMemset(b->p, s->poisonByte, b->bytes));
     HIP_TRY(hipDeviceSynchronize());
     return HPRT_OK;
@@ -1190,17 +1191,110 @@ int ChooseBatch(HprtScene *s, int32_t sppChunk, uint32_t nPix, uint32_t spp, uin
 // order the reference's tile loop would have added them (core/integrator.cpp:267-333).
 struct ExtraEntry { uint32_t dest; uint32_t srcTile; uint32_t srcPos; uint32_t sample; uint32_t srcPix; uint8_t pre; };
 
+// ---- Integrator "ambientocclusion" (device/ao.h): AOIntegrator::Li, integrators/ao.cpp:57-103 ----
+// Hemisphere rays per any-hit launch: the buffer of fixed size a batch's rays go through, hit range by hit range (1.2 GB of rays,
+// terms and bytes).  hprt_debug_ao_ray_capacity (tests) lowers it so that small renders take several ranges too.
+constexpr size_t kAoRayCapacity = (size_t)1 << 25, kAoRayBytes = 32 + 4 + 1;
+size_t g_aoRayCapacity = kAoRayCapacity;
+// Camera samples per batch: 136 bytes each (ray, hit, hit record), 16 M of them unless the caller's spp_chunk says otherwise
+constexpr size_t kAoSlotCapacity = (size_t)1 << 24;
+struct AoWorkspace { RayStream cam; HitStream hit; AoRecords recs; uint32_t *hitCount; RayStream rays; float *term; uint8_t *occ; size_t rayCap; };
+int CheckAoParams(const HprtAoParams *ao, int32_t spp, const char *fn) {
+    if (!ao) return SetError(HPRT_E_INVALID, std::string(fn) + ": null argument");
+    if (ao->n_samples < 1 || ao->n_samples > (int32_t)AO_MAX_SAMPLES)
+        return SetError(HPRT_E_INVALID, std::string(fn) + ": n_samples must lie in 1..1024");
+    if (spp <= 0) return SetError(HPRT_E_INVALID, "spp must be positive");
+    if ((int64_t)ao->n_samples * (int64_t)spp > 0x7fffffffll)
+        return SetError(HPRT_E_UNSUPPORTED, std::string(fn) + ": n_samples * spp exceeds INT32_MAX (the reference's int nSamples = size * samplesPerPixel "
+                                            "overflows there, core/sampler.cpp:157)");
+    return HPRT_OK;
+}
+int EnsureAoWorkspace(HprtScene *s, size_t nSlots, uint32_t nSamples, uint64_t maxRays, AoWorkspace *w) {
+    const bool instances = s->dev.nInstances != 0u;
+    HIP_TRY(s->aoSlots.alloc(nSlots * (32 + 16 + (instances ? 8 : 0) + 16 * AO_RECORD_PLANES) + 16 * 256));
+    PlaneAllocator a{s->aoSlots.as<char>(), 0, 0};
+    w->cam.a = a.take<float4>(nSlots); w->cam.b = a.take<float4>(nSlots);
+    w->hit.a = a.take<float4>(nSlots); w->hit.b = instances ? a.take<float2>(nSlots) : nullptr;
+    w->recs.rec = a.take<float4>(nSlots * AO_RECORD_PLANES); w->recs.stride = (uint32_t)nSlots;
+    w->hitCount = a.take<uint32_t>(64);
+    // never less than one hit's rays, never more than the render can produce
+    w->rayCap = (size_t)std::min<uint64_t>(std::max<uint64_t>(g_aoRayCapacity, nSamples), std::max<uint64_t>(maxRays, nSamples));
+    HIP_TRY(s->aoRays.alloc(w->rayCap * kAoRayBytes + 16 * 256));
+    PlaneAllocator b{s->aoRays.as<char>(), 0, 0};
+    w->rays.a = b.take<float4>(w->rayCap); w->rays.b = b.take<float4>(w->rayCap);
+    w->term = b.take<float>(w->rayCap); w->occ = b.take<uint8_t>(w->rayCap);
+    return HPRT_OK;
+}
+// One batch of nSlots camera samples: k_generate -> closest-hit trace -> k_ao_frame -> [hit count to the host] -> per range of hits
+// whose rays fit the ray buffer: k_ao_rays -> any-hit trace -> k_ao_resolve.  The any-hit trace is the scene's walk whatever the
+// scene: ShadowGridInUse is a property of the path render's light-directed rays, and these end at no light.
+int RunAoBatch(HprtScene *s, hipStream_t st, const RenderParams &rp, const HprtAoParams &ao, const AoWorkspace &w, const uint64_t *aoBase, uint32_t s0,
+               uint32_t nSlots, bool count, const AoRadiance &out, EventTimer &ev, BatchTimers *bt, HprtRenderStats *stats, const IrregularSink *irregular) {
+    const uint32_t n = (uint32_t)ao.n_samples;
+    PathStream camPath; camPath.ray = w.cam; camPath.beta = nullptr; camPath.L = nullptr;      // (k_generate stores the ray alone)
+    DevCounters *ctr = s->counters.as<DevCounters>();
+    uint32_t *wc = s->workCounter.as<uint32_t>();
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> evExt, evOcc, evAo[3];      // (evAo: the three kernels of device/ao.hip, for tools/bench_ao.py)
+    auto timed = [&](std::vector<std::pair<hipEvent_t, hipEvent_t>> &into, auto launch) -> int {
+        hipEvent_t e0 = ev.get(), e1 = ev.get();
+        HIP_TRY(hipEventRecord(e0, st));
+        launch();
+        HIP_TRY(hipEventRecord(e1, st));
+        into.push_back({e0, e1});
+        return HPRT_OK;
+    };
+    LaunchGenerate(st, s->dev, rp, camPath, s0, nSlots, irregular);
+    {
+        hipEvent_t e0 = ev.get(), e1 = ev.get();
+        HIP_TRY(hipEventRecord(e0, st));
+        Trace(s, st, false, count, nullptr, nullptr, nSlots, nSlots, w.cam, w.hit, nullptr, ctr, wc);
+        HIP_TRY(hipEventRecord(e1, st));
+        evExt.push_back({e0, e1}); bt->extendRays += nSlots; ++bt->extendLaunches;
+        stats->rays += nSlots;
+    }
+    HIP_TRY(hipMemsetAsync(w.hitCount, 0, sizeof(uint32_t), st));
+    if (int rc = timed(evAo[0], [&] { LaunchAoFrame(st, s->dev, rp, w.cam, w.hit, nSlots, s0, n, aoBase, w.recs, w.hitCount, out); })) return rc;
+    HIP_TRY(hipMemcpyAsync(s->hostCounts + 9, w.hitCount, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const uint32_t nHits = s->hostCounts[9];
+    if (nHits > nSlots) return SetError(HPRT_E_DEVICE, "internal error: more ambient-occlusion hits than camera samples");
+    const uint32_t hitsPerRange = (uint32_t)(w.rayCap / n);
+    HitStream none; none.a = nullptr; none.b = nullptr;
+    for (uint32_t h0 = 0; h0 < nHits; h0 += hitsPerRange) {
+        const uint32_t nh = std::min(hitsPerRange, nHits - h0), nr = nh * n;
+        if (int rc = timed(evAo[1], [&] { LaunchAoRays(st, s->dev, rp.hal, w.recs, h0, nh, n, ao.cos_sample != 0, w.rays, w.term); })) return rc;
+        hipEvent_t a = ev.get(), b = ev.get();
+        HIP_TRY(hipEventRecord(a, st));
+        Trace(s, st, true, count, nullptr, nullptr, nr, nr, w.rays, none, w.occ, ctr, wc);
+        HIP_TRY(hipEventRecord(b, st));
+        evOcc.push_back({a, b}); bt->occludedRays += nr; ++bt->occludedLaunches;
+        stats->shadow_rays += nr;
+        if (int rc = timed(evAo[2], [&] { LaunchAoResolve(st, w.recs, h0, nh, n, w.occ, w.term, out); })) return rc;
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    for (auto &p : evExt) { float ms = 0; if (hipEventElapsedTime(&ms, p.first, p.second) == hipSuccess) bt->extendMs += ms; }
+    for (auto &p : evOcc) { float ms = 0; if (hipEventElapsedTime(&ms, p.first, p.second) == hipSuccess) bt->occludedMs += ms; }
+    for (int k = 0; k < 3; ++k)
+        for (auto &p : evAo[k]) { float ms = 0; if (hipEventElapsedTime(&ms, p.first, p.second) == hipSuccess) s->aoKernelMs[k] += ms; }
+    ev.reset();
+    return HPRT_OK;
+}
+
 }  // namespace
 
-int hprt_render(HprtScene *s, const HprtRenderDesc *desc, float *d_film_xyzw, void *stream, HprtRenderStats *stats) try {
-    if (!s || !desc) return SetError(HPRT_E_INVALID, "hprt_render: null argument");
+// SamplerIntegrator::Render (core/integrator.cpp:230-360) with the estimator of hprt_render (ao == null: PathIntegrator::Li) or of
+// hprt_render_ao (AOIntegrator::Li): the same tiles, batches of camera samples, per-sample radiance store and film kernels
+static int RenderImpl(HprtScene *s, const HprtRenderDesc *desc, const HprtAoParams *ao, float *d_film_xyzw, void *stream, HprtRenderStats *stats) {
     HIP_TRY(hipSetDevice(s->device));
     hipStream_t st = (hipStream_t)stream;
     SceneCall call(s, st);      // (blocking: every path out of a started render has synchronised `st`, or failed)
     const HprtRenderOptions &o = desc->opt;
     int rc0;
-    if (o.spp <= 0 || o.max_depth < 0) return SetError(HPRT_E_INVALID, "spp must be positive and max_depth non-negative");
-    if ((rc0 = CheckDepth(o.max_depth)) != HPRT_OK) return rc0;
+    if (!ao) {
+        if (o.spp <= 0 || o.max_depth < 0) return SetError(HPRT_E_INVALID, "spp must be positive and max_depth non-negative");
+        if ((rc0 = CheckDepth(o.max_depth)) != HPRT_OK) return rc0;
+    }
     FrameSetup f;
     int rc = SetupFrame(o, &f);
     if (rc != HPRT_OK) return rc;
@@ -1232,11 +1326,18 @@ int hprt_render(HprtScene *s, const HprtRenderDesc *desc, float *d_film_xyzw, vo
     // two batches of 512 instead of 522 + 502 or, at the old 128 M cap, four of 256: -1 % per frame).  killeroo-simple
     // at 256 spp is one batch of 125 M paths: 6.5 % faster than two batches of 64 M.  (HPRT_BATCH_MPATHS changes the cap.)
     uint32_t chunk = 0;
-    if ((rc = ChooseBatch(s, desc->spp_chunk, nPix, spp, &chunk)) != HPRT_OK) return rc;
+    Workspace ps; QueueSet qa, qb; BinSet bins; AoWorkspace aw;
+    if (ao) {
+        for (double &ms : s->aoKernelMs) ms = 0;
+        // Ambient occlusion: spp_chunk keeps its meaning, an upper bound per pixel; left to the library, a batch holds up to
+        // kAoSlotCapacity camera samples.  Its hemisphere rays go through the ray buffer range by range (RunAoBatch).
+        chunk = desc->spp_chunk > 0 ? (uint32_t)desc->spp_chunk : std::max<uint32_t>(1u, (uint32_t)(kAoSlotCapacity / nPix));
+        chunk = std::min(chunk, spp);
+        if ((uint64_t)chunk * nPix > 0x7fffffffull) chunk = (uint32_t)(0x7fffffffull / nPix);
+        if ((rc = EnsureAoWorkspace(s, (size_t)chunk * nPix, (uint32_t)ao->n_samples, (uint64_t)chunk * nPix * (uint64_t)ao->n_samples, &aw)) != HPRT_OK) return rc;
+    } else if ((rc = ChooseBatch(s, desc->spp_chunk, nPix, spp, &chunk)) != HPRT_OK) return rc;
     const size_t maxSlots = (size_t)chunk * nPix;
-    Workspace ps; QueueSet qa, qb; BinSet bins;
-    rc = EnsureWorkspace(s, maxSlots, &ps, &qa, &qb, &bins);
-    if (rc != HPRT_OK) return rc;
+    if (!ao && (rc = EnsureWorkspace(s, maxSlots, &ps, &qa, &qb, &bins)) != HPRT_OK) return rc;
     HIP_TRY(s->Lall.alloc(lallBytes));
     if ((rc = PoisonWorkspace(s)) != HPRT_OK) return rc;
     float *LallR = s->Lall.as<float>(), *LallG = LallR + (size_t)spp * nPix, *LallB = LallG + (size_t)spp * nPix;
@@ -1287,6 +1388,11 @@ int hprt_render(HprtScene *s, const HprtRenderDesc *desc, float *d_film_xyzw, vo
     EventTimer ev; BatchTimers bt;
     for (uint32_t s0 = 0; s0 < spp; s0 += chunk) {
         const uint32_t c = std::min(chunk, spp - s0), nSlots = c * nPix;
+        if (ao) {      // (k_ao_frame and k_ao_resolve store each sample where k_store_radiance would)
+            rc = RunAoBatch(s, st, rp, *ao, aw, nullptr, s0, nSlots, count, AoRadiance{LallR, LallG, LallB, (size_t)s0 * nPix}, ev, &bt, stats, &sink);
+            if (rc != HPRT_OK) return rc;
+            continue;
+        }
         rc = RunBatch(s, st, rp, ps, qa, qb, bins, s0, nSlots, count, ev, &bt, stats, pixelStats, &sink);
         if (rc != HPRT_OK) return rc;
         LaunchStoreRadiance(st, ps.Lfinal, LallR, LallG, LallB, nPix, s0, nSlots);
@@ -1395,7 +1501,37 @@ int hprt_render(HprtScene *s, const HprtRenderDesc *desc, float *d_film_xyzw, vo
         stats->nodes_fetched_p = c.nodesFetchedP; stats->nodes_entered_p = c.nodesEnteredP; stats->tri_tests_p = c.triTestsP; stats->sphere_tests_p = c.sphereTestsP;
     }
     return HPRT_OK;
+}
+int hprt_render(HprtScene *s, const HprtRenderDesc *desc, float *d_film_xyzw, void *stream, HprtRenderStats *stats) try {
+    if (!s || !desc) return SetError(HPRT_E_INVALID, "hprt_render: null argument");
+    return RenderImpl(s, desc, nullptr, d_film_xyzw, stream, stats);
 } catch (...) { return hprt::HandleException(); }
+// The parameters are judged before the scene and the device are looked at: a refusal does not depend on either
+int hprt_render_ao(HprtScene *s, const HprtRenderDesc *desc, const HprtAoParams *ao, float *d_film_xyzw, void *stream, HprtRenderStats *stats) try {
+    if (!desc) return SetError(HPRT_E_INVALID, "hprt_render_ao: null argument");
+    if (int rc = CheckAoParams(ao, desc->opt.spp, "hprt_render_ao")) return rc;
+    if (desc->flags & ~HPRT_RENDER_COUNT_WORK)
+        return SetError(HPRT_E_UNSUPPORTED, "hprt_render_ao: only HPRT_RENDER_COUNT_WORK is supported (per-pixel statistics, EXPORT_FOREIGN, TRACE_ALL and "
+                                            "COUNT_TRACED stay with hprt_render)");
+    int dev;
+    if (int rc = CheckDevice(s ? s->device : -1, &dev)) return rc;
+    if (!s) return SetError(HPRT_E_INVALID, "hprt_render_ao: null argument");
+    return RenderImpl(s, desc, ao, d_film_xyzw, stream, stats);
+} catch (...) { return hprt::HandleException(); }
+// Diagnostics hook (not part of include/hprt.h; tools/bench_ao.py): HIP-event seconds of k_ao_frame, k_ao_rays and k_ao_resolve in the
+// scene's last hprt_render_ao
+__attribute__((visibility("default"))) int hprt_debug_ao_kernel_seconds(HprtScene *s, double out3[3]) {
+    if (!s || !out3) return HPRT_E_INVALID;
+    for (int k = 0; k < 3; ++k) out3[k] = s->aoKernelMs[k] * 1e-3;
+    return HPRT_OK;
+}
+// Diagnostics hook (not part of include/hprt.h; tests/test_gpu_ao.py): the hemisphere rays one any-hit launch of later hprt_render_ao
+// calls takes at most (never fewer than one hit's); 0: back to the default.  Returns the setting before.
+__attribute__((visibility("default"))) size_t hprt_debug_ao_ray_capacity(size_t rays) {
+    const size_t was = g_aoRayCapacity;
+    g_aoRayCapacity = rays ? rays : kAoRayCapacity;
+    return was;
+}
 
 // Pays for the coming hprt_render(s, desc, ...) at load time: the wavefront workspace (path streams and queues: ~365 B per path of
 // a batch, 98 GB for a 256 M-path batch) and the per-sample radiance store are allocated now, so that the render itself starts
@@ -1508,6 +1644,52 @@ int hprt_sample_radiance(HprtScene *s, const HprtRenderOptions *opt, size_t n, c
     std::vector<float> planes(3 * n);
     HIP_TRY(hipMemcpy(planes.data(), LR, 12 * n, hipMemcpyDeviceToHost));
     for (size_t i = 0; i < n; ++i) { L_out[3 * i] = planes[i]; L_out[3 * i + 1] = planes[n + i]; L_out[3 * i + 2] = planes[2 * n + i]; }
+    return HPRT_OK;
+} catch (...) { return hprt::HandleException(); }
+
+// hprt_sample_radiance for the ambient-occlusion estimator: slot i is sample[i] of pixel (px[i], py[i]); its camera sample sits at
+// GetIndexForSample(sample), its array samples at GetIndexForSample(sample * n_samples + j)
+int hprt_sample_ao(HprtScene *s, const HprtRenderOptions *opt, const HprtAoParams *ao, size_t n, const int32_t *px, const int32_t *py,
+                   const int64_t *sample, float *L3_out) try {
+    if (!opt || (n && (!px || !py || !sample || !L3_out))) return SetError(HPRT_E_INVALID, "hprt_sample_ao: null argument");
+    if (int rc = CheckAoParams(ao, std::max(1, opt->spp), "hprt_sample_ao")) return rc;
+    if (n > (1u << 22)) return SetError(HPRT_E_INVALID, "hprt_sample_ao: too many samples in one call");
+    int dev;
+    if (int rc = CheckDevice(s ? s->device : -1, &dev)) return rc;
+    if (!s) return SetError(HPRT_E_INVALID, "hprt_sample_ao: null argument");
+    if (n == 0) return HPRT_OK;
+    SceneCall call(s, nullptr);
+    FrameSetup f;
+    int rc = SetupFrame(*opt, &f);
+    if (rc != HPRT_OK) return rc;
+    std::vector<uint32_t> xy(n); std::vector<uint64_t> off(2 * n);      // camera-sample indices, then the first array sample's
+    for (size_t i = 0; i < n; ++i) {
+        if (px[i] < f.fg.sx0 || px[i] >= f.fg.sx1 || py[i] < f.fg.sy0 || py[i] >= f.fg.sy1 || sample[i] < 0 || sample[i] > 0x7fffffffll)
+            return SetError(HPRT_E_INVALID, "hprt_sample_ao: pixel outside the sample bounds, or sample number out of range");
+        xy[i] = (uint32_t)px[i] | ((uint32_t)py[i] << 16);
+        const uint64_t pixelOffset = (uint64_t)HaltonPixelOffset(f.hal, px[i], py[i]);
+        off[i] = pixelOffset + (uint64_t)sample[i] * (uint64_t)f.hal.sampleStride;
+        off[n + i] = pixelOffset + (uint64_t)sample[i] * (uint64_t)ao->n_samples * (uint64_t)f.hal.sampleStride;
+    }
+    AoWorkspace aw;
+    if ((rc = EnsureAoWorkspace(s, n, (uint32_t)ao->n_samples, (uint64_t)n * (uint64_t)ao->n_samples, &aw)) != HPRT_OK) return rc;
+    HIP_TRY(upload(s->pixelXY, xy)); HIP_TRY(upload(s->pixelOffset, off));
+    HIP_TRY(s->Lall.alloc(12 * n));
+    if ((rc = PoisonWorkspace(s)) != HPRT_OK) return rc;
+    RenderParams rp;
+    MakeCamera(*opt, &rp.cam);
+    rp.hal.baseScale1 = f.hal.baseScales[1]; rp.hal.baseExp0 = f.hal.baseExponents[0]; rp.hal.sampleStride = f.hal.sampleStride;
+    rp.hal.samplePixelCenter = opt->sample_pixel_center;
+    rp.pixelXY = s->pixelXY.as<uint32_t>(); rp.pixelOffset = s->pixelOffset.as<uint64_t>(); rp.nPix = (uint32_t)n;
+    rp.maxDepth = 0; rp.rrThreshold = 0.f; rp.invSqrtSpp = 1.f; rp.cullMis = 1; rp.speculate = rp.foldRepair = 0;      // (not read)
+    EventTimer ev; BatchTimers bt; HprtRenderStats stats; memset(&stats, 0, sizeof(stats));
+    float *LR = s->Lall.as<float>();
+    rc = RunAoBatch(s, nullptr, rp, *ao, aw, rp.pixelOffset + n, 0, (uint32_t)n, false, AoRadiance{LR, LR + n, LR + 2 * n, 0}, ev, &bt, &stats, nullptr);
+    if (rc != HPRT_OK) return rc;
+    HIP_TRY(hipGetLastError()); HIP_TRY(hipDeviceSynchronize());
+    std::vector<float> planes(3 * n);
+    HIP_TRY(hipMemcpy(planes.data(), LR, 12 * n, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; ++i) { L3_out[3 * i] = planes[i]; L3_out[3 * i + 1] = planes[n + i]; L3_out[3 * i + 2] = planes[2 * n + i]; }
     return HPRT_OK;
 } catch (...) { return hprt::HandleException(); }
 

@@ -822,7 +822,9 @@ int hprt_model_parse(const char *pbrt_path, const char *const *subst, int n_subs
         m->sc.warnings.push_back("Accelerator \"bvhold\": the host builds the tree (hprt_bvhold_build) and passes it to hprt_scene_create_from_model; "
                                  "hprt_bvh_build builds the fork's BVH");
     else if (acc != "bvh") m->sc.warnings.push_back("Accelerator \"" + acc + "\" is outside the hot-path scope; \"bvh\" used");
-    if (m->sc.opt.integrator != "path") m->sc.warnings.push_back("Integrator \"" + m->sc.opt.integrator + "\" is outside the hot-path scope; \"path\" used");
+    if (m->sc.opt.integrator == "ambientocclusion")
+        m->sc.warnings.push_back("Integrator \"ambientocclusion\": the host renders it with hprt_render_ao; hprt_render renders the path integrator");
+    else if (m->sc.opt.integrator != "path") m->sc.warnings.push_back("Integrator \"" + m->sc.opt.integrator + "\" is outside the hot-path scope; \"path\" used");
     if (m->sc.opt.sampler != "halton") m->sc.warnings.push_back("Sampler \"" + m->sc.opt.sampler + "\" is outside the hot-path scope; \"halton\" used");
     *out = m;
     return HPRT_OK;
@@ -1054,6 +1056,14 @@ int hprt_model_accelerator(const HprtModel *m, char *name, size_t cap) try {
     const std::string &a = m->sc.opt.accelerator;
     if (a.size() + 1 > cap) return SetError(HPRT_E_INVALID, "hprt_model_accelerator: buffer too small");
     memcpy(name, a.c_str(), a.size() + 1);
+    return HPRT_OK;
+} catch (...) { return hprt::HandleException(); }
+int hprt_model_integrator(const HprtModel *m, char *name, size_t cap, HprtAoParams *ao) try {
+    if (!m || !name || cap == 0) return SetError(HPRT_E_INVALID, "hprt_model_integrator: bad argument");
+    const std::string &a = m->sc.opt.integrator;
+    if (a.size() + 1 > cap) return SetError(HPRT_E_INVALID, "hprt_model_integrator: buffer too small");
+    memcpy(name, a.c_str(), a.size() + 1);
+    if (ao) { ao->n_samples = m->sc.opt.aoSamples; ao->cos_sample = m->sc.opt.aoCosSample; }
     return HPRT_OK;
 } catch (...) { return hprt::HandleException(); }
 int hprt_kdtree_build(const HprtModel *m, HprtKdTree **out) try {

@@ -93,6 +93,8 @@ struct HprtScene {
     hprt::DevBuf planes;                                    // backing store of the path streams (Workspace)
     hprt::DevBuf apiRays, apiHits;                          // stream copies of the plane-layout arguments of the *_device calls
     hprt::DevBuf queues, queueCounts;
+    double aoKernelMs[3] = {0, 0, 0};                       // HIP-event time of k_ao_frame, k_ao_rays and k_ao_resolve in the last hprt_render_ao (hprt_debug_ao_kernel_seconds)
+    hprt::DevBuf aoSlots, aoRays;                           // hprt_render_ao: the camera samples' streams and hit records; the hemisphere rays, terms and bytes
     hprt::DevBuf pixelXY, pixelOffset, Lall, film, irregular, irregularCount;
     hprt::DevBuf exOwnBegin, exOwnSrc, exOwnSample, exOwnPre, exFDest, exFDestBegin, exFGroupBegin, exFSrc, exFSample;
     // HPRT_RENDER_EXPORT_FOREIGN: the cross-tile film contributions of the last render, one record per (destination

@@ -609,11 +609,18 @@ struct Frontend {
         // CreateHaltonSampler, samplers/halton.cpp:133-139
         o.spp = samplerParams.oneInt("pixelsamples", 16);
         o.samplePixelCenter = samplerParams.oneBool("samplepixelcenter", false) ? 1 : 0;
-        // CreatePathIntegrator, integrators/path.cpp:206-229
-        o.maxDepth = integratorParams.oneInt("maxdepth", 5);
-        o.rrThreshold = integratorParams.oneFloat("rrthreshold", 1.f);
-        std::string ls = integratorParams.oneString("lightsamplestrategy", "spatial");
-        o.lightStrategy = ls == "uniform" ? kUniform : (ls == "power" ? kPower : kSpatial);
+        if (sc->opt.integrator == "ambientocclusion") {
+            // CreateAOIntegrator, integrators/ao.cpp:105-126: it reads none of the path integrator's parameters, so those are reported
+            // unused below as the reference reports them (and keep their defaults in the baked options)
+            o.aoSamples = integratorParams.oneInt("nsamples", 64);
+            o.aoCosSample = integratorParams.oneBool("cossample", true) ? 1 : 0;
+        } else {
+            // CreatePathIntegrator, integrators/path.cpp:206-229
+            o.maxDepth = integratorParams.oneInt("maxdepth", 5);
+            o.rrThreshold = integratorParams.oneFloat("rrthreshold", 1.f);
+            std::string ls = integratorParams.oneString("lightsamplestrategy", "spatial");
+            o.lightStrategy = ls == "uniform" ? kUniform : (ls == "power" ? kPower : kSpatial);
+        }
         // CreateBVHAccelerator, accelerators/bvh.cpp:529-535
         o.maxNodePrims = accelParams.oneInt("maxnodeprims", 4);
         o.isectCost = accelParams.oneInt("intersectcost", 8);

@@ -101,6 +101,8 @@ struct RenderOptions {
     // Accelerator "bvhold": CreateBVHAcceleratorOld's "splitmethod" (0 sah, 1 hlbvh, 2 middle, 3 equal: BVHOLD_*) and "maxnodeprims"
     // (accelerators/bvhOld.cpp:742-762); host side only (not baked)
     int32_t bvhOldSplitMethod = 0, bvhOldMaxNodePrims = 4;
+    // Integrator "ambientocclusion": CreateAOIntegrator's "nsamples" and "cossample" (integrators/ao.cpp:105-126); host side only (not baked)
+    int32_t aoSamples = 64, aoCosSample = 1;
     std::string filename = "pbrt.exr", accelerator = "bvh", integrator = "path", sampler = "halton";
 };
 struct SceneModel {
