@@ -76,6 +76,16 @@ int main(int argc, char **argv) {
     TRY(hprt_model_integrator(model, integ, sizeof(integ), &ao));
     const bool ambientOcclusion = std::string(integ) == "ambientocclusion";
     if (ambientOcclusion && gpus > 1) { std::fprintf(stderr, "Integrator \"ambientocclusion\" renders on one GPU (--gpus 1)\n"); return 2; }
+    // Integrator "directlighting" (core/api.cpp:1913): hprt_render_direct with the directive's "strategy" and "maxdepth" and every light's
+    // sample count as the scene file gives it
+    const bool directLighting = std::string(integ) == "directlighting";
+    HprtDirectParams direct;
+    size_t nLights = 0;
+    TRY(hprt_model_direct(model, &direct, nullptr, 0, &nLights));
+    std::vector<int32_t> lightSamples(nLights, 1);
+    if (nLights) TRY(hprt_model_direct(model, nullptr, lightSamples.data(), nLights, nullptr));
+    if (directLighting && gpus > 1) { std::fprintf(stderr, "Integrator \"directlighting\" renders on one GPU (--gpus 1)\n"); return 2; }
+    const char *renderName = ambientOcclusion ? "hprt_render_ao" : directLighting ? "hprt_render_direct" : "hprt_render";
 
     // BVHAccel's constructor on the host (accelerators/bvh.cpp:181-250); for Accelerator "bvhold" BVHAccelOld's
     // (accelerators/bvhOld.cpp:185-227) with the Accelerator line's split method: the same handle, the same walks
@@ -120,6 +130,7 @@ int main(int argc, char **argv) {
             desc.flags = gpus > 1 ? HPRT_RENDER_EXPORT_FOREIGN : 0;
             // (the library-owned film of this scene)
             rcs[(size_t)g] = ambientOcclusion ? hprt_render_ao(scenes[(size_t)g], &desc, &ao, nullptr, nullptr, &stats[(size_t)g])
+                             : directLighting ? hprt_render_direct(scenes[(size_t)g], &desc, &direct, lightSamples.data(), nLights, nullptr, nullptr, &stats[(size_t)g])
                                               : hprt_render(scenes[(size_t)g], &desc, nullptr, nullptr, &stats[(size_t)g]);
             if (rcs[(size_t)g] != HPRT_OK) errs[(size_t)g] = hprt_last_error();
         });
@@ -127,7 +138,7 @@ int main(int argc, char **argv) {
     HprtRenderStats total; std::memset(&total, 0, sizeof(total));
     double seconds = 0;
     for (int g = 0; g < gpus; ++g) {
-        if (rcs[(size_t)g] != HPRT_OK) { std::fprintf(stderr, "%s on GPU %d failed (%d): %s\n", ambientOcclusion ? "hprt_render_ao" : "hprt_render", g, rcs[(size_t)g], errs[(size_t)g].c_str()); return 1; }
+        if (rcs[(size_t)g] != HPRT_OK) { std::fprintf(stderr, "%s on GPU %d failed (%d): %s\n", renderName, g, rcs[(size_t)g], errs[(size_t)g].c_str()); return 1; }
         const HprtRenderStats &st = stats[(size_t)g];
         total.camera_rays += st.camera_rays; total.rays += st.rays; total.shadow_rays += st.shadow_rays;
         if (st.render_seconds > seconds) seconds = st.render_seconds;

@@ -189,6 +189,18 @@ typedef struct HprtAoParams { int32_t n_samples; int32_t cos_sample; } HprtAoPar
  * be NULL) receives the parameters of an Integrator "ambientocclusion" line, the defaults for every other name.  Like the
  * accelerators' parameters these live on the host side of the model and are not baked: baked models report "path". */
 int hprt_model_integrator(const HprtModel *m, char *name, size_t cap, HprtAoParams *ao);
+/* CreateDirectLightingIntegrator's parameters (integrators/directlighting.cpp:102-135): "strategy" "all" (0) or "one"
+ * (1), "maxdepth" 5 */
+typedef struct HprtDirectParams { int32_t strategy; /* 0 all, 1 one */ int32_t max_depth; } HprtDirectParams;
+/* hprt_render_direct refuses a max_depth above this (HPRT_E_UNSUPPORTED) */
+#define HPRT_DIRECT_MAX_DEPTH 8
+/* The parameters of the scene's Integrator "directlighting" line (the defaults, all and 5, for every other name), and
+ * Light::nSamples of every scene light in scene.lights order — one entry per triangle of a mesh emitter — as
+ * UniformSampleAllLights reads it: max(1, "samples" or else "nsamples") of AreaLightSource "diffuse" and LightSource
+ * "infinite" (lights/diffuse.cpp:140-141, lights/infinite.cpp:181-182, core/light.cpp:45), 1 for "point" and "distant".
+ * params and n_light_samples may be NULL; *n_lights (may be NULL) receives the number of lights, of which the first
+ * min(cap, *n_lights) are written.  Host side of the model, not baked: baked models report the defaults and 1. */
+int hprt_model_direct(const HprtModel *m, HprtDirectParams *params, int32_t *n_light_samples, size_t cap, size_t *n_lights);
 /* Built with the parameters of the scene's Accelerator line (defaults intersectcost 80, traversalcost 1, emptybonus 0,
  * maxprims 1, maxdepth -1 = round(2 + 1.6 Log2Int(N))).  Models with object instances: HPRT_E_UNSUPPORTED. */
 int hprt_kdtree_build(const HprtModel *m, HprtKdTree **out);
@@ -961,6 +973,47 @@ int hprt_render_ao(HprtScene *s, const HprtRenderDesc *desc, const HprtAoParams 
  * The AO twin of hprt_sample_radiance. */
 int hprt_sample_ao(HprtScene *s, const HprtRenderOptions *opt, const HprtAoParams *ao, size_t n, const int32_t *px,
                    const int32_t *py, const int64_t *sample, float *L3_out);
+
+/* ------------------------------------------------------------------------ */
+/* Integrator "directlighting" (core/api.cpp:1913).  SamplerIntegrator::Render */
+/* with DirectLightingIntegrator::Li (integrators/directlighting.cpp:62-100) as */
+/* the estimator: at every hit isect.Le(wo), then UniformSampleAllLights over   */
+/* the sampler's 2D arrays (two of n_light_samples[j] entries per light j and  */
+/* depth, Preprocess :45-60; dimensions 5 .. 5 + 4 max_depth n_lights - 1, the */
+/* plain dimensions follow; a node that finds the arrays used up takes one      */
+/* sample per light from plain dimensions, core/integrator.cpp:67-72) or       */
+/* UniformSampleOneLight (uniform pick), each through EstimateDirect; then,    */
+/* while depth + 1 < max_depth, SpecularReflect and SpecularTransmit           */
+/* (core/integrator.cpp:362-450) through mirror, uber and smooth-glass lobes   */
+/* (GlassMaterial without allowMultipleLobes: two specular lobes).  An escaped  */
+/* ray picks up every infinite light's Le.  All rays go through the scene's    */
+/* walk - the BVH or an attached tree - never through the shadow grid.         */
+/* n_light_samples: n_lights counts as hprt_model_direct reports them; NULL:   */
+/* all 1.  Same film, tiles, spp_chunk, d_film_xyzw, stream and stats contract */
+/* as hprt_render (rays: the node rays and EstimateDirect's BSDF-sampled rays; */
+/* shadow_rays: its visibility rays); opt.max_depth / rr_threshold /           */
+/* light_strategy are not read.                                                */
+/* Refused before the device is touched - HPRT_E_INVALID: max_depth < 1, a     */
+/* count < 1, n_lights other than the scene's; HPRT_E_UNSUPPORTED: max_depth   */
+/* above HPRT_DIRECT_MAX_DEPTH; a tree whose worst case could pass the         */
+/* reference's 1,000 Halton dimensions (5 + 4 max_depth n_lights for the       */
+/* arrays, then per node of a full binary tree of max_depth levels its plain   */
+/* light dimensions and, above the last level, 4 for the two specular calls);  */
+/* a count * spp above INT32_MAX (core/sampler.cpp:157); more than 65,536      */
+/* light samples per node; any flag but HPRT_RENDER_COUNT_WORK; and, with      */
+/* max_depth > 1, a scene that holds an image texture and a material with a    */
+/* specular lobe the recursion can follow (mirror; smooth glass; uber with     */
+/* non-black Kr or Kt or an opacity that is textured or not 1): the reference  */
+/* carries ray differentials through specular bounces, hprt does not.          */
+/* ------------------------------------------------------------------------ */
+int hprt_render_direct(HprtScene *s, const HprtRenderDesc *desc, const HprtDirectParams *params,
+                       const int32_t *n_light_samples, size_t n_lights, float *d_film_xyzw, void *stream,
+                       HprtRenderStats *stats);
+/* L (directlighting.cpp:62-100) of individual camera samples after the guards of core/integrator.cpp:300-321; L3_out =
+ * 3*n floats.  The twin of hprt_sample_ao. */
+int hprt_sample_direct(HprtScene *s, const HprtRenderOptions *opt, const HprtDirectParams *params,
+                       const int32_t *n_light_samples, size_t n_lights, size_t n, const int32_t *px, const int32_t *py,
+                       const int64_t *sample, float *L3_out);
 
 /* Halton sampler tables (host): ComputeRadicalInversePermutations
  * (core/lowdiscrepancy.cpp:2490-2504) with the default-seeded PCG32. */

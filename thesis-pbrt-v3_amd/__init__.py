@@ -86,6 +86,14 @@ class AoParams(C.Structure):
     _fields_ = [("n_samples", C.c_int32), ("cos_sample", C.c_int32)]
 
 
+class DirectParams(C.Structure):
+    """HprtDirectParams: CreateDirectLightingIntegrator's "strategy" (0 all, 1 one) and "maxdepth" (integrators/directlighting.cpp:102-135)."""
+    _fields_ = [("strategy", C.c_int32), ("max_depth", C.c_int32)]
+
+
+DIRECT_MAX_DEPTH = 8      # HPRT_DIRECT_MAX_DEPTH
+
+
 class RenderStats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in (
         "camera_rays", "rays", "shadow_rays", "nodes_fetched", "nodes_fetched_p", "nodes_entered", "nodes_entered_p",
@@ -399,6 +407,9 @@ def _load():
         "hprt_model_integrator": (C.c_int, [vp, vp, sz, P(AoParams)]),
         "hprt_render_ao": (C.c_int, [vp, P(RenderDesc), P(AoParams), vp, vp, P(RenderStats)]),
         "hprt_sample_ao": (C.c_int, [vp, P(RenderOptions), P(AoParams), sz, vp, vp, vp, vp]),
+        "hprt_model_direct": (C.c_int, [vp, P(DirectParams), vp, sz, P(sz)]),
+        "hprt_render_direct": (C.c_int, [vp, P(RenderDesc), P(DirectParams), vp, sz, vp, vp, P(RenderStats)]),
+        "hprt_sample_direct": (C.c_int, [vp, P(RenderOptions), P(DirectParams), vp, sz, sz, vp, vp, vp, vp]),
     }
     # the two-level handles' diagnostics hooks (not part of include/hprt.h, so not among EXPORTS)
     debug = {}
@@ -407,6 +418,8 @@ def _load():
         debug["hprt_debug_%s_set_tree" % prefix] = (C.c_int, [vp, C.c_int, sz, vp, sz, vp, vp])
     debug["hprt_debug_ao_ray_capacity"] = (sz, [sz])
     debug["hprt_debug_ao_kernel_seconds"] = (C.c_int, [vp, vp])
+    debug["hprt_debug_dl_ray_capacity"] = (sz, [sz])
+    debug["hprt_debug_dl_kernel_seconds"] = (C.c_int, [vp, vp])
     debug["hprt_debug_halton_index"] = (C.c_int, [P(RenderOptions), sz, vp, vp, vp, vp, vp, vp])
     # the light-centred shadow grid (csrc/shadow_grid.h)
     debug["hprt_debug_shadow_grid"] = (C.c_int, [C.c_int])
@@ -453,6 +466,8 @@ def _probe():
         p.hprt_debug_device_halton.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
         p.hprt_debug_device_bsdf.restype = C.c_int
         p.hprt_debug_device_bsdf.argtypes = [C.c_void_p, C.c_int, C.c_size_t] + [C.c_void_p] * 6
+        p.hprt_debug_device_bsdf_specular.restype = C.c_int
+        p.hprt_debug_device_bsdf_specular.argtypes = [C.c_void_p, C.c_int, C.c_size_t] + [C.c_void_p] * 5
         _probe_lib = p
     return _probe_lib
 
@@ -470,6 +485,12 @@ def debug_ao_ray_capacity(rays):
     """Test hook (not part of include/hprt.h): the hemisphere rays one any-hit launch of later render_ao calls takes at most (never fewer
     than one hit's n_samples); 0: back to the default.  Returns the setting before."""
     return int(lib.hprt_debug_ao_ray_capacity(int(rays)))
+
+
+def debug_dl_ray_capacity(items):
+    """Test hook (not part of include/hprt.h): the light samples one pair of trace launches of later render_direct calls takes at most (never
+    fewer than one hit's); 0: back to the default.  Returns the setting before."""
+    return int(lib.hprt_debug_dl_ray_capacity(int(items)))
 
 
 def shadow_grid_build(p9, light, res):
@@ -619,6 +640,17 @@ class Model:
         ao = AoParams()
         _check(lib.hprt_model_integrator(self._h, buf, 256, C.byref(ao)))
         return buf.value.decode(), int(ao.n_samples), bool(ao.cos_sample)
+
+    def direct(self):
+        """(strategy, max_depth, n_light_samples): the parameters of the scene's Integrator "directlighting" line ("all" or "one", maxdepth;
+        the defaults "all", 5 for any other name) and Light::nSamples of every scene light in scene.lights order, one per triangle of a
+        mesh emitter; baked models report the defaults and 1 for every light."""
+        dp = DirectParams()
+        n = C.c_size_t(0)
+        _check(lib.hprt_model_direct(self._h, C.byref(dp), None, 0, C.byref(n)))
+        counts = np.zeros(max(1, n.value), np.int32)
+        _check(lib.hprt_model_direct(self._h, None, _ptr(counts), n.value, None))
+        return ("one" if dp.strategy == 1 else "all"), int(dp.max_depth), [int(v) for v in counts[:n.value]]
 
     def warnings(self):
         w = lib.hprt_model_warnings(self._h).decode()
@@ -1297,6 +1329,56 @@ class Scene:
             _check(lib.hprt_film_read(self._h, _ptr(film), film.shape[0] * film.shape[1]))
         return film, st.as_dict()
 
+    @staticmethod
+    def _direct_args(strategy, max_depth, n_light_samples):
+        dp = DirectParams({"all": 0, "one": 1}.get(strategy, strategy), int(max_depth))
+        counts = None if n_light_samples is None else np.ascontiguousarray(n_light_samples, np.int32)
+        return dp, counts
+
+    def render_direct(self, strategy="all", max_depth=5, n_light_samples=None, n_lights=None, opt=None, tile_begin=0, tile_end=0, tile_stride=1, spp_chunk=0,
+                      count_work=False, film_ptr=None, stream=None, flags=None):
+        """hprt_render_direct: Render() with DirectLightingIntegrator::Li (integrators/directlighting.cpp) as the estimator; returns what
+        render() returns.  n_light_samples: one count per scene light (Model.direct()), None: all 1 — n_lights then says how many lights
+        the caller believes the scene has (default: the model's)."""
+        opt = opt or self._model.options
+        desc = RenderDesc()
+        desc.opt = opt
+        desc.tile_begin, desc.tile_end, desc.tile_stride = tile_begin, tile_end, tile_stride
+        desc.spp_chunk = spp_chunk
+        desc.flags = (RENDER_COUNT_WORK if count_work else 0) if flags is None else flags
+        dp, counts = self._direct_args(strategy, max_depth, n_light_samples)
+        if n_lights is None:
+            n_lights = counts.shape[0] if counts is not None else self._model.counts()["lights"]
+        st = RenderStats()
+        _check(lib.hprt_render_direct(self._h, C.byref(desc), C.byref(dp), None if counts is None else _ptr(counts), int(n_lights), film_ptr, stream, C.byref(st)))
+        self._film_shape = tuple(int(v) for v in (opt.film_bounds()[3] - opt.film_bounds()[1], opt.film_bounds()[2] - opt.film_bounds()[0]))
+        film = None
+        if film_ptr is None:
+            x0, y0, x1, y1 = opt.film_bounds()
+            film = np.zeros((y1 - y0, x1 - x0, 4), np.float32)
+            _check(lib.hprt_film_read(self._h, _ptr(film), film.shape[0] * film.shape[1]))
+        return film, st.as_dict()
+
+    def dl_kernel_seconds(self):
+        """Measurement hook (not part of include/hprt.h): HIP-event seconds of (k_dl_shade, k_dl_rays, k_dl_resolve, k_dl_advance) in the last
+        render_direct, and the tree-walk steps its batches took."""
+        out = np.zeros(5, np.float64)
+        _check(lib.hprt_debug_dl_kernel_seconds(self._h, _ptr(out)))
+        return tuple(float(v) for v in out[:4]), int(out[4])
+
+    def sample_direct(self, px, py, sample, strategy="all", max_depth=5, n_light_samples=None, n_lights=None, opt=None):
+        """hprt_sample_direct: L of individual camera samples under the direct-lighting estimator, [n, 3] float32."""
+        opt = opt or self._model.options
+        px = np.ascontiguousarray(px, np.int32); py = np.ascontiguousarray(py, np.int32)
+        sample = np.ascontiguousarray(sample, np.int64)
+        L = np.zeros((px.shape[0], 3), np.float32)
+        dp, counts = self._direct_args(strategy, max_depth, n_light_samples)
+        if n_lights is None:
+            n_lights = counts.shape[0] if counts is not None else self._model.counts()["lights"]
+        _check(lib.hprt_sample_direct(self._h, C.byref(opt), C.byref(dp), None if counts is None else _ptr(counts), int(n_lights), px.shape[0], _ptr(px), _ptr(py),
+                                      _ptr(sample), _ptr(L)))
+        return L
+
     def ao_kernel_seconds(self):
         """Measurement hook (not part of include/hprt.h): HIP-event seconds of (k_ao_frame, k_ao_rays, k_ao_resolve) in the last render_ao."""
         out = np.zeros(3, np.float64)
@@ -1348,6 +1430,20 @@ class Scene:
         assert shape.ndim == 1 and frame9.shape[0] == n and wo.shape[0] == n and wi.shape[0] == n and u.shape[0] == n
         out = np.zeros((n, 8), np.float32)
         _check(_probe().hprt_debug_device_bsdf(self._h, int(mode), n, _ptr(shape), _ptr(frame9), _ptr(wo), _ptr(wi), _ptr(u), _ptr(out)))
+        return out
+
+    def debug_device_bsdf_specular(self, mask, shape, frame9, wo, u):
+        """Test hook (not part of include/hprt.h): bsdf_sample_specular — BSDF::Sample_f under mask 17 (BSDF_REFLECTION | BSDF_SPECULAR) or 18
+        (BSDF_TRANSMISSION | BSDF_SPECULAR) — of shapes[shape[i]]'s material at the frame frame9[i].  Returns float32 [n, 8]: f, wi, pdf (wi
+        and pdf preset to (9, 9, 9) and -7), and 1 where the material can offer either mask a lobe."""
+        shape = np.ascontiguousarray(shape, np.int32)
+        frame9 = np.ascontiguousarray(frame9, np.float32).reshape(-1, 9)
+        wo = np.ascontiguousarray(wo, np.float32).reshape(-1, 3)
+        u = np.ascontiguousarray(u, np.float32).reshape(-1, 2)
+        n = shape.shape[0]
+        assert shape.ndim == 1 and frame9.shape[0] == n and wo.shape[0] == n and u.shape[0] == n
+        out = np.zeros((n, 8), np.float32)
+        _check(_probe().hprt_debug_device_bsdf_specular(self._h, int(mask), n, _ptr(shape), _ptr(frame9), _ptr(wo), _ptr(u), _ptr(out)))
         return out
 
     def film_records(self):

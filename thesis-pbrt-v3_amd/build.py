@@ -33,14 +33,19 @@ CUIDS = {"device/kernels.hip": "a6cd736c50efffab", "device/kd_walk.hip": "5c0d2e
 # lib/libhprt_probe.so: device probes for the tests (device/halton_probe.hip: halton_dim over host arrays; device/bsdf_probe.hip: the
 # BSDF functions over host arrays of queries), linked against libhprt.so.
 # A library of its own, so that libhprt.so's .hip_fatbin — what profiles/rNN_counters.json is stamped with — gains no code object.
-PROBE_SRCS = ["device/halton_probe.hip", "device/bsdf_probe.hip"]
+PROBE_SRCS = ["device/halton_probe.hip", "device/bsdf_probe.hip", "device/bsdf_specular_probe.hip"]
 CUIDS["device/halton_probe.hip"] = "f04b8d61c2a79e35"
 CUIDS["device/bsdf_probe.hip"] = "3d8a6f0b92e4c517"
+CUIDS["device/bsdf_specular_probe.hip"] = "81c6f2d05a9e347b"
 # lib/libhprt_ao.so: the ambient-occlusion kernels (device/ao.hip: k_ao_frame, k_ao_rays, k_ao_resolve and their launchers), which
 # libhprt.so links against and finds beside itself ($ORIGIN).  A library of its own for the probes' reason: libhprt.so's .hip_fatbin
 # gains no code object, so the stamp of the counter summaries still names the kernels they were measured on.
 AO_SRCS = ["device/ao.hip"]
 CUIDS["device/ao.hip"] = "c94e1a7b35f0d826"
+# lib/libhprt_dl.so: the direct-lighting kernels (device/direct.hip: k_dl_shade, k_dl_rays, k_dl_resolve, k_dl_advance and their
+# launchers), beside libhprt.so exactly as libhprt_ao.so is, and for its reason.
+DL_SRCS = ["device/direct.hip"]
+CUIDS["device/direct.hip"] = "5e0b93a7c42d16f8"
 COMMON = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-Wall", "-Wno-unused-function"]
 
 
@@ -77,7 +82,7 @@ def build(verbose=False, force=False):
         obj = os.path.join(OBJ, s.replace("/", "_") + ".o")
         cmd = [hipcc if s in HIPCC_HOST_SRCS else "g++"] + COMMON + ["-c", src, "-o", obj]
         jobs.append((src, obj, cmd))
-    for s in HIP_SRCS + AO_SRCS + PROBE_SRCS:
+    for s in HIP_SRCS + AO_SRCS + DL_SRCS + PROBE_SRCS:
         src = os.path.join(CSRC, s)
         obj = os.path.join(OBJ, s.replace("/", "_") + ".o")
         cmd = [hipcc, "--offload-arch=gfx950"] + COMMON + ["-Wno-unused-result", "-cuid=" + CUIDS[s], "-c", src, "-o", obj]
@@ -97,17 +102,21 @@ def build(verbose=False, force=False):
             if verbose and out:
                 print(out)
     lib = os.path.join(LIB, "libhprt.so")
+    n_side = len(PROBE_SRCS) + len(DL_SRCS) + len(AO_SRCS)
     probe_objs = [j[1] for j in jobs[len(jobs) - len(PROBE_SRCS):]]
-    ao_objs = [j[1] for j in jobs[len(jobs) - len(PROBE_SRCS) - len(AO_SRCS):len(jobs) - len(PROBE_SRCS)]]
-    objs = [j[1] for j in jobs[:len(jobs) - len(PROBE_SRCS) - len(AO_SRCS)]]
+    dl_objs = [j[1] for j in jobs[len(jobs) - len(PROBE_SRCS) - len(DL_SRCS):len(jobs) - len(PROBE_SRCS)]]
+    ao_objs = [j[1] for j in jobs[len(jobs) - n_side:len(jobs) - n_side + len(AO_SRCS)]]
+    objs = [j[1] for j in jobs[:len(jobs) - n_side]]
     ao = os.path.join(LIB, "libhprt_ao.so")
-    if force or _newer(ao_objs, ao):
-        cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-o", ao] + ao_objs
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        if r.returncode != 0:
-            raise RuntimeError("link failed: %s\n%s" % (" ".join(cmd), r.stderr))
-    if force or _newer(objs + [ao], lib):
-        cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-o", lib] + objs + ["-L" + LIB, "-lhprt_ao", "-Wl,-rpath,$ORIGIN", "-lz", "-L/opt/rocm/lib", "-lrccl"]   # zlib: PNG textures (texture_io.cpp); RCCL: film gather (capi_gather.hip)
+    dl = os.path.join(LIB, "libhprt_dl.so")
+    for side, side_objs in ((ao, ao_objs), (dl, dl_objs)):
+        if force or _newer(side_objs, side):
+            cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-o", side] + side_objs
+            r = subprocess.run(cmd, capture_output=True, text=True)
+            if r.returncode != 0:
+                raise RuntimeError("link failed: %s\n%s" % (" ".join(cmd), r.stderr))
+    if force or _newer(objs + [ao, dl], lib):
+        cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-o", lib] + objs + ["-L" + LIB, "-lhprt_ao", "-lhprt_dl", "-Wl,-rpath,$ORIGIN", "-lz", "-L/opt/rocm/lib", "-lrccl"]   # zlib: PNG textures (texture_io.cpp); RCCL: film gather (capi_gather.hip)
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError("link failed: %s\n%s" % (" ".join(cmd), r.stderr))

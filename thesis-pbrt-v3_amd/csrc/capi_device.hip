@@ -17,6 +17,7 @@
 #include "../../include/hprt.h"
 #include "device/kernels.h"
 #include "device/ao.h"
+#include "device/direct.h"
 #include "halton_tables.h"
 #include "host_transform.h"
 #include "hprt_internal.h"
@@ -172,6 +173,12 @@ int hprt_scene_create(const HprtSceneDesc *d, int device, HprtScene **out) try {
     sc->device = dev; sc->nPrims = L.nPrims;
     sc->topOrder = std::move(L.topOrder); sc->objectOrder = std::move(L.objectOrder); sc->objectPrimBase = std::move(L.objectPrimBase);
     sc->instanceObject = std::move(L.instanceObject); sc->instanced = L.instanced; sc->hasSubstrateBin = L.hasSubstrateBin;
+    for (const DevMaterial &m : L.materials) {      // (hprt_render_direct's refusals)
+        if (m.KdTex >= 0 || m.KsTex >= 0 || (m.type == 6 && m.opTex >= 0)) sc->hasImageTexture = true;
+        const bool uberLobe = m.type == 6 && (m.Kr[0] > 0 || m.Kr[1] > 0 || m.Kr[2] > 0 || m.Kt[0] > 0 || m.Kt[1] > 0 || m.Kt[2] > 0 || m.opTex >= 0 ||
+                                              m.opacity[0] != 1.f || m.opacity[1] != 1.f || m.opacity[2] != 1.f);
+        if (m.type == 2 || (m.type == 5 && !m.roughGlass) || uberLobe) sc->hasSpecularLobe = true;
+    }
     // Halton tables + 64-bit division magics
     const std::vector<uint16_t> &perms = HaltonPermutations();
     std::vector<int32_t> primes(PrimeTable().begin(), PrimeTable().end()), primeSums(PrimeSumTable().begin(), PrimeSumTable().end());
@@ -1158,7 +1165,7 @@ int EnsureWorkspace(HprtScene *s, size_t nSlots, Workspace *ps, QueueSet *qa, Qu
 // it never wrote (a fresh allocation on a busy card holds other processes' data, not zeros).
 int PoisonWorkspace(HprtScene *s) {
     if (s->poisonByte < 0) return HPRT_OK;
-    hprt::DevBuf *bufs[] = {&s->planes, &s->queues, &s->Lall, &s->deepStack, &s->rayStats, &s->irregular, &s->aoSlots, &s->aoRays};
+    hprt::DevBuf *bufs[] = {&s->planes, &s->queues, &s->Lall, &s->deepStack, &s->rayStats, &s->irregular, &s->aoSlots, &s->aoRays, &s->dlSlots, &s->dlRays};
     for (hprt::DevBuf *b : bufs) if (b->p && b->bytes) HIP_TRY(hipMemset(b->p, s->poisonByte, b->bytes));
     HIP_TRY(hipDeviceSynchronize());
     return HPRT_OK;
@@ -1281,17 +1288,201 @@ int RunAoBatch(HprtScene *s, hipStream_t st, const RenderParams &rp, const HprtA
     return HPRT_OK;
 }
 
+// ---- Integrator "directlighting" (device/direct.h): DirectLightingIntegrator::Li, integrators/directlighting.cpp:62-100 ----
+// Light samples per pair of trace launches: the buffer of fixed size a step's light work goes through, hit range by hit range (121 bytes
+// per item: its record, a shadow ray and its byte, a BSDF-sampled ray and its hit).  hprt_debug_dl_ray_capacity (tests) lowers it so
+// that small renders take several ranges too.
+constexpr size_t kDlRayCapacity = (size_t)1 << 24;
+size_t g_dlRayCapacity = kDlRayCapacity;
+// Camera samples per batch: 128 bytes per depth of stack and some 130 more each, 4 M of them unless the caller's spp_chunk says otherwise
+constexpr size_t kDlSlotCapacity = (size_t)1 << 22;
+// One hprt_render_direct / hprt_sample_direct call: the parameters as given, and the per-light counts (all 1 where the caller passed none)
+struct DlJob { HprtDirectParams params; std::vector<int32_t> nLightSamples; };
+struct DlWorkspace {
+    DlParams dp; DlState state; DlRecords recs; DlItems items; DlRays rays;
+    RayStream node[2]; uint32_t *live[2]; HitStream hit;
+    uint32_t *counts;      // hit, shadow-ray, BSDF-ray and next-node counters, 64 words apart
+    size_t itemCap;
+};
+// The worst case of the sampler's dimension cursor: the arrays, then every node of a full binary tree of maxDepth levels draws its plain
+// light sample values (only the nodes behind the first maxDepth can find the arrays used up) and, above the last level, two Get2D
+int64_t DirectWorstDimensions(int strategy, int64_t maxDepth, int64_t nLights) {
+    const int64_t nodes = ((int64_t)1 << maxDepth) - 1, inner = ((int64_t)1 << (maxDepth - 1)) - 1;
+    const int64_t lightDims = nLights == 0 ? 0 : strategy == 1 ? 5 * nodes : 4 * nLights * std::max<int64_t>(0, nodes - maxDepth);
+    return 5 + (strategy == 0 ? 4 * maxDepth * nLights : 0) + lightDims + 4 * inner;
+}
+// Everything hprt_render_direct and hprt_sample_direct refuse, judged without touching the device
+int CheckDirect(const HprtScene *s, const HprtDirectParams *p, const int32_t *nLightSamples, size_t nLights, int32_t spp, int32_t flags, const char *fn, DlJob *job) {
+    const std::string f(fn);
+    if (!p) return SetError(HPRT_E_INVALID, f + ": null argument");
+    if (p->strategy != 0 && p->strategy != 1) return SetError(HPRT_E_INVALID, f + ": strategy must be 0 (all) or 1 (one)");
+    if (p->max_depth < 1) return SetError(HPRT_E_INVALID, f + ": max_depth must be at least 1");
+    if (spp <= 0) return SetError(HPRT_E_INVALID, "spp must be positive");
+    if (nLightSamples) for (size_t j = 0; j < nLights; ++j) if (nLightSamples[j] < 1) return SetError(HPRT_E_INVALID, f + ": every light's sample count must be at least 1");
+    if (p->max_depth > HPRT_DIRECT_MAX_DEPTH) return SetError(HPRT_E_UNSUPPORTED, f + ": max_depth above " + std::to_string(HPRT_DIRECT_MAX_DEPTH));
+    if (flags & ~HPRT_RENDER_COUNT_WORK)
+        return SetError(HPRT_E_UNSUPPORTED, f + ": only HPRT_RENDER_COUNT_WORK is supported (per-pixel statistics, EXPORT_FOREIGN, TRACE_ALL and COUNT_TRACED stay with hprt_render)");
+    if (DirectWorstDimensions(p->strategy, p->max_depth, (int64_t)nLights) > 1000)
+        return SetError(HPRT_E_UNSUPPORTED, f + ": with max_depth " + std::to_string(p->max_depth) + " and " + std::to_string(nLights) + " lights a camera sample's tree could pass "
+                                            "the 1,000 sampler dimensions of the reference's Halton tables");
+    uint64_t items = 0;
+    for (size_t j = 0; j < nLights; ++j) {
+        const int64_t n = nLightSamples ? nLightSamples[j] : 1;
+        if (p->strategy == 0 && n * (int64_t)spp > 0x7fffffffll)
+            return SetError(HPRT_E_UNSUPPORTED, f + ": a light's sample count * spp exceeds INT32_MAX (the reference's int nSamples = size * samplesPerPixel overflows "
+                                                "there, core/sampler.cpp:157)");
+        items += (uint64_t)n;
+    }
+    if (p->strategy == 0 && items > DL_MAX_ITEMS) return SetError(HPRT_E_UNSUPPORTED, f + ": more than 65,536 light samples per node");
+    if (!s) return SetError(HPRT_E_INVALID, f + ": null argument");
+    if (nLights != (size_t)s->dev.nLights)
+        return SetError(HPRT_E_INVALID, f + ": n_lights is " + std::to_string(nLights) + ", the scene has " + std::to_string(s->dev.nLights) + " lights");
+    if (p->max_depth > 1 && s->hasImageTexture && s->hasSpecularLobe)
+        return SetError(HPRT_E_UNSUPPORTED, f + ": the scene holds an image texture and a material with a specular lobe; the reference carries ray differentials through "
+                                            "SpecularReflect / SpecularTransmit (core/integrator.cpp:376-393, 416-445), which decide the texture's filter — not built");
+    job->params = *p;
+    job->nLightSamples.assign(nLights, 1);
+    if (nLightSamples) job->nLightSamples.assign(nLightSamples, nLightSamples + nLights);
+    return HPRT_OK;
+}
+int EnsureDlWorkspace(HprtScene *s, const DlJob &job, size_t nSlots, DlWorkspace *w) {
+    const bool instances = s->dev.nInstances != 0u;
+    const uint32_t nLights = (uint32_t)job.nLightSamples.size(), maxDepth = (uint32_t)job.params.max_depth;
+    // ---- the per-light tables ----
+    std::vector<uint32_t> first(nLights + 1, 0u); std::vector<uint2> itemLight;
+    for (uint32_t j = 0; j < nLights; ++j) {
+        first[j] = (uint32_t)itemLight.size();
+        for (int32_t k = 0; k < job.nLightSamples[j]; ++k) itemLight.push_back(make_uint2(j, (uint32_t)k));
+    }
+    const uint32_t itemsPerHit = job.params.strategy == 1 ? 1u : (uint32_t)itemLight.size();
+    if (itemLight.empty()) itemLight.push_back(make_uint2(0u, 0u));
+    const size_t tA = ((nLights + 1) * 4 + 255) & ~(size_t)255, tB = tA;
+    HIP_TRY(s->dlTables.alloc(tA + tB + itemLight.size() * sizeof(uint2) + 256));
+    char *tb = s->dlTables.as<char>();
+    if (nLights) {
+        HIP_TRY(hipMemcpy(tb, job.nLightSamples.data(), nLights * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(tb + tA, first.data(), nLights * 4, hipMemcpyHostToDevice));
+    }
+    HIP_TRY(hipMemcpy(tb + tA + tB, itemLight.data(), itemLight.size() * sizeof(uint2), hipMemcpyHostToDevice));
+    w->dp.strategy = job.params.strategy; w->dp.maxDepth = job.params.max_depth; w->dp.nLights = nLights; w->dp.itemsPerHit = itemsPerHit;
+    w->dp.arrayEndDim = 5 + (job.params.strategy == 0 ? 4 * (int32_t)maxDepth * (int32_t)nLights : 0);
+    w->dp.nLightSamples = (const int32_t *)tb; w->dp.lightFirstItem = (const uint32_t *)(tb + tA); w->dp.itemLight = (const uint2 *)(tb + tA + tB);
+    // ---- per camera sample ----
+    const size_t perSlot = 4 + 16 * (size_t)DL_STACK_PLANES * maxDepth + 2 * 32 + 2 * 4 + 16 + (instances ? 8 : 0) + 16 * DL_RECORD_PLANES;
+    HIP_TRY(s->dlSlots.alloc(nSlots * perSlot + 256 * 16));
+    PlaneAllocator a{s->dlSlots.as<char>(), 0, 0};
+    w->state.state = a.take<uint32_t>(nSlots);
+    w->state.stack = a.take<float4>(nSlots * DL_STACK_PLANES * maxDepth); w->state.stride = (uint32_t)nSlots;
+    for (int k = 0; k < 2; ++k) { w->node[k].a = a.take<float4>(nSlots); w->node[k].b = a.take<float4>(nSlots); w->live[k] = a.take<uint32_t>(nSlots); }
+    w->hit.a = a.take<float4>(nSlots); w->hit.b = instances ? a.take<float2>(nSlots) : nullptr;
+    w->recs.q = a.take<uint4>(nSlots); w->recs.tex = a.take<float4>(nSlots * (DL_RECORD_PLANES - 1)); w->recs.stride = (uint32_t)nSlots;
+    w->counts = a.take<uint32_t>(256);
+    // ---- per light sample: never less than one hit's items, never more than a step can produce ----
+    const uint64_t most = std::max<uint64_t>((uint64_t)nSlots * std::max(1u, itemsPerHit), 1);
+    w->itemCap = (size_t)std::min<uint64_t>(std::max<uint64_t>(g_dlRayCapacity, std::max(1u, itemsPerHit)), most);
+    const size_t perItem = 2 * 16 + 4 + 32 + 1 + 32 + 16 + (instances ? 8 : 0);
+    HIP_TRY(s->dlRays.alloc(w->itemCap * perItem + 256 * 16));
+    PlaneAllocator b{s->dlRays.as<char>(), 0, 0};
+    w->items.a = b.take<float4>(w->itemCap); w->items.b = b.take<float4>(w->itemCap); w->items.light = b.take<uint32_t>(w->itemCap);
+    w->rays.shadow.a = b.take<float4>(w->itemCap); w->rays.shadow.b = b.take<float4>(w->itemCap); w->rays.occ = b.take<uint8_t>(w->itemCap);
+    w->rays.bsdf.a = b.take<float4>(w->itemCap); w->rays.bsdf.b = b.take<float4>(w->itemCap);
+    w->rays.bsdfHit.a = b.take<float4>(w->itemCap); w->rays.bsdfHit.b = instances ? b.take<float2>(w->itemCap) : nullptr;
+    w->rays.shadowCount = w->counts + 64; w->rays.bsdfCount = w->counts + 128;
+    return HPRT_OK;
+}
+// One batch of nSlots camera samples: k_generate, then step by step (one tree node per live sample) closest-hit trace -> k_dl_shade ->
+// [hit count to the host] -> per range of hits whose light work fits the buffer: k_dl_rays -> [ray counts to the host] -> any-hit trace,
+// closest-hit trace -> k_dl_resolve; then k_dl_advance -> [live count to the host].  Both traces are the scene's walk whatever the
+// scene: these shadow rays could take the shadow grid (they end at a light), and do not — a follow-up.
+int RunDlBatch(HprtScene *s, hipStream_t st, const RenderParams &rp, const DlWorkspace &w, const DlSlots &sl, uint32_t s0, uint32_t nSlots, bool count,
+               const DlRadiance &out, EventTimer &ev, BatchTimers *bt, HprtRenderStats *stats, const IrregularSink *irregular) {
+    PathStream camPath; camPath.ray = w.node[0]; camPath.beta = nullptr; camPath.L = nullptr;      // (k_generate stores the ray alone)
+    DevCounters *ctr = s->counters.as<DevCounters>();
+    uint32_t *wc = s->workCounter.as<uint32_t>();
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> evExt, evOcc, evDl[4];      // (evDl: the four kernels of device/direct.hip, for tools/bench_direct.py)
+    auto timed = [&](std::vector<std::pair<hipEvent_t, hipEvent_t>> &into, auto launch) -> int {
+        hipEvent_t e0 = ev.get(), e1 = ev.get();
+        HIP_TRY(hipEventRecord(e0, st));
+        launch();
+        HIP_TRY(hipEventRecord(e1, st));
+        into.push_back({e0, e1});
+        return HPRT_OK;
+    };
+    auto flush = [&]() {
+        for (auto &p : evExt) { float ms = 0; if (hipEventElapsedTime(&ms, p.first, p.second) == hipSuccess) bt->extendMs += ms; }
+        for (auto &p : evOcc) { float ms = 0; if (hipEventElapsedTime(&ms, p.first, p.second) == hipSuccess) bt->occludedMs += ms; }
+        for (int k = 0; k < 4; ++k) {
+            for (auto &p : evDl[k]) { float ms = 0; if (hipEventElapsedTime(&ms, p.first, p.second) == hipSuccess) s->dlKernelMs[k] += ms; }
+            evDl[k].clear();
+        }
+        evExt.clear(); evOcc.clear();
+        ev.reset();
+    };
+    LaunchGenerate(st, s->dev, rp, camPath, s0, nSlots, irregular);
+    uint32_t nLive = nSlots;
+    const uint32_t *live = nullptr;      // step 0: node i is slot i
+    const uint64_t maxSteps = ((uint64_t)1 << w.dp.maxDepth) - 1;
+    for (uint64_t step = 0; nLive > 0; ++step) {
+        if (step >= maxSteps) return SetError(HPRT_E_DEVICE, "internal error: a direct-lighting tree has more nodes than a full one");
+        const int cur = (int)(step & 1);
+        if (int rc = timed(evExt, [&] { Trace(s, st, false, count, nullptr, nullptr, nLive, nLive, w.node[cur], w.hit, nullptr, ctr, wc); })) return rc;
+        bt->extendRays += nLive; ++bt->extendLaunches;
+        stats->rays += nLive;
+        HIP_TRY(hipMemsetAsync(w.counts, 0, 256 * sizeof(uint32_t), st));
+        if (int rc = timed(evDl[0], [&] { LaunchDlShade(st, s->dev, rp, w.dp, sl, w.node[cur], w.hit, live, nLive, step == 0, w.state, w.recs, w.counts); })) return rc;
+        HIP_TRY(hipMemcpyAsync(s->hostCounts + 9, w.counts, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        const uint32_t nHits = s->hostCounts[9];
+        if (nHits > nLive) return SetError(HPRT_E_DEVICE, "internal error: more direct-lighting hits than nodes");
+        const uint32_t hitsPerRange = (uint32_t)(w.itemCap / std::max(1u, w.dp.itemsPerHit));
+        for (uint32_t h0 = 0; h0 < nHits && w.dp.itemsPerHit; h0 += hitsPerRange) {
+            const uint32_t nh = std::min(hitsPerRange, nHits - h0);
+            HIP_TRY(hipMemsetAsync(w.counts + 64, 0, 128 * sizeof(uint32_t), st));
+            if (int rc = timed(evDl[1], [&] { LaunchDlRays(st, s->dev, rp, w.dp, sl, w.state, w.recs, h0, nh, w.items, w.rays); })) return rc;
+            HIP_TRY(hipMemcpyAsync(s->hostCounts + 10, w.rays.shadowCount, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(s->hostCounts + 11, w.rays.bsdfCount, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            const uint32_t nShadow = s->hostCounts[10], nBsdf = s->hostCounts[11];
+            if (nShadow > w.itemCap || nBsdf > w.itemCap) return SetError(HPRT_E_DEVICE, "internal error: more direct-lighting rays than light samples");
+            HitStream none; none.a = nullptr; none.b = nullptr;
+            if (nShadow) {
+                if (int rc = timed(evOcc, [&] { Trace(s, st, true, count, nullptr, nullptr, nShadow, nShadow, w.rays.shadow, none, w.rays.occ, ctr, wc); })) return rc;
+                bt->occludedRays += nShadow; ++bt->occludedLaunches;
+                stats->shadow_rays += nShadow;
+            }
+            if (nBsdf) {
+                if (int rc = timed(evExt, [&] { Trace(s, st, false, count, nullptr, nullptr, nBsdf, nBsdf, w.rays.bsdf, w.rays.bsdfHit, nullptr, ctr, wc); })) return rc;
+                bt->extendRays += nBsdf; ++bt->extendLaunches;
+                stats->rays += nBsdf;
+            }
+            if (int rc = timed(evDl[2], [&] { LaunchDlResolve(st, s->dev, w.dp, w.state, w.recs, h0, nh, w.items, w.rays); })) return rc;
+        }
+        if (int rc = timed(evDl[3], [&] { LaunchDlAdvance(st, s->dev, rp, w.dp, sl, live, nLive, w.state, w.node[cur ^ 1], w.live[cur ^ 1], w.counts + 192, out); })) return rc;
+        HIP_TRY(hipMemcpyAsync(s->hostCounts + 9, w.counts + 192, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(st));
+        const uint32_t nNext = s->hostCounts[9];
+        if (nNext > nLive) return SetError(HPRT_E_DEVICE, "internal error: more direct-lighting children than nodes");
+        flush();
+        nLive = nNext; live = w.live[cur ^ 1];
+        ++s->dlSteps;
+    }
+    return HPRT_OK;
+}
+
 }  // namespace
 
-// SamplerIntegrator::Render (core/integrator.cpp:230-360) with the estimator of hprt_render (ao == null: PathIntegrator::Li) or of
-// hprt_render_ao (AOIntegrator::Li): the same tiles, batches of camera samples, per-sample radiance store and film kernels
-static int RenderImpl(HprtScene *s, const HprtRenderDesc *desc, const HprtAoParams *ao, float *d_film_xyzw, void *stream, HprtRenderStats *stats) {
+// SamplerIntegrator::Render (core/integrator.cpp:230-360) with the estimator of hprt_render (ao == dl == null: PathIntegrator::Li), of
+// hprt_render_ao (AOIntegrator::Li) or of hprt_render_direct (DirectLightingIntegrator::Li): the same tiles, batches of camera samples,
+// per-sample radiance store and film kernels
+static int RenderImpl(HprtScene *s, const HprtRenderDesc *desc, const HprtAoParams *ao, float *d_film_xyzw, void *stream, HprtRenderStats *stats,
+                      const DlJob *dl = nullptr) {
     HIP_TRY(hipSetDevice(s->device));
     hipStream_t st = (hipStream_t)stream;
     SceneCall call(s, st);      // (blocking: every path out of a started render has synchronised `st`, or failed)
     const HprtRenderOptions &o = desc->opt;
     int rc0;
-    if (!ao) {
+    if (!ao && !dl) {
         if (o.spp <= 0 || o.max_depth < 0) return SetError(HPRT_E_INVALID, "spp must be positive and max_depth non-negative");
         if ((rc0 = CheckDepth(o.max_depth)) != HPRT_OK) return rc0;
     }
@@ -1326,8 +1517,17 @@ static int RenderImpl(HprtScene *s, const HprtRenderDesc *desc, const HprtAoPara
     // two batches of 512 instead of 522 + 502 or, at the old 128 M cap, four of 256: -1 % per frame).  killeroo-simple
     // at 256 spp is one batch of 125 M paths: 6.5 % faster than two batches of 64 M.  (HPRT_BATCH_MPATHS changes the cap.)
     uint32_t chunk = 0;
-    Workspace ps; QueueSet qa, qb; BinSet bins; AoWorkspace aw;
-    if (ao) {
+    Workspace ps; QueueSet qa, qb; BinSet bins; AoWorkspace aw; DlWorkspace dw;
+    if (dl) {
+        for (double &ms : s->dlKernelMs) ms = 0;
+        s->dlSteps = 0;
+        // Direct lighting: spp_chunk keeps its meaning; left to the library, a batch holds up to kDlSlotCapacity camera samples, whose
+        // light work goes through the ray buffer range by range (RunDlBatch)
+        chunk = desc->spp_chunk > 0 ? (uint32_t)desc->spp_chunk : std::max<uint32_t>(1u, (uint32_t)(kDlSlotCapacity / nPix));
+        chunk = std::min(chunk, spp);
+        if ((uint64_t)chunk * nPix > 0x3fffffffull) chunk = std::max<uint32_t>(1u, (uint32_t)(0x3fffffffull / nPix));
+        if ((rc = EnsureDlWorkspace(s, *dl, (size_t)chunk * nPix, &dw)) != HPRT_OK) return rc;
+    } else if (ao) {
         for (double &ms : s->aoKernelMs) ms = 0;
         // Ambient occlusion: spp_chunk keeps its meaning, an upper bound per pixel; left to the library, a batch holds up to
         // kAoSlotCapacity camera samples.  Its hemisphere rays go through the ray buffer range by range (RunAoBatch).
@@ -1337,7 +1537,7 @@ static int RenderImpl(HprtScene *s, const HprtRenderDesc *desc, const HprtAoPara
         if ((rc = EnsureAoWorkspace(s, (size_t)chunk * nPix, (uint32_t)ao->n_samples, (uint64_t)chunk * nPix * (uint64_t)ao->n_samples, &aw)) != HPRT_OK) return rc;
     } else if ((rc = ChooseBatch(s, desc->spp_chunk, nPix, spp, &chunk)) != HPRT_OK) return rc;
     const size_t maxSlots = (size_t)chunk * nPix;
-    if (!ao && (rc = EnsureWorkspace(s, maxSlots, &ps, &qa, &qb, &bins)) != HPRT_OK) return rc;
+    if (!ao && !dl && (rc = EnsureWorkspace(s, maxSlots, &ps, &qa, &qb, &bins)) != HPRT_OK) return rc;
     HIP_TRY(s->Lall.alloc(lallBytes));
     if ((rc = PoisonWorkspace(s)) != HPRT_OK) return rc;
     float *LallR = s->Lall.as<float>(), *LallG = LallR + (size_t)spp * nPix, *LallB = LallG + (size_t)spp * nPix;
@@ -1388,6 +1588,11 @@ static int RenderImpl(HprtScene *s, const HprtRenderDesc *desc, const HprtAoPara
     EventTimer ev; BatchTimers bt;
     for (uint32_t s0 = 0; s0 < spp; s0 += chunk) {
         const uint32_t c = std::min(chunk, spp - s0), nSlots = c * nPix;
+        if (dl) {      // (k_dl_advance stores each sample where k_store_radiance would)
+            rc = RunDlBatch(s, st, rp, dw, DlSlots{rp.pixelOffset, nullptr, nPix, s0}, s0, nSlots, count, DlRadiance{LallR, LallG, LallB, (size_t)s0 * nPix}, ev, &bt, stats, &sink);
+            if (rc != HPRT_OK) return rc;
+            continue;
+        }
         if (ao) {      // (k_ao_frame and k_ao_resolve store each sample where k_store_radiance would)
             rc = RunAoBatch(s, st, rp, *ao, aw, nullptr, s0, nSlots, count, AoRadiance{LallR, LallG, LallB, (size_t)s0 * nPix}, ev, &bt, stats, &sink);
             if (rc != HPRT_OK) return rc;
@@ -1530,6 +1735,32 @@ __attribute__((visibility("default"))) int hprt_debug_ao_kernel_seconds(HprtScen
 __attribute__((visibility("default"))) size_t hprt_debug_ao_ray_capacity(size_t rays) {
     const size_t was = g_aoRayCapacity;
     g_aoRayCapacity = rays ? rays : kAoRayCapacity;
+    return was;
+}
+
+// The parameters and the scene's host-side facts are judged before the device is looked at: a refusal does not depend on it
+int hprt_render_direct(HprtScene *s, const HprtRenderDesc *desc, const HprtDirectParams *params, const int32_t *n_light_samples, size_t n_lights,
+                       float *d_film_xyzw, void *stream, HprtRenderStats *stats) try {
+    if (!desc) return SetError(HPRT_E_INVALID, "hprt_render_direct: null argument");
+    DlJob job;
+    if (int rc = CheckDirect(s, params, n_light_samples, n_lights, desc->opt.spp, desc->flags, "hprt_render_direct", &job)) return rc;
+    int dev;
+    if (int rc = CheckDevice(s->device, &dev)) return rc;
+    return RenderImpl(s, desc, nullptr, d_film_xyzw, stream, stats, &job);
+} catch (...) { return hprt::HandleException(); }
+// Diagnostics hook (not part of include/hprt.h; tools/bench_direct.py): HIP-event seconds of k_dl_shade, k_dl_rays, k_dl_resolve and
+// k_dl_advance in the scene's last hprt_render_direct, and the tree-walk steps its batches took
+__attribute__((visibility("default"))) int hprt_debug_dl_kernel_seconds(HprtScene *s, double out5[5]) {
+    if (!s || !out5) return HPRT_E_INVALID;
+    for (int k = 0; k < 4; ++k) out5[k] = s->dlKernelMs[k] * 1e-3;
+    out5[4] = (double)s->dlSteps;
+    return HPRT_OK;
+}
+// Diagnostics hook (not part of include/hprt.h; tests/test_gpu_direct.py): the light samples one pair of trace launches of later
+// hprt_render_direct calls takes at most (never fewer than one hit's); 0: back to the default.  Returns the setting before.
+__attribute__((visibility("default"))) size_t hprt_debug_dl_ray_capacity(size_t items) {
+    const size_t was = g_dlRayCapacity;
+    g_dlRayCapacity = items ? items : kDlRayCapacity;
     return was;
 }
 
@@ -1685,6 +1916,61 @@ int hprt_sample_ao(HprtScene *s, const HprtRenderOptions *opt, const HprtAoParam
     EventTimer ev; BatchTimers bt; HprtRenderStats stats; memset(&stats, 0, sizeof(stats));
     float *LR = s->Lall.as<float>();
     rc = RunAoBatch(s, nullptr, rp, *ao, aw, rp.pixelOffset + n, 0, (uint32_t)n, false, AoRadiance{LR, LR + n, LR + 2 * n, 0}, ev, &bt, &stats, nullptr);
+    if (rc != HPRT_OK) return rc;
+    HIP_TRY(hipGetLastError()); HIP_TRY(hipDeviceSynchronize());
+    std::vector<float> planes(3 * n);
+    HIP_TRY(hipMemcpy(planes.data(), LR, 12 * n, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; ++i) { L3_out[3 * i] = planes[i]; L3_out[3 * i + 1] = planes[n + i]; L3_out[3 * i + 2] = planes[2 * n + i]; }
+    return HPRT_OK;
+} catch (...) { return hprt::HandleException(); }
+
+// hprt_sample_radiance for the direct-lighting estimator: slot i is sample[i] of pixel (px[i], py[i]); its camera sample and plain
+// dimensions sit at GetIndexForSample(sample), element k of an array of size n at GetIndexForSample(sample * n + k)
+int hprt_sample_direct(HprtScene *s, const HprtRenderOptions *opt, const HprtDirectParams *params, const int32_t *n_light_samples, size_t n_lights, size_t n,
+                       const int32_t *px, const int32_t *py, const int64_t *sample, float *L3_out) try {
+    if (!opt || (n && (!px || !py || !sample || !L3_out))) return SetError(HPRT_E_INVALID, "hprt_sample_direct: null argument");
+    DlJob job;
+    if (int rc = CheckDirect(s, params, n_light_samples, n_lights, std::max(1, opt->spp), 0, "hprt_sample_direct", &job)) return rc;
+    if (n > (1u << 22)) return SetError(HPRT_E_INVALID, "hprt_sample_direct: too many samples in one call");
+    int dev;
+    if (int rc = CheckDevice(s->device, &dev)) return rc;
+    if (n == 0) return HPRT_OK;
+    SceneCall call(s, nullptr);
+    FrameSetup f;
+    int rc = SetupFrame(*opt, &f);
+    if (rc != HPRT_OK) return rc;
+    // camera-sample indices (k_generate's), then the pixels' own offsets; the sample numbers travel with the pixel words
+    std::vector<uint32_t> xy(2 * n); std::vector<uint64_t> off(2 * n);
+    for (size_t i = 0; i < n; ++i) {
+        if (px[i] < f.fg.sx0 || px[i] >= f.fg.sx1 || py[i] < f.fg.sy0 || py[i] >= f.fg.sy1 || sample[i] < 0 || sample[i] > 0x7fffffffll)
+            return SetError(HPRT_E_INVALID, "hprt_sample_direct: pixel outside the sample bounds, or sample number out of range");
+        for (int32_t c : job.nLightSamples)
+            if (job.params.strategy == 0 && (int64_t)c * (sample[i] + 1) > 0x7fffffffll)
+                return SetError(HPRT_E_UNSUPPORTED, "hprt_sample_direct: a light's sample count * (sample + 1) exceeds INT32_MAX");
+        xy[i] = (uint32_t)px[i] | ((uint32_t)py[i] << 16);
+        xy[n + i] = (uint32_t)sample[i];
+        const uint64_t pixelOffset = (uint64_t)HaltonPixelOffset(f.hal, px[i], py[i]);
+        off[i] = pixelOffset + (uint64_t)sample[i] * (uint64_t)f.hal.sampleStride;
+        off[n + i] = pixelOffset;
+    }
+    DlWorkspace dw;
+    if ((rc = EnsureDlWorkspace(s, job, n, &dw)) != HPRT_OK) return rc;
+    HIP_TRY(upload(s->pixelXY, xy)); HIP_TRY(upload(s->pixelOffset, off));
+    HIP_TRY(s->Lall.alloc(12 * n));
+    if ((rc = PoisonWorkspace(s)) != HPRT_OK) return rc;
+    RenderParams rp;
+    MakeCamera(*opt, &rp.cam);
+    rp.hal.baseScale1 = f.hal.baseScales[1]; rp.hal.baseExp0 = f.hal.baseExponents[0]; rp.hal.sampleStride = f.hal.sampleStride;
+    rp.hal.samplePixelCenter = opt->sample_pixel_center;
+    rp.pixelXY = s->pixelXY.as<uint32_t>(); rp.pixelOffset = s->pixelOffset.as<uint64_t>(); rp.nPix = (uint32_t)n;
+    rp.maxDepth = 0; rp.rrThreshold = 0.f; rp.cullMis = 1; rp.speculate = rp.foldRepair = 0;      // (not read)
+    rp.invSqrtSpp = 1 / std::sqrt((float)std::max(1, opt->spp));      // ScaleDifferentials' factor, core/integrator.cpp:288-289
+    EventTimer ev; BatchTimers bt; HprtRenderStats stats; memset(&stats, 0, sizeof(stats));
+    float *LR = s->Lall.as<float>();
+    // (the camera index of slot i is rp.pixelOffset[i] + 0 * stride: s0 = 0 and nPix = n make k_generate's sample number 0; the estimator
+    // reads the pixel's own offset and the sample number)
+    rc = RunDlBatch(s, nullptr, rp, dw, DlSlots{rp.pixelOffset + n, rp.pixelXY + n, (uint32_t)n, 0u}, 0, (uint32_t)n, false, DlRadiance{LR, LR + n, LR + 2 * n, 0}, ev, &bt,
+                    &stats, nullptr);
     if (rc != HPRT_OK) return rc;
     HIP_TRY(hipGetLastError()); HIP_TRY(hipDeviceSynchronize());
     std::vector<float> planes(3 * n);

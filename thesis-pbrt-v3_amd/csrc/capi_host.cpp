@@ -824,6 +824,8 @@ int hprt_model_parse(const char *pbrt_path, const char *const *subst, int n_subs
     else if (acc != "bvh") m->sc.warnings.push_back("Accelerator \"" + acc + "\" is outside the hot-path scope; \"bvh\" used");
     if (m->sc.opt.integrator == "ambientocclusion")
         m->sc.warnings.push_back("Integrator \"ambientocclusion\": the host renders it with hprt_render_ao; hprt_render renders the path integrator");
+    else if (m->sc.opt.integrator == "directlighting")
+        m->sc.warnings.push_back("Integrator \"directlighting\": the host renders it with hprt_render_direct; hprt_render renders the path integrator");
     else if (m->sc.opt.integrator != "path") m->sc.warnings.push_back("Integrator \"" + m->sc.opt.integrator + "\" is outside the hot-path scope; \"path\" used");
     if (m->sc.opt.sampler != "halton") m->sc.warnings.push_back("Sampler \"" + m->sc.opt.sampler + "\" is outside the hot-path scope; \"halton\" used");
     *out = m;
@@ -1064,6 +1066,15 @@ int hprt_model_integrator(const HprtModel *m, char *name, size_t cap, HprtAoPara
     if (a.size() + 1 > cap) return SetError(HPRT_E_INVALID, "hprt_model_integrator: buffer too small");
     memcpy(name, a.c_str(), a.size() + 1);
     if (ao) { ao->n_samples = m->sc.opt.aoSamples; ao->cos_sample = m->sc.opt.aoCosSample; }
+    return HPRT_OK;
+} catch (...) { return hprt::HandleException(); }
+int hprt_model_direct(const HprtModel *m, HprtDirectParams *params, int32_t *n_light_samples, size_t cap, size_t *n_lights) try {
+    if (!m || (cap && !n_light_samples)) return SetError(HPRT_E_INVALID, "hprt_model_direct: bad argument");
+    if (params) { params->strategy = m->sc.opt.dlStrategy; params->max_depth = m->sc.opt.dlMaxDepth; }
+    const size_t n = m->sc.lights.size();
+    if (n_lights) *n_lights = n;
+    // (a loaded model keeps no counts: they are not baked)
+    for (size_t i = 0; i < n && i < cap; ++i) n_light_samples[i] = i < m->sc.lightSamples.size() ? m->sc.lightSamples[i] : 1;
     return HPRT_OK;
 } catch (...) { return hprt::HandleException(); }
 int hprt_kdtree_build(const HprtModel *m, HprtKdTree **out) try {

@@ -95,6 +95,15 @@ struct HprtScene {
     hprt::DevBuf queues, queueCounts;
     double aoKernelMs[3] = {0, 0, 0};                       // HIP-event time of k_ao_frame, k_ao_rays and k_ao_resolve in the last hprt_render_ao (hprt_debug_ao_kernel_seconds)
     hprt::DevBuf aoSlots, aoRays;                           // hprt_render_ao: the camera samples' streams and hit records; the hemisphere rays, terms and bytes
+    // hprt_render_direct (device/direct.h): per camera sample the walk's state, stack, node rays, hits and hit records; per light sample
+    // the item records and the two ray streams; the per-light tables.  dlKernelMs: HIP-event time of k_dl_shade, k_dl_rays, k_dl_resolve
+    // and k_dl_advance in the last hprt_render_direct (hprt_debug_dl_kernel_seconds); dlSteps: tree-walk steps of its batches
+    hprt::DevBuf dlSlots, dlRays, dlTables;
+    double dlKernelMs[4] = {0, 0, 0, 0};
+    uint64_t dlSteps = 0;
+    // what CheckDirectScene refuses without touching the device: a material with an image texture; a material with a specular lobe that
+    // SpecularReflect / SpecularTransmit can follow (mirror, smooth glass, uber with Kr, Kt or an opacity that is textured or not 1)
+    bool hasImageTexture = false, hasSpecularLobe = false;
     hprt::DevBuf pixelXY, pixelOffset, Lall, film, irregular, irregularCount;
     hprt::DevBuf exOwnBegin, exOwnSrc, exOwnSample, exOwnPre, exFDest, exFDestBegin, exFGroupBegin, exFSrc, exFSample;
     // HPRT_RENDER_EXPORT_FOREIGN: the cross-tile film contributions of the last render, one record per (destination

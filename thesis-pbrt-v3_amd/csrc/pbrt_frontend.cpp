@@ -381,9 +381,14 @@ struct Frontend {
         gs.areaLightParams.rgb3("scale", scv);
         for (int i = 0; i < 3; ++i) l.I[i] = L[i] * scv[i];
         l.twoSided = gs.areaLightParams.oneBool("twosided", false) ? 1 : 0;
+        // "samples", else "nsamples", else 1 (lights/diffuse.cpp:140-141); Light::Light keeps max(1, nSamples) (core/light.cpp:45).  Read by
+        // Integrator "directlighting" alone; beside the light, not in it: LightDesc is baked
+        areaLightSamples = std::max(1, gs.areaLightParams.oneInt("samples", gs.areaLightParams.oneInt("nsamples", 1)));
         reportUnused(gs.areaLightParams, "AreaLightSource", {"nsamples", "samples"});
         return l;
     }
+    int areaLightSamples = 1;      // of the light makeAreaLight returned last
+    void pushLight(const LightDesc &l, int nSamples) { sc->lights.push_back(l); sc->lightSamples.push_back(nSamples); }
 
     // ---- shapes (core/api.cpp:1561-1651) ------------------------------------
     bool addMeshShape(const ParamList &params, std::vector<int> &idx, std::vector<float> &P, std::vector<float> &N,
@@ -426,7 +431,7 @@ struct Frontend {
             LightDesc l = makeAreaLight();
             l.shape = (int)sc->shapes.size();
             sh.areaLight = (int)sc->lights.size();
-            for (size_t t = 0; t < idx.size() / 3; ++t) sc->lights.push_back(l);
+            for (size_t t = 0; t < idx.size() / 3; ++t) pushLight(l, areaLightSamples);
         }
         pushShape(std::move(sh));
         return true;
@@ -494,7 +499,7 @@ struct Frontend {
                 LightDesc l = makeAreaLight();
                 l.shape = (int)sc->shapes.size();
                 sh.areaLight = (int)sc->lights.size();
-                sc->lights.push_back(l);
+                pushLight(l, areaLightSamples);
             }
             pushShape(std::move(sh));
             return true;
@@ -552,7 +557,9 @@ struct Frontend {
             warn("light \"" + name + "\" is outside the hot-path scope; skipped");
             return true;
         }
-        sc->lights.push_back(l);
+        // Light::nSamples: "samples", else "nsamples", else 1 for an infinite light (lights/infinite.cpp:181-182; core/light.cpp:45); point
+        // and distant lights are built without a count (lights/point.h:53, lights/distant.cpp:41-47: the constructor's default, 1)
+        pushLight(l, l.type == kInfiniteLight ? std::max(1, params.oneInt("samples", params.oneInt("nsamples", 1))) : 1);
         return true;
     }
     std::string resolve(const std::string &fn) const {
@@ -614,6 +621,16 @@ struct Frontend {
             // unused below as the reference reports them (and keep their defaults in the baked options)
             o.aoSamples = integratorParams.oneInt("nsamples", 64);
             o.aoCosSample = integratorParams.oneBool("cossample", true) ? 1 : 0;
+        } else if (sc->opt.integrator == "directlighting") {
+            // CreateDirectLightingIntegrator, integrators/directlighting.cpp:102-135: "maxdepth" is its own (not the baked options'), and
+            // the path integrator's other parameters are reported unused as the reference reports them
+            o.dlMaxDepth = integratorParams.oneInt("maxdepth", 5);
+            const std::string st = integratorParams.oneString("strategy", "all");
+            if (st == "one") o.dlStrategy = 1;
+            else {
+                if (st != "all") warn("Strategy \"" + st + "\" for direct lighting unknown. Using \"all\".");
+                o.dlStrategy = 0;
+            }
         } else {
             // CreatePathIntegrator, integrators/path.cpp:206-229
             o.maxDepth = integratorParams.oneInt("maxdepth", 5);

@@ -103,6 +103,9 @@ struct RenderOptions {
     int32_t bvhOldSplitMethod = 0, bvhOldMaxNodePrims = 4;
     // Integrator "ambientocclusion": CreateAOIntegrator's "nsamples" and "cossample" (integrators/ao.cpp:105-126); host side only (not baked)
     int32_t aoSamples = 64, aoCosSample = 1;
+    // Integrator "directlighting": CreateDirectLightingIntegrator's "strategy" (0 all, 1 one) and "maxdepth" (integrators/directlighting.cpp:
+    // 102-135); host side only (not baked)
+    int32_t dlStrategy = 0, dlMaxDepth = 5;
     std::string filename = "pbrt.exr", accelerator = "bvh", integrator = "path", sampler = "halton";
 };
 struct SceneModel {
@@ -110,6 +113,9 @@ struct SceneModel {
     std::vector<MaterialDesc> materials;
     std::vector<ShapeDesc> shapes;
     std::vector<LightDesc> lights;
+    // Light::nSamples of lights[i] as Integrator "directlighting" reads it (hprt_model_direct); host side only, not baked: empty for a
+    // loaded model, which reports 1 for every light
+    std::vector<int32_t> lightSamples;
     std::vector<TextureDesc> textures;
     uint32_t nObjects = 0;                // object ids are 0..nObjects-1 (ShapeDesc::object)
     std::vector<InstanceDesc> instances;
