@@ -428,6 +428,13 @@ def _load():
     debug["hprt_debug_shadow_grid_build"] = (C.c_int, [sz, vp, vp, C.c_uint32, vp, vp, sz, vp, sz])
     debug["hprt_debug_shadow_grid_image"] = (C.c_int, [sz, vp, vp, C.c_uint32, vp, vp, sz, vp, sz])
     debug["hprt_debug_shadow_grid_image_read"] = (C.c_int, [vp, vp, vp, sz, vp, sz])
+    # the light-aligned grid of a distant light (csrc/distant_grid.h)
+    debug["hprt_debug_shadow_grid_layout"] = (C.c_int, [vp, vp, vp])
+    debug["hprt_debug_distant_grid_info"] = (C.c_int, [vp, vp])
+    debug["hprt_debug_distant_grid_occluded"] = (C.c_int, [vp, sz, vp, vp, vp])
+    debug["hprt_debug_distant_grid_build"] = (C.c_int, [sz, vp, vp, vp, C.c_uint32, vp, vp, sz, vp, sz])
+    debug["hprt_debug_distant_grid_image"] = (C.c_int, [sz, vp, vp, vp, C.c_uint32, vp, vp, sz, vp, sz])
+    debug["hprt_debug_distant_grid_image_read"] = (C.c_int, [vp, vp, vp, sz, vp, sz])
     for name, (res, args) in list(sig.items()) + list(debug.items()):
         fn = getattr(lib, name)   # raises AttributeError if an export is missing
         fn.restype = res
@@ -512,16 +519,18 @@ def shadow_grid_build(p9, light, res):
 
 
 SG_BLOCK_WORDS, SG_RECORD_WORDS, SG_BLOCK_SLOTS = 32, 12, 2
+DG_DEFAULT_RES = 1024      # csrc/distant_grid.h
 
 
-def shadow_grid_image_decode(blocks, records, R, near):
+def shadow_grid_image_decode(blocks, records, R, near, faces=6):
     """The lists of a shadow grid's device image (csrc/shadow_grid.h, ShadowGridImage) as the kernel follows them: per cell the block's
-    slots, then the run of records its head points to; before them the near list, records 0 .. near - 1.  dict: blocks [6 R^2, 32] and
-    records [n, 12] uint32, count (per cell), overflow (per cell: the record of its third entry), cell_start (int64 [6 R^2 + 1], the
+    slots, then the run of records its head points to; before them the near list, records 0 .. near - 1.  faces: 6 for a point light's
+    grid, 1 for a distant light's.  dict: blocks [faces R^2, 32] and
+    records [n, 12] uint32, count (per cell), overflow (per cell: the record of its third entry), cell_start (int64 [faces R^2 + 1], the
     near list first, as ShadowGrid::cellStart), and per entry in list order prim_word, key_word (uint32), verts ([n, 9] uint32, the
     vertex floats' bits), next_key (uint32: the fourth lane of a record's third word; 0 for block slots), key2 (per cell: the block's
     copy of entry 2's key word)."""
-    blocks = np.asarray(blocks, np.uint32).reshape(6 * R * R, SG_BLOCK_WORDS)
+    blocks = np.asarray(blocks, np.uint32).reshape(faces * R * R, SG_BLOCK_WORDS)
     records = np.asarray(records, np.uint32).reshape(-1, SG_RECORD_WORDS)
     count = blocks[:, 0].astype(np.int64); overflow = blocks[:, 1].astype(np.int64)
     cell_start = near + np.concatenate([[0], np.cumsum(count)])
@@ -558,6 +567,58 @@ def shadow_grid_image(p9, light, res):
     info = np.zeros(6, np.float64)
     _check(lib.hprt_debug_shadow_grid_build(p9.shape[0], _ptr(p9), _ptr(light), int(res), _ptr(info), None, 0, None, 0))
     out = shadow_grid_image_decode(blocks, records, int(res), int(info[2]))
+    out["words"] = tuple(int(w) for w in words)
+    return out
+
+
+def _distant_grid_args(p9, direction, bound):
+    p9 = np.ascontiguousarray(p9, np.float32).reshape(-1, 9)
+    direction = np.ascontiguousarray(direction, np.float32)
+    bound = None if bound is None else np.ascontiguousarray(bound, np.float32).reshape(6)
+    return p9, direction, bound
+
+
+def distant_grid_build(p9, direction, res, bound=None):
+    """Test hook (not part of include/hprt.h; host only): the light-aligned shadow grid (csrc/distant_grid.h) of the triangles p9 ([n, 9]
+    float32, each a leaf of its own) under a distant light in `direction` (towards the light, normalised in float32) at res x res
+    cells, over `bound` ((min, max); None: the bound of the triangles).  dict as shadow_grid_build's, with cell_start uint32
+    [R^2 + 1] (cell = iv * R + iu), margin and height_margin (world units), and the frame the device computes a ray's cell and key
+    limit from: U, V, W (float32 [3]), u0, v0, scale_u, scale_v, h_top (float32)."""
+    p9, direction, bound = _distant_grid_args(p9, direction, bound)
+    info = np.zeros(22, np.float64)
+    _check(lib.hprt_debug_distant_grid_build(p9.shape[0], _ptr(p9), _ptr(direction), _ptr(bound), int(res), _ptr(info), None, 0, None, 0))
+    R, n_entries = int(info[0]), int(info[1])
+    cell_start = np.zeros(R * R + 1, np.uint32); entries = np.zeros((max(1, n_entries), 2), np.uint32)
+    _check(lib.hprt_debug_distant_grid_build(p9.shape[0], _ptr(p9), _ptr(direction), _ptr(bound), int(res), _ptr(info), _ptr(cell_start), cell_start.size, _ptr(entries), entries.shape[0]))
+    entries = entries[:n_entries]
+    f32 = np.float32
+    return {"R": R, "eps": float(info[3]), "near": int(info[2]), "longest": int(info[4]), "seconds": float(info[5]), "margin": float(info[6]), "height_margin": float(info[7]),
+            "U": info[8:11].astype(f32), "V": info[11:14].astype(f32), "W": info[14:17].astype(f32), "u0": f32(info[17]), "v0": f32(info[18]),
+            "scale_u": f32(info[19]), "scale_v": f32(info[20]), "h_top": f32(info[21]), "cell_start": cell_start,
+            "prim": (entries[:, 0] & SG_PRIM_MASK).astype(np.int64), "single": (entries[:, 0] & SG_SINGLE) != 0, "key": (entries[:, 1] & np.uint32(0xffff0000)).view(np.float32),
+            "rect": np.stack([(entries[:, 1] >> s) & 15 for s in (0, 4, 8, 12)], axis=1).astype(np.int64)}
+
+
+def shadow_grid_layout(model, bvh):
+    """Test hook (not part of include/hprt.h; host only): which shadow grid the layout of Scene(model, bvh) holds, as HPRT_SHADOW_GRID,
+    HPRT_SHADOW_GRID_RES and HPRT_SHADOW_GRID_MAX_MB stand.  dict: point (eligible, R), distant (eligible, R, entries, near, bytes, longest)."""
+    out = np.zeros(8, np.float64)
+    _check(lib.hprt_debug_shadow_grid_layout(model._h, bvh._h, _ptr(out)))
+    return {"point": {"eligible": bool(out[0]), "R": int(out[1])},
+            "distant": {"eligible": bool(out[2]), "R": int(out[3]), "entries": int(out[4]), "near": int(out[5]), "bytes": int(out[6]), "longest": int(out[7])}}
+
+
+def distant_grid_image(p9, direction, res, bound=None):
+    """Test hook (not part of include/hprt.h; host only): the device image of the grid distant_grid_build gives for the same arguments,
+    decoded by shadow_grid_image_decode (faces = 1); "words" as shadow_grid_image's."""
+    p9, direction, bound = _distant_grid_args(p9, direction, bound)
+    words = np.zeros(3, np.uint64)
+    _check(lib.hprt_debug_distant_grid_image(p9.shape[0], _ptr(p9), _ptr(direction), _ptr(bound), int(res), _ptr(words), None, 0, None, 0))
+    blocks = np.zeros(int(words[0]), np.uint32); records = np.zeros(int(words[1]), np.uint32)
+    _check(lib.hprt_debug_distant_grid_image(p9.shape[0], _ptr(p9), _ptr(direction), _ptr(bound), int(res), _ptr(words), _ptr(blocks), blocks.size, _ptr(records), records.size))
+    info = np.zeros(22, np.float64)
+    _check(lib.hprt_debug_distant_grid_build(p9.shape[0], _ptr(p9), _ptr(direction), _ptr(bound), int(res), _ptr(info), None, 0, None, 0))
+    out = shadow_grid_image_decode(blocks, records, int(res), int(info[2]), faces=1)
     out["words"] = tuple(int(w) for w in words)
     return out
 
@@ -1279,6 +1340,33 @@ class Scene:
         d = float32(light - o); returns the kernel's milliseconds."""
         ms = C.c_float()
         _check(lib.hprt_debug_shadow_grid_occluded(self._h, n, rays7_ptr, occ_ptr, C.byref(ms)))
+        return float(ms.value)
+
+    def distant_grid_info(self):
+        """Test hook (not part of include/hprt.h): the scene's light-aligned shadow grid of its one distant light — eligible (False: its
+        shadow rays take the walk), R, entries, near, bytes, build_seconds, pack_seconds, longest and mean list, w (towards the light), U, V
+        (the frame the cells lie in), render_launches (launches of k_distant_grid by this scene's renders so far), eps."""
+        out = np.zeros(20, np.float64)
+        _check(lib.hprt_debug_distant_grid_info(self._h, _ptr(out)))
+        return {"eligible": bool(out[0]), "R": int(out[1]), "entries": int(out[2]), "near": int(out[3]), "bytes": int(out[4]), "build_seconds": float(out[5]),
+                "pack_seconds": float(out[6]), "longest": int(out[7]), "mean": float(out[8]), "w": out[9:12].astype(np.float32), "U": out[12:15].astype(np.float32),
+                "V": out[15:18].astype(np.float32), "render_launches": int(out[18]), "eps": float(out[19])}
+
+    def distant_grid_image(self):
+        """Test hook (not part of include/hprt.h): the image k_distant_grid reads of this scene, copied back from the device and decoded as
+        shadow_grid_image_decode does (faces = 1)."""
+        words = np.zeros(2, np.uint64)
+        _check(lib.hprt_debug_distant_grid_image_read(self._h, _ptr(words), None, 0, None, 0))
+        blocks = np.zeros(int(words[0]), np.uint32); records = np.zeros(max(1, int(words[1])), np.uint32)
+        _check(lib.hprt_debug_distant_grid_image_read(self._h, _ptr(words), _ptr(blocks), blocks.size, _ptr(records), records.size))
+        info = self.distant_grid_info()
+        return shadow_grid_image_decode(blocks, records[:int(words[1])], info["R"], info["near"], faces=1)
+
+    def distant_grid_occluded_device(self, n, rays7_ptr, occ_ptr):
+        """Test hook (not part of include/hprt.h): k_distant_grid on n device rays ([7][n] planes) formed as a render forms the shadow
+        rays of the scene's distant light; returns the kernel's milliseconds."""
+        ms = C.c_float()
+        _check(lib.hprt_debug_distant_grid_occluded(self._h, n, rays7_ptr, occ_ptr, C.byref(ms)))
         return float(ms.value)
 
     def intersect_device(self, n, rays7_ptr, t_ptr, prim_ptr, bary_ptr=None, stream=None):

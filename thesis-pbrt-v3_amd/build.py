@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "lib")
-HOST_SRCS = ["pbrt_frontend.cpp", "loop_subdiv.cpp", "scene_io.cpp", "texture_io.cpp", "bvh_builder.cpp", "kdtree_builder.cpp", "rbsp_builder.cpp", "bsppaper_builder.cpp", "bspnode_builder.cpp", "bvhold_builder.cpp", "wide_bvh.cpp", "shadow_grid.cpp", "halton_tables.cpp", "capi_host.cpp"]
+HOST_SRCS = ["pbrt_frontend.cpp", "loop_subdiv.cpp", "scene_io.cpp", "texture_io.cpp", "bvh_builder.cpp", "kdtree_builder.cpp", "rbsp_builder.cpp", "bsppaper_builder.cpp", "bspnode_builder.cpp", "bvhold_builder.cpp", "wide_bvh.cpp", "shadow_grid.cpp", "distant_grid.cpp", "halton_tables.cpp", "capi_host.cpp"]
 # host code built by hipcc without an offload target (no code object): the float operations of the scene layout keep the code
 # generator they had when they sat in capi_device.hip
 HIPCC_HOST_SRCS = ["scene_layout.cpp"]
@@ -46,6 +46,10 @@ CUIDS["device/ao.hip"] = "c94e1a7b35f0d826"
 # launchers), beside libhprt.so exactly as libhprt_ao.so is, and for its reason.
 DL_SRCS = ["device/direct.hip"]
 CUIDS["device/direct.hip"] = "5e0b93a7c42d16f8"
+# lib/libhprt_dg.so: the distant light's shadow-grid kernel (device/distant_grid.hip: k_distant_grid and its launcher), beside
+# libhprt.so exactly as libhprt_ao.so is, and for its reason.
+DG_SRCS = ["device/distant_grid.hip"]
+CUIDS["device/distant_grid.hip"] = "7d2f8b4e61a9c035"
 COMMON = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-Wall", "-Wno-unused-function"]
 
 
@@ -82,7 +86,7 @@ def build(verbose=False, force=False):
         obj = os.path.join(OBJ, s.replace("/", "_") + ".o")
         cmd = [hipcc if s in HIPCC_HOST_SRCS else "g++"] + COMMON + ["-c", src, "-o", obj]
         jobs.append((src, obj, cmd))
-    for s in HIP_SRCS + AO_SRCS + DL_SRCS + PROBE_SRCS:
+    for s in HIP_SRCS + AO_SRCS + DL_SRCS + DG_SRCS + PROBE_SRCS:
         src = os.path.join(CSRC, s)
         obj = os.path.join(OBJ, s.replace("/", "_") + ".o")
         cmd = [hipcc, "--offload-arch=gfx950"] + COMMON + ["-Wno-unused-result", "-cuid=" + CUIDS[s], "-c", src, "-o", obj]
@@ -102,21 +106,23 @@ def build(verbose=False, force=False):
             if verbose and out:
                 print(out)
     lib = os.path.join(LIB, "libhprt.so")
-    n_side = len(PROBE_SRCS) + len(DL_SRCS) + len(AO_SRCS)
+    n_side = len(PROBE_SRCS) + len(DG_SRCS) + len(DL_SRCS) + len(AO_SRCS)
     probe_objs = [j[1] for j in jobs[len(jobs) - len(PROBE_SRCS):]]
-    dl_objs = [j[1] for j in jobs[len(jobs) - len(PROBE_SRCS) - len(DL_SRCS):len(jobs) - len(PROBE_SRCS)]]
+    dg_objs = [j[1] for j in jobs[len(jobs) - len(PROBE_SRCS) - len(DG_SRCS):len(jobs) - len(PROBE_SRCS)]]
+    dl_objs = [j[1] for j in jobs[len(jobs) - n_side + len(AO_SRCS):len(jobs) - n_side + len(AO_SRCS) + len(DL_SRCS)]]
     ao_objs = [j[1] for j in jobs[len(jobs) - n_side:len(jobs) - n_side + len(AO_SRCS)]]
     objs = [j[1] for j in jobs[:len(jobs) - n_side]]
     ao = os.path.join(LIB, "libhprt_ao.so")
     dl = os.path.join(LIB, "libhprt_dl.so")
-    for side, side_objs in ((ao, ao_objs), (dl, dl_objs)):
+    dg = os.path.join(LIB, "libhprt_dg.so")
+    for side, side_objs in ((ao, ao_objs), (dl, dl_objs), (dg, dg_objs)):
         if force or _newer(side_objs, side):
             cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-o", side] + side_objs
             r = subprocess.run(cmd, capture_output=True, text=True)
             if r.returncode != 0:
                 raise RuntimeError("link failed: %s\n%s" % (" ".join(cmd), r.stderr))
-    if force or _newer(objs + [ao, dl], lib):
-        cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-o", lib] + objs + ["-L" + LIB, "-lhprt_ao", "-lhprt_dl", "-Wl,-rpath,$ORIGIN", "-lz", "-L/opt/rocm/lib", "-lrccl"]   # zlib: PNG textures (texture_io.cpp); RCCL: film gather (capi_gather.hip)
+    if force or _newer(objs + [ao, dl, dg], lib):
+        cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-o", lib] + objs + ["-L" + LIB, "-lhprt_ao", "-lhprt_dl", "-lhprt_dg", "-Wl,-rpath,$ORIGIN", "-lz", "-L/opt/rocm/lib", "-lrccl"]   # zlib: PNG textures (texture_io.cpp); RCCL: film gather (capi_gather.hip)
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError("link failed: %s\n%s" % (" ".join(cmd), r.stderr))

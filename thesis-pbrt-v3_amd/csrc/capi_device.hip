@@ -209,6 +209,18 @@ int hprt_scene_create(const HprtSceneDesc *d, int device, HprtScene **out) try {
         sc->sgInfo.bytes = im.bytes();
         for (int a = 0; a < 3; ++a) sc->sgInfo.light[a] = sg.light[a];
     }
+    if (L.distantGrid.lists.eligible) {
+        const ShadowGrid &sg = L.distantGrid.lists;
+        const ShadowGridImage &im = L.distantGridImage;      // (blocks, then records, in one allocation, as the point light's grid above)
+        const size_t blockBytes = im.blocks.size() * sizeof(uint32_t), recordBytes = im.records.size() * sizeof(uint32_t);
+        if (blockBytes + recordBytes > 0xffff0000ull) return SetError(HPRT_E_INVALID, "hprt_scene_create: the distant grid's image is too large");
+        HIP_TRY(sc->dgImage.alloc(blockBytes + recordBytes));
+        HIP_TRY(hipMemcpy(sc->dgImage.p, im.blocks.data(), blockBytes, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy((char *)sc->dgImage.p + blockBytes, im.records.data(), recordBytes, hipMemcpyHostToDevice));
+        sc->dg = DevDistantGrid{sc->dgImage.as<uint32_t>(), (uint32_t)(blockBytes + recordBytes), (uint32_t)blockBytes, sg.nNear, sg.R, L.distantGrid.frame};
+        sc->dgInfo.nEntries = sg.entries.size(); sc->dgInfo.longest = sg.longest; sc->dgInfo.buildSeconds = sg.buildSeconds; sc->dgInfo.packSeconds = im.packSeconds;
+        sc->dgInfo.eps = sg.eps; sc->dgInfo.bytes = im.bytes();
+    }
     HIP_TRY(sc->counters.alloc(sizeof(DevCounters)));
     HIP_TRY(hipMemset(sc->counters.p, 0, sizeof(DevCounters)));
     HIP_TRY(sc->deepStack.alloc((size_t)HPRT_SPILL_STACK * HPRT_DEEP_THREADS * sizeof(uint2)));
@@ -375,6 +387,10 @@ static bool ShadowGridInUse(const HprtScene *s) {
     // (a phase-profile render keeps the walk: its any-hit records per ray are k_walk4's, and the grid kernel has no profile variant)
     return s->sg.image != nullptr && g_shadowGrid != 0 && s->walk == HprtScene::Walk::Bvh && hprt::WideWalkInUse(s->dev) && !hprt::TraceProfileInUse();
 }
+// Likewise the shadow rays of a scene lit by one distant light, to k_distant_grid (distant_grid.h)
+static bool DistantGridInUse(const HprtScene *s) {
+    return s->dg.image != nullptr && g_shadowGrid != 0 && s->walk == HprtScene::Walk::Bvh && hprt::WideWalkInUse(s->dev) && !hprt::TraceProfileInUse();
+}
 // Diagnostics hooks (not part of include/hprt.h; tests/test_gpu_shadow_grid.py, tools/shadow_grid_replay.py).
 // hprt_debug_shadow_grid: on = 0 sends the shadow rays of later renders through the walk again, 1 through the grid where a scene has
 // one, -1 back to the default; returns the setting before.
@@ -416,6 +432,50 @@ __attribute__((visibility("default"))) int hprt_debug_shadow_grid_occluded(HprtS
     LaunchPackRays(nullptr, d_rays7, (uint32_t)n, rays);
     HIP_TRY(hipEventRecord(ev.e[0], nullptr));
     LaunchShadowGrid(nullptr, s->dev, s->sg, nullptr, nullptr, (uint32_t)n, (uint32_t)n, rays, d_occ, s->workCounter.as<uint32_t>());
+    HIP_TRY(hipEventRecord(ev.e[1], nullptr));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    if (ms) HIP_TRY(hipEventElapsedTime(ms, ev.e[0], ev.e[1]));
+    return HPRT_OK;
+} catch (...) { return hprt::HandleException(); }
+// The distant light's grid (not part of include/hprt.h; tests/test_gpu_distant_grid.py, tools/distant_grid_replay.py).
+// hprt_debug_distant_grid_info: out = {has a grid, R, entries, near-list length, bytes of the device image, build seconds, pack seconds,
+// longest list, mean list, w x y z, U x y z, V x y z, launches of k_distant_grid by this scene's renders so far, eps}
+__attribute__((visibility("default"))) int hprt_debug_distant_grid_info(HprtScene *s, double out[20]) {
+    if (!s || !out) return HPRT_E_INVALID;
+    const bool has = s->dg.image != nullptr;
+    const double nCells = has ? (double)s->dg.R * s->dg.R : 1.0;
+    out[0] = has ? 1 : 0; out[1] = s->dg.R; out[2] = (double)s->dgInfo.nEntries; out[3] = s->dg.nNear; out[4] = (double)s->dgInfo.bytes;
+    out[5] = s->dgInfo.buildSeconds; out[6] = s->dgInfo.packSeconds; out[7] = s->dgInfo.longest;
+    out[8] = has ? (double)(s->dgInfo.nEntries - s->dg.nNear) / nCells : 0.0;
+    for (int a = 0; a < 3; ++a) { out[9 + a] = s->dg.f.W[a]; out[12 + a] = s->dg.f.U[a]; out[15 + a] = s->dg.f.V[a]; }
+    out[18] = (double)s->dgInfo.renderLaunches; out[19] = s->dgInfo.eps;
+    return HPRT_OK;
+}
+// hprt_debug_distant_grid_image_read: as hprt_debug_shadow_grid_image_read, of the image k_distant_grid reads
+__attribute__((visibility("default"))) int hprt_debug_distant_grid_image_read(HprtScene *s, size_t words2[2], uint32_t *blocks, size_t block_cap, uint32_t *records, size_t record_cap) try {
+    if (!s || !words2) return SetError(HPRT_E_INVALID, "hprt_debug_distant_grid_image_read: bad argument");
+    if (!s->dg.image) return SetError(HPRT_E_UNSUPPORTED, "hprt_debug_distant_grid_image_read: the scene has no distant grid");
+    HIP_TRY(hipSetDevice(s->device));
+    words2[0] = s->dg.recordsAt / sizeof(uint32_t); words2[1] = (s->dg.imageBytes - s->dg.recordsAt) / sizeof(uint32_t);
+    if (blocks && block_cap >= words2[0]) HIP_TRY(hipMemcpy(blocks, s->dg.image, words2[0] * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (records && record_cap >= words2[1]) HIP_TRY(hipMemcpy(records, s->dg.image + words2[0], words2[1] * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return HPRT_OK;
+} catch (...) { return hprt::HandleException(); }
+// hprt_debug_distant_grid_occluded: k_distant_grid on the n rays of d_rays7 ([7][n] planes, as hprt_occluded_device takes them), every
+// one formed as a render forms the shadow rays of the scene's light; ms, if given, receives the kernel's time.
+__attribute__((visibility("default"))) int hprt_debug_distant_grid_occluded(HprtScene *s, size_t n, const float *d_rays7, uint8_t *d_occ, float *ms) try {
+    if (!s || !d_rays7 || !d_occ || n == 0 || n > 0x7ffffff0ull) return SetError(HPRT_E_INVALID, "hprt_debug_distant_grid_occluded: bad argument");
+    if (!s->dg.image) return SetError(HPRT_E_UNSUPPORTED, "hprt_debug_distant_grid_occluded: the scene has no distant grid");
+    HIP_TRY(hipSetDevice(s->device));
+    SceneCall call(s, nullptr);
+    RayStream rays; HitStream hits;
+    if (int rc = ApiStreams(s, n, &rays, &hits)) return rc;
+    struct Events { hipEvent_t e[2] = {nullptr, nullptr}; ~Events() { for (auto x : e) if (x) (void)hipEventDestroy(x); } } ev;
+    for (auto &x : ev.e) HIP_TRY(hipEventCreate(&x));
+    LaunchPackRays(nullptr, d_rays7, (uint32_t)n, rays);
+    HIP_TRY(hipEventRecord(ev.e[0], nullptr));
+    LaunchDistantGrid(nullptr, s->dev, s->dg, nullptr, nullptr, (uint32_t)n, (uint32_t)n, rays, d_occ, s->workCounter.as<uint32_t>());
     HIP_TRY(hipEventRecord(ev.e[1], nullptr));
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
@@ -1094,6 +1154,10 @@ int RunBatch(HprtScene *s, hipStream_t st, const RenderParams &rpIn, const Works
             if (ShadowGridInUse(s) && !count && !rayStats && rp.cullMis) {
                 LaunchShadowGrid(st, s->dev, s->sg, cur.shadow, nullptr, nShadow, nShadow, vs.shadow, vs.occluded, wcPath);
                 ++s->sgInfo.renderLaunches;
+            }
+            else if (DistantGridInUse(s) && !count && !rayStats && rp.cullMis) {      // (one distant light: the light-aligned grid, under the same conditions)
+                LaunchDistantGrid(st, s->dev, s->dg, cur.shadow, nullptr, nShadow, nShadow, vs.shadow, vs.occluded, wcPath);
+                ++s->dgInfo.renderLaunches;
             }
             else Trace(s, st, true, count, cur.shadow, nullptr, nShadow, nShadow, vs.shadow, none, vs.occluded, ctr, wcPath, rayStats);
             if (pixelStats) LaunchPixelStats(st, rayStats, vs.pendBeta, cur.shadow, nullptr, nShadow, nShadow, rp.nPix, true, pixelStats);

@@ -26,6 +26,7 @@
 #include "hprt_math.h"
 #include "wide_bvh.h"
 #include "shadow_grid.h"
+#include "distant_grid.h"
 
 using namespace hprt;
 
@@ -1771,9 +1772,10 @@ int hprt_halton_permutations(uint16_t *out, size_t max_entries, size_t *n_entrie
     return HPRT_OK;
 } catch (...) { return hprt::HandleException(); }
 
-// hprt_scene_create over a parsed model and its BVH: the model's records as an HprtSceneDesc of borrowed pointers
-int hprt_scene_create_from_model(const HprtModel *m, const HprtBvh *b, int device, HprtScene **out) try {
-    if (!m || !b || !out) return SetError(HPRT_E_INVALID, "hprt_scene_create_from_model: null argument");
+}  // extern "C"
+// The records of a parsed model and its BVH as an HprtSceneDesc of borrowed pointers, handed to `use`
+template <class Use>
+static int WithModelDesc(const HprtModel *m, const HprtBvh *b, Use use) {
     const SceneModel &sm = m->sc;
     std::vector<HprtShapeDesc> shapes(sm.shapes.size());
     for (size_t i = 0; i < sm.shapes.size(); ++i) {
@@ -1851,7 +1853,20 @@ int hprt_scene_create_from_model(const HprtModel *m, const HprtBvh *b, int devic
     d.lights = lights.data(); d.n_lights = (uint32_t)lights.size();
     // a single light always gets the uniform distribution (core/lightdistrib.cpp:50-52)
     d.light_strategy = sm.lights.size() <= 1 ? 0 : sm.opt.lightStrategy;
-    return hprt_scene_create(&d, device, out);
+    return use(d);
+}
+extern "C" {
+// hprt_scene_create over a parsed model and its BVH
+int hprt_scene_create_from_model(const HprtModel *m, const HprtBvh *b, int device, HprtScene **out) try {
+    if (!m || !b || !out) return SetError(HPRT_E_INVALID, "hprt_scene_create_from_model: null argument");
+    return WithModelDesc(m, b, [&](const HprtSceneDesc &d) { return hprt_scene_create(&d, device, out); });
+} catch (...) { return hprt::HandleException(); }
+// Diagnostics hook (not part of include/hprt.h; tests/test_distant_grid_host.py): the host half of hprt_scene_create_from_model, no
+// device — which shadow grid the scene's layout holds.  out8 = {point grid: eligible, R; distant grid: eligible, R, entries, near-list
+// length, bytes of the image, longest list}
+__attribute__((visibility("default"))) int hprt_debug_shadow_grid_layout(const HprtModel *m, const HprtBvh *b, double out8[8]) try {
+    if (!m || !b || !out8) return SetError(HPRT_E_INVALID, "hprt_debug_shadow_grid_layout: null argument");
+    return WithModelDesc(m, b, [&](const HprtSceneDesc &d) { return LayoutGridsForDebug(d, out8); });
 } catch (...) { return hprt::HandleException(); }
 
 // Film::WriteImage, core/film.cpp:266-303 (no splats)
@@ -2070,6 +2085,70 @@ __attribute__((visibility("default"))) int hprt_debug_shadow_grid_image(size_t n
     ShadowGridImage im;
     PackShadowGrid(g, tris.data(), &im);
     words3[0] = im.blocks.size(); words3[1] = im.records.size(); words3[2] = ShadowGridImageBytes(g) / sizeof(uint32_t);
+    if (blocks && block_cap >= im.blocks.size()) memcpy(blocks, im.blocks.data(), 4 * im.blocks.size());
+    if (records && record_cap >= im.records.size()) memcpy(records, im.records.data(), 4 * im.records.size());
+    return HPRT_OK;
+} catch (...) { return hprt::HandleException(); }
+
+// The triangles of the distant-grid hooks below: 12 floats per triangle, each a leaf of its own, and their bound (bound6 = {min, max}
+// if given, else the min / max of the finite coordinates)
+static void DistantHookTriangles(size_t n, const float *p9, const float *bound6, std::vector<float> *tris, float lo[3], float hi[3]) {
+    tris->assign(12 * n, 0.f);
+    for (int a = 0; a < 3; ++a) { lo[a] = HPRT_INF; hi[a] = -HPRT_INF; }
+    for (size_t i = 0; i < n; ++i)
+        for (int v = 0; v < 3; ++v)
+            for (int a = 0; a < 3; ++a) {
+                const float x = p9[9 * i + 3 * v + a];
+                (*tris)[12 * i + 4 * v + a] = x;
+                if (!std::isfinite(x)) continue;
+                if (x < lo[a]) lo[a] = x;
+                if (x > hi[a]) hi[a] = x;
+            }
+    if (bound6) for (int a = 0; a < 3; ++a) { lo[a] = bound6[a]; hi[a] = bound6[3 + a]; }
+}
+
+// Diagnostics hook (not part of include/hprt.h; tests/test_distant_grid_host.py): BuildDistantGrid, no device, on n triangles given as
+// [n][9] floats — each a leaf of its own — under the light direction w, over bound6 (null: the bound of the triangles).
+// info22 = {R, entries, near-list length, eps, longest list, build seconds, footprint margin, height margin, U[3], V[3], W[3], u0, v0,
+// scaleU, scaleV, hTop}; cell_start (R^2 + 1 words) and entries ({primitive word, key bits} pairs) are written when they fit their
+// capacities (counted in words and pairs).
+__attribute__((visibility("default"))) int hprt_debug_distant_grid_build(size_t n, const float *p9, const float w[3], const float *bound6, uint32_t R, double info22[22],
+                                                                          uint32_t *cell_start, size_t cell_cap, uint32_t *entries, size_t entry_cap) try {
+    if (!n || !p9 || !w || !info22 || R == 0 || n >= (1u << 28)) return SetError(HPRT_E_INVALID, "hprt_debug_distant_grid_build: bad argument");
+    std::vector<float> tris;
+    std::vector<uint8_t> single(n, 1);
+    float lo[3], hi[3];
+    DistantHookTriangles(n, p9, bound6, &tris, lo, hi);
+    DistantGrid dg;
+    BuildDistantGrid(tris.data(), single.data(), (uint32_t)n, w, lo, hi, R, (size_t)1 << 27, 0.0, &dg);
+    const ShadowGrid &g = dg.lists;
+    if (!g.eligible) return SetError(HPRT_E_UNSUPPORTED, "hprt_debug_distant_grid_build: the lists do not fit, or the direction or the bound is not usable");
+    info22[0] = g.R; info22[1] = (double)g.entries.size(); info22[2] = g.nNear; info22[3] = g.eps; info22[4] = g.longest; info22[5] = g.buildSeconds;
+    info22[6] = dg.margin; info22[7] = dg.heightMargin;
+    const DgFrame &f = dg.frame;
+    for (int a = 0; a < 3; ++a) { info22[8 + a] = f.U[a]; info22[11 + a] = f.V[a]; info22[14 + a] = f.W[a]; }
+    info22[17] = f.u0; info22[18] = f.v0; info22[19] = f.scaleU; info22[20] = f.scaleV; info22[21] = f.hTop;
+    if (cell_start && cell_cap >= g.cellStart.size()) memcpy(cell_start, g.cellStart.data(), 4 * g.cellStart.size());
+    if (entries && entry_cap >= g.entries.size()) memcpy(entries, g.entries.data(), 8 * g.entries.size());
+    return HPRT_OK;
+} catch (...) { return hprt::HandleException(); }
+
+// Diagnostics hook (not part of include/hprt.h; tests/test_distant_grid_host.py): the device image (shadow_grid.h, ShadowGridImage) of
+// the grid that hprt_debug_distant_grid_build builds of the same arguments, no device; words3 and the arrays as
+// hprt_debug_shadow_grid_image gives them.
+__attribute__((visibility("default"))) int hprt_debug_distant_grid_image(size_t n, const float *p9, const float w[3], const float *bound6, uint32_t R, size_t words3[3],
+                                                                          uint32_t *blocks, size_t block_cap, uint32_t *records, size_t record_cap) try {
+    if (!n || !p9 || !w || !words3 || R == 0 || n >= (1u << 28)) return SetError(HPRT_E_INVALID, "hprt_debug_distant_grid_image: bad argument");
+    std::vector<float> tris;
+    std::vector<uint8_t> single(n, 1);
+    float lo[3], hi[3];
+    DistantHookTriangles(n, p9, bound6, &tris, lo, hi);
+    DistantGrid dg;
+    BuildDistantGrid(tris.data(), single.data(), (uint32_t)n, w, lo, hi, R, (size_t)1 << 27, 0.0, &dg);
+    if (!dg.lists.eligible || dg.lists.R != R) return SetError(HPRT_E_UNSUPPORTED, "hprt_debug_distant_grid_image: the lists do not fit");
+    ShadowGridImage im;
+    PackShadowGrid(dg.lists, tris.data(), &im);
+    words3[0] = im.blocks.size(); words3[1] = im.records.size(); words3[2] = ShadowGridImageBytes(dg.lists) / sizeof(uint32_t);
     if (blocks && block_cap >= im.blocks.size()) memcpy(blocks, im.blocks.data(), 4 * im.blocks.size());
     if (records && record_cap >= im.records.size()) memcpy(records, im.records.data(), 4 * im.records.size());
     return HPRT_OK;

@@ -17,6 +17,7 @@
 #include "device/rbspinst_walk.h"
 #include "device/bsppaperinst_walk.h"
 #include "device/shadow_grid.h"
+#include "device/distant_grid.h"
 #include "hprt_internal.h"
 
 #define HIP_TRY(expr)                                                                                   \
@@ -76,6 +77,10 @@ struct HprtScene {
     // what hprt_debug_shadow_grid_info reports of it
     hprt::DevBuf sgImage; hprt::DevShadowGrid sg{};
     struct ShadowGridInfo { size_t nEntries = 0; uint32_t longest = 0; double buildSeconds = 0, eps = 0; size_t bytes = 0; float light[3] = {0, 0, 0}; uint64_t renderLaunches = 0; } sgInfo;
+    // the light-aligned grid of a scene lit by one distant light (distant_grid.h; dg.image == null: none) and what
+    // hprt_debug_distant_grid_info reports of it
+    hprt::DevBuf dgImage; hprt::DevDistantGrid dg{};
+    struct DistantGridInfo { size_t nEntries = 0; uint32_t longest = 0; double buildSeconds = 0, packSeconds = 0, eps = 0; size_t bytes = 0; uint64_t renderLaunches = 0; } dgInfo;
     hprt::DevBuf counters, workCounter, deepStack;
     // hprt_debug_capture_rays (tools/sort_experiment.py): the next render copies the rays one bounce queues into a caller buffer
     struct Capture { int bounce = -1, kind = 0; float *out7 = nullptr; size_t cap = 0, n = 0; } capture;

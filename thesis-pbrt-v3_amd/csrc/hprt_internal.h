@@ -48,4 +48,7 @@ int HandleException();      // maps the exception in flight to an HPRT_E_* code 
 // triangle's or sphere's shape), per shape its DevShape flags and material
 int LayoutTagsForDebug(const HprtSceneDesc &d, std::vector<uint32_t> *tags, std::vector<uint32_t> *primShape, std::vector<uint32_t> *shapeFlags,
                        std::vector<int32_t> *shapeMaterial);
+// BuildSceneLayout on *d, for hprt_debug_shadow_grid_layout: out8 = {point grid: eligible, R; distant grid: eligible, R, entries, near-list
+// length, bytes of the image, longest list}
+int LayoutGridsForDebug(const HprtSceneDesc &d, double out8[8]);
 }  // namespace hprt

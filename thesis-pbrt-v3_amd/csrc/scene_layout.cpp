@@ -567,32 +567,38 @@ int LayoutWide(Work &w) {
     return HPRT_OK;
 }
 
-// The shadow grid (shadow_grid.h) of a scene whose every shadow ray ends at one point: exactly one light, a point light; triangles
-// only, no object instances; the leaf-exact walk in use (its leaf boxes and one-triangle marks are what the grid kernel tests with).
+// The shadow grid of a scene whose every shadow ray ends at one point (shadow_grid.h: exactly one light, a point light) or runs along
+// one direction (distant_grid.h: exactly one light, a distant light, worldRadius > 0); triangles only, no object instances; the
+// leaf-exact walk in use (its leaf boxes and one-triangle marks are what the grid kernels test with).
 // HPRT_SHADOW_GRID=0: no grid (A/B runs); unset: only a grid that is expected to be cheaper than the walk (SG_MAX_CANDIDATES); 1: any.
 // Everything else keeps the walk for its shadow rays.
 int LayoutShadowGrid(Work &w) {
     SceneLayout &L = w.L;
     const int mode = ShadowGridModeFromEnv();
-    if (mode == 0 || w.d.n_lights != 1 || L.lights.size() != 1 || L.lights[0].type != 0 || w.d.n_instances != 0 || w.d.n_objects != 0 ||
+    if (mode == 0 || w.d.n_lights != 1 || L.lights.size() != 1 || (L.lights[0].type != 0 && L.lights[0].type != 1) || w.d.n_instances != 0 || w.d.n_objects != 0 ||
         !L.spheres.empty() || L.wide.empty() || L.nPrims == 0 || L.nPrims >= (1u << 28))
         return HPRT_OK;
+    const bool distant = L.lights[0].type == 1;
+    if (distant && !(L.worldRadius > 0.f)) return HPRT_OK;
     for (uint32_t i = 0; i < L.nPrims; ++i) if ((f2u(L.tris[3 * (size_t)i].w) & TAG_KIND_MASK) != 0u) return HPRT_OK;
     static_assert(sizeof(float4) == 16, "triangle records are read as 12 floats per primitive");
     // at most 1 GiB of device image (HPRT_SHADOW_GRID_MAX_MB; the kernel forms 32-bit byte offsets into it): a finer grid is halved
     // until its image fits
     const size_t capMb = [] { const char *e = getenv("HPRT_SHADOW_GRID_MAX_MB"); return e ? (size_t)std::max(1l, atol(e)) : (size_t)1024; }();
     const size_t capBytes = std::min(capMb << 20, (size_t)0xffff0000u);
-    for (uint32_t R = ShadowGridResFromEnv();; R = std::max(1u, L.shadowGrid.R / 2)) {
-        while (R > 1 && (size_t)6 * R * R * SG_BLOCK_WORDS * sizeof(uint32_t) > capBytes) R /= 2;      // (the blocks alone)
+    const size_t faces = distant ? 1 : 6;
+    ShadowGrid &lists = distant ? L.distantGrid.lists : L.shadowGrid;
+    for (uint32_t R = distant ? DistantGridResFromEnv() : ShadowGridResFromEnv();; R = std::max(1u, lists.R / 2)) {
+        while (R > 1 && faces * R * R * SG_BLOCK_WORDS * sizeof(uint32_t) > capBytes) R /= 2;      // (the blocks alone)
         // no image that fits holds more entries: the records, and two in every block
-        const size_t maxEntries = capBytes / (SG_RECORD_WORDS * sizeof(uint32_t)) + (size_t)SG_BLOCK_SLOTS * 6 * R * R;
-        BuildShadowGrid(&L.tris[0].x, L.primSingle.data(), L.nPrims, L.lights[0].pos, L.wbMin, L.wbMax, R, maxEntries, mode < 0 ? SG_MAX_CANDIDATES : 0.0, &L.shadowGrid);
-        if (!L.shadowGrid.eligible) return HPRT_OK;
-        if (ShadowGridImageBytes(L.shadowGrid) <= capBytes) break;
-        if (L.shadowGrid.R == 1) { L.shadowGrid = ShadowGrid(); return HPRT_OK; }      // (not even one cell per face fits: the scene keeps the walk)
+        const size_t maxEntries = capBytes / (SG_RECORD_WORDS * sizeof(uint32_t)) + (size_t)SG_BLOCK_SLOTS * faces * R * R;
+        if (distant) BuildDistantGrid(&L.tris[0].x, L.primSingle.data(), L.nPrims, L.lights[0].pos, L.wbMin, L.wbMax, R, maxEntries, mode < 0 ? SG_MAX_CANDIDATES : 0.0, &L.distantGrid);
+        else BuildShadowGrid(&L.tris[0].x, L.primSingle.data(), L.nPrims, L.lights[0].pos, L.wbMin, L.wbMax, R, maxEntries, mode < 0 ? SG_MAX_CANDIDATES : 0.0, &L.shadowGrid);
+        if (!lists.eligible) return HPRT_OK;
+        if (ShadowGridImageBytes(lists) <= capBytes) break;
+        if (lists.R == 1) { L.shadowGrid = ShadowGrid(); L.distantGrid = DistantGrid(); return HPRT_OK; }      // (not even one cell per face fits: the scene keeps the walk)
     }
-    PackShadowGrid(L.shadowGrid, &L.tris[0].x, &L.shadowGridImage);
+    PackShadowGrid(lists, &L.tris[0].x, distant ? &L.distantGridImage : &L.shadowGridImage);
     return HPRT_OK;
 }
 
@@ -695,3 +701,15 @@ void VoxelSamplePoints(float *out) {
 
 // Diagnostics hook (not part of include/hprt.h): the 128 sample points of a voxel, RadicalInverse(0..4, i) as [5][128]
 extern "C" __attribute__((visibility("default"))) int hprt_debug_voxel_points(float out[640]) { if (!out) return HPRT_E_INVALID; hprt::VoxelSamplePoints(out); return HPRT_OK; }
+
+namespace hprt {
+int LayoutGridsForDebug(const HprtSceneDesc &d, double out8[8]) {
+    SceneLayout L;
+    if (int rc = BuildSceneLayout(d, &L)) return rc;
+    const ShadowGrid &dg = L.distantGrid.lists;
+    out8[0] = L.shadowGrid.eligible ? 1 : 0; out8[1] = L.shadowGrid.R;
+    out8[2] = dg.eligible ? 1 : 0; out8[3] = dg.R; out8[4] = (double)dg.entries.size(); out8[5] = dg.nNear;
+    out8[6] = dg.eligible ? (double)L.distantGridImage.bytes() : 0.0; out8[7] = dg.longest;
+    return HPRT_OK;
+}
+}  // namespace hprt

@@ -7,6 +7,7 @@
 #include "../../include/hprt.h"
 #include "device/dev_scene.h"
 #include "shadow_grid.h"
+#include "distant_grid.h"
 
 namespace hprt {
 
@@ -48,6 +49,9 @@ struct SceneLayout {
     // that is lit by one point light and takes the leaf-exact walk
     ShadowGrid shadowGrid;
     ShadowGridImage shadowGridImage;               // what is uploaded of it (filled when shadowGrid.eligible)
+    // the light-aligned grid of a scene lit by one distant light instead (distant_grid.h), under the same conditions
+    DistantGrid distantGrid;
+    ShadowGridImage distantGridImage;              // (filled when distantGrid.lists.eligible)
 };
 
 // Validates *d and fills *out; HPRT_OK or an HPRT_E_* code with hprt_last_error() set.

@@ -173,7 +173,7 @@ void PackShadowGrid(const ShadowGrid &g, const float *tris, ShadowGridImage *out
     ShadowGridImage &im = *out;
     im = ShadowGridImage();
     im.R = g.R; im.nNear = g.nNear;
-    const size_t nCells = (size_t)6 * g.R * g.R;
+    const size_t nCells = g.cellStart.empty() ? 0 : g.cellStart.size() - 1;      // faces * R^2: six faces here, one in distant_grid.h
     im.nRecords =(ShadowGridImageBytes(g) / sizeof(uint32_t) - nCells * SG_BLOCK_WORDS) / SG_RECORD_WORDS - SG_PAD_RECORDS;
     im.blocks.assign(nCells * SG_BLOCK_WORDS, 0u);
     im.records.assign((im.nRecords + SG_PAD_RECORDS) * SG_RECORD_WORDS, 0u);

@@ -59,7 +59,7 @@ enum : uint32_t { SG_BLOCK_WORDS = 32u, SG_BLOCK_SLOTS = 2u, SG_RECORD_WORDS = 1
 struct ShadowGridImage {
     uint32_t R = 0, nNear = 0;
     size_t nRecords = 0;                 // near list + overflow runs, without the padding
-    std::vector<uint32_t> blocks;        // 6 R^2 * SG_BLOCK_WORDS
+    std::vector<uint32_t> blocks;        // faces * R^2 * SG_BLOCK_WORDS (faces * R^2 = the grid's cellStart.size() - 1)
     std::vector<uint32_t> records;       // (nRecords + SG_PAD_RECORDS) * SG_RECORD_WORDS
     double packSeconds = 0;
     size_t bytes() const { return (blocks.size() + records.size()) * sizeof(uint32_t); }
