@@ -75,6 +75,24 @@ def scenes():
     }
 
 
+def grid_scene(hprt, model, res=None, grid="1"):
+    """Scene(model) on device 0 created under HPRT_SHADOW_GRID_RES = res (None: the default) and HPRT_SHADOW_GRID = grid — "1" a grid
+    whatever its lists' lengths, "0" none, None the default (a grid only where it is expected to beat the walk)"""
+    env = {"HPRT_SHADOW_GRID_RES": None if res is None else str(res), "HPRT_SHADOW_GRID": grid}
+    old = {k: os.environ.get(k) for k in env}
+    try:
+        for k, v in env.items():
+            os.environ.pop(k, None)
+            if v is not None:
+                os.environ[k] = v
+        return hprt.Scene(model, hprt.Bvh(model), device=0)
+    finally:
+        for k, v in old.items():
+            os.environ.pop(k, None)
+            if v is not None:
+                os.environ[k] = v
+
+
 def cell_of(d, R):
     """The device's sg_cell (csrc/device/shadow_grid.hip) of the directions -d, [n, 3] float32, restated operation for operation:
     (cell, su, sv) — the cell and the sixteenth of it along u and v"""

@@ -17,28 +17,13 @@ import pytest
 
 import distant_grid_cases as dgc
 import shadow_grid_cases as sgc
+from shadow_grid_cases import grid_scene as _scene
 from conftest import ROOT
 
 pytestmark = pytest.mark.gpu
 
 F = np.float32
 CUTS = (0, 1, 2, 3, 4, -1)      # the entry in front of which the key cut falls; -1: behind the list's last key
-
-
-def _scene(hprt, model, res=None, grid="1"):
-    env = {"HPRT_SHADOW_GRID_RES": None if res is None else str(res), "HPRT_SHADOW_GRID": grid}
-    old = {k: os.environ.get(k) for k in env}
-    try:
-        for k, v in env.items():
-            os.environ.pop(k, None)
-            if v is not None:
-                os.environ[k] = v
-        return hprt.Scene(model, hprt.Bvh(model), device=0)
-    finally:
-        for k, v in old.items():
-            os.environ.pop(k, None)
-            if v is not None:
-                os.environ[k] = v
 
 
 def _rays7(o, d, tm):

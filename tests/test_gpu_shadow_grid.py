@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 
 import shadow_grid_cases as sgc
+from shadow_grid_cases import grid_scene as _scene
 from conftest import GOLDEN, ROOT
 
 sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -42,24 +43,6 @@ def _baked(name, tmp, hprt):
     path = os.path.join(tmp, name + ".hprt")
     model.save(path)
     return model, path
-
-
-def _scene(hprt, model, res=None, grid="1"):
-    """grid: HPRT_SHADOW_GRID at scene creation — "1" a grid whatever its lists' lengths, "0" none, None the default (a grid only where it is
-    expected to beat the walk)"""
-    env = {"HPRT_SHADOW_GRID_RES": None if res is None else str(res), "HPRT_SHADOW_GRID": grid}
-    old = {k: os.environ.get(k) for k in env}
-    try:
-        for k, v in env.items():
-            os.environ.pop(k, None)
-            if v is not None:
-                os.environ[k] = v
-        return hprt.Scene(model, hprt.Bvh(model), device=0)
-    finally:
-        for k, v in old.items():
-            os.environ.pop(k, None)
-            if v is not None:
-                os.environ[k] = v
 
 
 def _ulps(x, k):

@@ -21,6 +21,7 @@ import numpy as np
 import pytest
 
 import shadow_grid_cases as sgc
+from shadow_grid_cases import grid_scene as _scene
 from conftest import ROOT
 
 sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -43,22 +44,6 @@ def _texts():
 
 TEXTS = _texts()
 NAMES = sorted(TEXTS)
-
-
-def _scene(hprt, model, res, grid):
-    env = {"HPRT_SHADOW_GRID_RES": None if res is None else str(res), "HPRT_SHADOW_GRID": grid}
-    old = {k: os.environ.get(k) for k in env}
-    try:
-        for k, v in env.items():
-            os.environ.pop(k, None)
-            if v is not None:
-                os.environ[k] = v
-        return hprt.Scene(model, hprt.Bvh(model), device=0)
-    finally:
-        for k, v in old.items():
-            os.environ.pop(k, None)
-            if v is not None:
-                os.environ[k] = v
 
 
 def _cell_directions(cells, R, rng):

@@ -1325,22 +1325,27 @@ class Scene:
         return {"eligible": bool(out[0]), "R": int(out[1]), "entries": int(out[2]), "near": int(out[3]), "bytes": int(out[4]), "build_seconds": float(out[5]),
                 "longest": int(out[6]), "mean": float(out[7]), "light": out[8:11].astype(np.float32), "render_launches": int(out[11])}
 
+    def _grid_image(self, read, info, faces):
+        words = np.zeros(2, np.uint64)
+        _check(read(self._h, _ptr(words), None, 0, None, 0))
+        blocks = np.zeros(int(words[0]), np.uint32); records = np.zeros(max(1, int(words[1])), np.uint32)
+        _check(read(self._h, _ptr(words), _ptr(blocks), blocks.size, _ptr(records), records.size))
+        return shadow_grid_image_decode(blocks, records[:int(words[1])], info["R"], info["near"], faces=faces)
+
+    def _grid_occluded(self, occluded, n, rays7_ptr, occ_ptr):
+        ms = C.c_float()
+        _check(occluded(self._h, n, rays7_ptr, occ_ptr, C.byref(ms)))
+        return float(ms.value)
+
     def shadow_grid_image(self):
         """Test hook (not part of include/hprt.h): the image k_shadow_grid reads of this scene, copied back from the device and decoded as
         shadow_grid_image_decode does."""
-        words = np.zeros(2, np.uint64)
-        _check(lib.hprt_debug_shadow_grid_image_read(self._h, _ptr(words), None, 0, None, 0))
-        blocks = np.zeros(int(words[0]), np.uint32); records = np.zeros(max(1, int(words[1])), np.uint32)
-        _check(lib.hprt_debug_shadow_grid_image_read(self._h, _ptr(words), _ptr(blocks), blocks.size, _ptr(records), records.size))
-        info = self.shadow_grid_info()
-        return shadow_grid_image_decode(blocks, records[:int(words[1])], info["R"], info["near"])
+        return self._grid_image(lib.hprt_debug_shadow_grid_image_read, self.shadow_grid_info(), 6)
 
     def shadow_grid_occluded_device(self, n, rays7_ptr, occ_ptr):
         """Test hook (not part of include/hprt.h): k_shadow_grid on n device rays ([7][n] planes) that all end at the scene's light,
         d = float32(light - o); returns the kernel's milliseconds."""
-        ms = C.c_float()
-        _check(lib.hprt_debug_shadow_grid_occluded(self._h, n, rays7_ptr, occ_ptr, C.byref(ms)))
-        return float(ms.value)
+        return self._grid_occluded(lib.hprt_debug_shadow_grid_occluded, n, rays7_ptr, occ_ptr)
 
     def distant_grid_info(self):
         """Test hook (not part of include/hprt.h): the scene's light-aligned shadow grid of its one distant light — eligible (False: its
@@ -1355,19 +1360,12 @@ class Scene:
     def distant_grid_image(self):
         """Test hook (not part of include/hprt.h): the image k_distant_grid reads of this scene, copied back from the device and decoded as
         shadow_grid_image_decode does (faces = 1)."""
-        words = np.zeros(2, np.uint64)
-        _check(lib.hprt_debug_distant_grid_image_read(self._h, _ptr(words), None, 0, None, 0))
-        blocks = np.zeros(int(words[0]), np.uint32); records = np.zeros(max(1, int(words[1])), np.uint32)
-        _check(lib.hprt_debug_distant_grid_image_read(self._h, _ptr(words), _ptr(blocks), blocks.size, _ptr(records), records.size))
-        info = self.distant_grid_info()
-        return shadow_grid_image_decode(blocks, records[:int(words[1])], info["R"], info["near"], faces=1)
+        return self._grid_image(lib.hprt_debug_distant_grid_image_read, self.distant_grid_info(), 1)
 
     def distant_grid_occluded_device(self, n, rays7_ptr, occ_ptr):
         """Test hook (not part of include/hprt.h): k_distant_grid on n device rays ([7][n] planes) formed as a render forms the shadow
         rays of the scene's distant light; returns the kernel's milliseconds."""
-        ms = C.c_float()
-        _check(lib.hprt_debug_distant_grid_occluded(self._h, n, rays7_ptr, occ_ptr, C.byref(ms)))
-        return float(ms.value)
+        return self._grid_occluded(lib.hprt_debug_distant_grid_occluded, n, rays7_ptr, occ_ptr)
 
     def intersect_device(self, n, rays7_ptr, t_ptr, prim_ptr, bary_ptr=None, stream=None):
         _check(lib.hprt_intersect_device(self._h, n, rays7_ptr, t_ptr, prim_ptr, bary_ptr, stream))

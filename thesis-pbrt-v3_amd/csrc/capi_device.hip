@@ -195,31 +195,21 @@ int hprt_scene_create(const HprtSceneDesc *d, int device, HprtScene **out) try {
     HIP_TRY(upload(sc->textures, L.textures)); HIP_TRY(upload(sc->mipLevels, L.mipLevels)); HIP_TRY(upload(sc->texels, L.texels)); HIP_TRY(upload(sc->weightLut, L.weightLut));
     HIP_TRY(upload(sc->wide, L.wide)); HIP_TRY(upload(sc->leafBox, L.leafBox));
     HIP_TRY(upload(sc->envLights, L.envLights)); HIP_TRY(upload(sc->envData, L.envData));
-    if (L.shadowGrid.eligible) {
-        const ShadowGrid &sg = L.shadowGrid;
-        const ShadowGridImage &im = L.shadowGridImage;      // (the lists with their triangles in list order: shadow_grid.h)
+    if (L.grid.lists.eligible) {
+        const ShadowGrid &sg = L.grid.lists;
+        const ShadowGridImage &im = L.gridImage;      // (the lists with their triangles in list order: shadow_grid.h)
         // blocks, then records, in one allocation (scene_layout.cpp keeps the image below 2^32 bytes)
         const size_t blockBytes = im.blocks.size() * sizeof(uint32_t), recordBytes = im.records.size() * sizeof(uint32_t);
-        if (blockBytes + recordBytes > 0xffff0000ull) return SetError(HPRT_E_INVALID, "hprt_scene_create: the shadow grid's image is too large");
-        HIP_TRY(sc->sgImage.alloc(blockBytes + recordBytes));
-        HIP_TRY(hipMemcpy(sc->sgImage.p, im.blocks.data(), blockBytes, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy((char *)sc->sgImage.p + blockBytes, im.records.data(), recordBytes, hipMemcpyHostToDevice));
-        sc->sg = DevShadowGrid{sc->sgImage.as<uint32_t>(), (uint32_t)(blockBytes + recordBytes), (uint32_t)blockBytes, sg.nNear, sg.R};
-        sc->sgInfo.nEntries = sg.entries.size(); sc->sgInfo.longest = sg.longest; sc->sgInfo.buildSeconds = sg.buildSeconds + im.packSeconds; sc->sgInfo.eps = sg.eps;
-        sc->sgInfo.bytes = im.bytes();
-        for (int a = 0; a < 3; ++a) sc->sgInfo.light[a] = sg.light[a];
-    }
-    if (L.distantGrid.lists.eligible) {
-        const ShadowGrid &sg = L.distantGrid.lists;
-        const ShadowGridImage &im = L.distantGridImage;      // (blocks, then records, in one allocation, as the point light's grid above)
-        const size_t blockBytes = im.blocks.size() * sizeof(uint32_t), recordBytes = im.records.size() * sizeof(uint32_t);
-        if (blockBytes + recordBytes > 0xffff0000ull) return SetError(HPRT_E_INVALID, "hprt_scene_create: the distant grid's image is too large");
-        HIP_TRY(sc->dgImage.alloc(blockBytes + recordBytes));
-        HIP_TRY(hipMemcpy(sc->dgImage.p, im.blocks.data(), blockBytes, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy((char *)sc->dgImage.p + blockBytes, im.records.data(), recordBytes, hipMemcpyHostToDevice));
-        sc->dg = DevDistantGrid{sc->dgImage.as<uint32_t>(), (uint32_t)(blockBytes + recordBytes), (uint32_t)blockBytes, sg.nNear, sg.R, L.distantGrid.frame};
-        sc->dgInfo.nEntries = sg.entries.size(); sc->dgInfo.longest = sg.longest; sc->dgInfo.buildSeconds = sg.buildSeconds; sc->dgInfo.packSeconds = im.packSeconds;
-        sc->dgInfo.eps = sg.eps; sc->dgInfo.bytes = im.bytes();
+        if (blockBytes + recordBytes > 0xffff0000ull)
+            return SetError(HPRT_E_INVALID, L.gridKind == GridKind::Point ? "hprt_scene_create: the shadow grid's image is too large" : "hprt_scene_create: the distant grid's image is too large");
+        HIP_TRY(sc->gridImage.alloc(blockBytes + recordBytes));
+        HIP_TRY(hipMemcpy(sc->gridImage.p, im.blocks.data(), blockBytes, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy((char *)sc->gridImage.p + blockBytes, im.records.data(), recordBytes, hipMemcpyHostToDevice));
+        sc->gridKind = L.gridKind;
+        sc->grid = DevDistantGrid{sc->gridImage.as<uint32_t>(), (uint32_t)(blockBytes + recordBytes), (uint32_t)blockBytes, sg.nNear, sg.R, L.grid.frame};
+        HprtScene::GridInfo &in = sc->gridInfo;
+        in.nEntries = sg.entries.size(); in.longest = sg.longest; in.buildSeconds = sg.buildSeconds; in.packSeconds = im.packSeconds; in.eps = sg.eps; in.bytes = im.bytes();
+        for (int a = 0; a < 3; ++a) in.light[a] = sg.light[a];
     }
     HIP_TRY(sc->counters.alloc(sizeof(DevCounters)));
     HIP_TRY(hipMemset(sc->counters.p, 0, sizeof(DevCounters)));
@@ -383,14 +373,55 @@ static void Trace(HprtScene *s, hipStream_t st, bool anyHit, bool count, const u
 // The shadow rays of a plain render go to k_shadow_grid: the scene has a grid (eligibility: scene_layout.cpp, LayoutShadowGrid), still
 // walks its BVH and takes the leaf-exact walk, whose leaf boxes the grid kernel tests with.  hprt_debug_shadow_grid(0) keeps the walk.
 static int g_shadowGrid = -1;
-static bool ShadowGridInUse(const HprtScene *s) {
-    // (a phase-profile render keeps the walk: its any-hit records per ray are k_walk4's, and the grid kernel has no profile variant)
-    return s->sg.image != nullptr && g_shadowGrid != 0 && s->walk == HprtScene::Walk::Bvh && hprt::WideWalkInUse(s->dev) && !hprt::TraceProfileInUse();
+static bool GridInUse(const HprtScene *s) {
+    // (a phase-profile render keeps the walk: its any-hit records per ray are k_walk4's, and the grid kernels have no profile variant)
+    return s->gridKind != GridKind::None && g_shadowGrid != 0 && s->walk == HprtScene::Walk::Bvh && hprt::WideWalkInUse(s->dev) && !hprt::TraceProfileInUse();
 }
-// Likewise the shadow rays of a scene lit by one distant light, to k_distant_grid (distant_grid.h)
-static bool DistantGridInUse(const HprtScene *s) {
-    return s->dg.image != nullptr && g_shadowGrid != 0 && s->walk == HprtScene::Walk::Bvh && hprt::WideWalkInUse(s->dev) && !hprt::TraceProfileInUse();
+// The scene's grid kernel — k_shadow_grid for a point light's grid, k_distant_grid (distant_grid.h) for a distant light's —
+// over the rays of a queue
+static void LaunchGrid(const HprtScene *s, hipStream_t st, const uint32_t *queue, uint32_t n, const RayStream &rays, uint8_t *occ, uint32_t *workCounter) {
+    const DevDistantGrid &g = s->grid;
+    if (s->gridKind == GridKind::Point) LaunchShadowGrid(st, s->dev, DevShadowGrid{g.image, g.imageBytes, g.recordsAt, g.nNear, g.R}, queue, nullptr, n, n, rays, occ, workCounter);
+    else LaunchDistantGrid(st, s->dev, g, queue, nullptr, n, n, rays, occ, workCounter);
 }
+// What the hooks of one kind see of a scene: its grid if it is of that kind, else none, all zeros
+struct GridOfKind {
+    bool has = false; DevDistantGrid g{}; HprtScene::GridInfo info;
+    GridOfKind(const HprtScene *s, GridKind k) { if (s->gridKind == k) { has = true; g = s->grid; info = s->gridInfo; } }
+    double meanList(double faces) const { return has ? (double)(info.nEntries - g.nNear) / (faces * g.R * g.R) : 0.0; }
+};
+// the image a grid kernel reads of this scene (shadow_grid.h, ShadowGridImage), copied back from the device: words2 = {block words,
+// record words, the padding included}; each array is written when it fits its capacity in words.
+static int GridImageRead(HprtScene *s, GridKind k, const char *badArg, const char *noGrid, size_t words2[2], uint32_t *blocks, size_t block_cap, uint32_t *records, size_t record_cap) try {
+    if (!s || !words2) return SetError(HPRT_E_INVALID, badArg);
+    if (s->gridKind != k) return SetError(HPRT_E_UNSUPPORTED, noGrid);
+    HIP_TRY(hipSetDevice(s->device));
+    const DevDistantGrid &g = s->grid;
+    words2[0] = g.recordsAt / sizeof(uint32_t); words2[1] = (g.imageBytes - g.recordsAt) / sizeof(uint32_t);
+    if (blocks && block_cap >= words2[0]) HIP_TRY(hipMemcpy(blocks, g.image, words2[0] * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (records && record_cap >= words2[1]) HIP_TRY(hipMemcpy(records, g.image + words2[0], words2[1] * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return HPRT_OK;
+} catch (...) { return hprt::HandleException(); }
+// the scene's grid kernel on the n rays of d_rays7 ([7][n] planes, as hprt_occluded_device takes them), every one formed as a render
+// forms the shadow rays of the scene's light (a point light: d = light - o in float); ms, if given, receives the kernel's time.
+static int GridOccluded(HprtScene *s, GridKind k, const char *badArg, const char *noGrid, size_t n, const float *d_rays7, uint8_t *d_occ, float *ms) try {
+    if (!s || !d_rays7 || !d_occ || n == 0 || n > 0x7ffffff0ull) return SetError(HPRT_E_INVALID, badArg);
+    if (s->gridKind != k) return SetError(HPRT_E_UNSUPPORTED, noGrid);
+    HIP_TRY(hipSetDevice(s->device));
+    SceneCall call(s, nullptr);
+    RayStream rays; HitStream hits;
+    if (int rc = ApiStreams(s, n, &rays, &hits)) return rc;
+    struct Events { hipEvent_t e[2] = {nullptr, nullptr}; ~Events() { for (auto x : e) if (x) (void)hipEventDestroy(x); } } ev;
+    for (auto &x : ev.e) HIP_TRY(hipEventCreate(&x));
+    LaunchPackRays(nullptr, d_rays7, (uint32_t)n, rays);
+    HIP_TRY(hipEventRecord(ev.e[0], nullptr));
+    LaunchGrid(s, nullptr, nullptr, (uint32_t)n, rays, d_occ, s->workCounter.as<uint32_t>());
+    HIP_TRY(hipEventRecord(ev.e[1], nullptr));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    if (ms) HIP_TRY(hipEventElapsedTime(ms, ev.e[0], ev.e[1]));
+    return HPRT_OK;
+} catch (...) { return hprt::HandleException(); }
 // Diagnostics hooks (not part of include/hprt.h; tests/test_gpu_shadow_grid.py, tools/shadow_grid_replay.py).
 // hprt_debug_shadow_grid: on = 0 sends the shadow rays of later renders through the walk again, 1 through the grid where a scene has
 // one, -1 back to the default; returns the setting before.
@@ -399,89 +430,37 @@ __attribute__((visibility("default"))) int hprt_debug_shadow_grid(int on) { cons
 // launches of k_shadow_grid by this scene's renders so far}
 __attribute__((visibility("default"))) int hprt_debug_shadow_grid_info(HprtScene *s, double out[12]) {
     if (!s || !out) return HPRT_E_INVALID;
-    for (int a = 0; a < 3; ++a) out[8 + a] = s->sgInfo.light[a];
-    out[11] = (double)s->sgInfo.renderLaunches;
-    const bool has = s->sg.image != nullptr;
-    const double nCells = has ? 6.0 * s->sg.R * s->sg.R : 1.0;
-    out[0] = has ? 1 : 0; out[1] = s->sg.R; out[2] = (double)s->sgInfo.nEntries; out[3] = s->sg.nNear; out[4] = (double)s->sgInfo.bytes;
-    out[5] = s->sgInfo.buildSeconds; out[6] = s->sgInfo.longest; out[7] = has ? (double)(s->sgInfo.nEntries - s->sg.nNear) / nCells : 0.0;
+    const GridOfKind v(s, GridKind::Point);
+    out[0] = v.has ? 1 : 0; out[1] = v.g.R; out[2] = (double)v.info.nEntries; out[3] = v.g.nNear; out[4] = (double)v.info.bytes;
+    out[5] = v.info.buildSeconds + v.info.packSeconds; out[6] = v.info.longest; out[7] = v.meanList(6.0);
+    for (int a = 0; a < 3; ++a) out[8 + a] = v.info.light[a];
+    out[11] = (double)v.info.renderLaunches;
     return HPRT_OK;
 }
-// hprt_debug_shadow_grid_image_read: the image k_shadow_grid reads of this scene (shadow_grid.h, ShadowGridImage), copied back from the
-// device: words2 = {block words, record words, the padding included}; each array is written when it fits its capacity in words.
-__attribute__((visibility("default"))) int hprt_debug_shadow_grid_image_read(HprtScene *s, size_t words2[2], uint32_t *blocks, size_t block_cap, uint32_t *records, size_t record_cap) try {
-    if (!s || !words2) return SetError(HPRT_E_INVALID, "hprt_debug_shadow_grid_image_read: bad argument");
-    if (!s->sg.image) return SetError(HPRT_E_UNSUPPORTED, "hprt_debug_shadow_grid_image_read: the scene has no shadow grid");
-    HIP_TRY(hipSetDevice(s->device));
-    words2[0] = s->sg.recordsAt / sizeof(uint32_t); words2[1] = (s->sg.imageBytes - s->sg.recordsAt) / sizeof(uint32_t);
-    if (blocks && block_cap >= words2[0]) HIP_TRY(hipMemcpy(blocks, s->sg.image, words2[0] * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (records && record_cap >= words2[1]) HIP_TRY(hipMemcpy(records, s->sg.image + words2[0], words2[1] * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    return HPRT_OK;
-} catch (...) { return hprt::HandleException(); }
-// hprt_debug_shadow_grid_occluded: k_shadow_grid on the n rays of d_rays7 ([7][n] planes, as hprt_occluded_device takes them), every one
-// of which must end at the scene's light (d = light - o in float); ms, if given, receives the kernel's time.
-__attribute__((visibility("default"))) int hprt_debug_shadow_grid_occluded(HprtScene *s, size_t n, const float *d_rays7, uint8_t *d_occ, float *ms) try {
-    if (!s || !d_rays7 || !d_occ || n == 0 || n > 0x7ffffff0ull) return SetError(HPRT_E_INVALID, "hprt_debug_shadow_grid_occluded: bad argument");
-    if (!s->sg.image) return SetError(HPRT_E_UNSUPPORTED, "hprt_debug_shadow_grid_occluded: the scene has no shadow grid");
-    HIP_TRY(hipSetDevice(s->device));
-    SceneCall call(s, nullptr);
-    RayStream rays; HitStream hits;
-    if (int rc = ApiStreams(s, n, &rays, &hits)) return rc;
-    struct Events { hipEvent_t e[2] = {nullptr, nullptr}; ~Events() { for (auto x : e) if (x) (void)hipEventDestroy(x); } } ev;
-    for (auto &x : ev.e) HIP_TRY(hipEventCreate(&x));
-    LaunchPackRays(nullptr, d_rays7, (uint32_t)n, rays);
-    HIP_TRY(hipEventRecord(ev.e[0], nullptr));
-    LaunchShadowGrid(nullptr, s->dev, s->sg, nullptr, nullptr, (uint32_t)n, (uint32_t)n, rays, d_occ, s->workCounter.as<uint32_t>());
-    HIP_TRY(hipEventRecord(ev.e[1], nullptr));
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipDeviceSynchronize());
-    if (ms) HIP_TRY(hipEventElapsedTime(ms, ev.e[0], ev.e[1]));
-    return HPRT_OK;
-} catch (...) { return hprt::HandleException(); }
+__attribute__((visibility("default"))) int hprt_debug_shadow_grid_image_read(HprtScene *s, size_t words2[2], uint32_t *blocks, size_t block_cap, uint32_t *records, size_t record_cap) {
+    return GridImageRead(s, GridKind::Point, "hprt_debug_shadow_grid_image_read: bad argument", "hprt_debug_shadow_grid_image_read: the scene has no shadow grid", words2, blocks, block_cap, records, record_cap);
+}
+__attribute__((visibility("default"))) int hprt_debug_shadow_grid_occluded(HprtScene *s, size_t n, const float *d_rays7, uint8_t *d_occ, float *ms) {
+    return GridOccluded(s, GridKind::Point, "hprt_debug_shadow_grid_occluded: bad argument", "hprt_debug_shadow_grid_occluded: the scene has no shadow grid", n, d_rays7, d_occ, ms);
+}
 // The distant light's grid (not part of include/hprt.h; tests/test_gpu_distant_grid.py, tools/distant_grid_replay.py).
 // hprt_debug_distant_grid_info: out = {has a grid, R, entries, near-list length, bytes of the device image, build seconds, pack seconds,
 // longest list, mean list, w x y z, U x y z, V x y z, launches of k_distant_grid by this scene's renders so far, eps}
 __attribute__((visibility("default"))) int hprt_debug_distant_grid_info(HprtScene *s, double out[20]) {
     if (!s || !out) return HPRT_E_INVALID;
-    const bool has = s->dg.image != nullptr;
-    const double nCells = has ? (double)s->dg.R * s->dg.R : 1.0;
-    out[0] = has ? 1 : 0; out[1] = s->dg.R; out[2] = (double)s->dgInfo.nEntries; out[3] = s->dg.nNear; out[4] = (double)s->dgInfo.bytes;
-    out[5] = s->dgInfo.buildSeconds; out[6] = s->dgInfo.packSeconds; out[7] = s->dgInfo.longest;
-    out[8] = has ? (double)(s->dgInfo.nEntries - s->dg.nNear) / nCells : 0.0;
-    for (int a = 0; a < 3; ++a) { out[9 + a] = s->dg.f.W[a]; out[12 + a] = s->dg.f.U[a]; out[15 + a] = s->dg.f.V[a]; }
-    out[18] = (double)s->dgInfo.renderLaunches; out[19] = s->dgInfo.eps;
+    const GridOfKind v(s, GridKind::Distant);
+    out[0] = v.has ? 1 : 0; out[1] = v.g.R; out[2] = (double)v.info.nEntries; out[3] = v.g.nNear; out[4] = (double)v.info.bytes;
+    out[5] = v.info.buildSeconds; out[6] = v.info.packSeconds; out[7] = v.info.longest; out[8] = v.meanList(1.0);
+    for (int a = 0; a < 3; ++a) { out[9 + a] = v.g.f.W[a]; out[12 + a] = v.g.f.U[a]; out[15 + a] = v.g.f.V[a]; }
+    out[18] = (double)v.info.renderLaunches; out[19] = v.info.eps;
     return HPRT_OK;
 }
-// hprt_debug_distant_grid_image_read: as hprt_debug_shadow_grid_image_read, of the image k_distant_grid reads
-__attribute__((visibility("default"))) int hprt_debug_distant_grid_image_read(HprtScene *s, size_t words2[2], uint32_t *blocks, size_t block_cap, uint32_t *records, size_t record_cap) try {
-    if (!s || !words2) return SetError(HPRT_E_INVALID, "hprt_debug_distant_grid_image_read: bad argument");
-    if (!s->dg.image) return SetError(HPRT_E_UNSUPPORTED, "hprt_debug_distant_grid_image_read: the scene has no distant grid");
-    HIP_TRY(hipSetDevice(s->device));
-    words2[0] = s->dg.recordsAt / sizeof(uint32_t); words2[1] = (s->dg.imageBytes - s->dg.recordsAt) / sizeof(uint32_t);
-    if (blocks && block_cap >= words2[0]) HIP_TRY(hipMemcpy(blocks, s->dg.image, words2[0] * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (records && record_cap >= words2[1]) HIP_TRY(hipMemcpy(records, s->dg.image + words2[0], words2[1] * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    return HPRT_OK;
-} catch (...) { return hprt::HandleException(); }
-// hprt_debug_distant_grid_occluded: k_distant_grid on the n rays of d_rays7 ([7][n] planes, as hprt_occluded_device takes them), every
-// one formed as a render forms the shadow rays of the scene's light; ms, if given, receives the kernel's time.
-__attribute__((visibility("default"))) int hprt_debug_distant_grid_occluded(HprtScene *s, size_t n, const float *d_rays7, uint8_t *d_occ, float *ms) try {
-    if (!s || !d_rays7 || !d_occ || n == 0 || n > 0x7ffffff0ull) return SetError(HPRT_E_INVALID, "hprt_debug_distant_grid_occluded: bad argument");
-    if (!s->dg.image) return SetError(HPRT_E_UNSUPPORTED, "hprt_debug_distant_grid_occluded: the scene has no distant grid");
-    HIP_TRY(hipSetDevice(s->device));
-    SceneCall call(s, nullptr);
-    RayStream rays; HitStream hits;
-    if (int rc = ApiStreams(s, n, &rays, &hits)) return rc;
-    struct Events { hipEvent_t e[2] = {nullptr, nullptr}; ~Events() { for (auto x : e) if (x) (void)hipEventDestroy(x); } } ev;
-    for (auto &x : ev.e) HIP_TRY(hipEventCreate(&x));
-    LaunchPackRays(nullptr, d_rays7, (uint32_t)n, rays);
-    HIP_TRY(hipEventRecord(ev.e[0], nullptr));
-    LaunchDistantGrid(nullptr, s->dev, s->dg, nullptr, nullptr, (uint32_t)n, (uint32_t)n, rays, d_occ, s->workCounter.as<uint32_t>());
-    HIP_TRY(hipEventRecord(ev.e[1], nullptr));
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipDeviceSynchronize());
-    if (ms) HIP_TRY(hipEventElapsedTime(ms, ev.e[0], ev.e[1]));
-    return HPRT_OK;
-} catch (...) { return hprt::HandleException(); }
+__attribute__((visibility("default"))) int hprt_debug_distant_grid_image_read(HprtScene *s, size_t words2[2], uint32_t *blocks, size_t block_cap, uint32_t *records, size_t record_cap) {
+    return GridImageRead(s, GridKind::Distant, "hprt_debug_distant_grid_image_read: bad argument", "hprt_debug_distant_grid_image_read: the scene has no distant grid", words2, blocks, block_cap, records, record_cap);
+}
+__attribute__((visibility("default"))) int hprt_debug_distant_grid_occluded(HprtScene *s, size_t n, const float *d_rays7, uint8_t *d_occ, float *ms) {
+    return GridOccluded(s, GridKind::Distant, "hprt_debug_distant_grid_occluded: bad argument", "hprt_debug_distant_grid_occluded: the scene has no distant grid", n, d_rays7, d_occ, ms);
+}
 // Diagnostics (tools/sort_experiment.py): what consuming rays through a PERMUTED index queue costs.  The n rays of d_rays7 stay where
 // they are; d_queue lists them in the order to be traced.  ms[0]: a streaming pass that gathers the rays through the queue into
 // [7][n] planes at d_scratch7 (the physical permutation a sort would have to do), ms[1]: the scene's walk reading the rays through the queue.
@@ -1149,15 +1128,11 @@ int RunBatch(HprtScene *s, hipStream_t st, const RenderParams &rpIn, const Works
             hipEvent_t a = ev.get(), b = ev.get();
             HIP_TRY(hipEventRecord(a, st));
             HitStream none; none.a = nullptr; none.b = nullptr;
-            // a plain render of an eligible scene answers its shadow rays from the light-centred grid; counting, per-pixel-statistics and
+            // a plain render of an eligible scene answers its shadow rays from its light's grid; counting, per-pixel-statistics and
             // trace-all renders keep the walk (their counters are the reference's node counts)
-            if (ShadowGridInUse(s) && !count && !rayStats && rp.cullMis) {
-                LaunchShadowGrid(st, s->dev, s->sg, cur.shadow, nullptr, nShadow, nShadow, vs.shadow, vs.occluded, wcPath);
-                ++s->sgInfo.renderLaunches;
-            }
-            else if (DistantGridInUse(s) && !count && !rayStats && rp.cullMis) {      // (one distant light: the light-aligned grid, under the same conditions)
-                LaunchDistantGrid(st, s->dev, s->dg, cur.shadow, nullptr, nShadow, nShadow, vs.shadow, vs.occluded, wcPath);
-                ++s->dgInfo.renderLaunches;
+            if (GridInUse(s) && !count && !rayStats && rp.cullMis) {
+                LaunchGrid(s, st, cur.shadow, nShadow, vs.shadow, vs.occluded, wcPath);
+                ++s->gridInfo.renderLaunches;
             }
             else Trace(s, st, true, count, cur.shadow, nullptr, nShadow, nShadow, vs.shadow, none, vs.occluded, ctr, wcPath, rayStats);
             if (pixelStats) LaunchPixelStats(st, rayStats, vs.pendBeta, cur.shadow, nullptr, nShadow, nShadow, rp.nPix, true, pixelStats);
@@ -1298,7 +1273,7 @@ int EnsureAoWorkspace(HprtScene *s, size_t nSlots, uint32_t nSamples, uint64_t m
 }
 // One batch of nSlots camera samples: k_generate -> closest-hit trace -> k_ao_frame -> [hit count to the host] -> per range of hits
 // whose rays fit the ray buffer: k_ao_rays -> any-hit trace -> k_ao_resolve.  The any-hit trace is the scene's walk whatever the
-// scene: ShadowGridInUse is a property of the path render's light-directed rays, and these end at no light.
+// scene: GridInUse is a property of the path render's light-directed rays, and these end at no light.
 int RunAoBatch(HprtScene *s, hipStream_t st, const RenderParams &rp, const HprtAoParams &ao, const AoWorkspace &w, const uint64_t *aoBase, uint32_t s0,
                uint32_t nSlots, bool count, const AoRadiance &out, EventTimer &ev, BatchTimers *bt, HprtRenderStats *stats, const IrregularSink *irregular) {
     const uint32_t n = (uint32_t)ao.n_samples;

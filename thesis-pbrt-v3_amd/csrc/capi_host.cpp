@@ -2035,122 +2035,97 @@ __attribute__((visibility("default"))) int hprt_debug_shape_inline(const HprtSce
     return HPRT_OK;
 } catch (...) { return hprt::HandleException(); }
 
-// Diagnostics hook (not part of include/hprt.h; tests/test_shadow_grid_host.py): BuildShadowGrid, no device, on n triangles given as
-// [n][9] floats — each a leaf of its own — around `light`, over the bound of the triangles.  info6 = {R, entries, near-list
-// length, eps, longest list, build seconds}; cell_start (6 R^2 + 1 words) and entries ({primitive word, key bits} pairs) are
-// written when they fit their capacities (counted in words and pairs).
-__attribute__((visibility("default"))) int hprt_debug_shadow_grid_build(size_t n, const float *p9, const float light[3], uint32_t R, double info6[6],
-                                                                         uint32_t *cell_start, size_t cell_cap, uint32_t *entries, size_t entry_cap) try {
-    if (!n || !p9 || !light || !info6 || R == 0 || n >= (1u << 28)) return SetError(HPRT_E_INVALID, "hprt_debug_shadow_grid_build: bad argument");
-    std::vector<float> tris(12 * n, 0.f);
-    std::vector<uint8_t> single(n, 1);
+// The triangles of the grid hooks below: n triangles given as [n][9] floats, as 12 floats per triangle, each a leaf of its own, and
+// their bound.  The point grid's hooks take the min / max of all coordinates as they compare (finiteOnly = false, no bound6); the
+// distant grid's skip the coordinates that are not finite, and take bound6 = {min, max} instead if it is given.
+struct GridHookTriangles {
+    std::vector<float> tris;
+    std::vector<uint8_t> single;
     float lo[3] = {HPRT_INF, HPRT_INF, HPRT_INF}, hi[3] = {-HPRT_INF, -HPRT_INF, -HPRT_INF};
-    for (size_t i = 0; i < n; ++i)
-        for (int v = 0; v < 3; ++v)
-            for (int a = 0; a < 3; ++a) {
-                const float x = p9[9 * i + 3 * v + a];
-                tris[12 * i + 4 * v + a] = x;
-                if (x < lo[a]) lo[a] = x;
-                if (x > hi[a]) hi[a] = x;
-            }
-    ShadowGrid g;
-    BuildShadowGrid(tris.data(), single.data(), (uint32_t)n, light, lo, hi, R, (size_t)1 << 27, 0.0, &g);
-    if (!g.eligible) return SetError(HPRT_E_UNSUPPORTED, "hprt_debug_shadow_grid_build: the lists do not fit");
-    info6[0] = g.R; info6[1] = (double)g.entries.size(); info6[2] = g.nNear; info6[3] = g.eps; info6[4] = g.longest; info6[5] = g.buildSeconds;
+    GridHookTriangles(size_t n, const float *p9, bool finiteOnly, const float *bound6) : tris(12 * n, 0.f), single(n, 1) {
+        for (size_t i = 0; i < n; ++i)
+            for (int v = 0; v < 3; ++v)
+                for (int a = 0; a < 3; ++a) {
+                    const float x = p9[9 * i + 3 * v + a];
+                    tris[12 * i + 4 * v + a] = x;
+                    if (finiteOnly && !std::isfinite(x)) continue;
+                    if (x < lo[a]) lo[a] = x;
+                    if (x > hi[a]) hi[a] = x;
+                }
+        if (bound6) for (int a = 0; a < 3; ++a) { lo[a] = bound6[a]; hi[a] = bound6[3 + a]; }
+    }
+};
+// info[0 .. 6) = {R, entries, near-list length, eps, longest list, build seconds}; cell_start and entries ({primitive word, key bits}
+// pairs) are written when they fit their capacities (counted in words and pairs)
+static void GridHookLists(const ShadowGrid &g, double *info, uint32_t *cell_start, size_t cell_cap, uint32_t *entries, size_t entry_cap) {
+    info[0] = g.R; info[1] = (double)g.entries.size(); info[2] = g.nNear; info[3] = g.eps; info[4] = g.longest; info[5] = g.buildSeconds;
     if (cell_start && cell_cap >= g.cellStart.size()) memcpy(cell_start, g.cellStart.data(), 4 * g.cellStart.size());
     if (entries && entry_cap >= g.entries.size()) memcpy(entries, g.entries.data(), 8 * g.entries.size());
-    return HPRT_OK;
-} catch (...) { return hprt::HandleException(); }
-
-// Diagnostics hook (not part of include/hprt.h; tests/test_shadow_grid_blocks_host.py): the device image (shadow_grid.h, ShadowGridImage)
-// of the grid that hprt_debug_shadow_grid_build builds of the same arguments, no device.  words3 = {block words, record words with
-// the padding, what ShadowGridImageBytes says of the grid}; each array is written when it fits its capacity in words.
-__attribute__((visibility("default"))) int hprt_debug_shadow_grid_image(size_t n, const float *p9, const float light[3], uint32_t R, size_t words3[3],
-                                                                         uint32_t *blocks, size_t block_cap, uint32_t *records, size_t record_cap) try {
-    if (!n || !p9 || !light || !words3 || R == 0 || n >= (1u << 28)) return SetError(HPRT_E_INVALID, "hprt_debug_shadow_grid_image: bad argument");
-    std::vector<float> tris(12 * n, 0.f);
-    std::vector<uint8_t> single(n, 1);
-    float lo[3] = {HPRT_INF, HPRT_INF, HPRT_INF}, hi[3] = {-HPRT_INF, -HPRT_INF, -HPRT_INF};
-    for (size_t i = 0; i < n; ++i)
-        for (int v = 0; v < 3; ++v)
-            for (int a = 0; a < 3; ++a) {
-                const float x = p9[9 * i + 3 * v + a];
-                tris[12 * i + 4 * v + a] = x;
-                if (x < lo[a]) lo[a] = x;
-                if (x > hi[a]) hi[a] = x;
-            }
-    ShadowGrid g;
-    BuildShadowGrid(tris.data(), single.data(), (uint32_t)n, light, lo, hi, R, (size_t)1 << 27, 0.0, &g);
-    if (!g.eligible || g.R != R) return SetError(HPRT_E_UNSUPPORTED, "hprt_debug_shadow_grid_image: the lists do not fit");
+}
+// The device image (shadow_grid.h, ShadowGridImage) of g: words3 = {block words, record words with the padding, what
+// ShadowGridImageBytes says of the grid}; each array is written when it fits its capacity in words.
+static void GridHookImage(const ShadowGrid &g, const float *tris, size_t words3[3], uint32_t *blocks, size_t block_cap, uint32_t *records, size_t record_cap) {
     ShadowGridImage im;
-    PackShadowGrid(g, tris.data(), &im);
+    PackShadowGrid(g, tris, &im);
     words3[0] = im.blocks.size(); words3[1] = im.records.size(); words3[2] = ShadowGridImageBytes(g) / sizeof(uint32_t);
     if (blocks && block_cap >= im.blocks.size()) memcpy(blocks, im.blocks.data(), 4 * im.blocks.size());
     if (records && record_cap >= im.records.size()) memcpy(records, im.records.data(), 4 * im.records.size());
+}
+
+// Diagnostics hook (not part of include/hprt.h; tests/test_shadow_grid_host.py): BuildShadowGrid, no device, on n triangles around
+// `light`, over the bound of the triangles.  info6 and the arrays (cell_start: 6 R^2 + 1 words): GridHookLists.
+__attribute__((visibility("default"))) int hprt_debug_shadow_grid_build(size_t n, const float *p9, const float light[3], uint32_t R, double info6[6],
+                                                                         uint32_t *cell_start, size_t cell_cap, uint32_t *entries, size_t entry_cap) try {
+    if (!n || !p9 || !light || !info6 || R == 0 || n >= (1u << 28)) return SetError(HPRT_E_INVALID, "hprt_debug_shadow_grid_build: bad argument");
+    const GridHookTriangles t(n, p9, false, nullptr);
+    ShadowGrid g;
+    BuildShadowGrid(t.tris.data(), t.single.data(), (uint32_t)n, light, t.lo, t.hi, R, (size_t)1 << 27, 0.0, &g);
+    if (!g.eligible) return SetError(HPRT_E_UNSUPPORTED, "hprt_debug_shadow_grid_build: the lists do not fit");
+    GridHookLists(g, info6, cell_start, cell_cap, entries, entry_cap);
     return HPRT_OK;
 } catch (...) { return hprt::HandleException(); }
 
-// The triangles of the distant-grid hooks below: 12 floats per triangle, each a leaf of its own, and their bound (bound6 = {min, max}
-// if given, else the min / max of the finite coordinates)
-static void DistantHookTriangles(size_t n, const float *p9, const float *bound6, std::vector<float> *tris, float lo[3], float hi[3]) {
-    tris->assign(12 * n, 0.f);
-    for (int a = 0; a < 3; ++a) { lo[a] = HPRT_INF; hi[a] = -HPRT_INF; }
-    for (size_t i = 0; i < n; ++i)
-        for (int v = 0; v < 3; ++v)
-            for (int a = 0; a < 3; ++a) {
-                const float x = p9[9 * i + 3 * v + a];
-                (*tris)[12 * i + 4 * v + a] = x;
-                if (!std::isfinite(x)) continue;
-                if (x < lo[a]) lo[a] = x;
-                if (x > hi[a]) hi[a] = x;
-            }
-    if (bound6) for (int a = 0; a < 3; ++a) { lo[a] = bound6[a]; hi[a] = bound6[3 + a]; }
-}
+// Diagnostics hook (not part of include/hprt.h; tests/test_shadow_grid_blocks_host.py): the device image of the grid that
+// hprt_debug_shadow_grid_build builds of the same arguments, no device.  words3 and the arrays: GridHookImage.
+__attribute__((visibility("default"))) int hprt_debug_shadow_grid_image(size_t n, const float *p9, const float light[3], uint32_t R, size_t words3[3],
+                                                                         uint32_t *blocks, size_t block_cap, uint32_t *records, size_t record_cap) try {
+    if (!n || !p9 || !light || !words3 || R == 0 || n >= (1u << 28)) return SetError(HPRT_E_INVALID, "hprt_debug_shadow_grid_image: bad argument");
+    const GridHookTriangles t(n, p9, false, nullptr);
+    ShadowGrid g;
+    BuildShadowGrid(t.tris.data(), t.single.data(), (uint32_t)n, light, t.lo, t.hi, R, (size_t)1 << 27, 0.0, &g);
+    if (!g.eligible || g.R != R) return SetError(HPRT_E_UNSUPPORTED, "hprt_debug_shadow_grid_image: the lists do not fit");
+    GridHookImage(g, t.tris.data(), words3, blocks, block_cap, records, record_cap);
+    return HPRT_OK;
+} catch (...) { return hprt::HandleException(); }
 
-// Diagnostics hook (not part of include/hprt.h; tests/test_distant_grid_host.py): BuildDistantGrid, no device, on n triangles given as
-// [n][9] floats — each a leaf of its own — under the light direction w, over bound6 (null: the bound of the triangles).
-// info22 = {R, entries, near-list length, eps, longest list, build seconds, footprint margin, height margin, U[3], V[3], W[3], u0, v0,
-// scaleU, scaleV, hTop}; cell_start (R^2 + 1 words) and entries ({primitive word, key bits} pairs) are written when they fit their
-// capacities (counted in words and pairs).
+// Diagnostics hook (not part of include/hprt.h; tests/test_distant_grid_host.py): BuildDistantGrid, no device, on n triangles under
+// the light direction w, over bound6 (null: the bound of the triangles).  info22 = {GridHookLists' six, footprint margin, height
+// margin, U[3], V[3], W[3], u0, v0, scaleU, scaleV, hTop}; the arrays (cell_start: R^2 + 1 words): GridHookLists.
 __attribute__((visibility("default"))) int hprt_debug_distant_grid_build(size_t n, const float *p9, const float w[3], const float *bound6, uint32_t R, double info22[22],
                                                                           uint32_t *cell_start, size_t cell_cap, uint32_t *entries, size_t entry_cap) try {
     if (!n || !p9 || !w || !info22 || R == 0 || n >= (1u << 28)) return SetError(HPRT_E_INVALID, "hprt_debug_distant_grid_build: bad argument");
-    std::vector<float> tris;
-    std::vector<uint8_t> single(n, 1);
-    float lo[3], hi[3];
-    DistantHookTriangles(n, p9, bound6, &tris, lo, hi);
+    const GridHookTriangles t(n, p9, true, bound6);
     DistantGrid dg;
-    BuildDistantGrid(tris.data(), single.data(), (uint32_t)n, w, lo, hi, R, (size_t)1 << 27, 0.0, &dg);
-    const ShadowGrid &g = dg.lists;
-    if (!g.eligible) return SetError(HPRT_E_UNSUPPORTED, "hprt_debug_distant_grid_build: the lists do not fit, or the direction or the bound is not usable");
-    info22[0] = g.R; info22[1] = (double)g.entries.size(); info22[2] = g.nNear; info22[3] = g.eps; info22[4] = g.longest; info22[5] = g.buildSeconds;
+    BuildDistantGrid(t.tris.data(), t.single.data(), (uint32_t)n, w, t.lo, t.hi, R, (size_t)1 << 27, 0.0, &dg);
+    if (!dg.lists.eligible) return SetError(HPRT_E_UNSUPPORTED, "hprt_debug_distant_grid_build: the lists do not fit, or the direction or the bound is not usable");
+    GridHookLists(dg.lists, info22, cell_start, cell_cap, entries, entry_cap);
     info22[6] = dg.margin; info22[7] = dg.heightMargin;
     const DgFrame &f = dg.frame;
     for (int a = 0; a < 3; ++a) { info22[8 + a] = f.U[a]; info22[11 + a] = f.V[a]; info22[14 + a] = f.W[a]; }
     info22[17] = f.u0; info22[18] = f.v0; info22[19] = f.scaleU; info22[20] = f.scaleV; info22[21] = f.hTop;
-    if (cell_start && cell_cap >= g.cellStart.size()) memcpy(cell_start, g.cellStart.data(), 4 * g.cellStart.size());
-    if (entries && entry_cap >= g.entries.size()) memcpy(entries, g.entries.data(), 8 * g.entries.size());
     return HPRT_OK;
 } catch (...) { return hprt::HandleException(); }
 
-// Diagnostics hook (not part of include/hprt.h; tests/test_distant_grid_host.py): the device image (shadow_grid.h, ShadowGridImage) of
-// the grid that hprt_debug_distant_grid_build builds of the same arguments, no device; words3 and the arrays as
-// hprt_debug_shadow_grid_image gives them.
+// Diagnostics hook (not part of include/hprt.h; tests/test_distant_grid_host.py): the device image of the grid that
+// hprt_debug_distant_grid_build builds of the same arguments, no device.  words3 and the arrays: GridHookImage.
 __attribute__((visibility("default"))) int hprt_debug_distant_grid_image(size_t n, const float *p9, const float w[3], const float *bound6, uint32_t R, size_t words3[3],
                                                                           uint32_t *blocks, size_t block_cap, uint32_t *records, size_t record_cap) try {
     if (!n || !p9 || !w || !words3 || R == 0 || n >= (1u << 28)) return SetError(HPRT_E_INVALID, "hprt_debug_distant_grid_image: bad argument");
-    std::vector<float> tris;
-    std::vector<uint8_t> single(n, 1);
-    float lo[3], hi[3];
-    DistantHookTriangles(n, p9, bound6, &tris, lo, hi);
+    const GridHookTriangles t(n, p9, true, bound6);
     DistantGrid dg;
-    BuildDistantGrid(tris.data(), single.data(), (uint32_t)n, w, lo, hi, R, (size_t)1 << 27, 0.0, &dg);
+    BuildDistantGrid(t.tris.data(), t.single.data(), (uint32_t)n, w, t.lo, t.hi, R, (size_t)1 << 27, 0.0, &dg);
     if (!dg.lists.eligible || dg.lists.R != R) return SetError(HPRT_E_UNSUPPORTED, "hprt_debug_distant_grid_image: the lists do not fit");
-    ShadowGridImage im;
-    PackShadowGrid(dg.lists, tris.data(), &im);
-    words3[0] = im.blocks.size(); words3[1] = im.records.size(); words3[2] = ShadowGridImageBytes(dg.lists) / sizeof(uint32_t);
-    if (blocks && block_cap >= im.blocks.size()) memcpy(blocks, im.blocks.data(), 4 * im.blocks.size());
-    if (records && record_cap >= im.records.size()) memcpy(records, im.records.data(), 4 * im.records.size());
+    GridHookImage(dg.lists, t.tris.data(), words3, blocks, block_cap, records, record_cap);
     return HPRT_OK;
 } catch (...) { return hprt::HandleException(); }
 

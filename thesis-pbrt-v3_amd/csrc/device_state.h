@@ -73,14 +73,12 @@ struct HprtScene {
     hprt::DevBuf nodes, tris, primVtx, primN, vUV, vS, shapes, materials, lights, spheres, instances, topEntry, topEntryWide, lightFunc, lightCdf, perms, primes, primeSums, primeMagic;
     hprt::DevBuf envLights, envData;      // infinite lights: DevEnvLight table and their Distribution2D tables
     hprt::DevBuf wide, leafBox;           // the leaf-exact walk structure (wide_bvh.h)
-    // the light-centred shadow grid (shadow_grid.h; sg.image == null: the scene is not eligible, its shadow rays take the walk) and
-    // what hprt_debug_shadow_grid_info reports of it
-    hprt::DevBuf sgImage; hprt::DevShadowGrid sg{};
-    struct ShadowGridInfo { size_t nEntries = 0; uint32_t longest = 0; double buildSeconds = 0, eps = 0; size_t bytes = 0; float light[3] = {0, 0, 0}; uint64_t renderLaunches = 0; } sgInfo;
-    // the light-aligned grid of a scene lit by one distant light (distant_grid.h; dg.image == null: none) and what
-    // hprt_debug_distant_grid_info reports of it
-    hprt::DevBuf dgImage; hprt::DevDistantGrid dg{};
-    struct DistantGridInfo { size_t nEntries = 0; uint32_t longest = 0; double buildSeconds = 0, packSeconds = 0, eps = 0; size_t bytes = 0; uint64_t renderLaunches = 0; } dgInfo;
+    // the scene's shadow grid: the light-centred one of a point light (shadow_grid.h), the light-aligned one of a distant light
+    // (distant_grid.h), or none (its shadow rays take the walk).  grid: the kernel's arguments, of which k_shadow_grid takes all but
+    // the frame; gridInfo: what hprt_debug_{shadow,distant}_grid_info report.
+    hprt::GridKind gridKind = hprt::GridKind::None;
+    hprt::DevBuf gridImage; hprt::DevDistantGrid grid{};
+    struct GridInfo { size_t nEntries = 0; uint32_t longest = 0; double buildSeconds = 0, packSeconds = 0, eps = 0; size_t bytes = 0; float light[3] = {0, 0, 0}; uint64_t renderLaunches = 0; } gridInfo;
     hprt::DevBuf counters, workCounter, deepStack;
     // hprt_debug_capture_rays (tools/sort_experiment.py): the next render copies the rays one bounce queues into a caller buffer
     struct Capture { int bounce = -1, kind = 0; float *out7 = nullptr; size_t cap = 0, n = 0; } capture;

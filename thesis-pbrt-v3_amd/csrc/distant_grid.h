@@ -27,6 +27,9 @@ struct DistantGrid {
     double margin = 0, heightMargin = 0;
 };
 
+// A scene has no grid, the point light's (lists alone) or the distant light's
+enum class GridKind { None, Point, Distant };
+
 // tris, single, bmin / bmax, R, maxEntries, maxCandidates: as BuildShadowGrid takes them.  w: the direction towards the light
 // (LightDesc::pos of a distant light, normalised in float).  A triangle with a vertex that is not finite goes to the near list;
 // every other one — edge-on to the light or degenerate too: a segment's or a point's widened rectangle — to the cells.

@@ -587,18 +587,19 @@ int LayoutShadowGrid(Work &w) {
     const size_t capMb = [] { const char *e = getenv("HPRT_SHADOW_GRID_MAX_MB"); return e ? (size_t)std::max(1l, atol(e)) : (size_t)1024; }();
     const size_t capBytes = std::min(capMb << 20, (size_t)0xffff0000u);
     const size_t faces = distant ? 1 : 6;
-    ShadowGrid &lists = distant ? L.distantGrid.lists : L.shadowGrid;
+    L.gridKind = distant ? GridKind::Distant : GridKind::Point;
+    ShadowGrid &lists = L.grid.lists;
     for (uint32_t R = distant ? DistantGridResFromEnv() : ShadowGridResFromEnv();; R = std::max(1u, lists.R / 2)) {
         while (R > 1 && faces * R * R * SG_BLOCK_WORDS * sizeof(uint32_t) > capBytes) R /= 2;      // (the blocks alone)
         // no image that fits holds more entries: the records, and two in every block
         const size_t maxEntries = capBytes / (SG_RECORD_WORDS * sizeof(uint32_t)) + (size_t)SG_BLOCK_SLOTS * faces * R * R;
-        if (distant) BuildDistantGrid(&L.tris[0].x, L.primSingle.data(), L.nPrims, L.lights[0].pos, L.wbMin, L.wbMax, R, maxEntries, mode < 0 ? SG_MAX_CANDIDATES : 0.0, &L.distantGrid);
-        else BuildShadowGrid(&L.tris[0].x, L.primSingle.data(), L.nPrims, L.lights[0].pos, L.wbMin, L.wbMax, R, maxEntries, mode < 0 ? SG_MAX_CANDIDATES : 0.0, &L.shadowGrid);
+        if (distant) BuildDistantGrid(&L.tris[0].x, L.primSingle.data(), L.nPrims, L.lights[0].pos, L.wbMin, L.wbMax, R, maxEntries, mode < 0 ? SG_MAX_CANDIDATES : 0.0, &L.grid);
+        else BuildShadowGrid(&L.tris[0].x, L.primSingle.data(), L.nPrims, L.lights[0].pos, L.wbMin, L.wbMax, R, maxEntries, mode < 0 ? SG_MAX_CANDIDATES : 0.0, &lists);
         if (!lists.eligible) return HPRT_OK;
         if (ShadowGridImageBytes(lists) <= capBytes) break;
-        if (lists.R == 1) { L.shadowGrid = ShadowGrid(); L.distantGrid = DistantGrid(); return HPRT_OK; }      // (not even one cell per face fits: the scene keeps the walk)
+        if (lists.R == 1) { L.gridKind = GridKind::None; L.grid = DistantGrid(); return HPRT_OK; }      // (not even one cell per face fits: the scene keeps the walk)
     }
-    PackShadowGrid(lists, &L.tris[0].x, distant ? &L.distantGridImage : &L.shadowGridImage);
+    PackShadowGrid(lists, &L.tris[0].x, &L.gridImage);
     return HPRT_OK;
 }
 
@@ -706,10 +707,14 @@ namespace hprt {
 int LayoutGridsForDebug(const HprtSceneDesc &d, double out8[8]) {
     SceneLayout L;
     if (int rc = BuildSceneLayout(d, &L)) return rc;
-    const ShadowGrid &dg = L.distantGrid.lists;
-    out8[0] = L.shadowGrid.eligible ? 1 : 0; out8[1] = L.shadowGrid.R;
-    out8[2] = dg.eligible ? 1 : 0; out8[3] = dg.R; out8[4] = (double)dg.entries.size(); out8[5] = dg.nNear;
-    out8[6] = dg.eligible ? (double)L.distantGridImage.bytes() : 0.0; out8[7] = dg.longest;
+    const ShadowGrid &g = L.grid.lists;
+    const bool point = L.gridKind == GridKind::Point, distant = L.gridKind == GridKind::Distant;
+    for (int i = 0; i < 8; ++i) out8[i] = 0.0;
+    if (point) { out8[0] = g.eligible ? 1 : 0; out8[1] = g.R; }
+    if (distant) {
+        out8[2] = g.eligible ? 1 : 0; out8[3] = g.R; out8[4] = (double)g.entries.size(); out8[5] = g.nNear;
+        out8[6] = g.eligible ? (double)L.gridImage.bytes() : 0.0; out8[7] = g.longest;
+    }
     return HPRT_OK;
 }
 }  // namespace hprt

@@ -45,13 +45,13 @@ struct SceneLayout {
     bool instanced = false, hasSubstrateBin = false;
     // per ordered primitive: its leaf holds that one triangle alone, marked WIDE_LEAF_BOXED | WIDE_LEAF_FIRST in the wide records
     std::vector<uint8_t> primSingle;
-    // the light-centred candidate grid of the shadow rays (shadow_grid.h): eligible for a triangle-only scene without instances
-    // that is lit by one point light and takes the leaf-exact walk
-    ShadowGrid shadowGrid;
-    ShadowGridImage shadowGridImage;               // what is uploaded of it (filled when shadowGrid.eligible)
-    // the light-aligned grid of a scene lit by one distant light instead (distant_grid.h), under the same conditions
-    DistantGrid distantGrid;
-    ShadowGridImage distantGridImage;              // (filled when distantGrid.lists.eligible)
+    // the candidate grid of the shadow rays, for a triangle-only scene without instances that is lit by one light and takes the
+    // leaf-exact walk: light-centred for a point light (shadow_grid.h), light-aligned for a distant light (distant_grid.h).
+    // gridKind: which builder filled `grid` (None: neither was tried); grid.lists.eligible: the scene has that grid.  frame and
+    // the margins are the distant grid's.
+    GridKind gridKind = GridKind::None;
+    DistantGrid grid;
+    ShadowGridImage gridImage;                     // what is uploaded of it (filled when grid.lists.eligible)
 };
 
 // Validates *d and fills *out; HPRT_OK or an HPRT_E_* code with hprt_last_error() set.
