@@ -602,6 +602,41 @@ int hprt_bspnodekd_build_from_triangles_device(size_t n_tris, const float *p9, c
                                                HprtBuildDeviceStats *stats, HprtBspPaperKd **out);
 
 /* ------------------------------------------------------------------------ */
+/* Two-level node-based BSP trees (the nine names above on a model with     */
+/* object instances).  Stands in for pbrtObjectInstance                     */
+/* (core/api.cpp:1794-1819) and pbrtWorldEnd under those accelerators, as   */
+/* the two-level general BSP trees do: a node-based tree whose leaves hold  */
+/* node-based trees.  Opt-in: hprt_bspnode_build and hprt_bspnodekd_build   */
+/* keep refusing such models, the front end keeps their BVH and its warning.*/
+/* ------------------------------------------------------------------------ */
+/* One entry for all nine names: the handle is an HprtBspPaperInst — kd-aware (BSPKdNode words) for HPRT_BSPNODE_FASTKD, plain
+ * (BSPNode words; a withkd tree's axis splits are plane nodes with a unit axis) for the other two forms — and hprt_bsppaperinst_info /
+ * _object_info / _copy / _object_copy / _destroy and hprt_scene_attach_bsppaperinst serve it as they are.  params NULL takes
+ * chooser, form and parameters from the scene's Accelerator line (HPRT_E_INVALID when it names no node-based tree).  One tree per
+ * object with more than one primitive, over the object's primitives in object space, and the top-level tree over the top-level
+ * items in creation order; every tree takes the same parameters, maxdepth -1 resolving per tree.  What the reference's builds call
+ * on a primitive is WorldBound, getBounds(direction) and, through the direction choosers, Normal; getSurfaceArea is not among them
+ * (only the debugging dump of genericBSP.h:107-130 calls it).  On the top level an instance is a TransformedPrimitive
+ * (core/primitive.h:144-182): its Normal() is (0, 0, 0) (:170-172), its getBounds is Primitive's over the 8 corners of its
+ * WorldBound (:72-82, :166-168), its getSurfaceArea() forwards to the wrapped primitive (:174-176) and is never asked.  So an
+ * instance offers the choosers a zero normal — chooseArbitraryNormals then returns zero vectors, which have no candidate;
+ * calculateClusterMeans clusters them at Angle = acos(0) and normalises zero sums — and the library does what the reference's code
+ * does with those values, refusing only where that code indexes past an array (as hprt_bspnode_build does).
+ * THE SEED RULE: every tree of the handle starts a fresh std::mt19937(seed).  This is the one deliberate departure from the
+ * reference stated above (it seeds each tree's engine from std::random_device), applied per tree, and no second one.
+ * Refusals, in this order: a null argument (HPRT_E_INVALID); a model without instances (HPRT_E_UNSUPPORTED: the job of
+ * hprt_bspnode_build / hprt_bspnodekd_build); parameters the reference's build is undefined for, before any primitive is looked at;
+ * a tree's own refusal, prefixed "object N:" or "top level:"; depth(top) + deepest object depth + 1 above HPRT_BSPPAPER_MAX_DEPTH
+ * (= HPRT_BSPPAPERKD_MAX_DEPTH). */
+int hprt_bspnodeinst_build(const HprtModel *m, const HprtBspNodeParams *params, HprtBspPaperInst **out);
+/* The device-assisted build of the same handle: the same bytes, refusals and messages.  The costing hook is installed once and ONE
+ * device session serves every tree; k_sweepcost costs the candidates of nodes with at least min_candidates candidates, overflowing
+ * candidates are costed again on the host, and stats (may be NULL) are summed over the trees.  Without a HIP device:
+ * HPRT_E_NO_DEVICE after the refusals that do not depend on a device or a primitive (the first three above), *out stays NULL. */
+int hprt_bspnodeinst_build_device(const HprtModel *m, const HprtBspNodeParams *params, const HprtBspBuildDeviceOpts *opts, HprtBuildDeviceStats *stats,
+                                  HprtBspPaperInst **out);
+
+/* ------------------------------------------------------------------------ */
 /* Device scene.  Upload step that follows the BVH build: stands in for the  */
 /* `primitives`/`nodes` members BVHAccel keeps (accelerators/bvh.h:69-79) and */
 /* the Scene object (core/scene.h:50-80).  The library copies everything to   */

@@ -401,6 +401,8 @@ def _load():
         "hprt_bspnode_build_from_triangles_device": (C.c_int, [sz, vp, vp, vp, vp, P(vp)]),
         "hprt_bspnodekd_build_device": (C.c_int, [vp, vp, vp, vp, P(vp)]),
         "hprt_bspnodekd_build_from_triangles_device": (C.c_int, [sz, vp, vp, vp, vp, P(vp)]),
+        "hprt_bspnodeinst_build": (C.c_int, [vp, vp, P(vp)]),
+        "hprt_bspnodeinst_build_device": (C.c_int, [vp, vp, vp, vp, P(vp)]),
         "hprt_scene_kd_counters": (C.c_int, [vp, vp]),
         "hprt_pixel_kd_stats_read": (C.c_int, [vp, vp, sz]),
         "hprt_write_pixel_stats_rbspkd": (C.c_int, [cp, vp, vp, C.c_int, C.c_int]),
@@ -1209,6 +1211,28 @@ def bspnode_tree(model, accelerator=None, **kw):
     if not fastkd:
         kw.pop("kd_trav_cost", None)
     return (BspNodeKd if fastkd else BspNode)(model, accelerator, **kw), ("attach_bsppaperkd" if fastkd else "attach_bsppaper")
+
+
+class BspNodeInst(BspPaperInst):
+    """Two-level node-based BSP trees (host) of a model WITH object instances, as pbrtObjectInstance and pbrtWorldEnd build them under
+    one of the nine node-based accelerators (core/api.cpp:1794-1819): one tree per object of more than one primitive and the
+    top-level tree over the top-level items, an instance a primitive with a zero normal and its world bound.  A BspPaperInst in all
+    but its builder — kd-aware for the fastkd forms — so info(), copy(), object_copy(), set_tree() and Scene.attach_bsppaperinst take
+    it unchanged.  BspNodeInst(model) takes accelerator and parameters from the scene's Accelerator line; given `accelerator`
+    ("bspcluster", "bsprandomfastkd", ...), the keyword parameters replace it.  Every tree starts a fresh std::mt19937(seed).
+    device: None builds on the host; a HIP device ordinal costs the split candidates of nodes with at least min_candidates candidates
+    on that GPU (k_sweepcost, one session for all trees; the same trees, byte for byte) and leaves HprtBuildDeviceStats, summed over
+    the trees, as a dict in self.build_stats.  max_edges / max_faces / max_face_edges: 0, or a value that lowers the kernel's
+    compiled capacity."""
+
+    def __init__(self, model, accelerator=None, n_directions=3, seed=BSPNODE_DEFAULT_SEED, isect_cost=80, trav_cost=5, kd_trav_cost=1,
+                 empty_bonus=0.0, max_prims=1, max_depth=-1, threads=0, device=None, min_candidates=0, max_edges=0, max_faces=0, max_face_edges=0):
+        prm = None
+        if accelerator is not None:
+            prm = C.byref(_bspnode_params(accelerator, accelerator.endswith("fastkd"), n_directions, seed, isect_cost, trav_cost, kd_trav_cost,
+                                          empty_bonus, max_prims, max_depth, threads))
+        self._h, self.build_stats = _build_tree("bspnodeinst", "build", (model._h,), prm,
+                                                _device_opts(BspBuildDeviceOpts, device, min_candidates, max_edges, max_faces, max_face_edges, 0))
 
 
 class Scene:

@@ -410,46 +410,60 @@ int BspNodeCostOnDevice(BspNodeCostDevice *dev, const uint32_t cap[4], const Bsp
     return *rc != HPRT_OK ? -1 : 0;
 }
 
+// HprtBspNodeParams over the Accelerator line's (or the defaults'); params NULL keeps *p
+void ApplyBspNodeParams(const HprtBspNodeParams *params, BspNodeParams *p) {
+    if (!params) return;
+    p->chooser = params->chooser; p->form = params->form; p->nDirections = params->n_directions; p->seed = params->seed;
+    p->isectCost = params->isect_cost; p->travCost = params->trav_cost; p->kdTravCost = params->kd_trav_cost; p->emptyBonus = params->empty_bonus;
+    p->maxPrims = params->max_prims; p->maxDepth = params->max_depth; p->threads = params->threads;
+}
+// The costing hook of a node-based build and what it keeps until the build ends or fails: installed once into the params, it serves
+// every BuildBspNodeTree call made with them — the one tree of hprt_bspnode_build_device, every tree of hprt_bspnodeinst_build_device
+// — through one device session, and st.bs sums the statistics over those calls.  The params hold lambdas that point back here.
+struct BspNodeHookState {
+    BspNodeDevicePtr dev;
+    HookState st;
+    uint32_t cap[4] = {0, 0, 0, 0};
+    BspNodeHookState() = default;
+    BspNodeHookState(const BspNodeHookState &) = delete;
+    int Install(const BspNodeHook *hook, BspNodeParams *p) {
+        return InstallHook<BspNodeCostRequest>(hook, p, &st, [&]() -> int {
+            // the refusals that do not depend on the primitives come first, as the host entry gives them, with or without a device
+            const std::string refused = BspNodeRefuseParams(*p);
+            if (!refused.empty()) return SetError(HPRT_E_UNSUPPORTED, refused);
+            const HprtBspBuildDeviceOpts *o = hook->opts;
+            const uint32_t asked[3] = {o ? o->max_edges : 0u, o ? o->max_faces : 0u, o ? o->max_face_edges : 0u};      // (max_stack: no BVH here)
+            std::string derr;
+            BspNodeCostDevice *d = nullptr;
+            const int rc = BspNodeCostDeviceCreate(o ? o->device : 0, asked, &d, &derr);
+            dev.reset(d);
+            if (rc != HPRT_OK) return SetError(rc, derr);
+            bspcost::Scalars sc{};
+            sc.maxEdges = asked[0]; sc.maxFaces = asked[1]; sc.maxFaceEdges = asked[2];
+            bspcost::Capacities(sc, cap);
+            return HPRT_OK;
+        }, [this](const BspNodeCostRequest &rq, std::string *e) -> int { return BspNodeCostOnDevice(dev.get(), cap, rq, &st.rc, e); },
+        [=](uint32_t node, const BspNodeCostRequest &rq) {
+            const HprtDebugBspSweepNode nd{rq.mesh, rq.nEdges, rq.dirs, rq.M, rq.sweep, rq.nDirs, &rq.sc, rq.cands, rq.n, rq.costs, rq.costsFixed, rq.level};
+            hook->sink(hook->user, node, &nd);
+        });
+    }
+};
+
 template <typename Handle>
 int BuildBspNode(const char *fn, size_t n, const float *lo, const float *hi, const float *tri9, const uint8_t *isTri, const HprtBspNodeParams *params,
                  BspNodeParams p, Handle **out, const BspNodeHook *hook = nullptr) {
     constexpr bool fastKd = std::is_same<Handle, HprtBspPaperKd>::value;
     if (hook) *out = nullptr;
-    if (params) {
-        p.chooser = params->chooser; p.form = params->form; p.nDirections = params->n_directions; p.seed = params->seed;
-        p.isectCost = params->isect_cost; p.travCost = params->trav_cost; p.kdTravCost = params->kd_trav_cost; p.emptyBonus = params->empty_bonus;
-        p.maxPrims = params->max_prims; p.maxDepth = params->max_depth; p.threads = params->threads;
-    }
+    ApplyBspNodeParams(params, &p);
     if ((p.form == BSPNODE_FASTKD) != fastKd)
         return SetError(HPRT_E_INVALID, std::string(fn) + (fastKd ? ": takes the fastkd form only (the plain and withkd forms are hprt_bspnode_build's)"
                                                                   : ": takes the plain and withkd forms only (the fastkd form is hprt_bspnodekd_build's)"));
     std::unique_ptr<Handle> t(new Handle());
-    BspNodeDevicePtr dev;                                // freed when the build ends or fails
-    HookState st;
-    uint32_t cap[4] = {0, 0, 0, 0};
-    const int rc = InstallHook<BspNodeCostRequest>(hook, &p, &st, [&]() -> int {
-        // the refusals that do not depend on the primitives come first, as the host entry gives them, with or without a device
-        const std::string refused = BspNodeRefuseParams(p);
-        if (!refused.empty()) return SetError(HPRT_E_UNSUPPORTED, refused);
-        const HprtBspBuildDeviceOpts *o = hook->opts;
-        const uint32_t asked[3] = {o ? o->max_edges : 0u, o ? o->max_faces : 0u, o ? o->max_face_edges : 0u};      // (max_stack: no BVH here)
-        std::string derr;
-        BspNodeCostDevice *d = nullptr;
-        const int rc = BspNodeCostDeviceCreate(o ? o->device : 0, asked, &d, &derr);
-        dev.reset(d);
-        if (rc != HPRT_OK) return SetError(rc, derr);
-        bspcost::Scalars sc{};
-        sc.maxEdges = asked[0]; sc.maxFaces = asked[1]; sc.maxFaceEdges = asked[2];
-        bspcost::Capacities(sc, cap);
-        return HPRT_OK;
-    }, [&](const BspNodeCostRequest &rq, std::string *e) -> int { return BspNodeCostOnDevice(dev.get(), cap, rq, &st.rc, e); },
-    [=](uint32_t node, const BspNodeCostRequest &rq) {
-        const HprtDebugBspSweepNode nd{rq.mesh, rq.nEdges, rq.dirs, rq.M, rq.sweep, rq.nDirs, &rq.sc, rq.cands, rq.n, rq.costs, rq.costsFixed, rq.level};
-        hook->sink(hook->user, node, &nd);
-    });
-    if (rc != HPRT_OK) return rc;
+    BspNodeHookState hs;                                 // (the device is freed when the build ends or fails)
+    if (const int rc = hs.Install(hook, &p)) return rc;
     const std::string err = BuildBspNodeTree(n, lo, hi, tri9, isTri, p, &t->tree);
-    return FinishBuild(hook, st, err, "node-based BSP tree", BspPaperTodoMax(fastKd), t, out);
+    return FinishBuild(hook, hs.st, err, "node-based BSP tree", BspPaperTodoMax(fastKd), t, out);
 }
 template <typename Handle>
 int BuildBspNodeFromModel(const char *fn, const HprtModel *m, const HprtBspNodeParams *params, Handle **out, const BspNodeHook *hook = nullptr) {
@@ -659,6 +673,49 @@ int BuildBspPaperInst(const char *fn, const HprtModel *m, const Params *params, 
                              for (int a = 0; a < 3 && n; ++a) { b->bounds[a] = lo[a]; b->bounds[3 + a] = hi[a]; }
                          },
                          out);
+}
+// hprt_bspnodeinst_build / hprt_bspnodeinst_build_device: the two-level form of the nine node-based trees.  Every tree is
+// BuildBspNodeTree over RbspPrimTriangles' view of its primitives, from a fresh std::mt19937(seed) (which is what a BuildBspNodeTree
+// call starts).  What the reference's builds call on a primitive is WorldBound, getBounds(d) and — through the choosers — Normal
+// (bspNodeBased.cpp:34,124, bspNodeBasedFastKd.cpp:38,206, randomNormals.h:22, clustering.h:63); getSurfaceArea is reached by the
+// debugging dump of genericBSP.h:107-130 alone.  On the top level an instance is a TransformedPrimitive (core/primitive.h:144-182):
+// Normal() is (0, 0, 0) and getBounds is Primitive's over the 8 corners of its WorldBound — isTri = 0, as the builder already
+// treats a sphere.  One hook (hook != NULL: the device-assisted build) serves every tree through one device session.
+int BuildBspNodeInst(const char *fn, const HprtModel *m, const HprtBspNodeParams *params, HprtBspPaperInst **out, const BspNodeHook *hook = nullptr) {
+    if (out) *out = nullptr;
+    if (!m || !out) return SetError(HPRT_E_INVALID, std::string(fn) + ": null argument");
+    const SceneModel &sc = m->sc;
+    if (sc.instances.empty())
+        return SetError(HPRT_E_UNSUPPORTED, std::string(fn) + ": the model has no object instances; build its tree with hprt_bspnode_build / hprt_bspnodekd_build");
+    BspNodeParams p = sc.opt.bspnode;
+    if (!params && !BspNodeAccelerator(sc.opt.accelerator, &p.chooser, &p.form))
+        return SetError(HPRT_E_INVALID, std::string(fn) + ": the scene's Accelerator \"" + sc.opt.accelerator + "\" is no node-based BSP tree; pass params");
+    ApplyBspNodeParams(params, &p);
+    const std::string refused = BspNodeRefuseParams(p);      // before any primitive is looked at, and before a device is opened
+    if (!refused.empty()) return SetError(HPRT_E_UNSUPPORTED, refused);
+    const bool fastKd = p.form == BSPNODE_FASTKD;
+    std::unique_ptr<HprtBspPaperInst> t(new HprtBspPaperInst());
+    t->kdAware = fastKd;
+    t->top.kdAware = fastKd;
+    BspNodeHookState hs;                                 // (the device is freed when the build ends or fails)
+    if (const int rc = hs.Install(hook, &p)) return rc;
+    std::vector<float> tri9;
+    std::vector<uint8_t> isTri;
+    const int rc = BuildTwoLevel(sc, std::move(t),
+                                 [&](int object, size_t n, const float *lo, const float *hi, BspPaperTree *b) {      // maxDepth -1 resolves per tree, from its n
+                                     if (n > (fastKd ? 0x0fffffffull : 0x3fffffffull)) return std::string("more primitives than a node's flags can count");
+                                     RbspPrimTriangles(sc, object, n, &tri9, &isTri);
+                                     return BuildBspNodeTree(n, lo, hi, tri9.data(), isTri.data(), p, b);
+                                 },
+                                 [&](size_t n, const float *lo, const float *hi, BspPaperTree *b) {
+                                     b->nPrims = (uint32_t)n; b->kdAware = fastKd;
+                                     for (int a = 0; a < 3 && n; ++a) { b->bounds[a] = lo[a]; b->bounds[3 + a] = hi[a]; }
+                                 },
+                                 out);
+    if (hook && hook->stats)
+        *hook->stats = HprtBuildDeviceStats{hs.st.bs.nodesDevice, hs.st.bs.candidatesDevice, hs.st.bs.candidatesRecosted, hs.st.bs.nodesHost, hs.st.bs.secondsDevice};
+    if (hs.st.rc != HPRT_OK) return SetError(hs.st.rc, g_lastError);      // the device's failure keeps its code under BuildTwoLevel's prefix
+    return rc;
 }
 // info[0..3] of one tree of a handle: an object without a tree has no leaves and no depth
 template <typename Tree>
@@ -1484,6 +1541,16 @@ int hprt_bspnodekd_build_from_triangles_device(size_t n, const float *p9, const 
                                                HprtBuildDeviceStats *stats, HprtBspPaperKd **out) try {
     BspNodeHook h; h.device = true; h.opts = opts; h.stats = stats;
     return BuildBspNodeFromTriangles("hprt_bspnodekd_build_from_triangles_device", n, p9, params, out, &h);
+} catch (...) { return hprt::HandleException(); }
+// ---- two-level node-based BSP trees (the nine names over object instances, core/api.cpp:1794-1819; BuildBspNodeInst above): the
+// handle is HprtBspPaperInst, kd-aware for the fastkd form, and hprt_bsppaperinst_* / hprt_scene_attach_bsppaperinst serve it ----
+int hprt_bspnodeinst_build(const HprtModel *m, const HprtBspNodeParams *params, HprtBspPaperInst **out) try {
+    return BuildBspNodeInst("hprt_bspnodeinst_build", m, params, out);
+} catch (...) { return hprt::HandleException(); }
+int hprt_bspnodeinst_build_device(const HprtModel *m, const HprtBspNodeParams *params, const HprtBspBuildDeviceOpts *opts, HprtBuildDeviceStats *stats,
+                                  HprtBspPaperInst **out) try {
+    BspNodeHook h; h.device = true; h.opts = opts; h.stats = stats;
+    return BuildBspNodeInst("hprt_bspnodeinst_build_device", m, params, out, &h);
 } catch (...) { return hprt::HandleException(); }
 // Diagnostics hooks of the node-based candidate costing (not part of include/hprt.h; tests/bspnode_cost_nodes.py).
 // hprt_debug_bspnode_root_nodes hands out the first max_nodes nodes a build costs, in build order: mesh, the node's directions, the

@@ -35,9 +35,10 @@ struct HprtRbspInst : HprtTwoLevel<hprt::RbspTree> {
 struct HprtBspPaper { hprt::BspPaperTree tree; };
 struct HprtBspPaperKd { hprt::BspPaperTree tree; };     // built with BspPaperParams::kdAware
 // Two-level general BSP trees (Accelerator "bsppaper" / "bsppaperkd"): one handle type for both cost models and node layouts; every
-// tree is built with the same parameters, so all carry BSPNode's flags or all BSPKdNode's.
+// tree is built with the same parameters, so all carry BSPNode's flags or all BSPKdNode's.  The two-level node-based trees
+// (hprt_bspnodeinst_build) are structurally these and use this handle: kd-aware for the fastkd form.
 struct HprtBspPaperInst : HprtTwoLevel<hprt::BspPaperTree> {
-    bool kdAware = false;                     // built by hprt_bsppaperkdinst_build: BSPKdNode's flags, walked with the kd form at kd nodes
+    bool kdAware = false;                     // built by hprt_bsppaperkdinst_build or as a fastkd tree: BSPKdNode's flags, walked with the kd form at kd nodes
 };
 
 namespace hprt {
